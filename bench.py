@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the headline benchmark of the MI355X metric-accumulation path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,9 +18,18 @@ timed region; nothing is skipped inside it.
 
 Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel (kta_metrics_scan):
 achieved = 20 algorithmic bytes/record x records per launch / mean kernel duration measured with
-HIP events on the library's compute stream during the timed steps.  `cpu_baseline` is the C oracle
-(oracle/kta_oracle.c, 1 thread — the reference is single threaded) on a bounded sample of the same
-records; `alive_pass` reports the --count-alive-keys pass (config "c3" shape) the same way.
+HIP events on the library's compute stream during the timed steps.
+
+A plain run does only what that line needs: set up, pre-roll + warm up, time --steps steps, print.
+`--full` adds the sub-benchmarks of a single-GPU c4 run, each in runs of its own after the timed steps:
+`cpu_baseline` is the C oracle (oracle/kta_oracle.c, 1 thread — the reference is single threaded) on a
+bounded sample of the same records; `alive_pass` reports the --count-alive-keys pass (config "c3" shape)
+the same way; then the Kafka decode and the PCIe-inclusive legs (the --no-* options leave any of them out).
+
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step (kta_finish,
+or kta_exchange_result when the exchange runs), as float64 .npy files: DIR/counters.npy, the [P, 7]
+per-partition counters, and DIR/result.npy, the KtaResult fields in declaration order.  The synthetic
+inputs are seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -88,6 +97,14 @@ def _alive_checked(got, preset, distinct, n_upto):
     if want is not None and int(got) != int(want):
         raise AssertionError(f"alive keys of {key}: the GPU says {int(got)}, the oracle {int(want)}")
     return {"alive_keys": int(got), "alive_keys_checked": want is not None}
+
+
+def dump_outputs(directory, res, counters):
+    """--dump-outputs: the (KtaResult, counters[P, 7]) a caller of the timed path receives, as float64 arrays."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "counters.npy"), counters.astype(np.float64))
+    np.save(os.path.join(directory, "result.npy"), np.array([getattr(res, f) for f, _ in res._fields_], dtype=np.float64))
 
 
 def cpu_baseline_metrics(h, batch, n_sample, P, min_seconds=10.0):
@@ -749,7 +766,7 @@ def raw_log_e2e_report(kta, device, n_records=4_000_000, passes=4):
     return out
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -769,6 +786,11 @@ def main():
                          "1/N of them per rank (config 4 as stated: 1 B records over 8 GPUs)")
     ap.add_argument("--part-mode", choices=["random", "runs"], default="random",
                     help="partition interleaving of the synthetic topic (random = worst case)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the sub-benchmarks (1 GPU, c4): CPU baseline, alive-key passes, Kafka decode, PCIe-inclusive "
+                         "legs; without it the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/counters.npy and DIR/result.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alive", action="store_true", help="skip the --count-alive-keys sub-benchmark")
     ap.add_argument("--alive-records", type=int, default=15 << 24,
@@ -781,7 +803,16 @@ def main():
     ap.add_argument("--no-hostfed", action="store_true", help="skip the PCIe-inclusive legs (host_fed, raw_log_e2e)")
     ap.add_argument("--decode-records", type=int, default=4_000_000)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    args = ap.parse_args()
+    return ap
+
+
+def runs_full(args, world):
+    """Whether the sub-benchmarks run: only with --full, and only on a single-GPU c4 run (they are c4 legs on one GPU)."""
+    return bool(args.full) and world == 1 and args.config == "c4"
+
+
+def main():
+    args = build_parser().parse_args()
 
     # stdout carries exactly ONE line (the JSON, rank 0): native libraries (RCCL prints a version banner
     # on stdout when the first communicator is created) are pointed at stderr at the fd level.
@@ -829,6 +860,7 @@ def main():
 
     P = 256
     c5 = args.config == "c5"
+    full = runs_full(args, world)
     n = args.records_per_gpu
     if c5:
         n = min(n, 15 << 24)                               # 16-byte keys: a batch's u32 key offsets address < 4 GiB
@@ -898,6 +930,8 @@ def main():
     elapsed = time.perf_counter() - t0
     avg_ms, cnt = h.kernel_time_stats()
     h.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *(h.exchange_result() if exchange else h.finish()))
 
     if exchange:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -964,13 +998,13 @@ def main():
                                                "achieved": algo / (alive_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                                "frac": algo / (alive_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                                "bytes_per_launch": algo, "traffic": None}}
-        if world == 1 and not args.no_cpu_baseline and not c5:
+        if full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_metrics(h, batch, min(n, 1 << 26), P, args.cpu_seconds)
             line["cpu_baseline"]["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
     h.device_batch_free(batch)
     h.close()
-    if rank == 0:
-        if world == 1 and not args.no_alive and not c5:
+    if rank == 0 and full:
+        if not args.no_alive:
             line["alive_pass"], line["both_handlers"] = alive_pass_report(kta, local_rank, max(3, args.steps // 5), 2,
                                                                           args.alive_records, args.cpu_seconds,
                                                                           extras=not args.no_alive_extras)
@@ -978,14 +1012,15 @@ def main():
                                                                                        extras=not args.no_alive_extras)
             if not args.no_alive_extras:
                 line["alive_pass_hot_key"] = alive_hot_key_report(kta, local_rank, 1 << 26)
-        if world == 1 and not args.no_decode and not c5:
+        if not args.no_decode:
             line["kafka_decode"] = kafka_decode_report(kta, local_rank, max(3, args.steps // 5), 2,
                                                        args.decode_records, args.cpu_seconds)
-        if world == 1 and not args.no_hostfed and not c5:
+        if not args.no_hostfed:
             # PCIe-inclusive legs (the link is the bound: never `value`)
             line["boundary_per_message"] = boundary_per_message_report(kta, local_rank)
             line["host_fed"] = host_fed_report(kta, local_rank)
             line["raw_log_e2e"] = raw_log_e2e_report(kta, local_rank)
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if exchange:

@@ -100,7 +100,7 @@ pos = np.repeat(src, kl) + (np.arange(int(kl.sum())) - np.repeat(off, kl))
 kb[:int(kl.sum())] = cols["key_bytes"][pos]
 shard = {"partition": cols["partition"][idx], "key_len": cols["key_len"][idx], "val_len": cols["val_len"][idx],
          "ts_ms": cols["ts_ms"][idx], "key_off": off.astype(np.uint32), "key_bytes": kb[:int(kl.sum())], "seq": seq[idx]}
-h = kta.HipMetricHandler(P, count_alive_keys=True, now=NOW, alive_table=True)
+h = kta.HipMetricHandler(P, count_alive_keys=True, now=NOW, alive_table=True, device=rank)   # RCCL: one rank per device
 if nranks > 1:
     if rank == 0:
         uid = kta.HipMetricHandler.comm_unique_id()
@@ -143,7 +143,12 @@ h.device_batch_free(b); h.comm_destroy(); h.close(); print("OK", rank, sent, rec
 def test_native_exchange_over_rccl(tmp_path, nranks):
     """kta_comm_create / kta_exchange: partition-sharded ranks with global sequence numbers, hash-range
     exchange of the alive entries + grouped SUM / MAX all-reduce of the snapshot vector, every rank ends with
-    the unsharded oracle's result.  Two ranks share the one reachable GPU (RCCL permitting)."""
+    the unsharded oracle's result.  Rank r on device r: real RCCL refuses two ranks on one device, so the two-rank
+    case needs two GPUs (on one, the RCCL test double runs the multi-rank paths below)."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < nranks:
+        pytest.skip(f"needs {nranks} GPUs (real RCCL refuses two ranks on one device), found {found}")
     script = tmp_path / "w.py"
     script.write_text(_NATIVE_WORKER)
     idfile = str(tmp_path / "rccl_id")
@@ -158,8 +163,6 @@ def test_native_exchange_over_rccl(tmp_path, nranks):
             for q in procs:
                 q.kill()
             raise
-    if nranks > 1 and any(rc == 3 for _, _, rc in outs):
-        pytest.skip("RCCL refused two ranks on one GPU: " + " | ".join(o[-300:] for o, _, _ in outs))
     for out, err, rc in outs:
         assert rc == 0 and "OK" in out, (out[-2000:], err[-3000:])
 
@@ -250,14 +253,18 @@ def test_native_exchange_logic_with_rccl_test_double(tmp_path, nranks, P, alive)
 
 
 # ---- the driver's own launch line: one bench.py process per rank ------------------------------------------------
-def _run_bench_ranks(tmp_path, nproc, port, extra, timeout=900):
+def _run_bench_ranks(tmp_path, nproc, port, extra, timeout=900, share_device=True):
     """`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` as the driver launches it,
-    on the one reachable GPU: every rank process on device 0 (KTA_BENCH_SHARE_DEVICE=1), the library's RCCL replaced by the
-    process-capable test double (tests/mock_rccl.cpp: shared-memory rendezvous keyed by the unique id).  Returns rank 0's
-    JSON line."""
+    on the one reachable GPU: every rank process on device 0 (KTA_BENCH_SHARE_DEVICE=1; share_device=False: rank r on
+    device r), the library's RCCL replaced by the process-capable test double (tests/mock_rccl.cpp: shared-memory
+    rendezvous keyed by the unique id).  Returns rank 0's JSON line."""
     lib = _build_mock_rccl(tmp_path)
-    env = dict(os.environ, KTA_RCCL_LIBRARY=str(lib), KTA_RCCL_ONLY_ENV="1", KTA_BENCH_SHARE_DEVICE="1",
-               HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
+    env = dict(os.environ, KTA_RCCL_LIBRARY=str(lib), KTA_RCCL_ONLY_ENV="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
+               OMP_NUM_THREADS="1")
+    if share_device:
+        env["KTA_BENCH_SHARE_DEVICE"] = "1"
+    else:
+        env.pop("KTA_BENCH_SHARE_DEVICE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline", "--no-alive",
@@ -304,10 +311,30 @@ def test_bench_two_rank_processes_config_5(tmp_path):
     o.close()
 
 
-def test_bench_eight_rank_processes_config_4(tmp_path):
-    """The target machine's eight ranks as eight bench.py processes (without -c: eight 32 GiB tables do not fit one GPU):
-    config 4's sharding, 32 partitions per rank, one grouped all-reduce per step."""
+def test_bench_three_rank_processes_config_4(tmp_path):
+    """bench.py's launch line with more than two rank processes on the one GPU: a three-way gloo rendezvous, the test
+    double's shared-memory exchange among three processes, and config 4's 256 partitions sharded p % 3 (86, 85, 85 per
+    rank: uneven).  Three ranks, the launcher and the pytest process stay within the six processes a test GPU may have
+    open at once; eight rank processes need eight GPUs (test_bench_eight_rank_processes_config_4)."""
     n = 1 << 21
-    line = _run_bench_ranks(tmp_path, 8, 29534, ["--records-per-gpu", str(n)], timeout=1200)
+    line = _run_bench_ranks(tmp_path, 3, 29535, ["--records-per-gpu", str(n)])
+    assert line["n_gpus"] == 3 and line["config"]["total_records_per_step"] == 3 * n
+    assert line["config"]["parallelism"] == "partition-sharded x3" and line["config"]["shared_device"] is True
+    assert abs(line["value"] - 3 * n * 3 / (line["ms_per_step"] * 3e-3)) < 1e-3 * line["value"]
+    assert line["roofline"]["launches"] == 3
+
+
+def test_bench_eight_rank_processes_config_4(tmp_path):
+    """The target machine's eight ranks as eight bench.py processes, one per GPU (without -c: eight 32 GiB tables):
+    config 4's sharding, 32 partitions per rank, one grouped all-reduce per step.  On one GPU the launch line runs with
+    three rank processes (above) and the eight communicator ranks as threads
+    (test_native_exchange_logic_with_rccl_test_double[8-256-False])."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < 8:
+        pytest.skip(f"needs 8 GPUs (one bench.py rank process per device), found {found}")
+    n = 1 << 21
+    line = _run_bench_ranks(tmp_path, 8, 29534, ["--records-per-gpu", str(n)], timeout=1200, share_device=False)
     assert line["n_gpus"] == 8 and line["config"]["total_records_per_step"] == 8 * n
     assert line["config"]["parallelism"] == "partition-sharded x8"
+    assert line["config"]["shared_device"] is False
