@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 6   /* 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -107,7 +107,9 @@ typedef struct kta_config {
 
 /* Additive analytics (NOT in the reference, never printed by the reference report): log2
  * histograms of key and value sizes and per-partition timestamp / message-size extrema,
- * accumulated by the same scan kernel in extra LDS arrays.  Opt-in: costs LDS, not bandwidth. */
+ * accumulated by the same scan kernel in extra LDS arrays.  Opt-in: costs LDS, not bandwidth.
+ * The scan keeps [P][4] extrema in LDS, so P is bounded (kta_analytics_max_partitions); with -c the
+ * batch takes two passes (scan, then the alive-key pass): the fused pass has no LDS room for them. */
 #define KTA_FLAG_ANALYTICS 1u
 /* The staging batches of kta_batch_acquire carry a `seq` column (with count_alive_keys): the producer writes
  * every record's GLOBAL consumption index, kta_batch_submit's base_seq is ignored.  For a rank of a
@@ -275,7 +277,13 @@ int kta_finish_device(kta_ctx *ctx);
  *                       synchronisation of the step is for the sizes of the sends.  A rank that fails locally
  *                       aborts its communicator (ncclCommAbort), so that its peers get an error instead of
  *                       waiting in their collectives; the context's communicator is unusable afterwards.
+ *                       With KTA_FLAG_ANALYTICS the same grouped launch also reduces the analytics snapshot:
+ *                       all-reduce SUM (u64) over its 2 x 34 histogram words and all-reduce MAX (i64) over its
+ *                       4 * P extrema words (neutral element INT64_MIN: a partition's owner wins).
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
+ *                       (kta_exchange_analytics: the same for the analytics)
+ * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS bit: the collectives
+ * of a rank with analytics do not match those of a rank without.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
 #define KTA_COMM_ID_BYTES 128
 int kta_comm_unique_id(uint8_t id[KTA_COMM_ID_BYTES]);
@@ -307,6 +315,23 @@ int kta_get_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec
  * partition [~min ts_ms, max ts_ms, ~smallest, largest] (signed MAX) — reducible across GPUs like
  * the counter vector. */
 int kta_analytics_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* The analytics of the SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes of the analytics vector,
+ * decoded like kta_get_analytics: after kta_exchange the whole job's analytics on every rank.  The live accumulator
+ * (kta_get_analytics, kta_analytics_vector) is never reduced, so further batches and a second exchange do not count
+ * anything twice. */
+int kta_exchange_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
+                           uint64_t *part_smallest, uint64_t *part_largest);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_analytics_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side decode of a (possibly all-reduced) analytics vector u64[2*34 + 4*P], conventions as kta_get_analytics. */
+int kta_decode_analytics(const uint64_t *vec, uint32_t n_partitions, kta_analytics *out, int64_t *part_min_ts_sec,
+                         int64_t *part_max_ts_sec, uint64_t *part_smallest, uint64_t *part_largest);
+/* Host-side merge of two analytics vectors (acc <- acc (+) other): SUM over the histograms, signed MAX over
+ * the extrema — exactly the reduction the two collectives of the exchange implement. */
+int kta_merge_analytics(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* The largest P a KTA_FLAG_ANALYTICS context may have: the analytics scan's LDS plan (7 u64 per partition slot plus
+ * the histograms) must fit one workgroup's 160 KiB of LDS on gfx950.  kta_create refuses more. */
+int kta_analytics_max_partitions(void);
 
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
@@ -352,6 +377,14 @@ int kta_render_report(const char *topic, uint64_t duration_secs, const uint64_t 
                       uint32_t n_partitions, int count_alive_keys, int64_t now_sec, uint32_t now_ns,
                       const int64_t *start_offsets, const int64_t *end_offsets, char *out,
                       size_t out_cap, size_t *out_len);
+
+/* The opt-in analytics section that kta-analyzer prints after the reference report (--librdkafka
+ * kta.analytics=1), from an analytics vector: a title line saying that it is not part of the reference report,
+ * a size table (Bytes | Keys | Keys % | Values | Vals %: rows None and 0 always, then each log2 bucket whose key
+ * or value count is non-zero; percentages of all records, %.2f), a per-partition table (P | Earliest | Latest |
+ * Smallest | Largest: times in seconds as the report's Earliest Message, `-` for a partition without records /
+ * without non-tombstones) and a closing `=` rule.  Output buffer conventions as kta_render_report. */
+int kta_render_analytics(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

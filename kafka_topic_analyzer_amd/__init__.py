@@ -24,7 +24,8 @@ from . import _native as N
 from ._native import KtaBatch, KtaConfig, KtaResult, KtaSynthSpec  # noqa: F401
 
 __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics", "Message", "KtaError",
-           "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats"]
+           "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats",
+           "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -334,16 +335,25 @@ class HipMetricHandler:
         return p.value, n.value
 
     def analytics(self) -> dict:
-        """Additive analytics (not in the reference): size histograms + per-partition extrema."""
+        """Additive analytics (not in the reference): size histograms + per-partition extrema of this
+        context's live accumulator."""
+        return self._analytics(self._lib.kta_get_analytics)
+
+    def exchange_analytics(self) -> dict:
+        """As analytics(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._analytics(self._lib.kta_exchange_analytics)
+
+    def _analytics(self, fn) -> dict:
         a = N.KtaAnalytics()
-        P = self.n_partitions
-        mn, mx = np.zeros(P, np.int64), np.zeros(P, np.int64)
-        sm, lg = np.zeros(P, np.uint64), np.zeros(P, np.uint64)
-        self._check(self._lib.kta_get_analytics(self._ctx, C.byref(a), _np_ptr(mn), _np_ptr(mx), _np_ptr(sm),
-                                                _np_ptr(lg)))
-        return {"key_size_hist": np.array(a.key_size_hist[:], dtype=np.uint64),
-                "value_size_hist": np.array(a.value_size_hist[:], dtype=np.uint64),
-                "part_min_ts_sec": mn, "part_max_ts_sec": mx, "part_smallest": sm, "part_largest": lg}
+        out = _analytics_arrays(self.n_partitions)
+        self._check(fn(self._ctx, C.byref(a), *[_np_ptr(out[k]) for k in _PART_KEYS]))
+        return _analytics_dict(a, out)
+
+    def analytics_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the analytics snapshot (for collectives: allreduce_analytics_vector)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.kta_analytics_result_vector(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
@@ -488,6 +498,69 @@ class LogCompactionInMemoryMetrics:
 
     def sum_all_alive(self) -> int:  # metric.rs:282-284
         return int(self._res.alive_keys)
+
+
+# ---------------------------------------------------------------------- analytics vectors (host side)
+_PART_KEYS = ("part_min_ts_sec", "part_max_ts_sec", "part_smallest", "part_largest")
+
+
+def _analytics_arrays(P: int) -> dict:
+    return {"part_min_ts_sec": np.zeros(P, np.int64), "part_max_ts_sec": np.zeros(P, np.int64),
+            "part_smallest": np.zeros(P, np.uint64), "part_largest": np.zeros(P, np.uint64)}
+
+
+def _analytics_dict(a: "N.KtaAnalytics", parts: dict) -> dict:
+    return {"key_size_hist": np.array(a.key_size_hist[:], dtype=np.uint64),
+            "value_size_hist": np.array(a.value_size_hist[:], dtype=np.uint64), **parts}
+
+
+def _analytics_vec(vec, P: int) -> np.ndarray:
+    v = np.ascontiguousarray(vec).view(np.uint64) if np.asarray(vec).dtype == np.int64 else np.ascontiguousarray(vec, np.uint64)
+    if v.size != N.KTA_ANALYTICS_HIST + 4 * P:
+        raise ValueError(f"an analytics vector of {P} partitions has {N.KTA_ANALYTICS_HIST + 4 * P} words, not {v.size}")
+    return v
+
+
+def decode_analytics(vec, n_partitions: int) -> dict:
+    """kta_decode_analytics: an analytics vector u64[2*34 + 4*P] -> the dict HipMetricHandler.analytics() returns."""
+    v = _analytics_vec(vec, n_partitions)
+    a = N.KtaAnalytics()
+    out = _analytics_arrays(n_partitions)
+    rc = N.load().kta_decode_analytics(_np_ptr(v), n_partitions, C.byref(a), *[_np_ptr(out[k]) for k in _PART_KEYS])
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_decode_analytics")
+    return _analytics_dict(a, out)
+
+
+def merge_analytics(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_analytics, in place on `acc` (uint64 or int64): SUM over the histograms, signed MAX over the extrema."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    a = _analytics_vec(acc, n_partitions)
+    rc = N.load().kta_merge_analytics(_np_ptr(a), _np_ptr(_analytics_vec(other, n_partitions)), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_analytics")
+    return acc
+
+
+def render_analytics(vec, n_partitions: int) -> str:
+    """kta_render_analytics: the section kta-analyzer prints after the report with --librdkafka kta.analytics=1."""
+    v = _analytics_vec(vec, n_partitions)
+    lib = N.load()
+    n = C.c_size_t()
+    rc = lib.kta_render_analytics(_np_ptr(v), n_partitions, None, 0, C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_analytics")
+    buf = C.create_string_buffer(n.value + 1)
+    rc = lib.kta_render_analytics(_np_ptr(v), n_partitions, buf, len(buf), C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_analytics")
+    return buf.value.decode()
+
+
+def analytics_max_partitions() -> int:
+    """The largest P a context with analytics may have (the analytics scan's LDS plan on gfx950)."""
+    return int(N.load().kta_analytics_max_partitions())
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

@@ -49,6 +49,7 @@ KTA_FLAG_ANALYTICS = 1
 KTA_FLAG_SEQ_COLUMN = 2
 KTA_FLAG_ALIVE_TABLE = 4
 KTA_HIST_BUCKETS = 34
+KTA_ANALYTICS_HIST = 2 * KTA_HIST_BUCKETS   # analytics vector: u64[2*34 + 4*P]
 
 
 class KtaAnalytics(C.Structure):
@@ -135,6 +136,13 @@ SIGNATURES = {
     "kta_merge_vectors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "kta_get_analytics": (C.c_int, [_P, C.POINTER(KtaAnalytics), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kta_analytics_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_exchange_analytics": (C.c_int, [_P, C.POINTER(KtaAnalytics), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kta_analytics_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_decode_analytics": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(KtaAnalytics), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "kta_merge_analytics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_analytics_max_partitions": (C.c_int, []),
+    "kta_render_analytics": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),
     "kta_alive_table": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "kta_alive_export_entries": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -187,7 +195,7 @@ SIGNATURES = {
 _lib = None
 
 
-KTA_ABI_VERSION = 6  # include/kta_hip.h
+KTA_ABI_VERSION = 7  # include/kta_hip.h
 
 
 def load() -> C.CDLL:

@@ -17,12 +17,15 @@
 //                                        v2; uncompressed, gzip, Snappy, LZ4, zstd): file k is partition k; decoded ON THE GPU
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
-// kta.batch=N, kta.write_dump=<path>, kta.per_message=1), so no flag is added or renamed.
+// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1), so no flag is added or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
 // visible devices), and replaces "the report reads the handlers" by ONE exchange step (kta_exchange: RCCL).
 // kta.per_message=1 drives the handler exactly like the reference's loop (kafka.rs:107-109): one
 // MetricHandler::handle_message call per record instead of filling columns.
+// kta.analytics=1 (every source, kta.gpus=N included) accumulates the additive analytics as well (KTA_FLAG_ANALYTICS:
+// key / value size histograms, per-partition timestamp and size extrema; no reference counterpart) and prints them
+// in a section of their own AFTER the reference report, which stays byte for byte what it is without the knob.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -163,6 +166,7 @@ struct ShardedJob {
     uint32_t P = 0;
     kta_synth_spec spec{};
     bool oversubscribe = false;                        // kta.oversubscribe=1: several ranks may share a device (test doubles of RCCL)
+    bool analytics = false;                            // kta.analytics=1: every rank's context, exchanged with the counters
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -175,7 +179,8 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
 {
     try {
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
-        const uint32_t flags = job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u;
+        const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
+                               (job.analytics ? KTA_FLAG_ANALYTICS : 0u);
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags);
         kta_ctx *ctx = h->ctx();
@@ -298,6 +303,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
     try {
         std::string text = kta::render_report(job.topic, duration_secs, metrics, h0->log_compaction(), partitions,
                                               job.start_offsets, job.end_offsets);
+        if (job.analytics) text += kta::render_analytics(*h0->analytics());   // the exchanged snapshot, printed once
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -383,6 +389,12 @@ int main(int argc, char **argv)
         }
     }
     const uint32_t P = hdr.n_partitions;
+    const bool analytics = cfg.count("kta.analytics") && cfg["kta.analytics"] == "1";
+    if (analytics && P > (uint32_t)kta_analytics_max_partitions()) {   // before any context, so before any kernel
+        fprintf(stderr, "kta.analytics=1: the topic has %u partitions, the analytics scan admits at most %d "
+                        "(its per-partition extrema live in LDS)\n", P, kta_analytics_max_partitions());
+        return 2;
+    }
 
     // librdkafka options are forwarded as in the reference (kafka.rs:38-42); the one this build can
     // honour for raw segments is check.crcs (default false): verify every batch's CRC-32C on the GPU
@@ -453,6 +465,7 @@ int main(int argc, char **argv)
         job.device = device;
         job.nranks = gpus;
         job.oversubscribe = oversubscribe;
+        job.analytics = analytics;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -468,7 +481,7 @@ int main(int argc, char **argv)
     // -c means a 32 GiB table)
     kta::HipMetricHandler *handler = nullptr;
     try {
-        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0);
+        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0, analytics ? KTA_FLAG_ANALYTICS : 0u);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
         return 2;
@@ -640,6 +653,7 @@ int main(int argc, char **argv)
     try {
         std::string text = kta::render_report(args.topic, duration_secs, metrics, handler->log_compaction(),
                                               partitions, start_offsets, end_offsets);
+        if (analytics) text += kta::render_analytics(*handler->analytics());
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -71,7 +71,7 @@ uint64_t MessageMetrics::smallest_message() const
 
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
                                    uint64_t key_bytes_capacity, uint32_t flags)
-    : P_(n_partitions), alive_(count_alive_keys)
+    : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -122,6 +122,7 @@ void HipMetricHandler::finish(bool tolerate_undelivered)
     undelivered_ = r.bad_partition_records;
     metrics_ = MessageMetrics(r, std::move(counters), now_);
     lc_ = LogCompactionInMemoryMetrics(r);
+    read_analytics();
 }
 
 void HipMetricHandler::comm_create(int nranks, int rank, const uint8_t *unique_id)
@@ -140,6 +141,27 @@ void HipMetricHandler::exchange(bool tolerate_undelivered)
     undelivered_ = r.bad_partition_records;
     metrics_ = MessageMetrics(r, std::move(counters), now_);
     lc_ = LogCompactionInMemoryMetrics(r);
+    read_analytics();
+}
+
+void HipMetricHandler::read_analytics()
+{
+    if (!analytics_on_) return;
+    Analytics &a = analytics_;
+    a.min_ts_sec.assign((size_t)P_, 0);
+    a.max_ts_sec.assign((size_t)P_, 0);
+    a.smallest.assign((size_t)P_, 0);
+    a.largest.assign((size_t)P_, 0);
+    check(kta_exchange_analytics(ctx_, &a.hist, a.min_ts_sec.data(), a.max_ts_sec.data(), a.smallest.data(),
+                                 a.largest.data()),
+          "kta_exchange_analytics");
+}
+
+uint64_t Analytics::records() const
+{
+    uint64_t n = 0;
+    for (int b = 0; b < KTA_HIST_BUCKETS; b++) n += hist.key_size_hist[b];
+    return n;
 }
 
 }  // namespace kta

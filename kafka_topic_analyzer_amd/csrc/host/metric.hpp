@@ -79,6 +79,14 @@ private:
     DateTimeUtc earliest_, latest_;
 };
 
+// The additive analytics (KTA_FLAG_ANALYTICS; no reference counterpart), decoded as kta_get_analytics does.
+struct Analytics {
+    kta_analytics hist{};
+    std::vector<int64_t> min_ts_sec, max_ts_sec;      // INT64_MAX / INT64_MIN: no record in the partition
+    std::vector<uint64_t> smallest, largest;          // UINT64_MAX / 0: no non-tombstone in the partition
+    uint64_t records() const;                         // every record lands in exactly one key-size bucket
+};
+
 class LogCompactionInMemoryMetrics {  // metric.rs:262-285
 public:
     LogCompactionInMemoryMetrics() {}
@@ -110,6 +118,9 @@ public:
     void comm_create(int nranks, int rank, const uint8_t *unique_id);
     void exchange(bool tolerate_undelivered = false);
     uint64_t undelivered_records() const { return undelivered_; }
+    // With KTA_FLAG_ANALYTICS: the analytics of the snapshot finish() / exchange() took (after exchange(), the whole
+    // job's); nullptr without the flag.
+    const Analytics *analytics() const { return analytics_on_ ? &analytics_ : nullptr; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -117,6 +128,7 @@ public:
 
 private:
     void check(int rc, const char *what);
+    void read_analytics();
     kta_ctx *ctx_ = nullptr;
     int32_t P_;
     bool alive_;
@@ -124,6 +136,8 @@ private:
     MessageMetrics metrics_;
     LogCompactionInMemoryMetrics lc_;
     uint64_t undelivered_ = 0;
+    bool analytics_on_ = false;
+    Analytics analytics_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -134,5 +148,7 @@ std::string format_f32_4(float x);
 std::string render_report(const std::string &topic, uint64_t duration_secs, const MessageMetrics &m,
                           const LogCompactionInMemoryMetrics *lc, const std::vector<int32_t> &partitions,
                           const std::vector<int64_t> &start_offsets, const std::vector<int64_t> &end_offsets);
+// the opt-in section kta-analyzer prints after the report with kta.analytics=1 (kta_render_analytics)
+std::string render_analytics(const Analytics &a);
 
 }  // namespace kta

@@ -130,7 +130,69 @@ std::string render_report(const std::string &topic, uint64_t duration_secs, cons
     return o;
 }
 
+// The opt-in analytics section (kta.analytics=1): no reference counterpart, printed after the reference report's
+// closing rule so that the report itself stays byte for byte the reference's.
+std::string render_analytics(const Analytics &a)
+{
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    const uint64_t records = a.records();
+    auto pct = [&](uint64_t count) {
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", records ? (double)count * 100.0 / (double)records : 0.0);
+        return std::string(buf);
+    };
+    std::string o;
+    o += "Size histograms and per-partition extrema (kta.analytics=1; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"Bytes", "Keys", "Keys %", "Values", "Vals %"});
+    for (int b = 0; b < KTA_HIST_BUCKETS; b++) {
+        const uint64_t k = a.hist.key_size_hist[b], v = a.hist.value_size_hist[b];
+        if (b >= 2 && k == 0 && v == 0) continue;   // None and 0 always, a log2 bucket when somebody is in it
+        std::string label;
+        if (b == 0) label = "None";
+        else if (b == 1) label = "0";
+        else if (b == 2) label = "1";
+        else label = u(1ull << (b - 2)) + "-" + u((2ull << (b - 2)) - 1);
+        rows.push_back({label, u(k), pct(k), u(v), pct(v)});
+    }
+    o += pretty_table(rows);
+    o += "\n";
+    rows.clear();
+    rows.push_back({"P", "Earliest", "Latest", "Smallest", "Largest"});
+    for (size_t p = 0; p < a.min_ts_sec.size(); p++) {
+        const bool seen = a.max_ts_sec[p] != INT64_MIN, live = a.largest[p] != 0 || a.smallest[p] != UINT64_MAX;
+        rows.push_back({std::to_string(p), seen ? format_datetime_utc(a.min_ts_sec[p], 0) : "-",
+                        seen ? format_datetime_utc(a.max_ts_sec[p], 0) : "-", live ? u(a.smallest[p]) : "-",
+                        live ? u(a.largest[p]) : "-"});
+    }
+    o += pretty_table(rows);
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_analytics(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap,
+                                    size_t *out_len)
+{
+    if (!vec || !out_len || n_partitions == 0) return KTA_ERR_INVALID;
+    kta::Analytics a;
+    a.min_ts_sec.resize(n_partitions);
+    a.max_ts_sec.resize(n_partitions);
+    a.smallest.resize(n_partitions);
+    a.largest.resize(n_partitions);
+    int rc = kta_decode_analytics(vec, n_partitions, &a.hist, a.min_ts_sec.data(), a.max_ts_sec.data(),
+                                  a.smallest.data(), a.largest.data());
+    if (rc != KTA_OK) return rc;
+    const std::string text = kta::render_analytics(a);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_report(const char *topic, uint64_t duration_secs, const uint64_t *vec,
                                  uint32_t n_partitions, int count_alive_keys, int64_t now_sec, uint32_t now_ns,

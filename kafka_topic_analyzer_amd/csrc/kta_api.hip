@@ -48,6 +48,7 @@ struct kta_ctx {
     bool analytics = false;
     bool stage_seq = false;         // KTA_FLAG_SEQ_COLUMN
     uint64_t *d_avec = nullptr;     // analytics vector u64[2*34 + 4*P] (KTA_FLAG_ANALYTICS)
+    uint64_t *d_avec_out = nullptr; // its snapshot (kta_finish_device), reduced by the exchange like d_vec_out
     uint64_t *d_vec = nullptr;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     uint64_t *d_vec_out = nullptr;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -442,6 +443,10 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     *out = nullptr;
     if (cfg->n_partitions <= 0 || cfg->n_partitions > 4096)
         return fail(nullptr, KTA_ERR_INVALID, "n_partitions must be in [1, 4096]");
+    if ((cfg->flags & KTA_FLAG_ANALYTICS) && cfg->n_partitions > kta_analytics_max_partitions())
+        return fail(nullptr, KTA_ERR_INVALID,
+                    "KTA_FLAG_ANALYTICS admits at most " + std::to_string(kta_analytics_max_partitions()) +
+                        " partitions (the analytics scan keeps 4 extrema per partition in LDS)");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -497,8 +502,10 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->max_rows = (uint32_t)ctx->cu_count * 8u;
     KTA_TRY(hipMalloc((void **)&ctx->d_partials,
                       (size_t)ctx->max_rows * kta::scan_row_len(ctx->P, ctx->analytics) * sizeof(uint64_t)));
-    if (ctx->analytics)
+    if (ctx->analytics) {
         KTA_TRY(hipMalloc((void **)&ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
+        KTA_TRY(hipMalloc((void **)&ctx->d_avec_out, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
+    }
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_TRY(hipMalloc((void **)&ctx->d_table, kta::kAliveSlots * sizeof(uint64_t)));
@@ -536,6 +543,7 @@ void kta_destroy(kta_ctx *ctx)
     if (ctx->d_vec_out) (void)hipFree(ctx->d_vec_out);
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_avec) (void)hipFree(ctx->d_avec);
+    if (ctx->d_avec_out) (void)hipFree(ctx->d_avec_out);
     if (ctx->d_table) (void)hipFree(ctx->d_table);
     if (ctx->d_bitmap) (void)hipFree(ctx->d_bitmap);
     if (ctx->d_written) (void)hipFree(ctx->d_written);
@@ -830,6 +838,9 @@ int kta_finish_device(kta_ctx *ctx)
     const size_t words = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
     KTA_HIP(ctx, hipMemcpyAsync(ctx->d_vec_out, ctx->d_vec, words * sizeof(uint64_t), hipMemcpyDeviceToDevice,
                                 ctx->s_compute));
+    if (ctx->analytics)
+        KTA_HIP(ctx, hipMemcpyAsync(ctx->d_avec_out, ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t),
+                                    hipMemcpyDeviceToDevice, ctx->s_compute));
     if (ctx->alive) {
         uint64_t *dst = ctx->d_vec_out + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
         if (ctx->running_valid)  // exact running count (every update so far ran a counting kernel): no table scan
@@ -937,6 +948,60 @@ int kta_analytics_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
     return KTA_OK;
 }
 
+int kta_decode_analytics(const uint64_t *vec, uint32_t P, kta_analytics *out, int64_t *part_min_ts_sec,
+                         int64_t *part_max_ts_sec, uint64_t *part_smallest, uint64_t *part_largest)
+{
+    if (!vec || !out || P == 0) return KTA_ERR_INVALID;
+    for (int b = 0; b < KTA_HIST_BUCKETS; b++) {
+        out->key_size_hist[b] = vec[b];
+        out->value_size_hist[b] = vec[KTA_HIST_BUCKETS + b];
+    }
+    for (uint32_t p = 0; p < P; p++) {
+        const int64_t *x = reinterpret_cast<const int64_t *>(vec) + kta::kAnalyticsHist + 4 * (size_t)p;
+        const bool seen = x[1] != INT64_MIN;     // max ts never written => no record in this partition
+        const bool live = x[3] != INT64_MIN;     // largest never written => no non-tombstone
+        if (part_min_ts_sec) part_min_ts_sec[p] = seen ? (~x[0]) / 1000 : INT64_MAX;  // metric.rs:210 (monotone)
+        if (part_max_ts_sec) part_max_ts_sec[p] = seen ? x[1] / 1000 : INT64_MIN;
+        if (part_smallest) part_smallest[p] = live ? (uint64_t)~x[2] : UINT64_MAX;
+        if (part_largest) part_largest[p] = live ? (uint64_t)x[3] : 0;
+    }
+    return KTA_OK;
+}
+
+int kta_merge_analytics(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    if (!acc || !other || P == 0) return KTA_ERR_INVALID;
+    for (size_t i = 0; i < kta::kAnalyticsHist; i++) acc[i] += other[i];
+    for (size_t i = kta::kAnalyticsHist; i < kta::analytics_len(P); i++)
+        if ((int64_t)other[i] > (int64_t)acc[i]) acc[i] = other[i];
+    return KTA_OK;
+}
+
+int kta_analytics_max_partitions(void)
+{
+    // the analytics scan's dynamic LDS (plan_scan; replication backs off to 1 first) plus its static reduction
+    // arrays (kta_metrics_scan's s_red) within one workgroup's LDS on gfx950
+    const uint32_t lds_limit = 160u * 1024u, static_lds = (kta::kWG / 64u) * 6u * 8u;
+    uint32_t lo = 0, hi = 4096;
+    while (lo < hi) {   // lds_bytes grows with P: the largest P that fits
+        const uint32_t mid = (lo + hi + 1) / 2;
+        if (kta::plan_scan(mid, 1, 1, 1, 0, true).lds_bytes + static_lds <= lds_limit) lo = mid;
+        else hi = mid - 1;
+    }
+    return (int)lo;
+}
+
+// the analytics vector at `d_vec` (the live accumulator or its snapshot) copied to the host and decoded
+static int read_analytics(kta_ctx *ctx, const uint64_t *d_vec, kta_analytics *out, int64_t *part_min_ts_sec,
+                          int64_t *part_max_ts_sec, uint64_t *part_smallest, uint64_t *part_largest)
+{
+    std::vector<uint64_t> host(kta::analytics_len(ctx->P));
+    KTA_HIP(ctx, hipMemcpyAsync(host.data(), d_vec, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return kta_decode_analytics(host.data(), ctx->P, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+}
+
 int kta_get_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
                       uint64_t *part_smallest, uint64_t *part_largest)
 {
@@ -945,23 +1010,24 @@ int kta_get_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    std::vector<uint64_t> host(kta::analytics_len(ctx->P));
-    KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_avec, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    for (int b = 0; b < KTA_HIST_BUCKETS; b++) {
-        out->key_size_hist[b] = host[b];
-        out->value_size_hist[b] = host[KTA_HIST_BUCKETS + b];
-    }
-    for (uint32_t p = 0; p < ctx->P; p++) {
-        const int64_t *x = reinterpret_cast<const int64_t *>(host.data()) + kta::kAnalyticsHist + 4 * (size_t)p;
-        const bool seen = x[1] != INT64_MIN;     // max ts never written => no record in this partition
-        const bool live = x[3] != INT64_MIN;     // largest never written => no non-tombstone
-        if (part_min_ts_sec) part_min_ts_sec[p] = seen ? (~x[0]) / 1000 : INT64_MAX;  // metric.rs:210 (monotone)
-        if (part_max_ts_sec) part_max_ts_sec[p] = seen ? x[1] / 1000 : INT64_MIN;
-        if (part_smallest) part_smallest[p] = live ? (uint64_t)~x[2] : UINT64_MAX;
-        if (part_largest) part_largest[p] = live ? (uint64_t)x[3] : 0;
-    }
+    return read_analytics(ctx, ctx->d_avec, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+}
+
+int kta_exchange_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
+                           uint64_t *part_smallest, uint64_t *part_largest)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_analytics(ctx, ctx->d_avec_out, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+}
+
+int kta_analytics_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
+    *device_ptr = ctx->d_avec_out;
+    *n_u64 = kta::analytics_len(ctx->P);
     return KTA_OK;
 }
 
@@ -1173,6 +1239,7 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *))
     return &ctx->comm_state;
 }
 uint64_t *kta_internal_vec_out(kta_ctx *ctx) { return ctx->d_vec_out; }
+uint64_t *kta_internal_avec_out(kta_ctx *ctx) { return ctx->d_avec_out; }
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table; }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }

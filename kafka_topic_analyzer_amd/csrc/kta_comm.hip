@@ -9,6 +9,9 @@
 //   counters   ONE grouped RCCL launch on the compute stream: all-reduce SUM (u64) over
 //              vec[0 : P*7 + 4] and all-reduce MAX (i64) over vec[P*7 + 4 : P*7 + 8] of the SNAPSHOT vector
 //              (kta_finish_device), never of the live accumulator.
+//   analytics  (KTA_FLAG_ANALYTICS, no reference counterpart) in the same grouped launch: all-reduce SUM (u64) over
+//              the 2 x 34 histogram words and all-reduce MAX (i64) over the 4 * P extrema words of the analytics
+//              snapshot; an extremum word nobody wrote is INT64_MIN, so a partition's owner rank wins.
 //   alive set  (-c) global and order dependent (src/metric.rs:262-264, 289-304): every rank's table holds
 //              GLOBAL sequence numbers; rank r owns the slots [ceil(r 2^32 / R), ceil((r+1) 2^32 / R)).
 //              Each rank exports the entries it ever wrote, one contiguous list per owner (<= 12 bytes per
@@ -37,6 +40,7 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *));
 bool kta_internal_count_alive(kta_ctx *ctx);
 bool kta_internal_alive_table(kta_ctx *ctx);
 uint64_t *kta_internal_vec_out(kta_ctx *ctx);
+uint64_t *kta_internal_avec_out(kta_ctx *ctx);
 uint32_t kta_internal_partitions(kta_ctx *ctx);
 uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
@@ -395,6 +399,11 @@ static int exchange_collectives(kta_ctx *ctx, CommState *st)
     CN(ctx, R->GroupStart());
     CN(ctx, R->AllReduce(vec, vec, sum_words, ncclUint64, ncclSum, st->comm, s));
     CN(ctx, R->AllReduce(vec + sum_words, vec + sum_words, KTA_NGLOBALS - KTA_NSUM_GLOBALS, ncclInt64, ncclMax, st->comm, s));
+    if (uint64_t *avec = kta_internal_avec_out(ctx)) {   // KTA_FLAG_ANALYTICS: every rank of the job has it
+        const size_t hist = kta::kAnalyticsHist, extrema = kta::analytics_len(kta_internal_partitions(ctx)) - hist;
+        CN(ctx, R->AllReduce(avec, avec, hist, ncclUint64, ncclSum, st->comm, s));
+        CN(ctx, R->AllReduce(avec + hist, avec + hist, extrema, ncclInt64, ncclMax, st->comm, s));
+    }
     CN(ctx, R->GroupEnd());
     return KTA_OK;
 }

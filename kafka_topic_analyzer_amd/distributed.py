@@ -56,6 +56,18 @@ def allreduce_counter_vector(vec, n_partitions: int, group=None, alive_keys: str
     dist.all_reduce(vec[k:], op=dist.ReduceOp.MAX, group=group)
 
 
+def allreduce_analytics_vector(avec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the analytics SNAPSHOT (kta_analytics_result_vector: device tensor,
+    or a CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_ANALYTICS:
+    all-reduce SUM over the 2 x 34 histogram words (i64 wrap == u64 wrap) and all-reduce MAX over the 4 * P extrema
+    words ([~min ts, max ts, ~smallest, largest] per partition; INT64_MIN where a rank saw nothing)."""
+    import torch.distributed as dist
+    k = N.KTA_ANALYTICS_HIST
+    assert avec.numel() == k + 4 * n_partitions
+    dist.all_reduce(avec[:k], op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(avec[k:], op=dist.ReduceOp.MAX, group=group)
+
+
 def allreduce_alive_table(table, group=None, chunk_elems: int = 1 << 28) -> None:
     """Element-wise MAX of the last-writer tables, in place, chunked (2 GiB of int64 per call) so
     RCCL's staging stays bounded.  Values are < 2^63, so signed MAX == unsigned MAX."""
