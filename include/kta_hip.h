@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -143,6 +143,35 @@ typedef struct kta_analytics {
  *                 for 16 bytes past the last key (kta_device_batch_alloc pads)
  *   seq[i]        optional global consumption index; NULL => base_seq+i  u64  (-c only)
  * Value bytes are never read by the reference path (only their length). */
+/* Device batch layouts (kta_batch.layout).
+ *   KTA_LAYOUT_RAW (0)           the columns as above, one element per record.  What a zero-initialised kta_batch
+ *                                means, what host batches and the staging ring always are.
+ *   KTA_LAYOUT_TILE_COMPACT (1)  what kta_device_batch_alloc returns.  Records are grouped in tiles of
+ *                                KTA_TILE_RECORDS; tile t owns the same bytes of each column as in the raw layout
+ *                                (records [t*1024, t*1024+1024)), and tile_hdr[t] says how partition and ts_ms use them:
+ *     KTA_TILE_RAW      the raw layout (a zero header: what a fresh allocation holds)
+ *     KTA_TILE_COMPACT  partition as u16 in the first half of the tile's partition bytes (KTA_COMPACT_PART_NONE == -1),
+ *                       ts_ms as an i32 offset from ts_base in the first half of the tile's ts_ms bytes
+ *                       (KTA_COMPACT_TS_NONE == -1, not available): 6 B per record instead of 12.  Taken when every
+ *                       partition id lies in [-1, 65535) and the tile's timestamps other than -1 span less than 2^31 ms.
+ *   key_len, val_len, key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
+ *   written by kta_synth_fill_device (compact tiles), kta_kafka_decode_device (raw tiles) and kta_batch_from_raw, and
+ *   read back by kta_batch_to_raw; a raw-layout kta_batch whose column pointers lie inside a tile-compact allocation of
+ *   the same context (a view at a record offset) is resolved to it by every entry point. */
+#define KTA_LAYOUT_RAW 0u
+#define KTA_LAYOUT_TILE_COMPACT 1u
+#define KTA_TILE_RECORDS 1024u
+#define KTA_TILE_RAW 0u
+#define KTA_TILE_COMPACT 1u
+#define KTA_COMPACT_PART_NONE 0xFFFFu        /* compact partition of a record whose id is -1 */
+#define KTA_COMPACT_TS_NONE INT32_MIN        /* compact timestamp of a record whose ts_ms is -1 */
+
+typedef struct kta_tile_hdr {
+    int64_t ts_base;   /* KTA_TILE_COMPACT: ts_ms = ts_base + offset */
+    uint32_t mode;     /* KTA_TILE_RAW / KTA_TILE_COMPACT */
+    uint32_t reserved;
+} kta_tile_hdr;
+
 typedef struct kta_batch {
     int32_t *partition;
     int32_t *key_len;
@@ -153,6 +182,9 @@ typedef struct kta_batch {
     uint64_t *seq;
     uint64_t capacity;           /* records the columns can hold   */
     uint64_t key_bytes_capacity; /* bytes key_bytes can hold       */
+    kta_tile_hdr *tile_hdr;      /* KTA_LAYOUT_TILE_COMPACT: one header per tile of the capacity */
+    uint32_t layout;             /* KTA_LAYOUT_*                   */
+    uint32_t reserved;           /* 0                              */
 } kta_batch;
 
 /* Decoded results: everything the reference's report reads (main.rs:130-170). */
@@ -230,6 +262,13 @@ int kta_submit_device_ex(kta_ctx *ctx, const kta_batch *cols, uint64_t n_records
 int kta_device_batch_alloc(kta_ctx *ctx, uint64_t capacity, uint64_t key_bytes_capacity,
                            int with_seq, kta_batch *out);
 int kta_device_batch_free(kta_ctx *ctx, kta_batch *cols);
+/* The four metric columns (partition, key_len, val_len, ts_ms) of records [0, n) between HOST columns in the raw layout
+ * and a device batch of either layout (synchronous).  from_raw packs every tile that the compact form holds losslessly
+ * and stores the others raw, so any i32 / i64 values round-trip exactly; into a tile-compact batch it writes from a
+ * tile boundary (record 0 of the allocation or of a view at a multiple of KTA_TILE_RECORDS) and may overwrite the rest
+ * of the last tile it touches.  to_raw unpacks. */
+int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *host_cols, uint64_t n, const kta_batch *device_cols);
+int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, const kta_batch *host_cols);
 int kta_copy_to_device(kta_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);
 int kta_copy_to_host(kta_ctx *ctx, void *dst_host, const void *src_device, size_t bytes);
 

@@ -58,6 +58,14 @@ def _np_ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
+def _host_batch(cols: dict) -> KtaBatch:
+    """A raw-layout kta_batch over contiguous numpy metric columns (the arrays must outlive its use)."""
+    hb = KtaBatch()
+    for name in ("partition", "key_len", "val_len", "ts_ms"):
+        setattr(hb, name, cols[name].ctypes.data)
+    return hb
+
+
 class HipMetricHandler:
     """Owns one `kta_ctx`.  `handle_message` == MetricHandler::handle_message (kafka.rs:18-20)."""
 
@@ -210,13 +218,12 @@ class HipMetricHandler:
         self._check(self._lib.kta_submit_device_ex(self._ctx, C.byref(b), n, base_seq, which))
 
     def download_batch(self, b: KtaBatch, n: int, n_key_bytes: int = 0):
-        """Copy a device batch's columns to numpy arrays (tests)."""
-        out = {}
-        for name, dt in (("partition", np.int32), ("key_len", np.int32), ("val_len", np.int32), ("ts_ms", np.int64)):
-            a = np.empty(n, dtype=dt)
-            if n:
-                self._check(self._lib.kta_copy_to_host(self._ctx, _np_ptr(a), getattr(b, name), a.nbytes))
-            out[name] = a
+        """Copy a device batch's columns to numpy arrays in the raw layout (tests; kta_batch_to_raw unpacks the
+        tile-compact layout)."""
+        out = {name: np.empty(n, dtype=dt) for name, dt in
+               (("partition", np.int32), ("key_len", np.int32), ("val_len", np.int32), ("ts_ms", np.int64))}
+        if n:
+            self._check(self._lib.kta_batch_to_raw(self._ctx, C.byref(b), n, C.byref(_host_batch(out))))
         if b.key_off:
             a = np.empty(n, dtype=np.uint32)
             if n:
@@ -238,10 +245,10 @@ class HipMetricHandler:
         n = len(cols["partition"])
         kbytes = np.ascontiguousarray(cols.get("key_bytes", np.zeros(0, np.uint8)), dtype=np.uint8)
         b = self.device_batch_alloc(max(n, 1), max(len(kbytes), 1) if with_keys else 0, "seq" in cols)
-        for name, dt in (("partition", np.int32), ("key_len", np.int32), ("val_len", np.int32), ("ts_ms", np.int64)):
-            a = np.ascontiguousarray(cols[name], dtype=dt)
-            if n:
-                self._check(self._lib.kta_copy_to_device(self._ctx, getattr(b, name), _np_ptr(a), a.nbytes))
+        metric = {name: np.ascontiguousarray(cols[name], dtype=dt) for name, dt in
+                  (("partition", np.int32), ("key_len", np.int32), ("val_len", np.int32), ("ts_ms", np.int64))}
+        if n:   # kta_batch_from_raw packs the tiles (raw where the compact form cannot hold them)
+            self._check(self._lib.kta_batch_from_raw(self._ctx, C.byref(_host_batch(metric)), n, C.byref(b)))
         if with_keys:
             a = np.ascontiguousarray(cols["key_off"], dtype=np.uint32)
             if n:

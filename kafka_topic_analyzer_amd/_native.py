@@ -56,10 +56,15 @@ class KtaAnalytics(C.Structure):
     _fields_ = [("key_size_hist", C.c_uint64 * 34), ("value_size_hist", C.c_uint64 * 34)]
 
 
+KTA_LAYOUT_RAW, KTA_LAYOUT_TILE_COMPACT = 0, 1   # kta_batch.layout (include/kta_hip.h)
+KTA_TILE_RECORDS = 1024
+
+
 class KtaBatch(C.Structure):
     _fields_ = [("partition", C.c_void_p), ("key_len", C.c_void_p), ("val_len", C.c_void_p),
                 ("ts_ms", C.c_void_p), ("key_off", C.c_void_p), ("key_bytes", C.c_void_p),
-                ("seq", C.c_void_p), ("capacity", C.c_uint64), ("key_bytes_capacity", C.c_uint64)]
+                ("seq", C.c_void_p), ("capacity", C.c_uint64), ("key_bytes_capacity", C.c_uint64),
+                ("tile_hdr", C.c_void_p), ("layout", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class KtaResult(C.Structure):
@@ -118,6 +123,8 @@ SIGNATURES = {
     "kta_submit_device_ex": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.c_uint64, C.c_int]),
     "kta_device_batch_alloc": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(KtaBatch)]),
     "kta_device_batch_free": (C.c_int, [_P, C.POINTER(KtaBatch)]),
+    "kta_batch_from_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
+    "kta_batch_to_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
     "kta_copy_to_device": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_copy_to_host": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_set_compute_stream": (C.c_int, [_P, C.c_void_p]),

@@ -335,8 +335,10 @@ __device__ __noinline__ uint32_t hot_filter(uint32_t guard_off, uint32_t lane, u
 // workspace, which kta_fold_partials folds as it folds the scan's.  A workgroup takes less than 2^21 records (the
 // host checks), so the 21-bit counts cannot overflow.
 struct FuseArgs {
-    const int32_t *partition;
-    const int64_t *ts_ms;
+    const int32_t *partition;    // hdr != null: the tile-compact layout (kta_hip.h), the pointers address the allocation's
+    const int64_t *ts_ms;        // record 0 and the batch's record i is the allocation's rec0 + i (tile_record)
+    const kta_tile_hdr *hdr;
+    uint64_t rec0;
     uint32_t P;                  // <= kFuseMaxP
     uint32_t rep_log2;           // replicas of a partition's sums in LDS: (P << rep_log2) <= kFuseSlots (fuse_replicas)
     uint64_t *partials;          // rows of row_len words, one per workgroup
@@ -450,6 +452,16 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
             long long ts[FUSE ? 4 : 1];
         };
         auto load_cols32 = [&](uint64_t tile, bool ok, Cols &r) __attribute__((always_inline)) {
+            // FUSE, tile-compact: a step's 256 records usually lie in one layout tile — then its header is loaded once
+            kta_tile_hdr th{};
+            uint64_t tt = 0;
+            bool one = false;
+            if (FUSE && fz.hdr && ok) {
+                const uint64_t a0 = fz.rec0 + tile * kTile;
+                tt = a0 / KTA_TILE_RECORDS;
+                one = (a0 + kTile - 1) / KTA_TILE_RECORDS == tt;
+                if (one) th = fz.hdr[tt];
+            }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint64_t i = tile * kTile + 64u * j + lane;
@@ -460,8 +472,14 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
                 r.ko[j] = KTA_P32_LOAD(c.key_off + ic);
                 r.kl[j] = in ? r.kl[j] : -1;               // key None: ignored (metric.rs:302)
                 if (FUSE) {
-                    r.pt[j] = KTA_P32_LOAD(fz.partition + ic);
-                    r.ts[j] = KTA_P32_LOAD(fz.ts_ms + ic);
+                    if (fz.hdr && one) {
+                        tile_record_h<true>(fz.partition, fz.ts_ms, th, tt, fz.rec0 + ic, r.pt[j], r.ts[j]);
+                    } else if (fz.hdr) {
+                        tile_record<true>(fz.partition, fz.ts_ms, fz.hdr, fz.rec0 + ic, r.pt[j], r.ts[j]);
+                    } else {
+                        r.pt[j] = KTA_P32_LOAD(fz.partition + ic);
+                        r.ts[j] = KTA_P32_LOAD(fz.ts_ms + ic);
+                    }
                     r.vl[j] = in ? r.vl[j] : 0;
                     r.pt[j] = in ? r.pt[j] : -2;           // no record here (a record's bad id stays what it is)
                 }
@@ -883,13 +901,28 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition48(AliveColum
         long long x_ts[FUSE ? 4 : 1];
         auto load_extra48 = [&](const Cols &r) __attribute__((always_inline)) {
             if (FUSE) {
+                kta_tile_hdr th{};   // (as kta_alive_partition32: one header load per step where the step lies in one tile)
+                uint64_t tt = 0;
+                bool one = false;
+                if (fz.hdr && r.on != 0u) {
+                    const uint64_t a0 = fz.rec0 + r.at;
+                    tt = a0 / KTA_TILE_RECORDS;
+                    one = (a0 + kTile - 1) / KTA_TILE_RECORDS == tt;
+                    if (one) th = fz.hdr[tt];
+                }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const uint32_t i = r.at + 64u * (uint32_t)j + lane;
                     const bool in = r.on != 0u && i < nn;
                     const uint32_t ic = in ? i : nn - 1u;
-                    x_pt[j] = ld_nt(fz.partition, ic * 4u);
-                    x_ts[j] = ld_nt(fz.ts_ms, ic * 8u);
+                    if (fz.hdr && one) {
+                        tile_record_h<true>(fz.partition, fz.ts_ms, th, tt, fz.rec0 + ic, x_pt[j], x_ts[j]);
+                    } else if (fz.hdr) {
+                        tile_record<true>(fz.partition, fz.ts_ms, fz.hdr, fz.rec0 + ic, x_pt[j], x_ts[j]);
+                    } else {
+                        x_pt[j] = ld_nt(fz.partition, ic * 4u);
+                        x_ts[j] = ld_nt(fz.ts_ms, ic * 8u);
+                    }
                     x_pt[j] = in ? x_pt[j] : -2;           // no record here (a record's bad id stays what it is)
                 }
             }
@@ -2243,14 +2276,14 @@ hipError_t launch_pair(const AliveColumns &c, uint64_t n, uint64_t base_seq, con
             KTA_UB_MARK(0);
             hipLaunchKernelGGL((kta_alive_partition32<BLOG2, true>), dim3(pl.segment_wgs), dim3(kPartThreads), lds1, s, c, n, pl.tiles_per_wg,
                                reinterpret_cast<uint32_t *>(pp), ws.counts, pl.cap, pool, pl.pool_pairs, ctl, hist,
-                               FuseArgs{fuse->partition, fuse->ts_ms, fuse->P, fuse_replicas_log2(fuse->P), fuse->partials, fuse->row_len});
+                               FuseArgs{fuse->partition, fuse->ts_ms, fuse->hdr, fuse->rec0, fuse->P, fuse_replicas_log2(fuse->P), fuse->partials, fuse->row_len});
         } else {
             e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_alive_partition32<BLOG2, false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0);
             if (e != hipSuccess) return e;
             KTA_UB_MARK(0);
             hipLaunchKernelGGL((kta_alive_partition32<BLOG2, false>), dim3(pl.segment_wgs), dim3(kPartThreads), lds0, s, c, n, pl.tiles_per_wg,
-                               reinterpret_cast<uint32_t *>(pp), ws.counts, pl.cap, pool, pl.pool_pairs, ctl, hist, FuseArgs{nullptr, nullptr, 0, 0, nullptr, 0});
+                               reinterpret_cast<uint32_t *>(pp), ws.counts, pl.cap, pool, pl.pool_pairs, ctl, hist, FuseArgs{nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0});
         }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -2290,10 +2323,10 @@ hipError_t launch_pair(const AliveColumns &c, uint64_t n, uint64_t base_seq, con
     const uint32_t *skip = c.seq ? flag : nullptr;       // (raised by pass 1 when the batch's seq column does not ascend)
     const size_t lds0 = (size_t)B * kRingW48 * 2 + (size_t)B * 8 + (size_t)kConsumers * 64 * 4 + 16;
     const size_t lds1 = lds0 + (fuse ? (size_t)3 * kFuseSlots * 8 + (size_t)kPartWaves * 5 * 8 : 0);
-    FuseArgs fz{nullptr, nullptr, 0, 0, nullptr, 0};
+    FuseArgs fz{nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0};
     if (fuse) {
         if (fuse->P > kFuseMaxP || (uint64_t)pl.tiles_per_wg * kTile >= (1ull << kFuseCntBits)) return hipErrorInvalidValue;
-        fz = FuseArgs{fuse->partition, fuse->ts_ms, fuse->P, fuse_replicas_log2(fuse->P), fuse->partials, fuse->row_len};
+        fz = FuseArgs{fuse->partition, fuse->ts_ms, fuse->hdr, fuse->rec0, fuse->P, fuse_replicas_log2(fuse->P), fuse->partials, fuse->row_len};
     }
     unsigned short *pp16 = reinterpret_cast<unsigned short *>(pp);
 #define KTA_LAUNCH_P48(SEQ, FUSE)                                                                                                    \

@@ -95,6 +95,9 @@ struct kta_ctx {
     // kta_alive_fallback; the word comes back with the stream and is never waited for
     uint64_t info_slices = 0, info_fused = 0, info_scanned = 0, info_failed_buckets = 0;
     std::vector<Stage> stages;
+    // the tile-compact batches kta_device_batch_alloc handed out (as allocated): a raw-layout kta_batch whose columns point
+    // inside one of them is a view of it at a record offset (resolve_batch)
+    std::vector<kta_batch> compact_batches;
     uint64_t batch_capacity = 0, key_bytes_capacity = 0;
     int cur = 0;
     bool acquired = false;
@@ -147,12 +150,20 @@ int hip_fail(kta_ctx *ctx, hipError_t e, const char *what)
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+uint64_t tiles_of(uint64_t n) { return (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS; }
+
+// Tile-compact (kta_hip.h): the columns cover whole tiles, so that a kernel may read any record of a tile the batch touches.
 int alloc_device_batch(kta_ctx *ctx, uint64_t cap, uint64_t kcap, bool keys, bool seq, kta_batch *b)
 {
     memset(b, 0, sizeof(*b));
     b->capacity = cap;
     b->key_bytes_capacity = keys ? kcap : 0;
-    const size_t c4 = pad16(cap * 4 + 16), c8 = pad16(cap * 8 + 16);
+    b->layout = KTA_LAYOUT_TILE_COMPACT;
+    const uint64_t ntiles = tiles_of(cap) ? tiles_of(cap) : 1;
+    const uint64_t rows = ntiles * KTA_TILE_RECORDS;
+    const size_t c4 = pad16(rows * 4 + 16), c8 = pad16(rows * 8 + 16);
+    KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * sizeof(kta_tile_hdr)));
+    KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * sizeof(kta_tile_hdr)));   // every tile raw
     KTA_HIP(ctx, hipMalloc((void **)&b->partition, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->key_len, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->val_len, c4));
@@ -174,7 +185,44 @@ void free_device_batch(kta_batch *b)
     if (b->key_off) (void)hipFree(b->key_off);
     if (b->key_bytes) (void)hipFree(b->key_bytes);
     if (b->seq) (void)hipFree(b->seq);
+    if (b->tile_hdr) (void)hipFree(b->tile_hdr);
     memset(b, 0, sizeof(*b));
+}
+
+// A device batch as the kernels take it.  hdr == null: the raw layout, the pointers are the caller's.  Otherwise a
+// tile-compact allocation: the pointers address its record 0 and the batch starts at its record rec0 — the allocation
+// itself (rec0 0), or a raw-layout kta_batch whose columns point inside one of the context's tile-compact allocations
+// (a view built by pointer arithmetic, rec0 = the offset).
+struct Resolved {
+    int32_t *partition, *key_len, *val_len;
+    int64_t *ts_ms;
+    kta_tile_hdr *hdr;
+    uint64_t rec0;
+};
+
+int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
+{
+    *r = Resolved{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0};
+    const uintptr_t p = reinterpret_cast<uintptr_t>(c->partition);
+    for (const kta_batch &e : ctx->compact_batches) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(e.partition);
+        const uint64_t rows = (tiles_of(e.capacity) ? tiles_of(e.capacity) : 1) * KTA_TILE_RECORDS;
+        if (!c->partition || p < lo || p >= lo + rows * 4) continue;
+        if ((p - lo) % 4 != 0) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
+        const uint64_t rec0 = (p - lo) / 4;
+        if ((c->ts_ms && c->ts_ms != e.ts_ms + rec0) || (c->key_len && c->key_len != e.key_len + rec0) ||
+            (c->val_len && c->val_len != e.val_len + rec0))
+            return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
+        *r = Resolved{e.partition, e.key_len, e.val_len, e.ts_ms, e.tile_hdr, rec0};
+        return KTA_OK;
+    }
+    if (c->layout == KTA_LAYOUT_TILE_COMPACT) {
+        if (!c->tile_hdr) return fail(ctx, KTA_ERR_INVALID, "a tile-compact batch needs its tile headers");
+        r->hdr = c->tile_hdr;
+    } else if (c->layout != KTA_LAYOUT_RAW) {
+        return fail(ctx, KTA_ERR_INVALID, "unknown batch layout");
+    }
+    return KTA_OK;
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -261,10 +309,21 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
             !aligned16(c->ts_ms))
             return fail(ctx, KTA_ERR_INVALID, "device columns must be 16-byte aligned");
     }
+    Resolved rb{};
+    if (which & 1) {
+        int rc = resolve_batch(ctx, c, &rb);
+        if (rc != KTA_OK) return rc;
+    }
+    // the metric columns of records [at, ...) of the batch
+    auto scan_cols = [&](uint64_t at) {
+        return kta::ScanColumns{rb.hdr ? rb.partition : rb.partition + at, rb.hdr ? rb.key_len : rb.key_len + at,
+                                rb.hdr ? rb.val_len : rb.val_len + at, rb.hdr ? rb.ts_ms : rb.ts_ms + at, rb.hdr,
+                                rb.rec0 + at};
+    };
     if ((which & 1) && !fuse) {
-        kta::ScanColumns sc{c->partition, c->key_len, c->val_len, c->ts_ms};
+        const kta::ScanColumns sc = scan_cols(0);
         kta::ScanPlan pl = kta::plan_scan(ctx->P, n, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant,
-                                          ctx->analytics);
+                                          ctx->analytics, sc.hdr != nullptr);
         if (pl.workgroups > ctx->max_rows) pl.workgroups = ctx->max_rows;
         if (ctx->timing) {
             int rc = timer_pair(ctx, 0, &a, &b);
@@ -353,7 +412,8 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                 if (fuse && kta::alive_fuse_possible(pl, ctx->P) && pl.segment_wgs <= ctx->max_rows) {
                     ctx->info_fused++;
                     const uint32_t row_len = kta::scan_row_len(ctx->P, false);
-                    const kta::AliveFuse fz{c->partition + at, c->ts_ms + at, ctx->P, ctx->d_partials, row_len};
+                    const kta::ScanColumns sc = scan_cols(at);
+                    const kta::AliveFuse fz{sc.partition, sc.ts_ms, sc.hdr, sc.rec0, ctx->P, ctx->d_partials, row_len};
                     KTA_HIP(ctx, kta::launch_alive_partitioned(sl, take, base_seq + at, st, pl, ws, report ? ctx->d_alive_stats : nullptr,
                                                                ctx->s_compute, &fz));
                     KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, pl.segment_wgs, ctx->P, ctx->d_vec, row_len, ctx->d_avec,
@@ -361,8 +421,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                 } else {
                     if (fuse) {      // (a slice the fused pass does not take: its records go through the scan)
                         ctx->info_scanned++;
-                        kta::ScanColumns sc{c->partition + at, c->key_len + at, c->val_len + at, c->ts_ms + at};
-                        kta::ScanPlan spl = kta::plan_scan(ctx->P, take, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics);
+                        const kta::ScanColumns sc = scan_cols(at);
+                        kta::ScanPlan spl = kta::plan_scan(ctx->P, take, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics,
+                                                           sc.hdr != nullptr);
                         if (spl.workgroups > ctx->max_rows) spl.workgroups = ctx->max_rows;
                         KTA_HIP(ctx, kta::launch_metrics_scan(spl, sc, take, ctx->P, ctx->d_partials, ctx->s_compute));
                         KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, spl.workgroups, ctx->P, ctx->d_vec, spl.row_len, ctx->d_avec,
@@ -781,6 +842,7 @@ int kta_device_batch_alloc(kta_ctx *ctx, uint64_t capacity, uint64_t key_bytes_c
         return fail(ctx, KTA_ERR_INVALID, "key_bytes_capacity must be < 4 GiB per batch");
     int rc = alloc_device_batch(ctx, capacity, key_bytes_capacity, key_bytes_capacity > 0, with_seq != 0, out);
     if (rc != KTA_OK) free_device_batch(out);
+    else ctx->compact_batches.push_back(*out);
     return rc;
 }
 
@@ -789,9 +851,124 @@ int kta_device_batch_free(kta_ctx *ctx, kta_batch *cols)
     if (!ctx || !cols) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    for (size_t i = 0; i < ctx->compact_batches.size(); i++)
+        if (cols->partition && ctx->compact_batches[i].partition == cols->partition) {
+            ctx->compact_batches.erase(ctx->compact_batches.begin() + (long)i);
+            break;
+        }
     free_device_batch(cols);
     return KTA_OK;
 }
+
+namespace {
+
+// Whether records [0, m) of host columns fit one compact tile (kta_hip.h), and its ts_base.
+bool tile_fits_compact(const int32_t *p, const int64_t *t, uint64_t m, int64_t *base)
+{
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    for (uint64_t j = 0; j < m; j++) {
+        if (p[j] < -1 || p[j] >= (int32_t)KTA_COMPACT_PART_NONE) return false;
+        if (t[j] == -1) continue;
+        lo = t[j] < lo ? t[j] : lo;
+        hi = t[j] > hi ? t[j] : hi;
+    }
+    *base = lo <= hi ? lo : 0;
+    return lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX;
+}
+
+} // namespace
+
+int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_batch *d)
+{
+    if (!ctx || !h || !d) return KTA_ERR_INVALID;
+    if (n == 0) return KTA_OK;
+    if (!h->partition || !h->key_len || !h->val_len || !h->ts_ms || !d->partition || !d->key_len || !d->val_len || !d->ts_ms)
+        return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    Resolved r{};
+    int rc = resolve_batch(ctx, d, &r);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpy(d->key_len, h->key_len, n * 4, hipMemcpyHostToDevice));
+    KTA_HIP(ctx, hipMemcpy(d->val_len, h->val_len, n * 4, hipMemcpyHostToDevice));
+    if (!r.hdr) {
+        KTA_HIP(ctx, hipMemcpy(d->partition, h->partition, n * 4, hipMemcpyHostToDevice));
+        KTA_HIP(ctx, hipMemcpy(d->ts_ms, h->ts_ms, n * 8, hipMemcpyHostToDevice));
+        return KTA_OK;
+    }
+    if (r.rec0 % KTA_TILE_RECORDS)
+        return fail(ctx, KTA_ERR_INVALID, "a tile-compact batch is written from a tile boundary");
+    // the tiles' images, then one copy per column and one of the headers
+    const uint64_t nt = tiles_of(n);
+    std::vector<int32_t> part(nt * KTA_TILE_RECORDS, 0);
+    std::vector<int64_t> ts(nt * KTA_TILE_RECORDS, 0);
+    std::vector<kta_tile_hdr> hdr(nt);
+    for (uint64_t T = 0; T < nt; T++) {
+        const uint64_t a = T * KTA_TILE_RECORDS, m = n - a < KTA_TILE_RECORDS ? n - a : KTA_TILE_RECORDS;
+        int64_t base = 0;
+        if (tile_fits_compact(h->partition + a, h->ts_ms + a, m, &base)) {
+            uint16_t *p16 = reinterpret_cast<uint16_t *>(part.data() + a);
+            int32_t *o32 = reinterpret_cast<int32_t *>(ts.data() + a);
+            for (uint64_t j = 0; j < m; j++) {
+                const int32_t p = h->partition[a + j];
+                const int64_t t = h->ts_ms[a + j];
+                p16[j] = p == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p;
+                o32[j] = t == -1 ? KTA_COMPACT_TS_NONE : (int32_t)((uint64_t)t - (uint64_t)base);
+            }
+            hdr[T] = kta_tile_hdr{base, KTA_TILE_COMPACT, 0};
+        } else {
+            memcpy(part.data() + a, h->partition + a, m * 4);
+            memcpy(ts.data() + a, h->ts_ms + a, m * 8);
+            hdr[T] = kta_tile_hdr{0, KTA_TILE_RAW, 0};
+        }
+    }
+    KTA_HIP(ctx, hipMemcpy(r.partition + r.rec0, part.data(), part.size() * 4, hipMemcpyHostToDevice));
+    KTA_HIP(ctx, hipMemcpy(r.ts_ms + r.rec0, ts.data(), ts.size() * 8, hipMemcpyHostToDevice));
+    KTA_HIP(ctx, hipMemcpy(r.hdr + r.rec0 / KTA_TILE_RECORDS, hdr.data(), nt * sizeof(kta_tile_hdr), hipMemcpyHostToDevice));
+    return KTA_OK;
+}
+
+int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n, const kta_batch *h)
+{
+    if (!ctx || !h || !d) return KTA_ERR_INVALID;
+    if (n == 0) return KTA_OK;
+    if (!h->partition || !h->key_len || !h->val_len || !h->ts_ms || !d->partition || !d->key_len || !d->val_len || !d->ts_ms)
+        return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    Resolved r{};
+    int rc = resolve_batch(ctx, d, &r);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpy(h->key_len, d->key_len, n * 4, hipMemcpyDeviceToHost));
+    KTA_HIP(ctx, hipMemcpy(h->val_len, d->val_len, n * 4, hipMemcpyDeviceToHost));
+    if (!r.hdr) {
+        KTA_HIP(ctx, hipMemcpy(h->partition, d->partition, n * 4, hipMemcpyDeviceToHost));
+        KTA_HIP(ctx, hipMemcpy(h->ts_ms, d->ts_ms, n * 8, hipMemcpyDeviceToHost));
+        return KTA_OK;
+    }
+    const uint64_t t0 = r.rec0 / KTA_TILE_RECORDS, nt = tiles_of(r.rec0 + n) - t0;
+    std::vector<int32_t> part(nt * KTA_TILE_RECORDS);
+    std::vector<int64_t> ts(nt * KTA_TILE_RECORDS);
+    std::vector<kta_tile_hdr> hdr(nt);
+    KTA_HIP(ctx, hipMemcpy(part.data(), r.partition + t0 * KTA_TILE_RECORDS, part.size() * 4, hipMemcpyDeviceToHost));
+    KTA_HIP(ctx, hipMemcpy(ts.data(), r.ts_ms + t0 * KTA_TILE_RECORDS, ts.size() * 8, hipMemcpyDeviceToHost));
+    KTA_HIP(ctx, hipMemcpy(hdr.data(), r.hdr + t0, nt * sizeof(kta_tile_hdr), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t a = r.rec0 + i - t0 * KTA_TILE_RECORDS, T = a / KTA_TILE_RECORDS;   // (a: index into the images)
+        if (hdr[T].mode == KTA_TILE_COMPACT) {
+            const uint64_t ci = a + T * KTA_TILE_RECORDS;
+            const uint16_t p = reinterpret_cast<const uint16_t *>(part.data())[ci];
+            const int32_t o = reinterpret_cast<const int32_t *>(ts.data())[ci];
+            h->partition[i] = p == KTA_COMPACT_PART_NONE ? -1 : (int32_t)p;
+            h->ts_ms[i] = o == KTA_COMPACT_TS_NONE ? -1 : (int64_t)((uint64_t)hdr[T].ts_base + (uint64_t)(int64_t)o);
+        } else {
+            h->partition[i] = part[a];
+            h->ts_ms[i] = ts[a];
+        }
+    }
+    return KTA_OK;
+}
+
 
 int kta_copy_to_device(kta_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
@@ -1261,3 +1438,25 @@ bool kta_internal_count_alive(kta_ctx *ctx) { return ctx->alive; }
 hipStream_t kta_internal_stream(kta_ctx *ctx) { return ctx->s_compute; }
 int kta_internal_device(kta_ctx *ctx) { return ctx->device; }
 void kta_internal_set_error(kta_ctx *ctx, const char *msg) { ctx->err = msg; }
+
+// Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
+// allocation that the range overlaps become raw (kta::launch_tiles_to_raw), on the compute stream.
+int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
+{
+    Resolved r{};
+    int rc = resolve_batch(ctx, d, &r);
+    if (rc != KTA_OK || !r.hdr || n == 0) return rc;
+    KTA_HIP(ctx, kta::launch_tiles_to_raw(r.partition, r.ts_ms, r.hdr, r.rec0, r.rec0 + n, ctx->s_compute));
+    return KTA_OK;
+}
+
+// The allocation's columns and the batch's first record there (hdr null: the raw layout).
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
+                         uint64_t *rec0)
+{
+    Resolved r{};
+    int rc = resolve_batch(ctx, d, &r);
+    if (rc != KTA_OK) return rc;
+    *partition = r.partition, *ts_ms = r.ts_ms, *hdr = r.hdr, *rec0 = r.rec0;
+    return KTA_OK;
+}

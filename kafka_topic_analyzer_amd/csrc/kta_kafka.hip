@@ -43,6 +43,7 @@ uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
 bool kta_internal_timing(kta_ctx *ctx);
 bool kta_internal_count_alive(kta_ctx *ctx);
 hipStream_t kta_internal_copy_stream(kta_ctx *ctx);
+int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
 
 namespace {
 
@@ -1588,6 +1589,8 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
     }
     KK(ctx, hipSetDevice(kta_internal_device(ctx)));
     hipStream_t s = kta_internal_stream(ctx);
+    // the decode stores the raw layout: the output's tiles become raw tiles first (a tile-compact batch, kta_hip.h)
+    if (int rc = kta_internal_prepare_raw(ctx, out, n_records)) return rc;
     KafkaState *st = state_of(ctx);
     hipStream_t cs = kta_internal_copy_stream(ctx);
     const int dk = st->desc_slot;

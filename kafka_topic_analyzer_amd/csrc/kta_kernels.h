@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kta_hip.h"
+
 namespace kta {
 
 constexpr int kWG = 256;                    // threads per workgroup (4 wave64)
@@ -17,11 +19,15 @@ enum ScanGlobal : uint32_t {
     SG_TMIN = 0, SG_TMAX = 1, SG_SMIN = 2, SG_SMAX = 3, SG_BAD = 4, SG_NREC = 5
 };
 
+// hdr == null: the raw layout, the pointers address record 0 of the batch.  Otherwise the tile-compact layout
+// (kta_hip.h): the pointers address record 0 of the ALLOCATION (tile 0) and the batch is its records [rec0, rec0 + n).
 struct ScanColumns {
     const int32_t *partition;
     const int32_t *key_len;
     const int32_t *val_len;
     const int64_t *ts_ms;
+    const kta_tile_hdr *hdr;
+    uint64_t rec0;
 };
 
 struct AliveColumns {
@@ -42,6 +48,37 @@ struct WrittenList {
 };
 
 #ifdef __HIPCC__
+// Partition id and raw timestamp of record i (an allocation index) of a tile-compact batch.  In a compact tile the
+// u16 / i32 of record i sit at element i + tile * KTA_TILE_RECORDS of the column seen as u16 / i32: the first half of
+// the tile's own bytes.
+// (tile_record_h: the header h of allocation tile `tile` is already loaded.  A record of another tile reads in-bounds
+// garbage — for records the caller masks.)
+template <bool NT>
+__device__ __forceinline__ void tile_record_h(const int32_t *part, const int64_t *ts, const kta_tile_hdr &h, uint64_t tile,
+                                              uint64_t i, int32_t &p, long long &t)
+{
+    if (h.mode == KTA_TILE_COMPACT) {
+        const uint64_t ci = i + tile * KTA_TILE_RECORDS;
+        const uint16_t *p16 = reinterpret_cast<const uint16_t *>(part) + ci;
+        const int32_t *t32 = reinterpret_cast<const int32_t *>(ts) + ci;
+        const uint32_t pu = NT ? __builtin_nontemporal_load(p16) : *p16;
+        const int32_t o = NT ? __builtin_nontemporal_load(t32) : *t32;
+        p = pu == KTA_COMPACT_PART_NONE ? -1 : (int32_t)pu;
+        t = o == KTA_COMPACT_TS_NONE ? -1ll : (long long)((uint64_t)h.ts_base + (uint64_t)(int64_t)o);
+    } else {
+        p = NT ? __builtin_nontemporal_load(part + i) : part[i];
+        t = NT ? __builtin_nontemporal_load(ts + i) : ts[i];
+    }
+}
+
+template <bool NT>
+__device__ __forceinline__ void tile_record(const int32_t *part, const int64_t *ts, const kta_tile_hdr *hdr, uint64_t i,
+                                            int32_t &p, long long &t)
+{
+    const uint64_t tile = i / KTA_TILE_RECORDS;
+    tile_record_h<NT>(part, ts, hdr[tile], tile, i, p, t);
+}
+
 // wave-aggregated append (works under divergence: the ballot covers the active lanes)
 __device__ __forceinline__ void note_new_slot(const WrittenList &wl, bool is_new, uint32_t slot)
 {
@@ -76,7 +113,9 @@ inline uint32_t scan_row_len(uint32_t P, bool analytics)
     return P * kScanCols + kScanGlobals + (analytics ? 4 * P + 2 * 34 : 0);
 }
 
-ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics);
+// tiled: the batch is tile-compact (ScanColumns.hdr): more workgroups per CU (see plan_scan)
+ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics,
+                   bool tiled = false);
 
 // K1: per-record metric accumulation (metric.rs:207-252) over one struct-of-arrays batch.
 hipError_t launch_metrics_scan(const ScanPlan &plan, const ScanColumns &c, uint64_t n, uint32_t P,
@@ -84,6 +123,9 @@ hipError_t launch_metrics_scan(const ScanPlan &plan, const ScanColumns &c, uint6
 // K5: fold the per-workgroup partial rows into the persistent counter vector.
 hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_t P, uint64_t *vec,
                                 uint32_t row_len, uint64_t *analytics_vec, hipStream_t s);
+// Tile-compact batches (kta_hip.h): make every tile that overlaps the allocation's records [lo, hi) raw (compact tiles are expanded in place, so
+// records outside the range keep their values) before a producer that writes the raw layout stores into it.
+hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, kta_tile_hdr *hdr, uint64_t lo, uint64_t hi, hipStream_t s);
 // reset the counter vector to the MessageMetrics::new state (metric.rs:30-46)
 hipError_t launch_init_vector(uint64_t *vec, uint32_t P, uint64_t *analytics_vec, hipStream_t s);
 
@@ -135,8 +177,10 @@ AlivePartitionPlan plan_alive_partition(uint64_t n, int req_wgs, int cu_count, b
 // workspace per partition workgroup (plan.segment_wgs rows of row_len words), to be folded by launch_fold_partials —
 // MessageMetrics::handle_message (metric.rs:207-252) without a second reading of key_len and val_len.
 struct AliveFuse {
-    const int32_t *partition;
+    const int32_t *partition;   // as ScanColumns: with hdr, the allocation's record 0 and the batch's first record rec0
     const int64_t *ts_ms;
+    const kta_tile_hdr *hdr;
+    uint64_t rec0;
     uint32_t P;
     uint64_t *partials;
     uint32_t row_len;

@@ -37,6 +37,13 @@ namespace kta {
 // folds the rows.  No floating point anywhere; integer adds commute, so results are
 // independent of scheduling.
 //
+// Tile-compact batches (TILED, kta_hip.h): the tiles are the layout's own (KTA_TILE_RECORDS = this kernel's 1024),
+// taken at their allocation positions, and records outside [rec0, rec0 + n) are masked per record (no scalar tail).
+// The tile's header (one uniform load) picks the loads: a compact tile is read as one uint2 of u16 partitions and
+// one int4 of i32 timestamp offsets per lane next to the two int4 length loads — 14 B per record, every
+// instruction a fully coalesced wave-wide stream (512 B or 1 KiB) — and a raw tile as above.  The compact values
+// travel in the raw registers of the Quad (p.xy, t0) and are widened when the tile is accumulated.
+//
 // Globals: min/max of ts_ms (-1 => 0 first, metric.rs:209) — the division by 1000
 // (metric.rs:210) is monotone, so it is applied once to the extrema on the host — and
 // min/max of key+value size over non-tombstones (metric.rs:249-251), both carried in
@@ -49,10 +56,14 @@ constexpr uint32_t kFlushTiles = 256;          // 256 tiles x 1024 records = 2^1
 struct Quad {
     int4 p, k, v;
     longlong2 t0, t1;
+    long long base;    // TILED: the tile's ts_base
+    uint32_t compact;  // TILED: 1 = p.xy hold four u16 partitions, t0 four i32 timestamp offsets
 };
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v2i __attribute__((ext_vector_type(2)));
 typedef long long v2l __attribute__((ext_vector_type(2)));
+static_assert(KTA_TILE_RECORDS == 4u * kWG, "a layout tile is one scan tile: 256 lanes x 4 records");
 
 // NT: non-temporal loads (the columns are streamed exactly once; keep them out of L2/MALL)
 template <bool NT>
@@ -75,6 +86,59 @@ __device__ __forceinline__ void load_quad(Quad &q, const ScanColumns &c, uint64_
         q.v = reinterpret_cast<const int4 *>(c.val_len)[qi];
         q.t0 = reinterpret_cast<const longlong2 *>(c.ts_ms)[2 * qi];
         q.t1 = reinterpret_cast<const longlong2 *>(c.ts_ms)[2 * qi + 1];
+    }
+    q.compact = 0u;
+}
+
+// TILED: the lane's 4 records of allocation tile T
+template <bool NT>
+__device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid)
+{
+    const kta_tile_hdr h = c.hdr[T];
+    const uint64_t qi = T * (KTA_TILE_RECORDS / 4) + tid;
+    if (h.mode != KTA_TILE_COMPACT) {
+        load_quad<NT>(q, c, qi);
+        return;
+    }
+    const uint64_t ci = T * (KTA_TILE_RECORDS / 2) + tid;   // the tile's first half, in 8-byte / 16-byte units
+    v2i p;
+    v4i o;
+    if (NT) {
+        const v4i k = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.key_len) + qi);
+        const v4i v = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.val_len) + qi);
+        p = __builtin_nontemporal_load(reinterpret_cast<const v2i *>(c.partition) + ci);
+        o = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.ts_ms) + ci);
+        q.k = make_int4(k.x, k.y, k.z, k.w);
+        q.v = make_int4(v.x, v.y, v.z, v.w);
+    } else {
+        q.k = reinterpret_cast<const int4 *>(c.key_len)[qi];
+        q.v = reinterpret_cast<const int4 *>(c.val_len)[qi];
+        p = reinterpret_cast<const v2i *>(c.partition)[ci];
+        o = reinterpret_cast<const v4i *>(c.ts_ms)[ci];
+    }
+    q.p.x = p.x;
+    q.p.y = p.y;
+    q.t0.x = (long long)(((uint64_t)(uint32_t)o.y << 32) | (uint32_t)o.x);
+    q.t0.y = (long long)(((uint64_t)(uint32_t)o.w << 32) | (uint32_t)o.z);
+    q.base = h.ts_base;
+    q.compact = 1u;
+}
+
+// the quad's partitions and raw timestamps, whichever form it was loaded in
+__device__ __forceinline__ void quad_part_ts(const Quad &q, uint32_t (&p)[4], long long (&t)[4])
+{
+    if (q.compact) {
+        const uint32_t u[4] = {(uint32_t)q.p.x & 0xFFFFu, (uint32_t)q.p.x >> 16, (uint32_t)q.p.y & 0xFFFFu, (uint32_t)q.p.y >> 16};
+        const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
+                              (int32_t)(uint32_t)q.t0.y, (int32_t)(uint32_t)((uint64_t)q.t0.y >> 32)};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            p[j] = u[j] == KTA_COMPACT_PART_NONE ? 0xFFFFFFFFu : u[j];
+            t[j] = o[j] == KTA_COMPACT_TS_NONE ? -1ll : (long long)((uint64_t)q.base + (uint64_t)(int64_t)o[j]);
+        }
+    } else {
+        p[0] = (uint32_t)q.p.x, p[1] = (uint32_t)q.p.y, p[2] = (uint32_t)q.p.z, p[3] = (uint32_t)q.p.w;
+        t[0] = q.t0.x, t[1] = q.t0.y, t[2] = q.t1.x, t[3] = q.t1.y;
     }
 }
 
@@ -171,23 +235,28 @@ __device__ __forceinline__ void lds_histograms(const Rec &r, const ScanLds &L)
 // The lane's 4 consecutive records of a tile.  A Kafka consumer delivers per-partition runs, so the
 // four usually share a partition: then their contributions are combined in registers and cost one
 // set of LDS atomics instead of four (4x fewer same-address conflicts inside a run).
+// valid: bit j = record j of the quad is one of the batch's
 template <int VARIANT, bool ANALYTICS>
-__device__ __forceinline__ void accumulate_quad(const Quad &q, bool valid, uint32_t P, uint32_t rep_log2,
+__device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2,
                                                 uint32_t rep, const ScanLds &L, LaneState &st)
 {
-    Rec r[4] = {make_rec((uint32_t)q.p.x, q.k.x, q.v.x, q.t0.x, P, valid),
-                make_rec((uint32_t)q.p.y, q.k.y, q.v.y, q.t0.y, P, valid),
-                make_rec((uint32_t)q.p.z, q.k.z, q.v.z, q.t1.x, P, valid),
-                make_rec((uint32_t)q.p.w, q.k.w, q.v.w, q.t1.y, P, valid)};
+    uint32_t pt[4];
+    long long ts[4];
+    quad_part_ts(q, pt, ts);
+    Rec r[4] = {make_rec(pt[0], q.k.x, q.v.x, ts[0], P, valid & 1u),
+                make_rec(pt[1], q.k.y, q.v.y, ts[1], P, (valid >> 1) & 1u),
+                make_rec(pt[2], q.k.z, q.v.z, ts[2], P, (valid >> 2) & 1u),
+                make_rec(pt[3], q.k.w, q.v.w, ts[3], P, (valid >> 3) & 1u)};
 #pragma unroll
-    for (int j = 0; j < 4; j++) lane_extrema(r[j], valid, st);
+    for (int j = 0; j < 4; j++) lane_extrema(r[j], (valid >> j) & 1u, st);
     if (VARIANT == 9) {
         st.smax = max(st.smax, r[0].part + r[1].part + r[2].part + r[3].part); // keep the loads alive
         return;
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) lds_histograms<ANALYTICS>(r[j], L);
-    const bool uniform = r[0].ok && r[0].part == r[1].part && r[0].part == r[2].part && r[0].part == r[3].part;
+    const bool uniform = r[0].ok && r[1].ok && r[2].ok && r[3].ok && r[0].part == r[1].part && r[0].part == r[2].part &&
+                         r[0].part == r[3].part;
     if (uniform) {
         const uint32_t slot = (r[0].part << rep_log2) | rep;
         const uint32_t tombs = r[0].tomb + r[1].tomb + r[2].tomb + r[3].tomb;
@@ -226,7 +295,7 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, bool valid, uint3
 // log2 histograms of key and value sizes and per-partition timestamp / message-size extrema, kept
 // in additional LDS arrays (extrema as signed-max arrays of [~ts, ts, ~size, size], histograms as
 // u32 counters replicated 16x by lane) and flushed with the counters.
-template <int VARIANT, bool NT, bool ANALYTICS>
+template <int VARIANT, bool NT, bool ANALYTICS, bool TILED>
 __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t n, uint32_t P,
                                                         uint32_t rep_log2,
                                                         uint64_t *__restrict__ partials,
@@ -312,36 +381,61 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
         __syncthreads();
     };
 
-    const uint64_t nquads = n >> 2;
-    const uint64_t ntiles = (nquads + kWG - 1) / kWG;
-    uint64_t tile = blockIdx.x;
     uint32_t since_flush = 0;
-
     Quad cur, nxt;
-    uint64_t qi = tile * kWG + tid;
-    bool cur_valid = (tile < ntiles) && (qi < nquads);
-    if (cur_valid) load_quad<NT>(cur, c, qi);
+    if (TILED) {
+        // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
+        const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
+        const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+        uint64_t tile = blockIdx.x;
+        if (tile < ntiles) load_tile_quad<NT>(cur, c, t0 + tile, tid);
+        while (tile < ntiles) { // uniform per workgroup
+            const uint64_t ntile = tile + gridDim.x;
+            if (ntile < ntiles) load_tile_quad<NT>(nxt, c, t0 + ntile, tid);
 
-    while (tile < ntiles) { // uniform per workgroup
-        const uint64_t ntile = tile + gridDim.x;
-        const uint64_t nqi = ntile * kWG + tid;
-        const bool nxt_valid = (ntile < ntiles) && (nqi < nquads);
-        if (nxt_valid) load_quad<NT>(nxt, c, nqi);
+            const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
+            uint32_t valid = 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+            accumulate_quad<VARIANT, ANALYTICS>(cur, valid, P, rep_log2, rep, L, st);
 
-        accumulate_quad<VARIANT, ANALYTICS>(cur, cur_valid, P, rep_log2, rep, L, st);
-
-        if (++since_flush == kFlushTiles) {
-            flush();
-            since_flush = 0;
+            if (++since_flush == kFlushTiles) {
+                flush();
+                since_flush = 0;
+            }
+            cur = nxt;
+            tile = ntile;
         }
-        cur = nxt;
-        cur_valid = nxt_valid;
-        tile = ntile;
+    } else {
+        const uint64_t nquads = n >> 2;
+        const uint64_t ntiles = (nquads + kWG - 1) / kWG;
+        uint64_t tile = blockIdx.x;
+
+        uint64_t qi = tile * kWG + tid;
+        bool cur_valid = (tile < ntiles) && (qi < nquads);
+        if (cur_valid) load_quad<NT>(cur, c, qi);
+
+        while (tile < ntiles) { // uniform per workgroup
+            const uint64_t ntile = tile + gridDim.x;
+            const uint64_t nqi = ntile * kWG + tid;
+            const bool nxt_valid = (ntile < ntiles) && (nqi < nquads);
+            if (nxt_valid) load_quad<NT>(nxt, c, nqi);
+
+            accumulate_quad<VARIANT, ANALYTICS>(cur, cur_valid ? 0xFu : 0u, P, rep_log2, rep, L, st);
+
+            if (++since_flush == kFlushTiles) {
+                flush();
+                since_flush = 0;
+            }
+            cur = nxt;
+            cur_valid = nxt_valid;
+            tile = ntile;
+        }
     }
 
-    // tail: the last n % 4 records, scalar, by the first lanes of workgroup 0
-    if (blockIdx.x == 0) {
-        const uint64_t i = (nquads << 2) + tid;
+    // tail (raw layout): the last n % 4 records, scalar, by the first lanes of workgroup 0
+    if (!TILED && blockIdx.x == 0) {
+        const uint64_t i = ((n >> 2) << 2) + tid;
         const bool v = (tid < 3) && (i < n);
         const uint64_t ii = v ? i : 0;
         if (tid < 64) {
@@ -480,6 +574,39 @@ __global__ __launch_bounds__(kWG) void kta_fold_partials(const uint64_t *__restr
             for (uint32_t r = r0; r < r1; r++) s += partials[(uint64_t)r * row_len + col];
             if (s) atomicAdd(&g[0], s);
         }
+    }
+}
+
+// launch_tiles_to_raw: one workgroup per tile, grid-strided over the allocation tiles that overlap [lo, hi).  A compact
+// tile wholly inside the range only changes its header (the producer that follows overwrites all of its records); one
+// the range cuts is expanded in place — every lane reads its 4 records before any lane writes, the compact halves
+// overlap the raw positions.
+__global__ __launch_bounds__(kWG) void kta_tiles_to_raw(int32_t *__restrict__ partition, int64_t *__restrict__ ts_ms,
+                                                        kta_tile_hdr *__restrict__ hdr, uint64_t lo, uint64_t hi)
+{
+    const uint64_t t0 = lo / KTA_TILE_RECORDS, t1 = (hi + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t T = t0 + blockIdx.x; T < t1; T += gridDim.x) {
+        if (hdr[T].mode != KTA_TILE_COMPACT) continue;   // (uniform)
+        const uint64_t first = T * KTA_TILE_RECORDS;
+        if (first < lo || first + KTA_TILE_RECORDS > hi) {
+            int32_t p[4];
+            long long t[4];
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) tile_record<false>(partition, ts_ms, hdr, first + 4u * tid + j, p[j], t[j]);
+            __syncthreads();
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                partition[first + 4u * tid + j] = p[j];
+                ts_ms[first + 4u * tid + j] = t[j];
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            hdr[T].ts_base = 0;
+            hdr[T].mode = KTA_TILE_RAW;
+        }
+        __syncthreads();
     }
 }
 
@@ -865,7 +992,7 @@ __global__ __launch_bounds__(kWG) void kta_alive_bitmap(const unsigned long long
 // launch wrappers
 // ---------------------------------------------------------------------------------------
 
-ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics)
+ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics, bool tiled)
 {
     ScanPlan pl;
     // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads
@@ -877,18 +1004,28 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
     const uint32_t hist_bytes = analytics ? 2u * kHistBuckets * kHistReps * 4u : 0u;
     // LDS budget per workgroup: 32 KiB (4 workgroups = 16 waves per CU can be resident); the
     // analytics kernel carries 7 arrays and gets 64 KiB (2 workgroups per CU) to keep the replication.
-    const uint32_t budget_slots = ((analytics ? 64u : 32u) * 1024u - hist_bytes) / (8u * arrays);
+    // Tile-compact analytics: 48 KiB, so that 3 workgroups per CU are resident (2^30 records of config 4: 4.89 ms with
+    // 64 KiB and 2 per CU, 3.33 with 48 KiB, 3.34 with 40, 3.62 with 32 KiB and 5 per CU).
+    const uint32_t budget_kib = analytics ? (tiled ? 48u : 64u) : 32u;
+    const uint32_t budget_slots = (budget_kib * 1024u - hist_bytes) / (8u * arrays);
     uint32_t rep_log2 = 0;
     while (rep_log2 < 6 && (P << (rep_log2 + 1)) <= budget_slots) rep_log2++;
     pl.rep_log2 = rep_log2;
     pl.lds_bytes = (P << rep_log2) * 8u * arrays + hist_bytes;
     pl.row_len = scan_row_len(P, analytics);
     const uint64_t ntiles = ((n >> 2) + kWG - 1) / kWG;
-    // 3 workgroups (12 waves) per CU saturate HBM (measured: 2-3 per CU best, more is slower), and
+    // Raw layout: 3 workgroups (12 waves) per CU saturate HBM (measured: 2-3 per CU best, more is slower), and
     // every workgroup is resident at once, so the static round-robin tile deal stays balanced.
     // (a workgroup needing more than 40 KiB of LDS only fits twice per CU: use 2 per CU then)
-    uint64_t wgs = req_workgroups > 0 ? (uint64_t)req_workgroups
-                                      : (uint64_t)cu_count * (pl.lds_bytes > 40u * 1024u ? 2u : 3u);
+    // Tile-compact layout: a lane has 56 B of a tile in flight instead of 80, and 3 per CU leave HBM short of
+    // requests (2^30 records of config 4: 2.85 ms at 3 per CU, 2.44 at 4, 2.32 at 5, 2.66 at 6, 2.96 at 7) — 5 per
+    // CU, as far as the LDS of 160 KiB per CU lets them all be resident.
+    uint32_t per_cu = pl.lds_bytes > 40u * 1024u ? 2u : 3u;
+    if (tiled) {
+        const uint32_t fit = (160u * 1024u) / (pl.lds_bytes + 256u);
+        per_cu = fit < 5u ? (fit > 0u ? fit : 1u) : 5u;
+    }
+    uint64_t wgs = req_workgroups > 0 ? (uint64_t)req_workgroups : (uint64_t)cu_count * per_cu;
     if (wgs > ntiles) wgs = ntiles;
     if (wgs < 1) wgs = 1;
     pl.workgroups = (uint32_t)wgs;
@@ -900,15 +1037,20 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
 {
     dim3 grid(pl.workgroups), block(kWG);
     // > 64 KiB of dynamic LDS (P > ~2700) must be opted into per kernel
-#define KTA_SCAN(V, NT, AN)                                                                                     \
-    do {                                                                                                        \
-        if (pl.lds_bytes > 48u * 1024u) {                                                                       \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan<V, NT, AN>),   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);  \
-            if (ea != hipSuccess) return ea;                                                                    \
-        }                                                                                                       \
-        hipLaunchKernelGGL((kta_metrics_scan<V, NT, AN>), grid, block, pl.lds_bytes, s, c, n, P, pl.rep_log2,   \
-                           partials, pl.row_len);                                                               \
+#define KTA_SCAN_T(V, NT, AN, TL)                                                                                   \
+    do {                                                                                                            \
+        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan<V, NT, AN, TL>),   \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);      \
+            if (ea != hipSuccess) return ea;                                                                        \
+        }                                                                                                           \
+        hipLaunchKernelGGL((kta_metrics_scan<V, NT, AN, TL>), grid, block, pl.lds_bytes, s, c, n, P, pl.rep_log2,   \
+                           partials, pl.row_len);                                                                   \
+    } while (0)
+#define KTA_SCAN(V, NT, AN)                                  \
+    do {                                                     \
+        if (c.hdr) KTA_SCAN_T(V, NT, AN, true);              \
+        else KTA_SCAN_T(V, NT, AN, false);                   \
     } while (0)
     if (pl.analytics) {
         KTA_SCAN(0, true, true);
@@ -919,6 +1061,7 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
     default: if (pl.nontemporal) KTA_SCAN(0, true, false); else KTA_SCAN(0, false, false); break;
     }
 #undef KTA_SCAN
+#undef KTA_SCAN_T
     return hipGetLastError();
 }
 
@@ -928,6 +1071,15 @@ hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_
     uint32_t slices = rows < 32 ? rows : 32;
     dim3 grid((row_len + kWG - 1) / kWG, slices), block(kWG);
     hipLaunchKernelGGL(kta_fold_partials, grid, block, 0, s, partials, rows, P, vec, row_len, avec);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, kta_tile_hdr *hdr, uint64_t lo, uint64_t hi, hipStream_t s)
+{
+    if (lo >= hi) return hipSuccess;
+    const uint64_t tiles = (hi + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - lo / KTA_TILE_RECORDS;
+    const uint32_t grid = (uint32_t)(tiles < 8192 ? tiles : 8192);
+    hipLaunchKernelGGL(kta_tiles_to_raw, dim3(grid), dim3(kWG), 0, s, partition, ts_ms, hdr, lo, hi);
     return hipGetLastError();
 }
 

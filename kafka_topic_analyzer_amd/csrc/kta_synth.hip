@@ -4,6 +4,7 @@
 #include "../../include/kta_synth.h"
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <string.h>
 
 #include <string>
@@ -11,6 +12,9 @@
 hipStream_t kta_internal_stream(kta_ctx *ctx);
 int kta_internal_device(kta_ctx *ctx);
 void kta_internal_set_error(kta_ctx *ctx, const char *msg);
+int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
+                         uint64_t *rec0);
 
 namespace {
 
@@ -32,6 +36,77 @@ __global__ __launch_bounds__(kWG) void synth_fill_cols(kta_synth_spec sp, uint64
         vlen[i] = vl;
         ts[i] = t;
         if (seq) seq[i] = first + i;
+    }
+}
+
+// The tile-compact layout (kta_hip.h): one workgroup per tile, 4 records per lane.  The lengths (and seq) go to the
+// batch's own columns (klen[i]); partition and timestamp are reduced over the tile first — does every id fit a u16, do
+// the timestamps span less than 2^31 ms — and then stored compact or raw into the allocation's tile t0 + T (part, ts),
+// with its header.  One pass, as the raw fill.
+__global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint64_t first, uint64_t n, int32_t *part,
+                                                        int32_t *klen, int32_t *vlen, int64_t *ts, uint64_t *seq,
+                                                        kta_tile_hdr *hdr, uint64_t t0)
+{
+    __shared__ long long s_red[kWG / 64][3];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t ntiles = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
+    for (uint64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
+        int32_t p[4];
+        int64_t t[4];
+        long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint64_t i = T * KTA_TILE_RECORDS + 4u * tid + j;
+            p[j] = -1;
+            t[j] = -1;
+            if (i >= n) continue;
+            int32_t kl, vl;
+            kta_synth_record(&sp, first + i, &p[j], &kl, &vl, &t[j]);
+            klen[i] = kl;
+            vlen[i] = vl;
+            if (seq) seq[i] = first + i;
+            wide |= (p[j] < -1 || p[j] >= (int32_t)KTA_COMPACT_PART_NONE) ? 1 : 0;
+            if (t[j] != -1) {
+                lo = t[j] < lo ? t[j] : lo;
+                hi = t[j] > hi ? t[j] : hi;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const long long a = __shfl_xor(lo, off), b = __shfl_xor(hi, off), c = __shfl_xor(wide, off);
+            lo = a < lo ? a : lo;
+            hi = b > hi ? b : hi;
+            wide |= c;
+        }
+        if ((tid & 63u) == 0u) {
+            s_red[tid >> 6][0] = lo;
+            s_red[tid >> 6][1] = hi;
+            s_red[tid >> 6][2] = wide;
+        }
+        __syncthreads();
+        for (uint32_t w = 0; w < kWG / 64; w++) {
+            lo = s_red[w][0] < lo ? s_red[w][0] : lo;
+            hi = s_red[w][1] > hi ? s_red[w][1] : hi;
+            wide |= s_red[w][2];
+        }
+        __syncthreads();   // (s_red is reused by the next tile)
+        const bool compact = !wide && (lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX);
+        const long long base = lo <= hi ? lo : 0;
+        const uint64_t A = (t0 + T) * KTA_TILE_RECORDS;   // the tile's first record in the allocation
+        if (compact) {
+            uint16_t u[4];
+            int32_t o[4];
+            for (uint32_t j = 0; j < 4; j++) {
+                u[j] = p[j] == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p[j];
+                o[j] = t[j] == -1 ? KTA_COMPACT_TS_NONE : (int32_t)((uint64_t)t[j] - (uint64_t)base);
+            }
+            reinterpret_cast<uint2 *>(part)[(2 * A) / 4 + tid] =
+                make_uint2((uint32_t)u[0] | ((uint32_t)u[1] << 16), (uint32_t)u[2] | ((uint32_t)u[3] << 16));
+            reinterpret_cast<int4 *>(ts)[(2 * A) / 4 + tid] = make_int4(o[0], o[1], o[2], o[3]);
+        } else {
+            reinterpret_cast<int4 *>(part)[A / 4 + tid] = make_int4(p[0], p[1], p[2], p[3]);
+            reinterpret_cast<longlong2 *>(ts)[A / 2 + 2 * tid] = make_longlong2(t[0], t[1]);
+            reinterpret_cast<longlong2 *>(ts)[A / 2 + 2 * tid + 1] = make_longlong2(t[2], t[3]);
+        }
+        if (tid == 0) hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, 0u};
     }
 }
 
@@ -211,7 +286,22 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
         }                                          \
     } while (0)
     const uint32_t grid = (uint32_t)((n + kWG - 1) / kWG < 8192 ? (n + kWG - 1) / kWG : 8192);
-    if (e == hipSuccess) {
+    // a tile-compact batch from a tile boundary takes the compact fill; anything else the raw one (its tiles made raw first)
+    int32_t *apart = nullptr;
+    int64_t *ats = nullptr;
+    kta_tile_hdr *ahdr = nullptr;
+    uint64_t rec0 = 0;
+    if (int rc = kta_internal_resolve(ctx, b, &apart, &ats, &ahdr, &rec0)) return rc;
+    if (ahdr && rec0 % KTA_TILE_RECORDS != 0) {
+        if (int rc = kta_internal_prepare_raw(ctx, b, n)) return rc;
+        ahdr = nullptr;
+    }
+    if (e == hipSuccess && ahdr) {
+        const uint64_t nt = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
+        hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, apart,
+                           b->key_len, b->val_len, ats, b->seq, ahdr, rec0 / KTA_TILE_RECORDS);
+        SY(hipGetLastError());
+    } else if (e == hipSuccess) {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);
         SY(hipGetLastError());
