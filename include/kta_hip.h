@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -131,6 +131,21 @@ typedef struct kta_analytics {
     uint64_t key_size_hist[KTA_HIST_BUCKETS];
     uint64_t value_size_hist[KTA_HIST_BUCKETS];
 } kta_analytics;
+
+/* Timeline (NOT in the reference, never printed by the reference report; kta_set_timeline): records, tombstones
+ * and bytes per time bucket, accumulated by the same scan in LDS.  Configured by origin_ms >= 0, bucket_ms >= 1
+ * and 1 <= n_buckets <= KTA_TIMELINE_MAX_BUCKETS, with origin_ms + n_buckets * bucket_ms within int64.  Every
+ * record the scan counts (partition in [0, P); the others only go to bad_partition_records) falls into exactly
+ * one row:
+ *   row 0             "no timestamp"  ts_ms < 0 (a raw -1)
+ *   row 1             "before"        0 <= ts_ms < origin_ms
+ *   row 2 + k         bucket k        origin_ms + k * bucket_ms <= ts_ms < origin_ms + (k + 1) * bucket_ms
+ *   row n_buckets + 2 "after"         ts_ms >= origin_ms + n_buckets * bucket_ms
+ * Each row holds KTA_TIMELINE_COLS u64 columns: records, tombstones (val_len == -1), bytes (max(key_len, 0) +
+ * max(val_len, 0), the report's P-Bytes summand).  The vector is u64[(n_buckets + 3) * KTA_TIMELINE_COLS],
+ * row-major; every word is a SUM, so the vectors of disjoint record sets add element-wise. */
+#define KTA_TIMELINE_MAX_BUCKETS 1024
+#define KTA_TIMELINE_COLS 3
 
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
@@ -319,10 +334,13 @@ int kta_finish_device(kta_ctx *ctx);
  *                       With KTA_FLAG_ANALYTICS the same grouped launch also reduces the analytics snapshot:
  *                       all-reduce SUM (u64) over its 2 x 34 histogram words and all-reduce MAX (i64) over its
  *                       4 * P extrema words (neutral element INT64_MIN: a partition's owner wins).
+ *                       With a timeline (kta_set_timeline) the same grouped launch also reduces the timeline
+ *                       snapshot: all-reduce SUM (u64) over all of its words.
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
- *                       (kta_exchange_analytics: the same for the analytics)
- * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS bit: the collectives
- * of a rank with analytics do not match those of a rank without.
+ *                       (kta_exchange_analytics, kta_exchange_timeline: the same for the analytics, the timeline)
+ * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS bit, and be given the same
+ * timeline configuration (or none on every rank): the collectives of a rank with analytics or a timeline do not
+ * match those of a rank without, and nothing checks that the configurations agree.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
 #define KTA_COMM_ID_BYTES 128
 int kta_comm_unique_id(uint8_t id[KTA_COMM_ID_BYTES]);
@@ -371,6 +389,29 @@ int kta_merge_analytics(uint64_t *acc, const uint64_t *other, uint32_t n_partiti
 /* The largest P a KTA_FLAG_ANALYTICS context may have: the analytics scan's LDS plan (7 u64 per partition slot plus
  * the histograms) must fit one workgroup's 160 KiB of LDS on gfx950.  kta_create refuses more. */
 int kta_analytics_max_partitions(void);
+
+/* Give the context a timeline (definition above KTA_TIMELINE_MAX_BUCKETS), zeroed.  Accepted only while the context
+ * has been handed no record since kta_create / kta_reset (kta_reset zeroes the timeline and keeps its
+ * configuration); may be called again then to change it.  KTA_ERR_INVALID, with a kta_last_error message and
+ * nothing launched, for a value out of range, after a batch, or when the scan's LDS plan with the timeline does not
+ * fit one workgroup (with KTA_FLAG_ANALYTICS and a large P: kta_timeline_max_partitions).  With -c, a batch of a
+ * context with a timeline takes two passes (scan, then the alive-key pass), as with analytics.
+ * Every timeline call below on a context without a timeline returns KTA_ERR_INVALID. */
+int kta_set_timeline(kta_ctx *ctx, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets);
+/* The largest P a context created with `flags` may have for a timeline of n_buckets buckets (host only; 0 for an
+ * n_buckets out of range).  Never more than kta_analytics_max_partitions() with KTA_FLAG_ANALYTICS. */
+int kta_timeline_max_partitions(uint32_t flags, uint32_t n_buckets);
+/* The live accumulator, copied to out[n_u64] (n_u64 = (n_buckets + 3) * KTA_TIMELINE_COLS; staged messages are
+ * flushed first). */
+int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of the live accumulator. */
+int kta_timeline_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes of the timeline, copied to out[n_u64]: after
+ * kta_exchange the whole job's timeline on every rank.  The live accumulator is never reduced, so further batches
+ * and a second exchange do not count anything twice. */
+int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
 
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
@@ -424,6 +465,16 @@ int kta_render_report(const char *topic, uint64_t duration_secs, const uint64_t 
  * Smallest | Largest: times in seconds as the report's Earliest Message, `-` for a partition without records /
  * without non-tombstones) and a closing `=` rule.  Output buffer conventions as kta_render_report. */
 int kta_render_analytics(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
+
+/* The opt-in timeline section that kta-analyzer prints after the reference report (and after the analytics section)
+ * with --librdkafka kta.timeline=<width>, from a timeline vector u64[(n_buckets + 3) * 3] (host only, no device):
+ * a title line saying that it is not part of the reference report with the width and the start, a table
+ * (From | Records | Records % | Tmb | Bytes) whose rows "No timestamp", "Before <start>" and "After <end>" are always
+ * printed and whose bucket rows, labelled with their start (format of the report's Earliest Message), run from the
+ * first to the last non-empty bucket; percentages of all timeline records, %.2f; then a closing `=` rule.
+ * Output buffer conventions as kta_render_report. */
+int kta_render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets, char *out,
+                        size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

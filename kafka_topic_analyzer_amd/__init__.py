@@ -25,7 +25,8 @@ from ._native import KtaBatch, KtaConfig, KtaResult, KtaSynthSpec  # noqa: F401
 
 __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics", "Message", "KtaError",
            "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats",
-           "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions"]
+           "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions", "render_timeline",
+           "timeline_max_partitions"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -72,10 +73,11 @@ class HipMetricHandler:
     def __init__(self, n_partitions: int, count_alive_keys: bool = False, device: int = 0,
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
-                 seq_column: bool = False):
+                 seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
-        seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN)."""
+        seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
+        timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline)."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -86,6 +88,13 @@ class HipMetricHandler:
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
             raise KtaError(rc, self._lib.kta_last_error(None).decode())
+        self.timeline_config = None
+        if timeline is not None:
+            try:
+                self.set_timeline(*timeline)
+            except KtaError:
+                self.close()
+                raise
         if now is None:  # Utc::now() at MessageMetrics::new (metric.rs:39)
             t = time.time_ns()
             now = (t // 1_000_000_000, t % 1_000_000_000)
@@ -362,6 +371,38 @@ class HipMetricHandler:
         self._check(self._lib.kta_analytics_result_vector(self._ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def set_timeline(self, origin_ms: int, bucket_ms: int, n_buckets: int) -> None:
+        """kta_set_timeline: only before the context has been handed any record (since creation / reset())."""
+        self._check(self._lib.kta_set_timeline(self._ctx, int(origin_ms), int(bucket_ms), int(n_buckets)))
+        self.timeline_config = (int(origin_ms), int(bucket_ms), int(n_buckets))
+
+    def _timeline(self, fn) -> np.ndarray:
+        n = (self.timeline_config[2] + 3) * N.KTA_TIMELINE_COLS if self.timeline_config else 0
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), n))
+        return out.reshape(-1, N.KTA_TIMELINE_COLS)
+
+    def timeline(self) -> np.ndarray:
+        """The live timeline, np.uint64[n_buckets + 3, 3]: rows [no timestamp, before, buckets..., after] of
+        [records, tombstones, bytes] (kta_get_timeline; staged messages are flushed first)."""
+        return self._timeline(self._lib.kta_get_timeline)
+
+    def exchange_timeline(self) -> np.ndarray:
+        """As timeline(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._timeline(self._lib.kta_exchange_timeline)
+
+    def timeline_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live timeline."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.kta_timeline_vector(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def timeline_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the timeline snapshot (for collectives: allreduce_timeline_vector)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.kta_timeline_result_vector(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
         ps, pv, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
@@ -568,6 +609,29 @@ def render_analytics(vec, n_partitions: int) -> str:
 def analytics_max_partitions() -> int:
     """The largest P a context with analytics may have (the analytics scan's LDS plan on gfx950)."""
     return int(N.load().kta_analytics_max_partitions())
+
+
+def render_timeline(vec, origin_ms: int, bucket_ms: int, n_buckets: int) -> str:
+    """kta_render_timeline: the section kta-analyzer prints after the report with --librdkafka kta.timeline=<width>,
+    from a timeline vector (u64[(n_buckets + 3) * 3], or its [n_buckets + 3, 3] shape)."""
+    v = np.ascontiguousarray(np.asarray(vec).reshape(-1)).view(np.uint64)
+    if v.size != (n_buckets + 3) * N.KTA_TIMELINE_COLS:
+        raise ValueError(f"a timeline of {n_buckets} buckets has {(n_buckets + 3) * N.KTA_TIMELINE_COLS} words, not {v.size}")
+    lib = N.load()
+    n = C.c_size_t()
+    rc = lib.kta_render_timeline(_np_ptr(v), origin_ms, bucket_ms, n_buckets, None, 0, C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_timeline")
+    buf = C.create_string_buffer(n.value + 1)
+    rc = lib.kta_render_timeline(_np_ptr(v), origin_ms, bucket_ms, n_buckets, buf, len(buf), C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_timeline")
+    return buf.value.decode()
+
+
+def timeline_max_partitions(n_buckets: int, analytics: bool = False) -> int:
+    """The largest P a context (with analytics or not) may have with a timeline of n_buckets buckets."""
+    return int(N.load().kta_timeline_max_partitions(N.KTA_FLAG_ANALYTICS if analytics else 0, n_buckets))
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

@@ -50,6 +50,8 @@ KTA_FLAG_SEQ_COLUMN = 2
 KTA_FLAG_ALIVE_TABLE = 4
 KTA_HIST_BUCKETS = 34
 KTA_ANALYTICS_HIST = 2 * KTA_HIST_BUCKETS   # analytics vector: u64[2*34 + 4*P]
+KTA_TIMELINE_MAX_BUCKETS = 1024             # timeline vector: u64[(n_buckets + 3) * KTA_TIMELINE_COLS]
+KTA_TIMELINE_COLS = 3
 
 
 class KtaAnalytics(C.Structure):
@@ -150,6 +152,14 @@ SIGNATURES = {
     "kta_merge_analytics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "kta_analytics_max_partitions": (C.c_int, []),
     "kta_render_analytics": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_set_timeline": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint32]),
+    "kta_timeline_max_partitions": (C.c_int, [C.c_uint32, C.c_uint32]),
+    "kta_get_timeline": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_timeline_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_exchange_timeline": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_timeline_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_render_timeline": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_char_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),
     "kta_alive_table": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "kta_alive_export_entries": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

@@ -17,7 +17,8 @@
 //                                        v2; uncompressed, gzip, Snappy, LZ4, zstd): file k is partition k; decoded ON THE GPU
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
-// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1), so no flag is added or renamed.
+// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>), so no flag is added
+// or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
 // visible devices), and replaces "the report reads the handlers" by ONE exchange step (kta_exchange: RCCL).
@@ -26,6 +27,10 @@
 // kta.analytics=1 (every source, kta.gpus=N included) accumulates the additive analytics as well (KTA_FLAG_ANALYTICS:
 // key / value size histograms, per-partition timestamp and size extrema; no reference counterpart) and prints them
 // in a section of their own AFTER the reference report, which stays byte for byte what it is without the knob.
+// kta.timeline=<width> (30s, 15m, 1h, 1d; a bare number is seconds; every source, kta.gpus=N included) accumulates a
+// timeline as well (kta_set_timeline: records, tombstones and bytes per time bucket; no reference counterpart):
+// kta.timeline.buckets=N buckets (default 168), from kta.timeline.start=<unix seconds> or else so that the last
+// bucket holds the run's start time.  Printed in a section of its own after the report (and the analytics).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,6 +50,33 @@
 #include "rdkafka_source.hpp"
 
 namespace {
+
+// kta.timeline=<width>: a positive number with an optional unit s, m, h or d (none: seconds) -> ms; 0 when malformed
+int64_t parse_timeline_width(const std::string &v)
+{
+    size_t i = 0;
+    while (i < v.size() && v[i] >= '0' && v[i] <= '9') i++;
+    if (i == 0 || i > 15) return 0;
+    const std::string unit = v.substr(i);
+    int64_t mult = 0;
+    if (unit.empty() || unit == "s") mult = 1000;
+    else if (unit == "m") mult = 60000;
+    else if (unit == "h") mult = 3600000;
+    else if (unit == "d") mult = 86400000;
+    else return 0;
+    const int64_t n = strtoll(v.substr(0, i).c_str(), nullptr, 10);
+    if (n <= 0 || n > INT64_MAX / mult) return 0;
+    return n * mult;
+}
+
+// a non-negative decimal integer of at most `digits` digits, else -1
+int64_t parse_decimal(const std::string &v, size_t digits)
+{
+    if (v.empty() || v.size() > digits) return -1;
+    for (char ch : v)
+        if (ch < '0' || ch > '9') return -1;
+    return strtoll(v.c_str(), nullptr, 10);
+}
 
 const char *kAbout = "Kafka Topic Analyzer 0.4.1";
 
@@ -167,6 +199,7 @@ struct ShardedJob {
     kta_synth_spec spec{};
     bool oversubscribe = false;                        // kta.oversubscribe=1: several ranks may share a device (test doubles of RCCL)
     bool analytics = false;                            // kta.analytics=1: every rank's context, exchanged with the counters
+    kta::TimelineConfig timeline;                      // kta.timeline=<width>: derived once, the same on every rank
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -182,7 +215,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u);
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
-                                                             job.batch, 0, flags);
+                                                             job.batch, 0, flags, job.timeline);
         kta_ctx *ctx = h->ctx();
         h->comm_create(job.nranks, rank, uid);
         if (job.synthetic) {
@@ -304,6 +337,9 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         std::string text = kta::render_report(job.topic, duration_secs, metrics, h0->log_compaction(), partitions,
                                               job.start_offsets, job.end_offsets);
         if (job.analytics) text += kta::render_analytics(*h0->analytics());   // the exchanged snapshot, printed once
+        if (job.timeline.n_buckets)
+            text += kta::render_timeline(h0->timeline()->data(), job.timeline.origin_ms, job.timeline.bucket_ms,
+                                         job.timeline.n_buckets);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -395,6 +431,51 @@ int main(int argc, char **argv)
                         "(its per-partition extrema live in LDS)\n", P, kta_analytics_max_partitions());
         return 2;
     }
+    kta::TimelineConfig timeline;   // kta.timeline=<width>: refused here, before any context, when it cannot be had
+    if (cfg.count("kta.timeline")) {
+        const std::string &wv = cfg["kta.timeline"];
+        const int64_t width = parse_timeline_width(wv);
+        if (width == 0) {
+            fprintf(stderr, "kta.timeline=%s: expected a bucket width such as 30s, 15m, 1h or 1d (a bare number is seconds)\n",
+                    wv.c_str());
+            return 2;
+        }
+        int64_t n = 168;
+        if (cfg.count("kta.timeline.buckets")) {
+            n = parse_decimal(cfg["kta.timeline.buckets"], 5);
+            if (n < 1 || n > KTA_TIMELINE_MAX_BUCKETS) {
+                fprintf(stderr, "kta.timeline.buckets=%s: expected a bucket count in [1, %d]\n",
+                        cfg["kta.timeline.buckets"].c_str(), KTA_TIMELINE_MAX_BUCKETS);
+                return 2;
+            }
+        }
+        int64_t origin = 0;
+        if (cfg.count("kta.timeline.start")) {
+            const int64_t sec = parse_decimal(cfg["kta.timeline.start"], 15);
+            if (sec < 0) {
+                fprintf(stderr, "kta.timeline.start=%s: expected unix seconds >= 0\n", cfg["kta.timeline.start"].c_str());
+                return 2;
+            }
+            origin = sec * 1000;
+        } else {   // the last bucket holds the run's start time
+            const int64_t now_ms = (int64_t)std::chrono::duration_cast<std::chrono::milliseconds>(
+                                       std::chrono::system_clock::now().time_since_epoch()).count();
+            origin = std::max<int64_t>(0, (now_ms / width - (n - 1)) * width);
+        }
+        if (width > (INT64_MAX - origin) / n) {
+            fprintf(stderr, "kta.timeline=%s: %lld buckets from %lld ms overflow the int64 millisecond range\n", wv.c_str(),
+                    (long long)n, (long long)origin);
+            return 2;
+        }
+        const int pmax = kta_timeline_max_partitions(analytics ? KTA_FLAG_ANALYTICS : 0u, (uint32_t)n);
+        if (P > (uint32_t)pmax) {
+            fprintf(stderr, "kta.timeline=%s: the topic has %u partitions, the scan with %lld timeline buckets%s admits at "
+                            "most %d (its rows live in LDS)\n", wv.c_str(), P, (long long)n,
+                    analytics ? " and the analytics" : "", pmax);
+            return 2;
+        }
+        timeline = kta::TimelineConfig{origin, width, (uint32_t)n};
+    }
 
     // librdkafka options are forwarded as in the reference (kafka.rs:38-42); the one this build can
     // honour for raw segments is check.crcs (default false): verify every batch's CRC-32C on the GPU
@@ -466,6 +547,7 @@ int main(int argc, char **argv)
         job.nranks = gpus;
         job.oversubscribe = oversubscribe;
         job.analytics = analytics;
+        job.timeline = timeline;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -481,7 +563,8 @@ int main(int argc, char **argv)
     // -c means a 32 GiB table)
     kta::HipMetricHandler *handler = nullptr;
     try {
-        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0, analytics ? KTA_FLAG_ANALYTICS : 0u);
+        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0, analytics ? KTA_FLAG_ANALYTICS : 0u,
+                                            timeline);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
         return 2;
@@ -654,6 +737,8 @@ int main(int argc, char **argv)
         std::string text = kta::render_report(args.topic, duration_secs, metrics, handler->log_compaction(),
                                               partitions, start_offsets, end_offsets);
         if (analytics) text += kta::render_analytics(*handler->analytics());
+        if (timeline.n_buckets)
+            text += kta::render_timeline(handler->timeline()->data(), timeline.origin_ms, timeline.bucket_ms, timeline.n_buckets);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -70,8 +70,8 @@ uint64_t MessageMetrics::smallest_message() const
 }
 
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
-                                   uint64_t key_bytes_capacity, uint32_t flags)
-    : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0)
+                                   uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline)
+    : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -85,6 +85,15 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
     cfg.flags = flags;
     int rc = kta_create(&cfg, &ctx_);
     if (rc != KTA_OK) throw std::runtime_error(std::string("kta_create failed: ") + kta_last_error(nullptr));
+    if (timeline_.n_buckets) {
+        rc = kta_set_timeline(ctx_, timeline_.origin_ms, timeline_.bucket_ms, timeline_.n_buckets);
+        if (rc != KTA_OK) {
+            const std::string msg = std::string("kta_set_timeline failed: ") + kta_last_error(ctx_);
+            kta_destroy(ctx_);
+            ctx_ = nullptr;
+            throw std::runtime_error(msg);
+        }
+    }
 }
 
 HipMetricHandler::~HipMetricHandler() { kta_destroy(ctx_); }
@@ -146,6 +155,10 @@ void HipMetricHandler::exchange(bool tolerate_undelivered)
 
 void HipMetricHandler::read_analytics()
 {
+    if (timeline_.n_buckets) {
+        tvec_.assign((size_t)(timeline_.n_buckets + 3) * KTA_TIMELINE_COLS, 0);
+        check(kta_exchange_timeline(ctx_, tvec_.data(), tvec_.size()), "kta_exchange_timeline");
+    }
     if (!analytics_on_) return;
     Analytics &a = analytics_;
     a.min_ts_sec.assign((size_t)P_, 0);

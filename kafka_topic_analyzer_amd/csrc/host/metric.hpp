@@ -87,6 +87,12 @@ struct Analytics {
     uint64_t records() const;                         // every record lands in exactly one key-size bucket
 };
 
+// The timeline's configuration (kta_set_timeline; no reference counterpart).
+struct TimelineConfig {
+    int64_t origin_ms = 0, bucket_ms = 0;
+    uint32_t n_buckets = 0;     // 0: no timeline
+};
+
 class LogCompactionInMemoryMetrics {  // metric.rs:262-285
 public:
     LogCompactionInMemoryMetrics() {}
@@ -102,7 +108,7 @@ private:
 class HipMetricHandler : public MetricHandler {
 public:
     HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device = 0, uint64_t batch_capacity = 0,
-                     uint64_t key_bytes_capacity = 0, uint32_t flags = 0);
+                     uint64_t key_bytes_capacity = 0, uint32_t flags = 0, const TimelineConfig &timeline = TimelineConfig{});
     ~HipMetricHandler() override;
     HipMetricHandler(const HipMetricHandler &) = delete;
     HipMetricHandler &operator=(const HipMetricHandler &) = delete;
@@ -121,6 +127,10 @@ public:
     // With KTA_FLAG_ANALYTICS: the analytics of the snapshot finish() / exchange() took (after exchange(), the whole
     // job's); nullptr without the flag.
     const Analytics *analytics() const { return analytics_on_ ? &analytics_ : nullptr; }
+    // With a timeline: the vector u64[(n_buckets + 3) * 3] of the snapshot finish() / exchange() took (after
+    // exchange(), the whole job's); nullptr without one.
+    const std::vector<uint64_t> *timeline() const { return timeline_.n_buckets ? &tvec_ : nullptr; }
+    const TimelineConfig &timeline_config() const { return timeline_; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -128,7 +138,7 @@ public:
 
 private:
     void check(int rc, const char *what);
-    void read_analytics();
+    void read_analytics();   // the analytics and the timeline of the snapshot
     kta_ctx *ctx_ = nullptr;
     int32_t P_;
     bool alive_;
@@ -138,6 +148,8 @@ private:
     uint64_t undelivered_ = 0;
     bool analytics_on_ = false;
     Analytics analytics_;
+    TimelineConfig timeline_;
+    std::vector<uint64_t> tvec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -150,5 +162,10 @@ std::string render_report(const std::string &topic, uint64_t duration_secs, cons
                           const std::vector<int64_t> &start_offsets, const std::vector<int64_t> &end_offsets);
 // the opt-in section kta-analyzer prints after the report with kta.analytics=1 (kta_render_analytics)
 std::string render_analytics(const Analytics &a);
+// the opt-in section kta-analyzer prints after the report (and the analytics) with kta.timeline=<width>
+// (kta_render_timeline)
+std::string render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets);
+// a timeline width as kta.timeline takes it (86400000 -> "1d", 90000 -> "90s", 7 -> "7ms")
+std::string format_width_ms(int64_t w);
 
 }  // namespace kta

@@ -170,7 +170,75 @@ std::string render_analytics(const Analytics &a)
     return o;
 }
 
+// A width in ms as kta.timeline takes it: the largest of d, h, m, s that divides it, else ms.
+std::string format_width_ms(int64_t w)
+{
+    static const struct { int64_t ms; const char *unit; } units[] = {{86400000, "d"}, {3600000, "h"}, {60000, "m"}, {1000, "s"}};
+    for (const auto &u : units)
+        if (w % u.ms == 0) return std::to_string(w / u.ms) + u.unit;
+    return std::to_string(w) + "ms";
+}
+
+static std::string format_ms_utc(int64_t ms)   // ms >= 0
+{
+    return format_datetime_utc(ms / 1000, (uint32_t)(ms % 1000) * 1000000u);
+}
+
+// The opt-in timeline section (kta.timeline=<width>): no reference counterpart, printed after the reference report's
+// closing rule (and after the analytics section).  vec: u64[(n_buckets + 3) * 3] (kta_hip.h).
+std::string render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets)
+{
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    const uint32_t rows_n = n_buckets + 3u;
+    uint64_t records = 0;
+    for (uint32_t r = 0; r < rows_n; r++) records += vec[(size_t)r * KTA_TIMELINE_COLS];
+    auto pct = [&](uint64_t count) {
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", records ? (double)count * 100.0 / (double)records : 0.0);
+        return std::string(buf);
+    };
+    const std::string start = format_ms_utc(origin_ms);
+    std::string o;
+    o += "Timeline, " + format_width_ms(bucket_ms) + " buckets from " + start +
+         " (kta.timeline; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"From", "Records", "Records %", "Tmb", "Bytes"});
+    auto row = [&](const std::string &label, uint32_t r) {
+        const uint64_t *x = vec + (size_t)r * KTA_TIMELINE_COLS;
+        rows.push_back({label, u(x[0]), pct(x[0]), u(x[1]), u(x[2])});
+    };
+    row("No timestamp", 0);
+    row("Before " + start, 1);
+    uint32_t first = n_buckets, last = 0;
+    for (uint32_t k = 0; k < n_buckets; k++)
+        if (vec[(size_t)(2 + k) * KTA_TIMELINE_COLS] != 0) {
+            first = std::min(first, k);
+            last = k;
+        }
+    for (uint32_t k = first; k < n_buckets && k <= last; k++) row(format_ms_utc(origin_ms + (int64_t)k * bucket_ms), 2 + k);
+    row("After " + format_ms_utc(origin_ms + (int64_t)n_buckets * bucket_ms), n_buckets + 2);
+    o += pretty_table(rows);
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets,
+                                   char *out, size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || origin_ms < 0 || bucket_ms < 1 || n_buckets < 1 || n_buckets > KTA_TIMELINE_MAX_BUCKETS ||
+        bucket_ms > (INT64_MAX - origin_ms) / (int64_t)n_buckets)
+        return KTA_ERR_INVALID;
+    const std::string text = kta::render_timeline(vec, origin_ms, bucket_ms, n_buckets);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_analytics(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap,
                                     size_t *out_len)

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <cstdlib>
 #include <string>
@@ -49,6 +50,11 @@ struct kta_ctx {
     bool stage_seq = false;         // KTA_FLAG_SEQ_COLUMN
     uint64_t *d_avec = nullptr;     // analytics vector u64[2*34 + 4*P] (KTA_FLAG_ANALYTICS)
     uint64_t *d_avec_out = nullptr; // its snapshot (kta_finish_device), reduced by the exchange like d_vec_out
+    // timeline (kta_set_timeline): d_tvec u64[(n_buckets + 3) * 3] the live accumulator, d_tvec_out its snapshot
+    bool timeline = false;
+    kta::TimelineArgs tl{};
+    uint64_t *d_tvec = nullptr, *d_tvec_out = nullptr;
+    bool handed_records = false;    // a record reached the context since kta_create / kta_reset (kta_set_timeline refuses)
     uint64_t *d_vec = nullptr;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     uint64_t *d_vec_out = nullptr;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -270,6 +276,8 @@ kta::WrittenList written_list(kta_ctx *ctx) { return kta::WrittenList{ctx->d_wri
 int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
 {
     if (n == 0) return KTA_OK;
+    const kta::TimelineArgs *tl = ctx->timeline ? &ctx->tl : nullptr;
+    const uint32_t tl_buckets = ctx->timeline ? ctx->tl.n_buckets : 0u;
     hipEvent_t a = nullptr, b = nullptr;
     // every refusal comes before the first launch: a batch is counted by both handlers or by neither
     if ((which & 2) && ctx->alive && (!c->key_len || !c->val_len || !c->key_off || !c->key_bytes))
@@ -295,9 +303,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     // Both handlers over one batch (what kafka.rs:107-109 does with every message): with at most 256 partitions, pass 1 of
     // the partitioned alive-key pass does the metrics handler's work as well (kta_alive.hip, FuseArgs) — the batch is read
     // once: 40 B + key per record instead of 20 + 28 in the bit set state, 48 B + key instead of 20 + 36 for a sharded
-    // rank's batch with its seq column (table state).
+    // rank's batch with its seq column (table state).  The fused pass has no LDS room for the analytics or the timeline.
     bool fuse = false;
-    if (which == 3 && ctx->alive && use_partitioned && !ctx->analytics && ctx->fuse_handlers) {
+    if (which == 3 && ctx->alive && use_partitioned && !ctx->analytics && !ctx->timeline && ctx->fuse_handlers) {
         const uint64_t first = n > kta::kAlivePartitionMax ? kta::kAlivePartitionMax : n;
         const kta::AlivePartitionPlan pl0 = kta::plan_alive_partition(first, ctx->alive_wgs, ctx->cu_count, !ctx->alive_table);
         fuse = kta::alive_fuse_possible(pl0, ctx->P) && pl0.segment_wgs <= ctx->max_rows;
@@ -323,14 +331,15 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     if ((which & 1) && !fuse) {
         const kta::ScanColumns sc = scan_cols(0);
         kta::ScanPlan pl = kta::plan_scan(ctx->P, n, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant,
-                                          ctx->analytics, sc.hdr != nullptr);
+                                          ctx->analytics, sc.hdr != nullptr, tl_buckets);
         if (pl.workgroups > ctx->max_rows) pl.workgroups = ctx->max_rows;
         if (ctx->timing) {
             int rc = timer_pair(ctx, 0, &a, &b);
             if (rc != KTA_OK) return rc;
             KTA_HIP(ctx, hipEventRecord(a, ctx->s_compute));
         }
-        KTA_HIP(ctx, kta::launch_metrics_scan(pl, sc, n, ctx->P, ctx->d_partials, ctx->s_compute));
+        ctx->handed_records = true;
+        KTA_HIP(ctx, kta::launch_metrics_scan(pl, sc, n, ctx->P, ctx->d_partials, ctx->s_compute, tl));
         if (ctx->timing) {
             KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
             int rc = timer_pair(ctx, 1, &a, &b);
@@ -411,6 +420,7 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                 ctx->info_slices++;
                 if (fuse && kta::alive_fuse_possible(pl, ctx->P) && pl.segment_wgs <= ctx->max_rows) {
                     ctx->info_fused++;
+                    ctx->handed_records = true;
                     const uint32_t row_len = kta::scan_row_len(ctx->P, false);
                     const kta::ScanColumns sc = scan_cols(at);
                     const kta::AliveFuse fz{sc.partition, sc.ts_ms, sc.hdr, sc.rec0, ctx->P, ctx->d_partials, row_len};
@@ -423,9 +433,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                         ctx->info_scanned++;
                         const kta::ScanColumns sc = scan_cols(at);
                         kta::ScanPlan spl = kta::plan_scan(ctx->P, take, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics,
-                                                           sc.hdr != nullptr);
+                                                           sc.hdr != nullptr, tl_buckets);
                         if (spl.workgroups > ctx->max_rows) spl.workgroups = ctx->max_rows;
-                        KTA_HIP(ctx, kta::launch_metrics_scan(spl, sc, take, ctx->P, ctx->d_partials, ctx->s_compute));
+                        KTA_HIP(ctx, kta::launch_metrics_scan(spl, sc, take, ctx->P, ctx->d_partials, ctx->s_compute, tl));
                         KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, spl.workgroups, ctx->P, ctx->d_vec, spl.row_len, ctx->d_avec,
                                                                ctx->s_compute));
                     }
@@ -458,6 +468,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
 int reset_state(kta_ctx *ctx)
 {
     KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec, ctx->P, ctx->d_avec, ctx->s_compute));
+    if (ctx->timeline)   // the configuration stays
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec, 0, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t), ctx->s_compute));
+    ctx->handed_records = false;
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_HIP(ctx, hipMemsetAsync(ctx->d_table, 0, kta::kAliveSlots * sizeof(uint64_t), ctx->s_compute));
@@ -605,6 +618,8 @@ void kta_destroy(kta_ctx *ctx)
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     if (ctx->d_avec) (void)hipFree(ctx->d_avec);
     if (ctx->d_avec_out) (void)hipFree(ctx->d_avec_out);
+    if (ctx->d_tvec) (void)hipFree(ctx->d_tvec);
+    if (ctx->d_tvec_out) (void)hipFree(ctx->d_tvec_out);
     if (ctx->d_table) (void)hipFree(ctx->d_table);
     if (ctx->d_bitmap) (void)hipFree(ctx->d_bitmap);
     if (ctx->d_written) (void)hipFree(ctx->d_written);
@@ -779,6 +794,7 @@ int kta_handle_message(kta_ctx *ctx, int32_t partition, int64_t ts_ms, const voi
     }
     kta_batch &h = ctx->stages[ctx->cur].host;
     const uint64_t i = ctx->fill_n;
+    ctx->handed_records = true;
     h.partition[i] = partition;
     h.ts_ms[i] = ts_ms;
     h.key_len[i] = key_len < 0 ? -1 : (int32_t)key_len;
@@ -1018,6 +1034,9 @@ int kta_finish_device(kta_ctx *ctx)
     if (ctx->analytics)
         KTA_HIP(ctx, hipMemcpyAsync(ctx->d_avec_out, ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t),
                                     hipMemcpyDeviceToDevice, ctx->s_compute));
+    if (ctx->timeline)
+        KTA_HIP(ctx, hipMemcpyAsync(ctx->d_tvec_out, ctx->d_tvec, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t),
+                                    hipMemcpyDeviceToDevice, ctx->s_compute));
     if (ctx->alive) {
         uint64_t *dst = ctx->d_vec_out + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
         if (ctx->running_valid)  // exact running count (every update so far ran a counting kernel): no table scan
@@ -1205,6 +1224,116 @@ int kta_analytics_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
     if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
     *device_ptr = ctx->d_avec_out;
     *n_u64 = kta::analytics_len(ctx->P);
+    return KTA_OK;
+}
+
+// The largest P whose scan plan (raw and tile-compact) with `timeline_buckets` (0: none) fits one workgroup's LDS on
+// gfx950, its static reduction arrays (kta_metrics_scan's s_red) included.
+static uint32_t max_partitions_for(bool analytics, uint32_t timeline_buckets)
+{
+    const uint32_t lds_limit = 160u * 1024u, static_lds = (kta::kWG / 64u) * 6u * 8u;
+    uint32_t lo = 0, hi = 4096;
+    while (lo < hi) {   // lds_bytes grows with P: the largest P that fits
+        const uint32_t mid = (lo + hi + 1) / 2;
+        const uint32_t lds = std::max(kta::plan_scan(mid, 1, 1, 1, 0, analytics, false, timeline_buckets).lds_bytes,
+                                      kta::plan_scan(mid, 1, 1, 1, 0, analytics, true, timeline_buckets).lds_bytes);
+        if (lds + static_lds <= lds_limit) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+int kta_timeline_max_partitions(uint32_t flags, uint32_t n_buckets)
+{
+    if (n_buckets < 1 || n_buckets > KTA_TIMELINE_MAX_BUCKETS) return 0;
+    return (int)max_partitions_for((flags & KTA_FLAG_ANALYTICS) != 0, n_buckets);
+}
+
+int kta_set_timeline(kta_ctx *ctx, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (origin_ms < 0) return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: origin_ms must be >= 0");
+    if (bucket_ms < 1) return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: bucket_ms must be >= 1");
+    if (n_buckets < 1 || n_buckets > KTA_TIMELINE_MAX_BUCKETS)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: n_buckets must be in [1, " +
+                                              std::to_string(KTA_TIMELINE_MAX_BUCKETS) + "]");
+    if (bucket_ms > (INT64_MAX - origin_ms) / (int64_t)n_buckets)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: origin_ms + n_buckets * bucket_ms overflows int64");
+    if (ctx->handed_records || ctx->fill_n)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: the context has been handed records since kta_create / kta_reset");
+    const uint32_t pmax = max_partitions_for(ctx->analytics, n_buckets);
+    if (ctx->P > pmax)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_timeline: the scan's LDS plan with " + std::to_string(n_buckets) +
+                                              " buckets admits at most " + std::to_string(pmax) + " partitions" +
+                                              (ctx->analytics ? " with KTA_FLAG_ANALYTICS" : ""));
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t words = kta::timeline_len(n_buckets);
+    if (!ctx->timeline || ctx->tl.n_buckets != n_buckets) {
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+        if (ctx->d_tvec) (void)hipFree(ctx->d_tvec);
+        if (ctx->d_tvec_out) (void)hipFree(ctx->d_tvec_out);
+        ctx->d_tvec = ctx->d_tvec_out = nullptr;
+        ctx->timeline = false;
+        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_tvec, words * sizeof(uint64_t)));
+        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_tvec_out, words * sizeof(uint64_t)));
+    }
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec, 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec_out, 0, words * sizeof(uint64_t), ctx->s_compute));
+    ctx->tl.origin = origin_ms;
+    ctx->tl.width = (unsigned long long)bucket_ms;
+    ctx->tl.span = (unsigned long long)bucket_ms * n_buckets;
+    ctx->tl.inv_width = (float)(1.0 / (double)bucket_ms);
+    ctx->tl.n_buckets = n_buckets;
+    ctx->tl.vec = ctx->d_tvec;
+    ctx->timeline = true;
+    return KTA_OK;
+}
+
+static int timeline_copy(kta_ctx *ctx, const uint64_t *d_src, uint64_t *out, size_t n_u64)
+{
+    if (!out) return KTA_ERR_INVALID;
+    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
+    const size_t words = kta::timeline_len(ctx->tl.n_buckets);
+    if (n_u64 != words)
+        return fail(ctx, KTA_ERR_INVALID, "the timeline has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
+    KTA_HIP(ctx, hipMemcpyAsync(out, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return KTA_OK;
+}
+
+int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return timeline_copy(ctx, ctx->d_tvec, out, n_u64);
+}
+
+int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return timeline_copy(ctx, ctx->d_tvec_out, out, n_u64);
+}
+
+int kta_timeline_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
+    *device_ptr = ctx->d_tvec;
+    *n_u64 = kta::timeline_len(ctx->tl.n_buckets);
+    return KTA_OK;
+}
+
+int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
+    *device_ptr = ctx->d_tvec_out;
+    *n_u64 = kta::timeline_len(ctx->tl.n_buckets);
     return KTA_OK;
 }
 
@@ -1417,6 +1546,11 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *))
 }
 uint64_t *kta_internal_vec_out(kta_ctx *ctx) { return ctx->d_vec_out; }
 uint64_t *kta_internal_avec_out(kta_ctx *ctx) { return ctx->d_avec_out; }
+uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64)
+{
+    *n_u64 = ctx->timeline ? kta::timeline_len(ctx->tl.n_buckets) : 0;
+    return ctx->timeline ? ctx->d_tvec_out : nullptr;
+}
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table; }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }

@@ -12,6 +12,8 @@
 //   analytics  (KTA_FLAG_ANALYTICS, no reference counterpart) in the same grouped launch: all-reduce SUM (u64) over
 //              the 2 x 34 histogram words and all-reduce MAX (i64) over the 4 * P extrema words of the analytics
 //              snapshot; an extremum word nobody wrote is INT64_MIN, so a partition's owner rank wins.
+//   timeline   (kta_set_timeline, no reference counterpart) in the same grouped launch: all-reduce SUM (u64) over the
+//              whole timeline snapshot.
 //   alive set  (-c) global and order dependent (src/metric.rs:262-264, 289-304): every rank's table holds
 //              GLOBAL sequence numbers; rank r owns the slots [ceil(r 2^32 / R), ceil((r+1) 2^32 / R)).
 //              Each rank exports the entries it ever wrote, one contiguous list per owner (<= 12 bytes per
@@ -41,6 +43,7 @@ bool kta_internal_count_alive(kta_ctx *ctx);
 bool kta_internal_alive_table(kta_ctx *ctx);
 uint64_t *kta_internal_vec_out(kta_ctx *ctx);
 uint64_t *kta_internal_avec_out(kta_ctx *ctx);
+uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64);
 uint32_t kta_internal_partitions(kta_ctx *ctx);
 uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
@@ -404,6 +407,9 @@ static int exchange_collectives(kta_ctx *ctx, CommState *st)
         CN(ctx, R->AllReduce(avec, avec, hist, ncclUint64, ncclSum, st->comm, s));
         CN(ctx, R->AllReduce(avec + hist, avec + hist, extrema, ncclInt64, ncclMax, st->comm, s));
     }
+    size_t tl_words = 0;
+    if (uint64_t *tvec = kta_internal_tvec_out(ctx, &tl_words))   // a timeline: every rank of the job has the same one
+        CN(ctx, R->AllReduce(tvec, tvec, tl_words, ncclUint64, ncclSum, st->comm, s));
     CN(ctx, R->GroupEnd());
     return KTA_OK;
 }

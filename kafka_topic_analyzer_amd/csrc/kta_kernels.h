@@ -101,6 +101,21 @@ struct ScanPlan {
     bool nontemporal;      // stream the columns with non-temporal loads
     bool analytics;        // additive outputs: size histograms + per-partition extrema
     uint32_t row_len;      // u64 words per workgroup row of the partial workspace
+    uint32_t timeline_rows; // TIMELINE: n_buckets + 3 rows of {packed count, bytes} in LDS after the other arrays; 0 = none
+};
+
+// Timeline (kta_set_timeline): vector u64[(n_buckets + 3) * 3], rows [no timestamp, before, bucket 0..n-1, after] of
+// [records, tombstones, bytes].  The scan places a counted record with the host-side reciprocal of the width and an
+// exact +-1 correction (no 64-bit division per record).
+constexpr uint32_t kTimelineCols = KTA_TIMELINE_COLS;
+inline uint32_t timeline_len(uint32_t n_buckets) { return (n_buckets + 3u) * kTimelineCols; }
+struct TimelineArgs {
+    long long origin;           // origin_ms >= 0
+    unsigned long long width;   // bucket_ms >= 1
+    unsigned long long span;    // n_buckets * bucket_ms (no int64 overflow with origin)
+    float inv_width;            // 1 / bucket_ms, rounded: an estimate the kernel corrects
+    uint32_t n_buckets;         // 1 .. KTA_TIMELINE_MAX_BUCKETS
+    uint64_t *vec;              // the live accumulator (device-scope atomicAdd of the non-zero rows at every flush)
 };
 
 constexpr uint32_t kAnalyticsHist = 2 * 34; // key-size and value-size log2 histograms
@@ -114,12 +129,14 @@ inline uint32_t scan_row_len(uint32_t P, bool analytics)
 }
 
 // tiled: the batch is tile-compact (ScanColumns.hdr): more workgroups per CU (see plan_scan)
+// timeline_buckets: 0 = no timeline (the plan of before); else the timeline's rows come out of the same LDS budget
 ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics,
-                   bool tiled = false);
+                   bool tiled = false, uint32_t timeline_buckets = 0);
 
 // K1: per-record metric accumulation (metric.rs:207-252) over one struct-of-arrays batch.
+// tl: the timeline (plan.timeline_rows != 0), else null.
 hipError_t launch_metrics_scan(const ScanPlan &plan, const ScanColumns &c, uint64_t n, uint32_t P,
-                               uint64_t *partials, hipStream_t s);
+                               uint64_t *partials, hipStream_t s, const TimelineArgs *tl = nullptr);
 // K5: fold the per-workgroup partial rows into the persistent counter vector.
 hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_t P, uint64_t *vec,
                                 uint32_t row_len, uint64_t *analytics_vec, hipStream_t s);

@@ -232,13 +232,101 @@ __device__ __forceinline__ void lds_histograms(const Rec &r, const ScanLds &L)
     }
 }
 
+// TIMELINE (kta_set_timeline; no reference counterpart): records, tombstones and bytes per time bucket of every counted
+// record, in LDS rows of {count word (records | tombstones << kCntBits, as the counters pack them), bytes}, flushed
+// with the counters (so the 21-bit fields cannot overflow) by a device-scope atomicAdd of every non-zero row into the
+// live vector.  Rows: 0 no timestamp (ts < 0), 1 before the origin, 2 + k bucket k, n + 2 after the window.
+struct TimelineLds {
+    unsigned long long *C, *B;         // [n_buckets + 3] count words, bytes
+};
+
+// The row of a record with raw timestamp ts, d = ts - origin (mod 2^64, exact when ts >= origin).  No 64-bit division:
+// the float estimate d * (1 / width) of k = floor(d / width) is off by at most one (d / width < 1024 here and the
+// three float roundings cost a relative 2^-22 at most, an absolute 2^-12), and one multiply-compare moves it to k:
+// exact for every int64 timestamp.
+__device__ __forceinline__ uint32_t timeline_row(long long ts, unsigned long long d, const TimelineArgs &a)
+{
+    if (ts < 0) return 0u;
+    if (ts < a.origin) return 1u;
+    if (d >= a.span) return a.n_buckets + 2u;
+    uint32_t k = (uint32_t)((float)d * a.inv_width);
+    k = min(k, a.n_buckets - 1u);
+    const unsigned long long kw = (unsigned long long)k * a.width;
+    if (kw > d) k--;
+    else if (d - kw >= a.width) k++;
+    return 2u + k;
+}
+
+__device__ __forceinline__ unsigned long long timeline_count(uint32_t records, uint32_t tombs)
+{
+    return (unsigned long long)records | ((unsigned long long)tombs << kCntBits);
+}
+
+// The quad's records on the timeline.  Kafka timestamps ascend inside a partition, so an ordered topic puts a whole
+// wave into one bucket, and 64 same-address LDS atomics would serialise: the lane's quad is combined in registers
+// (as accumulate_quad does for partitions), a wave whose quads all share one row is reduced across the wave and
+// issues one pair of atomics, and only a scattered wave pays per-record atomics.
+__device__ __forceinline__ void timeline_quad(const Quad &q, const Rec (&r)[4], const long long (&ts)[4],
+                                              const TimelineArgs &a, const TimelineLds &T)
+{
+    unsigned long long d[4];
+    if (q.compact) {
+        // compact tile: ts = ts_base + o, so d = (ts_base - origin) + o with the difference taken once per tile
+        const unsigned long long db = (unsigned long long)q.base - (unsigned long long)a.origin;
+        const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
+                              (int32_t)(uint32_t)q.t0.y, (int32_t)(uint32_t)((uint64_t)q.t0.y >> 32)};
+#pragma unroll
+        for (int j = 0; j < 4; j++) d[j] = db + (unsigned long long)(long long)o[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) d[j] = (unsigned long long)ts[j] - (unsigned long long)a.origin;
+    }
+    uint32_t row[4], by[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        row[j] = timeline_row(ts[j], d[j], a);
+        by[j] = r[j].ks + r[j].vs;     // < 2^32: both < 2^31
+    }
+    const bool quni = r[0].ok && r[1].ok && r[2].ok && r[3].ok && row[0] == row[1] && row[0] == row[2] &&
+                      row[0] == row[3];
+    const uint32_t tombs = r[0].tomb + r[1].tomb + r[2].tomb + r[3].tomb;
+    const unsigned long long bytes = (unsigned long long)by[0] + by[1] + by[2] + by[3];
+    const uint32_t first = __builtin_amdgcn_readfirstlane(quni ? row[0] : 0xFFFFFFFFu);
+    if (__ballot(quni && row[0] == first) == __ballot(1)) {   // (wave-uniform) every quad of the wave in one row
+        uint32_t c = 4u | (tombs << 16);                     // a wave's 256 records: two 16-bit fields
+        unsigned long long b = bytes;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            c += __shfl_xor(c, off);
+            b += __shfl_xor(b, off);
+        }
+        if ((threadIdx.x & 63u) == 0u) {
+            atomicAdd(&T.C[first], timeline_count(c & 0xFFFFu, c >> 16));
+            atomicAdd(&T.B[first], b);
+        }
+        return;
+    }
+    if (quni) {
+        atomicAdd(&T.C[row[0]], timeline_count(4u, tombs));
+        atomicAdd(&T.B[row[0]], bytes);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (r[j].ok) {
+            atomicAdd(&T.C[row[j]], timeline_count(1u, r[j].tomb));
+            atomicAdd(&T.B[row[j]], (unsigned long long)by[j]);
+        }
+}
+
 // The lane's 4 consecutive records of a tile.  A Kafka consumer delivers per-partition runs, so the
 // four usually share a partition: then their contributions are combined in registers and cost one
 // set of LDS atomics instead of four (4x fewer same-address conflicts inside a run).
 // valid: bit j = record j of the quad is one of the batch's
-template <int VARIANT, bool ANALYTICS>
+template <int VARIANT, bool ANALYTICS, bool TIMELINE = false>
 __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2,
-                                                uint32_t rep, const ScanLds &L, LaneState &st)
+                                                uint32_t rep, const ScanLds &L, LaneState &st,
+                                                const TimelineArgs &ta = TimelineArgs{}, const TimelineLds &T = TimelineLds{})
 {
     uint32_t pt[4];
     long long ts[4];
@@ -255,6 +343,7 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, u
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) lds_histograms<ANALYTICS>(r[j], L);
+    if (TIMELINE) timeline_quad(q, r, ts, ta, T);
     const bool uniform = r[0].ok && r[1].ok && r[2].ok && r[3].ok && r[0].part == r[1].part && r[0].part == r[2].part &&
                          r[0].part == r[3].part;
     if (uniform) {
@@ -295,12 +384,20 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, u
 // log2 histograms of key and value sizes and per-partition timestamp / message-size extrema, kept
 // in additional LDS arrays (extrema as signed-max arrays of [~ts, ts, ~size, size], histograms as
 // u32 counters replicated 16x by lane) and flushed with the counters.
-template <int VARIANT, bool NT, bool ANALYTICS, bool TILED>
+// TIMELINE: the kernel takes one more argument, the TimelineArgs (Extra = TimelineArgs; the timeline rows follow
+// the other LDS arrays).  Instantiated for the accumulating, non-temporal scan only: raw and tiled, with and without
+// analytics.  Without it (Extra empty) the kernel has the parameters and the code of before.
+__device__ __forceinline__ TimelineArgs timeline_args() { return TimelineArgs{}; }
+__device__ __forceinline__ TimelineArgs timeline_args(const TimelineArgs &a) { return a; }
+
+template <int VARIANT, bool NT, bool ANALYTICS, bool TILED, typename... Extra>
 __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t n, uint32_t P,
                                                         uint32_t rep_log2,
                                                         uint64_t *__restrict__ partials,
-                                                        uint32_t row_len)
+                                                        uint32_t row_len, Extra... extra)
 {
+    constexpr bool TIMELINE = sizeof...(Extra) != 0;
+    const TimelineArgs ta = timeline_args(extra...);
     extern __shared__ unsigned long long lds[];
     __shared__ long long s_red[kWG / 64][6];
 
@@ -313,12 +410,19 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
     long long *sX = reinterpret_cast<long long *>(lds + n_arrays * slots);          // ANALYTICS: [4][slots]
     uint32_t *sH = reinterpret_cast<uint32_t *>(lds + (n_arrays + 4) * slots);      // ANALYTICS: [2][34][16]
     const ScanLds L{sA, sK, sV, sX, sH, slots};
+    // TIMELINE: [n_buckets + 3] count words, then as many byte sums, after the arrays above
+    const uint32_t tl_rows = TIMELINE ? ta.n_buckets + 3u : 0u;
+    unsigned long long *sT = lds + (n_arrays + (ANALYTICS ? 4u : 0u)) * slots +
+                             (ANALYTICS ? 2u * kHistBuckets * kHistReps / 2u : 0u);
+    const TimelineLds T{sT, sT + tl_rows};
 
     for (uint32_t i = tid; i < n_arrays * slots; i += kWG) lds[i] = 0ull;
     if (ANALYTICS) {
         for (uint32_t i = tid; i < 4 * slots; i += kWG) sX[i] = LLONG_MIN;
         for (uint32_t i = tid; i < 2 * kHistBuckets * kHistReps; i += kWG) sH[i] = 0u;
     }
+    if (TIMELINE)
+        for (uint32_t i = tid; i < 2 * tl_rows; i += kWG) sT[i] = 0ull;
     __syncthreads();
 
     const uint32_t rep = tid & ((1u << rep_log2) - 1u);
@@ -377,6 +481,20 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
                 hrow[bkt] = first_flush ? t : hrow[bkt] + t;
             }
         }
+        if (TIMELINE) {
+            unsigned long long *tv = reinterpret_cast<unsigned long long *>(ta.vec);
+            for (uint32_t i = tid; i < tl_rows; i += kWG) {
+                const unsigned long long a = T.C[i];
+                if (a == 0ull) continue;
+                const unsigned long long b = T.B[i];
+                T.C[i] = 0ull;
+                T.B[i] = 0ull;
+                const unsigned long long tombs = (a >> kCntBits) & kCntMask;
+                atomicAdd(&tv[(uint64_t)i * kTimelineCols], a & kCntMask);
+                if (tombs) atomicAdd(&tv[(uint64_t)i * kTimelineCols + 1], tombs);
+                if (b) atomicAdd(&tv[(uint64_t)i * kTimelineCols + 2], b);
+            }
+        }
         first_flush = false;
         __syncthreads();
     };
@@ -397,7 +515,7 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
             uint32_t valid = 0u;
 #pragma unroll
             for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-            accumulate_quad<VARIANT, ANALYTICS>(cur, valid, P, rep_log2, rep, L, st);
+            accumulate_quad<VARIANT, ANALYTICS, TIMELINE>(cur, valid, P, rep_log2, rep, L, st, ta, T);
 
             if (++since_flush == kFlushTiles) {
                 flush();
@@ -421,7 +539,7 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
             const bool nxt_valid = (ntile < ntiles) && (nqi < nquads);
             if (nxt_valid) load_quad<NT>(nxt, c, nqi);
 
-            accumulate_quad<VARIANT, ANALYTICS>(cur, cur_valid ? 0xFu : 0u, P, rep_log2, rep, L, st);
+            accumulate_quad<VARIANT, ANALYTICS, TIMELINE>(cur, cur_valid ? 0xFu : 0u, P, rep_log2, rep, L, st, ta, T);
 
             if (++since_flush == kFlushTiles) {
                 flush();
@@ -445,6 +563,11 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
             lane_extrema(r, v, st);
             lds_histograms<ANALYTICS>(r, L);
             lds_record<VARIANT, ANALYTICS>(r, L, rep_log2, rep);
+            if (TIMELINE && r.ok) {
+                const uint32_t tr = timeline_row(ts, (unsigned long long)ts - (unsigned long long)ta.origin, ta);
+                atomicAdd(&T.C[tr], timeline_count(1u, r.tomb));
+                atomicAdd(&T.B[tr], (unsigned long long)(r.ks + r.vs));
+            }
         }
     }
 
@@ -992,26 +1115,33 @@ __global__ __launch_bounds__(kWG) void kta_alive_bitmap(const unsigned long long
 // launch wrappers
 // ---------------------------------------------------------------------------------------
 
-ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics, bool tiled)
+ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int req_variant, bool analytics, bool tiled,
+                   uint32_t timeline_buckets)
 {
     ScanPlan pl;
     // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads
     const int base = req_variant & 15;
+    const bool timeline = timeline_buckets != 0u;
     pl.analytics = analytics;
-    pl.nontemporal = analytics ? true : (req_variant & 16) != 0;
-    pl.variant = analytics ? 0u : (base == 9 ? 9u : 0u);
+    pl.nontemporal = (analytics || timeline) ? true : (req_variant & 16) != 0;
+    pl.variant = (analytics || timeline) ? 0u : (base == 9 ? 9u : 0u);
+    pl.timeline_rows = timeline ? timeline_buckets + 3u : 0u;
     const uint32_t arrays = 3u + (analytics ? 4u : 0u);
     const uint32_t hist_bytes = analytics ? 2u * kHistBuckets * kHistReps * 4u : 0u;
     // LDS budget per workgroup: 32 KiB (4 workgroups = 16 waves per CU can be resident); the
     // analytics kernel carries 7 arrays and gets 64 KiB (2 workgroups per CU) to keep the replication.
     // Tile-compact analytics: 48 KiB, so that 3 workgroups per CU are resident (2^30 records of config 4: 4.89 ms with
     // 64 KiB and 2 per CU, 3.33 with 48 KiB, 3.34 with 40, 3.62 with 32 KiB and 5 per CU).
+    // The timeline's rows (16 B each, 16.05 KiB at 1024 buckets) come out of the same budget: the replication backs
+    // off, the workgroups per CU stay.
     const uint32_t budget_kib = analytics ? (tiled ? 48u : 64u) : 32u;
-    const uint32_t budget_slots = (budget_kib * 1024u - hist_bytes) / (8u * arrays);
+    const uint32_t tl_bytes = pl.timeline_rows * 16u;
+    const uint32_t fixed = hist_bytes + tl_bytes;
+    const uint32_t budget_slots = budget_kib * 1024u > fixed ? (budget_kib * 1024u - fixed) / (8u * arrays) : 0u;
     uint32_t rep_log2 = 0;
     while (rep_log2 < 6 && (P << (rep_log2 + 1)) <= budget_slots) rep_log2++;
     pl.rep_log2 = rep_log2;
-    pl.lds_bytes = (P << rep_log2) * 8u * arrays + hist_bytes;
+    pl.lds_bytes = (P << rep_log2) * 8u * arrays + fixed;
     pl.row_len = scan_row_len(P, analytics);
     const uint64_t ntiles = ((n >> 2) + kWG - 1) / kWG;
     // Raw layout: 3 workgroups (12 waves) per CU saturate HBM (measured: 2-3 per CU best, more is slower), and
@@ -1033,25 +1163,37 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
 }
 
 hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_t n, uint32_t P,
-                               uint64_t *partials, hipStream_t s)
+                               uint64_t *partials, hipStream_t s, const TimelineArgs *tl)
 {
     dim3 grid(pl.workgroups), block(kWG);
+    if (pl.timeline_rows && (!tl || tl->n_buckets + 3u != pl.timeline_rows)) return hipErrorInvalidValue;
     // > 64 KiB of dynamic LDS (P > ~2700) must be opted into per kernel
-#define KTA_SCAN_T(V, NT, AN, TL)                                                                                   \
+#define KTA_SCAN_T(V, NT, AN, TL, ...)                                                                              \
     do {                                                                                                            \
         if (pl.lds_bytes > 48u * 1024u) {                                                                           \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan<V, NT, AN, TL>),   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);      \
+            hipError_t ea = hipFuncSetAttribute(                                                                    \
+                reinterpret_cast<const void *>(&kta_metrics_scan<V, NT, AN, TL __VA_OPT__(, ) __VA_ARGS__>),        \
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);                                     \
             if (ea != hipSuccess) return ea;                                                                        \
         }                                                                                                           \
-        hipLaunchKernelGGL((kta_metrics_scan<V, NT, AN, TL>), grid, block, pl.lds_bytes, s, c, n, P, pl.rep_log2,   \
-                           partials, pl.row_len);                                                                   \
+        hipLaunchKernelGGL((kta_metrics_scan<V, NT, AN, TL __VA_OPT__(, ) __VA_ARGS__>), grid, block, pl.lds_bytes,  \
+                           s, c, n, P, pl.rep_log2, partials, pl.row_len __VA_OPT__(, *tl));                        \
     } while (0)
 #define KTA_SCAN(V, NT, AN)                                  \
     do {                                                     \
         if (c.hdr) KTA_SCAN_T(V, NT, AN, true);              \
         else KTA_SCAN_T(V, NT, AN, false);                   \
     } while (0)
+    if (pl.timeline_rows) {   // (plan_scan: accumulating, non-temporal)
+        if (pl.analytics) {
+            if (c.hdr) KTA_SCAN_T(0, true, true, true, TimelineArgs);
+            else KTA_SCAN_T(0, true, true, false, TimelineArgs);
+        } else {
+            if (c.hdr) KTA_SCAN_T(0, true, false, true, TimelineArgs);
+            else KTA_SCAN_T(0, true, false, false, TimelineArgs);
+        }
+        return hipGetLastError();
+    }
     if (pl.analytics) {
         KTA_SCAN(0, true, true);
         return hipGetLastError();

@@ -68,6 +68,15 @@ def allreduce_analytics_vector(avec, n_partitions: int, group=None) -> None:
     dist.all_reduce(avec[k:], op=dist.ReduceOp.MAX, group=group)
 
 
+def allreduce_timeline_vector(tvec, group=None) -> None:
+    """In-place exchange of an int64 view of the timeline SNAPSHOT (kta_timeline_result_vector: device tensor, or a
+    CPU tensor in the tests) — what kta_exchange does natively for a context with a timeline: all-reduce SUM over
+    every word (i64 wrap == u64 wrap).  Every rank must have the same timeline configuration."""
+    import torch.distributed as dist
+    assert tvec.numel() % N.KTA_TIMELINE_COLS == 0
+    dist.all_reduce(tvec, op=dist.ReduceOp.SUM, group=group)
+
+
 def allreduce_alive_table(table, group=None, chunk_elems: int = 1 << 28) -> None:
     """Element-wise MAX of the last-writer tables, in place, chunked (2 GiB of int64 per call) so
     RCCL's staging stays bounded.  Values are < 2^63, so signed MAX == unsigned MAX."""
