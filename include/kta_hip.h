@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -147,14 +147,34 @@ typedef struct kta_analytics {
 #define KTA_TIMELINE_MAX_BUCKETS 1024
 #define KTA_TIMELINE_COLS 3
 
+/* Key sketch (NOT in the reference, never printed by the reference report): one HyperLogLog sketch per partition over
+ * the keys, to estimate the distinct keys each partition holds.  Opt-in at kta_create.  For every record the metrics
+ * handler counts (partition in [0, P)) whose key is Some (key_len >= 0: the empty key and tombstones included):
+ *   h = fnv1a(key)                     the reference's variant, init = mul = 0x811c9dc5 (fnv32.rs:76-101), as -c hashes
+ *   x = fmix32(h)                      x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16
+ *   j = x >> 20                        the register, 0 .. 4095
+ *   w = x << 12                        the other 20 bits, left-aligned
+ *   rho = w == 0 ? 21 : clz32(w) + 1   1 .. 21
+ *   M[p][j] = max(M[p][j], rho)        0: no key seen
+ * Null keys, partitions outside [0, P) and records handed only to the alive-key handler (which == 2) are skipped.  The
+ * registers are maxima: exact, independent of order and batching, and they reduce across GPUs with MAX.
+ * The host-side vector is u64[P * KTA_SKETCH_REGISTERS], word p * 4096 + j, one register per word (the collectives
+ * reduce 8-byte words).  It counts distinct 32-bit key HASHES, as -c counts alive keys by hash slot: at 10^8 keys
+ * visibly fewer than the distinct keys (about 1.2 % fewer).  The estimate (kta_key_sketch_estimate) has a standard
+ * error of 1.04 / sqrt(4096), about 1.6 %.  kta_create refuses the flag above KTA_SKETCH_MAX_PARTITIONS partitions. */
+#define KTA_FLAG_KEY_SKETCH 8u
+#define KTA_SKETCH_LOG2 12
+#define KTA_SKETCH_REGISTERS (1u << KTA_SKETCH_LOG2)
+#define KTA_SKETCH_MAX_PARTITIONS 16384   /* 512 MiB of u64 snapshot */
+
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
  *   partition[i]  m.partition()                                          i32
  *   ts_ms[i]      raw rdkafka timestamp in ms; -1 == not available       i64
  *   key_len[i]    m.key():  -1 == None, >= 0 == Some(k).len()            i32
  *   val_len[i]    m.payload(): -1 == None (tombstone), >= 0 == len       i32
- *   key_off[i]    offset of the key's bytes in key_bytes (if key_len>0)  u32  (-c only)
- *   key_bytes     concatenated key bytes; device buffers must be readable  u8   (-c only)
+ *   key_off[i]    offset of the key's bytes in key_bytes (if key_len>0)  u32  (-c or KTA_FLAG_KEY_SKETCH only)
+ *   key_bytes     concatenated key bytes; device buffers must be readable  u8   (-c or KTA_FLAG_KEY_SKETCH only)
  *                 for 16 bytes past the last key (kta_device_batch_alloc pads)
  *   seq[i]        optional global consumption index; NULL => base_seq+i  u64  (-c only)
  * Value bytes are never read by the reference path (only their length). */
@@ -336,11 +356,14 @@ int kta_finish_device(kta_ctx *ctx);
  *                       4 * P extrema words (neutral element INT64_MIN: a partition's owner wins).
  *                       With a timeline (kta_set_timeline) the same grouped launch also reduces the timeline
  *                       snapshot: all-reduce SUM (u64) over all of its words.
+ *                       With KTA_FLAG_KEY_SKETCH the same grouped launch also reduces the key sketch's snapshot:
+ *                       all-reduce MAX (u64) over all of its P * 4096 words.
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
- *                       (kta_exchange_analytics, kta_exchange_timeline: the same for the analytics, the timeline)
- * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS bit, and be given the same
- * timeline configuration (or none on every rank): the collectives of a rank with analytics or a timeline do not
- * match those of a rank without, and nothing checks that the configurations agree.
+ *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch: the same for the
+ *                       analytics, the timeline, the key sketch)
+ * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS and KTA_FLAG_KEY_SKETCH bits, and
+ * be given the same timeline configuration (or none on every rank): the collectives of a rank with analytics, a key
+ * sketch or a timeline do not match those of a rank without, and nothing checks that the configurations agree.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
 #define KTA_COMM_ID_BYTES 128
 int kta_comm_unique_id(uint8_t id[KTA_COMM_ID_BYTES]);
@@ -413,6 +436,32 @@ int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64);
 /* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
 int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
 
+/* Key sketch (context created with KTA_FLAG_KEY_SKETCH; definition above KTA_FLAG_KEY_SKETCH).  With the flag the staging
+ * batches carry key_off and key_bytes without -c as well (kta_handle_message, kta_batch_submit, kta_replay_messages, the
+ * Kafka decode), and a device batch handed to the metrics handler (which & 1) without key columns is refused with
+ * KTA_ERR_INVALID before anything is launched.  kta_reset zeroes the registers; kta_finish_device snapshots them.  Every
+ * call below on a context without the flag returns KTA_ERR_INVALID.
+ * The live accumulator, copied to out[n_u64] (n_u64 = P * 4096; staged messages are flushed first). */
+int kta_get_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's sketch on every rank.  The live accumulator is never reduced. */
+int kta_exchange_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_key_sketch_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two sketch vectors u64[P * 4096] (acc <- max(acc, other), word by word): what the exchange's
+ * all-reduce MAX implements. */
+int kta_merge_key_sketch(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* Host-side estimate of a sketch vector (no device): per_partition[P] (may be NULL) the estimated distinct keys of each
+ * partition, *topic (may be NULL) the estimate of the register-wise max over all partitions — a key hash seen in two
+ * partitions counts once, as for -c.  Ertl's improved raw estimator (Ertl 2017, "New cardinality estimation algorithms
+ * for HyperLogLog sketches", Algorithm 6), q = 20: exactly 0 for an empty sketch, +inf when every register is 21.
+ * KTA_ERR_INVALID for a register above 21. */
+int kta_key_sketch_estimate(const uint64_t *vec, uint32_t n_partitions, double *per_partition, double *topic);
+/* Work counters of the sketch kernel since kta_create / kta_reset (profiling; waits for the compute stream): out[0]
+ * keyed records it looked at, out[1] of them past the floor filter (a read of their register), out[2] atomics issued,
+ * out[3] launches. */
+int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4]);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -475,6 +524,16 @@ int kta_render_analytics(const uint64_t *vec, uint32_t n_partitions, char *out, 
  * Output buffer conventions as kta_render_report. */
 int kta_render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets, char *out,
                         size_t out_cap, size_t *out_len);
+
+/* The opt-in key sketch section that kta-analyzer prints after the reference report (and after the analytics and
+ * timeline sections) with --librdkafka kta.distinct_keys=1, from a sketch vector u64[P * 4096] and the counter vector
+ * u64[P * 7 + 8] of the same records (host only): a title line that gives the method and its standard error and says
+ * that it is not part of the reference report, a table (P | Keyed records | Distinct keys | Records per key: keyed
+ * records = key_non_null, distinct keys = the estimate rounded to an integer, records per key %.2f; `-` for a partition
+ * without keyed records), a topic row with the topic-wide estimate, and a closing `=` rule.  Output buffer conventions
+ * as kta_render_report. */
+int kta_render_distinct_keys(const uint64_t *sketch_vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out,
+                             size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

@@ -26,7 +26,7 @@ from ._native import KtaBatch, KtaConfig, KtaResult, KtaSynthSpec  # noqa: F401
 __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics", "Message", "KtaError",
            "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats",
            "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions", "render_timeline",
-           "timeline_max_partitions"]
+           "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -73,17 +73,20 @@ class HipMetricHandler:
     def __init__(self, n_partitions: int, count_alive_keys: bool = False, device: int = 0,
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
-                 seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None):
+                 seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
-        timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline)."""
+        timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline);
+        key_sketch: a HyperLogLog sketch of the key hashes per partition (KTA_FLAG_KEY_SKETCH: estimate_distinct_keys)."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
         self.count_alive_keys = bool(count_alive_keys)
+        self.key_sketch_on = bool(key_sketch)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
+                        (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -168,7 +171,8 @@ class HipMetricHandler:
         val_len = np.ascontiguousarray(val_len, dtype=np.int32)
         ts_ms = np.ascontiguousarray(ts_ms, dtype=np.int64)
         n = len(partition)
-        if self.count_alive_keys:
+        keys = self.count_alive_keys or self.key_sketch_on   # the staging batches carry the keys
+        if keys:
             key_off = np.ascontiguousarray(key_off, dtype=np.uint32)
             key_bytes = np.ascontiguousarray(key_bytes, dtype=np.uint8)
         seq0 = self._next_seq if base_seq is None else base_seq
@@ -178,7 +182,7 @@ class HipMetricHandler:
             self._check(self._lib.kta_batch_acquire(self._ctx, C.byref(b)))
             m = min(n - i, b.capacity)
             kb = 0
-            if self.count_alive_keys:
+            if keys:
                 # largest prefix whose (packed, monotone) key bytes fit the staging key capacity
                 kl = np.maximum(key_len[i:i + m], 0).astype(np.int64)
                 ends = np.cumsum(kl)
@@ -402,6 +406,32 @@ class HipMetricHandler:
         p, n = C.c_void_p(), C.c_size_t()
         self._check(self._lib.kta_timeline_result_vector(self._ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def _key_sketch(self, fn) -> np.ndarray:
+        out = np.zeros((self.n_partitions, N.KTA_SKETCH_REGISTERS), dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), out.size))
+        return out
+
+    def key_sketch(self) -> np.ndarray:
+        """The live key sketch, np.uint64[P, 4096]: register j of partition p (kta_get_key_sketch; staged messages are
+        flushed first)."""
+        return self._key_sketch(self._lib.kta_get_key_sketch)
+
+    def exchange_key_sketch(self) -> np.ndarray:
+        """As key_sketch(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._key_sketch(self._lib.kta_exchange_key_sketch)
+
+    def key_sketch_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the key sketch snapshot (for collectives: allreduce_key_sketch_vector)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._lib.kta_key_sketch_result_vector(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def key_sketch_info(self) -> dict:
+        """Work counters of the sketch kernel since creation / reset() (kta_key_sketch_info)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.kta_key_sketch_info(self._ctx, C.byref(out)))
+        return {"keyed": int(out[0]), "reads": int(out[1]), "atomics": int(out[2]), "launches": int(out[3])}
 
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
@@ -632,6 +662,56 @@ def render_timeline(vec, origin_ms: int, bucket_ms: int, n_buckets: int) -> str:
 def timeline_max_partitions(n_buckets: int, analytics: bool = False) -> int:
     """The largest P a context (with analytics or not) may have with a timeline of n_buckets buckets."""
     return int(N.load().kta_timeline_max_partitions(N.KTA_FLAG_ANALYTICS if analytics else 0, n_buckets))
+
+
+def _sketch_vec(vec, P: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    if v.size != P * N.KTA_SKETCH_REGISTERS:
+        raise ValueError(f"a key sketch of {P} partitions has {P * N.KTA_SKETCH_REGISTERS} words, not {v.size}")
+    return v
+
+
+def estimate_distinct_keys(vec, n_partitions: int) -> Tuple[np.ndarray, float]:
+    """kta_key_sketch_estimate: a key sketch (u64[P * 4096] or [P, 4096]) -> (per-partition estimates float64[P], the
+    topic-wide estimate of the register-wise max over the partitions)."""
+    v = _sketch_vec(vec, n_partitions)
+    per = np.zeros(n_partitions, np.float64)
+    topic = C.c_double()
+    rc = N.load().kta_key_sketch_estimate(_np_ptr(v), n_partitions, _np_ptr(per), C.byref(topic))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_key_sketch_estimate")
+    return per, topic.value
+
+
+def merge_key_sketch(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_key_sketch, in place on `acc` (contiguous uint64 / int64): the register-wise max."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    a = _sketch_vec(acc, n_partitions)
+    rc = N.load().kta_merge_key_sketch(_np_ptr(a), _np_ptr(_sketch_vec(other, n_partitions)), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_key_sketch")
+    return acc
+
+
+def render_distinct_keys(sketch_vec, counter_vec, n_partitions: int) -> str:
+    """kta_render_distinct_keys: the section kta-analyzer prints after the report with --librdkafka kta.distinct_keys=1,
+    from a key sketch and the counter vector u64[P * 7 + 8] of the same records."""
+    v = _sketch_vec(sketch_vec, n_partitions)
+    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
+    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    lib = N.load()
+    n = C.c_size_t()
+    rc = lib.kta_render_distinct_keys(_np_ptr(v), _np_ptr(c), n_partitions, None, 0, C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_distinct_keys")
+    buf = C.create_string_buffer(n.value + 1)
+    rc = lib.kta_render_distinct_keys(_np_ptr(v), _np_ptr(c), n_partitions, buf, len(buf), C.byref(n))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_render_distinct_keys")
+    return buf.value.decode()
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

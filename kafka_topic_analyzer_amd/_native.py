@@ -52,6 +52,10 @@ KTA_HIST_BUCKETS = 34
 KTA_ANALYTICS_HIST = 2 * KTA_HIST_BUCKETS   # analytics vector: u64[2*34 + 4*P]
 KTA_TIMELINE_MAX_BUCKETS = 1024             # timeline vector: u64[(n_buckets + 3) * KTA_TIMELINE_COLS]
 KTA_TIMELINE_COLS = 3
+KTA_FLAG_KEY_SKETCH = 8
+KTA_SKETCH_LOG2 = 12
+KTA_SKETCH_REGISTERS = 1 << KTA_SKETCH_LOG2   # key sketch vector: u64[P * 4096], one register per word
+KTA_SKETCH_MAX_PARTITIONS = 16384
 
 
 class KtaAnalytics(C.Structure):
@@ -160,6 +164,14 @@ SIGNATURES = {
     "kta_timeline_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "kta_render_timeline": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_char_p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]),
+    "kta_get_key_sketch": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_key_sketch": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_key_sketch_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_key_sketch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_key_sketch_estimate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "kta_key_sketch_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4)]),
+    "kta_render_distinct_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),
     "kta_alive_table": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "kta_alive_export_entries": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

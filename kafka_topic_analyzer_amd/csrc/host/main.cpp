@@ -17,8 +17,8 @@
 //                                        v2; uncompressed, gzip, Snappy, LZ4, zstd): file k is partition k; decoded ON THE GPU
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
-// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>), so no flag is added
-// or renamed.
+// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1), so
+// no flag is added or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
 // visible devices), and replaces "the report reads the handlers" by ONE exchange step (kta_exchange: RCCL).
@@ -31,6 +31,9 @@
 // timeline as well (kta_set_timeline: records, tombstones and bytes per time bucket; no reference counterpart):
 // kta.timeline.buckets=N buckets (default 168), from kta.timeline.start=<unix seconds> or else so that the last
 // bucket holds the run's start time.  Printed in a section of its own after the report (and the analytics).
+// kta.distinct_keys=1 (every source, kta.gpus=N included) keeps a HyperLogLog sketch of the key hashes per partition as well
+// (KTA_FLAG_KEY_SKETCH; no reference counterpart) and prints the estimated distinct keys per partition and of the topic in a
+// section of its own after the report (and the analytics and the timeline).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -76,6 +79,14 @@ int64_t parse_decimal(const std::string &v, size_t digits)
     for (char ch : v)
         if (ch < '0' || ch > '9') return -1;
     return strtoll(v.c_str(), nullptr, 10);
+}
+
+// key_non_null of partitions [0, P): the keyed records of the kta.distinct_keys section
+std::vector<uint64_t> keyed_records(const kta::MessageMetrics &m, uint32_t P)
+{
+    std::vector<uint64_t> keyed(P);
+    for (uint32_t p = 0; p < P; p++) keyed[p] = m.key_non_null((int32_t)p);
+    return keyed;
 }
 
 const char *kAbout = "Kafka Topic Analyzer 0.4.1";
@@ -200,6 +211,7 @@ struct ShardedJob {
     bool oversubscribe = false;                        // kta.oversubscribe=1: several ranks may share a device (test doubles of RCCL)
     bool analytics = false;                            // kta.analytics=1: every rank's context, exchanged with the counters
     kta::TimelineConfig timeline;                      // kta.timeline=<width>: derived once, the same on every rank
+    bool distinct_keys = false;                        // kta.distinct_keys=1: every rank's context, exchanged with the counters
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -213,7 +225,8 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
     try {
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
-                               (job.analytics ? KTA_FLAG_ANALYTICS : 0u);
+                               (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u);
+        const bool keys = job.count_alive || job.distinct_keys;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline);
         kta_ctx *ctx = h->ctx();
@@ -237,7 +250,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                 kta_batch tmp{};
                 tmp.partition = part.data(); tmp.key_len = kl.data(); tmp.val_len = vl.data(); tmp.ts_ms = ts.data();
                 tmp.capacity = n;
-                if (job.count_alive) {
+                if (keys) {
                     check(kta_synth_fill_host(&job.spec, at, n, &tmp, &kb), ctx, "kta_synth_fill_host");   // key bytes needed
                     kbuf.resize(kb + 16);
                     tmp.key_off = ko.data(); tmp.key_bytes = kbuf.data(); tmp.key_bytes_capacity = kb;
@@ -245,19 +258,19 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                 check(kta_synth_fill_host(&job.spec, at, n, &tmp, &kb), ctx, "kta_synth_fill_host");
                 for (uint64_t i = 0; i < n; i++) {
                     if (part[i] % job.nranks != rank) continue;
-                    const uint64_t klen = job.count_alive && kl[i] > 0 ? (uint64_t)kl[i] : 0;
+                    const uint64_t klen = keys && kl[i] > 0 ? (uint64_t)kl[i] : 0;
                     if (open && (fill == hb.capacity || fill_kb + klen > hb.key_bytes_capacity)) submit();
                     if (!open) {
                         check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
                         open = true;
                     }
                     hb.partition[fill] = part[i]; hb.key_len[fill] = kl[i]; hb.val_len[fill] = vl[i]; hb.ts_ms[fill] = ts[i];
-                    if (job.count_alive) {
+                    if (keys) {
                         hb.key_off[fill] = (uint32_t)fill_kb;
                         if (klen) memcpy(hb.key_bytes + fill_kb, kbuf.data() + ko[i], klen);
                         fill_kb += klen;
-                        hb.seq[fill] = at + i;
                     }
+                    if (job.count_alive) hb.seq[fill] = at + i;
                     fill++;
                 }
                 at += n;
@@ -340,6 +353,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         if (job.timeline.n_buckets)
             text += kta::render_timeline(h0->timeline()->data(), job.timeline.origin_ms, job.timeline.bucket_ms,
                                          job.timeline.n_buckets);
+        if (job.distinct_keys) text += kta::render_distinct_keys(h0->key_sketch()->data(), keyed_records(metrics, job.P));
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -429,6 +443,12 @@ int main(int argc, char **argv)
     if (analytics && P > (uint32_t)kta_analytics_max_partitions()) {   // before any context, so before any kernel
         fprintf(stderr, "kta.analytics=1: the topic has %u partitions, the analytics scan admits at most %d "
                         "(its per-partition extrema live in LDS)\n", P, kta_analytics_max_partitions());
+        return 2;
+    }
+    const bool distinct_keys = cfg.count("kta.distinct_keys") && cfg["kta.distinct_keys"] == "1";
+    if (distinct_keys && P > KTA_SKETCH_MAX_PARTITIONS) {   // before any context, so before any kernel
+        fprintf(stderr, "kta.distinct_keys=1: the topic has %u partitions, the key sketch admits at most %d "
+                        "(4096 registers per partition)\n", P, KTA_SKETCH_MAX_PARTITIONS);
         return 2;
     }
     kta::TimelineConfig timeline;   // kta.timeline=<width>: refused here, before any context, when it cannot be had
@@ -548,6 +568,7 @@ int main(int argc, char **argv)
         job.oversubscribe = oversubscribe;
         job.analytics = analytics;
         job.timeline = timeline;
+        job.distinct_keys = distinct_keys;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -563,7 +584,8 @@ int main(int argc, char **argv)
     // -c means a 32 GiB table)
     kta::HipMetricHandler *handler = nullptr;
     try {
-        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0, analytics ? KTA_FLAG_ANALYTICS : 0u,
+        handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
+                                            (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u),
                                             timeline);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -632,7 +654,7 @@ int main(int argc, char **argv)
             kta_batch hb;
             check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
             uint64_t n = std::min<uint64_t>(hb.capacity, n_records - seq), kb = 0;
-            if (!count_alive && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
+            if (!count_alive && !distinct_keys && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
             int rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
             while (rc == KTA_ERR_CAPACITY && n > 1) {  // key bytes did not fit: shrink the batch
                 n /= 2;
@@ -676,7 +698,7 @@ int main(int argc, char **argv)
                 kta_batch hb;
                 check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
                 uint64_t n = std::min<uint64_t>(hb.capacity, db.n - done), kb = 0;
-                if (count_alive) {  // re-pack this chunk's keys
+                if (count_alive || distinct_keys) {  // re-pack this chunk's keys
                     uint64_t m = 0;
                     for (; m < n; m++) {
                         const uint64_t kl = db.key_len[done + m] > 0 ? (uint64_t)db.key_len[done + m] : 0;
@@ -739,6 +761,7 @@ int main(int argc, char **argv)
         if (analytics) text += kta::render_analytics(*handler->analytics());
         if (timeline.n_buckets)
             text += kta::render_timeline(handler->timeline()->data(), timeline.origin_ms, timeline.bucket_ms, timeline.n_buckets);
+        if (distinct_keys) text += kta::render_distinct_keys(handler->key_sketch()->data(), keyed_records(metrics, P));
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -71,7 +71,8 @@ uint64_t MessageMetrics::smallest_message() const
 
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
                                    uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline)
-    : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline)
+    : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
+      sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -158,6 +159,10 @@ void HipMetricHandler::read_analytics()
     if (timeline_.n_buckets) {
         tvec_.assign((size_t)(timeline_.n_buckets + 3) * KTA_TIMELINE_COLS, 0);
         check(kta_exchange_timeline(ctx_, tvec_.data(), tvec_.size()), "kta_exchange_timeline");
+    }
+    if (sketch_on_) {
+        svec_.assign((size_t)P_ * KTA_SKETCH_REGISTERS, 0);
+        check(kta_exchange_key_sketch(ctx_, svec_.data(), svec_.size()), "kta_exchange_key_sketch");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

@@ -131,6 +131,9 @@ public:
     // exchange(), the whole job's); nullptr without one.
     const std::vector<uint64_t> *timeline() const { return timeline_.n_buckets ? &tvec_ : nullptr; }
     const TimelineConfig &timeline_config() const { return timeline_; }
+    // With KTA_FLAG_KEY_SKETCH: the key sketch u64[P * 4096] of the snapshot finish() / exchange() took (after exchange(),
+    // the whole job's); nullptr without the flag.
+    const std::vector<uint64_t> *key_sketch() const { return sketch_on_ ? &svec_ : nullptr; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -138,7 +141,7 @@ public:
 
 private:
     void check(int rc, const char *what);
-    void read_analytics();   // the analytics and the timeline of the snapshot
+    void read_analytics();   // the analytics, the timeline and the key sketch of the snapshot
     kta_ctx *ctx_ = nullptr;
     int32_t P_;
     bool alive_;
@@ -150,6 +153,8 @@ private:
     Analytics analytics_;
     TimelineConfig timeline_;
     std::vector<uint64_t> tvec_;
+    bool sketch_on_ = false;
+    std::vector<uint64_t> svec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -167,5 +172,8 @@ std::string render_analytics(const Analytics &a);
 std::string render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets);
 // a timeline width as kta.timeline takes it (86400000 -> "1d", 90000 -> "90s", 7 -> "7ms")
 std::string format_width_ms(int64_t w);
+// the opt-in section kta-analyzer prints after the report (and the analytics and the timeline) with kta.distinct_keys=1
+// (kta_render_distinct_keys): sketch u64[P * 4096], keyed[p] = key_non_null of partition p
+std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint64_t> &keyed);
 
 }  // namespace kta

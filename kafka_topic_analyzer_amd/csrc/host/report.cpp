@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "metric.hpp"
 
@@ -222,7 +223,60 @@ std::string render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t buck
     return o;
 }
 
+// The opt-in key sketch section (kta.distinct_keys=1): no reference counterpart, printed after the reference report's
+// closing rule (and after the analytics and timeline sections).
+std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint64_t> &keyed)
+{
+    const uint32_t P = (uint32_t)keyed.size();
+    std::vector<double> est(P);
+    double topic = 0.0;
+    if (kta_key_sketch_estimate(sketch, P, est.data(), &topic) != KTA_OK) return std::string();
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    auto count = [](double e) { return std::isfinite(e) ? std::to_string((uint64_t)std::llround(e)) : std::string("inf"); };
+    auto per_key = [](uint64_t records, double e) {
+        if (!std::isfinite(e) || std::llround(e) == 0) return std::string("-");
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)records / (double)std::llround(e));
+        return std::string(buf);
+    };
+    std::string o;
+    o += "Distinct keys per partition, estimated (HyperLogLog of the key hashes, +/-1.6 %; kta.distinct_keys=1; not part of the "
+         "reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Keyed records", "Distinct keys", "Records per key"});
+    uint64_t all = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        all += keyed[p];
+        if (keyed[p] == 0) rows.push_back({std::to_string(p), "0", "-", "-"});
+        else rows.push_back({std::to_string(p), u(keyed[p]), count(est[p]), per_key(keyed[p], est[p])});
+    }
+    if (all == 0) rows.push_back({"Topic", "0", "-", "-"});
+    else rows.push_back({"Topic", u(all), count(topic), per_key(all, topic)});
+    o += pretty_table(rows);
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_distinct_keys(const uint64_t *sketch_vec, const uint64_t *counter_vec, uint32_t n_partitions,
+                                        char *out, size_t out_cap, size_t *out_len)
+{
+    if (!sketch_vec || !counter_vec || !out_len || n_partitions == 0 || n_partitions > KTA_SKETCH_MAX_PARTITIONS)
+        return KTA_ERR_INVALID;
+    std::vector<uint64_t> keyed(n_partitions);
+    for (uint32_t p = 0; p < n_partitions; p++) keyed[p] = counter_vec[(size_t)p * KTA_NCOUNTERS + KTA_C_KEY_NON_NULL];
+    int rc = kta_key_sketch_estimate(sketch_vec, n_partitions, nullptr, nullptr);   // (a register above 21: refused)
+    if (rc != KTA_OK) return rc;
+    const std::string text = kta::render_distinct_keys(sketch_vec, keyed);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_ms, uint32_t n_buckets,
                                    char *out, size_t out_cap, size_t *out_len)

@@ -6,6 +6,7 @@
 #include "kta_kernels.h"
 
 #include <limits.h>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -30,7 +31,7 @@ struct Stage {
     kta_batch dev{};   // column pointers into dev_slab
     uint8_t *host_slab = nullptr, *dev_slab = nullptr;
     size_t metric_bytes = 0;      // [partition .. ts_ms]
-    size_t key_bytes_off = 0;     // where key_bytes starts (0 without -c)
+    size_t key_bytes_off = 0;     // where key_bytes starts (0 without -c or the key sketch)
     size_t slab_bytes = 0;
     hipEvent_t done = nullptr;
     bool busy = false;
@@ -55,6 +56,13 @@ struct kta_ctx {
     kta::TimelineArgs tl{};
     uint64_t *d_tvec = nullptr, *d_tvec_out = nullptr;
     bool handed_records = false;    // a record reached the context since kta_create / kta_reset (kta_set_timeline refuses)
+    // key sketch (KTA_FLAG_KEY_SKETCH): d_sketch u32[P * 4096] the live registers, d_sketch_out the u64 snapshot, d_sketch_floor
+    // the floors of the sketch kernel's filter, d_sketch_stats its work counters (kta_key_sketch_info)
+    bool sketch = false;
+    uint32_t *d_sketch = nullptr;
+    uint64_t *d_sketch_out = nullptr, *d_sketch_stats = nullptr;
+    uint8_t *d_sketch_floor = nullptr;
+    uint64_t sketch_launches = 0;
     uint64_t *d_vec = nullptr;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     uint64_t *d_vec_out = nullptr;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -272,6 +280,27 @@ int timer_pair(kta_ctx *ctx, int k, hipEvent_t *a, hipEvent_t *b)
 
 kta::WrittenList written_list(kta_ctx *ctx) { return kta::WrittenList{ctx->d_written, ctx->d_written_n, ctx->written_cap}; }
 
+// The key sketch over a batch whose metric columns were resolved to rb.  A launch takes a slice, and the floors of its
+// filter are refreshed from the registers before each: the slices double from 2^20 records to 2^26, so that the floors
+// of a fresh sketch rise within the first large batch.
+constexpr uint64_t kSketchSliceMin = 1ull << 20, kSketchSliceMax = 1ull << 26;
+int run_key_sketch(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_t n)
+{
+    uint64_t slice = kSketchSliceMin;
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < slice ? n - at : slice;
+        const kta::SketchColumns sc{rb.hdr ? rb.partition : rb.partition + at, rb.hdr, rb.rec0 + at, c->key_len + at,
+                                    c->key_off + at, c->key_bytes};
+        KTA_HIP(ctx, kta::launch_key_sketch_floor(ctx->d_sketch, ctx->P, ctx->d_sketch_floor, ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_key_sketch(sc, take, ctx->P, ctx->d_sketch, ctx->d_sketch_floor, ctx->d_sketch_stats,
+                                            ctx->cu_count, ctx->s_compute));
+        ctx->sketch_launches++;
+        at += take;
+        slice = slice < kSketchSliceMax ? slice * 2 : slice;
+    }
+    return KTA_OK;
+}
+
 // Launch the handlers over device-resident columns on the compute stream.
 int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
 {
@@ -282,6 +311,8 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     // every refusal comes before the first launch: a batch is counted by both handlers or by neither
     if ((which & 2) && ctx->alive && (!c->key_len || !c->val_len || !c->key_off || !c->key_bytes))
         return fail(ctx, KTA_ERR_INVALID, "key columns missing (count_alive_keys)");
+    if ((which & 1) && ctx->sketch && (!c->key_off || !c->key_bytes))
+        return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
     // Table state: which kernels take the batch is decided before anything is launched (the fused pass below depends on it).
     // 3 = the partitioned pass for batches of >= 2^21 records (13: for batches of any size — tests), with the automatic
     // fall-back to the single-kernel filtered update (2) for batches of mostly unique keys; 1 / 2 / 8 / 9 = the
@@ -462,6 +493,10 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         }
         if (ctx->timing) KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
     }
+    if ((which & 1) && ctx->sketch) {   // after the scan or the fused pass, which it leaves as they are
+        int rc = run_key_sketch(ctx, c, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     return KTA_OK;
 }
 
@@ -470,6 +505,11 @@ int reset_state(kta_ctx *ctx)
     KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec, ctx->P, ctx->d_avec, ctx->s_compute));
     if (ctx->timeline)   // the configuration stays
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec, 0, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t), ctx->s_compute));
+    if (ctx->sketch) {
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch, 0, (size_t)ctx->P * kta::kSketchRegs * sizeof(uint32_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch_stats, 0, 3 * sizeof(uint64_t), ctx->s_compute));
+        ctx->sketch_launches = 0;
+    }
     ctx->handed_records = false;
     if (ctx->alive) {
         if (ctx->alive_table) {
@@ -521,6 +561,9 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         return fail(nullptr, KTA_ERR_INVALID,
                     "KTA_FLAG_ANALYTICS admits at most " + std::to_string(kta_analytics_max_partitions()) +
                         " partitions (the analytics scan keeps 4 extrema per partition in LDS)");
+    if ((cfg->flags & KTA_FLAG_KEY_SKETCH) && cfg->n_partitions > KTA_SKETCH_MAX_PARTITIONS)
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_KEY_SKETCH admits at most " + std::to_string(KTA_SKETCH_MAX_PARTITIONS) +
+                                                  " partitions (a u64 snapshot of 4096 registers per partition)");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -542,6 +585,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->P = (uint32_t)cfg->n_partitions;
     ctx->alive = cfg->count_alive_keys != 0;
     ctx->analytics = (cfg->flags & KTA_FLAG_ANALYTICS) != 0;
+    ctx->sketch = (cfg->flags & KTA_FLAG_KEY_SKETCH) != 0;
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
@@ -579,6 +623,14 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     if (ctx->analytics) {
         KTA_TRY(hipMalloc((void **)&ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
         KTA_TRY(hipMalloc((void **)&ctx->d_avec_out, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
+    }
+    if (ctx->sketch) {
+        const size_t regs = (size_t)ctx->P * kta::kSketchRegs;
+        KTA_TRY(hipMalloc((void **)&ctx->d_sketch, regs * sizeof(uint32_t)));
+        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_out, regs * sizeof(uint64_t)));
+        KTA_TRY(hipMemset(ctx->d_sketch_out, 0, regs * sizeof(uint64_t)));
+        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_floor, kta::kSketchFloorBytes));
+        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_stats, 3 * sizeof(uint64_t)));
     }
     if (ctx->alive) {
         if (ctx->alive_table) {
@@ -620,6 +672,10 @@ void kta_destroy(kta_ctx *ctx)
     if (ctx->d_avec_out) (void)hipFree(ctx->d_avec_out);
     if (ctx->d_tvec) (void)hipFree(ctx->d_tvec);
     if (ctx->d_tvec_out) (void)hipFree(ctx->d_tvec_out);
+    if (ctx->d_sketch) (void)hipFree(ctx->d_sketch);
+    if (ctx->d_sketch_out) (void)hipFree(ctx->d_sketch_out);
+    if (ctx->d_sketch_floor) (void)hipFree(ctx->d_sketch_floor);
+    if (ctx->d_sketch_stats) (void)hipFree(ctx->d_sketch_stats);
     if (ctx->d_table) (void)hipFree(ctx->d_table);
     if (ctx->d_bitmap) (void)hipFree(ctx->d_bitmap);
     if (ctx->d_written) (void)hipFree(ctx->d_written);
@@ -658,7 +714,7 @@ static int ensure_stage(kta_ctx *ctx, Stage &st)
 {
     if (st.host_slab) return KTA_OK;
     const uint64_t cap = ctx->batch_capacity, kcap = ctx->key_bytes_capacity;
-    const bool keys = ctx->alive, seq = ctx->alive && ctx->stage_seq;
+    const bool keys = ctx->alive || ctx->sketch, seq = ctx->alive && ctx->stage_seq;
     size_t off = 0, o_part, o_klen, o_vlen, o_ts, o_koff = 0, o_seq = 0, o_kb = 0;
     o_part = off; off += pad16(cap * 4);
     o_klen = off; off += pad16(cap * 4);
@@ -714,14 +770,15 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
 {
     if (!ctx) return KTA_ERR_INVALID;
     if (!ctx->acquired) return fail(ctx, KTA_ERR_INVALID, "kta_batch_submit without kta_batch_acquire");
-    if (n > ctx->batch_capacity || (ctx->alive && n_key_bytes > ctx->key_bytes_capacity))
+    const bool keys = ctx->alive || ctx->sketch;
+    if (n > ctx->batch_capacity || (keys && n_key_bytes > ctx->key_bytes_capacity))
         return fail(ctx, KTA_ERR_CAPACITY, "batch larger than the staging capacity");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     Stage &st = ctx->stages[ctx->cur];
     ctx->acquired = false;
     if (n == 0) return KTA_OK;
     hipStream_t cs = ctx->s_copy;
-    const size_t used = ctx->alive ? st.key_bytes_off + n_key_bytes : st.metric_bytes;
+    const size_t used = keys ? st.key_bytes_off + n_key_bytes : st.metric_bytes;
     if (n * 2 >= ctx->batch_capacity) {
         // a batch that is at least half full (every batch of a stream but its last): ONE copy of the slab's
         // used prefix — the unused tails of the columns travel along, the launches do not multiply
@@ -731,7 +788,7 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
         KTA_HIP(ctx, hipMemcpyAsync(st.dev.key_len, st.host.key_len, n * 4, hipMemcpyHostToDevice, cs));
         KTA_HIP(ctx, hipMemcpyAsync(st.dev.val_len, st.host.val_len, n * 4, hipMemcpyHostToDevice, cs));
         KTA_HIP(ctx, hipMemcpyAsync(st.dev.ts_ms, st.host.ts_ms, n * 8, hipMemcpyHostToDevice, cs));
-        if (ctx->alive) {
+        if (keys) {
             KTA_HIP(ctx, hipMemcpyAsync(st.dev.key_off, st.host.key_off, n * 4, hipMemcpyHostToDevice, cs));
             if (n_key_bytes)
                 KTA_HIP(ctx, hipMemcpyAsync(st.dev.key_bytes, st.host.key_bytes, n_key_bytes, hipMemcpyHostToDevice, cs));
@@ -776,7 +833,8 @@ int kta_handle_message(kta_ctx *ctx, int32_t partition, int64_t ts_ms, const voi
     if (key_len > INT32_MAX || val_len > INT32_MAX)
         return fail(ctx, KTA_ERR_INVALID, "key/value length above i32 range");
     if (!key) key_len = -1; // m.key() is None iff librdkafka's key pointer is null
-    const uint64_t kb = (ctx->alive && key_len > 0) ? (uint64_t)key_len : 0;
+    const bool keys = ctx->alive || ctx->sketch;
+    const uint64_t kb = (keys && key_len > 0) ? (uint64_t)key_len : 0;
     if (kb > ctx->key_bytes_capacity) return fail(ctx, KTA_ERR_CAPACITY, "key larger than key_bytes_capacity");
     if (ctx->fill_n > 0 && (ctx->fill_n == ctx->batch_capacity || ctx->fill_kb + kb > ctx->key_bytes_capacity)) {
         const uint64_t t0 = now_ns();
@@ -799,7 +857,7 @@ int kta_handle_message(kta_ctx *ctx, int32_t partition, int64_t ts_ms, const voi
     h.ts_ms[i] = ts_ms;
     h.key_len[i] = key_len < 0 ? -1 : (int32_t)key_len;
     h.val_len[i] = val_len < 0 ? -1 : (int32_t)val_len;
-    if (ctx->alive) {
+    if (keys) {
         if (h.seq) h.seq[i] = ctx->next_seq + i;
         h.key_off[i] = (uint32_t)ctx->fill_kb;
         if (kb) {
@@ -817,6 +875,7 @@ int kta_replay_messages(kta_ctx *ctx, const kta_batch *c, uint64_t n)
     if (!ctx || !c) return KTA_ERR_INVALID;
     if (!c->partition || !c->key_len || !c->val_len || !c->ts_ms) return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
     if (ctx->alive && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (count_alive_keys)");
+    if (ctx->sketch && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
     // through a pointer the compiler cannot see through: the loop pays the call a foreign caller pays per message
     static int (*volatile entry)(kta_ctx *, int32_t, int64_t, const void *, int64_t, int64_t) = kta_handle_message;
     static const uint8_t no_bytes[1] = {0};
@@ -1037,6 +1096,9 @@ int kta_finish_device(kta_ctx *ctx)
     if (ctx->timeline)
         KTA_HIP(ctx, hipMemcpyAsync(ctx->d_tvec_out, ctx->d_tvec, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t),
                                     hipMemcpyDeviceToDevice, ctx->s_compute));
+    if (ctx->sketch)
+        KTA_HIP(ctx, kta::launch_key_sketch_widen(ctx->d_sketch, (uint64_t)ctx->P * kta::kSketchRegs, ctx->d_sketch_out,
+                                                  ctx->s_compute));
     if (ctx->alive) {
         uint64_t *dst = ctx->d_vec_out + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
         if (ctx->running_valid)  // exact running count (every update so far ran a counting kernel): no table scan
@@ -1337,6 +1399,140 @@ int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
     return KTA_OK;
 }
 
+static const char *const kNoSketch = "context was created without KTA_FLAG_KEY_SKETCH";
+
+static int sketch_words(kta_ctx *ctx, size_t n_u64)
+{
+    const size_t words = (size_t)ctx->P * kta::kSketchRegs;
+    if (n_u64 != words)
+        return fail(ctx, KTA_ERR_INVALID, "the key sketch has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
+    return KTA_OK;
+}
+
+int kta_get_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
+    int rc = sketch_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    std::vector<uint32_t> host(n_u64);   // the live registers are u32
+    KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_sketch, n_u64 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    for (size_t i = 0; i < n_u64; i++) out[i] = host[i];
+    return KTA_OK;
+}
+
+int kta_exchange_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
+    int rc = sketch_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_sketch_out, n_u64 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return KTA_OK;
+}
+
+int kta_key_sketch_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
+    *device_ptr = ctx->d_sketch_out;
+    *n_u64 = (size_t)ctx->P * kta::kSketchRegs;
+    return KTA_OK;
+}
+
+int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_sketch_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    out[3] = ctx->sketch_launches;
+    return KTA_OK;
+}
+
+int kta_merge_key_sketch(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    if (!acc || !other || P == 0 || P > KTA_SKETCH_MAX_PARTITIONS) return KTA_ERR_INVALID;
+    const size_t words = (size_t)P * KTA_SKETCH_REGISTERS;
+    for (size_t i = 0; i < words; i++)
+        if (other[i] > acc[i]) acc[i] = other[i];
+    return KTA_OK;
+}
+
+namespace {
+
+// Ertl 2017, Algorithm 6 (the improved raw estimator) for m = 4096 registers and q = 32 - 12 = 20 hash bits below the
+// register index, from the register histogram C[0 .. q + 1].
+constexpr int kSketchQ = 32 - KTA_SKETCH_LOG2;
+
+double hll_sigma(double x)
+{
+    if (x == 1.0) return INFINITY;
+    double y = 1.0, z = x, zp;
+    do {
+        x *= x;
+        zp = z;
+        z += x * y;
+        y += y;
+    } while (z != zp);
+    return z;
+}
+
+double hll_tau(double x)
+{
+    if (x == 0.0 || x == 1.0) return 0.0;
+    double y = 1.0, z = 1.0 - x, zp;
+    do {
+        x = sqrt(x);
+        zp = z;
+        y *= 0.5;
+        z -= (1.0 - x) * (1.0 - x) * y;
+    } while (z != zp);
+    return z / 3.0;
+}
+
+double hll_estimate(const uint64_t (&C)[kSketchQ + 2])
+{
+    const double m = (double)KTA_SKETCH_REGISTERS;
+    double z = m * hll_tau(1.0 - (double)C[kSketchQ + 1] / m);
+    for (int k = kSketchQ; k >= 1; k--) z = 0.5 * (z + (double)C[k]);
+    z += m * hll_sigma((double)C[0] / m);
+    return m * m / (2.0 * log(2.0)) / z;
+}
+
+} // namespace
+
+int kta_key_sketch_estimate(const uint64_t *vec, uint32_t P, double *per_partition, double *topic)
+{
+    if (!vec || P == 0 || P > KTA_SKETCH_MAX_PARTITIONS) return KTA_ERR_INVALID;
+    const size_t words = (size_t)P * KTA_SKETCH_REGISTERS;
+    for (size_t i = 0; i < words; i++)
+        if (vec[i] > (uint64_t)kSketchQ + 1) return KTA_ERR_INVALID;
+    std::vector<uint64_t> all(KTA_SKETCH_REGISTERS, 0);
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t *r = vec + (size_t)p * KTA_SKETCH_REGISTERS;
+        uint64_t C[kSketchQ + 2] = {};
+        for (uint32_t j = 0; j < KTA_SKETCH_REGISTERS; j++) {
+            C[r[j]]++;
+            all[j] = std::max(all[j], r[j]);
+        }
+        if (per_partition) per_partition[p] = hll_estimate(C);
+    }
+    if (topic) {
+        uint64_t C[kSketchQ + 2] = {};
+        for (uint32_t j = 0; j < KTA_SKETCH_REGISTERS; j++) C[all[j]]++;
+        *topic = hll_estimate(C);
+    }
+    return KTA_OK;
+}
+
 static const char *const kNeedsTable =
     "the context keeps the alive set as a bit set: create it with KTA_FLAG_ALIVE_TABLE for sequence-numbered entries";
 
@@ -1551,6 +1747,12 @@ uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64)
     *n_u64 = ctx->timeline ? kta::timeline_len(ctx->tl.n_buckets) : 0;
     return ctx->timeline ? ctx->d_tvec_out : nullptr;
 }
+uint64_t *kta_internal_sketch_out(kta_ctx *ctx, size_t *n_u64)
+{
+    *n_u64 = ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0;
+    return ctx->sketch ? ctx->d_sketch_out : nullptr;
+}
+bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch; }
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table; }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }

@@ -14,6 +14,8 @@
 //              snapshot; an extremum word nobody wrote is INT64_MIN, so a partition's owner rank wins.
 //   timeline   (kta_set_timeline, no reference counterpart) in the same grouped launch: all-reduce SUM (u64) over the
 //              whole timeline snapshot.
+//   key sketch (KTA_FLAG_KEY_SKETCH, no reference counterpart) in the same grouped launch: all-reduce MAX (u64) over the
+//              whole register snapshot, one register per word.
 //   alive set  (-c) global and order dependent (src/metric.rs:262-264, 289-304): every rank's table holds
 //              GLOBAL sequence numbers; rank r owns the slots [ceil(r 2^32 / R), ceil((r+1) 2^32 / R)).
 //              Each rank exports the entries it ever wrote, one contiguous list per owner (<= 12 bytes per
@@ -44,6 +46,7 @@ bool kta_internal_alive_table(kta_ctx *ctx);
 uint64_t *kta_internal_vec_out(kta_ctx *ctx);
 uint64_t *kta_internal_avec_out(kta_ctx *ctx);
 uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64);
+uint64_t *kta_internal_sketch_out(kta_ctx *ctx, size_t *n_u64);
 uint32_t kta_internal_partitions(kta_ctx *ctx);
 uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
@@ -410,6 +413,9 @@ static int exchange_collectives(kta_ctx *ctx, CommState *st)
     size_t tl_words = 0;
     if (uint64_t *tvec = kta_internal_tvec_out(ctx, &tl_words))   // a timeline: every rank of the job has the same one
         CN(ctx, R->AllReduce(tvec, tvec, tl_words, ncclUint64, ncclSum, st->comm, s));
+    size_t sk_words = 0;
+    if (uint64_t *svec = kta_internal_sketch_out(ctx, &sk_words))  // a key sketch: every rank of the job has the flag
+        CN(ctx, R->AllReduce(svec, svec, sk_words, ncclUint64, ncclMax, st->comm, s));
     CN(ctx, R->GroupEnd());
     return KTA_OK;
 }

@@ -41,7 +41,7 @@ void kta_internal_set_error(kta_ctx *ctx, const char *msg);
 void **kta_internal_ext_slot(kta_ctx *ctx, void (*free_fn)(void *));
 uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
 bool kta_internal_timing(kta_ctx *ctx);
-bool kta_internal_count_alive(kta_ctx *ctx);
+bool kta_internal_want_keys(kta_ctx *ctx);   // -c or the key sketch: the handlers read key_off / key_bytes
 hipStream_t kta_internal_copy_stream(kta_ctx *ctx);
 int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
 
@@ -1808,7 +1808,7 @@ int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kaf
     }
     if (rc != KTA_OK) return rc;
     if (stats->n_batches == 0) return KTA_OK;
-    const bool keys = kta_internal_count_alive(ctx);
+    const bool keys = kta_internal_want_keys(ctx);
     const uint64_t used = stats->bytes_consumed, nrec = stats->n_records, nb = stats->n_batches;
     // Compressed batches inflate into an area behind the raw bytes.  Its size is a bound per batch (zstd /
     // LZ4 frames without a content size: blocks x block maximum), so a blob of many small batches could ask

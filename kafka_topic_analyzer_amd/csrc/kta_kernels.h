@@ -238,4 +238,32 @@ hipError_t launch_alive_bitmap(const uint64_t *table, uint64_t n_slots, uint32_t
 hipError_t launch_fnv32(const uint8_t *key_bytes, const uint32_t *key_off, const int32_t *key_len,
                         uint64_t n, uint32_t *out, hipStream_t s);
 
+// Key sketch (KTA_FLAG_KEY_SKETCH, kta_sketch.hip): u32 registers [P][4096], the live accumulator, raised with atomicMax by
+// the records that get past two filters — a per-(partition, register group) floor in LDS (the least register of the
+// group, refreshed by launch_key_sketch_floor before every launch) and a read of the register itself.  Registers only
+// grow, so a filter that reads a stale (smaller) value costs an atomic, never an update.
+constexpr uint32_t kSketchRegs = 1u << KTA_SKETCH_LOG2;
+constexpr uint32_t kSketchFloorBytes = 16384;   // LDS of the floors: P * groups <= this, groups = 4096 >> group_shift
+inline uint32_t sketch_group_shift(uint32_t P)  // log2 of registers per floor group
+{
+    uint32_t s = 0;
+    while (((uint64_t)P * (kSketchRegs >> s)) > kSketchFloorBytes) s++;
+    return s;
+}
+struct SketchColumns {
+    const int32_t *partition;   // as ScanColumns: with hdr, the allocation's record 0 and the batch's first record rec0
+    const kta_tile_hdr *hdr;
+    uint64_t rec0;
+    const int32_t *key_len;     // the batch's record 0 (both layouts)
+    const uint32_t *key_off;
+    const uint8_t *key_bytes;   // readable 16 bytes past the last key
+};
+// stats: u64[3] += keyed records, records that read their register, records that reached an atomic (device words)
+hipError_t launch_key_sketch(const SketchColumns &c, uint64_t n, uint32_t P, uint32_t *regs, const uint8_t *floors,
+                             uint64_t *stats, int cu_count, hipStream_t s);
+// floors[p << (12 - group_shift) | g] = min of partition p's registers of group g (u8)
+hipError_t launch_key_sketch_floor(const uint32_t *regs, uint32_t P, uint8_t *floors, hipStream_t s);
+// out[i] = regs[i] (u32 -> u64): the snapshot kta_finish_device takes
+hipError_t launch_key_sketch_widen(const uint32_t *regs, uint64_t n, uint64_t *out, hipStream_t s);
+
 } // namespace kta

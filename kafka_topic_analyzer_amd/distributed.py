@@ -77,6 +77,15 @@ def allreduce_timeline_vector(tvec, group=None) -> None:
     dist.all_reduce(tvec, op=dist.ReduceOp.SUM, group=group)
 
 
+def allreduce_key_sketch_vector(svec, group=None) -> None:
+    """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
+    CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
+    MAX over every word (registers are 0..21, so signed MAX == unsigned MAX).  Every rank must have the flag."""
+    import torch.distributed as dist
+    assert svec.numel() % N.KTA_SKETCH_REGISTERS == 0
+    dist.all_reduce(svec, op=dist.ReduceOp.MAX, group=group)
+
+
 def allreduce_alive_table(table, group=None, chunk_elems: int = 1 << 28) -> None:
     """Element-wise MAX of the last-writer tables, in place, chunked (2 GiB of int64 per call) so
     RCCL's staging stays bounded.  Values are < 2^63, so signed MAX == unsigned MAX."""

@@ -1,6 +1,6 @@
-"""Compare the gfx950 assembly of every kernel of csrc/kta_kernels.hip between two trees (no GPU needed): each tree's
-kta_kernels.hip is compiled with `hipcc --cuda-device-only -S` and the build's flags, labels are renumbered, comments
-dropped, and the scan instantiations of the base tree are matched to this tree's with an empty `Extra` pack (the
+"""Compare the gfx950 assembly of every kernel of csrc/kta_kernels.hip and csrc/kta_alive.hip between two trees (no GPU
+needed): each tree's files are compiled with `hipcc --cuda-device-only -S` and the build's flags, labels are renumbered,
+comments dropped, and the scan instantiations of the base tree are matched to this tree's with an empty `Extra` pack (the
 timeline's kernel argument).  Prints one line per kernel and exits non-zero when any kernel differs.
 
     python tools/scan_isa_diff.py <base tree> [<tree, default: this one>]"""
@@ -15,10 +15,13 @@ FLAGS = ["--offload-arch=gfx950", "--cuda-device-only", "-S", "-O3", "-std=c++17
 OLD, NEW = "EEEvNS_11ScanColumnsEmjjPmj", "EJEEEvNS_11ScanColumnsEmjjPmjDpT3_"
 
 
-def assemble(tree, out):
+SOURCES = ("kta_kernels.hip", "kta_alive.hip")
+
+
+def assemble(tree, src, out):
     subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, "-I", os.path.join(tree, "include"),
                     "-I", os.path.join(tree, "kafka_topic_analyzer_amd", "csrc"),
-                    os.path.join(tree, "kafka_topic_analyzer_amd", "csrc", "kta_kernels.hip"), "-o", out],
+                    os.path.join(tree, "kafka_topic_analyzer_amd", "csrc", src), "-o", out],
                    check=True, capture_output=True)
 
 
@@ -44,11 +47,14 @@ def kernels(path):
 def main():
     base = sys.argv[1]
     tree = sys.argv[2] if len(sys.argv) > 2 else HERE
+    ka, kb = {}, {}
     with tempfile.TemporaryDirectory() as d:
-        a, b = os.path.join(d, "base.s"), os.path.join(d, "tree.s")
-        assemble(base, a)
-        assemble(tree, b)
-        ka, kb = kernels(a), kernels(b)
+        for src in SOURCES:
+            a, b = os.path.join(d, "base_" + src + ".s"), os.path.join(d, "tree_" + src + ".s")
+            assemble(base, src, a)
+            assemble(tree, src, b)
+            ka.update(kernels(a))
+            kb.update(kernels(b))
     bad = 0
     for k in sorted(ka):
         same = ka[k] == kb.get(k)
