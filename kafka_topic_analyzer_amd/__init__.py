@@ -337,11 +337,15 @@ class HipMetricHandler:
         self._check(self._lib.kta_comm_info(self._ctx, C.byref(nr), C.byref(rk), C.byref(se), C.byref(re)))
         return nr.value, rk.value, se.value, re.value
 
+    def _device_vector(self, fn) -> Tuple[int, int]:
+        """What a `(kta_ctx *, void **device_ptr, size_t *n_u64)` entry point answers."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(fn(self._ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the counter vector (for collectives)."""
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_result_vector(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_result_vector)
 
     def result_vector_host(self) -> np.ndarray:
         p, n = self.result_vector()
@@ -350,9 +354,7 @@ class HipMetricHandler:
         return a
 
     def alive_table(self) -> Tuple[int, int]:
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_alive_table(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_alive_table)
 
     def analytics(self) -> dict:
         """Additive analytics (not in the reference): size histograms + per-partition extrema of this
@@ -371,9 +373,7 @@ class HipMetricHandler:
 
     def analytics_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the analytics snapshot (for collectives: allreduce_analytics_vector)."""
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_analytics_result_vector(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_analytics_result_vector)
 
     def set_timeline(self, origin_ms: int, bucket_ms: int, n_buckets: int) -> None:
         """kta_set_timeline: only before the context has been handed any record (since creation / reset())."""
@@ -397,15 +397,11 @@ class HipMetricHandler:
 
     def timeline_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the live timeline."""
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_timeline_vector(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_timeline_vector)
 
     def timeline_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the timeline snapshot (for collectives: allreduce_timeline_vector)."""
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_timeline_result_vector(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_timeline_result_vector)
 
     def _key_sketch(self, fn) -> np.ndarray:
         out = np.zeros((self.n_partitions, N.KTA_SKETCH_REGISTERS), dtype=np.uint64)
@@ -423,9 +419,7 @@ class HipMetricHandler:
 
     def key_sketch_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the key sketch snapshot (for collectives: allreduce_key_sketch_vector)."""
-        p, n = C.c_void_p(), C.c_size_t()
-        self._check(self._lib.kta_key_sketch_result_vector(self._ctx, C.byref(p), C.byref(n)))
-        return p.value, n.value
+        return self._device_vector(self._lib.kta_key_sketch_result_vector)
 
     def key_sketch_info(self) -> dict:
         """Work counters of the sketch kernel since creation / reset() (kta_key_sketch_info)."""
@@ -621,19 +615,22 @@ def merge_analytics(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
     return acc
 
 
+def _render(fn, *args) -> str:
+    """A two-call renderer `fn(*args, buf, cap, &needed)`: ask for the size, allocate, call again."""
+    n = C.c_size_t()
+    buf = None
+    for _ in range(2):
+        rc = fn(*args, buf, len(buf) if buf else 0, C.byref(n))
+        if rc != N.KTA_OK:
+            raise KtaError(rc, fn.__name__)
+        buf = buf or C.create_string_buffer(n.value + 1)
+    return buf.value.decode()
+
+
 def render_analytics(vec, n_partitions: int) -> str:
     """kta_render_analytics: the section kta-analyzer prints after the report with --librdkafka kta.analytics=1."""
     v = _analytics_vec(vec, n_partitions)
-    lib = N.load()
-    n = C.c_size_t()
-    rc = lib.kta_render_analytics(_np_ptr(v), n_partitions, None, 0, C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_analytics")
-    buf = C.create_string_buffer(n.value + 1)
-    rc = lib.kta_render_analytics(_np_ptr(v), n_partitions, buf, len(buf), C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_analytics")
-    return buf.value.decode()
+    return _render(N.load().kta_render_analytics, _np_ptr(v), n_partitions)
 
 
 def analytics_max_partitions() -> int:
@@ -647,16 +644,7 @@ def render_timeline(vec, origin_ms: int, bucket_ms: int, n_buckets: int) -> str:
     v = np.ascontiguousarray(np.asarray(vec).reshape(-1)).view(np.uint64)
     if v.size != (n_buckets + 3) * N.KTA_TIMELINE_COLS:
         raise ValueError(f"a timeline of {n_buckets} buckets has {(n_buckets + 3) * N.KTA_TIMELINE_COLS} words, not {v.size}")
-    lib = N.load()
-    n = C.c_size_t()
-    rc = lib.kta_render_timeline(_np_ptr(v), origin_ms, bucket_ms, n_buckets, None, 0, C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_timeline")
-    buf = C.create_string_buffer(n.value + 1)
-    rc = lib.kta_render_timeline(_np_ptr(v), origin_ms, bucket_ms, n_buckets, buf, len(buf), C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_timeline")
-    return buf.value.decode()
+    return _render(N.load().kta_render_timeline, _np_ptr(v), origin_ms, bucket_ms, n_buckets)
 
 
 def timeline_max_partitions(n_buckets: int, analytics: bool = False) -> int:
@@ -702,16 +690,7 @@ def render_distinct_keys(sketch_vec, counter_vec, n_partitions: int) -> str:
     c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
     if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
-    lib = N.load()
-    n = C.c_size_t()
-    rc = lib.kta_render_distinct_keys(_np_ptr(v), _np_ptr(c), n_partitions, None, 0, C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_distinct_keys")
-    buf = C.create_string_buffer(n.value + 1)
-    rc = lib.kta_render_distinct_keys(_np_ptr(v), _np_ptr(c), n_partitions, buf, len(buf), C.byref(n))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_render_distinct_keys")
-    return buf.value.decode()
+    return _render(N.load().kta_render_distinct_keys, _np_ptr(v), _np_ptr(c), n_partitions)
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

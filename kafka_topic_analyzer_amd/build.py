@@ -71,8 +71,9 @@ def build_lib(force: bool = False) -> str:
             flags = [f for f in HIPCC_FLAGS if not f.startswith("--offload-arch")]
             _run([hipcc, *arch, *flags, "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c", src, "-o", obj])
         objs.append(obj)
+    # -z defs: a kta_internal.h declaration without a definition fails here, not at the first dlopen
     _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, "-ldl",
-          "-Wl,-rpath,/opt/rocm/lib"])
+          "-Wl,-z,defs", "-Wl,-rpath,/opt/rocm/lib"])
     return LIB
 
 

@@ -3,6 +3,7 @@
 // Host code only; the kernels are in kta_kernels.hip.  There is no CPU fallback: every
 // entry point that computes anything needs a gfx950 device.
 #include "../../include/kta_hip.h"
+#include "kta_internal.h"
 #include "kta_kernels.h"
 
 #include <limits.h>
@@ -29,79 +30,82 @@ thread_local std::string g_create_error = "";
 struct Stage {
     kta_batch host{};  // column pointers into host_slab (pinned)
     kta_batch dev{};   // column pointers into dev_slab
-    uint8_t *host_slab = nullptr, *dev_slab = nullptr;
+    PinnedBuf<uint8_t> host_slab;
+    DeviceBuf<uint8_t> dev_slab;
     size_t metric_bytes = 0;      // [partition .. ts_ms]
     size_t key_bytes_off = 0;     // where key_bytes starts (0 without -c or the key sketch)
     size_t slab_bytes = 0;
-    hipEvent_t done = nullptr;
+    Event done;
     bool busy = false;
 };
+
+constexpr size_t kMaxTimedPairs = 2048;
 
 } // namespace
 
 struct kta_ctx {
+    // kta_destroy releases what the context owns by deleting it: members go in the reverse of this order, so the streams
+    // come first here (destroyed last, after every buffer and event), and nothing below may outlive them.
+    Stream s_own;                   // the context's own compute stream (s_compute may be caller-owned)
+    Stream s_copy;
     int device = 0;
     uint32_t P = 0;
     bool alive = false;
     int cu_count = 256;
-    hipStream_t s_compute = nullptr, s_copy = nullptr;
-    hipStream_t s_own = nullptr;    // the context's own compute stream (s_compute may be caller-owned)
-    hipEvent_t ev_copied = nullptr;
+    hipStream_t s_compute = nullptr;
+    Event ev_copied;
     bool analytics = false;
     bool stage_seq = false;         // KTA_FLAG_SEQ_COLUMN
-    uint64_t *d_avec = nullptr;     // analytics vector u64[2*34 + 4*P] (KTA_FLAG_ANALYTICS)
-    uint64_t *d_avec_out = nullptr; // its snapshot (kta_finish_device), reduced by the exchange like d_vec_out
+    DeviceBuf<uint64_t> d_avec;     // analytics vector u64[2*34 + 4*P] (KTA_FLAG_ANALYTICS)
+    DeviceBuf<uint64_t> d_avec_out; // its snapshot (kta_finish_device), reduced by the exchange like d_vec_out
     // timeline (kta_set_timeline): d_tvec u64[(n_buckets + 3) * 3] the live accumulator, d_tvec_out its snapshot
     bool timeline = false;
     kta::TimelineArgs tl{};
-    uint64_t *d_tvec = nullptr, *d_tvec_out = nullptr;
+    DeviceBuf<uint64_t> d_tvec, d_tvec_out;
     bool handed_records = false;    // a record reached the context since kta_create / kta_reset (kta_set_timeline refuses)
     // key sketch (KTA_FLAG_KEY_SKETCH): d_sketch u32[P * 4096] the live registers, d_sketch_out the u64 snapshot, d_sketch_floor
     // the floors of the sketch kernel's filter, d_sketch_stats its work counters (kta_key_sketch_info)
     bool sketch = false;
-    uint32_t *d_sketch = nullptr;
-    uint64_t *d_sketch_out = nullptr, *d_sketch_stats = nullptr;
-    uint8_t *d_sketch_floor = nullptr;
+    DeviceBuf<uint32_t> d_sketch;
+    DeviceBuf<uint64_t> d_sketch_out, d_sketch_stats;
+    DeviceBuf<uint8_t> d_sketch_floor;
     uint64_t sketch_launches = 0;
-    uint64_t *d_vec = nullptr;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
-    uint64_t *d_vec_out = nullptr;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
+    DeviceBuf<uint64_t> d_vec;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
+    DeviceBuf<uint64_t> d_vec_out;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
-    uint64_t *d_partials = nullptr; // scan workspace: max_rows x row_len
+    DeviceBuf<uint64_t> d_partials; // scan workspace: max_rows x row_len
     uint32_t max_rows = 0;
     // -c: the persistent state is ONE of
     //   d_bitmap  the reference's bit set, u32[2^27] (default: batches are applied in submission order), or
     //   d_table   u64[2^32] last-writer table (KTA_FLAG_ALIVE_TABLE / KTA_FLAG_SEQ_COLUMN: global sequence numbers)
     bool alive_table = false;
-    uint32_t *d_bitmap = nullptr;
-    uint64_t *d_table = nullptr;
-    int64_t *d_alive_running = nullptr; // running alive count
+    DeviceBuf<uint32_t> d_bitmap;
+    DeviceBuf<uint64_t> d_table;
+    DeviceBuf<int64_t> d_alive_running; // running alive count
     bool running_valid = true;          // false once an update ran without counting
     // table state: the slots ever written (what the exchange exports); invalid once somebody else wrote the table
-    uint32_t *d_written = nullptr;
-    unsigned long long *d_written_n = nullptr;
-    uint64_t written_cap = 0;
+    DeviceBuf<uint32_t> d_written;  // (its size is the list's capacity)
+    DeviceBuf<unsigned long long> d_written_n;
     bool written_valid = true;
-    uint32_t *d_exp_slots = nullptr;    // kta_alive_export_entries buffers
-    uint64_t *d_exp_vals = nullptr, *d_exp_count = nullptr;
-    uint64_t exp_cap = 0;
-    uint32_t *d_hash_scratch = nullptr; // ablation variants only
-    uint64_t hash_scratch_cap = 0;
-    uint64_t *d_pairs = nullptr;        // partitioned alive pass: (hash, local seq, alive) pairs by [workgroup][bucket]
-    uint32_t *d_pair_counts = nullptr;  //   and the fill of every segment, [bucket][workgroup]
-    uint64_t *d_pool = nullptr;         //   pairs whose segment was full
-    void *d_pool_ctl = nullptr;         //   pool cursor, histogram, order flag
-    uint32_t *d_fail_from = nullptr;    //   buckets handed to the fallback kernel (bit set state)
-    uint64_t pairs_cap = 0, pair_counts_cap = 0, pool_cap = 0;
+    DeviceBuf<uint32_t> d_exp_slots;    // kta_alive_export_entries buffers
+    DeviceBuf<uint64_t> d_exp_vals, d_exp_count;
+    DeviceBuf<uint32_t> d_hash_scratch; // ablation variants only
+    DeviceBuf<uint64_t> d_pairs;        // partitioned alive pass: (hash, local seq, alive) pairs by [workgroup][bucket]
+    DeviceBuf<uint32_t> d_pair_counts;  //   and the fill of every segment, [bucket][workgroup]
+    DeviceBuf<uint64_t> d_pool;         //   pairs whose segment was full (8 words more than the plan's pool_words)
+    DeviceBuf<uint8_t> d_pool_ctl;      //   pool cursor, histogram, order flag
+    DeviceBuf<uint32_t> d_fail_from;    //   buckets handed to the fallback kernel (bit set state)
     // Feedback for the automatic choice (alive_variant 3 / 4): the partitioned pass pays when records die in
     // LDS (a compacted topic repeats its keys inside a batch); a batch of mostly unique keys is cheaper in
     // the single-kernel update.  Every partitioned batch reports [pairs, entries claimed]; a batch that
     // claimed more than kAliveUniqueNum / kAliveUniqueDen of its pairs sends the next kAliveBackoff batches
     // down the single-kernel path before the partitioned pass is tried again.
-    uint64_t *d_alive_stats = nullptr, *h_alive_stats = nullptr;
-    hipEvent_t ev_alive_stats = nullptr;
+    DeviceBuf<uint64_t> d_alive_stats;
+    PinnedBuf<uint64_t> h_alive_stats;
+    Event ev_alive_stats;
     bool alive_stats_pending = false;
     bool fuse_handlers = true;      // both handlers of a batch in one pass where that is possible (KTA_NO_FUSE=1: never)
-    uint64_t *d_failed_total = nullptr; // buckets handed to kta_alive_fallback since create / reset (kta_alive_pass_info)
+    DeviceBuf<uint64_t> d_failed_total; // buckets handed to kta_alive_fallback since create / reset (kta_alive_pass_info)
     int alive_backoff = 0;
     // what the partitioned pass did since kta_create / kta_reset (kta_alive_pass_info): launch pairs, of them with both
     // handlers in the one pass, of them with the metrics handler through the scan although the batch began fused, and the
@@ -123,10 +127,7 @@ struct kta_ctx {
     bool timing = false;
     // HIP-event pairs recorded around each kernel on the compute stream (no host sync while
     // recording); drained by kta_kernel_time_stats.  kind: 0 scan, 1 fold, 2 alive update.
-    std::vector<hipEvent_t> ev_pool[3];
-    size_t ev_used[3] = {0, 0, 0};
-    double ms_sum[3] = {0, 0, 0};
-    uint64_t ms_cnt[3] = {0, 0, 0};
+    TimerPool<3> timers{2 * kMaxTimedPairs};
     // extension state owned by another translation unit of the library (kta_kafka.hip)
     void *ext_state = nullptr;
     void (*ext_free)(void *) = nullptr;
@@ -134,6 +135,12 @@ struct kta_ctx {
     void (*comm_free)(void *) = nullptr;
     std::string err;
 };
+
+int kta_internal_fail(kta_ctx *ctx, int code, const std::string &msg)
+{
+    if (ctx) ctx->err = msg; else g_create_error = msg;
+    return code;
+}
 
 namespace {
 
@@ -143,24 +150,6 @@ uint64_t now_ns()
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
 }
-
-int fail(kta_ctx *ctx, int code, const std::string &msg)
-{
-    if (ctx) ctx->err = msg; else g_create_error = msg;
-    return code;
-}
-
-int hip_fail(kta_ctx *ctx, hipError_t e, const char *what)
-{
-    std::string m = std::string(what) + ": " + hipGetErrorString(e);
-    return fail(ctx, e == hipErrorOutOfMemory ? KTA_ERR_NOMEM : KTA_ERR_HIP, m);
-}
-
-#define KTA_HIP(ctx, call)                                         \
-    do {                                                           \
-        hipError_t e__ = (call);                                   \
-        if (e__ != hipSuccess) return hip_fail(ctx, e__, #call);   \
-    } while (0)
 
 size_t pad16(size_t b) { return (b + 15) & ~(size_t)15; }
 
@@ -241,44 +230,10 @@ int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-constexpr size_t kMaxTimedPairs = 2048;
 constexpr uint64_t kAliveUniqueNum = 2, kAliveUniqueDen = 5;   // > 40 % of a batch's pairs claimed an entry: mostly unique keys
 constexpr int kAliveBackoff = 7;
 
-int drain_timers(kta_ctx *ctx)
-{
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    for (int k = 0; k < 3; k++) {
-        for (size_t i = 0; i + 1 < ctx->ev_used[k]; i += 2) {
-            float ms = 0.f;
-            KTA_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[k][i], ctx->ev_pool[k][i + 1]));
-            ctx->ms_sum[k] += ms;
-            ctx->ms_cnt[k] += 1;
-        }
-        ctx->ev_used[k] = 0;
-    }
-    return KTA_OK;
-}
-
-// next (start, stop) event pair of kernel kind k
-int timer_pair(kta_ctx *ctx, int k, hipEvent_t *a, hipEvent_t *b)
-{
-    if (ctx->ev_used[k] + 2 > 2 * kMaxTimedPairs) {
-        int rc = drain_timers(ctx);
-        if (rc != KTA_OK) return rc;
-    }
-    while (ctx->ev_pool[k].size() < ctx->ev_used[k] + 2) {
-        hipEvent_t e;
-        KTA_HIP(ctx, hipEventCreate(&e));
-        ctx->ev_pool[k].push_back(e);
-    }
-    *a = ctx->ev_pool[k][ctx->ev_used[k]];
-    *b = ctx->ev_pool[k][ctx->ev_used[k] + 1];
-    ctx->ev_used[k] += 2;
-    return KTA_OK;
-}
-
-kta::WrittenList written_list(kta_ctx *ctx) { return kta::WrittenList{ctx->d_written, ctx->d_written_n, ctx->written_cap}; }
+kta::WrittenList written_list(kta_ctx *ctx) { return kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()}; }
 
 // The key sketch over a batch whose metric columns were resolved to rb.  A launch takes a slice, and the floors of its
 // filter are refreshed from the registers before each: the slices double from 2^20 records to 2^26, so that the floors
@@ -291,13 +246,34 @@ int run_key_sketch(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_
         const uint64_t take = n - at < slice ? n - at : slice;
         const kta::SketchColumns sc{rb.hdr ? rb.partition : rb.partition + at, rb.hdr, rb.rec0 + at, c->key_len + at,
                                     c->key_off + at, c->key_bytes};
-        KTA_HIP(ctx, kta::launch_key_sketch_floor(ctx->d_sketch, ctx->P, ctx->d_sketch_floor, ctx->s_compute));
-        KTA_HIP(ctx, kta::launch_key_sketch(sc, take, ctx->P, ctx->d_sketch, ctx->d_sketch_floor, ctx->d_sketch_stats,
+        KTA_HIP(ctx, kta::launch_key_sketch_floor(ctx->d_sketch.get(), ctx->P, ctx->d_sketch_floor.get(), ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_key_sketch(sc, take, ctx->P, ctx->d_sketch.get(), ctx->d_sketch_floor.get(), ctx->d_sketch_stats.get(),
                                             ctx->cu_count, ctx->s_compute));
         ctx->sketch_launches++;
         at += take;
         slice = slice < kSketchSliceMax ? slice * 2 : slice;
     }
+    return KTA_OK;
+}
+
+// The workspace of the partitioned alive pass, large enough for plan pl: the pairs, their counts and the pool grow
+// together (all three released, after the compute stream has drained, before any is allocated again); the pool's control
+// words and the fail lists are allocated once.
+int grow_alive_workspace(kta_ctx *ctx, const kta::AlivePartitionPlan &pl)
+{
+    if (ctx->d_pairs.size() < pl.pair_words || ctx->d_pair_counts.size() < pl.count_words ||
+        ctx->d_pool.size() < pl.pool_words + 8) {
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+        ctx->d_pairs.reset();
+        ctx->d_pair_counts.reset();
+        ctx->d_pool.reset();
+        KTA_HIP(ctx, ctx->d_pairs.alloc(pl.pair_words));
+        KTA_HIP(ctx, ctx->d_pair_counts.alloc(pl.count_words));
+        KTA_HIP(ctx, ctx->d_pool.alloc(pl.pool_words + 8));
+    }
+    if (!ctx->d_pool_ctl) KTA_HIP(ctx, ctx->d_pool_ctl.alloc(pl.ctl_bytes));
+    // (per bucket + the list of given-up buckets + the list for the slot-range passes)
+    if (!ctx->d_fail_from) KTA_HIP(ctx, ctx->d_fail_from.alloc((size_t)3 << pl.bucket_log2));
     return KTA_OK;
 }
 
@@ -321,9 +297,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     const bool partitioned = !ctx->alive_table || (part_kind && (n >= kta::kAlivePartitionMin || ctx->alive_variant >= 13));
     bool use_partitioned = partitioned;
     if ((which & 2) && ctx->alive && partitioned && ctx->alive_table && ctx->alive_variant < 13) {   // automatic choice only (13 forces it)
-        if (ctx->alive_stats_pending && hipEventQuery(ctx->ev_alive_stats) == hipSuccess) {
+        if (ctx->alive_stats_pending && hipEventQuery(ctx->ev_alive_stats.get()) == hipSuccess) {
             ctx->alive_stats_pending = false;
-            const uint64_t pairs = ctx->h_alive_stats[0], claims = ctx->h_alive_stats[1];
+            const uint64_t pairs = ctx->h_alive_stats.get()[0], claims = ctx->h_alive_stats.get()[1];
             if (pairs && claims * kAliveUniqueDen > pairs * kAliveUniqueNum) ctx->alive_backoff = kAliveBackoff;
         }
         if (ctx->alive_backoff > 0) {
@@ -359,41 +335,45 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                                 rb.hdr ? rb.val_len : rb.val_len + at, rb.hdr ? rb.ts_ms : rb.ts_ms + at, rb.hdr,
                                 rb.rec0 + at};
     };
-    if ((which & 1) && !fuse) {
-        const kta::ScanColumns sc = scan_cols(0);
-        kta::ScanPlan pl = kta::plan_scan(ctx->P, n, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant,
-                                          ctx->analytics, sc.hdr != nullptr, tl_buckets);
+    // The metrics handler over records [at, at + m): plan the scan, clamp it to the partial workspace, launch it and
+    // fold its rows.  timed: with the event pairs of kinds 0 (scan) and 1 (fold) around the two launches.
+    auto scan_and_fold = [&](uint64_t at, uint64_t m, bool timed) -> int {
+        const kta::ScanColumns sc = scan_cols(at);
+        kta::ScanPlan pl = kta::plan_scan(ctx->P, m, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics,
+                                          sc.hdr != nullptr, tl_buckets);
         if (pl.workgroups > ctx->max_rows) pl.workgroups = ctx->max_rows;
-        if (ctx->timing) {
-            int rc = timer_pair(ctx, 0, &a, &b);
+        if (timed) {
+            int rc = ctx->timers.pair(ctx, ctx->s_compute, 0, &a, &b);
             if (rc != KTA_OK) return rc;
             KTA_HIP(ctx, hipEventRecord(a, ctx->s_compute));
         }
-        ctx->handed_records = true;
-        KTA_HIP(ctx, kta::launch_metrics_scan(pl, sc, n, ctx->P, ctx->d_partials, ctx->s_compute, tl));
-        if (ctx->timing) {
+        KTA_HIP(ctx, kta::launch_metrics_scan(pl, sc, m, ctx->P, ctx->d_partials.get(), ctx->s_compute, tl));
+        if (timed) {
             KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
-            int rc = timer_pair(ctx, 1, &a, &b);
+            int rc = ctx->timers.pair(ctx, ctx->s_compute, 1, &a, &b);
             if (rc != KTA_OK) return rc;
             KTA_HIP(ctx, hipEventRecord(a, ctx->s_compute));
         }
-        KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, pl.workgroups, ctx->P, ctx->d_vec, pl.row_len,
-                                               ctx->d_avec, ctx->s_compute));
-        if (ctx->timing) KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials.get(), pl.workgroups, ctx->P, ctx->d_vec.get(), pl.row_len, ctx->d_avec.get(),
+                                               ctx->s_compute));
+        if (timed) KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
+        return KTA_OK;
+    };
+    if ((which & 1) && !fuse) {
+        ctx->handed_records = true;
+        int rc = scan_and_fold(0, n, ctx->timing);
+        if (rc != KTA_OK) return rc;
     }
     if ((which & 2) && ctx->alive) {
         kta::AliveColumns ac{c->key_len, c->val_len, c->key_off, c->key_bytes, c->seq};
         if (ctx->timing) {
-            int rc = timer_pair(ctx, 2, &a, &b);
+            int rc = ctx->timers.pair(ctx, ctx->s_compute, 2, &a, &b);
             if (rc != KTA_OK) return rc;
             KTA_HIP(ctx, hipEventRecord(a, ctx->s_compute));
         }
-        if (ctx->alive_table && (ctx->alive_variant == 8 || ctx->alive_variant == 9) && ctx->hash_scratch_cap < n) {
+        if (ctx->alive_table && (ctx->alive_variant == 8 || ctx->alive_variant == 9) && ctx->d_hash_scratch.size() < n) {
             KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-            if (ctx->d_hash_scratch) (void)hipFree(ctx->d_hash_scratch);
-            ctx->d_hash_scratch = nullptr;
-            KTA_HIP(ctx, hipMalloc((void **)&ctx->d_hash_scratch, n * sizeof(uint32_t)));
-            ctx->hash_scratch_cap = n;
+            KTA_HIP(ctx, ctx->d_hash_scratch.alloc(n));
         }
         // Bit set state: every batch takes the partitioned pass (hash + partition, per-bucket merge in LDS, the
         // bucket's bitmap region streamed through LDS); batches are applied in submission order, base_seq and a
@@ -405,9 +385,9 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         if (ctx->alive_table && ctx->alive_variant != 1 && ctx->alive_variant != 2 && !part_kind) ctx->running_valid = false;   // non-counting kernels
         if (use_partitioned) {
             if (!ctx->d_alive_stats) {   // (four words: builds with KTA_ALIVE_PHASES add instalments and side-table entries)
-                KTA_HIP(ctx, hipMalloc((void **)&ctx->d_alive_stats, 4 * sizeof(uint64_t)));
-                KTA_HIP(ctx, hipHostMalloc((void **)&ctx->h_alive_stats, 4 * sizeof(uint64_t), hipHostMallocDefault));
-                KTA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_alive_stats, hipEventDisableTiming));
+                KTA_HIP(ctx, ctx->d_alive_stats.alloc(4));
+                KTA_HIP(ctx, ctx->h_alive_stats.alloc(4));
+                KTA_HIP(ctx, hipEventCreateWithFlags(ctx->ev_alive_stats.put(), hipEventDisableTiming));
             }
             const bool report = ctx->alive_table && !ctx->alive_stats_pending;       // one report in flight at a time
             // Bit set state: a bucket with more distinct slots than pass 2's LDS table takes is applied in instalments (careful
@@ -417,78 +397,57 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
             // with such buckets in slices of 2^26 records; with the groups sized from the fills a whole batch of config 5's
             // law takes 8.2 ms where four slices took 10.1, and the slicing went.)
             if (!ctx->d_failed_total) {
-                KTA_HIP(ctx, hipMalloc((void **)&ctx->d_failed_total, sizeof(uint64_t)));
-                KTA_HIP(ctx, hipMemsetAsync(ctx->d_failed_total, 0, sizeof(uint64_t), ctx->s_compute));
+                KTA_HIP(ctx, ctx->d_failed_total.alloc(1));
+                KTA_HIP(ctx, hipMemsetAsync(ctx->d_failed_total.get(), 0, sizeof(uint64_t), ctx->s_compute));
             }
-            if (report) KTA_HIP(ctx, hipMemsetAsync(ctx->d_alive_stats, 0, 4 * sizeof(uint64_t), ctx->s_compute));
+            if (report) KTA_HIP(ctx, hipMemsetAsync(ctx->d_alive_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
             for (uint64_t at = 0; at < n;) {
                 const uint64_t left = n - at;
                 kta::AlivePartitionPlan pl = kta::plan_alive_partition(left, ctx->alive_wgs, ctx->cu_count, !ctx->alive_table);
                 const uint64_t take = left < pl.max_records ? left : pl.max_records;
-                if (ctx->pairs_cap < pl.pair_words || ctx->pair_counts_cap < pl.count_words || ctx->pool_cap < pl.pool_words) {
-                    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-                    if (ctx->d_pairs) (void)hipFree(ctx->d_pairs);
-                    if (ctx->d_pair_counts) (void)hipFree(ctx->d_pair_counts);
-                    if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-                    ctx->d_pairs = nullptr;
-                    ctx->d_pair_counts = nullptr;
-                    ctx->d_pool = nullptr;
-                    ctx->pairs_cap = ctx->pair_counts_cap = ctx->pool_cap = 0;
-                    KTA_HIP(ctx, hipMalloc((void **)&ctx->d_pairs, pl.pair_words * sizeof(uint64_t)));
-                    KTA_HIP(ctx, hipMalloc((void **)&ctx->d_pair_counts, pl.count_words * sizeof(uint32_t)));
-                    KTA_HIP(ctx, hipMalloc((void **)&ctx->d_pool, (pl.pool_words + 8) * sizeof(uint64_t)));
-                    ctx->pairs_cap = pl.pair_words;
-                    ctx->pair_counts_cap = pl.count_words;
-                    ctx->pool_cap = pl.pool_words;
-                }
-                if (!ctx->d_pool_ctl) KTA_HIP(ctx, hipMalloc(&ctx->d_pool_ctl, pl.ctl_bytes));
-                if (!ctx->d_fail_from) KTA_HIP(ctx, hipMalloc((void **)&ctx->d_fail_from, 3 * sizeof(uint32_t) << pl.bucket_log2));   // (per bucket + the list of given-up buckets + the list for the slot-range passes)
+                int rc = grow_alive_workspace(ctx, pl);
+                if (rc != KTA_OK) return rc;
                 kta::AliveColumns sl{c->key_len + at, c->val_len + at, c->key_off + at, c->key_bytes,
                                      ctx->alive_table && c->seq ? c->seq + at : nullptr};
-                kta::AliveState st{ctx->alive_table ? ctx->d_table : nullptr, ctx->alive_table ? nullptr : ctx->d_bitmap,
-                                   ctx->d_alive_running, written_list(ctx)};
-                kta::AliveWorkspace ws{ctx->d_pairs, ctx->d_pair_counts, ctx->d_pool, ctx->d_pool_ctl, ctx->d_fail_from, ctx->d_failed_total};
+                kta::AliveState st{ctx->alive_table ? ctx->d_table.get() : nullptr, ctx->alive_table ? nullptr : ctx->d_bitmap.get(),
+                                   ctx->d_alive_running.get(), written_list(ctx)};
+                kta::AliveWorkspace ws{ctx->d_pairs.get(), ctx->d_pair_counts.get(), ctx->d_pool.get(), ctx->d_pool_ctl.get(), ctx->d_fail_from.get(), ctx->d_failed_total.get()};
                 ctx->info_slices++;
                 if (fuse && kta::alive_fuse_possible(pl, ctx->P) && pl.segment_wgs <= ctx->max_rows) {
                     ctx->info_fused++;
                     ctx->handed_records = true;
                     const uint32_t row_len = kta::scan_row_len(ctx->P, false);
                     const kta::ScanColumns sc = scan_cols(at);
-                    const kta::AliveFuse fz{sc.partition, sc.ts_ms, sc.hdr, sc.rec0, ctx->P, ctx->d_partials, row_len};
-                    KTA_HIP(ctx, kta::launch_alive_partitioned(sl, take, base_seq + at, st, pl, ws, report ? ctx->d_alive_stats : nullptr,
+                    const kta::AliveFuse fz{sc.partition, sc.ts_ms, sc.hdr, sc.rec0, ctx->P, ctx->d_partials.get(), row_len};
+                    KTA_HIP(ctx, kta::launch_alive_partitioned(sl, take, base_seq + at, st, pl, ws, report ? ctx->d_alive_stats.get() : nullptr,
                                                                ctx->s_compute, &fz));
-                    KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, pl.segment_wgs, ctx->P, ctx->d_vec, row_len, ctx->d_avec,
+                    KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials.get(), pl.segment_wgs, ctx->P, ctx->d_vec.get(), row_len, ctx->d_avec.get(),
                                                            ctx->s_compute));
                 } else {
                     if (fuse) {      // (a slice the fused pass does not take: its records go through the scan)
                         ctx->info_scanned++;
-                        const kta::ScanColumns sc = scan_cols(at);
-                        kta::ScanPlan spl = kta::plan_scan(ctx->P, take, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics,
-                                                           sc.hdr != nullptr, tl_buckets);
-                        if (spl.workgroups > ctx->max_rows) spl.workgroups = ctx->max_rows;
-                        KTA_HIP(ctx, kta::launch_metrics_scan(spl, sc, take, ctx->P, ctx->d_partials, ctx->s_compute, tl));
-                        KTA_HIP(ctx, kta::launch_fold_partials(ctx->d_partials, spl.workgroups, ctx->P, ctx->d_vec, spl.row_len, ctx->d_avec,
-                                                               ctx->s_compute));
+                        int rc = scan_and_fold(at, take, false);
+                        if (rc != KTA_OK) return rc;
                     }
                     KTA_HIP(ctx, kta::launch_alive_partitioned(sl, take, base_seq + at, st, pl, ws,
-                                                               report ? ctx->d_alive_stats : nullptr, ctx->s_compute));
+                                                               report ? ctx->d_alive_stats.get() : nullptr, ctx->s_compute));
                 }
                 if (sl.seq)   // the batch's seq column did not ascend: the pair did nothing, this runs instead
-                    KTA_HIP(ctx, kta::launch_alive_update(sl, take, base_seq + at, ctx->d_table, 0, 2, nullptr,
-                                                          ctx->d_alive_running, ctx->s_compute,
+                    KTA_HIP(ctx, kta::launch_alive_update(sl, take, base_seq + at, ctx->d_table.get(), 0, 2, nullptr,
+                                                          ctx->d_alive_running.get(), ctx->s_compute,
                                                           kta::alive_order_flag(ws, (int)pl.bucket_log2), written_list(ctx)));
                 at += take;
             }
             if (report) {
-                KTA_HIP(ctx, hipMemcpyAsync(ctx->h_alive_stats, ctx->d_alive_stats, 2 * sizeof(uint64_t),
+                KTA_HIP(ctx, hipMemcpyAsync(ctx->h_alive_stats.get(), ctx->d_alive_stats.get(), 2 * sizeof(uint64_t),
                                             hipMemcpyDeviceToHost, ctx->s_compute));
-                KTA_HIP(ctx, hipEventRecord(ctx->ev_alive_stats, ctx->s_compute));
+                KTA_HIP(ctx, hipEventRecord(ctx->ev_alive_stats.get(), ctx->s_compute));
                 ctx->alive_stats_pending = true;
             }
         } else {
             const int v = part_kind ? 2 : ctx->alive_variant;
-            KTA_HIP(ctx, kta::launch_alive_update(ac, n, base_seq, ctx->d_table, ctx->alive_wgs > 2048 ? 0 : ctx->alive_wgs,
-                                                  v, ctx->d_hash_scratch, ctx->d_alive_running, ctx->s_compute, nullptr,
+            KTA_HIP(ctx, kta::launch_alive_update(ac, n, base_seq, ctx->d_table.get(), ctx->alive_wgs > 2048 ? 0 : ctx->alive_wgs,
+                                                  v, ctx->d_hash_scratch.get(), ctx->d_alive_running.get(), ctx->s_compute, nullptr,
                                                   written_list(ctx)));
         }
         if (ctx->timing) KTA_HIP(ctx, hipEventRecord(b, ctx->s_compute));
@@ -502,28 +461,28 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
 
 int reset_state(kta_ctx *ctx)
 {
-    KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec, ctx->P, ctx->d_avec, ctx->s_compute));
+    KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec.get(), ctx->P, ctx->d_avec.get(), ctx->s_compute));
     if (ctx->timeline)   // the configuration stays
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec, 0, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec.get(), 0, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t), ctx->s_compute));
     if (ctx->sketch) {
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch, 0, (size_t)ctx->P * kta::kSketchRegs * sizeof(uint32_t), ctx->s_compute));
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch_stats, 0, 3 * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch.get(), 0, (size_t)ctx->P * kta::kSketchRegs * sizeof(uint32_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->sketch_launches = 0;
     }
     ctx->handed_records = false;
     if (ctx->alive) {
         if (ctx->alive_table) {
-            KTA_HIP(ctx, hipMemsetAsync(ctx->d_table, 0, kta::kAliveSlots * sizeof(uint64_t), ctx->s_compute));
-            KTA_HIP(ctx, hipMemsetAsync(ctx->d_written_n, 0, sizeof(unsigned long long), ctx->s_compute));
+            KTA_HIP(ctx, hipMemsetAsync(ctx->d_table.get(), 0, kta::kAliveSlots * sizeof(uint64_t), ctx->s_compute));
+            KTA_HIP(ctx, hipMemsetAsync(ctx->d_written_n.get(), 0, sizeof(unsigned long long), ctx->s_compute));
             ctx->written_valid = true;
         } else {
-            KTA_HIP(ctx, hipMemsetAsync(ctx->d_bitmap, 0, (size_t)(kta::kAliveSlots / 8), ctx->s_compute));
+            KTA_HIP(ctx, hipMemsetAsync(ctx->d_bitmap.get(), 0, (size_t)(kta::kAliveSlots / 8), ctx->s_compute));
         }
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_alive_running, 0, sizeof(int64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_alive_running.get(), 0, sizeof(int64_t), ctx->s_compute));
         ctx->running_valid = true;
         // a new topic: what the old one's batches taught about backing off does not carry over (a word still on its way
         // lands in h_alive_stats before any later copy — same stream — and is never looked at)
-        if (ctx->d_failed_total) KTA_HIP(ctx, hipMemsetAsync(ctx->d_failed_total, 0, sizeof(uint64_t), ctx->s_compute));
+        if (ctx->d_failed_total) KTA_HIP(ctx, hipMemsetAsync(ctx->d_failed_total.get(), 0, sizeof(uint64_t), ctx->s_compute));
         ctx->alive_stats_pending = false;
         ctx->alive_backoff = 0;
         ctx->info_slices = ctx->info_fused = ctx->info_scanned = ctx->info_failed_buckets = 0;
@@ -533,7 +492,55 @@ int reset_state(kta_ctx *ctx)
     return KTA_OK;
 }
 
+// One snapshot as a *_result_vector entry point hands it out.
+int hand_out(const ResultVector &v, void **device_ptr, size_t *n_u64)
+{
+    *device_ptr = v.out;
+    *n_u64 = v.words;
+    return KTA_OK;
+}
+
+// `words` u64 words of a vector on the device (a live accumulator or a snapshot), once the compute stream has reached them.
+int read_words(kta_ctx *ctx, const uint64_t *d_src, uint64_t *host, size_t words)
+{
+    KTA_HIP(ctx, hipMemcpyAsync(host, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return KTA_OK;
+}
+
+// the caller's buffer for the vector called `name` has its length
+int check_words(kta_ctx *ctx, const char *name, size_t words, size_t n_u64)
+{
+    if (n_u64 == words) return KTA_OK;
+    return fail(ctx, KTA_ERR_INVALID, std::string("the ") + name + " has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
+}
+
+// acc = acc (+) other by the rule of the result vectors: SUM over [0, sum_words), MAX over the rest
+void merge_words(uint64_t *acc, const uint64_t *other, size_t words, size_t sum_words, bool max_signed)
+{
+    for (size_t i = 0; i < sum_words; i++) acc[i] += other[i];
+    for (size_t i = sum_words; i < words; i++)
+        if (max_signed ? (int64_t)other[i] > (int64_t)acc[i] : other[i] > acc[i]) acc[i] = other[i];
+}
+
 } // namespace
+
+void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
+{
+    const size_t nc = (size_t)ctx->P * KTA_NCOUNTERS, alen = kta::analytics_len(ctx->P);
+    const size_t tlen = ctx->timeline ? kta::timeline_len(ctx->tl.n_buckets) : 0;
+    rv[KTA_RV_COUNTERS] = ResultVector{ctx->d_vec_out.get(), nc + KTA_NGLOBALS, nc + KTA_NSUM_GLOBALS, true};
+    rv[KTA_RV_ANALYTICS] = ResultVector{ctx->d_avec_out.get(), ctx->analytics ? alen : 0, ctx->analytics ? kta::kAnalyticsHist : 0, true};
+    rv[KTA_RV_TIMELINE] = ResultVector{ctx->timeline ? ctx->d_tvec_out.get() : nullptr, tlen, tlen, false};
+    rv[KTA_RV_KEY_SKETCH] = ResultVector{ctx->d_sketch_out.get(), ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0, 0, false};
+}
+
+static ResultVector result_vector(kta_ctx *ctx, int kind)
+{
+    ResultVector rv[KTA_RV_KINDS];
+    kta_internal_result_vectors(ctx, rv);
+    return rv[kind];
+}
 
 extern "C" {
 
@@ -610,38 +617,36 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         hipError_t e__ = (call);                                          \
         if (e__ != hipSuccess) return bail(hip_fail(ctx, e__, #call));    \
     } while (0)
-    KTA_TRY(hipStreamCreateWithFlags(&ctx->s_compute, hipStreamNonBlocking));
-    ctx->s_own = ctx->s_compute;
-    KTA_TRY(hipStreamCreateWithFlags(&ctx->s_copy, hipStreamNonBlocking));
-    KTA_TRY(hipEventCreateWithFlags(&ctx->ev_copied, hipEventDisableTiming));
+    KTA_TRY(hipStreamCreateWithFlags(ctx->s_own.put(), hipStreamNonBlocking));
+    ctx->s_compute = ctx->s_own.get();
+    KTA_TRY(hipStreamCreateWithFlags(ctx->s_copy.put(), hipStreamNonBlocking));
+    KTA_TRY(hipEventCreateWithFlags(ctx->ev_copied.put(), hipEventDisableTiming));
     const size_t vec_words = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
-    KTA_TRY(hipMalloc((void **)&ctx->d_vec, vec_words * sizeof(uint64_t)));
-    KTA_TRY(hipMalloc((void **)&ctx->d_vec_out, vec_words * sizeof(uint64_t)));
+    KTA_TRY(ctx->d_vec.alloc(vec_words));
+    KTA_TRY(ctx->d_vec_out.alloc(vec_words));
     ctx->max_rows = (uint32_t)ctx->cu_count * 8u;
-    KTA_TRY(hipMalloc((void **)&ctx->d_partials,
-                      (size_t)ctx->max_rows * kta::scan_row_len(ctx->P, ctx->analytics) * sizeof(uint64_t)));
+    KTA_TRY(ctx->d_partials.alloc((size_t)ctx->max_rows * kta::scan_row_len(ctx->P, ctx->analytics)));
     if (ctx->analytics) {
-        KTA_TRY(hipMalloc((void **)&ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
-        KTA_TRY(hipMalloc((void **)&ctx->d_avec_out, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_avec.alloc(kta::analytics_len(ctx->P)));
+        KTA_TRY(ctx->d_avec_out.alloc(kta::analytics_len(ctx->P)));
     }
     if (ctx->sketch) {
         const size_t regs = (size_t)ctx->P * kta::kSketchRegs;
-        KTA_TRY(hipMalloc((void **)&ctx->d_sketch, regs * sizeof(uint32_t)));
-        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_out, regs * sizeof(uint64_t)));
-        KTA_TRY(hipMemset(ctx->d_sketch_out, 0, regs * sizeof(uint64_t)));
-        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_floor, kta::kSketchFloorBytes));
-        KTA_TRY(hipMalloc((void **)&ctx->d_sketch_stats, 3 * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_sketch.alloc(regs));
+        KTA_TRY(ctx->d_sketch_out.alloc(regs));
+        KTA_TRY(hipMemset(ctx->d_sketch_out.get(), 0, regs * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_sketch_floor.alloc(kta::kSketchFloorBytes));
+        KTA_TRY(ctx->d_sketch_stats.alloc(3));
     }
     if (ctx->alive) {
         if (ctx->alive_table) {
-            KTA_TRY(hipMalloc((void **)&ctx->d_table, kta::kAliveSlots * sizeof(uint64_t)));
-            ctx->written_cap = 1ull << 28;                 // 1 GiB of slot numbers; beyond that the exchange sweeps the table
-            KTA_TRY(hipMalloc((void **)&ctx->d_written, ctx->written_cap * sizeof(uint32_t)));
-            KTA_TRY(hipMalloc((void **)&ctx->d_written_n, sizeof(unsigned long long)));
+            KTA_TRY(ctx->d_table.alloc(kta::kAliveSlots));
+            KTA_TRY(ctx->d_written.alloc((size_t)1 << 28));   // 1 GiB of slot numbers; beyond that the exchange sweeps the table
+            KTA_TRY(ctx->d_written_n.alloc(1));
         } else {
-            KTA_TRY(hipMalloc((void **)&ctx->d_bitmap, (size_t)(kta::kAliveSlots / 8)));
+            KTA_TRY(ctx->d_bitmap.alloc((size_t)(kta::kAliveSlots / 32)));
         }
-        KTA_TRY(hipMalloc((void **)&ctx->d_alive_running, sizeof(int64_t)));
+        KTA_TRY(ctx->d_alive_running.alloc(1));
     }
 #undef KTA_TRY
     rc = reset_state(ctx);
@@ -657,48 +662,10 @@ void kta_destroy(kta_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->s_compute) (void)hipStreamSynchronize(ctx->s_compute);
-    if (ctx->s_copy) (void)hipStreamSynchronize(ctx->s_copy);
+    if (ctx->s_copy) (void)hipStreamSynchronize(ctx->s_copy.get());
     if (ctx->ext_state && ctx->ext_free) ctx->ext_free(ctx->ext_state);
     if (ctx->comm_state && ctx->comm_free) ctx->comm_free(ctx->comm_state);
-    for (auto &st : ctx->stages) {
-        if (st.host_slab) (void)hipHostFree(st.host_slab);
-        if (st.dev_slab) (void)hipFree(st.dev_slab);
-        if (st.done) (void)hipEventDestroy(st.done);
-    }
-    if (ctx->d_vec) (void)hipFree(ctx->d_vec);
-    if (ctx->d_vec_out) (void)hipFree(ctx->d_vec_out);
-    if (ctx->d_partials) (void)hipFree(ctx->d_partials);
-    if (ctx->d_avec) (void)hipFree(ctx->d_avec);
-    if (ctx->d_avec_out) (void)hipFree(ctx->d_avec_out);
-    if (ctx->d_tvec) (void)hipFree(ctx->d_tvec);
-    if (ctx->d_tvec_out) (void)hipFree(ctx->d_tvec_out);
-    if (ctx->d_sketch) (void)hipFree(ctx->d_sketch);
-    if (ctx->d_sketch_out) (void)hipFree(ctx->d_sketch_out);
-    if (ctx->d_sketch_floor) (void)hipFree(ctx->d_sketch_floor);
-    if (ctx->d_sketch_stats) (void)hipFree(ctx->d_sketch_stats);
-    if (ctx->d_table) (void)hipFree(ctx->d_table);
-    if (ctx->d_bitmap) (void)hipFree(ctx->d_bitmap);
-    if (ctx->d_written) (void)hipFree(ctx->d_written);
-    if (ctx->d_written_n) (void)hipFree(ctx->d_written_n);
-    if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-    if (ctx->d_pool_ctl) (void)hipFree(ctx->d_pool_ctl);
-    if (ctx->d_fail_from) (void)hipFree(ctx->d_fail_from);
-    if (ctx->d_failed_total) (void)hipFree(ctx->d_failed_total);
-    if (ctx->d_hash_scratch) (void)hipFree(ctx->d_hash_scratch);
-    if (ctx->d_alive_stats) (void)hipFree(ctx->d_alive_stats);
-    if (ctx->h_alive_stats) (void)hipHostFree(ctx->h_alive_stats);
-    if (ctx->ev_alive_stats) (void)hipEventDestroy(ctx->ev_alive_stats);
-    if (ctx->d_pairs) (void)hipFree(ctx->d_pairs);
-    if (ctx->d_pair_counts) (void)hipFree(ctx->d_pair_counts);
-    if (ctx->d_alive_running) (void)hipFree(ctx->d_alive_running);
-    if (ctx->d_exp_slots) (void)hipFree(ctx->d_exp_slots);
-    if (ctx->d_exp_vals) (void)hipFree(ctx->d_exp_vals);
-    if (ctx->d_exp_count) (void)hipFree(ctx->d_exp_count);
-    if (ctx->ev_copied) (void)hipEventDestroy(ctx->ev_copied);
-    for (auto &pool : ctx->ev_pool)
-        for (auto ev : pool) (void)hipEventDestroy(ev);
-    if (ctx->s_own) (void)hipStreamDestroy(ctx->s_own);
-    if (ctx->s_copy) (void)hipStreamDestroy(ctx->s_copy);
+    // the context's memory and events, the streams last (the member order of kta_ctx)
     delete ctx;
 }
 
@@ -728,8 +695,8 @@ static int ensure_stage(kta_ctx *ctx, Stage &st)
     }
     st.key_bytes_off = o_kb;
     st.slab_bytes = off;
-    KTA_HIP(ctx, hipHostMalloc((void **)&st.host_slab, off, hipHostMallocDefault));
-    KTA_HIP(ctx, hipMalloc((void **)&st.dev_slab, off));
+    KTA_HIP(ctx, st.host_slab.alloc(off));
+    KTA_HIP(ctx, st.dev_slab.alloc(off));
     auto point = [&](kta_batch &b, uint8_t *base) {
         memset(&b, 0, sizeof b);
         b.capacity = cap;
@@ -744,9 +711,9 @@ static int ensure_stage(kta_ctx *ctx, Stage &st)
             if (seq) b.seq = reinterpret_cast<uint64_t *>(base + o_seq);
         }
     };
-    point(st.host, st.host_slab);
-    point(st.dev, st.dev_slab);
-    KTA_HIP(ctx, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    point(st.host, st.host_slab.get());
+    point(st.dev, st.dev_slab.get());
+    KTA_HIP(ctx, hipEventCreateWithFlags(st.done.put(), hipEventDisableTiming));
     return KTA_OK;
 }
 
@@ -758,7 +725,7 @@ int kta_batch_acquire(kta_ctx *ctx, kta_batch *out)
     int rc = ensure_stage(ctx, st);
     if (rc != KTA_OK) return rc;
     if (st.busy) { // the ring wrapped: wait until the kernels that read this stage are done
-        KTA_HIP(ctx, hipEventSynchronize(st.done));
+        KTA_HIP(ctx, hipEventSynchronize(st.done.get()));
         st.busy = false;
     }
     *out = st.host;
@@ -777,12 +744,12 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
     Stage &st = ctx->stages[ctx->cur];
     ctx->acquired = false;
     if (n == 0) return KTA_OK;
-    hipStream_t cs = ctx->s_copy;
+    hipStream_t cs = ctx->s_copy.get();
     const size_t used = keys ? st.key_bytes_off + n_key_bytes : st.metric_bytes;
     if (n * 2 >= ctx->batch_capacity) {
         // a batch that is at least half full (every batch of a stream but its last): ONE copy of the slab's
         // used prefix — the unused tails of the columns travel along, the launches do not multiply
-        KTA_HIP(ctx, hipMemcpyAsync(st.dev_slab, st.host_slab, used, hipMemcpyHostToDevice, cs));
+        KTA_HIP(ctx, hipMemcpyAsync(st.dev_slab.get(), st.host_slab.get(), used, hipMemcpyHostToDevice, cs));
     } else {
         KTA_HIP(ctx, hipMemcpyAsync(st.dev.partition, st.host.partition, n * 4, hipMemcpyHostToDevice, cs));
         KTA_HIP(ctx, hipMemcpyAsync(st.dev.key_len, st.host.key_len, n * 4, hipMemcpyHostToDevice, cs));
@@ -796,11 +763,11 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
                 KTA_HIP(ctx, hipMemcpyAsync(st.dev.seq, st.host.seq, n * 8, hipMemcpyHostToDevice, cs));
         }
     }
-    KTA_HIP(ctx, hipEventRecord(ctx->ev_copied, cs));
-    KTA_HIP(ctx, hipStreamWaitEvent(ctx->s_compute, ctx->ev_copied, 0));
+    KTA_HIP(ctx, hipEventRecord(ctx->ev_copied.get(), cs));
+    KTA_HIP(ctx, hipStreamWaitEvent(ctx->s_compute, ctx->ev_copied.get(), 0));
     int rc = run_device_batch(ctx, &st.dev, n, base_seq, 3);
     if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipEventRecord(st.done, ctx->s_compute));
+    KTA_HIP(ctx, hipEventRecord(st.done.get(), ctx->s_compute));
     st.busy = true;
     ctx->cur = (ctx->cur + 1) % (int)ctx->stages.size();
     return KTA_OK;
@@ -1068,7 +1035,7 @@ int kta_set_compute_stream(kta_ctx *ctx, void *hip_stream)
     if (!ctx) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // nothing of ours may still be in flight on the old stream
-    ctx->s_compute = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->s_own;
+    ctx->s_compute = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->s_own.get();
     return KTA_OK;
 }
 
@@ -1076,7 +1043,7 @@ int kta_sync(kta_ctx *ctx)
 {
     if (!ctx) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_copy));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_copy.get()));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     return KTA_OK;
 }
@@ -1087,28 +1054,26 @@ int kta_finish_device(kta_ctx *ctx)
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    const size_t words = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
-    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_vec_out, ctx->d_vec, words * sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                ctx->s_compute));
-    if (ctx->analytics)
-        KTA_HIP(ctx, hipMemcpyAsync(ctx->d_avec_out, ctx->d_avec, (size_t)kta::analytics_len(ctx->P) * sizeof(uint64_t),
-                                    hipMemcpyDeviceToDevice, ctx->s_compute));
-    if (ctx->timeline)
-        KTA_HIP(ctx, hipMemcpyAsync(ctx->d_tvec_out, ctx->d_tvec, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t),
-                                    hipMemcpyDeviceToDevice, ctx->s_compute));
+    ResultVector rv[KTA_RV_KINDS];
+    kta_internal_result_vectors(ctx, rv);
+    // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
+    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr};
+    for (int k = 0; k < KTA_RV_KINDS; k++)
+        if (rv[k].out && live[k])
+            KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
     if (ctx->sketch)
-        KTA_HIP(ctx, kta::launch_key_sketch_widen(ctx->d_sketch, (uint64_t)ctx->P * kta::kSketchRegs, ctx->d_sketch_out,
+        KTA_HIP(ctx, kta::launch_key_sketch_widen(ctx->d_sketch.get(), (uint64_t)ctx->P * kta::kSketchRegs, ctx->d_sketch_out.get(),
                                                   ctx->s_compute));
     if (ctx->alive) {
-        uint64_t *dst = ctx->d_vec_out + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
+        uint64_t *dst = ctx->d_vec_out.get() + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
         if (ctx->running_valid)  // exact running count (every update so far ran a counting kernel): no table scan
-            KTA_HIP(ctx, hipMemcpyAsync(dst, ctx->d_alive_running, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+            KTA_HIP(ctx, hipMemcpyAsync(dst, ctx->d_alive_running.get(), sizeof(uint64_t), hipMemcpyDeviceToDevice,
                                         ctx->s_compute));
         else if (ctx->alive_table)
-            KTA_HIP(ctx, kta::launch_alive_count(ctx->d_table, kta::kAliveSlots, dst, ctx->s_compute));
+            KTA_HIP(ctx, kta::launch_alive_count(ctx->d_table.get(), kta::kAliveSlots, dst, ctx->s_compute));
         else {
             KTA_HIP(ctx, hipMemsetAsync(dst, 0, sizeof(uint64_t), ctx->s_compute));
-            KTA_HIP(ctx, kta::launch_bitmap_count(ctx->d_bitmap, dst, ctx->s_compute));
+            KTA_HIP(ctx, kta::launch_bitmap_count(ctx->d_bitmap.get(), dst, ctx->s_compute));
         }
     }
     return KTA_OK;
@@ -1117,9 +1082,7 @@ int kta_finish_device(kta_ctx *ctx)
 int kta_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    *device_ptr = ctx->d_vec_out;
-    *n_u64 = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
-    return KTA_OK;
+    return hand_out(result_vector(ctx, KTA_RV_COUNTERS), device_ptr, n_u64);
 }
 
 int kta_decode_vector(const uint64_t *vec, uint32_t P, int count_alive_keys, kta_result *out,
@@ -1161,9 +1124,7 @@ int kta_merge_vectors(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
     if (!acc || !other || P == 0) return KTA_ERR_INVALID;
     const size_t nc = (size_t)P * KTA_NCOUNTERS;
-    for (size_t i = 0; i < nc + KTA_NSUM_GLOBALS; i++) acc[i] += other[i];
-    for (size_t i = nc + KTA_NSUM_GLOBALS; i < nc + KTA_NGLOBALS; i++)
-        if ((int64_t)other[i] > (int64_t)acc[i]) acc[i] = other[i];
+    merge_words(acc, other, nc + KTA_NGLOBALS, nc + KTA_NSUM_GLOBALS, true);
     return KTA_OK;
 }
 
@@ -1179,12 +1140,11 @@ int kta_exchange_result(kta_ctx *ctx, kta_result *out, uint64_t *counters_out)
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t words = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
-    std::vector<uint64_t> host(words);
-    KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_vec_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    int rc = kta_decode_vector(host.data(), ctx->P, ctx->alive ? 1 : 0, out, counters_out);
+    const ResultVector v = result_vector(ctx, KTA_RV_COUNTERS);
+    std::vector<uint64_t> host(v.words);
+    int rc = read_words(ctx, v.out, host.data(), v.words);
+    if (rc != KTA_OK) return rc;
+    rc = kta_decode_vector(host.data(), ctx->P, ctx->alive ? 1 : 0, out, counters_out);
     if (rc == KTA_ERR_BAD_PARTITION) {
         char buf[128];
         snprintf(buf, sizeof buf, "%llu record(s) had a partition id outside [0, %u)",
@@ -1201,7 +1161,7 @@ int kta_analytics_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    *device_ptr = ctx->d_avec;
+    *device_ptr = ctx->d_avec.get();
     *n_u64 = kta::analytics_len(ctx->P);
     return KTA_OK;
 }
@@ -1229,24 +1189,8 @@ int kta_decode_analytics(const uint64_t *vec, uint32_t P, kta_analytics *out, in
 int kta_merge_analytics(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
     if (!acc || !other || P == 0) return KTA_ERR_INVALID;
-    for (size_t i = 0; i < kta::kAnalyticsHist; i++) acc[i] += other[i];
-    for (size_t i = kta::kAnalyticsHist; i < kta::analytics_len(P); i++)
-        if ((int64_t)other[i] > (int64_t)acc[i]) acc[i] = other[i];
+    merge_words(acc, other, kta::analytics_len(P), kta::kAnalyticsHist, true);
     return KTA_OK;
-}
-
-int kta_analytics_max_partitions(void)
-{
-    // the analytics scan's dynamic LDS (plan_scan; replication backs off to 1 first) plus its static reduction
-    // arrays (kta_metrics_scan's s_red) within one workgroup's LDS on gfx950
-    const uint32_t lds_limit = 160u * 1024u, static_lds = (kta::kWG / 64u) * 6u * 8u;
-    uint32_t lo = 0, hi = 4096;
-    while (lo < hi) {   // lds_bytes grows with P: the largest P that fits
-        const uint32_t mid = (lo + hi + 1) / 2;
-        if (kta::plan_scan(mid, 1, 1, 1, 0, true).lds_bytes + static_lds <= lds_limit) lo = mid;
-        else hi = mid - 1;
-    }
-    return (int)lo;
 }
 
 // the analytics vector at `d_vec` (the live accumulator or its snapshot) copied to the host and decoded
@@ -1254,9 +1198,8 @@ static int read_analytics(kta_ctx *ctx, const uint64_t *d_vec, kta_analytics *ou
                           int64_t *part_max_ts_sec, uint64_t *part_smallest, uint64_t *part_largest)
 {
     std::vector<uint64_t> host(kta::analytics_len(ctx->P));
-    KTA_HIP(ctx, hipMemcpyAsync(host.data(), d_vec, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    int rc = read_words(ctx, d_vec, host.data(), host.size());
+    if (rc != KTA_OK) return rc;
     return kta_decode_analytics(host.data(), ctx->P, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
 
@@ -1268,7 +1211,7 @@ int kta_get_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    return read_analytics(ctx, ctx->d_avec, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+    return read_analytics(ctx, ctx->d_avec.get(), out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
 
 int kta_exchange_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
@@ -1277,16 +1220,14 @@ int kta_exchange_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_t
     if (!ctx || !out) return KTA_ERR_INVALID;
     if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_analytics(ctx, ctx->d_avec_out, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+    return read_analytics(ctx, ctx->d_avec_out.get(), out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
 
 int kta_analytics_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    *device_ptr = ctx->d_avec_out;
-    *n_u64 = kta::analytics_len(ctx->P);
-    return KTA_OK;
+    return hand_out(result_vector(ctx, KTA_RV_ANALYTICS), device_ptr, n_u64);
 }
 
 // The largest P whose scan plan (raw and tile-compact) with `timeline_buckets` (0: none) fits one workgroup's LDS on
@@ -1304,6 +1245,8 @@ static uint32_t max_partitions_for(bool analytics, uint32_t timeline_buckets)
     }
     return lo;
 }
+
+int kta_analytics_max_partitions(void) { return (int)max_partitions_for(true, 0); }
 
 int kta_timeline_max_partitions(uint32_t flags, uint32_t n_buckets)
 {
@@ -1332,21 +1275,20 @@ int kta_set_timeline(kta_ctx *ctx, int64_t origin_ms, int64_t bucket_ms, uint32_
     const size_t words = kta::timeline_len(n_buckets);
     if (!ctx->timeline || ctx->tl.n_buckets != n_buckets) {
         KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-        if (ctx->d_tvec) (void)hipFree(ctx->d_tvec);
-        if (ctx->d_tvec_out) (void)hipFree(ctx->d_tvec_out);
-        ctx->d_tvec = ctx->d_tvec_out = nullptr;
+        ctx->d_tvec.reset();
+        ctx->d_tvec_out.reset();
         ctx->timeline = false;
-        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_tvec, words * sizeof(uint64_t)));
-        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_tvec_out, words * sizeof(uint64_t)));
+        KTA_HIP(ctx, ctx->d_tvec.alloc(words));
+        KTA_HIP(ctx, ctx->d_tvec_out.alloc(words));
     }
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec, 0, words * sizeof(uint64_t), ctx->s_compute));
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec_out, 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec_out.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
     ctx->tl.origin = origin_ms;
     ctx->tl.width = (unsigned long long)bucket_ms;
     ctx->tl.span = (unsigned long long)bucket_ms * n_buckets;
     ctx->tl.inv_width = (float)(1.0 / (double)bucket_ms);
     ctx->tl.n_buckets = n_buckets;
-    ctx->tl.vec = ctx->d_tvec;
+    ctx->tl.vec = ctx->d_tvec.get();
     ctx->timeline = true;
     return KTA_OK;
 }
@@ -1356,11 +1298,8 @@ static int timeline_copy(kta_ctx *ctx, const uint64_t *d_src, uint64_t *out, siz
     if (!out) return KTA_ERR_INVALID;
     if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
     const size_t words = kta::timeline_len(ctx->tl.n_buckets);
-    if (n_u64 != words)
-        return fail(ctx, KTA_ERR_INVALID, "the timeline has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
-    KTA_HIP(ctx, hipMemcpyAsync(out, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    return KTA_OK;
+    int rc = check_words(ctx, "timeline", words, n_u64);
+    return rc != KTA_OK ? rc : read_words(ctx, d_src, out, words);
 }
 
 int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
@@ -1370,7 +1309,7 @@ int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    return timeline_copy(ctx, ctx->d_tvec, out, n_u64);
+    return timeline_copy(ctx, ctx->d_tvec.get(), out, n_u64);
 }
 
 int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
@@ -1378,14 +1317,14 @@ int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
     if (!ctx) return KTA_ERR_INVALID;
     if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return timeline_copy(ctx, ctx->d_tvec_out, out, n_u64);
+    return timeline_copy(ctx, ctx->d_tvec_out.get(), out, n_u64);
 }
 
 int kta_timeline_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    *device_ptr = ctx->d_tvec;
+    *device_ptr = ctx->d_tvec.get();
     *n_u64 = kta::timeline_len(ctx->tl.n_buckets);
     return KTA_OK;
 }
@@ -1394,20 +1333,12 @@ int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    *device_ptr = ctx->d_tvec_out;
-    *n_u64 = kta::timeline_len(ctx->tl.n_buckets);
-    return KTA_OK;
+    return hand_out(result_vector(ctx, KTA_RV_TIMELINE), device_ptr, n_u64);
 }
 
 static const char *const kNoSketch = "context was created without KTA_FLAG_KEY_SKETCH";
 
-static int sketch_words(kta_ctx *ctx, size_t n_u64)
-{
-    const size_t words = (size_t)ctx->P * kta::kSketchRegs;
-    if (n_u64 != words)
-        return fail(ctx, KTA_ERR_INVALID, "the key sketch has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
-    return KTA_OK;
-}
+static int sketch_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "key sketch", (size_t)ctx->P * kta::kSketchRegs, n_u64); }
 
 int kta_get_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
 {
@@ -1419,7 +1350,7 @@ int kta_get_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
     rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
     std::vector<uint32_t> host(n_u64);   // the live registers are u32
-    KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_sketch, n_u64 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_sketch.get(), n_u64 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->s_compute));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     for (size_t i = 0; i < n_u64; i++) out[i] = host[i];
     return KTA_OK;
@@ -1432,18 +1363,14 @@ int kta_exchange_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
     int rc = sketch_words(ctx, n_u64);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_sketch_out, n_u64 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    return KTA_OK;
+    return read_words(ctx, ctx->d_sketch_out.get(), out, n_u64);
 }
 
 int kta_key_sketch_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
-    *device_ptr = ctx->d_sketch_out;
-    *n_u64 = (size_t)ctx->P * kta::kSketchRegs;
-    return KTA_OK;
+    return hand_out(result_vector(ctx, KTA_RV_KEY_SKETCH), device_ptr, n_u64);
 }
 
 int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4])
@@ -1451,18 +1378,15 @@ int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4])
     if (!ctx || !out) return KTA_ERR_INVALID;
     if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_sketch_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    int rc = read_words(ctx, ctx->d_sketch_stats.get(), out, 3);
     out[3] = ctx->sketch_launches;
-    return KTA_OK;
+    return rc;
 }
 
 int kta_merge_key_sketch(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
     if (!acc || !other || P == 0 || P > KTA_SKETCH_MAX_PARTITIONS) return KTA_ERR_INVALID;
-    const size_t words = (size_t)P * KTA_SKETCH_REGISTERS;
-    for (size_t i = 0; i < words; i++)
-        if (other[i] > acc[i]) acc[i] = other[i];
+    merge_words(acc, other, (size_t)P * KTA_SKETCH_REGISTERS, 0, false);
     return KTA_OK;
 }
 
@@ -1543,19 +1467,18 @@ int kta_export_alive_bitmap(kta_ctx *ctx, void *dst)
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    uint32_t *d_bm = nullptr;
     const size_t bytes = (size_t)(kta::kAliveSlots / 8);
     if (!ctx->alive_table) {       // the state IS the reference's bit set
-        KTA_HIP(ctx, hipMemcpyAsync(dst, ctx->d_bitmap, bytes, hipMemcpyDeviceToHost, ctx->s_compute));
+        KTA_HIP(ctx, hipMemcpyAsync(dst, ctx->d_bitmap.get(), bytes, hipMemcpyDeviceToHost, ctx->s_compute));
         KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
         return KTA_OK;
     }
-    KTA_HIP(ctx, hipMalloc((void **)&d_bm, bytes));
-    hipError_t e = kta::launch_alive_bitmap(ctx->d_table, kta::kAliveSlots, d_bm, ctx->s_compute);
-    if (e == hipSuccess) e = hipMemcpyAsync(dst, d_bm, bytes, hipMemcpyDeviceToHost, ctx->s_compute);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
-    (void)hipFree(d_bm);
-    if (e != hipSuccess) return hip_fail(ctx, e, "alive bitmap export");
+    DeviceBuf<uint32_t> d_bm;   // (released on every return; hipFree waits for the device first)
+    KTA_HIP(ctx, d_bm.alloc(bytes / sizeof(uint32_t)));
+    const char *const what = "alive bitmap export";
+    KTA_HIP_AS(ctx, kta::launch_alive_bitmap(ctx->d_table.get(), kta::kAliveSlots, d_bm.get(), ctx->s_compute), what);
+    KTA_HIP_AS(ctx, hipMemcpyAsync(dst, d_bm.get(), bytes, hipMemcpyDeviceToHost, ctx->s_compute), what);
+    KTA_HIP_AS(ctx, hipStreamSynchronize(ctx->s_compute), what);
     return KTA_OK;
 }
 
@@ -1564,7 +1487,7 @@ int kta_alive_table(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
     if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
     if (!ctx->alive) return fail(ctx, KTA_ERR_INVALID, "context was created without count_alive_keys");
     if (!ctx->alive_table) return fail(ctx, KTA_ERR_INVALID, kNeedsTable);
-    *device_ptr = ctx->d_table;
+    *device_ptr = ctx->d_table.get();
     *n_u64 = (size_t)kta::kAliveSlots;
     return KTA_OK;
 }
@@ -1578,26 +1501,24 @@ int kta_alive_export_entries(kta_ctx *ctx, void **d_slots, void **d_vals, uint64
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
     hipStream_t s = ctx->s_compute;
-    if (!ctx->d_exp_count) KTA_HIP(ctx, hipMalloc((void **)&ctx->d_exp_count, sizeof(uint64_t)));
+    if (!ctx->d_exp_count) KTA_HIP(ctx, ctx->d_exp_count.alloc(1));
     uint64_t written = 0;
-    KTA_HIP(ctx, kta::launch_alive_count_written(ctx->d_table, kta::kAliveSlots, ctx->d_exp_count, s));
-    KTA_HIP(ctx, hipMemcpyAsync(&written, ctx->d_exp_count, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    KTA_HIP(ctx, kta::launch_alive_count_written(ctx->d_table.get(), kta::kAliveSlots, ctx->d_exp_count.get(), s));
+    KTA_HIP(ctx, hipMemcpyAsync(&written, ctx->d_exp_count.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     KTA_HIP(ctx, hipStreamSynchronize(s));
-    if (ctx->exp_cap < written) {
-        if (ctx->d_exp_slots) (void)hipFree(ctx->d_exp_slots);
-        if (ctx->d_exp_vals) (void)hipFree(ctx->d_exp_vals);
-        ctx->d_exp_slots = nullptr;
-        ctx->d_exp_vals = nullptr;
-        ctx->exp_cap = written + written / 8 + 1024;
-        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_exp_slots, ctx->exp_cap * sizeof(uint32_t)));
-        KTA_HIP(ctx, hipMalloc((void **)&ctx->d_exp_vals, ctx->exp_cap * sizeof(uint64_t)));
+    if (ctx->d_exp_vals.size() < written) {   // (the stream is idle: both lists go before either comes back)
+        const size_t cap = written + written / 8 + 1024;
+        ctx->d_exp_slots.reset();
+        ctx->d_exp_vals.reset();
+        KTA_HIP(ctx, ctx->d_exp_slots.alloc(cap));
+        KTA_HIP(ctx, ctx->d_exp_vals.alloc(cap));
     }
     if (written)
-        KTA_HIP(ctx, kta::launch_alive_export(ctx->d_table, kta::kAliveSlots, ctx->d_exp_slots, ctx->d_exp_vals,
-                                              ctx->d_exp_count, ctx->exp_cap, s));
+        KTA_HIP(ctx, kta::launch_alive_export(ctx->d_table.get(), kta::kAliveSlots, ctx->d_exp_slots.get(), ctx->d_exp_vals.get(),
+                                              ctx->d_exp_count.get(), ctx->d_exp_vals.size(), s));
     KTA_HIP(ctx, hipStreamSynchronize(s));
-    *d_slots = ctx->d_exp_slots;
-    *d_vals = ctx->d_exp_vals;
+    *d_slots = ctx->d_exp_slots.get();
+    *d_vals = ctx->d_exp_vals.get();
     *n = written;
     return KTA_OK;
 }
@@ -1611,7 +1532,7 @@ int kta_alive_import_entries(kta_ctx *ctx, const void *d_slots, const void *d_va
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, kta::launch_alive_import(static_cast<const uint32_t *>(d_slots), static_cast<const uint64_t *>(d_vals),
-                                          n, ctx->d_table, ctx->d_alive_running, written_list(ctx), ctx->s_compute));
+                                          n, ctx->d_table.get(), ctx->d_alive_running.get(), written_list(ctx), ctx->s_compute));
     return KTA_OK;
 }
 
@@ -1624,9 +1545,9 @@ int kta_alive_count_range(kta_ctx *ctx, uint64_t slot_lo, uint64_t slot_hi, uint
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
     hipStream_t s = ctx->s_compute;
-    if (!ctx->d_exp_count) KTA_HIP(ctx, hipMalloc((void **)&ctx->d_exp_count, sizeof(uint64_t)));
-    KTA_HIP(ctx, kta::launch_alive_count_span(ctx->d_table, slot_lo, slot_hi, ctx->d_exp_count, s));
-    KTA_HIP(ctx, hipMemcpyAsync(count, ctx->d_exp_count, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (!ctx->d_exp_count) KTA_HIP(ctx, ctx->d_exp_count.alloc(1));
+    KTA_HIP(ctx, kta::launch_alive_count_span(ctx->d_table.get(), slot_lo, slot_hi, ctx->d_exp_count.get(), s));
+    KTA_HIP(ctx, hipMemcpyAsync(count, ctx->d_exp_count.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     KTA_HIP(ctx, hipStreamSynchronize(s));
     return KTA_OK;
 }
@@ -1646,25 +1567,21 @@ int kta_fnv32_device(kta_ctx *ctx, const uint8_t *key_bytes, const uint32_t *key
     if (!ctx || !key_off || !key_len || !hash_out) return KTA_ERR_INVALID;
     if (n == 0) return KTA_OK;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    uint8_t *d_kb = nullptr;
-    uint32_t *d_off = nullptr, *d_out = nullptr;
-    int32_t *d_len = nullptr;
-    hipError_t e = hipMalloc((void **)&d_kb, pad16(n_key_bytes + 16));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_off, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_len, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, n * 4);
+    DeviceBuf<uint8_t> d_kb;
+    DeviceBuf<uint32_t> d_off, d_out;
+    DeviceBuf<int32_t> d_len;
+    const char *const what = "kta_fnv32_device";
     hipStream_t s = ctx->s_compute;
-    if (e == hipSuccess && n_key_bytes) e = hipMemcpyAsync(d_kb, key_bytes, n_key_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, key_off, n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, key_len, n * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = kta::launch_fnv32(d_kb, d_off, d_len, n, d_out, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hash_out, d_out, n * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (d_kb) (void)hipFree(d_kb);
-    if (d_off) (void)hipFree(d_off);
-    if (d_len) (void)hipFree(d_len);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return hip_fail(ctx, e, "kta_fnv32_device");
+    KTA_HIP_AS(ctx, d_kb.alloc(pad16(n_key_bytes + 16)), what);
+    KTA_HIP_AS(ctx, d_off.alloc(n), what);
+    KTA_HIP_AS(ctx, d_len.alloc(n), what);
+    KTA_HIP_AS(ctx, d_out.alloc(n), what);
+    if (n_key_bytes) KTA_HIP_AS(ctx, hipMemcpyAsync(d_kb.get(), key_bytes, n_key_bytes, hipMemcpyHostToDevice, s), what);
+    KTA_HIP_AS(ctx, hipMemcpyAsync(d_off.get(), key_off, n * 4, hipMemcpyHostToDevice, s), what);
+    KTA_HIP_AS(ctx, hipMemcpyAsync(d_len.get(), key_len, n * 4, hipMemcpyHostToDevice, s), what);
+    KTA_HIP_AS(ctx, kta::launch_fnv32(d_kb.get(), d_off.get(), d_len.get(), n, d_out.get(), s), what);
+    KTA_HIP_AS(ctx, hipMemcpyAsync(hash_out, d_out.get(), n * 4, hipMemcpyDeviceToHost, s), what);
+    KTA_HIP_AS(ctx, hipStreamSynchronize(s), what);
     return KTA_OK;
 }
 
@@ -1679,15 +1596,7 @@ int kta_kernel_time_stats(kta_ctx *ctx, float avg_ms[3], uint64_t launches[3])
 {
     if (!ctx || !avg_ms || !launches) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = drain_timers(ctx);
-    if (rc != KTA_OK) return rc;
-    for (int k = 0; k < 3; k++) {
-        launches[k] = ctx->ms_cnt[k];
-        avg_ms[k] = ctx->ms_cnt[k] ? (float)(ctx->ms_sum[k] / (double)ctx->ms_cnt[k]) : -1.f;
-        ctx->ms_sum[k] = 0;
-        ctx->ms_cnt[k] = 0;
-    }
-    return KTA_OK;
+    return ctx->timers.stats(ctx, ctx->s_compute, avg_ms, launches);
 }
 
 int kta_set_tuning(kta_ctx *ctx, int scan_workgroups, int scan_variant, int alive_workgroups, int alive_variant)
@@ -1715,7 +1624,7 @@ int kta_alive_pass_info(kta_ctx *ctx, uint64_t out[6])
     ctx->info_failed_buckets = 0;
     if (ctx->d_failed_total) {
         KTA_HIP(ctx, hipSetDevice(ctx->device));
-        KTA_HIP(ctx, hipMemcpyAsync(&ctx->info_failed_buckets, ctx->d_failed_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+        KTA_HIP(ctx, hipMemcpyAsync(&ctx->info_failed_buckets, ctx->d_failed_total.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
         KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     }
     out[0] = kta::kAlivePartitionMax;
@@ -1729,7 +1638,7 @@ int kta_alive_pass_info(kta_ctx *ctx, uint64_t out[6])
 
 } // extern "C"
 
-// exported for kta_synth.hip / kta_kafka.hip (same shared object)
+// what kta_internal.h declares for the other translation units of the library
 void **kta_internal_ext_slot(kta_ctx *ctx, void (*free_fn)(void *))
 {
     ctx->ext_free = free_fn;
@@ -1740,28 +1649,16 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *))
     ctx->comm_free = free_fn;
     return &ctx->comm_state;
 }
-uint64_t *kta_internal_vec_out(kta_ctx *ctx) { return ctx->d_vec_out; }
-uint64_t *kta_internal_avec_out(kta_ctx *ctx) { return ctx->d_avec_out; }
-uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64)
-{
-    *n_u64 = ctx->timeline ? kta::timeline_len(ctx->tl.n_buckets) : 0;
-    return ctx->timeline ? ctx->d_tvec_out : nullptr;
-}
-uint64_t *kta_internal_sketch_out(kta_ctx *ctx, size_t *n_u64)
-{
-    *n_u64 = ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0;
-    return ctx->sketch ? ctx->d_sketch_out : nullptr;
-}
 bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch; }
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
-uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table; }
+uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {
-    *out = kta::WrittenList{ctx->d_written, ctx->d_written_n, ctx->written_cap};
-    return ctx->written_valid && ctx->d_written != nullptr;
+    *out = kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()};
+    return ctx->written_valid && ctx->d_written.get();
 }
-int64_t *kta_internal_running(kta_ctx *ctx) { return ctx->d_alive_running; }
+int64_t *kta_internal_running(kta_ctx *ctx) { return ctx->d_alive_running.get(); }
 uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n)
 {
     const uint64_t base = ctx->next_seq;
@@ -1769,14 +1666,12 @@ uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n)
     return base;
 }
 bool kta_internal_timing(kta_ctx *ctx) { return ctx->timing; }
-hipStream_t kta_internal_copy_stream(kta_ctx *ctx) { return ctx->s_copy; }
+hipStream_t kta_internal_copy_stream(kta_ctx *ctx) { return ctx->s_copy.get(); }
 bool kta_internal_count_alive(kta_ctx *ctx) { return ctx->alive; }
 hipStream_t kta_internal_stream(kta_ctx *ctx) { return ctx->s_compute; }
 int kta_internal_device(kta_ctx *ctx) { return ctx->device; }
 void kta_internal_set_error(kta_ctx *ctx, const char *msg) { ctx->err = msg; }
 
-// Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
-// allocation that the range overlaps become raw (kta::launch_tiles_to_raw), on the compute stream.
 int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
 {
     Resolved r{};
@@ -1786,7 +1681,6 @@ int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
     return KTA_OK;
 }
 
-// The allocation's columns and the batch's first record there (hdr null: the raw layout).
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
                          uint64_t *rec0)
 {

@@ -27,6 +27,7 @@
 // RCCL is bound at run time (dlopen, RTLD_LOCAL): a process that also imports PyTorch keeps PyTorch's own
 // bundled RCCL apart from this one, and contexts that never exchange never load it.
 #include "../../include/kta_hip.h"
+#include "kta_internal.h"
 #include "kta_kernels.h"
 
 #include <dlfcn.h>
@@ -36,21 +37,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-hipStream_t kta_internal_stream(kta_ctx *ctx);
-int kta_internal_device(kta_ctx *ctx);
-void kta_internal_set_error(kta_ctx *ctx, const char *msg);
-void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *));
-bool kta_internal_count_alive(kta_ctx *ctx);
-bool kta_internal_alive_table(kta_ctx *ctx);
-uint64_t *kta_internal_vec_out(kta_ctx *ctx);
-uint64_t *kta_internal_avec_out(kta_ctx *ctx);
-uint64_t *kta_internal_tvec_out(kta_ctx *ctx, size_t *n_u64);
-uint64_t *kta_internal_sketch_out(kta_ctx *ctx, size_t *n_u64);
-uint32_t kta_internal_partitions(kta_ctx *ctx);
-uint64_t *kta_internal_table(kta_ctx *ctx);
-int64_t *kta_internal_running(kta_ctx *ctx);
-bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);
 
 namespace {
 
@@ -136,12 +122,11 @@ Rccl *rccl()
 struct CommState {
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-    uint64_t *d_counts = nullptr;      // [nranks] entries this rank sends to every owner, then [nranks x nranks] gathered, ..., the overflow flag
-    uint64_t *h_pinned = nullptr;      // pinned: [nranks + nranks x nranks + 1] read back, then [nranks] offsets of the owners' lists
-    uint64_t *d_scalar = nullptr;
-    uint32_t *d_send_slots = nullptr, *d_recv_slots = nullptr;
-    uint64_t *d_send_vals = nullptr, *d_recv_vals = nullptr;
-    uint64_t send_cap = 0, recv_cap = 0;
+    DeviceBuf<uint64_t> d_counts;      // [nranks] entries this rank sends to every owner, then [nranks x nranks] gathered, ..., the overflow flag
+    PinnedBuf<uint64_t> h_pinned;      // pinned: [nranks + nranks x nranks + 1] read back, then [nranks] offsets of the owners' lists
+    DeviceBuf<uint64_t> d_scalar;
+    DeviceBuf<uint32_t> d_send_slots, d_recv_slots;
+    DeviceBuf<uint64_t> d_send_vals, d_recv_vals;
     uint64_t last_sent = 0, last_received = 0;
     bool aborted = false;
 };
@@ -151,29 +136,8 @@ void free_comm(void *p)
     CommState *st = static_cast<CommState *>(p);
     if (!st) return;
     if (st->comm && rccl()->CommDestroy) (void)rccl()->CommDestroy(st->comm);
-    if (st->d_counts) (void)hipFree(st->d_counts);
-    if (st->h_pinned) (void)hipHostFree(st->h_pinned);
-    if (st->d_scalar) (void)hipFree(st->d_scalar);
-    if (st->d_send_slots) (void)hipFree(st->d_send_slots);
-    if (st->d_recv_slots) (void)hipFree(st->d_recv_slots);
-    if (st->d_send_vals) (void)hipFree(st->d_send_vals);
-    if (st->d_recv_vals) (void)hipFree(st->d_recv_vals);
     delete st;
 }
-
-int fail(kta_ctx *ctx, int code, const std::string &m)
-{
-    kta_internal_set_error(ctx, m.c_str());
-    return code;
-}
-
-#define CH(ctx, call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e__ = (call);                                                                          \
-        if (e__ != hipSuccess)                                                                            \
-            return fail(ctx, e__ == hipErrorOutOfMemory ? KTA_ERR_NOMEM : KTA_ERR_HIP,                    \
-                        std::string(#call) + ": " + hipGetErrorString(e__));                              \
-    } while (0)
 
 #define CN(ctx, call)                                                                                     \
     do {                                                                                                  \
@@ -185,18 +149,15 @@ int fail(kta_ctx *ctx, int code, const std::string &m)
 // first slot owned by rank r of R: owner(slot) == (slot * R) >> 32
 uint64_t range_lo(int r, int R) { return (((uint64_t)r << 32) + (uint64_t)R - 1) / (uint64_t)R; }
 
-int grow(kta_ctx *ctx, uint32_t **slots, uint64_t **vals, uint64_t *cap, uint64_t need)
+// a (slot, value) list for `need` entries: both halves go before either comes back, an eighth larger than asked for
+int grow(kta_ctx *ctx, DeviceBuf<uint32_t> &slots, DeviceBuf<uint64_t> &vals, uint64_t need)
 {
-    if (*cap >= need) return KTA_OK;
-    if (*slots) (void)hipFree(*slots);
-    if (*vals) (void)hipFree(*vals);
-    *slots = nullptr;
-    *vals = nullptr;
-    *cap = 0;
+    if (vals.size() >= need) return KTA_OK;
+    slots.reset();
+    vals.reset();
     const uint64_t want = need + need / 8 + 1024;
-    CH(ctx, hipMalloc((void **)slots, want * sizeof(uint32_t)));
-    CH(ctx, hipMalloc((void **)vals, want * sizeof(uint64_t)));
-    *cap = want;
+    KTA_HIP(ctx, slots.alloc(want));
+    KTA_HIP(ctx, vals.alloc(want));
     return KTA_OK;
 }
 
@@ -219,27 +180,28 @@ int exchange_alive(kta_ctx *ctx, CommState *st)
     const int n = st->nranks;
     // what a rank contributes to the all-gather: its n counts and its overflow flag; what comes back: n such rows
     const size_t row = (size_t)n + 1, n_read = row + row * n;
-    if (!st->d_counts) CH(ctx, hipMalloc((void **)&st->d_counts, (n_read + 2 * (size_t)n) * sizeof(uint64_t)));
-    if (!st->h_pinned) CH(ctx, hipHostMalloc((void **)&st->h_pinned, (n_read + (size_t)n) * sizeof(uint64_t), hipHostMallocDefault));
-    if (!st->d_scalar) CH(ctx, hipMalloc((void **)&st->d_scalar, sizeof(uint64_t)));
+    if (!st->d_counts) KTA_HIP(ctx, st->d_counts.alloc(n_read + 2 * (size_t)n));
+    if (!st->h_pinned) KTA_HIP(ctx, st->h_pinned.alloc(n_read + (size_t)n));
+    if (!st->d_scalar) KTA_HIP(ctx, st->d_scalar.alloc(1));
+    uint64_t *const d_counts = st->d_counts.get();
     kta::WrittenList wl;
     bool listed = kta_internal_written(ctx, &wl);
     if (n > 64) listed = false;                          // the list kernels keep one LDS counter per owner, 64 of them: sweep
-    uint64_t *d_flag = st->d_counts + n, *d_owner_at = st->d_counts + n_read, *d_cursors = d_owner_at + n;
-    const uint64_t *send = st->h_pinned, *matrix = st->h_pinned + row;          // matrix[r * row + o]: rank r's entries for owner o
-    uint64_t *h_owner_at = st->h_pinned + n_read;
+    uint64_t *d_flag = d_counts + n, *d_owner_at = d_counts + n_read, *d_cursors = d_owner_at + n;
+    const uint64_t *send = st->h_pinned.get(), *matrix = send + row;          // matrix[r * row + o]: rank r's entries for owner o
+    uint64_t *h_owner_at = st->h_pinned.get() + n_read;
     // 1. how many entries does this rank hold for every owner
     for (int attempt = 0;; attempt++) {
-        CH(ctx, hipMemsetAsync(st->d_counts, 0, row * sizeof(uint64_t), s));
+        KTA_HIP(ctx, hipMemsetAsync(d_counts, 0, row * sizeof(uint64_t), s));
         if (listed) {
-            CH(ctx, kta::launch_written_count(wl, n, st->d_counts, d_flag, s));
+            KTA_HIP(ctx, kta::launch_written_count(wl, n, d_counts, d_flag, s));
         } else {
             for (int r = 0; r < n; r++)
-                CH(ctx, kta::launch_alive_count_written_span(table, range_lo(r, n), range_lo(r + 1, n), st->d_counts + r, s));
+                KTA_HIP(ctx, kta::launch_alive_count_written_span(table, range_lo(r, n), range_lo(r + 1, n), d_counts + r, s));
         }
-        CN(ctx, R->AllGather(st->d_counts, st->d_counts + row, row, ncclUint64, st->comm, s));
-        CH(ctx, hipMemcpyAsync(st->h_pinned, st->d_counts, n_read * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        CH(ctx, hipStreamSynchronize(s));                // THE synchronisation of the exchange
+        CN(ctx, R->AllGather(d_counts, d_counts + row, row, ncclUint64, st->comm, s));
+        KTA_HIP(ctx, hipMemcpyAsync(st->h_pinned.get(), d_counts, n_read * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        KTA_HIP(ctx, hipStreamSynchronize(s));                // THE synchronisation of the exchange
         // A list that overflowed (only its device knew) counted its first entries only: that rank counts again, with
         // sweeps — and every rank gathers again, because all of them have to issue the same collectives: the flags
         // travel with the counts, so all ranks see the same ones and decide alike.
@@ -263,23 +225,25 @@ int exchange_alive(kta_ctx *ctx, CommState *st)
         recv_at[r] = recv_total;
         if (r != st->rank) recv_total += matrix[(size_t)r * row + st->rank];
     }
-    int rc = grow(ctx, &st->d_send_slots, &st->d_send_vals, &st->send_cap, send_total);
+    int rc = grow(ctx, st->d_send_slots, st->d_send_vals, send_total);
     if (rc != KTA_OK) return rc;
-    rc = grow(ctx, &st->d_recv_slots, &st->d_recv_vals, &st->recv_cap, recv_total);
+    rc = grow(ctx, st->d_recv_slots, st->d_recv_vals, recv_total);
     if (rc != KTA_OK) return rc;
+    uint32_t *const send_slots = st->d_send_slots.get(), *const recv_slots = st->d_recv_slots.get();
+    uint64_t *const send_vals = st->d_send_vals.get(), *const recv_vals = st->d_recv_vals.get();
     // 2. one contiguous list per owner (the rank's own range stays where it is)
     if (listed) {
         if (send_total) {
             for (int r = 0; r < n; r++) h_owner_at[r] = send_at[r];
-            CH(ctx, hipMemcpyAsync(d_owner_at, h_owner_at, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, s));   // (pinned: no wait)
-            CH(ctx, hipMemsetAsync(d_cursors, 0, (size_t)n * sizeof(uint64_t), s));
-            CH(ctx, kta::launch_written_export(wl, table, n, st->rank, d_owner_at, d_cursors, st->d_send_slots, st->d_send_vals, s));
+            KTA_HIP(ctx, hipMemcpyAsync(d_owner_at, h_owner_at, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, s));   // (pinned: no wait)
+            KTA_HIP(ctx, hipMemsetAsync(d_cursors, 0, (size_t)n * sizeof(uint64_t), s));
+            KTA_HIP(ctx, kta::launch_written_export(wl, table, n, st->rank, d_owner_at, d_cursors, send_slots, send_vals, s));
         }
     } else {
         for (int r = 0; r < n; r++) {
             if (r == st->rank || send[r] == 0) continue;
-            CH(ctx, kta::launch_alive_export_span(table, range_lo(r, n), range_lo(r + 1, n), st->d_send_slots + send_at[r],
-                                                  st->d_send_vals + send_at[r], st->d_scalar, send[r], s));
+            KTA_HIP(ctx, kta::launch_alive_export_span(table, range_lo(r, n), range_lo(r + 1, n), send_slots + send_at[r],
+                                                  send_vals + send_at[r], st->d_scalar.get(), send[r], s));
         }
     }
     // 3. every list to its owner: one grouped launch, all links at once
@@ -288,25 +252,27 @@ int exchange_alive(kta_ctx *ctx, CommState *st)
         if (r == st->rank) continue;
         const uint64_t ns = send[r], nr = matrix[(size_t)r * row + st->rank];
         if (ns) {
-            CN(ctx, R->Send(st->d_send_slots + send_at[r], ns, ncclUint32, r, st->comm, s));
-            CN(ctx, R->Send(st->d_send_vals + send_at[r], ns, ncclUint64, r, st->comm, s));
+            CN(ctx, R->Send(send_slots + send_at[r], ns, ncclUint32, r, st->comm, s));
+            CN(ctx, R->Send(send_vals + send_at[r], ns, ncclUint64, r, st->comm, s));
         }
         if (nr) {
-            CN(ctx, R->Recv(st->d_recv_slots + recv_at[r], nr, ncclUint32, r, st->comm, s));
-            CN(ctx, R->Recv(st->d_recv_vals + recv_at[r], nr, ncclUint64, r, st->comm, s));
+            CN(ctx, R->Recv(recv_slots + recv_at[r], nr, ncclUint32, r, st->comm, s));
+            CN(ctx, R->Recv(recv_vals + recv_at[r], nr, ncclUint64, r, st->comm, s));
         }
     }
     CN(ctx, R->GroupEnd());
     // 4. the owner merges (last writer by global sequence number; new slots join its list) and counts its range
     if (recv_total)
-        CH(ctx, kta::launch_alive_import(st->d_recv_slots, st->d_recv_vals, recv_total, table, kta_internal_running(ctx), wl, s));
-    uint64_t *dst = kta_internal_vec_out(ctx) + (size_t)kta_internal_partitions(ctx) * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
+        KTA_HIP(ctx, kta::launch_alive_import(recv_slots, recv_vals, recv_total, table, kta_internal_running(ctx), wl, s));
+    ResultVector rv[KTA_RV_KINDS];
+    kta_internal_result_vectors(ctx, rv);
+    uint64_t *dst = rv[KTA_RV_COUNTERS].out + (size_t)kta_internal_partitions(ctx) * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
     if (listed) {
         // (the list may have grown by the import, past its capacity even: the kernels read its length on the device, and
         // the range itself is counted when the list is no longer complete)
-        CH(ctx, kta::launch_written_alive_count(wl, table, range_lo(st->rank, n), range_lo(st->rank + 1, n), dst, s));
+        KTA_HIP(ctx, kta::launch_written_alive_count(wl, table, range_lo(st->rank, n), range_lo(st->rank + 1, n), dst, s));
     } else {
-        CH(ctx, kta::launch_alive_count_span(table, range_lo(st->rank, n), range_lo(st->rank + 1, n), dst, s));
+        KTA_HIP(ctx, kta::launch_alive_count_span(table, range_lo(st->rank, n), range_lo(st->rank + 1, n), dst, s));
     }
     st->last_sent = send_total;
     st->last_received = recv_total;
@@ -336,7 +302,7 @@ int kta_comm_create(kta_ctx *ctx, int nranks, int rank, const uint8_t id[KTA_COM
     if (*slot) return fail(ctx, KTA_ERR_INVALID, "kta_comm_create: the context already has a communicator");
     if (nranks > 1 && kta_internal_count_alive(ctx) && !kta_internal_alive_table(ctx))
         return fail(ctx, KTA_ERR_INVALID, "kta_comm_create: a -c rank of a sharded run needs KTA_FLAG_ALIVE_TABLE (global sequence numbers)");
-    CH(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     CommState *st = new CommState();
     st->nranks = nranks;
     st->rank = rank;
@@ -393,29 +359,25 @@ static int exchange_failed(CommState *st, int rc)
 
 static int exchange_collectives(kta_ctx *ctx, CommState *st)
 {
-    CH(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     if (kta_internal_count_alive(ctx) && kta_internal_alive_table(ctx)) {
         int rc = exchange_alive(ctx, st);
         if (rc != KTA_OK) return rc;
     }
     Rccl *R = rccl();
     hipStream_t s = kta_internal_stream(ctx);
-    uint64_t *vec = kta_internal_vec_out(ctx);
-    const size_t sum_words = (size_t)kta_internal_partitions(ctx) * KTA_NCOUNTERS + KTA_NSUM_GLOBALS;
+    // Every snapshot the context has (every rank of the job has the same sections, flags and timeline), in their fixed
+    // order: the SUM prefix, then the MAX suffix, a half of no words left out.  Ranks pair their collectives by order.
+    ResultVector rv[KTA_RV_KINDS];
+    kta_internal_result_vectors(ctx, rv);
     CN(ctx, R->GroupStart());
-    CN(ctx, R->AllReduce(vec, vec, sum_words, ncclUint64, ncclSum, st->comm, s));
-    CN(ctx, R->AllReduce(vec + sum_words, vec + sum_words, KTA_NGLOBALS - KTA_NSUM_GLOBALS, ncclInt64, ncclMax, st->comm, s));
-    if (uint64_t *avec = kta_internal_avec_out(ctx)) {   // KTA_FLAG_ANALYTICS: every rank of the job has it
-        const size_t hist = kta::kAnalyticsHist, extrema = kta::analytics_len(kta_internal_partitions(ctx)) - hist;
-        CN(ctx, R->AllReduce(avec, avec, hist, ncclUint64, ncclSum, st->comm, s));
-        CN(ctx, R->AllReduce(avec + hist, avec + hist, extrema, ncclInt64, ncclMax, st->comm, s));
+    for (const ResultVector &v : rv) {
+        if (!v.out) continue;
+        uint64_t *const mx = v.out + v.sum_words;
+        if (v.sum_words) CN(ctx, R->AllReduce(v.out, v.out, v.sum_words, ncclUint64, ncclSum, st->comm, s));
+        if (v.words > v.sum_words)
+            CN(ctx, R->AllReduce(mx, mx, v.words - v.sum_words, v.max_signed ? ncclInt64 : ncclUint64, ncclMax, st->comm, s));
     }
-    size_t tl_words = 0;
-    if (uint64_t *tvec = kta_internal_tvec_out(ctx, &tl_words))   // a timeline: every rank of the job has the same one
-        CN(ctx, R->AllReduce(tvec, tvec, tl_words, ncclUint64, ncclSum, st->comm, s));
-    size_t sk_words = 0;
-    if (uint64_t *svec = kta_internal_sketch_out(ctx, &sk_words))  // a key sketch: every rank of the job has the flag
-        CN(ctx, R->AllReduce(svec, svec, sk_words, ncclUint64, ncclMax, st->comm, s));
     CN(ctx, R->GroupEnd());
     return KTA_OK;
 }
@@ -441,19 +403,19 @@ int kta_comm_allreduce_i64(kta_ctx *ctx, int64_t *host_values, size_t n, int op_
     CommState *st = static_cast<CommState *>(*slot);
     if (!st) return fail(ctx, KTA_ERR_INVALID, "kta_comm_allreduce_i64 without kta_comm_create");
     if (!st->comm || n == 0) return KTA_OK;
-    CH(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     hipStream_t s = kta_internal_stream(ctx);
-    int64_t *d = nullptr;
-    CH(ctx, hipMalloc((void **)&d, n * sizeof(int64_t)));
-    hipError_t e = hipMemcpyAsync(d, host_values, n * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    int r = ncclSuccess;
-    if (e == hipSuccess) r = rccl()->AllReduce(d, d, n, ncclInt64, op_max ? ncclMax : ncclSum, st->comm, s);
-    if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(host_values, d, n * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d);
+    DeviceBuf<int64_t> d;
+    KTA_HIP(ctx, d.alloc(n));
+    // (a step that fails after the allocation answers KTA_ERR_HIP whatever the error, as it always has)
+    auto failed = [&](hipError_t e) { return fail(ctx, KTA_ERR_HIP, std::string("kta_comm_allreduce_i64: ") + hipGetErrorString(e)); };
+    hipError_t e = hipMemcpyAsync(d.get(), host_values, n * sizeof(int64_t), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return failed(e);
+    const int r = rccl()->AllReduce(d.get(), d.get(), n, ncclInt64, op_max ? ncclMax : ncclSum, st->comm, s);
+    if (r == ncclSuccess) e = hipMemcpyAsync(host_values, d.get(), n * sizeof(int64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // also after a collective that failed: what was enqueued still reads d
     if (r != ncclSuccess) return fail(ctx, KTA_ERR_COMM, std::string("ncclAllReduce: ") + rccl()->GetErrorString(r));
-    if (e != hipSuccess) return fail(ctx, KTA_ERR_HIP, std::string("kta_comm_allreduce_i64: ") + hipGetErrorString(e));
-    return KTA_OK;
+    return e == hipSuccess ? KTA_OK : failed(e);
 }
 
 int kta_comm_info(kta_ctx *ctx, int *nranks, int *rank, uint64_t *entries_sent, uint64_t *entries_received)

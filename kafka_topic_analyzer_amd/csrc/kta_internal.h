@@ -1,0 +1,218 @@
+// kta_internal.h — what the host code of libkta_hip.so shares between its translation units (kta_api.hip,
+// kta_comm.hip, kta_kafka.hip, kta_synth.hip): the context's internal accessors, the HIP-error macro, the owners
+// of device and pinned memory, streams and events, the event-pair timing pool and the description of the result
+// vectors.  Host code only; not installed, not part of the ABI.  The library is linked with -z defs: a
+// declaration here without a definition fails the build.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "kta_hip.h"
+
+namespace kta {
+struct WrittenList;   // kta_kernels.h
+}
+
+// ---- the context, as the other translation units see it (defined in kta_api.hip) ----------------------------------
+// Sets the context's message and returns `code`.  ctx null: the thread's kta_create message (kta_last_error(NULL)).
+int kta_internal_fail(kta_ctx *ctx, int code, const std::string &msg);
+void kta_internal_set_error(kta_ctx *ctx, const char *msg);
+void **kta_internal_ext_slot(kta_ctx *ctx, void (*free_fn)(void *));    // kta_kafka.hip's state
+void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *));   // kta_comm.hip's state
+int kta_internal_device(kta_ctx *ctx);
+hipStream_t kta_internal_stream(kta_ctx *ctx);
+hipStream_t kta_internal_copy_stream(kta_ctx *ctx);
+bool kta_internal_timing(kta_ctx *ctx);
+uint32_t kta_internal_partitions(kta_ctx *ctx);
+bool kta_internal_want_keys(kta_ctx *ctx);   // -c or the key sketch: the handlers read key_off / key_bytes
+bool kta_internal_count_alive(kta_ctx *ctx);
+bool kta_internal_alive_table(kta_ctx *ctx);
+uint64_t *kta_internal_table(kta_ctx *ctx);
+int64_t *kta_internal_running(kta_ctx *ctx);
+bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);
+uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
+// Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
+// allocation that the range overlaps become raw, on the compute stream.
+int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
+// The allocation's columns and the batch's first record there (hdr null: the raw layout).
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
+                         uint64_t *rec0);
+
+// ---- result vectors -----------------------------------------------------------------------------------------------
+// Every section of the result has a snapshot that kta_finish_device takes and kta_exchange reduces in place: words
+// [0, sum_words) with u64 SUM, words [sum_words, words) with MAX (i64 when max_signed, else u64).  A new opt-in
+// section adds a kind here and a row in kta_internal_result_vectors.
+//
+//   kind        u64 words          SUM prefix     MAX suffix
+//   counters    P*7 + 8            P*7 + 4        4      (i64)
+//   analytics   68 + 4*P           68             4*P    (i64)
+//   timeline    (n_buckets+3)*3    all            none
+//   key sketch  P*4096             none           all    (u64)
+struct ResultVector {
+    uint64_t *out;     // the snapshot (device); null: the context has no such section
+    size_t words, sum_words;
+    bool max_signed;
+};
+enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_KINDS };
+void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);
+
+// ---- errors -------------------------------------------------------------------------------------------------------
+static inline int fail(kta_ctx *ctx, int code, const std::string &msg) { return kta_internal_fail(ctx, code, msg); }
+
+// "<what>: <hipGetErrorString>"; out of memory is KTA_ERR_NOMEM, everything else KTA_ERR_HIP
+static inline int hip_fail(kta_ctx *ctx, hipError_t e, const char *what)
+{
+    return fail(ctx, e == hipErrorOutOfMemory ? KTA_ERR_NOMEM : KTA_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// a step that fails ends the function, reported under `what`
+#define KTA_HIP_AS(ctx, call, what)                                \
+    do {                                                           \
+        hipError_t e__ = (call);                                   \
+        if (e__ != hipSuccess) return hip_fail(ctx, e__, what);    \
+    } while (0)
+#define KTA_HIP(ctx, call) KTA_HIP_AS(ctx, call, #call)
+
+// ---- owners -------------------------------------------------------------------------------------------------------
+// Move-only owner of `size()` elements of device (hipMalloc) or pinned host (hipHostMalloc) memory.
+template <class T, bool Pinned> class HipBuf {
+    T *p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    HipBuf() = default;
+    HipBuf(const HipBuf &) = delete;
+    HipBuf &operator=(const HipBuf &) = delete;
+    HipBuf(HipBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    HipBuf &operator=(HipBuf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
+        }
+        return *this;
+    }
+    ~HipBuf() { reset(); }
+    T *get() const { return p_; }
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset()
+    {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr, n_ = 0;
+    }
+    // The growth policy of every buffer here: release first, then allocate n elements (the caller chooses n, and waits
+    // for whatever may still read the old memory).  Goes inside KTA_HIP; after a failure the owner is empty.
+    hipError_t alloc(size_t n)
+    {
+        reset();
+        void *p = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T));
+        if (e == hipSuccess) p_ = static_cast<T *>(p), n_ = n;
+        return e;
+    }
+};
+template <class T> using DeviceBuf = HipBuf<T, false>;
+template <class T> using PinnedBuf = HipBuf<T, true>;
+
+// Move-only owner of a stream or an event: `Create(x.put(), ...)` fills it.
+template <class H, hipError_t (*Destroy)(H)> class HipHandle {
+    H h_ = nullptr;
+
+public:
+    HipHandle() = default;
+    HipHandle(const HipHandle &) = delete;
+    HipHandle &operator=(const HipHandle &) = delete;
+    HipHandle(HipHandle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    HipHandle &operator=(HipHandle &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    ~HipHandle() { reset(); }
+    H get() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+    H *put()
+    {
+        reset();
+        return &h_;
+    }
+    void reset()
+    {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+};
+using Stream = HipHandle<hipStream_t, hipStreamDestroy>;
+using Event = HipHandle<hipEvent_t, hipEventDestroy>;
+
+// ---- timing ---------------------------------------------------------------------------------------------------------
+// HIP-event pairs recorded around the kernels of `Kinds` kinds on one stream (no host synchronisation while recording),
+// drained into a sum and a count per kind.  A kind holds at most max_events events before it drains.
+template <int Kinds> struct TimerPool {
+    size_t max_events;
+    std::vector<Event> ev[Kinds];
+    size_t used[Kinds] = {};
+    double ms_sum[Kinds] = {};
+    uint64_t ms_cnt[Kinds] = {};
+
+    explicit TimerPool(size_t max_events_) : max_events(max_events_) {}
+
+    int drain(kta_ctx *ctx, hipStream_t s)
+    {
+        KTA_HIP(ctx, hipStreamSynchronize(s));
+        for (int k = 0; k < Kinds; k++) {
+            for (size_t i = 0; i + 1 < used[k]; i += 2) {
+                float ms = 0.f;
+                KTA_HIP(ctx, hipEventElapsedTime(&ms, ev[k][i].get(), ev[k][i + 1].get()));
+                ms_sum[k] += ms;
+                ms_cnt[k] += 1;
+            }
+            used[k] = 0;
+        }
+        return KTA_OK;
+    }
+
+    // next (start, stop) event pair of kernel kind k
+    int pair(kta_ctx *ctx, hipStream_t s, int k, hipEvent_t *a, hipEvent_t *b)
+    {
+        if (used[k] + 2 > max_events) {
+            int rc = drain(ctx, s);
+            if (rc != KTA_OK) return rc;
+        }
+        while (ev[k].size() < used[k] + 2) {
+            Event e;
+            KTA_HIP(ctx, hipEventCreate(e.put()));
+            ev[k].push_back(std::move(e));
+        }
+        *a = ev[k][used[k]].get();
+        *b = ev[k][used[k] + 1].get();
+        used[k] += 2;
+        return KTA_OK;
+    }
+
+    // drain, report the averages (-1: no launch) and start over
+    int stats(kta_ctx *ctx, hipStream_t s, float *avg_ms, uint64_t *launches)
+    {
+        int rc = drain(ctx, s);
+        if (rc != KTA_OK) return rc;
+        for (int k = 0; k < Kinds; k++) {
+            launches[k] = ms_cnt[k];
+            avg_ms[k] = ms_cnt[k] ? (float)(ms_sum[k] / (double)ms_cnt[k]) : -1.f;
+            ms_sum[k] = 0;
+            ms_cnt[k] = 0;
+        }
+        return KTA_OK;
+    }
+};

@@ -27,6 +27,7 @@
 #include "kta_gzip.h"
 #include "kta_zstd.h"
 #include "kta_records.h"
+#include "kta_internal.h"
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -34,16 +35,6 @@
 
 #include <string>
 #include <vector>
-
-hipStream_t kta_internal_stream(kta_ctx *ctx);
-int kta_internal_device(kta_ctx *ctx);
-void kta_internal_set_error(kta_ctx *ctx, const char *msg);
-void **kta_internal_ext_slot(kta_ctx *ctx, void (*free_fn)(void *));
-uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
-bool kta_internal_timing(kta_ctx *ctx);
-bool kta_internal_want_keys(kta_ctx *ctx);   // -c or the key sketch: the handlers read key_off / key_bytes
-hipStream_t kta_internal_copy_stream(kta_ctx *ctx);
-int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
 
 namespace {
 
@@ -1140,14 +1131,13 @@ __global__ __launch_bounds__(64) void kafka_crc32c(const uint4 *blocks, kta_kafk
 // One stage of the raw-log pipeline: a pinned host blob the fetcher fills, its device copy, the
 // pinned batch index and the decoded columns.
 struct BlobStage {
-    uint8_t *h_blob = nullptr, *d_blob = nullptr;
-    uint64_t cap = 0;      // host blob capacity
-    uint64_t d_cap = 0;    // device buffer capacity: the blob plus the inflate area of compressed batches
-    kta_kafka_batch_desc *h_descs = nullptr; // pinned: the H2D copy of the index is truly asynchronous
-    uint64_t desc_cap = 0;
-    kta_batch out{};
+    PinnedBuf<uint8_t> h_blob;
+    DeviceBuf<uint8_t> d_blob;   // the blob plus the inflate area of compressed batches
+    uint64_t cap = 0;            // host blob capacity (h_blob holds 64 bytes more)
+    PinnedBuf<kta_kafka_batch_desc> h_descs; // pinned: the H2D copy of the index is truly asynchronous
+    kta_batch out{};             // raw pointers: handed to kta_submit_device as a batch (free_out)
     uint64_t out_cap = 0;
-    hipEvent_t copied = nullptr, done = nullptr;
+    Event copied, done;
     bool busy = false;
 };
 
@@ -1157,14 +1147,13 @@ struct KafkaState {
     // kernels of call k instead of in front of its own: round 5's bench line had a step of 0.396 ms around a 0.210 ms kernel,
     // now 0.23-0.25 around 0.21-0.22.  (Descriptors in pinned memory — the upload a DMA the host does not wait for — were tried
     // as an API and dropped: a host that enqueues that far ahead of the GPU met 9 ms stalls of the runtime every few calls.)
-    kta_kafka_batch_desc *d_descs2[2] = {nullptr, nullptr};
-    uint64_t desc_cap2[2] = {0, 0};
-    hipEvent_t ev_desc_up[2] = {nullptr, nullptr}, ev_desc_free[2] = {nullptr, nullptr};   // uploaded (copy stream) / no longer read (compute stream)
+    DeviceBuf<kta_kafka_batch_desc> d_descs2[2];
+    Event ev_desc_up[2], ev_desc_free[2];   // uploaded (copy stream) / no longer read (compute stream)
     bool desc_used[2] = {false, false};
     int desc_slot = 0;
-    uint64_t *d_scalars = nullptr; // [0] key-byte total, [1] bad batches
-    CrcTables *d_crc_tables = nullptr;
-    uint64_t *d_crc_bad = nullptr;  // CRC failures since the context was created
+    DeviceBuf<uint64_t> d_scalars; // [0] key-byte total, [1] bad batches
+    DeviceBuf<CrcTables> d_crc_tables;
+    DeviceBuf<uint64_t> d_crc_bad;  // CRC failures since the context was created
     bool check_crcs = false;
     std::vector<BlobStage> stages;
     uint64_t blob_capacity = 256ull << 20;
@@ -1172,10 +1161,7 @@ struct KafkaState {
     int variant = 0;                // kta_kafka_set_variant: 0 = automatic, 1 = lane per batch, 2 / 10 / 11 = wave geometries
     int cur = 0;
     bool acquired = false;
-    std::vector<hipEvent_t> ev[2];
-    size_t ev_used[2] = {0, 0};
-    double ms_sum[2] = {0, 0};
-    uint64_t ms_cnt[2] = {0, 0};
+    TimerPool<2> timers{1024};      // kind 0: the CRC kernel, 1: the decode
 };
 
 void free_out(kta_batch &o)
@@ -1192,24 +1178,7 @@ void free_state(void *p)
 {
     KafkaState *st = static_cast<KafkaState *>(p);
     if (!st) return;
-    for (int k = 0; k < 2; k++) {
-        if (st->d_descs2[k]) (void)hipFree(st->d_descs2[k]);
-        if (st->ev_desc_up[k]) (void)hipEventDestroy(st->ev_desc_up[k]);
-        if (st->ev_desc_free[k]) (void)hipEventDestroy(st->ev_desc_free[k]);
-    }
-    if (st->d_scalars) (void)hipFree(st->d_scalars);
-    if (st->d_crc_tables) (void)hipFree(st->d_crc_tables);
-    if (st->d_crc_bad) (void)hipFree(st->d_crc_bad);
-    for (auto &g : st->stages) {
-        if (g.h_blob) (void)hipHostFree(g.h_blob);
-        if (g.d_blob) (void)hipFree(g.d_blob);
-        if (g.h_descs) (void)hipHostFree(g.h_descs);
-        free_out(g.out);
-        if (g.copied) (void)hipEventDestroy(g.copied);
-        if (g.done) (void)hipEventDestroy(g.done);
-    }
-    for (auto &v : st->ev)
-        for (auto e : v) (void)hipEventDestroy(e);
+    for (auto &g : st->stages) free_out(g.out);
     delete st;
 }
 
@@ -1220,54 +1189,9 @@ KafkaState *state_of(kta_ctx *ctx)
     return static_cast<KafkaState *>(*slot);
 }
 
-int hip_err(kta_ctx *ctx, hipError_t e, const char *what)
-{
-    std::string m = std::string(what) + ": " + hipGetErrorString(e);
-    kta_internal_set_error(ctx, m.c_str());
-    return e == hipErrorOutOfMemory ? KTA_ERR_NOMEM : KTA_ERR_HIP;
-}
-
-#define KK(ctx, call)                                            \
-    do {                                                         \
-        hipError_t e__ = (call);                                 \
-        if (e__ != hipSuccess) return hip_err(ctx, e__, #call);  \
-    } while (0)
-
 inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 inline uint64_t be64(const uint8_t *p) { return ((uint64_t)be32(p) << 32) | be32(p + 4); }
 inline uint16_t be16(const uint8_t *p) { return (uint16_t)(((uint16_t)p[0] << 8) | p[1]); }
-
-int drain(kta_ctx *ctx, KafkaState *st)
-{
-    KK(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
-    for (int k = 0; k < 2; k++) {
-        for (size_t i = 0; i + 1 < st->ev_used[k]; i += 2) {
-            float ms = 0.f;
-            KK(ctx, hipEventElapsedTime(&ms, st->ev[k][i], st->ev[k][i + 1]));
-            st->ms_sum[k] += ms;
-            st->ms_cnt[k]++;
-        }
-        st->ev_used[k] = 0;
-    }
-    return KTA_OK;
-}
-
-int pair(kta_ctx *ctx, KafkaState *st, int k, hipEvent_t *a, hipEvent_t *b)
-{
-    if (st->ev_used[k] + 2 > 1024) {
-        int rc = drain(ctx, st);
-        if (rc != KTA_OK) return rc;
-    }
-    while (st->ev[k].size() < st->ev_used[k] + 2) {
-        hipEvent_t e;
-        KK(ctx, hipEventCreate(&e));
-        st->ev[k].push_back(e);
-    }
-    *a = st->ev[k][st->ev_used[k]];
-    *b = st->ev[k][st->ev_used[k] + 1];
-    st->ev_used[k] += 2;
-    return KTA_OK;
-}
 
 } // namespace
 
@@ -1579,15 +1503,11 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
     if (n_bad_batches) *n_bad_batches = 0;
     if (n_batches == 0) return KTA_OK;
     if (!blob_device || !descs_host) return KTA_ERR_INVALID;
-    if ((reinterpret_cast<uintptr_t>(blob_device) & 15u) != 0) {
-        kta_internal_set_error(ctx, "blob_device must be 16-byte aligned (and padded to a multiple of 16 bytes)");
-        return KTA_ERR_INVALID;
-    }
-    if (n_records > out->capacity) {
-        kta_internal_set_error(ctx, "decoded records exceed the output batch capacity");
-        return KTA_ERR_CAPACITY;
-    }
-    KK(ctx, hipSetDevice(kta_internal_device(ctx)));
+    if ((reinterpret_cast<uintptr_t>(blob_device) & 15u) != 0)
+        return fail(ctx, KTA_ERR_INVALID, "blob_device must be 16-byte aligned (and padded to a multiple of 16 bytes)");
+    if (n_records > out->capacity)
+        return fail(ctx, KTA_ERR_CAPACITY, "decoded records exceed the output batch capacity");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     hipStream_t s = kta_internal_stream(ctx);
     // the decode stores the raw layout: the output's tiles become raw tiles first (a tile-compact batch, kta_hip.h)
     if (int rc = kta_internal_prepare_raw(ctx, out, n_records)) return rc;
@@ -1596,38 +1516,34 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
     const int dk = st->desc_slot;
     st->desc_slot ^= 1;
     if (!st->ev_desc_up[dk]) {
-        KK(ctx, hipEventCreateWithFlags(&st->ev_desc_up[dk], hipEventDisableTiming));
-        KK(ctx, hipEventCreateWithFlags(&st->ev_desc_free[dk], hipEventDisableTiming));
+        KTA_HIP(ctx, hipEventCreateWithFlags(st->ev_desc_up[dk].put(), hipEventDisableTiming));
+        KTA_HIP(ctx, hipEventCreateWithFlags(st->ev_desc_free[dk].put(), hipEventDisableTiming));
     }
-    if (st->desc_cap2[dk] < n_batches) {
-        KK(ctx, hipStreamSynchronize(s));
-        KK(ctx, hipStreamSynchronize(cs));
-        if (st->d_descs2[dk]) (void)hipFree(st->d_descs2[dk]);
-        st->d_descs2[dk] = nullptr;
-        KK(ctx, hipMalloc((void **)&st->d_descs2[dk], n_batches * sizeof(kta_kafka_batch_desc)));
-        st->desc_cap2[dk] = n_batches;
+    if (st->d_descs2[dk].size() < n_batches) {
+        KTA_HIP(ctx, hipStreamSynchronize(s));
+        KTA_HIP(ctx, hipStreamSynchronize(cs));
+        KTA_HIP(ctx, st->d_descs2[dk].alloc(n_batches));
         st->desc_used[dk] = false;
     }
-    kta_kafka_batch_desc *const d_descs = st->d_descs2[dk];
+    kta_kafka_batch_desc *const d_descs = st->d_descs2[dk].get();
     if (!st->d_scalars) {
-        KK(ctx, hipMalloc((void **)&st->d_scalars, 2 * sizeof(uint64_t)));
-        KK(ctx, hipMemsetAsync(st->d_scalars, 0, 2 * sizeof(uint64_t), s));
+        KTA_HIP(ctx, st->d_scalars.alloc(2));
+        KTA_HIP(ctx, hipMemsetAsync(st->d_scalars.get(), 0, 2 * sizeof(uint64_t), s));
     }
+    uint64_t *const d_scalars = st->d_scalars.get();
     // (the kernels of the call before last read this buffer: the copy waits for them on the device, not the host)
-    if (st->desc_used[dk]) KK(ctx, hipStreamWaitEvent(cs, st->ev_desc_free[dk], 0));
-    KK(ctx, hipMemcpyAsync(d_descs, descs_host, n_batches * sizeof(kta_kafka_batch_desc), hipMemcpyHostToDevice, cs));
-    KK(ctx, hipEventRecord(st->ev_desc_up[dk], cs));
-    KK(ctx, hipStreamWaitEvent(s, st->ev_desc_up[dk], 0));
+    if (st->desc_used[dk]) KTA_HIP(ctx, hipStreamWaitEvent(cs, st->ev_desc_free[dk].get(), 0));
+    KTA_HIP(ctx, hipMemcpyAsync(d_descs, descs_host, n_batches * sizeof(kta_kafka_batch_desc), hipMemcpyHostToDevice, cs));
+    KTA_HIP(ctx, hipEventRecord(st->ev_desc_up[dk].get(), cs));
+    KTA_HIP(ctx, hipStreamWaitEvent(s, st->ev_desc_up[dk].get(), 0));
     st->desc_used[dk] = true;
     if (n_bad_batches || n_key_bytes)   // per-call counts wanted: start from zero (otherwise they accumulate)
-        KK(ctx, hipMemsetAsync(st->d_scalars, 0, 2 * sizeof(uint64_t), s));
+        KTA_HIP(ctx, hipMemsetAsync(d_scalars, 0, 2 * sizeof(uint64_t), s));
     // Zero-copy keys: key_off[i] is the key's offset inside the raw blob, so the caller passes the
     // blob itself as `key_bytes` to kta_submit_device; nothing is copied.  out->key_bytes is ignored.
     const bool want_keys = out->key_off != nullptr;
-    if (want_keys && blob_len >= (1ull << 32)) {
-        kta_internal_set_error(ctx, "record set must be < 4 GiB when key offsets are wanted (key_off is u32)");
-        return KTA_ERR_CAPACITY;
-    }
+    if (want_keys && blob_len >= (1ull << 32))
+        return fail(ctx, KTA_ERR_CAPACITY, "record set must be < 4 GiB when key offsets are wanted (key_off is u32)");
     const bool timing = kta_internal_timing(ctx);
     const uint32_t grid = (uint32_t)((n_batches + kLanesPerBlock - 1) / kLanesPerBlock);
     const uint4 *words = reinterpret_cast<const uint4 *>(blob_device);
@@ -1635,20 +1551,19 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
     uint64_t scal[2] = {0, 0};
     if (st->check_crcs) {   // librdkafka check.crcs=true: verify every batch before it is decoded
         if (!st->d_crc_tables) {
-            CrcTables *host = new CrcTables();
-            build_crc_tables(*host);
-            hipError_t e = hipMalloc((void **)&st->d_crc_tables, sizeof(CrcTables));
-            if (e == hipSuccess) e = hipMemcpy(st->d_crc_tables, host, sizeof(CrcTables), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMalloc((void **)&st->d_crc_bad, sizeof(uint64_t));
-            if (e == hipSuccess) e = hipMemset(st->d_crc_bad, 0, sizeof(uint64_t));
-            delete host;
-            if (e != hipSuccess) return hip_err(ctx, e, "CRC-32C tables");
+            std::vector<CrcTables> host(1);   // (too large for the stack)
+            build_crc_tables(host[0]);
+            const char *const what = "CRC-32C tables";
+            KTA_HIP_AS(ctx, st->d_crc_tables.alloc(1), what);
+            KTA_HIP_AS(ctx, hipMemcpy(st->d_crc_tables.get(), host.data(), sizeof(CrcTables), hipMemcpyHostToDevice), what);
+            KTA_HIP_AS(ctx, st->d_crc_bad.alloc(1), what);
+            KTA_HIP_AS(ctx, hipMemset(st->d_crc_bad.get(), 0, sizeof(uint64_t)), what);
         }
-        if (timing) { int rc = pair(ctx, st, 0, &a, &b); if (rc != KTA_OK) return rc; KK(ctx, hipEventRecord(a, s)); }
+        if (timing) { int rc = st->timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
         hipLaunchKernelGGL(kafka_crc32c, dim3((uint32_t)n_batches), dim3(64), 0, s, words, d_descs, n_batches,
-                           st->d_crc_tables, reinterpret_cast<unsigned long long *>(st->d_crc_bad));
-        KK(ctx, hipGetLastError());
-        if (timing) KK(ctx, hipEventRecord(b, s));
+                           st->d_crc_tables.get(), reinterpret_cast<unsigned long long *>(st->d_crc_bad.get()));
+        KTA_HIP(ctx, hipGetLastError());
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
     }
     bool any_snappy = false, any_lz4 = false, any_gzip = false, any_zstd = false;
     uint64_t buffer_end = blob_len;
@@ -1661,10 +1576,8 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
             if (descs_host[i].payload_end > buffer_end) buffer_end = descs_host[i].payload_end;
             if (descs_host[i].scratch_end > buffer_end) buffer_end = descs_host[i].scratch_end;
         }
-    if (want_keys && buffer_end >= (1ull << 32)) {
-        kta_internal_set_error(ctx, "blob + inflate area must be < 4 GiB when key offsets are wanted (key_off is u32)");
-        return KTA_ERR_CAPACITY;
-    }
+    if (want_keys && buffer_end >= (1ull << 32))
+        return fail(ctx, KTA_ERR_CAPACITY, "blob + inflate area must be < 4 GiB when key offsets are wanted (key_off is u32)");
     if (any_snappy || any_lz4 || any_gzip || any_zstd) {   // inflate compressed batches into their slices of the same buffer
         uint8_t *buf = const_cast<uint8_t *>(blob_device);
         uint32_t lane_codecs = 0u;
@@ -1700,11 +1613,11 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
         if (lane_codecs)
             hipLaunchKernelGGL(kafka_inflate_lane, dim3(grid), dim3(kLanesPerBlock), 0, s, buf, d_descs, n_batches,
                                lane_codecs);
-        KK(ctx, hipGetLastError());
+        KTA_HIP(ctx, hipGetLastError());
     }
-    if (timing) { int rc = pair(ctx, st, 1, &a, &b); if (rc != KTA_OK) return rc; KK(ctx, hipEventRecord(a, s)); }
-    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(st->d_scalars + 1);
-    unsigned long long *d_keyb = n_key_bytes ? reinterpret_cast<unsigned long long *>(st->d_scalars) : nullptr;
+    if (timing) { int rc = st->timers.pair(ctx, s, 1, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+    unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(d_scalars + 1);
+    unsigned long long *d_keyb = n_key_bytes ? reinterpret_cast<unsigned long long *>(d_scalars) : nullptr;
     const int wk = want_keys ? 1 : 0;
 #define KTA_DECODE_COOP(G, W, R)                                                                                      \
     hipLaunchKernelGGL((kafka_decode_coop<G, W, R>), dim3((uint32_t)((n_batches + (G) - 1) / (G))), dim3(64), 0, s,  \
@@ -1721,12 +1634,12 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
     default: KTA_DECODE_COOP(2, 8192u, 32u); break;   // (11) 32 lanes per batch, 8 KiB windows (~31 records), one parse round
     }
 #undef KTA_DECODE_COOP
-    KK(ctx, hipGetLastError());
-    if (timing) KK(ctx, hipEventRecord(b, s));
-    KK(ctx, hipEventRecord(st->ev_desc_free[dk], s));          // the descriptors' buffer is free once these kernels are done
+    KTA_HIP(ctx, hipGetLastError());
+    if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+    KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
-        KK(ctx, hipMemcpyAsync(scal, st->d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        KK(ctx, hipStreamSynchronize(s));
+        KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        KTA_HIP(ctx, hipStreamSynchronize(s));
         if (n_bad_batches) *n_bad_batches = scal[1];
         if (n_key_bytes) *n_key_bytes = scal[0];
     }
@@ -1737,15 +1650,11 @@ int kta_kafka_configure(kta_ctx *ctx, uint64_t blob_capacity, int n_stages)
 {
     if (!ctx || n_stages < 0 || n_stages > 16) return KTA_ERR_INVALID;
     KafkaState *st = state_of(ctx);
-    if (!st->stages.empty()) {
-        kta_internal_set_error(ctx, "kta_kafka_configure must precede the first kta_kafka_blob_acquire");
-        return KTA_ERR_INVALID;
-    }
+    if (!st->stages.empty())
+        return fail(ctx, KTA_ERR_INVALID, "kta_kafka_configure must precede the first kta_kafka_blob_acquire");
     if (blob_capacity) st->blob_capacity = blob_capacity;
-    if (st->blob_capacity >= (1ull << 32) - 64) {
-        kta_internal_set_error(ctx, "blob capacity must be < 4 GiB (key offsets are u32)");
-        return KTA_ERR_INVALID;
-    }
+    if (st->blob_capacity >= (1ull << 32) - 64)
+        return fail(ctx, KTA_ERR_INVALID, "blob capacity must be < 4 GiB (key offsets are u32)");
     st->stages.resize(n_stages ? (size_t)n_stages : 3);
     return KTA_OK;
 }
@@ -1753,23 +1662,22 @@ int kta_kafka_configure(kta_ctx *ctx, uint64_t blob_capacity, int n_stages)
 int kta_kafka_blob_acquire(kta_ctx *ctx, uint8_t **host_ptr, uint64_t *capacity)
 {
     if (!ctx || !host_ptr || !capacity) return KTA_ERR_INVALID;
-    KK(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     KafkaState *st = state_of(ctx);
     if (st->stages.empty()) st->stages.resize(3);
     BlobStage &g = st->stages[st->cur];
     if (!g.h_blob) {
         g.cap = st->blob_capacity;
-        KK(ctx, hipHostMalloc((void **)&g.h_blob, g.cap + 64, hipHostMallocDefault));
-        g.d_cap = g.cap + 128;
-        KK(ctx, hipMalloc((void **)&g.d_blob, g.d_cap));
-        KK(ctx, hipEventCreateWithFlags(&g.copied, hipEventDisableTiming));
-        KK(ctx, hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
+        KTA_HIP(ctx, g.h_blob.alloc(g.cap + 64));
+        KTA_HIP(ctx, g.d_blob.alloc(g.cap + 128));
+        KTA_HIP(ctx, hipEventCreateWithFlags(g.copied.put(), hipEventDisableTiming));
+        KTA_HIP(ctx, hipEventCreateWithFlags(g.done.put(), hipEventDisableTiming));
     }
     if (g.busy) { // the ring wrapped: the kernels that read this stage's device blob must be done
-        KK(ctx, hipEventSynchronize(g.done));
+        KTA_HIP(ctx, hipEventSynchronize(g.done.get()));
         g.busy = false;
     }
-    *host_ptr = g.h_blob;
+    *host_ptr = g.h_blob.get();
     *capacity = g.cap;
     st->acquired = true;
     return KTA_OK;
@@ -1778,35 +1686,27 @@ int kta_kafka_blob_acquire(kta_ctx *ctx, uint8_t **host_ptr, uint64_t *capacity)
 int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kafka_index_stats *stats)
 {
     if (!ctx || !stats) return KTA_ERR_INVALID;
-    KK(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     KafkaState *st = state_of(ctx);
-    if (!st->acquired) {
-        kta_internal_set_error(ctx, "kta_kafka_blob_submit without kta_kafka_blob_acquire");
-        return KTA_ERR_INVALID;
-    }
+    if (!st->acquired)
+        return fail(ctx, KTA_ERR_INVALID, "kta_kafka_blob_submit without kta_kafka_blob_acquire");
     BlobStage &g = st->stages[st->cur];
-    if (len > g.cap) {
-        kta_internal_set_error(ctx, "record set larger than the blob staging capacity");
-        return KTA_ERR_CAPACITY;
-    }
+    if (len > g.cap)
+        return fail(ctx, KTA_ERR_CAPACITY, "record set larger than the blob staging capacity");
     st->acquired = false;
     int rc = kta_flush(ctx); // keep consumption order with per-message records staged earlier
     if (rc != KTA_OK) return rc;
     hipStream_t s = kta_internal_stream(ctx), cs = kta_internal_copy_stream(ctx);
     // 1. host: index the batch headers (pinned descriptor array, grown on demand)
-    if (g.desc_cap == 0) {
-        g.desc_cap = 4096;
-        KK(ctx, hipHostMalloc((void **)&g.h_descs, g.desc_cap * sizeof(kta_kafka_batch_desc), hipHostMallocDefault));
-    }
+    if (!g.h_descs) KTA_HIP(ctx, g.h_descs.alloc(4096));
     const uint64_t inflate_at = (len + 127) & ~63ull;   // inflate area: right behind the raw bytes, 64-byte aligned
-    rc = kta_kafka_index_host(g.h_blob, len, partition, 0, 0, inflate_at, g.h_descs, g.desc_cap, stats);
+    rc = kta_kafka_index_host(g.h_blob.get(), len, partition, 0, 0, inflate_at, g.h_descs.get(), g.h_descs.size(), stats);
     if (rc == KTA_ERR_CAPACITY) {
-        (void)hipHostFree(g.h_descs);
-        g.desc_cap = stats->n_batches + stats->n_batches / 4;
-        KK(ctx, hipHostMalloc((void **)&g.h_descs, g.desc_cap * sizeof(kta_kafka_batch_desc), hipHostMallocDefault));
-        rc = kta_kafka_index_host(g.h_blob, len, partition, 0, 0, inflate_at, g.h_descs, g.desc_cap, stats);
+        KTA_HIP(ctx, g.h_descs.alloc(stats->n_batches + stats->n_batches / 4));
+        rc = kta_kafka_index_host(g.h_blob.get(), len, partition, 0, 0, inflate_at, g.h_descs.get(), g.h_descs.size(), stats);
     }
     if (rc != KTA_OK) return rc;
+    kta_kafka_batch_desc *const h_descs = g.h_descs.get();
     if (stats->n_batches == 0) return KTA_OK;
     const bool keys = kta_internal_want_keys(ctx);
     const uint64_t used = stats->bytes_consumed, nrec = stats->n_records, nb = stats->n_batches;
@@ -1819,10 +1719,10 @@ int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kaf
     uint64_t limit = st->inflate_limit ? st->inflate_limit : (1ull << 30);
     const uint64_t addressable = (1ull << 32) - (128ull << 20);
     if (keys && inflate_at + limit > addressable) limit = addressable > inflate_at + (64ull << 20) ? addressable - inflate_at : (64ull << 20);
-    auto inflate_lo = [&](uint64_t i) { return g.h_descs[i].payload_off; };   // compressed batches only
-    auto is_comp = [&](uint64_t i) { return (g.h_descs[i].flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD)) != 0; };
+    auto inflate_lo = [&](uint64_t i) { return h_descs[i].payload_off; };   // compressed batches only
+    auto is_comp = [&](uint64_t i) { return (h_descs[i].flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD)) != 0; };
     auto inflate_hi = [&](uint64_t i) {
-        const uint64_t e = g.h_descs[i].scratch_end > g.h_descs[i].payload_end ? g.h_descs[i].scratch_end : g.h_descs[i].payload_end;
+        const uint64_t e = h_descs[i].scratch_end > h_descs[i].payload_end ? h_descs[i].scratch_end : h_descs[i].payload_end;
         return (e + 63) & ~63ull;
     };
     std::vector<uint64_t> cut{0};                         // group k = batches [cut[k], cut[k+1])
@@ -1842,31 +1742,28 @@ int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kaf
         if (lo != ~0ull && hi - lo > max_span) max_span = hi - lo;
         cut.push_back(nb);
     }
-    if (inflate_at + max_span + 128 > g.d_cap) {   // grow the device buffer (the stage is idle here)
-        (void)hipFree(g.d_blob);
-        g.d_blob = nullptr;
-        g.d_cap = inflate_at + max_span + max_span / 4 + 4096;
-        KK(ctx, hipMalloc((void **)&g.d_blob, g.d_cap));
-    }
+    if (inflate_at + max_span + 128 > g.d_blob.size())   // grow the device buffer (the stage is idle here)
+        KTA_HIP(ctx, g.d_blob.alloc(inflate_at + max_span + max_span / 4 + 4096));
+    uint8_t *const d_blob = g.d_blob.get();
     // 2. decoded columns of this stage (grown on demand; the stage is idle here).  Every group is submitted
     // as its own batch, whose columns must start 16-byte aligned: a group's records start at a multiple of 4.
     const uint64_t ncol = nrec + 4 * (cut.size() - 1);
     if (g.out_cap < ncol || (keys && !g.out.key_off)) {
         free_out(g.out);
         g.out_cap = ncol + ncol / 4 + 1024;
-        KK(ctx, hipMalloc((void **)&g.out.partition, g.out_cap * 4 + 16));
-        KK(ctx, hipMalloc((void **)&g.out.key_len, g.out_cap * 4 + 16));
-        KK(ctx, hipMalloc((void **)&g.out.val_len, g.out_cap * 4 + 16));
-        KK(ctx, hipMalloc((void **)&g.out.ts_ms, g.out_cap * 8 + 16));
-        if (keys) KK(ctx, hipMalloc((void **)&g.out.key_off, g.out_cap * 4 + 16));
+        KTA_HIP(ctx, hipMalloc((void **)&g.out.partition, g.out_cap * 4 + 16));
+        KTA_HIP(ctx, hipMalloc((void **)&g.out.key_len, g.out_cap * 4 + 16));
+        KTA_HIP(ctx, hipMalloc((void **)&g.out.val_len, g.out_cap * 4 + 16));
+        KTA_HIP(ctx, hipMalloc((void **)&g.out.ts_ms, g.out_cap * 8 + 16));
+        if (keys) KTA_HIP(ctx, hipMalloc((void **)&g.out.key_off, g.out_cap * 4 + 16));
         g.out.capacity = g.out_cap;
     }
-    g.out.key_bytes = keys ? g.d_blob : nullptr; // zero-copy: keys are hashed in place in the raw log
+    g.out.key_bytes = keys ? d_blob : nullptr; // zero-copy: keys are hashed in place in the raw log
     g.out.key_bytes_capacity = keys ? inflate_at + max_span : 0;
     // 3. raw log over PCIe on the copy stream; decode + metric handlers on the compute stream
-    KK(ctx, hipMemcpyAsync(g.d_blob, g.h_blob, (used + 63) & ~63ull, hipMemcpyHostToDevice, cs));
-    KK(ctx, hipEventRecord(g.copied, cs));
-    KK(ctx, hipStreamWaitEvent(s, g.copied, 0));
+    KTA_HIP(ctx, hipMemcpyAsync(d_blob, g.h_blob.get(), (used + 63) & ~63ull, hipMemcpyHostToDevice, cs));
+    KTA_HIP(ctx, hipEventRecord(g.copied.get(), cs));
+    KTA_HIP(ctx, hipStreamWaitEvent(s, g.copied.get(), 0));
     const uint64_t base = kta_internal_take_seq(ctx, nrec);
     for (size_t k = 0; k + 1 < cut.size(); k++) {
         const uint64_t b0 = cut[k], b1 = cut[k + 1];
@@ -1877,16 +1774,16 @@ int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kaf
         if (shift)
             for (uint64_t i = b0; i < b1; i++)
                 if (is_comp(i)) {
-                    g.h_descs[i].payload_off -= shift;
-                    g.h_descs[i].payload_end -= shift;
-                    g.h_descs[i].scratch_end -= shift;
+                    h_descs[i].payload_off -= shift;
+                    h_descs[i].payload_end -= shift;
+                    h_descs[i].scratch_end -= shift;
                 }
-        const uint64_t r0 = g.h_descs[b0].record_base;                       // consumption index of the group's first record
-        const uint64_t r1 = b1 < nb ? g.h_descs[b1].record_base : nrec;
+        const uint64_t r0 = h_descs[b0].record_base;                       // consumption index of the group's first record
+        const uint64_t r1 = b1 < nb ? h_descs[b1].record_base : nrec;
         const uint64_t c0 = (r0 + 4 * k + 3) & ~3ull;                         // its place in the columns: aligned, past group k-1
         if (c0 != r0)
-            for (uint64_t i = b0; i < b1; i++) g.h_descs[i].record_base += c0 - r0;
-        rc = kta_kafka_decode_device(ctx, g.d_blob, used, g.h_descs + b0, b1 - b0, ncol, &g.out, nullptr, nullptr);
+            for (uint64_t i = b0; i < b1; i++) h_descs[i].record_base += c0 - r0;
+        rc = kta_kafka_decode_device(ctx, d_blob, used, h_descs + b0, b1 - b0, ncol, &g.out, nullptr, nullptr);
         if (rc != KTA_OK) return rc;
         kta_batch view = g.out;                           // this group's records: [c0, c0 + r1 - r0) of the stage's columns
         view.partition += c0;
@@ -1899,7 +1796,7 @@ int kta_kafka_blob_submit(kta_ctx *ctx, uint64_t len, int32_t partition, kta_kaf
         rc = kta_submit_device(ctx, &view, r1 - r0, base + r0);
         if (rc != KTA_OK) return rc;
     }
-    KK(ctx, hipEventRecord(g.done, s));
+    KTA_HIP(ctx, hipEventRecord(g.done.get(), s));
     g.busy = true;
     st->cur = (st->cur + 1) % (int)st->stages.size();
     return KTA_OK;
@@ -1939,10 +1836,8 @@ int kta_kafka_consume(kta_ctx *ctx, const uint8_t *bytes, uint64_t len, int32_t 
         stats->bytes_consumed += one.bytes_consumed;
         if (one.bytes_consumed == 0) {   // not even one whole batch fits / trailing partial batch
             stats->trailing_bytes = len - pos;
-            if (n == cap && cap < len - pos) {
-                kta_internal_set_error(ctx, "a single record batch exceeds the blob staging capacity");
-                return KTA_ERR_CAPACITY;
-            }
+            if (n == cap && cap < len - pos)
+                return fail(ctx, KTA_ERR_CAPACITY, "a single record batch exceeds the blob staging capacity");
             return KTA_OK;
         }
         pos += one.bytes_consumed;
@@ -1971,9 +1866,9 @@ int kta_kafka_crc_errors(kta_ctx *ctx, uint64_t *n)
     KafkaState *st = state_of(ctx);
     *n = 0;
     if (!st->d_crc_bad) return KTA_OK;
-    KK(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KK(ctx, hipMemcpyAsync(n, st->d_crc_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
-    KK(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KTA_HIP(ctx, hipMemcpyAsync(n, st->d_crc_bad.get(), sizeof(uint64_t), hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
+    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
     return KTA_OK;
 }
 
@@ -1987,16 +1882,7 @@ int kta_kafka_set_variant(kta_ctx *ctx, int variant)
 int kta_kafka_time_stats(kta_ctx *ctx, float avg_ms[2], uint64_t launches[2])
 {
     if (!ctx || !avg_ms || !launches) return KTA_ERR_INVALID;
-    KafkaState *st = state_of(ctx);
-    int rc = drain(ctx, st);
-    if (rc != KTA_OK) return rc;
-    for (int k = 0; k < 2; k++) {
-        launches[k] = st->ms_cnt[k];
-        avg_ms[k] = st->ms_cnt[k] ? (float)(st->ms_sum[k] / (double)st->ms_cnt[k]) : -1.f;
-        st->ms_sum[k] = 0;
-        st->ms_cnt[k] = 0;
-    }
-    return KTA_OK;
+    return state_of(ctx)->timers.stats(ctx, kta_internal_stream(ctx), avg_ms, launches);
 }
 
 } // extern "C"

@@ -3,18 +3,13 @@
 // Input generation only: nothing here is on the measured hot path.
 #include "../../include/kta_synth.h"
 
+#include "kta_internal.h"
+
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <string.h>
 
 #include <string>
-
-hipStream_t kta_internal_stream(kta_ctx *ctx);
-int kta_internal_device(kta_ctx *ctx);
-void kta_internal_set_error(kta_ctx *ctx, const char *msg);
-int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
-int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
-                         uint64_t *rec0);
 
 namespace {
 
@@ -264,27 +259,12 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
                           const kta_batch *b, uint64_t *n_key_bytes)
 {
     if (!ctx || !b) return KTA_ERR_INVALID;
-    if (check_spec(spec) != KTA_OK) {
-        kta_internal_set_error(ctx, "invalid synthetic spec");
-        return KTA_ERR_INVALID;
-    }
-    if (n > b->capacity) {
-        kta_internal_set_error(ctx, "synthetic batch larger than the device batch capacity");
-        return KTA_ERR_CAPACITY;
-    }
+    if (check_spec(spec) != KTA_OK) return fail(ctx, KTA_ERR_INVALID, "invalid synthetic spec");
+    if (n > b->capacity) return fail(ctx, KTA_ERR_CAPACITY, "synthetic batch larger than the device batch capacity");
     if (n_key_bytes) *n_key_bytes = 0;
     if (n == 0) return KTA_OK;
     hipStream_t s = kta_internal_stream(ctx);
-    hipError_t e = hipSetDevice(kta_internal_device(ctx));
-    uint64_t *d_chunks = nullptr;
-    std::string what;
-#define SY(call)                                   \
-    do {                                           \
-        if (e == hipSuccess) {                     \
-            e = (call);                            \
-            if (e != hipSuccess) what = #call;     \
-        }                                          \
-    } while (0)
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     const uint32_t grid = (uint32_t)((n + kWG - 1) / kWG < 8192 ? (n + kWG - 1) / kWG : 8192);
     // a tile-compact batch from a tile boundary takes the compact fill; anything else the raw one (its tiles made raw first)
     int32_t *apart = nullptr;
@@ -296,48 +276,39 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
         if (int rc = kta_internal_prepare_raw(ctx, b, n)) return rc;
         ahdr = nullptr;
     }
-    if (e == hipSuccess && ahdr) {
+    if (ahdr) {
         const uint64_t nt = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
         hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, apart,
                            b->key_len, b->val_len, ats, b->seq, ahdr, rec0 / KTA_TILE_RECORDS);
-        SY(hipGetLastError());
-    } else if (e == hipSuccess) {
+    } else {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);
-        SY(hipGetLastError());
     }
+    KTA_HIP(ctx, hipGetLastError());
     uint64_t total = 0;
     if (b->key_off && b->key_bytes) {
         const uint64_t n_chunks = (n + kScanChunk - 1) / kScanChunk;
-        SY(hipMalloc((void **)&d_chunks, (n_chunks + 1) * sizeof(uint64_t)));
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(synth_chunk_sums, dim3((uint32_t)n_chunks), dim3(kWG), 0, s, b->key_len, n, d_chunks);
-            hipLaunchKernelGGL(synth_scan_chunks, dim3(1), dim3(1024), 0, s, d_chunks, n_chunks, d_chunks + n_chunks);
-            SY(hipGetLastError());
-        }
-        SY(hipMemcpyAsync(&total, d_chunks + n_chunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        SY(hipStreamSynchronize(s));
-        if (e == hipSuccess && (total > b->key_bytes_capacity || total >= (1ull << 32))) {
-            (void)hipFree(d_chunks);
-            kta_internal_set_error(ctx, "synthetic key bytes exceed the device batch key capacity");
+        DeviceBuf<uint64_t> chunks;   // (released on every return; hipFree waits for the device first)
+        // This allocation answers KTA_ERR_HIP also when it runs out of memory (everywhere else in the library that is
+        // KTA_ERR_NOMEM): callers have seen that code from here since the function exists, and it stays.
+        if (hipError_t e = chunks.alloc(n_chunks + 1))
+            return fail(ctx, KTA_ERR_HIP, std::string("chunks.alloc(n_chunks + 1): ") + hipGetErrorString(e));
+        uint64_t *const d_chunks = chunks.get();
+        hipLaunchKernelGGL(synth_chunk_sums, dim3((uint32_t)n_chunks), dim3(kWG), 0, s, b->key_len, n, d_chunks);
+        hipLaunchKernelGGL(synth_scan_chunks, dim3(1), dim3(1024), 0, s, d_chunks, n_chunks, d_chunks + n_chunks);
+        KTA_HIP(ctx, hipGetLastError());
+        KTA_HIP(ctx, hipMemcpyAsync(&total, d_chunks + n_chunks, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        KTA_HIP(ctx, hipStreamSynchronize(s));
+        if (total > b->key_bytes_capacity || total >= (1ull << 32)) {
             if (n_key_bytes) *n_key_bytes = total;
-            return KTA_ERR_CAPACITY;
+            return fail(ctx, KTA_ERR_CAPACITY, "synthetic key bytes exceed the device batch key capacity");
         }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(synth_key_offsets, dim3((uint32_t)n_chunks), dim3(kWG), 0, s, b->key_len, n, d_chunks,
-                               b->key_off);
-            hipLaunchKernelGGL(synth_fill_keys, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->key_len, b->key_off,
-                               b->key_bytes);
-            SY(hipGetLastError());
-        }
-        SY(hipStreamSynchronize(s));
-        if (d_chunks) (void)hipFree(d_chunks);
-    }
-#undef SY
-    if (e != hipSuccess) {
-        std::string m = what + ": " + hipGetErrorString(e);
-        kta_internal_set_error(ctx, m.c_str());
-        return KTA_ERR_HIP;
+        hipLaunchKernelGGL(synth_key_offsets, dim3((uint32_t)n_chunks), dim3(kWG), 0, s, b->key_len, n, d_chunks,
+                           b->key_off);
+        hipLaunchKernelGGL(synth_fill_keys, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->key_len, b->key_off,
+                           b->key_bytes);
+        KTA_HIP(ctx, hipGetLastError());
+        KTA_HIP(ctx, hipStreamSynchronize(s));
     }
     if (n_key_bytes) *n_key_bytes = total;
     return KTA_OK;

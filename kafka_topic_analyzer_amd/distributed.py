@@ -37,6 +37,16 @@ def sum_prefix_len(n_partitions: int) -> int:
     return n_partitions * N.KTA_NCOUNTERS + N.KTA_NSUM_GLOBALS
 
 
+def _allreduce_sum_max(vec, sum_words: int, group) -> None:
+    """The rule of every result vector, in place: all-reduce SUM over vec[:sum_words], all-reduce MAX over the rest
+    (a half of no words is left out)."""
+    import torch.distributed as dist
+    if sum_words:
+        dist.all_reduce(vec[:sum_words], op=dist.ReduceOp.SUM, group=group)
+    if sum_words < vec.numel():
+        dist.all_reduce(vec[sum_words:], op=dist.ReduceOp.MAX, group=group)
+
+
 def allreduce_counter_vector(vec, n_partitions: int, group=None, alive_keys: str = "share") -> None:
     """In-place exchange step over an int64 view of the SNAPSHOT counter vector (kta_result_vector: device
     tensor, or a CPU tensor in the tests) — the live accumulator is never reduced.
@@ -47,13 +57,11 @@ def allreduce_counter_vector(vec, n_partitions: int, group=None, alive_keys: str
     "merged" — the tables were fully merged first (exchange_alive_entries / allreduce_alive_table), every rank
                holds the global count: all ranks but 0 contribute zero."""
     import torch.distributed as dist
-    k = sum_prefix_len(n_partitions)
     assert vec.numel() == n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS
     assert alive_keys in ("share", "merged")
     if alive_keys == "merged" and dist.get_rank(group) != 0:
         vec[n_partitions * N.KTA_NCOUNTERS + N.KTA_G_ALIVE_KEYS] = 0
-    dist.all_reduce(vec[:k], op=dist.ReduceOp.SUM, group=group)
-    dist.all_reduce(vec[k:], op=dist.ReduceOp.MAX, group=group)
+    _allreduce_sum_max(vec, sum_prefix_len(n_partitions), group)
 
 
 def allreduce_analytics_vector(avec, n_partitions: int, group=None) -> None:
@@ -61,29 +69,24 @@ def allreduce_analytics_vector(avec, n_partitions: int, group=None) -> None:
     or a CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_ANALYTICS:
     all-reduce SUM over the 2 x 34 histogram words (i64 wrap == u64 wrap) and all-reduce MAX over the 4 * P extrema
     words ([~min ts, max ts, ~smallest, largest] per partition; INT64_MIN where a rank saw nothing)."""
-    import torch.distributed as dist
-    k = N.KTA_ANALYTICS_HIST
-    assert avec.numel() == k + 4 * n_partitions
-    dist.all_reduce(avec[:k], op=dist.ReduceOp.SUM, group=group)
-    dist.all_reduce(avec[k:], op=dist.ReduceOp.MAX, group=group)
+    assert avec.numel() == N.KTA_ANALYTICS_HIST + 4 * n_partitions
+    _allreduce_sum_max(avec, N.KTA_ANALYTICS_HIST, group)
 
 
 def allreduce_timeline_vector(tvec, group=None) -> None:
     """In-place exchange of an int64 view of the timeline SNAPSHOT (kta_timeline_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively for a context with a timeline: all-reduce SUM over
     every word (i64 wrap == u64 wrap).  Every rank must have the same timeline configuration."""
-    import torch.distributed as dist
     assert tvec.numel() % N.KTA_TIMELINE_COLS == 0
-    dist.all_reduce(tvec, op=dist.ReduceOp.SUM, group=group)
+    _allreduce_sum_max(tvec, tvec.numel(), group)
 
 
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
     MAX over every word (registers are 0..21, so signed MAX == unsigned MAX).  Every rank must have the flag."""
-    import torch.distributed as dist
     assert svec.numel() % N.KTA_SKETCH_REGISTERS == 0
-    dist.all_reduce(svec, op=dist.ReduceOp.MAX, group=group)
+    _allreduce_sum_max(svec, 0, group)
 
 
 def allreduce_alive_table(table, group=None, chunk_elems: int = 1 << 28) -> None:
