@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -167,14 +167,60 @@ typedef struct kta_analytics {
 #define KTA_SKETCH_REGISTERS (1u << KTA_SKETCH_LOG2)
 #define KTA_SKETCH_MAX_PARTITIONS 16384   /* 512 MiB of u64 snapshot */
 
+/* Hot keys (NOT in the reference, never printed by the reference report): a topic-wide sketch that names the keys
+ * holding the largest shares of the keyed records.  Opt-in at kta_create.  The vector is
+ * u64[KTA_HOT_ROWS][KTA_HOT_CELLS][KTA_HOT_WORDS] (47 104 words, 368 KiB), every word a SUM, so the vectors of disjoint
+ * record sets add word by word and the sketch depends on no order, batching or sharding.  For every record the metrics
+ * handler counts (partition in [0, P)) whose key is Some (key_len >= 0: the empty key and tombstones included; the key
+ * sketch's records), with h = fnv1a(key) and x = fmix32(h) as above KTA_FLAG_KEY_SKETCH:
+ *   row 0: cell c0 = x & 1023,          rest y0 = x >> 10
+ *   row 1: cell c1 = (x >> 10) & 1023,  rest y1 = (x & 1023) | ((x >> 20) << 10)
+ * and in each row r the record adds 1 to word 0 of cell c_r (the cell's total T) and, for every set bit b of the 22-bit
+ * y_r, 1 to word 1 + b.  The cell index supplies ten bits of x and the 22 bit counters the others; fmix32 is a bijection,
+ * so x names h.
+ * Readout (kta_hot_keys_recover: host only, deterministic).  For every cell with T > 0 the candidate is the x put
+ * together from the cell index and the bits b with 2 * count_b > T.  For a candidate, in each of its two rows,
+ * agree_b = count_b where its bit b is set, else T - count_b.  Then
+ *   upper U = min over both rows of min(T, min_b agree_b)
+ *   lower L = max(0, max over both rows of T - sum_b (T - agree_b))
+ * and L <= (records of the hash) <= U whatever the data: every record of the hash agrees in every bit, every other
+ * record of the cell disagrees in at least one.  A candidate is reported when U * 512 >= keyed, keyed = the sum of row
+ * 0's totals; candidates are de-duplicated by x, ordered by U descending, then hash ascending, and cut at the caller's
+ * maximum.  The reported hash is h = the inverse of fmix32 at x.  A key below 1/512 of the keyed records is not
+ * promised; two keys of one 32-bit hash are one key here, as for -c.
+ * Exemplars: a table of [KTA_HOT_ROWS][KTA_HOT_CELLS] kta_hot_exemplar slots on the device keeps, best effort, the bytes
+ * (at most KTA_HOT_EXEMPLAR_BYTES) of one record's key per cell whose hash was the cell's candidate when a launch began.
+ * A valid slot always holds one record's key whose hash is the slot's `hash`.  Counts never depend on exemplars, and
+ * collectives do not move them. */
+#define KTA_FLAG_HOT_KEYS 16u
+#define KTA_HOT_ROWS 2
+#define KTA_HOT_CELLS 1024
+#define KTA_HOT_WORDS 23
+#define KTA_HOT_VECTOR_WORDS (KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS)
+#define KTA_HOT_EXEMPLAR_BYTES 32
+#define KTA_HOT_MAX_REPORTED 64
+typedef struct kta_hot_exemplar {
+    uint32_t hash;      /* fnv1a of the key */
+    uint32_t key_len;   /* the key's own length; bytes holds its first min(key_len, 32) */
+    uint32_t valid;     /* 0: the slot is empty */
+    uint32_t pad;
+    uint8_t bytes[KTA_HOT_EXEMPLAR_BYTES];
+} kta_hot_exemplar;
+typedef struct kta_hot_key {
+    uint32_t hash;      /* fnv1a of the key(s) */
+    uint32_t pad;
+    uint64_t upper;     /* records of the hash, at most */
+    uint64_t lower;     /* records of the hash, at least */
+} kta_hot_key;
+
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
  *   partition[i]  m.partition()                                          i32
  *   ts_ms[i]      raw rdkafka timestamp in ms; -1 == not available       i64
  *   key_len[i]    m.key():  -1 == None, >= 0 == Some(k).len()            i32
  *   val_len[i]    m.payload(): -1 == None (tombstone), >= 0 == len       i32
- *   key_off[i]    offset of the key's bytes in key_bytes (if key_len>0)  u32  (-c or KTA_FLAG_KEY_SKETCH only)
- *   key_bytes     concatenated key bytes; device buffers must be readable  u8   (-c or KTA_FLAG_KEY_SKETCH only)
+ *   key_off[i]    offset of the key's bytes in key_bytes (if key_len>0)  u32  (-c, KTA_FLAG_KEY_SKETCH or KTA_FLAG_HOT_KEYS only)
+ *   key_bytes     concatenated key bytes; device buffers must be readable  u8   (-c, KTA_FLAG_KEY_SKETCH or KTA_FLAG_HOT_KEYS only)
  *                 for 16 bytes past the last key (kta_device_batch_alloc pads)
  *   seq[i]        optional global consumption index; NULL => base_seq+i  u64  (-c only)
  * Value bytes are never read by the reference path (only their length). */
@@ -358,10 +404,13 @@ int kta_finish_device(kta_ctx *ctx);
  *                       snapshot: all-reduce SUM (u64) over all of its words.
  *                       With KTA_FLAG_KEY_SKETCH the same grouped launch also reduces the key sketch's snapshot:
  *                       all-reduce MAX (u64) over all of its P * 4096 words.
+ *                       With KTA_FLAG_HOT_KEYS the same grouped launch also reduces the hot-key snapshot:
+ *                       all-reduce SUM (u64) over all of its 47 104 words (exemplars stay on their rank).
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
- *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch: the same for the
- *                       analytics, the timeline, the key sketch)
- * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS and KTA_FLAG_KEY_SKETCH bits, and
+ *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch, kta_exchange_hot_keys:
+ *                       the same for the analytics, the timeline, the key sketch, the hot keys)
+ * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS, KTA_FLAG_KEY_SKETCH and
+ * KTA_FLAG_HOT_KEYS bits, and
  * be given the same timeline configuration (or none on every rank): the collectives of a rank with analytics, a key
  * sketch or a timeline do not match those of a rank without, and nothing checks that the configurations agree.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
@@ -462,6 +511,37 @@ int kta_key_sketch_estimate(const uint64_t *vec, uint32_t n_partitions, double *
  * out[3] launches. */
 int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4]);
 
+/* Hot keys (context created with KTA_FLAG_HOT_KEYS; definition above KTA_FLAG_HOT_KEYS).  With the flag the staging
+ * batches carry key_off and key_bytes without -c as well, and a device batch handed to the metrics handler (which & 1)
+ * without key columns is refused with KTA_ERR_INVALID before anything is launched.  kta_reset zeroes the vector and the
+ * exemplars; kta_finish_device snapshots the vector.  Every call below that takes a context fails on one without the flag
+ * with KTA_ERR_INVALID and a message naming KTA_FLAG_HOT_KEYS.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_HOT_VECTOR_WORDS; staged messages are flushed first). */
+int kta_get_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's vector on every rank.  The live accumulator is never reduced. */
+int kta_exchange_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_hot_keys_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors (acc <- acc + other, word by word): what the exchange's all-reduce SUM implements. */
+int kta_merge_hot_keys(uint64_t *acc, const uint64_t *other);
+/* Host-side readout of a vector (no device): at most max_out (<= 2048) entries to `entries`, their number to *n_out,
+ * the keyed records to *keyed (may be NULL).  KTA_ERR_INVALID for a vector no record set leaves: a bit count above its
+ * cell's total, or a total of 2^54 and more. */
+int kta_hot_keys_recover(const uint64_t *vec, uint32_t max_out, kta_hot_key *entries, uint32_t *n_out, uint64_t *keyed);
+/* The exemplar table, copied to out[KTA_HOT_ROWS * KTA_HOT_CELLS] (staged messages are flushed first; waits for the
+ * compute stream).  The exemplar of a reported hash h, x = fmix32(h), is in slot [0][x & 1023] or [1][(x >> 10) & 1023]
+ * when one of them is valid and holds h. */
+int kta_get_hot_key_exemplars(kta_ctx *ctx, kta_hot_exemplar *out, size_t n_slots);
+/* Work counters of the hot-key pass since kta_create / kta_reset (profiling; waits for the compute stream): out[0]
+ * keyed records, out[1] groups of lanes that added to LDS as one (a lane alone is a group), out[2] flushes of a
+ * workgroup's LDS counters before its end (every workgroup of a launch makes the same number), out[3] launches, out[4]
+ * exemplars captured, out[5] workgroups launched. */
+int kta_hot_keys_info(kta_ctx *ctx, uint64_t out[6]);
+/* Tests: the rounds (4096 records of a workgroup each) after which a workgroup flushes its LDS counters; 0 = the
+ * default, the most the 21-bit fields admit (511).  KTA_ERR_INVALID above that. */
+int kta_set_hot_flush_rounds(kta_ctx *ctx, uint32_t rounds);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -534,6 +614,17 @@ int kta_render_timeline(const uint64_t *vec, int64_t origin_ms, int64_t bucket_m
  * as kta_render_report. */
 int kta_render_distinct_keys(const uint64_t *sketch_vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out,
                              size_t out_cap, size_t *out_len);
+
+/* The opt-in hot-key section that kta-analyzer prints after the reference report (and after the other opt-in sections)
+ * with --librdkafka kta.hot_keys=K (1 <= K <= KTA_HOT_MAX_REPORTED), from a hot-key vector and an exemplar table
+ * (kta_hot_exemplar[2048], or NULL for none; host only): a title line that names the method and says that it is not
+ * part of the reference report, a table (# | Key | Hash | Records (at most) | (at least) | Share of keyed records: the
+ * key's first 32 bytes with printable ASCII except the backslash as is and every other byte as \xNN, `...` behind a
+ * longer key, `-` without an exemplar; the hash as 8 hex digits; the share is the upper bound's, %.2f) and a closing
+ * `=` rule.  When no key is reported: the title and one line saying so.  Output buffer conventions as
+ * kta_render_report. */
+int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys, char *out,
+                        size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

@@ -26,7 +26,8 @@ from ._native import KtaBatch, KtaConfig, KtaResult, KtaSynthSpec  # noqa: F401
 __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics", "Message", "KtaError",
            "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats",
            "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions", "render_timeline",
-           "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys"]
+           "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys",
+           "recover_hot_keys", "merge_hot_keys", "render_hot_keys"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -73,20 +74,23 @@ class HipMetricHandler:
     def __init__(self, n_partitions: int, count_alive_keys: bool = False, device: int = 0,
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
-                 seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False):
+                 seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
+                 hot_keys: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
         timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline);
-        key_sketch: a HyperLogLog sketch of the key hashes per partition (KTA_FLAG_KEY_SKETCH: estimate_distinct_keys)."""
+        key_sketch: a HyperLogLog sketch of the key hashes per partition (KTA_FLAG_KEY_SKETCH: estimate_distinct_keys);
+        hot_keys: the topic-wide hot-key sketch (KTA_FLAG_HOT_KEYS: recover_hot_keys, hot_key_exemplars)."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
         self.count_alive_keys = bool(count_alive_keys)
         self.key_sketch_on = bool(key_sketch)
+        self.hot_keys_on = bool(hot_keys)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
-                        (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) |
+                        (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -171,7 +175,7 @@ class HipMetricHandler:
         val_len = np.ascontiguousarray(val_len, dtype=np.int32)
         ts_ms = np.ascontiguousarray(ts_ms, dtype=np.int64)
         n = len(partition)
-        keys = self.count_alive_keys or self.key_sketch_on   # the staging batches carry the keys
+        keys = self.count_alive_keys or self.key_sketch_on or self.hot_keys_on   # the staging batches carry the keys
         if keys:
             key_off = np.ascontiguousarray(key_off, dtype=np.uint32)
             key_bytes = np.ascontiguousarray(key_bytes, dtype=np.uint8)
@@ -426,6 +430,41 @@ class HipMetricHandler:
         out = (C.c_uint64 * 4)()
         self._check(self._lib.kta_key_sketch_info(self._ctx, C.byref(out)))
         return {"keyed": int(out[0]), "reads": int(out[1]), "atomics": int(out[2]), "launches": int(out[3])}
+
+    def _hot_keys(self, fn) -> np.ndarray:
+        out = np.zeros((N.KTA_HOT_ROWS, N.KTA_HOT_CELLS, N.KTA_HOT_WORDS), dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), out.size))
+        return out
+
+    def hot_keys(self) -> np.ndarray:
+        """The live hot-key vector, np.uint64[2, 1024, 23]: per row and cell the total and the 22 bit counts
+        (kta_get_hot_keys; staged messages are flushed first)."""
+        return self._hot_keys(self._lib.kta_get_hot_keys)
+
+    def exchange_hot_keys(self) -> np.ndarray:
+        """As hot_keys(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._hot_keys(self._lib.kta_exchange_hot_keys)
+
+    def hot_keys_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the hot-key snapshot (for collectives: allreduce_hot_keys_vector)."""
+        return self._device_vector(self._lib.kta_hot_keys_result_vector)
+
+    def hot_keys_info(self) -> dict:
+        """Work counters of the hot-key pass since creation / reset() (kta_hot_keys_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_hot_keys_info(self._ctx, C.byref(out)))
+        return dict(zip(("keyed", "groups", "flushes", "launches", "exemplars", "workgroups"), (int(x) for x in out)))
+
+    def set_hot_flush_rounds(self, rounds: int) -> None:
+        """Tests: a workgroup of the hot-key pass flushes its LDS counters every `rounds` rounds (0: the default)."""
+        self._check(self._lib.kta_set_hot_flush_rounds(self._ctx, int(rounds)))
+
+    def hot_key_exemplars(self) -> np.ndarray:
+        """This context's exemplar table (kta_get_hot_key_exemplars): a structured array [2048] with the fields hash,
+        key_len, valid, pad, bytes[32]; render_hot_keys and hot_key_exemplar_of read it."""
+        out = np.zeros(N.KTA_HOT_ROWS * N.KTA_HOT_CELLS, dtype=HOT_EXEMPLAR_DTYPE)
+        self._check(self._lib.kta_get_hot_key_exemplars(self._ctx, _np_ptr(out), out.size))
+        return out
 
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
@@ -691,6 +730,52 @@ def render_distinct_keys(sketch_vec, counter_vec, n_partitions: int) -> str:
     if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
     return _render(N.load().kta_render_distinct_keys, _np_ptr(v), _np_ptr(c), n_partitions)
+
+
+HOT_EXEMPLAR_DTYPE = np.dtype([("hash", np.uint32), ("key_len", np.uint32), ("valid", np.uint32), ("pad", np.uint32),
+                               ("bytes", np.uint8, (N.KTA_HOT_EXEMPLAR_BYTES,))])
+
+
+def _hot_vec(vec) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    if v.size != N.KTA_HOT_VECTOR_WORDS:
+        raise ValueError(f"a hot-key vector has {N.KTA_HOT_VECTOR_WORDS} words, not {v.size}")
+    return v
+
+
+def recover_hot_keys(vec, max_keys: int = N.KTA_HOT_MAX_REPORTED) -> Tuple[list, int]:
+    """kta_hot_keys_recover: a hot-key vector -> ([(hash, upper, lower), ...] by upper descending then hash, at most
+    max_keys of them, the keyed records)."""
+    v = _hot_vec(vec)
+    out = (N.KtaHotKey * max(int(max_keys), 1))()
+    n, keyed = C.c_uint32(), C.c_uint64()
+    rc = N.load().kta_hot_keys_recover(_np_ptr(v), int(max_keys), C.byref(out), C.byref(n), C.byref(keyed))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_hot_keys_recover")
+    return [(int(out[k].hash), int(out[k].upper), int(out[k].lower)) for k in range(n.value)], int(keyed.value)
+
+
+def merge_hot_keys(acc: np.ndarray, other) -> np.ndarray:
+    """kta_merge_hot_keys, in place on `acc` (contiguous uint64 / int64): the word-wise sum."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    rc = N.load().kta_merge_hot_keys(_np_ptr(_hot_vec(acc)), _np_ptr(_hot_vec(other)))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_hot_keys")
+    return acc
+
+
+def render_hot_keys(vec, exemplars=None, max_keys: int = 10) -> str:
+    """kta_render_hot_keys: the section kta-analyzer prints last with --librdkafka kta.hot_keys=K, from a hot-key vector
+    and an exemplar table (HipMetricHandler.hot_key_exemplars(), or None)."""
+    v = _hot_vec(vec)
+    ex = None
+    if exemplars is not None:
+        ex = np.ascontiguousarray(exemplars, dtype=HOT_EXEMPLAR_DTYPE)
+        if ex.size != N.KTA_HOT_ROWS * N.KTA_HOT_CELLS:
+            raise ValueError("an exemplar table has 2048 slots")
+    return _render(N.load().kta_render_hot_keys, _np_ptr(v), _np_ptr(ex) if ex is not None else None, int(max_keys))
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

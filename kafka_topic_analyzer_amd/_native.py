@@ -56,6 +56,20 @@ KTA_FLAG_KEY_SKETCH = 8
 KTA_SKETCH_LOG2 = 12
 KTA_SKETCH_REGISTERS = 1 << KTA_SKETCH_LOG2   # key sketch vector: u64[P * 4096], one register per word
 KTA_SKETCH_MAX_PARTITIONS = 16384
+KTA_FLAG_HOT_KEYS = 16
+KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
+KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
+KTA_HOT_EXEMPLAR_BYTES = 32
+KTA_HOT_MAX_REPORTED = 64
+
+
+class KtaHotExemplar(C.Structure):
+    _fields_ = [("hash", C.c_uint32), ("key_len", C.c_uint32), ("valid", C.c_uint32), ("pad", C.c_uint32),
+                ("bytes", C.c_uint8 * KTA_HOT_EXEMPLAR_BYTES)]
+
+
+class KtaHotKey(C.Structure):
+    _fields_ = [("hash", C.c_uint32), ("pad", C.c_uint32), ("upper", C.c_uint64), ("lower", C.c_uint64)]
 
 
 class KtaAnalytics(C.Structure):
@@ -170,6 +184,15 @@ SIGNATURES = {
     "kta_merge_key_sketch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "kta_key_sketch_estimate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "kta_key_sketch_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4)]),
+    "kta_get_hot_keys": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_hot_keys": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_hot_keys_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_hot_keys": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kta_hot_keys_recover": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "kta_get_hot_key_exemplars": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_hot_keys_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_set_hot_flush_rounds": (C.c_int, [_P, C.c_uint32]),
+    "kta_render_hot_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_render_distinct_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),

@@ -17,7 +17,7 @@
 //                                        v2; uncompressed, gzip, Snappy, LZ4, zstd): file k is partition k; decoded ON THE GPU
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
-// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1), so
+// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1, kta.hot_keys=K), so
 // no flag is added or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
@@ -34,6 +34,10 @@
 // kta.distinct_keys=1 (every source, kta.gpus=N included) keeps a HyperLogLog sketch of the key hashes per partition as well
 // (KTA_FLAG_KEY_SKETCH; no reference counterpart) and prints the estimated distinct keys per partition and of the topic in a
 // section of its own after the report (and the analytics and the timeline).
+// kta.hot_keys=K (1 <= K <= 64; every source, kta.gpus=N included) keeps the hot-key sketch as well (KTA_FLAG_HOT_KEYS; no
+// reference counterpart) and prints, last of all, the at most K keys that hold 1/512 of the keyed records and more, with
+// bounds on their records and, where the device caught one, the key's bytes (with kta.gpus=N from the lowest rank that
+// has them).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -87,6 +91,17 @@ std::vector<uint64_t> keyed_records(const kta::MessageMetrics &m, uint32_t P)
     std::vector<uint64_t> keyed(P);
     for (uint32_t p = 0; p < P; p++) keyed[p] = m.key_non_null((int32_t)p);
     return keyed;
+}
+
+// murmur3's finaliser: x = hot_fmix32(hash) places a key hash in the hot-key sketch (kta_hip.h)
+uint32_t hot_fmix32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
 }
 
 const char *kAbout = "Kafka Topic Analyzer 0.4.1";
@@ -212,6 +227,7 @@ struct ShardedJob {
     bool analytics = false;                            // kta.analytics=1: every rank's context, exchanged with the counters
     kta::TimelineConfig timeline;                      // kta.timeline=<width>: derived once, the same on every rank
     bool distinct_keys = false;                        // kta.distinct_keys=1: every rank's context, exchanged with the counters
+    uint32_t hot_keys = 0;                             // kta.hot_keys=K: likewise; the exemplars stay on their ranks
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -225,8 +241,9 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
     try {
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
-                               (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u);
-        const bool keys = job.count_alive || job.distinct_keys;   // the staging batches carry key_off / key_bytes
+                               (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
+                               (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u);
+        const bool keys = job.count_alive || job.distinct_keys || job.hot_keys;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline);
         kta_ctx *ctx = h->ctx();
@@ -354,6 +371,28 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             text += kta::render_timeline(h0->timeline()->data(), job.timeline.origin_ms, job.timeline.bucket_ms,
                                          job.timeline.n_buckets);
         if (job.distinct_keys) text += kta::render_distinct_keys(h0->key_sketch()->data(), keyed_records(metrics, job.P));
+        if (job.hot_keys) {
+            // a slot a lower rank filled stays: every reported hash gets its exemplar from the lowest rank that has it
+            std::vector<kta_hot_exemplar> merged = *h0->hot_key_exemplars();
+            for (size_t r = 1; r < handlers.size(); r++) {
+                const std::vector<kta_hot_exemplar> &ex = *handlers[r]->hot_key_exemplars();
+                std::vector<kta_hot_key> keys(job.hot_keys);
+                uint32_t n = 0;
+                if (kta_hot_keys_recover(h0->hot_keys()->data(), job.hot_keys, keys.data(), &n, nullptr) != KTA_OK) n = 0;
+                for (uint32_t k = 0; k < n; k++) {
+                    const uint32_t x = hot_fmix32(keys[k].hash);
+                    const size_t at[2] = {x & 1023u, KTA_HOT_CELLS + ((x >> 10) & 1023u)};
+                    const bool have = (merged[at[0]].valid && merged[at[0]].hash == keys[k].hash) ||
+                                      (merged[at[1]].valid && merged[at[1]].hash == keys[k].hash);
+                    for (size_t a : at)
+                        if (!have && ex[a].valid && ex[a].hash == keys[k].hash) {
+                            merged[a] = ex[a];
+                            break;
+                        }
+                }
+            }
+            text += kta::render_hot_keys(h0->hot_keys()->data(), merged.data(), job.hot_keys);
+        }
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -450,6 +489,16 @@ int main(int argc, char **argv)
         fprintf(stderr, "kta.distinct_keys=1: the topic has %u partitions, the key sketch admits at most %d "
                         "(4096 registers per partition)\n", P, KTA_SKETCH_MAX_PARTITIONS);
         return 2;
+    }
+    uint32_t hot_keys = 0;
+    if (cfg.count("kta.hot_keys")) {
+        const int64_t k = parse_decimal(cfg["kta.hot_keys"], 3);
+        if (k < 1 || k > KTA_HOT_MAX_REPORTED) {
+            fprintf(stderr, "kta.hot_keys=%s: expected the number of keys to report, 1 to %d\n", cfg["kta.hot_keys"].c_str(),
+                    KTA_HOT_MAX_REPORTED);
+            return 2;
+        }
+        hot_keys = (uint32_t)k;
     }
     kta::TimelineConfig timeline;   // kta.timeline=<width>: refused here, before any context, when it cannot be had
     if (cfg.count("kta.timeline")) {
@@ -569,6 +618,7 @@ int main(int argc, char **argv)
         job.analytics = analytics;
         job.timeline = timeline;
         job.distinct_keys = distinct_keys;
+        job.hot_keys = hot_keys;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -585,7 +635,8 @@ int main(int argc, char **argv)
     kta::HipMetricHandler *handler = nullptr;
     try {
         handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
-                                            (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u),
+                                            (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
+                                                (hot_keys ? KTA_FLAG_HOT_KEYS : 0u),
                                             timeline);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -654,7 +705,7 @@ int main(int argc, char **argv)
             kta_batch hb;
             check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
             uint64_t n = std::min<uint64_t>(hb.capacity, n_records - seq), kb = 0;
-            if (!count_alive && !distinct_keys && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
+            if (!count_alive && !distinct_keys && !hot_keys && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
             int rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
             while (rc == KTA_ERR_CAPACITY && n > 1) {  // key bytes did not fit: shrink the batch
                 n /= 2;
@@ -698,7 +749,7 @@ int main(int argc, char **argv)
                 kta_batch hb;
                 check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
                 uint64_t n = std::min<uint64_t>(hb.capacity, db.n - done), kb = 0;
-                if (count_alive || distinct_keys) {  // re-pack this chunk's keys
+                if (count_alive || distinct_keys || hot_keys) {  // re-pack this chunk's keys
                     uint64_t m = 0;
                     for (; m < n; m++) {
                         const uint64_t kl = db.key_len[done + m] > 0 ? (uint64_t)db.key_len[done + m] : 0;
@@ -762,6 +813,7 @@ int main(int argc, char **argv)
         if (timeline.n_buckets)
             text += kta::render_timeline(handler->timeline()->data(), timeline.origin_ms, timeline.bucket_ms, timeline.n_buckets);
         if (distinct_keys) text += kta::render_distinct_keys(handler->key_sketch()->data(), keyed_records(metrics, P));
+        if (hot_keys) text += kta::render_hot_keys(handler->hot_keys()->data(), handler->hot_key_exemplars()->data(), hot_keys);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -72,7 +72,7 @@ uint64_t MessageMetrics::smallest_message() const
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
                                    uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline)
     : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
-      sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0)
+      sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -163,6 +163,12 @@ void HipMetricHandler::read_analytics()
     if (sketch_on_) {
         svec_.assign((size_t)P_ * KTA_SKETCH_REGISTERS, 0);
         check(kta_exchange_key_sketch(ctx_, svec_.data(), svec_.size()), "kta_exchange_key_sketch");
+    }
+    if (hot_on_) {
+        hvec_.assign(KTA_HOT_VECTOR_WORDS, 0);
+        check(kta_exchange_hot_keys(ctx_, hvec_.data(), hvec_.size()), "kta_exchange_hot_keys");
+        hex_.assign((size_t)KTA_HOT_ROWS * KTA_HOT_CELLS, kta_hot_exemplar{});
+        check(kta_get_hot_key_exemplars(ctx_, hex_.data(), hex_.size()), "kta_get_hot_key_exemplars");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

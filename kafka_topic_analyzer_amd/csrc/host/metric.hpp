@@ -134,6 +134,10 @@ public:
     // With KTA_FLAG_KEY_SKETCH: the key sketch u64[P * 4096] of the snapshot finish() / exchange() took (after exchange(),
     // the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *key_sketch() const { return sketch_on_ ? &svec_ : nullptr; }
+    // With KTA_FLAG_HOT_KEYS: the hot-key vector u64[2 * 1024 * 23] of the snapshot finish() / exchange() took (after
+    // exchange(), the whole job's) and this context's own exemplar table [2 * 1024]; nullptr without the flag.
+    const std::vector<uint64_t> *hot_keys() const { return hot_on_ ? &hvec_ : nullptr; }
+    const std::vector<kta_hot_exemplar> *hot_key_exemplars() const { return hot_on_ ? &hex_ : nullptr; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -141,7 +145,7 @@ public:
 
 private:
     void check(int rc, const char *what);
-    void read_analytics();   // the analytics, the timeline and the key sketch of the snapshot
+    void read_analytics();   // the analytics, the timeline, the key sketch and the hot keys of the snapshot
     kta_ctx *ctx_ = nullptr;
     int32_t P_;
     bool alive_;
@@ -155,6 +159,9 @@ private:
     std::vector<uint64_t> tvec_;
     bool sketch_on_ = false;
     std::vector<uint64_t> svec_;
+    bool hot_on_ = false;
+    std::vector<uint64_t> hvec_;
+    std::vector<kta_hot_exemplar> hex_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -175,5 +182,8 @@ std::string format_width_ms(int64_t w);
 // the opt-in section kta-analyzer prints after the report (and the analytics and the timeline) with kta.distinct_keys=1
 // (kta_render_distinct_keys): sketch u64[P * 4096], keyed[p] = key_non_null of partition p
 std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint64_t> &keyed);
+// the opt-in section kta-analyzer prints last with kta.hot_keys=K (kta_render_hot_keys): vec u64[2 * 1024 * 23],
+// exemplars [2 * 1024] or null; empty for a vector kta_hot_keys_recover refuses
+std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys);
 
 }  // namespace kta

@@ -257,7 +257,83 @@ std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint6
     return o;
 }
 
+// murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
+static uint32_t fmix32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
+}
+
+// The opt-in hot-key section (kta.hot_keys=K): no reference counterpart, printed after every other section.
+std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys)
+{
+    std::vector<kta_hot_key> keys(max_keys);
+    uint32_t n = 0;
+    uint64_t keyed = 0;
+    if (kta_hot_keys_recover(vec, max_keys, keys.data(), &n, &keyed) != KTA_OK) return std::string();
+    std::string o;
+    o += "Hot keys, at most " + std::to_string(max_keys) + " (sums of bit counters over the key hashes, 2 rows of 1024 cells: keys from "
+         "1/512 of the keyed records; kta.hot_keys=" + std::to_string(max_keys) + "; not part of the reference report)\n";
+    if (n == 0) {
+        o += "No key holds 1/512 of the " + std::to_string(keyed) + " keyed records.\n";
+        return o;
+    }
+    auto key_text = [&](uint32_t hash) {
+        if (!exemplars) return std::string("-");
+        const uint32_t x = fmix32(hash);
+        const kta_hot_exemplar *found = nullptr;
+        for (const kta_hot_exemplar *e : {exemplars + (x & 1023u), exemplars + KTA_HOT_CELLS + ((x >> 10) & 1023u)})
+            if (!found && e->valid && e->hash == hash) found = e;
+        if (!found) return std::string("-");
+        std::string t;
+        const uint32_t shown = std::min<uint32_t>(found->key_len, KTA_HOT_EXEMPLAR_BYTES);
+        for (uint32_t b = 0; b < shown; b++) {
+            const uint8_t ch = found->bytes[b];
+            if (ch >= 0x20 && ch < 0x7f && ch != '\\') {
+                t += (char)ch;
+            } else {
+                char buf[8];
+                snprintf(buf, sizeof buf, "\\x%02X", ch);
+                t += buf;
+            }
+        }
+        if (found->key_len > KTA_HOT_EXEMPLAR_BYTES) t += "...";
+        return t;
+    };
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"#", "Key", "Hash", "Records (at most)", "(at least)", "Share of keyed records"});
+    for (uint32_t k = 0; k < n; k++) {
+        char hash[16], share[32];
+        snprintf(hash, sizeof hash, "%08x", keys[k].hash);
+        snprintf(share, sizeof share, "%.2f", (double)keys[k].upper * 100.0 / (double)keyed);
+        rows.push_back({std::to_string(k + 1), key_text(keys[k].hash), hash, std::to_string(keys[k].upper),
+                        std::to_string(keys[k].lower), share});
+    }
+    o += pretty_table(rows);
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys, char *out,
+                                   size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || max_keys < 1 || max_keys > KTA_HOT_MAX_REPORTED) return KTA_ERR_INVALID;
+    const std::string text = kta::render_hot_keys(vec, exemplars, max_keys);
+    if (text.empty()) return KTA_ERR_INVALID;   // (a vector no record set leaves)
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_distinct_keys(const uint64_t *sketch_vec, const uint64_t *counter_vec, uint32_t n_partitions,
                                         char *out, size_t out_cap, size_t *out_len)

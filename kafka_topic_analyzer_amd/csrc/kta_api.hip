@@ -33,7 +33,7 @@ struct Stage {
     PinnedBuf<uint8_t> host_slab;
     DeviceBuf<uint8_t> dev_slab;
     size_t metric_bytes = 0;      // [partition .. ts_ms]
-    size_t key_bytes_off = 0;     // where key_bytes starts (0 without -c or the key sketch)
+    size_t key_bytes_off = 0;     // where key_bytes starts (0 without -c, the key sketch or the hot keys)
     size_t slab_bytes = 0;
     Event done;
     bool busy = false;
@@ -70,6 +70,14 @@ struct kta_ctx {
     DeviceBuf<uint64_t> d_sketch_out, d_sketch_stats;
     DeviceBuf<uint8_t> d_sketch_floor;
     uint64_t sketch_launches = 0;
+    // hot keys (KTA_FLAG_HOT_KEYS): d_hot u64[2 * 1024 * 23] the live accumulator, d_hot_out its snapshot, d_hot_slots the
+    // exemplar table, d_hot_ctl the words of its claiming [want 2048 | claim 2048 | mark 64], d_hot_stats the pass's counters
+    bool hot = false;
+    DeviceBuf<uint64_t> d_hot, d_hot_out, d_hot_stats;
+    DeviceBuf<kta_hot_exemplar> d_hot_slots;
+    DeviceBuf<uint32_t> d_hot_ctl;
+    uint64_t hot_launches = 0, hot_workgroups = 0;
+    uint32_t hot_flush_rounds = 0;   // kta_set_hot_flush_rounds (tests); 0: the most the fields admit
     DeviceBuf<uint64_t> d_vec;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     DeviceBuf<uint64_t> d_vec_out;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -256,6 +264,34 @@ int run_key_sketch(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_
     return KTA_OK;
 }
 
+// The hot-key pass over a batch whose metric columns were resolved to rb.  A launch takes a slice, and the candidates its
+// exemplars go by are computed from the accumulator before each: the slices double from 2^16 records to 2^26, so that the
+// heavy keys of a topic's first batch get their exemplars within it.
+constexpr uint64_t kHotSliceMin = 1ull << 16, kHotSliceMax = 1ull << 26;
+constexpr size_t kHotSlotsN = (size_t)KTA_HOT_ROWS * KTA_HOT_CELLS;
+kta::HotState hot_state(kta_ctx *ctx)
+{
+    uint32_t *ctl = ctx->d_hot_ctl.get();
+    return kta::HotState{ctx->d_hot.get(), ctx->d_hot_slots.get(), ctl, ctl + 2 * kHotSlotsN, ctl + kHotSlotsN, ctx->d_hot_stats.get()};
+}
+int run_hot_keys(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_t n)
+{
+    const kta::HotState st = hot_state(ctx);
+    uint64_t slice = kHotSliceMin;
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < slice ? n - at : slice;
+        const kta::SketchColumns sc{rb.hdr ? rb.partition : rb.partition + at, rb.hdr, rb.rec0 + at, c->key_len + at,
+                                    c->key_off + at, c->key_bytes};
+        uint32_t wgs = 0;
+        KTA_HIP(ctx, kta::launch_hot_keys(sc, take, ctx->P, st, ctx->hot_flush_rounds, ctx->cu_count, &wgs, ctx->s_compute));
+        ctx->hot_launches++;
+        ctx->hot_workgroups += wgs;
+        at += take;
+        slice = slice < kHotSliceMax ? slice * 2 : slice;
+    }
+    return KTA_OK;
+}
+
 // The workspace of the partitioned alive pass, large enough for plan pl: the pairs, their counts and the pool grow
 // together (all three released, after the compute stream has drained, before any is allocated again); the pool's control
 // words and the fail lists are allocated once.
@@ -289,6 +325,8 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         return fail(ctx, KTA_ERR_INVALID, "key columns missing (count_alive_keys)");
     if ((which & 1) && ctx->sketch && (!c->key_off || !c->key_bytes))
         return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
+    if ((which & 1) && ctx->hot && (!c->key_off || !c->key_bytes))
+        return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_HOT_KEYS)");
     // Table state: which kernels take the batch is decided before anything is launched (the fused pass below depends on it).
     // 3 = the partitioned pass for batches of >= 2^21 records (13: for batches of any size — tests), with the automatic
     // fall-back to the single-kernel filtered update (2) for batches of mostly unique keys; 1 / 2 / 8 / 9 = the
@@ -456,6 +494,10 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         int rc = run_key_sketch(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
     }
+    if ((which & 1) && ctx->hot) {      // a pass of its own, likewise
+        int rc = run_hot_keys(ctx, c, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     return KTA_OK;
 }
 
@@ -468,6 +510,12 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch.get(), 0, (size_t)ctx->P * kta::kSketchRegs * sizeof(uint32_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->sketch_launches = 0;
+    }
+    if (ctx->hot) {
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot.get(), 0, KTA_HOT_VECTOR_WORDS * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_slots.get(), 0, kHotSlotsN * sizeof(kta_hot_exemplar), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
+        ctx->hot_launches = ctx->hot_workgroups = 0;
     }
     ctx->handed_records = false;
     if (ctx->alive) {
@@ -533,6 +581,7 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
     rv[KTA_RV_ANALYTICS] = ResultVector{ctx->d_avec_out.get(), ctx->analytics ? alen : 0, ctx->analytics ? kta::kAnalyticsHist : 0, true};
     rv[KTA_RV_TIMELINE] = ResultVector{ctx->timeline ? ctx->d_tvec_out.get() : nullptr, tlen, tlen, false};
     rv[KTA_RV_KEY_SKETCH] = ResultVector{ctx->d_sketch_out.get(), ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0, 0, false};
+    rv[KTA_RV_HOT_KEYS] = ResultVector{ctx->d_hot_out.get(), ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, false};
 }
 
 static ResultVector result_vector(kta_ctx *ctx, int kind)
@@ -593,6 +642,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->alive = cfg->count_alive_keys != 0;
     ctx->analytics = (cfg->flags & KTA_FLAG_ANALYTICS) != 0;
     ctx->sketch = (cfg->flags & KTA_FLAG_KEY_SKETCH) != 0;
+    ctx->hot = (cfg->flags & KTA_FLAG_HOT_KEYS) != 0;
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
@@ -638,6 +688,14 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_sketch_floor.alloc(kta::kSketchFloorBytes));
         KTA_TRY(ctx->d_sketch_stats.alloc(3));
     }
+    if (ctx->hot) {
+        KTA_TRY(ctx->d_hot.alloc(KTA_HOT_VECTOR_WORDS));
+        KTA_TRY(ctx->d_hot_out.alloc(KTA_HOT_VECTOR_WORDS));
+        KTA_TRY(hipMemset(ctx->d_hot_out.get(), 0, KTA_HOT_VECTOR_WORDS * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_hot_slots.alloc(kHotSlotsN));
+        KTA_TRY(ctx->d_hot_ctl.alloc(2 * kHotSlotsN + kHotSlotsN / 32));
+        KTA_TRY(ctx->d_hot_stats.alloc(4));
+    }
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_TRY(ctx->d_table.alloc(kta::kAliveSlots));
@@ -681,7 +739,7 @@ static int ensure_stage(kta_ctx *ctx, Stage &st)
 {
     if (st.host_slab) return KTA_OK;
     const uint64_t cap = ctx->batch_capacity, kcap = ctx->key_bytes_capacity;
-    const bool keys = ctx->alive || ctx->sketch, seq = ctx->alive && ctx->stage_seq;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot, seq = ctx->alive && ctx->stage_seq;
     size_t off = 0, o_part, o_klen, o_vlen, o_ts, o_koff = 0, o_seq = 0, o_kb = 0;
     o_part = off; off += pad16(cap * 4);
     o_klen = off; off += pad16(cap * 4);
@@ -737,7 +795,7 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
 {
     if (!ctx) return KTA_ERR_INVALID;
     if (!ctx->acquired) return fail(ctx, KTA_ERR_INVALID, "kta_batch_submit without kta_batch_acquire");
-    const bool keys = ctx->alive || ctx->sketch;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot;
     if (n > ctx->batch_capacity || (keys && n_key_bytes > ctx->key_bytes_capacity))
         return fail(ctx, KTA_ERR_CAPACITY, "batch larger than the staging capacity");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
@@ -800,7 +858,7 @@ int kta_handle_message(kta_ctx *ctx, int32_t partition, int64_t ts_ms, const voi
     if (key_len > INT32_MAX || val_len > INT32_MAX)
         return fail(ctx, KTA_ERR_INVALID, "key/value length above i32 range");
     if (!key) key_len = -1; // m.key() is None iff librdkafka's key pointer is null
-    const bool keys = ctx->alive || ctx->sketch;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot;
     const uint64_t kb = (keys && key_len > 0) ? (uint64_t)key_len : 0;
     if (kb > ctx->key_bytes_capacity) return fail(ctx, KTA_ERR_CAPACITY, "key larger than key_bytes_capacity");
     if (ctx->fill_n > 0 && (ctx->fill_n == ctx->batch_capacity || ctx->fill_kb + kb > ctx->key_bytes_capacity)) {
@@ -843,6 +901,7 @@ int kta_replay_messages(kta_ctx *ctx, const kta_batch *c, uint64_t n)
     if (!c->partition || !c->key_len || !c->val_len || !c->ts_ms) return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
     if (ctx->alive && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (count_alive_keys)");
     if (ctx->sketch && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
+    if (ctx->hot && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_HOT_KEYS)");
     // through a pointer the compiler cannot see through: the loop pays the call a foreign caller pays per message
     static int (*volatile entry)(kta_ctx *, int32_t, int64_t, const void *, int64_t, int64_t) = kta_handle_message;
     static const uint8_t no_bytes[1] = {0};
@@ -1057,7 +1116,7 @@ int kta_finish_device(kta_ctx *ctx)
     ResultVector rv[KTA_RV_KINDS];
     kta_internal_result_vectors(ctx, rv);
     // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
-    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr};
+    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get()};
     for (int k = 0; k < KTA_RV_KINDS; k++)
         if (rv[k].out && live[k])
             KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -1390,6 +1449,164 @@ int kta_merge_key_sketch(uint64_t *acc, const uint64_t *other, uint32_t P)
     return KTA_OK;
 }
 
+static const char *const kNoHot = "context was created without KTA_FLAG_HOT_KEYS";
+
+static int hot_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "hot-key vector", KTA_HOT_VECTOR_WORDS, n_u64); }
+
+int kta_get_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    int rc = hot_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_hot.get(), out, n_u64);
+}
+
+int kta_exchange_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    int rc = hot_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_words(ctx, ctx->d_hot_out.get(), out, n_u64);
+}
+
+int kta_hot_keys_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    return hand_out(result_vector(ctx, KTA_RV_HOT_KEYS), device_ptr, n_u64);
+}
+
+int kta_get_hot_key_exemplars(kta_ctx *ctx, kta_hot_exemplar *out, size_t n_slots)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    if (n_slots != kHotSlotsN)
+        return fail(ctx, KTA_ERR_INVALID, "the exemplar table has " + std::to_string(kHotSlotsN) + " slots, not " + std::to_string(n_slots));
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_hot_slots.get(), kHotSlotsN * sizeof(kta_hot_exemplar), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return KTA_OK;
+}
+
+int kta_hot_keys_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t st[4];
+    int rc = read_words(ctx, ctx->d_hot_stats.get(), st, 4);
+    out[0] = st[0], out[1] = st[1], out[2] = st[2], out[3] = ctx->hot_launches, out[4] = st[3], out[5] = ctx->hot_workgroups;
+    return rc;
+}
+
+int kta_set_hot_flush_rounds(kta_ctx *ctx, uint32_t rounds)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    if (rounds > kta::kHotFlushRoundsMax)
+        return fail(ctx, KTA_ERR_INVALID, "a workgroup flushes after at most " + std::to_string(kta::kHotFlushRoundsMax) + " rounds");
+    ctx->hot_flush_rounds = rounds;
+    return KTA_OK;
+}
+
+int kta_merge_hot_keys(uint64_t *acc, const uint64_t *other)
+{
+    if (!acc || !other) return KTA_ERR_INVALID;
+    merge_words(acc, other, KTA_HOT_VECTOR_WORDS, KTA_HOT_VECTOR_WORDS, false);
+    return KTA_OK;
+}
+
+namespace {
+
+// a^-1 mod 2^32 of an odd a, by Newton's iteration (each step doubles the correct low bits: 3, 6, 12, 24, 48)
+constexpr uint32_t inverse_mod_2_32(uint32_t a)
+{
+    uint32_t v = a;
+    for (int i = 0; i < 5; i++) v *= 2u - a * v;
+    return v;
+}
+constexpr uint32_t kFmixInv1 = inverse_mod_2_32(0x85ebca6bu), kFmixInv2 = inverse_mod_2_32(0xc2b2ae35u);
+static_assert(kFmixInv1 * 0x85ebca6bu == 1u && kFmixInv2 * 0xc2b2ae35u == 1u, "the inverses of fmix32's multipliers");
+
+uint32_t fmix32_inverse(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= kFmixInv2;
+    x ^= (x >> 13) ^ (x >> 26);
+    x *= kFmixInv1;
+    x ^= x >> 16;
+    return x;
+}
+
+// the cell of x in `row` and the 22 bits the cell index leaves
+void hot_cell_of(uint32_t x, int row, uint32_t *cell, uint32_t *y)
+{
+    if (row == 0) *cell = x & 1023u, *y = x >> 10;
+    else *cell = (x >> 10) & 1023u, *y = (x & 1023u) | ((x >> 20) << 10);
+}
+
+} // namespace
+
+int kta_hot_keys_recover(const uint64_t *vec, uint32_t max_out, kta_hot_key *entries, uint32_t *n_out, uint64_t *keyed_out)
+{
+    if (!vec || !n_out || (max_out && !entries) || max_out > KTA_HOT_ROWS * KTA_HOT_CELLS) return KTA_ERR_INVALID;
+    *n_out = 0;
+    uint64_t keyed = 0;
+    for (uint32_t i = 0; i < KTA_HOT_ROWS * KTA_HOT_CELLS; i++) {
+        const uint64_t *a = vec + (size_t)i * KTA_HOT_WORDS;
+        if (a[0] >= (1ull << 54)) return KTA_ERR_INVALID;
+        for (uint32_t b = 1; b < KTA_HOT_WORDS; b++)
+            if (a[b] > a[0]) return KTA_ERR_INVALID;
+        if (i < KTA_HOT_CELLS) keyed += a[0];
+    }
+    if (keyed_out) *keyed_out = keyed;
+    struct Cand { uint32_t x, hash; uint64_t upper, lower; };
+    std::vector<Cand> found;
+    for (uint32_t i = 0; i < KTA_HOT_ROWS * KTA_HOT_CELLS; i++) {
+        const uint64_t *a = vec + (size_t)i * KTA_HOT_WORDS;
+        const uint64_t T = a[0];
+        if (T == 0) continue;
+        uint32_t y = 0;
+        for (uint32_t b = 0; b < KTA_HOT_WORDS - 1; b++)
+            if (2 * a[1 + b] > T) y |= 1u << b;
+        const uint32_t cell = i % KTA_HOT_CELLS;
+        const uint32_t x = i < KTA_HOT_CELLS ? (cell | (y << 10)) : ((y & 1023u) | (cell << 10) | ((y >> 10) << 20));
+        uint64_t upper = UINT64_MAX, lower = 0;
+        for (int row = 0; row < KTA_HOT_ROWS; row++) {
+            uint32_t rc, ry;
+            hot_cell_of(x, row, &rc, &ry);
+            const uint64_t *r = vec + ((size_t)row * KTA_HOT_CELLS + rc) * KTA_HOT_WORDS;
+            const uint64_t Tr = r[0];
+            uint64_t least = Tr, deficit = 0;
+            for (uint32_t b = 0; b < KTA_HOT_WORDS - 1; b++) {
+                const uint64_t agree = ((ry >> b) & 1u) ? r[1 + b] : Tr - r[1 + b];
+                least = std::min(least, agree);
+                deficit += Tr - agree;
+            }
+            upper = std::min(upper, least);
+            lower = std::max(lower, deficit >= Tr ? 0 : Tr - deficit);
+        }
+        if (upper * 512 < keyed) continue;
+        found.push_back(Cand{x, fmix32_inverse(x), upper, lower});
+    }
+    std::sort(found.begin(), found.end(), [](const Cand &p, const Cand &q) {
+        return p.upper != q.upper ? p.upper > q.upper : p.hash < q.hash;
+    });
+    found.erase(std::unique(found.begin(), found.end(), [](const Cand &p, const Cand &q) { return p.x == q.x; }), found.end());
+    const uint32_t n = (uint32_t)std::min<size_t>(found.size(), max_out);
+    for (uint32_t k = 0; k < n; k++) entries[k] = kta_hot_key{found[k].hash, 0u, found[k].upper, found[k].lower};
+    *n_out = n;
+    return KTA_OK;
+}
+
 namespace {
 
 // Ertl 2017, Algorithm 6 (the improved raw estimator) for m = 4096 registers and q = 32 - 12 = 20 hash bits below the
@@ -1649,7 +1866,7 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *))
     ctx->comm_free = free_fn;
     return &ctx->comm_state;
 }
-bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch; }
+bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch || ctx->hot; }
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }

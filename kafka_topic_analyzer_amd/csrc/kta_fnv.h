@@ -1,6 +1,7 @@
 // kta_fnv.h — the reference's FNV-32 variant (src/fnv32.rs:76-101) on gfx950: the byte chain, the 16-byte and four-keys
-// forms and the hash of a key whose first 16 bytes were prefetched.  Shared by the alive-key pass (kta_alive.hip) and the
-// key sketch (kta_sketch.hip); device code only, every helper inlined into its caller.
+// forms and the hash of a key whose first 16 bytes were prefetched, and fmix32, which the sketches put behind it.  Shared by
+// the alive-key pass (kta_alive.hip), the key sketch (kta_sketch.hip) and the hot-key sketch (kta_hot.hip); device code only,
+// every helper inlined into its caller.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,16 @@ namespace {
 
 constexpr uint32_t kFnvInit = 0x811c9dc5u;   // fnv32.rs:80
 constexpr uint32_t kFnvMul = 0x811c9dc5u;    // fnv32.rs:97: the multiplier is the offset basis, not the FNV prime
+
+__device__ __forceinline__ uint32_t fmix32(uint32_t x)   // murmur3's finaliser: a bijection
+{
+    x ^= x >> 16;
+    x *= 0x85ebca6bu;
+    x ^= x >> 13;
+    x *= 0xc2b2ae35u;
+    x ^= x >> 16;
+    return x;
+}
 
 __device__ __forceinline__ uint32_t fnv_byte(uint32_t h, uint32_t b) { return (h ^ b) * kFnvMul; }
 

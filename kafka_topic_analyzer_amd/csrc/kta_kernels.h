@@ -266,4 +266,21 @@ hipError_t launch_key_sketch_floor(const uint32_t *regs, uint32_t P, uint8_t *fl
 // out[i] = regs[i] (u32 -> u64): the snapshot kta_finish_device takes
 hipError_t launch_key_sketch_widen(const uint32_t *regs, uint64_t n, uint64_t *out, hipStream_t s);
 
+// Hot keys (KTA_FLAG_HOT_KEYS, kta_hot.hip): the live accumulator u64[2][1024][23] that the workgroups of launch_hot_keys
+// add their LDS counters to, the exemplar table and the three per-slot words of its claiming (kta_hot_candidates writes
+// them before every launch: the cell's candidate x, a mark bit when the slot does not hold it, a zeroed claim).
+constexpr uint32_t kHotFlushRoundsMax = 511;    // rounds of 4096 records between two flushes: below 2^21 records
+constexpr uint32_t kHotLdsBytes = KTA_HOT_ROWS * KTA_HOT_CELLS * (8 * 8 + 4) + KTA_HOT_ROWS * KTA_HOT_CELLS / 8;
+struct HotState {
+    uint64_t *acc;              // u64[KTA_HOT_VECTOR_WORDS]
+    kta_hot_exemplar *slots;    // [2][1024]
+    uint32_t *want;             // u32[2048]
+    uint32_t *mark;             // u32[64]: a bit per slot
+    uint32_t *claim;            // u32[2048]
+    uint64_t *stats;            // u64[4] += keyed records, add groups, mid-stream flushes, exemplars captured
+};
+// the candidates, then the pass over records [0, n) of c; *workgroups = the pass's grid.  flush_rounds 0: the most.
+hipError_t launch_hot_keys(const SketchColumns &c, uint64_t n, uint32_t P, const HotState &st, uint32_t flush_rounds, int cu_count,
+                           uint32_t *workgroups, hipStream_t s);
+
 } // namespace kta

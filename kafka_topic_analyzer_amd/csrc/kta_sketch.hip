@@ -27,16 +27,6 @@ constexpr int kSketchWgPerCu = 8;
 
 typedef uint32_t v4u_any __attribute__((ext_vector_type(4), aligned(1)));   // 16 key bytes at any address
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t x)   // murmur3's finaliser: a bijection
-{
-    x ^= x >> 16;
-    x *= 0x85ebca6bu;
-    x ^= x >> 13;
-    x *= 0xc2b2ae35u;
-    x ^= x >> 16;
-    return x;
-}
-
 struct SketchCols {
     int32_t kl[4];       // -1: key None, or no record
     uint32_t ko[4];

@@ -81,6 +81,14 @@ def allreduce_timeline_vector(tvec, group=None) -> None:
     _allreduce_sum_max(tvec, tvec.numel(), group)
 
 
+def allreduce_hot_keys_vector(hvec, group=None) -> None:
+    """In-place exchange of an int64 view of the hot-key SNAPSHOT (kta_hot_keys_result_vector: device tensor, or a CPU
+    tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_HOT_KEYS: all-reduce SUM over
+    all of its 2 * 1024 * 23 words.  Exemplars are not moved."""
+    assert hvec.numel() == N.KTA_HOT_VECTOR_WORDS
+    _allreduce_sum_max(hvec, hvec.numel(), group)
+
+
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
