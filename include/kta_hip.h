@@ -229,16 +229,28 @@ typedef struct kta_hot_key {
  *                                means, what host batches and the staging ring always are.
  *   KTA_LAYOUT_TILE_COMPACT (1)  what kta_device_batch_alloc returns.  Records are grouped in tiles of
  *                                KTA_TILE_RECORDS; tile t owns the same bytes of each column as in the raw layout
- *                                (records [t*1024, t*1024+1024)), and tile_hdr[t] says how partition and ts_ms use them:
+ *                                (records [t*1024, t*1024+1024)), and tile_hdr[t].mode says how partition and ts_ms use them:
  *     KTA_TILE_RAW      the raw layout (a zero header: what a fresh allocation holds)
  *     KTA_TILE_COMPACT  partition as u16 in the first half of the tile's partition bytes (KTA_COMPACT_PART_NONE == -1),
  *                       ts_ms as an i32 offset from ts_base in the first half of the tile's ts_ms bytes
  *                       (KTA_COMPACT_TS_NONE == -1, not available): 6 B per record instead of 12.  Taken when every
  *                       partition id lies in [-1, 65535) and the tile's timestamps other than -1 span less than 2^31 ms.
- *   key_len, val_len, key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
+ *   tile_hdr[t].lens, independent of mode, says how key_len and val_len use the tile's bytes:
+ *     KTA_TILE_LENS_I32  i32 per record in both columns, as in the raw layout (a zero header)
+ *     KTA_TILE_LENS_U16  the tile's own 4 KiB of the key_len column hold 256 groups of 16 B: group g has the four u16
+ *                        key lengths of the tile's records 4g .. 4g+3, then their four u16 value lengths
+ *                        (KTA_COMPACT_LEN_NONE == -1, None); the tile's bytes of the val_len column are unused: 4 B per
+ *                        record instead of 8.  Taken when every key_len and val_len of the tile lies in [-1, 65535).
+ *                        ONLY in allocations without key columns (kta_device_batch_alloc with key_bytes_capacity == 0):
+ *                        a keyed allocation never has lens != 0, so the kernels that read lengths next to keys always
+ *                        see plain i32 columns.  When a view into a keyless allocation is handed to a key-reading pass
+ *                        together with key columns of the caller's own, the lengths of the tiles it touches are widened
+ *                        in place first.
+ *   key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
  *   written by kta_synth_fill_device (compact tiles), kta_kafka_decode_device (raw tiles) and kta_batch_from_raw, and
  *   read back by kta_batch_to_raw; a raw-layout kta_batch whose column pointers lie inside a tile-compact allocation of
- *   the same context (a view at a record offset) is resolved to it by every entry point. */
+ *   the same context (a view at a record offset) is resolved to it by every entry point.  Reading key_len / val_len of a
+ *   keyless tile-compact allocation with a plain copy gives the tiles' stored form: use kta_batch_to_raw. */
 #define KTA_LAYOUT_RAW 0u
 #define KTA_LAYOUT_TILE_COMPACT 1u
 #define KTA_TILE_RECORDS 1024u
@@ -246,11 +258,14 @@ typedef struct kta_hot_key {
 #define KTA_TILE_COMPACT 1u
 #define KTA_COMPACT_PART_NONE 0xFFFFu        /* compact partition of a record whose id is -1 */
 #define KTA_COMPACT_TS_NONE INT32_MIN        /* compact timestamp of a record whose ts_ms is -1 */
+#define KTA_TILE_LENS_I32 0u
+#define KTA_TILE_LENS_U16 1u
+#define KTA_COMPACT_LEN_NONE 0xFFFFu         /* u16 length of a record whose key_len / val_len is -1 */
 
 typedef struct kta_tile_hdr {
     int64_t ts_base;   /* KTA_TILE_COMPACT: ts_ms = ts_base + offset */
-    uint32_t mode;     /* KTA_TILE_RAW / KTA_TILE_COMPACT */
-    uint32_t reserved;
+    uint32_t mode;     /* KTA_TILE_RAW / KTA_TILE_COMPACT: partition and ts_ms */
+    uint32_t lens;     /* KTA_TILE_LENS_I32 / KTA_TILE_LENS_U16: key_len and val_len */
 } kta_tile_hdr;
 
 typedef struct kta_batch {
@@ -345,7 +360,7 @@ int kta_device_batch_alloc(kta_ctx *ctx, uint64_t capacity, uint64_t key_bytes_c
 int kta_device_batch_free(kta_ctx *ctx, kta_batch *cols);
 /* The four metric columns (partition, key_len, val_len, ts_ms) of records [0, n) between HOST columns in the raw layout
  * and a device batch of either layout (synchronous).  from_raw packs every tile that the compact form holds losslessly
- * and stores the others raw, so any i32 / i64 values round-trip exactly; into a tile-compact batch it writes from a
+ * (partition and ts_ms; in an allocation without key columns also the lengths, as u16) and stores the others raw, so any i32 / i64 values round-trip exactly; into a tile-compact batch it writes from a
  * tile boundary (record 0 of the allocation or of a view at a multiple of KTA_TILE_RECORDS) and may overwrite the rest
  * of the last tile it touches.  to_raw unpacks. */
 int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *host_cols, uint64_t n, const kta_batch *device_cols);

@@ -78,6 +78,8 @@ class KtaAnalytics(C.Structure):
 
 KTA_LAYOUT_RAW, KTA_LAYOUT_TILE_COMPACT = 0, 1   # kta_batch.layout (include/kta_hip.h)
 KTA_TILE_RECORDS = 1024
+KTA_TILE_RAW, KTA_TILE_COMPACT = 0, 1             # kta_tile_hdr.mode
+KTA_TILE_LENS_I32, KTA_TILE_LENS_U16 = 0, 1        # kta_tile_hdr.lens
 
 
 class KtaBatch(C.Structure):

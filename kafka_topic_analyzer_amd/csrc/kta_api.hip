@@ -203,17 +203,19 @@ void free_device_batch(kta_batch *b)
 // A device batch as the kernels take it.  hdr == null: the raw layout, the pointers are the caller's.  Otherwise a
 // tile-compact allocation: the pointers address its record 0 and the batch starts at its record rec0 — the allocation
 // itself (rec0 0), or a raw-layout kta_batch whose columns point inside one of the context's tile-compact allocations
-// (a view built by pointer arithmetic, rec0 = the offset).
+// (a view built by pointer arithmetic, rec0 = the offset).  keyless: an allocation of the context's without key columns,
+// the only kind whose tiles may hold u16 lengths (kta_hip.h).
 struct Resolved {
     int32_t *partition, *key_len, *val_len;
     int64_t *ts_ms;
     kta_tile_hdr *hdr;
     uint64_t rec0;
+    bool keyless;
 };
 
 int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
 {
-    *r = Resolved{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0};
+    *r = Resolved{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false};
     const uintptr_t p = reinterpret_cast<uintptr_t>(c->partition);
     for (const kta_batch &e : ctx->compact_batches) {
         const uintptr_t lo = reinterpret_cast<uintptr_t>(e.partition);
@@ -224,7 +226,7 @@ int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
         if ((c->ts_ms && c->ts_ms != e.ts_ms + rec0) || (c->key_len && c->key_len != e.key_len + rec0) ||
             (c->val_len && c->val_len != e.val_len + rec0))
             return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
-        *r = Resolved{e.partition, e.key_len, e.val_len, e.ts_ms, e.tile_hdr, rec0};
+        *r = Resolved{e.partition, e.key_len, e.val_len, e.ts_ms, e.tile_hdr, rec0, e.key_bytes == nullptr};
         return KTA_OK;
     }
     if (c->layout == KTA_LAYOUT_TILE_COMPACT) {
@@ -237,6 +239,26 @@ int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Before a pass that reads plain i32 lengths next to keys (the alive-key pass, the key sketch, the hot keys) runs over
+// records [0, n) of c: when c's length columns lie in a keyless allocation — a view of it handed over with key columns
+// of the caller's own —, the u16 tiles the range touches are widened in place (exact; one small pass, and none when the
+// lengths are the caller's own or a keyed allocation's).
+int widen_lens_for_keys(kta_ctx *ctx, const kta_batch *c, uint64_t n)
+{
+    const uintptr_t p = reinterpret_cast<uintptr_t>(c->key_len);
+    for (const kta_batch &e : ctx->compact_batches) {
+        if (e.key_bytes) continue;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(e.key_len);
+        const uint64_t rows = (tiles_of(e.capacity) ? tiles_of(e.capacity) : 1) * KTA_TILE_RECORDS;
+        if (!c->key_len || p < lo || p >= lo + rows * 4) continue;
+        const uint64_t rec0 = (p - lo) / 4;
+        const uint64_t hi = rec0 + n < rows ? rec0 + n : rows;
+        KTA_HIP(ctx, kta::launch_tiles_to_raw(e.partition, e.ts_ms, e.key_len, e.val_len, e.tile_hdr, rec0, hi, 2u, true, ctx->s_compute));
+        return KTA_OK;
+    }
+    return KTA_OK;
+}
 
 constexpr uint64_t kAliveUniqueNum = 2, kAliveUniqueDen = 5;   // > 40 % of a batch's pairs claimed an entry: mostly unique keys
 constexpr int kAliveBackoff = 7;
@@ -365,6 +387,10 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     Resolved rb{};
     if (which & 1) {
         int rc = resolve_batch(ctx, c, &rb);
+        if (rc != KTA_OK) return rc;
+    }
+    if (((which & 2) && ctx->alive) || ((which & 1) && (ctx->sketch || ctx->hot))) {
+        int rc = widen_lens_for_keys(ctx, c, n);
         if (rc != KTA_OK) return rc;
     }
     // the metric columns of records [at, ...) of the batch
@@ -977,6 +1003,14 @@ bool tile_fits_compact(const int32_t *p, const int64_t *t, uint64_t m, int64_t *
     return lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX;
 }
 
+// Whether the lengths of records [0, m) of host columns fit one u16 tile (kta_hip.h).
+bool tile_lens_fit_u16(const int32_t *k, const int32_t *v, uint64_t m)
+{
+    for (uint64_t j = 0; j < m; j++)
+        if (k[j] < -1 || k[j] >= (int32_t)KTA_COMPACT_LEN_NONE || v[j] < -1 || v[j] >= (int32_t)KTA_COMPACT_LEN_NONE) return false;
+    return true;
+}
+
 } // namespace
 
 int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_batch *d)
@@ -990,8 +1024,10 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     int rc = resolve_batch(ctx, d, &r);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    KTA_HIP(ctx, hipMemcpy(d->key_len, h->key_len, n * 4, hipMemcpyHostToDevice));
-    KTA_HIP(ctx, hipMemcpy(d->val_len, h->val_len, n * 4, hipMemcpyHostToDevice));
+    if (!r.hdr || !r.keyless) {   // (a keyless tile-compact allocation takes the lengths tile by tile, below)
+        KTA_HIP(ctx, hipMemcpy(d->key_len, h->key_len, n * 4, hipMemcpyHostToDevice));
+        KTA_HIP(ctx, hipMemcpy(d->val_len, h->val_len, n * 4, hipMemcpyHostToDevice));
+    }
     if (!r.hdr) {
         KTA_HIP(ctx, hipMemcpy(d->partition, h->partition, n * 4, hipMemcpyHostToDevice));
         KTA_HIP(ctx, hipMemcpy(d->ts_ms, h->ts_ms, n * 8, hipMemcpyHostToDevice));
@@ -1004,6 +1040,11 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     std::vector<int32_t> part(nt * KTA_TILE_RECORDS, 0);
     std::vector<int64_t> ts(nt * KTA_TILE_RECORDS, 0);
     std::vector<kta_tile_hdr> hdr(nt);
+    std::vector<int32_t> klen, vlen;
+    if (r.keyless) {
+        klen.assign(nt * KTA_TILE_RECORDS, 0);
+        vlen.assign(nt * KTA_TILE_RECORDS, 0);
+    }
     for (uint64_t T = 0; T < nt; T++) {
         const uint64_t a = T * KTA_TILE_RECORDS, m = n - a < KTA_TILE_RECORDS ? n - a : KTA_TILE_RECORDS;
         int64_t base = 0;
@@ -1016,12 +1057,28 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
                 p16[j] = p == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p;
                 o32[j] = t == -1 ? KTA_COMPACT_TS_NONE : (int32_t)((uint64_t)t - (uint64_t)base);
             }
-            hdr[T] = kta_tile_hdr{base, KTA_TILE_COMPACT, 0};
+            hdr[T] = kta_tile_hdr{base, KTA_TILE_COMPACT, KTA_TILE_LENS_I32};
         } else {
             memcpy(part.data() + a, h->partition + a, m * 4);
             memcpy(ts.data() + a, h->ts_ms + a, m * 8);
-            hdr[T] = kta_tile_hdr{0, KTA_TILE_RAW, 0};
+            hdr[T] = kta_tile_hdr{0, KTA_TILE_RAW, KTA_TILE_LENS_I32};
         }
+        if (!r.keyless) continue;
+        if (tile_lens_fit_u16(h->key_len + a, h->val_len + a, m)) {
+            uint16_t *g16 = reinterpret_cast<uint16_t *>(klen.data() + a);   // 256 groups of {4 key lengths, 4 value lengths}
+            for (uint64_t j = 0; j < m; j++) {
+                g16[(j / 4) * 8 + j % 4] = (uint16_t)h->key_len[a + j];      // (-1 -> KTA_COMPACT_LEN_NONE)
+                g16[(j / 4) * 8 + 4 + j % 4] = (uint16_t)h->val_len[a + j];
+            }
+            hdr[T].lens = KTA_TILE_LENS_U16;
+        } else {
+            memcpy(klen.data() + a, h->key_len + a, m * 4);
+            memcpy(vlen.data() + a, h->val_len + a, m * 4);
+        }
+    }
+    if (r.keyless) {
+        KTA_HIP(ctx, hipMemcpy(r.key_len + r.rec0, klen.data(), klen.size() * 4, hipMemcpyHostToDevice));
+        KTA_HIP(ctx, hipMemcpy(r.val_len + r.rec0, vlen.data(), vlen.size() * 4, hipMemcpyHostToDevice));
     }
     KTA_HIP(ctx, hipMemcpy(r.partition + r.rec0, part.data(), part.size() * 4, hipMemcpyHostToDevice));
     KTA_HIP(ctx, hipMemcpy(r.ts_ms + r.rec0, ts.data(), ts.size() * 8, hipMemcpyHostToDevice));
@@ -1040,7 +1097,7 @@ int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n, const kta_bat
     int rc = resolve_batch(ctx, d, &r);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    KTA_HIP(ctx, hipMemcpy(h->key_len, d->key_len, n * 4, hipMemcpyDeviceToHost));
+    KTA_HIP(ctx, hipMemcpy(h->key_len, d->key_len, n * 4, hipMemcpyDeviceToHost));   // (the records of u16 tiles: replaced below)
     KTA_HIP(ctx, hipMemcpy(h->val_len, d->val_len, n * 4, hipMemcpyDeviceToHost));
     if (!r.hdr) {
         KTA_HIP(ctx, hipMemcpy(h->partition, d->partition, n * 4, hipMemcpyDeviceToHost));
@@ -1065,6 +1122,19 @@ int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n, const kta_bat
         } else {
             h->partition[i] = part[a];
             h->ts_ms[i] = ts[a];
+        }
+    }
+    // u16 tiles (keyless allocations): their groups, tile by tile
+    std::vector<uint16_t> g16(KTA_TILE_RECORDS * 2);
+    for (uint64_t T = 0; T < nt; T++) {
+        if (hdr[T].lens != KTA_TILE_LENS_U16) continue;
+        KTA_HIP(ctx, hipMemcpy(g16.data(), r.key_len + (t0 + T) * KTA_TILE_RECORDS, g16.size() * 2, hipMemcpyDeviceToHost));
+        for (uint64_t j = 0; j < KTA_TILE_RECORDS; j++) {
+            const uint64_t rec = (t0 + T) * KTA_TILE_RECORDS + j;   // allocation index
+            if (rec < r.rec0 || rec - r.rec0 >= n) continue;
+            const uint16_t k = g16[(j / 4) * 8 + j % 4], v = g16[(j / 4) * 8 + 4 + j % 4];
+            h->key_len[rec - r.rec0] = k == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)k;
+            h->val_len[rec - r.rec0] = v == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)v;
         }
     }
     return KTA_OK;
@@ -1894,16 +1964,16 @@ int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
     Resolved r{};
     int rc = resolve_batch(ctx, d, &r);
     if (rc != KTA_OK || !r.hdr || n == 0) return rc;
-    KTA_HIP(ctx, kta::launch_tiles_to_raw(r.partition, r.ts_ms, r.hdr, r.rec0, r.rec0 + n, ctx->s_compute));
+    KTA_HIP(ctx, kta::launch_tiles_to_raw(r.partition, r.ts_ms, r.key_len, r.val_len, r.hdr, r.rec0, r.rec0 + n,
+                                          r.keyless ? 3u : 1u, false, ctx->s_compute));
     return KTA_OK;
 }
 
-int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
-                         uint64_t *rec0)
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out)
 {
     Resolved r{};
     int rc = resolve_batch(ctx, d, &r);
     if (rc != KTA_OK) return rc;
-    *partition = r.partition, *ts_ms = r.ts_ms, *hdr = r.hdr, *rec0 = r.rec0;
+    *out = kta_internal_columns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.keyless};
     return KTA_OK;
 }

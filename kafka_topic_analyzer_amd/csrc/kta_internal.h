@@ -38,11 +38,19 @@ int64_t *kta_internal_running(kta_ctx *ctx);
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);
 uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
 // Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
-// allocation that the range overlaps become raw, on the compute stream.
+// allocation that the range overlaps become raw (partition, ts_ms and, in a keyless allocation, the lengths), on the
+// compute stream.
 int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
-// The allocation's columns and the batch's first record there (hdr null: the raw layout).
-int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, int32_t **partition, int64_t **ts_ms, kta_tile_hdr **hdr,
-                         uint64_t *rec0);
+// The allocation's columns and the batch's first record there (hdr null: the raw layout, the batch's own columns).
+// keyless: an allocation of the context's without key columns — the only kind whose tiles may hold u16 lengths.
+struct kta_internal_columns {
+    int32_t *partition, *key_len, *val_len;
+    int64_t *ts_ms;
+    kta_tile_hdr *hdr;
+    uint64_t rec0;
+    bool keyless;
+};
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out);
 
 // ---- result vectors -----------------------------------------------------------------------------------------------
 // Every section of the result has a snapshot that kta_finish_device takes and kta_exchange reduces in place: words

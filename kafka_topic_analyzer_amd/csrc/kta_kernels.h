@@ -20,7 +20,8 @@ enum ScanGlobal : uint32_t {
 };
 
 // hdr == null: the raw layout, the pointers address record 0 of the batch.  Otherwise the tile-compact layout
-// (kta_hip.h): the pointers address record 0 of the ALLOCATION (tile 0) and the batch is its records [rec0, rec0 + n).
+// (kta_hip.h): the pointers — all four — address record 0 of the ALLOCATION (tile 0) and the batch is its records
+// [rec0, rec0 + n); a tile's header says how its bytes of the four columns are used.
 struct ScanColumns {
     const int32_t *partition;
     const int32_t *key_len;
@@ -140,9 +141,12 @@ hipError_t launch_metrics_scan(const ScanPlan &plan, const ScanColumns &c, uint6
 // K5: fold the per-workgroup partial rows into the persistent counter vector.
 hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_t P, uint64_t *vec,
                                 uint32_t row_len, uint64_t *analytics_vec, hipStream_t s);
-// Tile-compact batches (kta_hip.h): make every tile that overlaps the allocation's records [lo, hi) raw (compact tiles are expanded in place, so
-// records outside the range keep their values) before a producer that writes the raw layout stores into it.
-hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, kta_tile_hdr *hdr, uint64_t lo, uint64_t hi, hipStream_t s);
+// Tile-compact batches (kta_hip.h): make every tile that overlaps the allocation's records [lo, hi) raw (what bit 0:
+// partition and ts_ms; bit 1: the lengths, u16 -> i32), expanded in place, so records outside the range keep their values:
+// before a producer that writes the raw layout stores into the range (what 3), or, with keep — the tiles inside the range
+// are expanded as well —, before a pass that reads plain i32 lengths next to keys runs over it (what 2).
+hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, int32_t *key_len, int32_t *val_len, kta_tile_hdr *hdr,
+                               uint64_t lo, uint64_t hi, uint32_t what, bool keep, hipStream_t s);
 // reset the counter vector to the MessageMetrics::new state (metric.rs:30-46)
 hipError_t launch_init_vector(uint64_t *vec, uint32_t P, uint64_t *analytics_vec, hipStream_t s);
 

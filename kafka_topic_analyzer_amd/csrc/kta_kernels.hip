@@ -43,6 +43,10 @@ namespace kta {
 // one int4 of i32 timestamp offsets per lane next to the two int4 length loads — 14 B per record, every
 // instruction a fully coalesced wave-wide stream (512 B or 1 KiB) — and a raw tile as above.  The compact values
 // travel in the raw registers of the Quad (p.xy, t0) and are widened when the tile is accumulated.
+// The same header's `lens` picks the length loads, independently: a u16 tile (keyless allocations only) gives a lane
+// the four key lengths and the four value lengths of its records in ONE int4 of the key_len column — 10 B per record
+// with compact partitions and timestamps — which rides in the Quad's k registers and is widened (0xFFFF -> -1) when the
+// tile is accumulated.
 //
 // Globals: min/max of ts_ms (-1 => 0 first, metric.rs:209) — the division by 1000
 // (metric.rs:210) is monotone, so it is applied once to the extrema on the host — and
@@ -52,13 +56,20 @@ namespace kta {
 constexpr uint32_t kCntBits = 21;
 constexpr uint64_t kCntMask = (1ull << kCntBits) - 1;
 constexpr uint32_t kFlushTiles = 256;          // 256 tiles x 1024 records = 2^18 records
+#ifndef KTA_SCAN_PREFETCH
+#define KTA_SCAN_PREFETCH 1
+#endif
+constexpr int kTilePrefetch = KTA_SCAN_PREFETCH;   // TILED: tiles a workgroup loads ahead of the one it accumulates (1 or 2)
+static_assert(kTilePrefetch == 1 || kTilePrefetch == 2, "the prefetch ring has two or three slots");
 
 struct Quad {
     int4 p, k, v;
     longlong2 t0, t1;
     long long base;    // TILED: the tile's ts_base
-    uint32_t compact;  // TILED: 1 = p.xy hold four u16 partitions, t0 four i32 timestamp offsets
+    uint32_t compact;  // TILED: bit 0 = p.xy hold four u16 partitions, t0 four i32 timestamp offsets;
+                       //        bit 1 = k holds four u16 key lengths (k.xy) and four u16 value lengths (k.zw)
 };
+constexpr uint32_t kQuadCompact = 1u, kQuadLens16 = 2u;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
@@ -90,44 +101,53 @@ __device__ __forceinline__ void load_quad(Quad &q, const ScanColumns &c, uint64_
     q.compact = 0u;
 }
 
-// TILED: the lane's 4 records of allocation tile T
+template <bool NT>
+__device__ __forceinline__ int4 load16(const void *col, uint64_t i)   // 16-byte unit i of a column
+{
+    if (NT) {
+        const v4i x = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(col) + i);
+        return make_int4(x.x, x.y, x.z, x.w);
+    }
+    return reinterpret_cast<const int4 *>(col)[i];
+}
+
+// TILED: the lane's 4 records of allocation tile T.  One header load picks the length loads (lens) and the partition /
+// timestamp loads (mode).
 template <bool NT>
 __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid)
 {
     const kta_tile_hdr h = c.hdr[T];
     const uint64_t qi = T * (KTA_TILE_RECORDS / 4) + tid;
+    const bool lens16 = h.lens == KTA_TILE_LENS_U16;
+    q.k = load16<NT>(c.key_len, qi);     // u16 tile: group tid, both lengths of the lane's four records
+    if (!lens16) q.v = load16<NT>(c.val_len, qi);
     if (h.mode != KTA_TILE_COMPACT) {
-        load_quad<NT>(q, c, qi);
+        q.p = load16<NT>(c.partition, qi);
+        const int4 a = load16<NT>(c.ts_ms, 2 * qi), b = load16<NT>(c.ts_ms, 2 * qi + 1);
+        q.t0.x = (long long)(((uint64_t)(uint32_t)a.y << 32) | (uint32_t)a.x);
+        q.t0.y = (long long)(((uint64_t)(uint32_t)a.w << 32) | (uint32_t)a.z);
+        q.t1.x = (long long)(((uint64_t)(uint32_t)b.y << 32) | (uint32_t)b.x);
+        q.t1.y = (long long)(((uint64_t)(uint32_t)b.w << 32) | (uint32_t)b.z);
+        q.compact = lens16 ? kQuadLens16 : 0u;
         return;
     }
     const uint64_t ci = T * (KTA_TILE_RECORDS / 2) + tid;   // the tile's first half, in 8-byte / 16-byte units
     v2i p;
-    v4i o;
-    if (NT) {
-        const v4i k = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.key_len) + qi);
-        const v4i v = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.val_len) + qi);
-        p = __builtin_nontemporal_load(reinterpret_cast<const v2i *>(c.partition) + ci);
-        o = __builtin_nontemporal_load(reinterpret_cast<const v4i *>(c.ts_ms) + ci);
-        q.k = make_int4(k.x, k.y, k.z, k.w);
-        q.v = make_int4(v.x, v.y, v.z, v.w);
-    } else {
-        q.k = reinterpret_cast<const int4 *>(c.key_len)[qi];
-        q.v = reinterpret_cast<const int4 *>(c.val_len)[qi];
-        p = reinterpret_cast<const v2i *>(c.partition)[ci];
-        o = reinterpret_cast<const v4i *>(c.ts_ms)[ci];
-    }
+    if (NT) p = __builtin_nontemporal_load(reinterpret_cast<const v2i *>(c.partition) + ci);
+    else p = reinterpret_cast<const v2i *>(c.partition)[ci];
+    const int4 o = load16<NT>(c.ts_ms, ci);
     q.p.x = p.x;
     q.p.y = p.y;
     q.t0.x = (long long)(((uint64_t)(uint32_t)o.y << 32) | (uint32_t)o.x);
     q.t0.y = (long long)(((uint64_t)(uint32_t)o.w << 32) | (uint32_t)o.z);
     q.base = h.ts_base;
-    q.compact = 1u;
+    q.compact = kQuadCompact | (lens16 ? kQuadLens16 : 0u);
 }
 
 // the quad's partitions and raw timestamps, whichever form it was loaded in
 __device__ __forceinline__ void quad_part_ts(const Quad &q, uint32_t (&p)[4], long long (&t)[4])
 {
-    if (q.compact) {
+    if (q.compact & kQuadCompact) {
         const uint32_t u[4] = {(uint32_t)q.p.x & 0xFFFFu, (uint32_t)q.p.x >> 16, (uint32_t)q.p.y & 0xFFFFu, (uint32_t)q.p.y >> 16};
         const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
                               (int32_t)(uint32_t)q.t0.y, (int32_t)(uint32_t)((uint64_t)q.t0.y >> 32)};
@@ -139,6 +159,20 @@ __device__ __forceinline__ void quad_part_ts(const Quad &q, uint32_t (&p)[4], lo
     } else {
         p[0] = (uint32_t)q.p.x, p[1] = (uint32_t)q.p.y, p[2] = (uint32_t)q.p.z, p[3] = (uint32_t)q.p.w;
         t[0] = q.t0.x, t[1] = q.t0.y, t[2] = q.t1.x, t[3] = q.t1.y;
+    }
+}
+
+// the quad's lengths as i32, whichever form they were loaded in
+__device__ __forceinline__ int32_t widen_len16(uint32_t u) { return u == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)u; }
+template <bool TILED>
+__device__ __forceinline__ void quad_lens(const Quad &q, int4 &k, int4 &v)
+{
+    k = q.k;
+    v = q.v;
+    if (TILED && (q.compact & kQuadLens16)) {   // (the raw layout has no such tiles: its instantiations keep their code)
+        const uint32_t kx = (uint32_t)q.k.x, ky = (uint32_t)q.k.y, vx = (uint32_t)q.k.z, vy = (uint32_t)q.k.w;
+        k = make_int4(widen_len16(kx & 0xFFFFu), widen_len16(kx >> 16), widen_len16(ky & 0xFFFFu), widen_len16(ky >> 16));
+        v = make_int4(widen_len16(vx & 0xFFFFu), widen_len16(vx >> 16), widen_len16(vy & 0xFFFFu), widen_len16(vy >> 16));
     }
 }
 
@@ -270,7 +304,7 @@ __device__ __forceinline__ void timeline_quad(const Quad &q, const Rec (&r)[4], 
                                               const TimelineArgs &a, const TimelineLds &T)
 {
     unsigned long long d[4];
-    if (q.compact) {
+    if (q.compact & kQuadCompact) {
         // compact tile: ts = ts_base + o, so d = (ts_base - origin) + o with the difference taken once per tile
         const unsigned long long db = (unsigned long long)q.base - (unsigned long long)a.origin;
         const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
@@ -323,18 +357,20 @@ __device__ __forceinline__ void timeline_quad(const Quad &q, const Rec (&r)[4], 
 // four usually share a partition: then their contributions are combined in registers and cost one
 // set of LDS atomics instead of four (4x fewer same-address conflicts inside a run).
 // valid: bit j = record j of the quad is one of the batch's
-template <int VARIANT, bool ANALYTICS, bool TIMELINE = false>
+template <int VARIANT, bool ANALYTICS, bool TIMELINE = false, bool TILED = false>
 __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2,
                                                 uint32_t rep, const ScanLds &L, LaneState &st,
                                                 const TimelineArgs &ta = TimelineArgs{}, const TimelineLds &T = TimelineLds{})
 {
     uint32_t pt[4];
     long long ts[4];
+    int4 k, v;
     quad_part_ts(q, pt, ts);
-    Rec r[4] = {make_rec(pt[0], q.k.x, q.v.x, ts[0], P, valid & 1u),
-                make_rec(pt[1], q.k.y, q.v.y, ts[1], P, (valid >> 1) & 1u),
-                make_rec(pt[2], q.k.z, q.v.z, ts[2], P, (valid >> 2) & 1u),
-                make_rec(pt[3], q.k.w, q.v.w, ts[3], P, (valid >> 3) & 1u)};
+    quad_lens<TILED>(q, k, v);
+    Rec r[4] = {make_rec(pt[0], k.x, v.x, ts[0], P, valid & 1u),
+                make_rec(pt[1], k.y, v.y, ts[1], P, (valid >> 1) & 1u),
+                make_rec(pt[2], k.z, v.z, ts[2], P, (valid >> 2) & 1u),
+                make_rec(pt[3], k.w, v.w, ts[3], P, (valid >> 3) & 1u)};
 #pragma unroll
     for (int j = 0; j < 4; j++) lane_extrema(r[j], (valid >> j) & 1u, st);
     if (VARIANT == 9) {
@@ -505,23 +541,29 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
         // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
         const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
         const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+        // prefetch ring: the loads of the tile kTilePrefetch deals ahead are issued before the current tile is accumulated;
+        // the slots rotate by moves (cur <- nxt <- nx2), and a slot past the last tile is never loaded nor accumulated
         uint64_t tile = blockIdx.x;
+        Quad nx2;
         if (tile < ntiles) load_tile_quad<NT>(cur, c, t0 + tile, tid);
+        if (kTilePrefetch == 2 && tile + gridDim.x < ntiles) load_tile_quad<NT>(nxt, c, t0 + tile + gridDim.x, tid);
         while (tile < ntiles) { // uniform per workgroup
             const uint64_t ntile = tile + gridDim.x;
-            if (ntile < ntiles) load_tile_quad<NT>(nxt, c, t0 + ntile, tid);
+            const uint64_t ahead = tile + (uint64_t)kTilePrefetch * gridDim.x;
+            if (ahead < ntiles) load_tile_quad<NT>(kTilePrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid);
 
             const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
             uint32_t valid = 0u;
 #pragma unroll
             for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-            accumulate_quad<VARIANT, ANALYTICS, TIMELINE>(cur, valid, P, rep_log2, rep, L, st, ta, T);
+            accumulate_quad<VARIANT, ANALYTICS, TIMELINE, true>(cur, valid, P, rep_log2, rep, L, st, ta, T);
 
             if (++since_flush == kFlushTiles) {
                 flush();
                 since_flush = 0;
             }
             cur = nxt;
+            if (kTilePrefetch == 2) nxt = nx2;
             tile = ntile;
         }
     } else {
@@ -700,34 +742,55 @@ __global__ __launch_bounds__(kWG) void kta_fold_partials(const uint64_t *__restr
     }
 }
 
-// launch_tiles_to_raw: one workgroup per tile, grid-strided over the allocation tiles that overlap [lo, hi).  A compact
-// tile wholly inside the range only changes its header (the producer that follows overwrites all of its records); one
-// the range cuts is expanded in place — every lane reads its 4 records before any lane writes, the compact halves
-// overlap the raw positions.
+// launch_tiles_to_raw: one workgroup per tile, grid-strided over the allocation tiles that overlap [lo, hi).  what bit 0:
+// compact partitions / timestamps become raw; bit 1: u16 lengths become i32.  A tile wholly inside the range only changes
+// its header unless `keep` (the producer that follows overwrites all of its records; a key-reading pass that follows
+// needs them: keep); one the range cuts is expanded in place — every lane reads its 4 records before any lane writes, the
+// compact halves and the u16 groups overlap the raw positions of the tile's first records.
 __global__ __launch_bounds__(kWG) void kta_tiles_to_raw(int32_t *__restrict__ partition, int64_t *__restrict__ ts_ms,
-                                                        kta_tile_hdr *__restrict__ hdr, uint64_t lo, uint64_t hi)
+                                                        int32_t *__restrict__ key_len, int32_t *__restrict__ val_len,
+                                                        kta_tile_hdr *__restrict__ hdr, uint64_t lo, uint64_t hi,
+                                                        uint32_t what, uint32_t keep)
 {
     const uint64_t t0 = lo / KTA_TILE_RECORDS, t1 = (hi + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
     const uint32_t tid = threadIdx.x;
     for (uint64_t T = t0 + blockIdx.x; T < t1; T += gridDim.x) {
-        if (hdr[T].mode != KTA_TILE_COMPACT) continue;   // (uniform)
+        const kta_tile_hdr h = hdr[T];
+        const bool dm = (what & 1u) && h.mode == KTA_TILE_COMPACT, dl = (what & 2u) && h.lens == KTA_TILE_LENS_U16;
+        if (!dm && !dl) continue;   // (uniform)
         const uint64_t first = T * KTA_TILE_RECORDS;
-        if (first < lo || first + KTA_TILE_RECORDS > hi) {
+        if (keep || first < lo || first + KTA_TILE_RECORDS > hi) {
             int32_t p[4];
             long long t[4];
+            int4 g = make_int4(0, 0, 0, 0);
+            if (dm) {
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) tile_record<false>(partition, ts_ms, hdr, first + 4u * tid + j, p[j], t[j]);
+                for (uint32_t j = 0; j < 4; j++) tile_record_h<false>(partition, ts_ms, h, T, first + 4u * tid + j, p[j], t[j]);
+            }
+            if (dl) g = reinterpret_cast<const int4 *>(key_len)[first / 4 + tid];
             __syncthreads();
+            if (dm) {
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                partition[first + 4u * tid + j] = p[j];
-                ts_ms[first + 4u * tid + j] = t[j];
+                for (uint32_t j = 0; j < 4; j++) {
+                    partition[first + 4u * tid + j] = p[j];
+                    ts_ms[first + 4u * tid + j] = t[j];
+                }
+            }
+            if (dl) {
+                const uint32_t w[4] = {(uint32_t)g.x, (uint32_t)g.y, (uint32_t)g.z, (uint32_t)g.w};
+                reinterpret_cast<int4 *>(key_len)[first / 4 + tid] = make_int4(
+                    widen_len16(w[0] & 0xFFFFu), widen_len16(w[0] >> 16), widen_len16(w[1] & 0xFFFFu), widen_len16(w[1] >> 16));
+                reinterpret_cast<int4 *>(val_len)[first / 4 + tid] = make_int4(
+                    widen_len16(w[2] & 0xFFFFu), widen_len16(w[2] >> 16), widen_len16(w[3] & 0xFFFFu), widen_len16(w[3] >> 16));
             }
         }
         __syncthreads();
         if (tid == 0) {
-            hdr[T].ts_base = 0;
-            hdr[T].mode = KTA_TILE_RAW;
+            if (dm) {
+                hdr[T].ts_base = 0;
+                hdr[T].mode = KTA_TILE_RAW;
+            }
+            if (dl) hdr[T].lens = KTA_TILE_LENS_I32;
         }
         __syncthreads();
     }
@@ -1216,12 +1279,14 @@ hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, kta_tile_hdr *hdr, uint64_t lo, uint64_t hi, hipStream_t s)
+hipError_t launch_tiles_to_raw(int32_t *partition, int64_t *ts_ms, int32_t *key_len, int32_t *val_len, kta_tile_hdr *hdr,
+                               uint64_t lo, uint64_t hi, uint32_t what, bool keep, hipStream_t s)
 {
     if (lo >= hi) return hipSuccess;
     const uint64_t tiles = (hi + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - lo / KTA_TILE_RECORDS;
     const uint32_t grid = (uint32_t)(tiles < 8192 ? tiles : 8192);
-    hipLaunchKernelGGL(kta_tiles_to_raw, dim3(grid), dim3(kWG), 0, s, partition, ts_ms, hdr, lo, hi);
+    hipLaunchKernelGGL(kta_tiles_to_raw, dim3(grid), dim3(kWG), 0, s, partition, ts_ms, key_len, val_len, hdr, lo, hi, what,
+                       keep ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -34,32 +34,32 @@ __global__ __launch_bounds__(kWG) void synth_fill_cols(kta_synth_spec sp, uint64
     }
 }
 
-// The tile-compact layout (kta_hip.h): one workgroup per tile, 4 records per lane.  The lengths (and seq) go to the
-// batch's own columns (klen[i]); partition and timestamp are reduced over the tile first — does every id fit a u16, do
-// the timestamps span less than 2^31 ms — and then stored compact or raw into the allocation's tile t0 + T (part, ts),
-// with its header.  One pass, as the raw fill.
+// The tile-compact layout (kta_hip.h): one workgroup per tile, 4 records per lane.  seq goes to the batch's own column;
+// the four metric columns are reduced over the tile first — does every id fit a u16, do the timestamps span less than
+// 2^31 ms, and (lens16: the allocation has no key columns) does every length fit a u16 — and then stored compact or raw
+// into the allocation's tile t0 + T (part, klen, vlen, ts: the allocation's record 0), with its header.  One pass, as
+// the raw fill.
 __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint64_t first, uint64_t n, int32_t *part,
                                                         int32_t *klen, int32_t *vlen, int64_t *ts, uint64_t *seq,
-                                                        kta_tile_hdr *hdr, uint64_t t0)
+                                                        kta_tile_hdr *hdr, uint64_t t0, uint32_t lens16)
 {
     __shared__ long long s_red[kWG / 64][3];
     const uint32_t tid = threadIdx.x;
     const uint64_t ntiles = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
     for (uint64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
-        int32_t p[4];
+        int32_t p[4], kl[4], vl[4];
         int64_t t[4];
-        long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;
+        long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;   // wide: bit 0 a partition id, bit 1 a length outside the u16 form
         for (uint32_t j = 0; j < 4; j++) {
             const uint64_t i = T * KTA_TILE_RECORDS + 4u * tid + j;
             p[j] = -1;
             t[j] = -1;
+            kl[j] = vl[j] = 0;
             if (i >= n) continue;
-            int32_t kl, vl;
-            kta_synth_record(&sp, first + i, &p[j], &kl, &vl, &t[j]);
-            klen[i] = kl;
-            vlen[i] = vl;
+            kta_synth_record(&sp, first + i, &p[j], &kl[j], &vl[j], &t[j]);
             if (seq) seq[i] = first + i;
             wide |= (p[j] < -1 || p[j] >= (int32_t)KTA_COMPACT_PART_NONE) ? 1 : 0;
+            wide |= (kl[j] < -1 || kl[j] >= (int32_t)KTA_COMPACT_LEN_NONE || vl[j] < -1 || vl[j] >= (int32_t)KTA_COMPACT_LEN_NONE) ? 2 : 0;
             if (t[j] != -1) {
                 lo = t[j] < lo ? t[j] : lo;
                 hi = t[j] > hi ? t[j] : hi;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             wide |= s_red[w][2];
         }
         __syncthreads();   // (s_red is reused by the next tile)
-        const bool compact = !wide && (lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX);
+        const bool compact = !(wide & 1) && (lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX);
         const long long base = lo <= hi ? lo : 0;
         const uint64_t A = (t0 + T) * KTA_TILE_RECORDS;   // the tile's first record in the allocation
         if (compact) {
@@ -101,7 +101,17 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             reinterpret_cast<longlong2 *>(ts)[A / 2 + 2 * tid] = make_longlong2(t[0], t[1]);
             reinterpret_cast<longlong2 *>(ts)[A / 2 + 2 * tid + 1] = make_longlong2(t[2], t[3]);
         }
-        if (tid == 0) hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, 0u};
+        const bool u16 = lens16 && !(wide & 2);
+        if (u16) {   // group tid: the lane's four key lengths, then its four value lengths (-1 -> KTA_COMPACT_LEN_NONE)
+            reinterpret_cast<uint4 *>(klen)[A / 4 + tid] =
+                make_uint4((uint32_t)(uint16_t)kl[0] | ((uint32_t)(uint16_t)kl[1] << 16), (uint32_t)(uint16_t)kl[2] | ((uint32_t)(uint16_t)kl[3] << 16),
+                           (uint32_t)(uint16_t)vl[0] | ((uint32_t)(uint16_t)vl[1] << 16), (uint32_t)(uint16_t)vl[2] | ((uint32_t)(uint16_t)vl[3] << 16));
+        } else {     // (whole tiles: the allocation covers them, and the records past n are nobody's)
+            reinterpret_cast<int4 *>(klen)[A / 4 + tid] = make_int4(kl[0], kl[1], kl[2], kl[3]);
+            reinterpret_cast<int4 *>(vlen)[A / 4 + tid] = make_int4(vl[0], vl[1], vl[2], vl[3]);
+        }
+        if (tid == 0)
+            hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, u16 ? KTA_TILE_LENS_U16 : KTA_TILE_LENS_I32};
     }
 }
 
@@ -267,19 +277,21 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
     KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     const uint32_t grid = (uint32_t)((n + kWG - 1) / kWG < 8192 ? (n + kWG - 1) / kWG : 8192);
     // a tile-compact batch from a tile boundary takes the compact fill; anything else the raw one (its tiles made raw first)
-    int32_t *apart = nullptr;
-    int64_t *ats = nullptr;
-    kta_tile_hdr *ahdr = nullptr;
-    uint64_t rec0 = 0;
-    if (int rc = kta_internal_resolve(ctx, b, &apart, &ats, &ahdr, &rec0)) return rc;
+    kta_internal_columns ac{};
+    if (int rc = kta_internal_resolve(ctx, b, &ac)) return rc;
+    kta_tile_hdr *ahdr = ac.hdr;
+    const uint64_t rec0 = ac.rec0;
     if (ahdr && rec0 % KTA_TILE_RECORDS != 0) {
         if (int rc = kta_internal_prepare_raw(ctx, b, n)) return rc;
         ahdr = nullptr;
     }
     if (ahdr) {
         const uint64_t nt = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
-        hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, apart,
-                           b->key_len, b->val_len, ats, b->seq, ahdr, rec0 / KTA_TILE_RECORDS);
+        // u16 lengths only where no kernel reads lengths next to keys: an allocation without key columns, and no key columns
+        // of the caller's own beside it
+        const uint32_t lens16 = ac.keyless && !b->key_off && !b->key_bytes ? 1u : 0u;
+        hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, ac.partition,
+                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, rec0 / KTA_TILE_RECORDS, lens16);
     } else {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);
