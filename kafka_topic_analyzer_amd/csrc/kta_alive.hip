@@ -35,8 +35,7 @@
 // be finished on chip (pool pairs, list overflow) is left untouched and reported to kta_alive_fallback, which
 // resolves it exactly in direct-indexed passes over the bucket's pairs.  A bucket with more distinct slots
 // than the LDS table takes is applied in instalments, in segment order (older ranges first).
-#include "kta_kernels.h"
-#include "kta_fnv.h"
+#include "kta_key_stream.h"
 
 #include <limits.h>
 
@@ -156,7 +155,6 @@ __device__ __forceinline__ T ld_nt(const T *base, uint32_t byte_off)
 {
     return __builtin_nontemporal_load(reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off));
 }
-typedef uint32_t v4u_any __attribute__((ext_vector_type(4), aligned(1)));   // 16 key bytes at any address (unaligned access mode)
 constexpr uint32_t kBlk32 = 16;                    // pairs of a block: what leaves the ring in one piece (64 bytes)
 constexpr uint32_t kRing32 = 2 * kBlk32;           // pairs per bucket ring: two blocks
 constexpr uint32_t kBlkLanes = kBlk32 / 4;         // lanes that move a block (16 bytes each)
@@ -222,7 +220,7 @@ __device__ __noinline__ uint32_t hot_filter(uint32_t guard_off, uint32_t lane, u
 // host checks), so the 21-bit counts cannot overflow.
 struct FuseArgs {
     const int32_t *partition;    // hdr != null: the tile-compact layout (kta_hip.h), the pointers address the allocation's
-    const int64_t *ts_ms;        // record 0 and the batch's record i is the allocation's rec0 + i (tile_record)
+    const int64_t *ts_ms;        // record 0 and the batch's record i is the allocation's rec0 + i (kta_tile.h)
     const kta_tile_hdr *hdr;
     uint64_t rec0;
     uint32_t P;                  // <= kFuseMaxP
@@ -282,6 +280,127 @@ __device__ __forceinline__ void fuse_write_row(const FuseArgs &fz, uint32_t w, c
     }
 }
 
+// FUSE: the lane's share of the global extrema (metric.rs:56-72) and of the records outside [0, P)
+struct FuseLane {
+    long long tmin = LLONG_MAX, tmax = LLONG_MIN;
+    uint32_t smin = 0xFFFFFFFFu, smax = 0u, bad = 0u;   // (0xFFFFFFFF is no size: both lengths are below 2^31)
+};
+
+// FUSE: partition (-2: no record here; a record's bad id stays what it is) and timestamp of the four records
+// at + 64 j + lane of a step (on: the step has a tile at all), as the columns' loads unconditional.  Tile-compact: one
+// header load per step where the step lies in one layout tile (step_tile).  IDX: the batch index's type — with 32 bits
+// (a batch of at most 2^28 records) the raw columns are read at a 32-bit byte offset from a scalar base.
+template <typename IDX>
+__device__ __forceinline__ void fuse_load(const FuseArgs &fz, IDX at, bool on, IDX n, uint32_t lane, int32_t (&pt)[4], long long (&ts)[4])
+{
+    const StepTile st = step_tile(fz.hdr, fz.rec0 + at, kTile, on);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const IDX i = at + 64u * (uint32_t)j + lane;
+        const bool in = on && i < n;
+        const IDX ic = in ? i : n - 1u;
+        if (fz.hdr) {
+            step_tile_record<true>(st, fz.partition, fz.ts_ms, fz.hdr, fz.rec0 + ic, pt[j], ts[j]);
+        } else if (sizeof(IDX) == 4) {
+            pt[j] = ld_nt(fz.partition, (uint32_t)ic * 4u);
+            ts[j] = ld_nt(fz.ts_ms, (uint32_t)ic * 8u);
+        } else {
+            pt[j] = KTA_P32_LOAD(fz.partition + ic);
+            ts[j] = KTA_P32_LOAD(fz.ts_ms + ic);
+        }
+        pt[j] = in ? pt[j] : -2;
+    }
+}
+
+// FUSE: MessageMetrics::handle_message (metric.rs:207-252) for a step's four records, keyed or not
+__device__ __forceinline__ void fuse_accumulate(const FuseArgs &fz, unsigned long long *s_acc, uint32_t lane, const int32_t (&kl)[4],
+                                                const int32_t (&vl)[4], const int32_t (&pt)[4], const long long (&ts)[4], FuseLane &f)
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const bool there = pt[j] != -2;
+        const bool ok = there && (uint32_t)pt[j] < fz.P;                 // (unsigned: negative ids are out as well)
+        const uint32_t tomb = (uint32_t)vl[j] >> 31, knull = (uint32_t)kl[j] >> 31;   // payload None / key None (metric.rs:227-244)
+        const uint32_t ks = knull ? 0u : (uint32_t)kl[j], vs = tomb ? 0u : (uint32_t)vl[j];
+        const long long t = ts[j] == -1ll ? 0ll : ts[j];                 // to_millis() None -> unwrap_or(0) (metric.rs:209)
+        f.bad += there && !ok ? 1u : 0u;
+        if (ok) {
+            f.tmin = t < f.tmin ? t : f.tmin;
+            f.tmax = t > f.tmax ? t : f.tmax;
+            if (!tomb) {                                                 // metric.rs:249-251
+                f.smin = min(f.smin, ks + vs);
+                f.smax = max(f.smax, ks + vs);
+            }
+            unsigned long long *a = s_acc + 3u * (((uint32_t)pt[j] << fz.rep_log2) | (lane & ((1u << fz.rep_log2) - 1u)));
+            atomicAdd(a, 1ull | ((unsigned long long)tomb << kFuseCntBits) | ((unsigned long long)knull << (2 * kFuseCntBits)));
+            atomicAdd(a + 1, (unsigned long long)ks);
+            atomicAdd(a + 2, (unsigned long long)vs);
+        }
+    }
+}
+
+// FUSE, before the workgroup's last barrier: the wave's extrema into its row of s_red
+__device__ __forceinline__ void fuse_reduce_wave(const FuseLane &f, uint32_t lane, uint32_t wave, long long *s_red)
+{
+    long long tmin = f.tmin, tmax = f.tmax, smin = (long long)f.smin, smax = (long long)f.smax, bad = (long long)f.bad;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long a = __shfl_xor(tmin, off), b2 = __shfl_xor(tmax, off), c2 = __shfl_xor(smin, off), d2 = __shfl_xor(smax, off);
+        bad += __shfl_xor(bad, off);
+        tmin = a < tmin ? a : tmin;
+        tmax = b2 > tmax ? b2 : tmax;
+        smin = c2 < smin ? c2 : smin;
+        smax = d2 > smax ? d2 : smax;
+    }
+    if (lane == 0) {
+        long long *o = s_red + wave * 5u;
+        o[0] = tmin, o[1] = tmax, o[2] = smin, o[3] = smax, o[4] = bad;
+    }
+}
+
+// The window walk of a partition workgroup.  Its range of tiles [first, end) is cut into (at most 255) windows of
+// consecutive tiles, and the waves take them as they come (a counter in LDS; from a start that differs from workgroup
+// to workgroup, and around: the ranges lie a power of two apart, and in step all workgroups would ask the same few
+// memory channels).  A window is walked by ONE wave, in order, and its number — its place in the range, not the order
+// of the taking — is what the bit set state's pairs carry (the table state's carry their index: there a window is only
+// the unit of work).
+struct WindowWalk {
+    uint64_t first, end;
+    uint32_t wtiles, nwin, woff;                // tiles per window, windows, the workgroup's first
+    uint64_t cur_tile = 0, cur_stop = 0;        // the cursor (wave-uniform)
+    uint32_t cur_win = 0;
+    __device__ __forceinline__ WindowWalk(uint64_t first_, uint64_t end_, uint32_t w) : first(first_), end(end_)
+    {
+        const uint64_t span = end > first ? end - first : 0u;
+        wtiles = (uint32_t)((span + 254u) / 255u);
+        nwin = wtiles ? (uint32_t)((span + wtiles - 1u) / wtiles) : 0u;
+        woff = nwin ? (w * 37u) % nwin : 0u;
+    }
+};
+// the wave's next tile and its window + 1 (win = 0: the range is used up); next_window: the workgroup's counter in LDS
+__device__ __forceinline__ void next_tile(WindowWalk &k, uint32_t *next_window, uint32_t lane, uint64_t &tile, uint32_t &win)
+{
+    if (k.cur_tile + 1 < k.cur_stop) {
+        k.cur_tile++;
+    } else {
+        uint32_t g = 0;
+        if (lane == 0) g = lds_add(next_window, 1u);
+        g = __builtin_amdgcn_readfirstlane(g);
+        if (g < k.nwin) {
+            const uint32_t cw = g + k.woff < k.nwin ? g + k.woff : g + k.woff - k.nwin;
+            k.cur_tile = k.first + (uint64_t)cw * k.wtiles;
+            k.cur_stop = k.cur_tile + k.wtiles < k.end ? k.cur_tile + k.wtiles : k.end;
+            k.cur_win = cw + 1u;
+        } else {
+            k.cur_win = 0u;
+            k.cur_stop = 0u;
+            k.cur_tile = 0u;
+        }
+    }
+    tile = k.cur_tile;
+    win = k.cur_win;
+}
+
 template <int BLOG2, bool FUSE>
 __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColumns c, uint64_t n, uint32_t tiles_per_wg,
                                                                       uint32_t *__restrict__ pairs, uint32_t *__restrict__ counts,
@@ -313,9 +432,7 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
         if (FUSE)
             for (uint32_t e = threadIdx.x; e < 3 * kFuseSlots; e += kPartThreads) s_acc[e] = 0ull;
     }
-    // FUSE: the lane's share of the global extrema (metric.rs:56-72) and of the records outside [0, P)
-    long long f_tmin = LLONG_MAX, f_tmax = LLONG_MIN;
-    uint32_t f_smin = 0xFFFFFFFFu, f_smax = 0u, f_bad = 0u;   // (0xFFFFFFFF is no size: both lengths are below 2^31)
+    FuseLane f;
     __syncthreads();
     const uint32_t W = gridDim.x, w = blockIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -338,16 +455,6 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
             long long ts[FUSE ? 4 : 1];
         };
         auto load_cols32 = [&](uint64_t tile, bool ok, Cols &r) __attribute__((always_inline)) {
-            // FUSE, tile-compact: a step's 256 records usually lie in one layout tile — then its header is loaded once
-            kta_tile_hdr th{};
-            uint64_t tt = 0;
-            bool one = false;
-            if (FUSE && fz.hdr && ok) {
-                const uint64_t a0 = fz.rec0 + tile * kTile;
-                tt = a0 / KTA_TILE_RECORDS;
-                one = (a0 + kTile - 1) / KTA_TILE_RECORDS == tt;
-                if (one) th = fz.hdr[tt];
-            }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint64_t i = tile * kTile + 64u * j + lane;
@@ -357,102 +464,25 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
                 r.vl[j] = KTA_P32_LOAD(c.val_len + ic);
                 r.ko[j] = KTA_P32_LOAD(c.key_off + ic);
                 r.kl[j] = in ? r.kl[j] : -1;               // key None: ignored (metric.rs:302)
-                if (FUSE) {
-                    if (fz.hdr && one) {
-                        tile_record_h<true>(fz.partition, fz.ts_ms, th, tt, fz.rec0 + ic, r.pt[j], r.ts[j]);
-                    } else if (fz.hdr) {
-                        tile_record<true>(fz.partition, fz.ts_ms, fz.hdr, fz.rec0 + ic, r.pt[j], r.ts[j]);
-                    } else {
-                        r.pt[j] = KTA_P32_LOAD(fz.partition + ic);
-                        r.ts[j] = KTA_P32_LOAD(fz.ts_ms + ic);
-                    }
-                    r.vl[j] = in ? r.vl[j] : 0;
-                    r.pt[j] = in ? r.pt[j] : -2;           // no record here (a record's bad id stays what it is)
-                }
+                if (FUSE) r.vl[j] = in ? r.vl[j] : 0;
             }
+            if constexpr (FUSE) fuse_load<uint64_t>(fz, tile * kTile, ok, n, lane, r.pt, r.ts);
         };
-        auto load_keys32 = [&](const Cols &r, uint4 (&k)[4]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const v4u_any kk = KTA_P32_LOAD(reinterpret_cast<const v4u_any *>(c.key_bytes + (r.kl[j] > 0 ? r.ko[j] : 0u)));
-                k[j] = make_uint4(kk.x, kk.y, kk.z, kk.w);
-            }
-        };
-        // The workgroup's range is cut into (at most 255) windows of consecutive tiles, and the waves take them as they
-        // come (a counter in LDS; from a start that differs from workgroup to workgroup, and around: the ranges lie a
-        // power of two apart, and in step all workgroups would ask the same few memory channels).  A window is
-        // walked by ONE wave, in order, and its number — its place in the range, not the order of the taking — is
-        // what the pairs carry.
-        const uint64_t span = end > first ? end - first : 0u;
-        const uint32_t wtiles = (uint32_t)((span + 254u) / 255u);                 // tiles per window
-        const uint32_t nwin = wtiles ? (uint32_t)((span + wtiles - 1u) / wtiles) : 0u;
-        const uint32_t woff = nwin ? (w * 37u) % nwin : 0u;
-        uint64_t cur_tile = 0, cur_stop = 0;                                     // the walk's cursor (wave-uniform)
-        uint32_t cur_win = 0;
-        auto next_tile = [&](uint64_t &tile, uint32_t &win) __attribute__((always_inline)) {   // win = 0: the range is used up
-            if (cur_tile + 1 < cur_stop) {
-                cur_tile++;
-            } else {
-                uint32_t g = 0;
-                if (lane == 0) g = lds_add(&s_misc[1], 1u);
-                g = __builtin_amdgcn_readfirstlane(g);
-                if (g < nwin) {
-                    const uint32_t cw = g + woff < nwin ? g + woff : g + woff - nwin;
-                    cur_tile = first + (uint64_t)cw * wtiles;
-                    cur_stop = cur_tile + wtiles < end ? cur_tile + wtiles : end;
-                    cur_win = cw + 1u;
-                } else {
-                    cur_win = 0u;
-                    cur_stop = 0u;
-                    cur_tile = 0u;
-                }
-            }
-            tile = cur_tile;
-            win = cur_win;
-        };
+        WindowWalk walk(first, end, w);
         {
             Cols cols_a, cols_b;
             uint4 keys_a[4], keys_b[4];
             uint64_t tl;
-            next_tile(tl, cols_a.win);
+            next_tile(walk, &s_misc[1], lane, tl, cols_a.win);
             load_cols32(tl, cols_a.win != 0u, cols_a);
-            next_tile(tl, cols_b.win);
+            next_tile(walk, &s_misc[1], lane, tl, cols_b.win);
             load_cols32(tl, cols_b.win != 0u, cols_b);
-            load_keys32(cols_a, keys_a);
+            prefetch_keys4<true>(c.key_bytes, cols_a.kl, cols_a.ko, keys_a);
             bool hot = false;                                        // (wave-uniform) the last step dropped records: hot keys about
             auto step = [&](Cols &r, uint4 (&keys)[4], Cols &r_next, uint4 (&keys_next)[4]) __attribute__((always_inline)) {
                 uint32_t h[4];
-                if (__all(r.kl[0] == 16 && r.kl[1] == 16 && r.kl[2] == 16 && r.kl[3] == 16)) {
-                    fnv_16x4(h, keys);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        h[j] = r.kl[j] > 0 ? fnv32_prefetched(keys[j], c.key_bytes + r.ko[j], (uint32_t)r.kl[j]) : kFnvInit;
-                }
-                if (FUSE) {
-                    // MessageMetrics::handle_message (metric.rs:207-252) for the tile's records, keyed or not
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const bool there = r.pt[j] != -2;
-                        const bool ok = there && (uint32_t)r.pt[j] < fz.P;                 // (unsigned: negative ids are out as well)
-                        const uint32_t tomb = (uint32_t)r.vl[j] >> 31, knull = (uint32_t)r.kl[j] >> 31;   // payload None / key None (metric.rs:227-244)
-                        const uint32_t ks = knull ? 0u : (uint32_t)r.kl[j], vs = tomb ? 0u : (uint32_t)r.vl[j];
-                        const long long t = r.ts[j] == -1ll ? 0ll : r.ts[j];               // to_millis() None -> unwrap_or(0) (metric.rs:209)
-                        f_bad += there && !ok ? 1u : 0u;
-                        if (ok) {
-                            f_tmin = t < f_tmin ? t : f_tmin;
-                            f_tmax = t > f_tmax ? t : f_tmax;
-                            if (!tomb) {                                                   // metric.rs:249-251
-                                f_smin = min(f_smin, ks + vs);
-                                f_smax = max(f_smax, ks + vs);
-                            }
-                            unsigned long long *a = s_acc + 3u * (((uint32_t)r.pt[j] << fz.rep_log2) | (lane & ((1u << fz.rep_log2) - 1u)));
-                            atomicAdd(a, 1ull | ((unsigned long long)tomb << kFuseCntBits) | ((unsigned long long)knull << (2 * kFuseCntBits)));
-                            atomicAdd(a + 1, (unsigned long long)ks);
-                            atomicAdd(a + 2, (unsigned long long)vs);
-                        }
-                    }
-                }
+                hash_keys4(h, keys, c.key_bytes, r.kl, r.ko);
+                if constexpr (FUSE) fuse_accumulate(fz, s_acc, lane, r.kl, r.vl, r.pt, r.ts, f);
                 uint32_t pr[4];
                 bool keyed[4];
                 const uint32_t vv = r.win;                           // the window: what the order sees of the tile's place
@@ -461,10 +491,10 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
                     keyed[j] = r.kl[j] >= 0;
                     pr[j] = (h[j] << kPair32Shift) | (vv << 1) | (r.vl[j] >= 0 ? 1u : 0u);
                 }
-                load_keys32(r_next, keys_next);                      // their columns were requested a step ago
+                prefetch_keys4<true>(c.key_bytes, r_next.kl, r_next.ko, keys_next);   // their columns were requested a step ago
                 {
                     uint64_t tn;
-                    next_tile(tn, r.win);
+                    next_tile(walk, &s_misc[1], lane, tn, r.win);
                     load_cols32(tn, r.win != 0u, r);                 // r is spent: hashed
                 }
                 // ---- hot keys: a record whose hash comes again in a LATER instruction of this tile is superseded by that
@@ -632,22 +662,7 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
         }
         for (uint32_t blk = pc_next + lane; blk < pc_end; blk += 64u) pool_tags[blk] = 0u;   // what is left of the last chunk holds nothing
     }
-    if (FUSE) {                                        // the waves' extrema (the consumers' are the neutral elements)
-        long long tmin = f_tmin, tmax = f_tmax, smin = (long long)f_smin, smax = (long long)f_smax, bad = (long long)f_bad;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const long long a = __shfl_xor(tmin, off), b2 = __shfl_xor(tmax, off), c2 = __shfl_xor(smin, off), d2 = __shfl_xor(smax, off);
-            bad += __shfl_xor(bad, off);
-            tmin = a < tmin ? a : tmin;
-            tmax = b2 > tmax ? b2 : tmax;
-            smin = c2 < smin ? c2 : smin;
-            smax = d2 > smax ? d2 : smax;
-        }
-        if (lane == 0) {
-            long long *o = s_red + wave * 5u;
-            o[0] = tmin, o[1] = tmax, o[2] = smin, o[3] = smax, o[4] = bad;
-        }
-    }
+    if (FUSE) fuse_reduce_wave(f, lane, wave, s_red);   // (the consumers' are the neutral elements)
     __syncthreads();
     if (FUSE) fuse_write_row(fz, w, s_acc, s_red);
     // the last, partial block of every segment, and the segment fills for pass 2
@@ -682,8 +697,9 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition32(AliveColum
 // pairs, 2 GB written and read again per 2^28 records — and the kernel read its columns 16 bytes per lane, four
 // consecutive records each, with a register budget (119 of 128) that left no room for the metrics handler.  Now:
 //
-//   * the stream, the window walk and the FUSE arm are kta_alive_partition32's (4-byte column loads, lane j of an
-//     instruction = one record; both handlers of kafka.rs:107-109 in the one pass for a sharded rank as well);
+//   * the stream, the window walk and the FUSE arm are kta_alive_partition32's, the same functions (kta_key_stream.h,
+//     next_tile, fuse_load, fuse_accumulate: 4-byte column loads, lane j of an instruction = one record; both handlers of
+//     kafka.rs:107-109 in the one pass for a sharded rank as well);
 //   * pair48 = slot in the bucket (22 bits), alive, and the record's index INSIDE THE WORKGROUP'S RANGE (22 bits: a
 //     workgroup takes at most 2^22 records, the plan sees to it) — the workgroup is the pair's segment, so the batch-local
 //     index is segment x range + index.  The order of two pairs of one slot is their index: no windows, no guard;
@@ -737,9 +753,7 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition48(AliveColum
         if (FUSE)
             for (uint32_t e = threadIdx.x; e < 3 * kFuseSlots; e += kPartThreads) s_acc[e] = 0ull;
     }
-    // FUSE: the lane's share of the global extrema (metric.rs:56-72) and of the records outside [0, P)
-    long long f_tmin = LLONG_MAX, f_tmax = LLONG_MIN;
-    uint32_t f_smin = 0xFFFFFFFFu, f_smax = 0u, f_bad = 0u;   // (0xFFFFFFFF is no size: both lengths are below 2^31)
+    FuseLane f;
     __syncthreads();
     const uint32_t W = gridDim.x, w = blockIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -774,118 +788,26 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition48(AliveColum
                 if (FUSE) r.vl[j] = in ? r.vl[j] : 0;
             }
         };
-        auto load_keys48 = [&](const Cols &r, uint4 (&k)[4]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const v4u_any kk = KTA_P32_LOAD(reinterpret_cast<const v4u_any *>(c.key_bytes + (r.kl[j] > 0 ? r.ko[j] : 0u)));
-                k[j] = make_uint4(kk.x, kk.y, kk.z, kk.w);
-            }
-        };
         // What only the head of a tile's step reads — FUSE: partition (-2: no record) and timestamp — lives in ONE register
         // set, requested with the tile's key bytes (a step ahead) and spent before the next tile's are requested.
         int32_t x_pt[FUSE ? 4 : 1];
         long long x_ts[FUSE ? 4 : 1];
-        auto load_extra48 = [&](const Cols &r) __attribute__((always_inline)) {
-            if (FUSE) {
-                kta_tile_hdr th{};   // (as kta_alive_partition32: one header load per step where the step lies in one tile)
-                uint64_t tt = 0;
-                bool one = false;
-                if (fz.hdr && r.on != 0u) {
-                    const uint64_t a0 = fz.rec0 + r.at;
-                    tt = a0 / KTA_TILE_RECORDS;
-                    one = (a0 + kTile - 1) / KTA_TILE_RECORDS == tt;
-                    if (one) th = fz.hdr[tt];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint32_t i = r.at + 64u * (uint32_t)j + lane;
-                    const bool in = r.on != 0u && i < nn;
-                    const uint32_t ic = in ? i : nn - 1u;
-                    if (fz.hdr && one) {
-                        tile_record_h<true>(fz.partition, fz.ts_ms, th, tt, fz.rec0 + ic, x_pt[j], x_ts[j]);
-                    } else if (fz.hdr) {
-                        tile_record<true>(fz.partition, fz.ts_ms, fz.hdr, fz.rec0 + ic, x_pt[j], x_ts[j]);
-                    } else {
-                        x_pt[j] = ld_nt(fz.partition, ic * 4u);
-                        x_ts[j] = ld_nt(fz.ts_ms, ic * 8u);
-                    }
-                    x_pt[j] = in ? x_pt[j] : -2;           // no record here (a record's bad id stays what it is)
-                }
-            }
-        };
-        // the walk: kta_alive_partition32's — windows of consecutive tiles taken from a counter, from a start that differs from
-        // workgroup to workgroup (here a window is only the unit of work: the pairs carry their index)
-        const uint64_t span = end > first ? end - first : 0u;
-        const uint32_t wtiles = (uint32_t)((span + 254u) / 255u);                 // tiles per window
-        const uint32_t nwin = wtiles ? (uint32_t)((span + wtiles - 1u) / wtiles) : 0u;
-        const uint32_t woff = nwin ? (w * 37u) % nwin : 0u;
-        uint64_t cur_tile = 0, cur_stop = 0;                                     // the walk's cursor (wave-uniform)
-        uint32_t cur_on = 0;
-        auto next_tile = [&](uint64_t &tile, uint32_t &on) __attribute__((always_inline)) {   // on = 0: the range is used up
-            if (cur_tile + 1 < cur_stop) {
-                cur_tile++;
-            } else {
-                uint32_t g = 0;
-                if (lane == 0) g = lds_add(&s_misc[1], 1u);
-                g = __builtin_amdgcn_readfirstlane(g);
-                if (g < nwin) {
-                    const uint32_t cw = g + woff < nwin ? g + woff : g + woff - nwin;
-                    cur_tile = first + (uint64_t)cw * wtiles;
-                    cur_stop = cur_tile + wtiles < end ? cur_tile + wtiles : end;
-                    cur_on = 1u;
-                } else {
-                    cur_on = 0u;
-                    cur_stop = 0u;
-                    cur_tile = 0u;
-                }
-            }
-            tile = cur_tile;
-            on = cur_on;
-        };
+        WindowWalk walk(first, end, w);
         uint32_t pc_next = 0, pc_end = 0;                  // this wave's chunk of the pool, in pairs (wave-uniform)
         {
             Cols cols_a, cols_b;
             uint4 keys_a[4], keys_b[4];
             uint64_t tl;
-            next_tile(tl, cols_a.on);
+            next_tile(walk, &s_misc[1], lane, tl, cols_a.on);
             load_cols48(tl, cols_a.on != 0u, cols_a);
-            next_tile(tl, cols_b.on);
+            next_tile(walk, &s_misc[1], lane, tl, cols_b.on);
             load_cols48(tl, cols_b.on != 0u, cols_b);
-            load_keys48(cols_a, keys_a);
-            load_extra48(cols_a);
+            prefetch_keys4<true>(c.key_bytes, cols_a.kl, cols_a.ko, keys_a);
+            if constexpr (FUSE) fuse_load<uint32_t>(fz, cols_a.at, cols_a.on != 0u, nn, lane, x_pt, x_ts);
             auto step = [&](Cols &r, uint4 (&keys)[4], Cols &r_next, uint4 (&keys_next)[4]) __attribute__((always_inline)) {
                 uint32_t h[4];
-                if (__all(r.kl[0] == 16 && r.kl[1] == 16 && r.kl[2] == 16 && r.kl[3] == 16)) {
-                    fnv_16x4(h, keys);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        h[j] = r.kl[j] > 0 ? fnv32_prefetched(keys[j], c.key_bytes + r.ko[j], (uint32_t)r.kl[j]) : kFnvInit;
-                }
-                if (FUSE) {
-                    // MessageMetrics::handle_message (metric.rs:207-252) for the tile's records, keyed or not
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const bool there = x_pt[j] != -2;
-                        const bool ok = there && (uint32_t)x_pt[j] < fz.P;                 // (unsigned: negative ids are out as well)
-                        const uint32_t tomb = (uint32_t)r.vl[j] >> 31, knull = (uint32_t)r.kl[j] >> 31;   // payload None / key None (metric.rs:227-244)
-                        const uint32_t ks = knull ? 0u : (uint32_t)r.kl[j], vs = tomb ? 0u : (uint32_t)r.vl[j];
-                        const long long t = x_ts[j] == -1ll ? 0ll : x_ts[j];               // to_millis() None -> unwrap_or(0) (metric.rs:209)
-                        f_bad += there && !ok ? 1u : 0u;
-                        if (ok) {
-                            f_tmin = t < f_tmin ? t : f_tmin;
-                            f_tmax = t > f_tmax ? t : f_tmax;
-                            if (!tomb) {                                                   // metric.rs:249-251
-                                f_smin = min(f_smin, ks + vs);
-                                f_smax = max(f_smax, ks + vs);
-                            }
-                            unsigned long long *a = s_acc + 3u * (((uint32_t)x_pt[j] << fz.rep_log2) | (lane & ((1u << fz.rep_log2) - 1u)));
-                            atomicAdd(a, 1ull | ((unsigned long long)tomb << kFuseCntBits) | ((unsigned long long)knull << (2 * kFuseCntBits)));
-                            atomicAdd(a + 1, (unsigned long long)ks);
-                            atomicAdd(a + 2, (unsigned long long)vs);
-                        }
-                    }
-                }
+                hash_keys4(h, keys, c.key_bytes, r.kl, r.ko);
+                if constexpr (FUSE) fuse_accumulate(fz, s_acc, lane, r.kl, r.vl, x_pt, x_ts, f);
                 // what the inserts need of the tile, in few registers (the columns' are about to be requested again)
                 const uint32_t at = r.at - first_rec + lane;         // the index, inside the workgroup's range, of the lane's first record
                 uint32_t alive_m = 0, ins_m = 0;                     // bit j: record j has a payload / a key
@@ -894,11 +816,11 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition48(AliveColum
                     alive_m |= (r.vl[j] >= 0 ? 1u : 0u) << j;
                     ins_m |= (r.kl[j] >= 0 ? 1u : 0u) << j;
                 }
-                load_keys48(r_next, keys_next);                      // their columns were requested a step ago
-                load_extra48(r_next);
+                prefetch_keys4<true>(c.key_bytes, r_next.kl, r_next.ko, keys_next);   // their columns were requested a step ago
+                if constexpr (FUSE) fuse_load<uint32_t>(fz, r_next.at, r_next.on != 0u, nn, lane, x_pt, x_ts);
                 {
                     uint64_t tn;
-                    next_tile(tn, r.on);
+                    next_tile(walk, &s_misc[1], lane, tn, r.on);
                     load_cols48(tn, r.on != 0u, r);                  // r is spent: hashed
                 }
                 // ---- positions, then the pairs once their ring words are free: straight-line, so that a lane's four
@@ -1083,22 +1005,7 @@ __global__ __launch_bounds__(kPartThreads) void kta_alive_partition48(AliveColum
         }
         if (SEQ && __any(disorder) && lane == 0) atomicOr(order_flag, 1u);
     }
-    if (FUSE) {                                        // the waves' extrema (the consumers' are the neutral elements)
-        long long tmin = f_tmin, tmax = f_tmax, smin = (long long)f_smin, smax = (long long)f_smax, bad = (long long)f_bad;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const long long a = __shfl_xor(tmin, off), b2 = __shfl_xor(tmax, off), c2 = __shfl_xor(smin, off), d2 = __shfl_xor(smax, off);
-            bad += __shfl_xor(bad, off);
-            tmin = a < tmin ? a : tmin;
-            tmax = b2 > tmax ? b2 : tmax;
-            smin = c2 < smin ? c2 : smin;
-            smax = d2 > smax ? d2 : smax;
-        }
-        if (lane == 0) {
-            long long *o = s_red + wave * 5u;
-            o[0] = tmin, o[1] = tmax, o[2] = smin, o[3] = smax, o[4] = bad;
-        }
-    }
+    if (FUSE) fuse_reduce_wave(f, lane, wave, s_red);   // (the consumers' are the neutral elements)
     __syncthreads();
     if (FUSE) fuse_write_row(fz, w, s_acc, s_red);
     // the last, partial block of every segment, and the segment fills for pass 2

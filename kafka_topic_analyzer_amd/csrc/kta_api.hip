@@ -122,7 +122,7 @@ struct kta_ctx {
     uint64_t info_slices = 0, info_fused = 0, info_scanned = 0, info_failed_buckets = 0;
     std::vector<Stage> stages;
     // the tile-compact batches kta_device_batch_alloc handed out (as allocated): a raw-layout kta_batch whose columns point
-    // inside one of them is a view of it at a record offset (resolve_batch)
+    // inside one of them is a view of it at a record offset (kta_internal_resolve)
     std::vector<kta_batch> compact_batches;
     uint64_t batch_capacity = 0, key_bytes_capacity = 0;
     int cur = 0;
@@ -200,42 +200,46 @@ void free_device_batch(kta_batch *b)
     memset(b, 0, sizeof(*b));
 }
 
-// A device batch as the kernels take it.  hdr == null: the raw layout, the pointers are the caller's.  Otherwise a
-// tile-compact allocation: the pointers address its record 0 and the batch starts at its record rec0 — the allocation
-// itself (rec0 0), or a raw-layout kta_batch whose columns point inside one of the context's tile-compact allocations
-// (a view built by pointer arithmetic, rec0 = the offset).  keyless: an allocation of the context's without key columns,
-// the only kind whose tiles may hold u16 lengths (kta_hip.h).
-struct Resolved {
-    int32_t *partition, *key_len, *val_len;
-    int64_t *ts_ms;
-    kta_tile_hdr *hdr;
-    uint64_t rec0;
-    bool keyless;
-};
+// A device batch as the kernels take it is a kta_internal_columns (kta_internal.h).  hdr == null: the raw layout, the
+// pointers are the caller's.  Otherwise a tile-compact allocation: the pointers address its record 0 and the batch starts
+// at its record rec0 — the allocation itself (rec0 0), or a raw-layout kta_batch whose columns point inside one of the
+// context's tile-compact allocations (a view built by pointer arithmetic, rec0 = the offset).
 
-int resolve_batch(kta_ctx *ctx, const kta_batch *c, Resolved *r)
+uint64_t allocation_rows(const kta_batch &e) { return (tiles_of(e.capacity) ? tiles_of(e.capacity) : 1) * KTA_TILE_RECORDS; }
+
+// The tile-compact allocation of the context whose column `col` (partition or key_len) holds the address p, and the
+// record of it that p lies in; null: none does.
+kta_batch *find_allocation(kta_ctx *ctx, const int32_t *p, int32_t *kta_batch::*col, uint64_t *rec0)
 {
-    *r = Resolved{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false};
-    const uintptr_t p = reinterpret_cast<uintptr_t>(c->partition);
-    for (const kta_batch &e : ctx->compact_batches) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(e.partition);
-        const uint64_t rows = (tiles_of(e.capacity) ? tiles_of(e.capacity) : 1) * KTA_TILE_RECORDS;
-        if (!c->partition || p < lo || p >= lo + rows * 4) continue;
-        if ((p - lo) % 4 != 0) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
-        const uint64_t rec0 = (p - lo) / 4;
-        if ((c->ts_ms && c->ts_ms != e.ts_ms + rec0) || (c->key_len && c->key_len != e.key_len + rec0) ||
-            (c->val_len && c->val_len != e.val_len + rec0))
-            return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
-        *r = Resolved{e.partition, e.key_len, e.val_len, e.ts_ms, e.tile_hdr, rec0, e.key_bytes == nullptr};
-        return KTA_OK;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    for (kta_batch &e : ctx->compact_batches) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(e.*col);
+        if (!p || a < lo || a >= lo + allocation_rows(e) * 4) continue;
+        *rec0 = (a - lo) / 4;
+        return &e;
     }
-    if (c->layout == KTA_LAYOUT_TILE_COMPACT) {
-        if (!c->tile_hdr) return fail(ctx, KTA_ERR_INVALID, "a tile-compact batch needs its tile headers");
-        r->hdr = c->tile_hdr;
-    } else if (c->layout != KTA_LAYOUT_RAW) {
-        return fail(ctx, KTA_ERR_INVALID, "unknown batch layout");
-    }
-    return KTA_OK;
+    return nullptr;
+}
+
+// The columns of records [at, ...) of a resolved batch, in either layout: a raw batch's pointers move, a tile-compact
+// batch keeps the allocation's record 0 and its first record moves.
+kta_internal_columns columns_at(const kta_internal_columns &rb, uint64_t at)
+{
+    kta_internal_columns r = rb;
+    r.rec0 += at;
+    if (!rb.hdr) r.partition += at, r.key_len += at, r.val_len += at, r.ts_ms += at;
+    return r;
+}
+kta::ScanColumns scan_columns(const kta_internal_columns &rb, uint64_t at)
+{
+    const kta_internal_columns r = columns_at(rb, at);
+    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0};
+}
+// (the key-reading passes take the lengths and the keys from the batch's own columns: plain i32 in both layouts)
+kta::SketchColumns sketch_columns(const kta_internal_columns &rb, const kta_batch *c, uint64_t at)
+{
+    const kta_internal_columns r = columns_at(rb, at);
+    return kta::SketchColumns{r.partition, r.hdr, r.rec0, c->key_len + at, c->key_off + at, c->key_bytes};
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -246,17 +250,11 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 // lengths are the caller's own or a keyed allocation's).
 int widen_lens_for_keys(kta_ctx *ctx, const kta_batch *c, uint64_t n)
 {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(c->key_len);
-    for (const kta_batch &e : ctx->compact_batches) {
-        if (e.key_bytes) continue;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(e.key_len);
-        const uint64_t rows = (tiles_of(e.capacity) ? tiles_of(e.capacity) : 1) * KTA_TILE_RECORDS;
-        if (!c->key_len || p < lo || p >= lo + rows * 4) continue;
-        const uint64_t rec0 = (p - lo) / 4;
-        const uint64_t hi = rec0 + n < rows ? rec0 + n : rows;
-        KTA_HIP(ctx, kta::launch_tiles_to_raw(e.partition, e.ts_ms, e.key_len, e.val_len, e.tile_hdr, rec0, hi, 2u, true, ctx->s_compute));
-        return KTA_OK;
-    }
+    uint64_t rec0 = 0;
+    const kta_batch *e = find_allocation(ctx, c->key_len, &kta_batch::key_len, &rec0);
+    if (!e || e->key_bytes) return KTA_OK;
+    const uint64_t rows = allocation_rows(*e), hi = rec0 + n < rows ? rec0 + n : rows;
+    KTA_HIP(ctx, kta::launch_tiles_to_raw(e->partition, e->ts_ms, e->key_len, e->val_len, e->tile_hdr, rec0, hi, 2u, true, ctx->s_compute));
     return KTA_OK;
 }
 
@@ -265,25 +263,31 @@ constexpr int kAliveBackoff = 7;
 
 kta::WrittenList written_list(kta_ctx *ctx) { return kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()}; }
 
+// A pass that takes a batch in slices that double from lo records to hi: launch(at, take) per slice.
+template <class F> int for_doubling_slices(uint64_t n, uint64_t lo, uint64_t hi, F launch)
+{
+    for (uint64_t at = 0, slice = lo; at < n; slice = slice < hi ? slice * 2 : slice) {
+        const uint64_t take = n - at < slice ? n - at : slice;
+        int rc = launch(at, take);
+        if (rc != KTA_OK) return rc;
+        at += take;
+    }
+    return KTA_OK;
+}
+
 // The key sketch over a batch whose metric columns were resolved to rb.  A launch takes a slice, and the floors of its
 // filter are refreshed from the registers before each: the slices double from 2^20 records to 2^26, so that the floors
 // of a fresh sketch rise within the first large batch.
 constexpr uint64_t kSketchSliceMin = 1ull << 20, kSketchSliceMax = 1ull << 26;
-int run_key_sketch(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_t n)
+int run_key_sketch(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n)
 {
-    uint64_t slice = kSketchSliceMin;
-    for (uint64_t at = 0; at < n;) {
-        const uint64_t take = n - at < slice ? n - at : slice;
-        const kta::SketchColumns sc{rb.hdr ? rb.partition : rb.partition + at, rb.hdr, rb.rec0 + at, c->key_len + at,
-                                    c->key_off + at, c->key_bytes};
+    return for_doubling_slices(n, kSketchSliceMin, kSketchSliceMax, [&](uint64_t at, uint64_t take) -> int {
         KTA_HIP(ctx, kta::launch_key_sketch_floor(ctx->d_sketch.get(), ctx->P, ctx->d_sketch_floor.get(), ctx->s_compute));
-        KTA_HIP(ctx, kta::launch_key_sketch(sc, take, ctx->P, ctx->d_sketch.get(), ctx->d_sketch_floor.get(), ctx->d_sketch_stats.get(),
-                                            ctx->cu_count, ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_key_sketch(sketch_columns(rb, c, at), take, ctx->P, ctx->d_sketch.get(), ctx->d_sketch_floor.get(),
+                                            ctx->d_sketch_stats.get(), ctx->cu_count, ctx->s_compute));
         ctx->sketch_launches++;
-        at += take;
-        slice = slice < kSketchSliceMax ? slice * 2 : slice;
-    }
-    return KTA_OK;
+        return KTA_OK;
+    });
 }
 
 // The hot-key pass over a batch whose metric columns were resolved to rb.  A launch takes a slice, and the candidates its
@@ -296,22 +300,16 @@ kta::HotState hot_state(kta_ctx *ctx)
     uint32_t *ctl = ctx->d_hot_ctl.get();
     return kta::HotState{ctx->d_hot.get(), ctx->d_hot_slots.get(), ctl, ctl + 2 * kHotSlotsN, ctl + kHotSlotsN, ctx->d_hot_stats.get()};
 }
-int run_hot_keys(kta_ctx *ctx, const kta_batch *c, const Resolved &rb, uint64_t n)
+int run_hot_keys(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n)
 {
     const kta::HotState st = hot_state(ctx);
-    uint64_t slice = kHotSliceMin;
-    for (uint64_t at = 0; at < n;) {
-        const uint64_t take = n - at < slice ? n - at : slice;
-        const kta::SketchColumns sc{rb.hdr ? rb.partition : rb.partition + at, rb.hdr, rb.rec0 + at, c->key_len + at,
-                                    c->key_off + at, c->key_bytes};
+    return for_doubling_slices(n, kHotSliceMin, kHotSliceMax, [&](uint64_t at, uint64_t take) -> int {
         uint32_t wgs = 0;
-        KTA_HIP(ctx, kta::launch_hot_keys(sc, take, ctx->P, st, ctx->hot_flush_rounds, ctx->cu_count, &wgs, ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_hot_keys(sketch_columns(rb, c, at), take, ctx->P, st, ctx->hot_flush_rounds, ctx->cu_count, &wgs, ctx->s_compute));
         ctx->hot_launches++;
         ctx->hot_workgroups += wgs;
-        at += take;
-        slice = slice < kHotSliceMax ? slice * 2 : slice;
-    }
-    return KTA_OK;
+        return KTA_OK;
+    });
 }
 
 // The workspace of the partitioned alive pass, large enough for plan pl: the pairs, their counts and the pool grow
@@ -384,25 +382,19 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
             !aligned16(c->ts_ms))
             return fail(ctx, KTA_ERR_INVALID, "device columns must be 16-byte aligned");
     }
-    Resolved rb{};
+    kta_internal_columns rb{};
     if (which & 1) {
-        int rc = resolve_batch(ctx, c, &rb);
+        int rc = kta_internal_resolve(ctx, c, &rb);
         if (rc != KTA_OK) return rc;
     }
     if (((which & 2) && ctx->alive) || ((which & 1) && (ctx->sketch || ctx->hot))) {
         int rc = widen_lens_for_keys(ctx, c, n);
         if (rc != KTA_OK) return rc;
     }
-    // the metric columns of records [at, ...) of the batch
-    auto scan_cols = [&](uint64_t at) {
-        return kta::ScanColumns{rb.hdr ? rb.partition : rb.partition + at, rb.hdr ? rb.key_len : rb.key_len + at,
-                                rb.hdr ? rb.val_len : rb.val_len + at, rb.hdr ? rb.ts_ms : rb.ts_ms + at, rb.hdr,
-                                rb.rec0 + at};
-    };
     // The metrics handler over records [at, at + m): plan the scan, clamp it to the partial workspace, launch it and
     // fold its rows.  timed: with the event pairs of kinds 0 (scan) and 1 (fold) around the two launches.
     auto scan_and_fold = [&](uint64_t at, uint64_t m, bool timed) -> int {
-        const kta::ScanColumns sc = scan_cols(at);
+        const kta::ScanColumns sc = scan_columns(rb, at);
         kta::ScanPlan pl = kta::plan_scan(ctx->P, m, ctx->cu_count, ctx->scan_wgs, ctx->scan_variant, ctx->analytics,
                                           sc.hdr != nullptr, tl_buckets);
         if (pl.workgroups > ctx->max_rows) pl.workgroups = ctx->max_rows;
@@ -481,7 +473,7 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
                     ctx->info_fused++;
                     ctx->handed_records = true;
                     const uint32_t row_len = kta::scan_row_len(ctx->P, false);
-                    const kta::ScanColumns sc = scan_cols(at);
+                    const kta::ScanColumns sc = scan_columns(rb, at);
                     const kta::AliveFuse fz{sc.partition, sc.ts_ms, sc.hdr, sc.rec0, ctx->P, ctx->d_partials.get(), row_len};
                     KTA_HIP(ctx, kta::launch_alive_partitioned(sl, take, base_seq + at, st, pl, ws, report ? ctx->d_alive_stats.get() : nullptr,
                                                                ctx->s_compute, &fz));
@@ -978,40 +970,12 @@ int kta_device_batch_free(kta_ctx *ctx, kta_batch *cols)
     if (!ctx || !cols) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    for (size_t i = 0; i < ctx->compact_batches.size(); i++)
-        if (cols->partition && ctx->compact_batches[i].partition == cols->partition) {
-            ctx->compact_batches.erase(ctx->compact_batches.begin() + (long)i);
-            break;
-        }
+    uint64_t rec0 = 0;
+    const kta_batch *e = find_allocation(ctx, cols->partition, &kta_batch::partition, &rec0);
+    if (e && e->partition == cols->partition) ctx->compact_batches.erase(ctx->compact_batches.begin() + (e - ctx->compact_batches.data()));
     free_device_batch(cols);
     return KTA_OK;
 }
-
-namespace {
-
-// Whether records [0, m) of host columns fit one compact tile (kta_hip.h), and its ts_base.
-bool tile_fits_compact(const int32_t *p, const int64_t *t, uint64_t m, int64_t *base)
-{
-    int64_t lo = INT64_MAX, hi = INT64_MIN;
-    for (uint64_t j = 0; j < m; j++) {
-        if (p[j] < -1 || p[j] >= (int32_t)KTA_COMPACT_PART_NONE) return false;
-        if (t[j] == -1) continue;
-        lo = t[j] < lo ? t[j] : lo;
-        hi = t[j] > hi ? t[j] : hi;
-    }
-    *base = lo <= hi ? lo : 0;
-    return lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX;
-}
-
-// Whether the lengths of records [0, m) of host columns fit one u16 tile (kta_hip.h).
-bool tile_lens_fit_u16(const int32_t *k, const int32_t *v, uint64_t m)
-{
-    for (uint64_t j = 0; j < m; j++)
-        if (k[j] < -1 || k[j] >= (int32_t)KTA_COMPACT_LEN_NONE || v[j] < -1 || v[j] >= (int32_t)KTA_COMPACT_LEN_NONE) return false;
-    return true;
-}
-
-} // namespace
 
 int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_batch *d)
 {
@@ -1020,8 +984,8 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     if (!h->partition || !h->key_len || !h->val_len || !h->ts_ms || !d->partition || !d->key_len || !d->val_len || !d->ts_ms)
         return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    Resolved r{};
-    int rc = resolve_batch(ctx, d, &r);
+    kta_internal_columns r{};
+    int rc = kta_internal_resolve(ctx, d, &r);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     if (!r.hdr || !r.keyless) {   // (a keyless tile-compact allocation takes the lengths tile by tile, below)
@@ -1047,34 +1011,8 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     }
     for (uint64_t T = 0; T < nt; T++) {
         const uint64_t a = T * KTA_TILE_RECORDS, m = n - a < KTA_TILE_RECORDS ? n - a : KTA_TILE_RECORDS;
-        int64_t base = 0;
-        if (tile_fits_compact(h->partition + a, h->ts_ms + a, m, &base)) {
-            uint16_t *p16 = reinterpret_cast<uint16_t *>(part.data() + a);
-            int32_t *o32 = reinterpret_cast<int32_t *>(ts.data() + a);
-            for (uint64_t j = 0; j < m; j++) {
-                const int32_t p = h->partition[a + j];
-                const int64_t t = h->ts_ms[a + j];
-                p16[j] = p == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p;
-                o32[j] = t == -1 ? KTA_COMPACT_TS_NONE : (int32_t)((uint64_t)t - (uint64_t)base);
-            }
-            hdr[T] = kta_tile_hdr{base, KTA_TILE_COMPACT, KTA_TILE_LENS_I32};
-        } else {
-            memcpy(part.data() + a, h->partition + a, m * 4);
-            memcpy(ts.data() + a, h->ts_ms + a, m * 8);
-            hdr[T] = kta_tile_hdr{0, KTA_TILE_RAW, KTA_TILE_LENS_I32};
-        }
-        if (!r.keyless) continue;
-        if (tile_lens_fit_u16(h->key_len + a, h->val_len + a, m)) {
-            uint16_t *g16 = reinterpret_cast<uint16_t *>(klen.data() + a);   // 256 groups of {4 key lengths, 4 value lengths}
-            for (uint64_t j = 0; j < m; j++) {
-                g16[(j / 4) * 8 + j % 4] = (uint16_t)h->key_len[a + j];      // (-1 -> KTA_COMPACT_LEN_NONE)
-                g16[(j / 4) * 8 + 4 + j % 4] = (uint16_t)h->val_len[a + j];
-            }
-            hdr[T].lens = KTA_TILE_LENS_U16;
-        } else {
-            memcpy(klen.data() + a, h->key_len + a, m * 4);
-            memcpy(vlen.data() + a, h->val_len + a, m * 4);
-        }
+        hdr[T] = kta::tile_pack_host(h->partition + a, h->ts_ms + a, h->key_len + a, h->val_len + a, m, r.keyless, part.data() + a, ts.data() + a,
+                                     r.keyless ? klen.data() + a : nullptr, r.keyless ? vlen.data() + a : nullptr);
     }
     if (r.keyless) {
         KTA_HIP(ctx, hipMemcpy(r.key_len + r.rec0, klen.data(), klen.size() * 4, hipMemcpyHostToDevice));
@@ -1093,8 +1031,8 @@ int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n, const kta_bat
     if (!h->partition || !h->key_len || !h->val_len || !h->ts_ms || !d->partition || !d->key_len || !d->val_len || !d->ts_ms)
         return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    Resolved r{};
-    int rc = resolve_batch(ctx, d, &r);
+    kta_internal_columns r{};
+    int rc = kta_internal_resolve(ctx, d, &r);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     KTA_HIP(ctx, hipMemcpy(h->key_len, d->key_len, n * 4, hipMemcpyDeviceToHost));   // (the records of u16 tiles: replaced below)
@@ -1111,31 +1049,16 @@ int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n, const kta_bat
     KTA_HIP(ctx, hipMemcpy(part.data(), r.partition + t0 * KTA_TILE_RECORDS, part.size() * 4, hipMemcpyDeviceToHost));
     KTA_HIP(ctx, hipMemcpy(ts.data(), r.ts_ms + t0 * KTA_TILE_RECORDS, ts.size() * 8, hipMemcpyDeviceToHost));
     KTA_HIP(ctx, hipMemcpy(hdr.data(), r.hdr + t0, nt * sizeof(kta_tile_hdr), hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t a = r.rec0 + i - t0 * KTA_TILE_RECORDS, T = a / KTA_TILE_RECORDS;   // (a: index into the images)
-        if (hdr[T].mode == KTA_TILE_COMPACT) {
-            const uint64_t ci = a + T * KTA_TILE_RECORDS;
-            const uint16_t p = reinterpret_cast<const uint16_t *>(part.data())[ci];
-            const int32_t o = reinterpret_cast<const int32_t *>(ts.data())[ci];
-            h->partition[i] = p == KTA_COMPACT_PART_NONE ? -1 : (int32_t)p;
-            h->ts_ms[i] = o == KTA_COMPACT_TS_NONE ? -1 : (int64_t)((uint64_t)hdr[T].ts_base + (uint64_t)(int64_t)o);
-        } else {
-            h->partition[i] = part[a];
-            h->ts_ms[i] = ts[a];
-        }
-    }
-    // u16 tiles (keyless allocations): their groups, tile by tile
-    std::vector<uint16_t> g16(KTA_TILE_RECORDS * 2);
+    // tile by tile, the batch's records of it; a u16 tile (keyless allocations) brings its groups
+    std::vector<int32_t> g16(KTA_TILE_RECORDS);
     for (uint64_t T = 0; T < nt; T++) {
-        if (hdr[T].lens != KTA_TILE_LENS_U16) continue;
-        KTA_HIP(ctx, hipMemcpy(g16.data(), r.key_len + (t0 + T) * KTA_TILE_RECORDS, g16.size() * 2, hipMemcpyDeviceToHost));
-        for (uint64_t j = 0; j < KTA_TILE_RECORDS; j++) {
-            const uint64_t rec = (t0 + T) * KTA_TILE_RECORDS + j;   // allocation index
-            if (rec < r.rec0 || rec - r.rec0 >= n) continue;
-            const uint16_t k = g16[(j / 4) * 8 + j % 4], v = g16[(j / 4) * 8 + 4 + j % 4];
-            h->key_len[rec - r.rec0] = k == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)k;
-            h->val_len[rec - r.rec0] = v == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)v;
-        }
+        const uint64_t a = (t0 + T) * KTA_TILE_RECORDS;   // the tile's first record in the allocation
+        const uint64_t j0 = a < r.rec0 ? r.rec0 - a : 0, j1 = r.rec0 + n - a < KTA_TILE_RECORDS ? r.rec0 + n - a : KTA_TILE_RECORDS;
+        const bool u16 = hdr[T].lens == KTA_TILE_LENS_U16;
+        if (u16) KTA_HIP(ctx, hipMemcpy(g16.data(), r.key_len + a, g16.size() * 4, hipMemcpyDeviceToHost));
+        const uint64_t o = a + j0 - r.rec0;               // the batch's record
+        kta::tile_unpack_host(hdr[T], part.data() + T * KTA_TILE_RECORDS, ts.data() + T * KTA_TILE_RECORDS, u16 ? g16.data() : nullptr, nullptr,
+                              j0, j1, h->partition + o, h->ts_ms + o, h->key_len + o, h->val_len + o);
     }
     return KTA_OK;
 }
@@ -1961,19 +1884,31 @@ void kta_internal_set_error(kta_ctx *ctx, const char *msg) { ctx->err = msg; }
 
 int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
 {
-    Resolved r{};
-    int rc = resolve_batch(ctx, d, &r);
+    kta_internal_columns r{};
+    int rc = kta_internal_resolve(ctx, d, &r);
     if (rc != KTA_OK || !r.hdr || n == 0) return rc;
     KTA_HIP(ctx, kta::launch_tiles_to_raw(r.partition, r.ts_ms, r.key_len, r.val_len, r.hdr, r.rec0, r.rec0 + n,
                                           r.keyless ? 3u : 1u, false, ctx->s_compute));
     return KTA_OK;
 }
 
-int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out)
+int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns *r)
 {
-    Resolved r{};
-    int rc = resolve_batch(ctx, d, &r);
-    if (rc != KTA_OK) return rc;
-    *out = kta_internal_columns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.keyless};
+    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false};
+    uint64_t rec0 = 0;
+    if (const kta_batch *e = find_allocation(ctx, c->partition, &kta_batch::partition, &rec0)) {
+        if (e->partition + rec0 != c->partition) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
+        if ((c->ts_ms && c->ts_ms != e->ts_ms + rec0) || (c->key_len && c->key_len != e->key_len + rec0) ||
+            (c->val_len && c->val_len != e->val_len + rec0))
+            return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
+        *r = kta_internal_columns{e->partition, e->key_len, e->val_len, e->ts_ms, e->tile_hdr, rec0, e->key_bytes == nullptr};
+        return KTA_OK;
+    }
+    if (c->layout == KTA_LAYOUT_TILE_COMPACT) {
+        if (!c->tile_hdr) return fail(ctx, KTA_ERR_INVALID, "a tile-compact batch needs its tile headers");
+        r->hdr = c->tile_hdr;
+    } else if (c->layout != KTA_LAYOUT_RAW) {
+        return fail(ctx, KTA_ERR_INVALID, "unknown batch layout");
+    }
     return KTA_OK;
 }

@@ -1,7 +1,7 @@
 // kta_fnv.h — the reference's FNV-32 variant (src/fnv32.rs:76-101) on gfx950: the byte chain, the 16-byte and four-keys
 // forms and the hash of a key whose first 16 bytes were prefetched, and fmix32, which the sketches put behind it.  Shared by
-// the alive-key pass (kta_alive.hip), the key sketch (kta_sketch.hip) and the hot-key sketch (kta_hot.hip); device code only,
-// every helper inlined into its caller.
+// the alive-key pass (kta_alive.hip), the key sketch (kta_sketch.hip) and the hot-key sketch (kta_hot.hip) through the keyed
+// record stream (kta_key_stream.h); device code only, every helper inlined into its caller.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -21,8 +21,7 @@
 //                       per slot and launch.
 //   kta_hot_candidates  before every launch: every cell's candidate x from the live accumulator (the bits set in more than
 //                       half of the cell's records), marked when the cell's slot does not hold it; clears the claims.
-#include "kta_kernels.h"
-#include "kta_fnv.h"
+#include "kta_key_stream.h"
 
 #include <algorithm>
 
@@ -42,14 +41,6 @@ constexpr uint32_t kHotLdsWords = kHotSlots * kHotCellWords;
 constexpr int kHotCombine = 2;                   // groups of equal x combined per instruction
 static_assert(kHotFlushRoundsMax * kHotRound <= kHotFieldMask, "a field holds the records of a flush period");
 static_assert(kHotLdsBytes == kHotLdsWords * 8 + kHotSlots * 4 + kHotSlots / 8, "counters, want, mark");
-
-typedef uint32_t v4u_any __attribute__((ext_vector_type(4), aligned(1)));   // 16 key bytes at any address
-
-struct HotCols {
-    int32_t kl[4];       // -1: key None, or no record
-    uint32_t ko[4];
-    int32_t pt[4];
-};
 
 __global__ __launch_bounds__(kHotThreads) void kta_hot_keys(SketchColumns c, uint64_t n, uint32_t P, unsigned long long *acc,
                                                             const uint32_t *__restrict__ want, const uint32_t *__restrict__ mark,
@@ -72,35 +63,6 @@ __global__ __launch_bounds__(kHotThreads) void kta_hot_keys(SketchColumns c, uin
     const uint64_t rounds = (nsteps + per_round - 1) / per_round;   // the same for every wave of the grid
     uint64_t step = (uint64_t)blockIdx.x * kHotWaves + (threadIdx.x >> 6);
     uint32_t n_keyed = 0, n_groups = 0, n_flush = 0, n_claim = 0;   // (wave-uniform but n_claim)
-
-    auto load_cols = [&](uint64_t st, HotCols &r) __attribute__((always_inline)) {
-        const bool ok = st < nsteps;
-        // tile-compact: the step's records usually lie in one layout tile, whose mode is then loaded once
-        const uint64_t a0 = c.rec0 + st * kHotStep;
-        const uint64_t t0 = a0 / KTA_TILE_RECORDS;
-        const uint32_t m0 = (c.hdr && ok) ? c.hdr[t0].mode : KTA_TILE_RAW;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint64_t i = st * kHotStep + 64u * j + lane;
-            const bool in = ok && i < n;
-            const uint64_t ic = in ? i : n - 1;
-            r.kl[j] = __builtin_nontemporal_load(c.key_len + ic);
-            r.ko[j] = __builtin_nontemporal_load(c.key_off + ic);
-            if (c.hdr) {
-                const uint64_t ai = c.rec0 + ic, t = ai / KTA_TILE_RECORDS;
-                const uint32_t mode = t == t0 ? m0 : c.hdr[t].mode;
-                if (mode == KTA_TILE_COMPACT) {
-                    const uint32_t pu = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(c.partition) + ai + t * KTA_TILE_RECORDS);
-                    r.pt[j] = pu == KTA_COMPACT_PART_NONE ? -1 : (int32_t)pu;
-                } else {
-                    r.pt[j] = __builtin_nontemporal_load(c.partition + ai);
-                }
-            } else {
-                r.pt[j] = __builtin_nontemporal_load(c.partition + ic);
-            }
-            r.kl[j] = in ? r.kl[j] : -1;
-        }
-    };
 
     // the workgroup's non-zero fields to the accumulator (between two barriers)
     auto flush = [&]() __attribute__((always_inline)) {
@@ -131,8 +93,8 @@ __global__ __launch_bounds__(kHotThreads) void kta_hot_keys(SketchColumns c, uin
         }
     };
 
-    HotCols cur;
-    load_cols(step, cur);
+    KeyedCols cur;
+    load_keyed_cols<kHotStep>(c, step, nsteps, n, lane, cur);
     for (uint64_t round = 0; round < rounds; round++) {
         if (round != 0 && round % flush_rounds == 0) {
             __syncthreads();
@@ -141,22 +103,12 @@ __global__ __launch_bounds__(kHotThreads) void kta_hot_keys(SketchColumns c, uin
             n_flush++;
         }
         uint4 keys[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const v4u_any kk = *reinterpret_cast<const v4u_any *>(c.key_bytes + (cur.kl[j] > 0 ? cur.ko[j] : 0u));
-            keys[j] = make_uint4(kk.x, kk.y, kk.z, kk.w);
-        }
+        prefetch_keys4<false>(c.key_bytes, cur.kl, cur.ko, keys);
         const uint64_t next = step + per_round;
-        HotCols nxt;
-        load_cols(next, nxt);
+        KeyedCols nxt;
+        load_keyed_cols<kHotStep>(c, next, nsteps, n, lane, nxt);
         uint32_t h[4];
-        if (__all(cur.kl[0] == 16 && cur.kl[1] == 16 && cur.kl[2] == 16 && cur.kl[3] == 16)) {
-            fnv_16x4(h, keys);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                h[j] = cur.kl[j] > 0 ? fnv32_prefetched(keys[j], c.key_bytes + cur.ko[j], (uint32_t)cur.kl[j]) : kFnvInit;
-        }
+        hash_keys4(h, keys, c.key_bytes, cur.kl, cur.ko);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             // key Some (the empty key included) in a partition the metrics handler counts

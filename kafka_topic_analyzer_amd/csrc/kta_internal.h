@@ -41,7 +41,8 @@ uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
 // allocation that the range overlaps become raw (partition, ts_ms and, in a keyless allocation, the lengths), on the
 // compute stream.
 int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n);
-// The allocation's columns and the batch's first record there (hdr null: the raw layout, the batch's own columns).
+// A device batch resolved: the allocation's columns and the batch's first record there (hdr null: the raw layout, the
+// batch's own columns) — what kta_api.hip itself works with and builds the kernels' column structs from.
 // keyless: an allocation of the context's without key columns — the only kind whose tiles may hold u16 lengths.
 struct kta_internal_columns {
     int32_t *partition, *key_len, *val_len;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "kta_hip.h"
+#include "kta_tile.h"
 
 namespace kta {
 
@@ -49,37 +50,6 @@ struct WrittenList {
 };
 
 #ifdef __HIPCC__
-// Partition id and raw timestamp of record i (an allocation index) of a tile-compact batch.  In a compact tile the
-// u16 / i32 of record i sit at element i + tile * KTA_TILE_RECORDS of the column seen as u16 / i32: the first half of
-// the tile's own bytes.
-// (tile_record_h: the header h of allocation tile `tile` is already loaded.  A record of another tile reads in-bounds
-// garbage — for records the caller masks.)
-template <bool NT>
-__device__ __forceinline__ void tile_record_h(const int32_t *part, const int64_t *ts, const kta_tile_hdr &h, uint64_t tile,
-                                              uint64_t i, int32_t &p, long long &t)
-{
-    if (h.mode == KTA_TILE_COMPACT) {
-        const uint64_t ci = i + tile * KTA_TILE_RECORDS;
-        const uint16_t *p16 = reinterpret_cast<const uint16_t *>(part) + ci;
-        const int32_t *t32 = reinterpret_cast<const int32_t *>(ts) + ci;
-        const uint32_t pu = NT ? __builtin_nontemporal_load(p16) : *p16;
-        const int32_t o = NT ? __builtin_nontemporal_load(t32) : *t32;
-        p = pu == KTA_COMPACT_PART_NONE ? -1 : (int32_t)pu;
-        t = o == KTA_COMPACT_TS_NONE ? -1ll : (long long)((uint64_t)h.ts_base + (uint64_t)(int64_t)o);
-    } else {
-        p = NT ? __builtin_nontemporal_load(part + i) : part[i];
-        t = NT ? __builtin_nontemporal_load(ts + i) : ts[i];
-    }
-}
-
-template <bool NT>
-__device__ __forceinline__ void tile_record(const int32_t *part, const int64_t *ts, const kta_tile_hdr *hdr, uint64_t i,
-                                            int32_t &p, long long &t)
-{
-    const uint64_t tile = i / KTA_TILE_RECORDS;
-    tile_record_h<NT>(part, ts, hdr[tile], tile, i, p, t);
-}
-
 // wave-aggregated append (works under divergence: the ballot covers the active lanes)
 __device__ __forceinline__ void note_new_slot(const WrittenList &wl, bool is_new, uint32_t slot)
 {

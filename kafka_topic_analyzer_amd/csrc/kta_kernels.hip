@@ -148,13 +148,14 @@ __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, ui
 __device__ __forceinline__ void quad_part_ts(const Quad &q, uint32_t (&p)[4], long long (&t)[4])
 {
     if (q.compact & kQuadCompact) {
-        const uint32_t u[4] = {(uint32_t)q.p.x & 0xFFFFu, (uint32_t)q.p.x >> 16, (uint32_t)q.p.y & 0xFFFFu, (uint32_t)q.p.y >> 16};
-        const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
-                              (int32_t)(uint32_t)q.t0.y, (int32_t)(uint32_t)((uint64_t)q.t0.y >> 32)};
+        uint32_t u[4];
+        int32_t o[4];
+        tile_u16x4((uint32_t)q.p.x, (uint32_t)q.p.y, u);
+        tile_i32x4(q.t0.x, q.t0.y, o);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            p[j] = u[j] == KTA_COMPACT_PART_NONE ? 0xFFFFFFFFu : u[j];
-            t[j] = o[j] == KTA_COMPACT_TS_NONE ? -1ll : (long long)((uint64_t)q.base + (uint64_t)(int64_t)o[j]);
+            p[j] = (uint32_t)tile_unpack_part(u[j]);
+            t[j] = tile_unpack_ts(o[j], q.base);
         }
     } else {
         p[0] = (uint32_t)q.p.x, p[1] = (uint32_t)q.p.y, p[2] = (uint32_t)q.p.z, p[3] = (uint32_t)q.p.w;
@@ -163,16 +164,21 @@ __device__ __forceinline__ void quad_part_ts(const Quad &q, uint32_t (&p)[4], lo
 }
 
 // the quad's lengths as i32, whichever form they were loaded in
-__device__ __forceinline__ int32_t widen_len16(uint32_t u) { return u == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)u; }
+// (half a u16 group: two dwords are four key lengths, or four value lengths)
+__device__ __forceinline__ int4 widen_lens4(int32_t w0, int32_t w1)
+{
+    uint32_t u[4];
+    tile_u16x4((uint32_t)w0, (uint32_t)w1, u);
+    return make_int4(tile_unpack_len(u[0]), tile_unpack_len(u[1]), tile_unpack_len(u[2]), tile_unpack_len(u[3]));
+}
 template <bool TILED>
 __device__ __forceinline__ void quad_lens(const Quad &q, int4 &k, int4 &v)
 {
     k = q.k;
     v = q.v;
     if (TILED && (q.compact & kQuadLens16)) {   // (the raw layout has no such tiles: its instantiations keep their code)
-        const uint32_t kx = (uint32_t)q.k.x, ky = (uint32_t)q.k.y, vx = (uint32_t)q.k.z, vy = (uint32_t)q.k.w;
-        k = make_int4(widen_len16(kx & 0xFFFFu), widen_len16(kx >> 16), widen_len16(ky & 0xFFFFu), widen_len16(ky >> 16));
-        v = make_int4(widen_len16(vx & 0xFFFFu), widen_len16(vx >> 16), widen_len16(vy & 0xFFFFu), widen_len16(vy >> 16));
+        k = widen_lens4(q.k.x, q.k.y);
+        v = widen_lens4(q.k.z, q.k.w);
     }
 }
 
@@ -307,8 +313,8 @@ __device__ __forceinline__ void timeline_quad(const Quad &q, const Rec (&r)[4], 
     if (q.compact & kQuadCompact) {
         // compact tile: ts = ts_base + o, so d = (ts_base - origin) + o with the difference taken once per tile
         const unsigned long long db = (unsigned long long)q.base - (unsigned long long)a.origin;
-        const int32_t o[4] = {(int32_t)(uint32_t)q.t0.x, (int32_t)(uint32_t)((uint64_t)q.t0.x >> 32),
-                              (int32_t)(uint32_t)q.t0.y, (int32_t)(uint32_t)((uint64_t)q.t0.y >> 32)};
+        int32_t o[4];
+        tile_i32x4(q.t0.x, q.t0.y, o);
 #pragma unroll
         for (int j = 0; j < 4; j++) d[j] = db + (unsigned long long)(long long)o[j];
     } else {
@@ -777,11 +783,8 @@ __global__ __launch_bounds__(kWG) void kta_tiles_to_raw(int32_t *__restrict__ pa
                 }
             }
             if (dl) {
-                const uint32_t w[4] = {(uint32_t)g.x, (uint32_t)g.y, (uint32_t)g.z, (uint32_t)g.w};
-                reinterpret_cast<int4 *>(key_len)[first / 4 + tid] = make_int4(
-                    widen_len16(w[0] & 0xFFFFu), widen_len16(w[0] >> 16), widen_len16(w[1] & 0xFFFFu), widen_len16(w[1] >> 16));
-                reinterpret_cast<int4 *>(val_len)[first / 4 + tid] = make_int4(
-                    widen_len16(w[2] & 0xFFFFu), widen_len16(w[2] >> 16), widen_len16(w[3] & 0xFFFFu), widen_len16(w[3] >> 16));
+                reinterpret_cast<int4 *>(key_len)[first / 4 + tid] = widen_lens4(g.x, g.y);
+                reinterpret_cast<int4 *>(val_len)[first / 4 + tid] = widen_lens4(g.z, g.w);
             }
         }
         __syncthreads();

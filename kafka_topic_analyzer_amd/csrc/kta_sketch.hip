@@ -12,8 +12,7 @@
 //                         update: the registers are exact whatever the filters see.
 //   kta_key_sketch_floor  floors[p][g] = min of the group's registers (u8)
 //   kta_key_sketch_widen  the u32 live registers into the u64 snapshot (one register per word: what the collectives reduce)
-#include "kta_kernels.h"
-#include "kta_fnv.h"
+#include "kta_key_stream.h"
 
 #include <algorithm>
 
@@ -24,14 +23,6 @@ namespace {
 constexpr int kSketchThreads = 256;
 constexpr uint32_t kSketchStep = 256;            // records of one wave step: instruction j of it takes the records 64 j + lane
 constexpr int kSketchWgPerCu = 8;
-
-typedef uint32_t v4u_any __attribute__((ext_vector_type(4), aligned(1)));   // 16 key bytes at any address
-
-struct SketchCols {
-    int32_t kl[4];       // -1: key None, or no record
-    uint32_t ko[4];
-    int32_t pt[4];
-};
 
 __global__ __launch_bounds__(kSketchThreads) void kta_key_sketch(SketchColumns c, uint64_t n, uint32_t P, uint32_t *regs,
                                                                   const uint8_t *__restrict__ floors, uint32_t group_shift,
@@ -50,55 +41,16 @@ __global__ __launch_bounds__(kSketchThreads) void kta_key_sketch(SketchColumns c
     uint64_t step = (uint64_t)blockIdx.x * (kSketchThreads / 64) + (threadIdx.x >> 6);
     uint32_t n_keyed = 0, n_read = 0, n_atomic = 0;   // (wave-uniform: popcounts of ballots)
 
-    auto load_cols = [&](uint64_t st, SketchCols &r) __attribute__((always_inline)) {
-        const bool ok = st < nsteps;
-        // tile-compact: the step's records usually lie in one layout tile, whose mode is then loaded once
-        const uint64_t a0 = c.rec0 + st * kSketchStep;
-        const uint64_t t0 = a0 / KTA_TILE_RECORDS;
-        const uint32_t m0 = (c.hdr && ok) ? c.hdr[t0].mode : KTA_TILE_RAW;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint64_t i = st * kSketchStep + 64u * j + lane;
-            const bool in = ok && i < n;
-            const uint64_t ic = in ? i : n - 1;
-            r.kl[j] = __builtin_nontemporal_load(c.key_len + ic);
-            r.ko[j] = __builtin_nontemporal_load(c.key_off + ic);
-            if (c.hdr) {
-                const uint64_t ai = c.rec0 + ic, t = ai / KTA_TILE_RECORDS;
-                const uint32_t mode = t == t0 ? m0 : c.hdr[t].mode;
-                if (mode == KTA_TILE_COMPACT) {
-                    const uint32_t pu = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>(c.partition) + ai + t * KTA_TILE_RECORDS);
-                    r.pt[j] = pu == KTA_COMPACT_PART_NONE ? -1 : (int32_t)pu;
-                } else {
-                    r.pt[j] = __builtin_nontemporal_load(c.partition + ai);
-                }
-            } else {
-                r.pt[j] = __builtin_nontemporal_load(c.partition + ic);
-            }
-            r.kl[j] = in ? r.kl[j] : -1;
-        }
-    };
-
-    SketchCols cur;
-    load_cols(step, cur);
+    KeyedCols cur;
+    load_keyed_cols<kSketchStep>(c, step, nsteps, n, lane, cur);
     while (step < nsteps) {
         uint4 keys[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const v4u_any kk = *reinterpret_cast<const v4u_any *>(c.key_bytes + (cur.kl[j] > 0 ? cur.ko[j] : 0u));
-            keys[j] = make_uint4(kk.x, kk.y, kk.z, kk.w);
-        }
+        prefetch_keys4<false>(c.key_bytes, cur.kl, cur.ko, keys);
         const uint64_t next = step + waves;
-        SketchCols nxt;
-        load_cols(next, nxt);
+        KeyedCols nxt;
+        load_keyed_cols<kSketchStep>(c, next, nsteps, n, lane, nxt);
         uint32_t h[4];
-        if (__all(cur.kl[0] == 16 && cur.kl[1] == 16 && cur.kl[2] == 16 && cur.kl[3] == 16)) {
-            fnv_16x4(h, keys);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                h[j] = cur.kl[j] > 0 ? fnv32_prefetched(keys[j], c.key_bytes + cur.ko[j], (uint32_t)cur.kl[j]) : kFnvInit;
-        }
+        hash_keys4(h, keys, c.key_bytes, cur.kl, cur.ko);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             // key Some (the empty key included) in a partition the metrics handler counts

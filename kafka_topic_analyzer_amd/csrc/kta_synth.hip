@@ -4,6 +4,7 @@
 #include "../../include/kta_synth.h"
 
 #include "kta_internal.h"
+#include "kta_tile.h"
 
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -58,8 +59,8 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             if (i >= n) continue;
             kta_synth_record(&sp, first + i, &p[j], &kl[j], &vl[j], &t[j]);
             if (seq) seq[i] = first + i;
-            wide |= (p[j] < -1 || p[j] >= (int32_t)KTA_COMPACT_PART_NONE) ? 1 : 0;
-            wide |= (kl[j] < -1 || kl[j] >= (int32_t)KTA_COMPACT_LEN_NONE || vl[j] < -1 || vl[j] >= (int32_t)KTA_COMPACT_LEN_NONE) ? 2 : 0;
+            wide |= kta::tile_part_fits(p[j]) ? 0 : 1;
+            wide |= kta::tile_len_fits(kl[j]) && kta::tile_len_fits(vl[j]) ? 0 : 2;
             if (t[j] != -1) {
                 lo = t[j] < lo ? t[j] : lo;
                 hi = t[j] > hi ? t[j] : hi;
@@ -83,18 +84,18 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             wide |= s_red[w][2];
         }
         __syncthreads();   // (s_red is reused by the next tile)
-        const bool compact = !(wide & 1) && (lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX);
-        const long long base = lo <= hi ? lo : 0;
+        int64_t base;
+        const bool compact = kta::tile_ts_fits(lo, hi, &base) && !(wide & 1);
         const uint64_t A = (t0 + T) * KTA_TILE_RECORDS;   // the tile's first record in the allocation
         if (compact) {
             uint16_t u[4];
             int32_t o[4];
             for (uint32_t j = 0; j < 4; j++) {
-                u[j] = p[j] == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p[j];
-                o[j] = t[j] == -1 ? KTA_COMPACT_TS_NONE : (int32_t)((uint64_t)t[j] - (uint64_t)base);
+                u[j] = kta::tile_pack_part(p[j]);
+                o[j] = kta::tile_pack_ts(t[j], base);
             }
             reinterpret_cast<uint2 *>(part)[(2 * A) / 4 + tid] =
-                make_uint2((uint32_t)u[0] | ((uint32_t)u[1] << 16), (uint32_t)u[2] | ((uint32_t)u[3] << 16));
+                make_uint2(kta::tile_u16x2_word(u[0], u[1]), kta::tile_u16x2_word(u[2], u[3]));
             reinterpret_cast<int4 *>(ts)[(2 * A) / 4 + tid] = make_int4(o[0], o[1], o[2], o[3]);
         } else {
             reinterpret_cast<int4 *>(part)[A / 4 + tid] = make_int4(p[0], p[1], p[2], p[3]);
@@ -102,10 +103,11 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             reinterpret_cast<longlong2 *>(ts)[A / 2 + 2 * tid + 1] = make_longlong2(t[2], t[3]);
         }
         const bool u16 = lens16 && !(wide & 2);
-        if (u16) {   // group tid: the lane's four key lengths, then its four value lengths (-1 -> KTA_COMPACT_LEN_NONE)
+        if (u16) {   // group tid: the lane's four key lengths, then its four value lengths
+            using kta::tile_pack_len;
             reinterpret_cast<uint4 *>(klen)[A / 4 + tid] =
-                make_uint4((uint32_t)(uint16_t)kl[0] | ((uint32_t)(uint16_t)kl[1] << 16), (uint32_t)(uint16_t)kl[2] | ((uint32_t)(uint16_t)kl[3] << 16),
-                           (uint32_t)(uint16_t)vl[0] | ((uint32_t)(uint16_t)vl[1] << 16), (uint32_t)(uint16_t)vl[2] | ((uint32_t)(uint16_t)vl[3] << 16));
+                make_uint4(kta::tile_u16x2_word(tile_pack_len(kl[0]), tile_pack_len(kl[1])), kta::tile_u16x2_word(tile_pack_len(kl[2]), tile_pack_len(kl[3])),
+                           kta::tile_u16x2_word(tile_pack_len(vl[0]), tile_pack_len(vl[1])), kta::tile_u16x2_word(tile_pack_len(vl[2]), tile_pack_len(vl[3])));
         } else {     // (whole tiles: the allocation covers them, and the records past n are nobody's)
             reinterpret_cast<int4 *>(klen)[A / 4 + tid] = make_int4(kl[0], kl[1], kl[2], kl[3]);
             reinterpret_cast<int4 *>(vlen)[A / 4 + tid] = make_int4(vl[0], vl[1], vl[2], vl[3]);

@@ -52,13 +52,17 @@ def find(sub, counter, largest_grid=False):
 
 
 KIB = 1024.0
-out = {"round": 6, "source": path,
+out = {"round": 14, "source": path,
        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --steps 5 --warmup 1 "
                  "--preroll 5 --no-cpu-baseline` (tools/profile_round.sh; --no-alive-extras: every kernel at one launch size), turned into this file by tools/make_traffic.py; counters "
                  "are KiB per launch (average over the launches of the kernel unless stated).  FETCH_SIZE is doubled for wide "
                  "coalesced streaming reads per the gfx950 correction (MI355X_MICROARCH.md, HBM section); WRITE_SIZE as reported.  "
                  "bench.py replays these numbers (roofline.traffic, traffic_source), it does not measure them."}
 
+# a kernel's entry goes stale with any file its device code comes from: its own and the shared headers (kta_kernels.h
+# includes kta_tile.h; the partition kernels take the keyed stream, the tile layout and the hash from the three headers)
+CSRC = "kafka_topic_analyzer_amd/csrc/"
+SCAN_SRC = "+".join(CSRC + f for f in ("kta_kernels.hip", "kta_tile.h"))
 n_scan = 1 << 30
 # the flagship's batch is tile-compact and keyless: the TILED instantiation, 10 B per record read where every
 # tile is compact with u16 lengths (config 4); the algorithmic bytes stay the 20 of the four fields
@@ -71,7 +75,7 @@ scan_entry = {"kernel": SCAN.replace(" ", ""), "records_per_launch": n_scan,
               "ratio_to_algorithmic": (rd + wr) / (20 * n_scan), "bytes_per_record": (rd + wr) / n_scan,
               "note": "the batch is tile-compact and keyless (every tile of config 4 compact with u16 lengths: 10 B per record "
                       "read); the algorithmic bytes stay the 20 of the four fields",
-              **src("kafka_topic_analyzer_amd/csrc/kta_kernels.hip")}
+              **src(SCAN_SRC)}
 print("scan: read %.3f GB = %.2f B per record vs 20 B x 2^30 = %.3f GB" % (rd / 1e9, rd / n_scan, 20 * n_scan / 1e9), file=sys.stderr)
 if len(sys.argv) > 2 and sys.argv[2] == "--scan-only":
     # passes over the default bench line alone (the scan is its only large kernel): the other entries of the committed
@@ -85,7 +89,7 @@ if len(sys.argv) > 2 and sys.argv[2] == "--scan-only":
 out["kta_metrics_scan"] = scan_entry
 
 n_alive = 15 << 24                            # bench.py --alive-records
-ALIVE_SRC = src("kafka_topic_analyzer_amd/csrc/kta_alive.hip")
+ALIVE_SRC = src("+".join(CSRC + f for f in ("kta_alive.hip", "kta_key_stream.h", "kta_tile.h", "kta_fnv.h")))
 
 
 def entry(key, kernel, match, algo, fetch_factor, note, source=ALIVE_SRC, n=n_alive):
