@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -212,6 +212,33 @@ typedef struct kta_hot_key {
     uint64_t upper;     /* records of the hash, at most */
     uint64_t lower;     /* records of the hash, at least */
 } kta_hot_key;
+
+/* Timestamp order (NOT in the reference, never printed by the reference report): how out of order a topic's timestamps
+ * are, per partition — exact, every word an integer.  Opt-in at kta_create.  A context created with KTA_FLAG_TS_ORDER
+ * keeps a running maximum hi[p] per partition, initially "none".  Records are taken in consumption order:
+ *   - batches in the order they were submitted to the context;
+ *   - records by their index inside a batch.
+ * A seq column and base_seq are not looked at.  A record that the metrics handler counts (which & 1, partition in
+ * [0, P)) and whose ts_ms >= 0 is TIMESTAMPED.  Any negative timestamp counts as "not available", as the timeline
+ * treats it.  A timestamped record of partition p is handled like this:
+ *   timed += 1
+ *   if hi[p] is set and hi[p] > ts:            late: older than something its partition delivered before it
+ *       d = hi[p] - ts                         1 <= d < 2^63
+ *       late[p] += 1;  late_ms_sum[p] += d     the sum wraps modulo 2^64
+ *       max_late_ms[p] = max(max_late_ms[p], d)
+ *       hist[63 - clz64(d)] += 1               floor(log2 d), 0..62
+ *   else:
+ *       hi[p] = ts                             an equal timestamp is in order
+ * Records with a negative timestamp, records with a partition outside [0, P) and records handed only to the alive-key
+ * handler (which == 2) touch nothing.
+ * The result vector is u64[3 P + 64]: [P][2] = late, late_ms_sum; then hist[63]; then timed — all of these SUM words —;
+ * then max_late_ms[P], MAX words that are never negative.  That is a SUM prefix of 2 P + 64 words and a MAX suffix of P
+ * words.  hi[p] is device state of the context and not part of the vector; kta_reset clears the vector and hi.
+ * Two such vectors merge exactly (SUM / MAX) when every partition's records went through ONE context in order: how
+ * kta.gpus=N and bench.py --gpus N shard (p on rank p % N).  kta_create refuses the flag above
+ * kta_ts_order_max_partitions() partitions. */
+#define KTA_FLAG_TS_ORDER 32u
+#define KTA_TS_ORDER_HIST 63   /* hist[k]: late by 2^k <= d < 2^(k+1) ms */
 
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
@@ -421,11 +448,14 @@ int kta_finish_device(kta_ctx *ctx);
  *                       all-reduce MAX (u64) over all of its P * 4096 words.
  *                       With KTA_FLAG_HOT_KEYS the same grouped launch also reduces the hot-key snapshot:
  *                       all-reduce SUM (u64) over all of its 47 104 words (exemplars stay on their rank).
+ *                       With KTA_FLAG_TS_ORDER the same grouped launch also reduces the timestamp-order snapshot:
+ *                       all-reduce SUM (u64) over its first 2 P + 64 words and all-reduce MAX (i64) over its last P.
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
  *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch, kta_exchange_hot_keys:
  *                       the same for the analytics, the timeline, the key sketch, the hot keys)
- * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS, KTA_FLAG_KEY_SKETCH and
- * KTA_FLAG_HOT_KEYS bits, and
+ * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS, KTA_FLAG_KEY_SKETCH,
+ * KTA_FLAG_HOT_KEYS and KTA_FLAG_TS_ORDER bits (and, for the timestamp order to be the topic's, every partition's records
+ * must have gone through ONE rank in order: partition p on rank p % N), and
  * be given the same timeline configuration (or none on every rank): the collectives of a rank with analytics, a key
  * sketch or a timeline do not match those of a rank without, and nothing checks that the configurations agree.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
@@ -557,6 +587,31 @@ int kta_hot_keys_info(kta_ctx *ctx, uint64_t out[6]);
  * default, the most the 21-bit fields admit (511).  KTA_ERR_INVALID above that. */
 int kta_set_hot_flush_rounds(kta_ctx *ctx, uint32_t rounds);
 
+/* Timestamp order (context created with KTA_FLAG_TS_ORDER; definition above KTA_FLAG_TS_ORDER).  The pass needs no key
+ * columns.  kta_reset zeroes the vector and clears hi; kta_finish_device snapshots the vector.  Every call below that
+ * takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_TS_ORDER.
+ * The live accumulator, copied to out[n_u64] (n_u64 = 3 P + 64; staged messages are flushed first). */
+int kta_get_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's vector on every rank.  The live accumulator is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_ts_order_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[3 P + 64] (acc <- acc (+) other): SUM over the first 2 P + 64 words, signed MAX over
+ * the last P — what the two collectives of the exchange implement.  Precondition, as for the exchange: every partition's
+ * records went through ONE of the two contexts, in order (and both were created with the same P and flags). */
+int kta_merge_ts_order(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* The largest P a KTA_FLAG_TS_ORDER context may have (a wave of the apply kernel keeps run[P] in LDS). */
+int kta_ts_order_max_partitions(void);
+/* Work counters of the pass since kta_create / kta_reset (profiling; waits for the compute stream): out[0] launch triples
+ * (chunk maxima, prefix, apply), out[1] chunks, out[2] wave instructions (64 records) that held a timestamped record,
+ * out[3] of them on the one-partition path, out[4] colliding groups the general path resolved, out[5] the records per
+ * chunk of the last launch triple. */
+int kta_ts_order_info(kta_ctx *ctx, uint64_t out[6]);
+/* Tests: records per chunk, a multiple of 64 (64 is the smallest); 0 = the default, by the length of the slice.
+ * KTA_ERR_INVALID otherwise. */
+int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -640,6 +695,19 @@ int kta_render_distinct_keys(const uint64_t *sketch_vec, const uint64_t *counter
  * kta_render_report. */
 int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys, char *out,
                         size_t out_cap, size_t *out_len);
+
+/* The opt-in timestamp-order section that kta-analyzer prints after the reference report (and after the analytics,
+ * timeline and distinct-key sections, before the hot keys) with --librdkafka kta.ts_order=1, from a timestamp-order vector
+ * u64[3 P + 64] and the counter vector u64[P * 7 + 8] of the same records (host only): a title line saying that it is not
+ * part of the reference report; a table (P | Records | Late records | Late % | Mean lateness ms | Max lateness ms: Records
+ * = total_messages, Late % of them, %.2f; the mean is late_ms_sum / late, truncating; `-` for the mean and the max of a
+ * partition without a late record); a Topic row; a line `Records without a timestamp: ` total - timed; unless no record is
+ * late (one line saying so), a table (Late by | Records | Cumulative %) from the first to the last non-empty histogram
+ * bucket, rows labelled `< 2^(k+1) ms` written as a number, Cumulative % the share of the timestamped records that are in
+ * order or late by less than the row's bound (%.2f): the figure a grace period is read from; a closing `=` rule.
+ * Output buffer conventions as kta_render_report. */
+int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
+                        size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

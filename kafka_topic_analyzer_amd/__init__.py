@@ -27,7 +27,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "DivideByZeroPanic", "DateTimeRangePanic", "synth_preset", "synth_fill_host", "fnv_reference_kats",
            "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions", "render_timeline",
            "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys",
-           "recover_hot_keys", "merge_hot_keys", "render_hot_keys"]
+           "recover_hot_keys", "merge_hot_keys", "render_hot_keys", "render_ts_order", "merge_ts_order",
+           "ts_order_max_partitions", "split_ts_order"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -75,13 +76,14 @@ class HipMetricHandler:
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
-                 hot_keys: bool = False):
+                 hot_keys: bool = False, ts_order: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
         timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline);
         key_sketch: a HyperLogLog sketch of the key hashes per partition (KTA_FLAG_KEY_SKETCH: estimate_distinct_keys);
-        hot_keys: the topic-wide hot-key sketch (KTA_FLAG_HOT_KEYS: recover_hot_keys, hot_key_exemplars)."""
+        hot_keys: the topic-wide hot-key sketch (KTA_FLAG_HOT_KEYS: recover_hot_keys, hot_key_exemplars);
+        ts_order: the timestamp-order pass (KTA_FLAG_TS_ORDER: late records per partition, ts_order())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -91,6 +93,7 @@ class HipMetricHandler:
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
+                        (N.KTA_FLAG_TS_ORDER if ts_order else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -466,6 +469,34 @@ class HipMetricHandler:
         self._check(self._lib.kta_get_hot_key_exemplars(self._ctx, _np_ptr(out), out.size))
         return out
 
+    def _ts_order(self, fn) -> dict:
+        out = np.zeros(3 * self.n_partitions + 64, dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), out.size))
+        return split_ts_order(out, self.n_partitions)
+
+    def ts_order(self) -> dict:
+        """The live timestamp-order vector as a dict of np.uint64 arrays: late[P], late_ms_sum[P], max_late_ms[P], hist[63],
+        timed (kta_get_ts_order; staged messages are flushed first); "vector" is the whole u64[3 P + 64]."""
+        return self._ts_order(self._lib.kta_get_ts_order)
+
+    def exchange_ts_order(self) -> dict:
+        """As ts_order(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._ts_order(self._lib.kta_exchange_ts_order)
+
+    def ts_order_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the timestamp-order snapshot (for collectives: allreduce_ts_order_vector)."""
+        return self._device_vector(self._lib.kta_ts_order_result_vector)
+
+    def ts_order_info(self) -> dict:
+        """Work counters of the timestamp-order pass since creation / reset() (kta_ts_order_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_ts_order_info(self._ctx, C.byref(out)))
+        return dict(zip(("launches", "chunks", "instructions", "one_partition", "groups", "chunk_records"), (int(x) for x in out)))
+
+    def set_ts_order_chunk(self, records: int) -> None:
+        """Tests: the records per chunk of the timestamp-order pass, a multiple of 64 (0: the default)."""
+        self._check(self._lib.kta_set_ts_order_chunk(self._ctx, int(records)))
+
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
         ps, pv, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
@@ -776,6 +807,49 @@ def render_hot_keys(vec, exemplars=None, max_keys: int = 10) -> str:
         if ex.size != N.KTA_HOT_ROWS * N.KTA_HOT_CELLS:
             raise ValueError("an exemplar table has 2048 slots")
     return _render(N.load().kta_render_hot_keys, _np_ptr(v), _np_ptr(ex) if ex is not None else None, int(max_keys))
+
+
+def _ts_order_vec(vec, P: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    if v.size != 3 * P + 64:
+        raise ValueError(f"a timestamp-order vector of {P} partitions has {3 * P + 64} words, not {v.size}")
+    return v
+
+
+def split_ts_order(vec, n_partitions: int) -> dict:
+    """A timestamp-order vector u64[3 P + 64] as a dict: late[P], late_ms_sum[P], hist[63], timed, max_late_ms[P], and the
+    vector itself under "vector"."""
+    P = n_partitions
+    v = _ts_order_vec(vec, P)
+    return {"late": v[0:2 * P:2].copy(), "late_ms_sum": v[1:2 * P:2].copy(), "hist": v[2 * P:2 * P + N.KTA_TS_ORDER_HIST].copy(),
+            "timed": int(v[2 * P + N.KTA_TS_ORDER_HIST]), "max_late_ms": v[2 * P + 64:].copy(), "vector": v}
+
+
+def merge_ts_order(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_ts_order, in place on `acc` (contiguous uint64 / int64): SUM over the first 2 P + 64 words, MAX over the
+    last P.  Exact when every partition's records went through one of the two contexts, in order."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    rc = N.load().kta_merge_ts_order(_np_ptr(_ts_order_vec(acc, n_partitions)), _np_ptr(_ts_order_vec(other, n_partitions)), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_ts_order")
+    return acc
+
+
+def render_ts_order(vec, counter_vec, n_partitions: int) -> str:
+    """kta_render_ts_order: the section kta-analyzer prints with --librdkafka kta.ts_order=1, from a timestamp-order vector
+    and the counter vector u64[P * 7 + 8] of the same records."""
+    v = _ts_order_vec(vec, n_partitions)
+    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
+    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    return _render(N.load().kta_render_ts_order, _np_ptr(v), _np_ptr(c), n_partitions)
+
+
+def ts_order_max_partitions() -> int:
+    """The largest P a context with the timestamp-order pass may have."""
+    return int(N.load().kta_ts_order_max_partitions())
 
 
 # ---------------------------------------------------------------------- synthetic topic helpers

@@ -17,7 +17,8 @@
 //                                        v2; uncompressed, gzip, Snappy, LZ4, zstd): file k is partition k; decoded ON THE GPU
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
-// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1, kta.hot_keys=K), so
+// kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1, kta.hot_keys=K,
+// kta.ts_order=1), so
 // no flag is added or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
@@ -34,6 +35,9 @@
 // kta.distinct_keys=1 (every source, kta.gpus=N included) keeps a HyperLogLog sketch of the key hashes per partition as well
 // (KTA_FLAG_KEY_SKETCH; no reference counterpart) and prints the estimated distinct keys per partition and of the topic in a
 // section of its own after the report (and the analytics and the timeline).
+// kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
+// (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
+// per partition — older than one their partition delivered before them — and a histogram of their lateness.
 // kta.hot_keys=K (1 <= K <= 64; every source, kta.gpus=N included) keeps the hot-key sketch as well (KTA_FLAG_HOT_KEYS; no
 // reference counterpart) and prints, last of all, the at most K keys that hold 1/512 of the keyed records and more, with
 // bounds on their records and, where the device caught one, the key's bytes (with kta.gpus=N from the lowest rank that
@@ -91,6 +95,14 @@ std::vector<uint64_t> keyed_records(const kta::MessageMetrics &m, uint32_t P)
     std::vector<uint64_t> keyed(P);
     for (uint32_t p = 0; p < P; p++) keyed[p] = m.key_non_null((int32_t)p);
     return keyed;
+}
+
+// total_messages of partitions [0, P): the records of the kta.ts_order section
+std::vector<uint64_t> total_records(const kta::MessageMetrics &m, uint32_t P)
+{
+    std::vector<uint64_t> total(P);
+    for (uint32_t p = 0; p < P; p++) total[p] = m.total((int32_t)p);
+    return total;
 }
 
 // murmur3's finaliser: x = hot_fmix32(hash) places a key hash in the hot-key sketch (kta_hip.h)
@@ -228,6 +240,7 @@ struct ShardedJob {
     kta::TimelineConfig timeline;                      // kta.timeline=<width>: derived once, the same on every rank
     bool distinct_keys = false;                        // kta.distinct_keys=1: every rank's context, exchanged with the counters
     uint32_t hot_keys = 0;                             // kta.hot_keys=K: likewise; the exemplars stay on their ranks
+    bool ts_order = false;                             // kta.ts_order=1: likewise (a partition's records stay on one rank)
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -242,7 +255,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
-                               (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u);
+                               (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline);
@@ -371,6 +384,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             text += kta::render_timeline(h0->timeline()->data(), job.timeline.origin_ms, job.timeline.bucket_ms,
                                          job.timeline.n_buckets);
         if (job.distinct_keys) text += kta::render_distinct_keys(h0->key_sketch()->data(), keyed_records(metrics, job.P));
+        if (job.ts_order) text += kta::render_ts_order(h0->ts_order()->data(), total_records(metrics, job.P));
         if (job.hot_keys) {
             // a slot a lower rank filled stays: every reported hash gets its exemplar from the lowest rank that has it
             std::vector<kta_hot_exemplar> merged = *h0->hot_key_exemplars();
@@ -489,6 +503,20 @@ int main(int argc, char **argv)
         fprintf(stderr, "kta.distinct_keys=1: the topic has %u partitions, the key sketch admits at most %d "
                         "(4096 registers per partition)\n", P, KTA_SKETCH_MAX_PARTITIONS);
         return 2;
+    }
+    bool ts_order = false;
+    if (cfg.count("kta.ts_order")) {
+        const std::string &v = cfg["kta.ts_order"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.ts_order=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        ts_order = v == "1";
+        if (ts_order && P > (uint32_t)kta_ts_order_max_partitions()) {   // before any context, so before any kernel
+            fprintf(stderr, "kta.ts_order=1: the topic has %u partitions, the timestamp-order pass admits at most %d\n", P,
+                    kta_ts_order_max_partitions());
+            return 2;
+        }
     }
     uint32_t hot_keys = 0;
     if (cfg.count("kta.hot_keys")) {
@@ -619,6 +647,7 @@ int main(int argc, char **argv)
         job.timeline = timeline;
         job.distinct_keys = distinct_keys;
         job.hot_keys = hot_keys;
+        job.ts_order = ts_order;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -636,7 +665,7 @@ int main(int argc, char **argv)
     try {
         handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
-                                                (hot_keys ? KTA_FLAG_HOT_KEYS : 0u),
+                                                (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u),
                                             timeline);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -813,6 +842,7 @@ int main(int argc, char **argv)
         if (timeline.n_buckets)
             text += kta::render_timeline(handler->timeline()->data(), timeline.origin_ms, timeline.bucket_ms, timeline.n_buckets);
         if (distinct_keys) text += kta::render_distinct_keys(handler->key_sketch()->data(), keyed_records(metrics, P));
+        if (ts_order) text += kta::render_ts_order(handler->ts_order()->data(), total_records(metrics, P));
         if (hot_keys) text += kta::render_hot_keys(handler->hot_keys()->data(), handler->hot_key_exemplars()->data(), hot_keys);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {

@@ -72,7 +72,8 @@ uint64_t MessageMetrics::smallest_message() const
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
                                    uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline)
     : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
-      sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0)
+      sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0),
+      tso_on_((flags & KTA_FLAG_TS_ORDER) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -169,6 +170,10 @@ void HipMetricHandler::read_analytics()
         check(kta_exchange_hot_keys(ctx_, hvec_.data(), hvec_.size()), "kta_exchange_hot_keys");
         hex_.assign((size_t)KTA_HOT_ROWS * KTA_HOT_CELLS, kta_hot_exemplar{});
         check(kta_get_hot_key_exemplars(ctx_, hex_.data(), hex_.size()), "kta_get_hot_key_exemplars");
+    }
+    if (tso_on_) {
+        ovec_.assign(3 * (size_t)P_ + 64, 0);
+        check(kta_exchange_ts_order(ctx_, ovec_.data(), ovec_.size()), "kta_exchange_ts_order");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

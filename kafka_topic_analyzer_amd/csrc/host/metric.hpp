@@ -138,6 +138,9 @@ public:
     // exchange(), the whole job's) and this context's own exemplar table [2 * 1024]; nullptr without the flag.
     const std::vector<uint64_t> *hot_keys() const { return hot_on_ ? &hvec_ : nullptr; }
     const std::vector<kta_hot_exemplar> *hot_key_exemplars() const { return hot_on_ ? &hex_ : nullptr; }
+    // With KTA_FLAG_TS_ORDER: the timestamp-order vector u64[3 P + 64] of the snapshot finish() / exchange() took (after
+    // exchange(), the whole job's); nullptr without the flag.
+    const std::vector<uint64_t> *ts_order() const { return tso_on_ ? &ovec_ : nullptr; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -162,6 +165,8 @@ private:
     bool hot_on_ = false;
     std::vector<uint64_t> hvec_;
     std::vector<kta_hot_exemplar> hex_;
+    bool tso_on_ = false;
+    std::vector<uint64_t> ovec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -182,6 +187,9 @@ std::string format_width_ms(int64_t w);
 // the opt-in section kta-analyzer prints after the report (and the analytics and the timeline) with kta.distinct_keys=1
 // (kta_render_distinct_keys): sketch u64[P * 4096], keyed[p] = key_non_null of partition p
 std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint64_t> &keyed);
+// the opt-in section kta-analyzer prints with kta.ts_order=1 after those and before the hot keys (kta_render_ts_order):
+// vec u64[3 P + 64], records[p] = total_messages of partition p
+std::string render_ts_order(const uint64_t *vec, const std::vector<uint64_t> &records);
 // the opt-in section kta-analyzer prints last with kta.hot_keys=K (kta_render_hot_keys): vec u64[2 * 1024 * 23],
 // exemplars [2 * 1024] or null; empty for a vector kta_hot_keys_recover refuses
 std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys);

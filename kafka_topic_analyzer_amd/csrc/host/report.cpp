@@ -257,6 +257,54 @@ std::string render_distinct_keys(const uint64_t *sketch, const std::vector<uint6
     return o;
 }
 
+// The opt-in timestamp-order section (kta.ts_order=1): no reference counterpart, printed after the analytics, timeline and
+// distinct-key sections and before the hot keys.  vec: u64[3 P + 64] (kta_hip.h), records[p] = total_messages.
+std::string render_ts_order(const uint64_t *vec, const std::vector<uint64_t> &records)
+{
+    const uint32_t P = (uint32_t)records.size();
+    const uint64_t *hist = vec + 2 * (size_t)P, timed = vec[2 * (size_t)P + KTA_TS_ORDER_HIST], *most = vec + 2 * (size_t)P + 64;
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    auto pct = [](uint64_t count, uint64_t of) {
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", of ? (double)count * 100.0 / (double)of : 0.0);
+        return std::string(buf);
+    };
+    std::string o;
+    o += "Timestamp order: records older than one their partition delivered before them (kta.ts_order=1; not part of the "
+         "reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Records", "Late records", "Late %", "Mean lateness ms", "Max lateness ms"});
+    uint64_t all = 0, late_all = 0, sum_all = 0, most_all = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t late = vec[2 * (size_t)p], sum = vec[2 * (size_t)p + 1];
+        all += records[p], late_all += late, sum_all += sum, most_all = std::max(most_all, most[p]);
+        rows.push_back({std::to_string(p), u(records[p]), u(late), pct(late, records[p]), late ? u(sum / late) : "-", late ? u(most[p]) : "-"});
+    }
+    rows.push_back({"Topic", u(all), u(late_all), pct(late_all, all), late_all ? u(sum_all / late_all) : "-", late_all ? u(most_all) : "-"});
+    o += pretty_table(rows);
+    o += "Records without a timestamp: " + u(all - timed) + "\n";
+    uint32_t first = KTA_TS_ORDER_HIST, last = 0;
+    for (uint32_t k = 0; k < KTA_TS_ORDER_HIST; k++)
+        if (hist[k] != 0) {
+            first = std::min(first, k);
+            last = k;
+        }
+    if (first == KTA_TS_ORDER_HIST) {
+        o += "No record is late.\n";
+    } else {
+        rows.clear();
+        rows.push_back({"Late by", "Records", "Cumulative %"});
+        uint64_t within = timed - late_all;   // in order
+        for (uint32_t k = first; k <= last; k++) {
+            within += hist[k];
+            rows.push_back({"< " + u(2ull << k) + " ms", u(hist[k]), pct(within, timed)});
+        }
+        o += pretty_table(rows);
+    }
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
 static uint32_t fmix32(uint32_t x)
 {
@@ -326,6 +374,22 @@ extern "C" int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *
     if (!vec || !out_len || max_keys < 1 || max_keys > KTA_HOT_MAX_REPORTED) return KTA_ERR_INVALID;
     const std::string text = kta::render_hot_keys(vec, exemplars, max_keys);
     if (text.empty()) return KTA_ERR_INVALID;   // (a vector no record set leaves)
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out,
+                                   size_t out_cap, size_t *out_len)
+{
+    if (!vec || !counter_vec || !out_len || n_partitions == 0 || (int)n_partitions > kta_ts_order_max_partitions()) return KTA_ERR_INVALID;
+    std::vector<uint64_t> records(n_partitions);
+    for (uint32_t p = 0; p < n_partitions; p++) records[p] = counter_vec[(size_t)p * KTA_NCOUNTERS + KTA_C_TOTAL];
+    const std::string text = kta::render_ts_order(vec, records);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

@@ -78,6 +78,14 @@ struct kta_ctx {
     DeviceBuf<uint32_t> d_hot_ctl;
     uint64_t hot_launches = 0, hot_workgroups = 0;
     uint32_t hot_flush_rounds = 0;   // kta_set_hot_flush_rounds (tests); 0: the most the fields admit
+    // timestamp order (KTA_FLAG_TS_ORDER): d_tso u64[3 P + 64] the live vector, d_tso_out its snapshot, d_tso_hi i64[P] the
+    // running maximum per partition (-1: none) that carries over from batch to batch, d_tso_ws the workspace of a launch
+    // triple (allocated once), d_tso_stats the apply kernel's work counters (kta_ts_order_info)
+    bool tso = false;
+    DeviceBuf<uint64_t> d_tso, d_tso_out, d_tso_stats;
+    DeviceBuf<int64_t> d_tso_hi, d_tso_ws;
+    uint64_t tso_launches = 0, tso_chunks = 0, tso_last_chunk = 0;
+    uint64_t tso_chunk = 0;          // kta_set_ts_order_chunk (tests); 0: by the slice's length
     DeviceBuf<uint64_t> d_vec;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     DeviceBuf<uint64_t> d_vec_out;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -312,6 +320,30 @@ int run_hot_keys(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &r
     });
 }
 
+// The timestamp-order pass over a batch whose metric columns were resolved to rb: chunk maxima, prefix, apply per slice,
+// in order.  A slice is as many chunks as the workspace has rows for P partitions; the chunk is the slice over
+// kTsOrderChunks (enough waves to fill the device a few times over), a multiple of 256 records, or the tests' own.
+int run_ts_order(kta_ctx *ctx, const kta_internal_columns &rb, uint64_t n)
+{
+    const kta::TsOrderState st{ctx->d_tso.get(), ctx->d_tso_hi.get(), ctx->d_tso_ws.get(), ctx->d_tso_stats.get()};
+    const uint64_t max_rows = kta::kTsOrderWorkspaceWords / ctx->P;
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t left = n - at;
+        uint64_t chunk = ctx->tso_chunk;
+        if (chunk == 0) {
+            chunk = ((left + kta::kTsOrderChunks - 1) / kta::kTsOrderChunks + 255) / 256 * 256;
+            if (chunk < kta::kTsOrderChunkMin) chunk = kta::kTsOrderChunkMin;
+        }
+        const uint64_t take = left / chunk >= max_rows ? max_rows * chunk : left;
+        KTA_HIP(ctx, kta::launch_ts_order(scan_columns(rb, at), take, chunk, ctx->P, st, ctx->s_compute));
+        ctx->tso_launches++;
+        ctx->tso_chunks += (take + chunk - 1) / chunk;
+        ctx->tso_last_chunk = chunk;
+        at += take;
+    }
+    return KTA_OK;
+}
+
 // The workspace of the partitioned alive pass, large enough for plan pl: the pairs, their counts and the pool grow
 // together (all three released, after the compute stream has drained, before any is allocated again); the pool's control
 // words and the fail lists are allocated once.
@@ -512,6 +544,10 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         int rc = run_key_sketch(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
     }
+    if ((which & 1) && ctx->tso) {      // likewise; it reads partition and ts_ms only
+        int rc = run_ts_order(ctx, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     if ((which & 1) && ctx->hot) {      // a pass of its own, likewise
         int rc = run_hot_keys(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
@@ -534,6 +570,12 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_slots.get(), 0, kHotSlotsN * sizeof(kta_hot_exemplar), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
         ctx->hot_launches = ctx->hot_workgroups = 0;
+    }
+    if (ctx->tso) {                     // (hi: every byte 0xFF is -1, none)
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso.get(), 0, kta::ts_order_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_hi.get(), 0xFF, (size_t)ctx->P * sizeof(int64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
+        ctx->tso_launches = ctx->tso_chunks = ctx->tso_last_chunk = 0;
     }
     ctx->handed_records = false;
     if (ctx->alive) {
@@ -600,6 +642,7 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
     rv[KTA_RV_TIMELINE] = ResultVector{ctx->timeline ? ctx->d_tvec_out.get() : nullptr, tlen, tlen, false};
     rv[KTA_RV_KEY_SKETCH] = ResultVector{ctx->d_sketch_out.get(), ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0, 0, false};
     rv[KTA_RV_HOT_KEYS] = ResultVector{ctx->d_hot_out.get(), ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, false};
+    rv[KTA_RV_TS_ORDER] = ResultVector{ctx->d_tso_out.get(), ctx->tso ? kta::ts_order_len(ctx->P) : 0, ctx->tso ? 2 * (size_t)ctx->P + 64 : 0, true};
 }
 
 static ResultVector result_vector(kta_ctx *ctx, int kind)
@@ -638,6 +681,9 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     if ((cfg->flags & KTA_FLAG_KEY_SKETCH) && cfg->n_partitions > KTA_SKETCH_MAX_PARTITIONS)
         return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_KEY_SKETCH admits at most " + std::to_string(KTA_SKETCH_MAX_PARTITIONS) +
                                                   " partitions (a u64 snapshot of 4096 registers per partition)");
+    if ((cfg->flags & KTA_FLAG_TS_ORDER) && cfg->n_partitions > kta_ts_order_max_partitions())
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_TS_ORDER admits at most " + std::to_string(kta_ts_order_max_partitions()) +
+                                                  " partitions (a wave of the apply kernel keeps its running maxima in LDS)");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -661,6 +707,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->analytics = (cfg->flags & KTA_FLAG_ANALYTICS) != 0;
     ctx->sketch = (cfg->flags & KTA_FLAG_KEY_SKETCH) != 0;
     ctx->hot = (cfg->flags & KTA_FLAG_HOT_KEYS) != 0;
+    ctx->tso = (cfg->flags & KTA_FLAG_TS_ORDER) != 0;
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
@@ -713,6 +760,14 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_hot_slots.alloc(kHotSlotsN));
         KTA_TRY(ctx->d_hot_ctl.alloc(2 * kHotSlotsN + kHotSlotsN / 32));
         KTA_TRY(ctx->d_hot_stats.alloc(4));
+    }
+    if (ctx->tso) {
+        KTA_TRY(ctx->d_tso.alloc(kta::ts_order_len(ctx->P)));
+        KTA_TRY(ctx->d_tso_out.alloc(kta::ts_order_len(ctx->P)));
+        KTA_TRY(hipMemset(ctx->d_tso_out.get(), 0, kta::ts_order_len(ctx->P) * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_tso_hi.alloc(ctx->P));
+        KTA_TRY(ctx->d_tso_ws.alloc(kta::kTsOrderWorkspaceWords));
+        KTA_TRY(ctx->d_tso_stats.alloc(3));
     }
     if (ctx->alive) {
         if (ctx->alive_table) {
@@ -1109,7 +1164,7 @@ int kta_finish_device(kta_ctx *ctx)
     ResultVector rv[KTA_RV_KINDS];
     kta_internal_result_vectors(ctx, rv);
     // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
-    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get()};
+    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get()};
     for (int k = 0; k < KTA_RV_KINDS; k++)
         if (rv[k].out && live[k])
             KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -1514,6 +1569,69 @@ int kta_merge_hot_keys(uint64_t *acc, const uint64_t *other)
 {
     if (!acc || !other) return KTA_ERR_INVALID;
     merge_words(acc, other, KTA_HOT_VECTOR_WORDS, KTA_HOT_VECTOR_WORDS, false);
+    return KTA_OK;
+}
+
+static const char *const kNoTso = "context was created without KTA_FLAG_TS_ORDER";
+
+static int tso_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "timestamp-order vector", kta::ts_order_len(ctx->P), n_u64); }
+
+int kta_ts_order_max_partitions(void) { return (int)kta::kTsOrderMaxPartitions; }
+
+int kta_get_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    int rc = tso_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_tso.get(), out, n_u64);
+}
+
+int kta_exchange_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    int rc = tso_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_words(ctx, ctx->d_tso_out.get(), out, n_u64);
+}
+
+int kta_ts_order_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    return hand_out(result_vector(ctx, KTA_RV_TS_ORDER), device_ptr, n_u64);
+}
+
+int kta_merge_ts_order(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    if (!acc || !other || P == 0 || P > kta::kTsOrderMaxPartitions) return KTA_ERR_INVALID;
+    merge_words(acc, other, kta::ts_order_len(P), 2 * (size_t)P + 64, true);
+    return KTA_OK;
+}
+
+int kta_ts_order_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t st[3];
+    int rc = read_words(ctx, ctx->d_tso_stats.get(), st, 3);
+    out[0] = ctx->tso_launches, out[1] = ctx->tso_chunks, out[2] = st[0], out[3] = st[1], out[4] = st[2], out[5] = ctx->tso_last_chunk;
+    return rc;
+}
+
+int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    if (records % 64 != 0 || records > (1ull << 32))
+        return fail(ctx, KTA_ERR_INVALID, "a chunk is a multiple of 64 records, at most 2^32 (0: the default)");
+    ctx->tso_chunk = records;
     return KTA_OK;
 }
 

@@ -257,4 +257,22 @@ struct HotState {
 hipError_t launch_hot_keys(const SketchColumns &c, uint64_t n, uint32_t P, const HotState &st, uint32_t flush_rounds, int cu_count,
                            uint32_t *workgroups, hipStream_t s);
 
+// Timestamp order (KTA_FLAG_TS_ORDER, kta_ts_order.hip): the live vector u64[3 P + 64] = [P][2] late records and their
+// lateness | hist[63] | timed | the largest lateness [P], the running maximum hi i64[P] (-1: none) that carries over from
+// batch to batch, and the workspace i64[chunks][P] of one launch triple.
+constexpr uint32_t kTsOrderMaxPartitions = 4096;            // the apply kernel's LDS plan: one wave per workgroup up there
+constexpr size_t kTsOrderWorkspaceWords = (size_t)1 << 22;  // 32 MiB: chunks per launch triple = this / P
+constexpr uint64_t kTsOrderChunkMin = 1024;                 // default chunk: the slice over kTsOrderChunks, at least this
+constexpr uint64_t kTsOrderChunks = 8192;
+inline size_t ts_order_len(uint32_t P) { return 3 * (size_t)P + 64; }
+struct TsOrderState {
+    uint64_t *vec;              // u64[3 P + 64]
+    int64_t *hi;                // i64[P]
+    int64_t *ws;                // i64[kTsOrderWorkspaceWords]
+    uint64_t *stats;            // u64[3] += instructions with a timestamped record, of them one partition, colliding groups
+};
+// Records [0, n) of c in chunks of `chunk` records (a multiple of 64; ceil(n / chunk) * P <= kTsOrderWorkspaceWords):
+// chunk maxima, prefix, apply.
+hipError_t launch_ts_order(const ScanColumns &c, uint64_t n, uint64_t chunk, uint32_t P, const TsOrderState &st, hipStream_t s);
+
 } // namespace kta

@@ -89,6 +89,15 @@ def allreduce_hot_keys_vector(hvec, group=None) -> None:
     _allreduce_sum_max(hvec, hvec.numel(), group)
 
 
+def allreduce_ts_order_vector(ovec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the timestamp-order SNAPSHOT (kta_ts_order_result_vector: device tensor, or a
+    CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_TS_ORDER: all-reduce SUM over
+    the first 2 P + 64 words (i64 wrap == u64 wrap) and all-reduce MAX over the last P (never negative).  Exact when every
+    partition's records went through ONE rank in order (partition p on rank p % N)."""
+    assert ovec.numel() == 3 * n_partitions + 64
+    _allreduce_sum_max(ovec, 2 * n_partitions + 64, group)
+
+
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
