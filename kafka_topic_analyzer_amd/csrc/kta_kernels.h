@@ -69,6 +69,8 @@ struct ScanPlan {
     uint32_t rep_log2;     // LDS replication of each partition's slots
     uint32_t lds_bytes;    // dynamic LDS per workgroup
     uint32_t variant;      // 0 = accumulate (three 64-bit LDS atomics per record or quad), 9 = loads only (diagnostic)
+    bool packed;           // tile-compact, accumulating, no additive outputs: kta_metrics_scan_packed (two atomics, two
+                           // levels of partials in LDS: lds_bytes = 16 P R + 40 P)
     bool nontemporal;      // stream the columns with non-temporal loads
     bool analytics;        // additive outputs: size histograms + per-partition extrema
     uint32_t row_len;      // u64 words per workgroup row of the partial workspace

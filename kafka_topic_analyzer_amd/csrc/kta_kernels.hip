@@ -48,6 +48,10 @@ namespace kta {
 // with compact partitions and timestamps — which rides in the Quad's k registers and is widened (0xFFFF -> -1) when the
 // tile is accumulated.
 //
+// The accumulating scan of a tile-compact batch without additive outputs — the flagship's — is a kernel of its own,
+// kta_metrics_scan_packed (K1p below): the same loads and tile deal, two atomics per record into packed words, a second,
+// full-width level of partials in LDS, one row write at the end.
+//
 // Globals: min/max of ts_ms (-1 => 0 first, metric.rs:209) — the division by 1000
 // (metric.rs:210) is monotone, so it is applied once to the extrema on the host — and
 // min/max of key+value size over non-tombstones (metric.rs:249-251), both carried in
@@ -422,6 +426,51 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, u
     for (int j = 0; j < 4; j++) lds_record<VARIANT, ANALYTICS>(r[j], L, rep_log2, rep);
 }
 
+// The workgroup's extrema and bad-partition count into the globals of its partial row: wave shuffle tree, then the
+// four waves through LDS (kta_metrics_scan_packed's; kta_metrics_scan keeps its own copy of these lines, so that its
+// instantiations compile to the instructions they had before there was a second kernel).
+__device__ __forceinline__ void write_scan_globals(const LaneState &st, long long (&s_red)[kWG / 64][6], uint64_t *row, uint32_t P,
+                                                   uint32_t tid)
+{
+    long long tmin = st.tmin, tmax = st.tmax;
+    long long smin = (long long)st.smin, smax = (long long)st.smax, bad = (long long)st.bad;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long a = __shfl_xor(tmin, off), b = __shfl_xor(tmax, off);
+        const long long cmin = __shfl_xor(smin, off), cmax = __shfl_xor(smax, off);
+        const long long d = __shfl_xor(bad, off);
+        tmin = a < tmin ? a : tmin;
+        tmax = b > tmax ? b : tmax;
+        smin = cmin < smin ? cmin : smin;
+        smax = cmax > smax ? cmax : smax;
+        bad += d;
+    }
+    const uint32_t wave = tid >> 6;
+    if ((tid & 63u) == 0u) {
+        s_red[wave][0] = tmin; s_red[wave][1] = tmax; s_red[wave][2] = smin;
+        s_red[wave][3] = smax; s_red[wave][4] = bad;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (uint32_t w = 1; w < kWG / 64; w++) {
+            tmin = s_red[w][0] < tmin ? s_red[w][0] : tmin;
+            tmax = s_red[w][1] > tmax ? s_red[w][1] : tmax;
+            smin = s_red[w][2] < smin ? s_red[w][2] : smin;
+            smax = s_red[w][3] > smax ? s_red[w][3] : smax;
+            bad += s_red[w][4];
+        }
+        uint64_t *g = row + (uint64_t)P * kScanCols;
+        g[SG_TMIN] = (uint64_t)tmin;
+        g[SG_TMAX] = (uint64_t)tmax;
+        g[SG_SMIN] = (smin == 0xFFFFFFFFll) ? (uint64_t)LLONG_MAX : (uint64_t)smin;
+        g[SG_SMAX] = (uint64_t)smax;
+        g[SG_BAD] = (uint64_t)bad;
+        g[SG_NREC] = 0;
+        g[6] = 0;
+        g[7] = 0;
+    }
+}
+
 // ANALYTICS (opt-in, no reference counterpart — the additive outputs named by the project brief):
 // log2 histograms of key and value sizes and per-partition timestamp / message-size extrema, kept
 // in additional LDS arrays (extrema as signed-max arrays of [~ts, ts, ~size, size], histograms as
@@ -659,6 +708,247 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
         g[6] = 0;
         g[7] = 0;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// K1p  metrics scan of a tile-compact batch, packed accumulation (no analytics, no timeline)
+// ---------------------------------------------------------------------------------------
+// The same loads, tile deal, prefetch ring and partial row as kta_metrics_scan<0, NT, false, true>; what differs is
+// where a record's five sums go.  Two levels of partials in LDS:
+//   front  W1, W2 [P << rep_log2], replicated by lane, updated with TWO 64-bit atomics per record (or quad):
+//              W1 += 1 | tomb << 16 | (u64)key_size << 32        W2 += key_null | (u64)value_size << 32
+//          (a u16-lens tile: its sizes are below 2^16; the dwords are built independently, no 64-bit shift).
+//          A tile whose lengths are i32 adds its counts to the low dwords alone and its two sizes, with two more
+//          atomics, straight to the back level: exact for every i32 length, and such tiles are rare.
+//   back   B [kScanCols][P], full-width u64, unreplicated.  Every kFrontFlushTiles tiles of the workgroup, between
+//          two barriers, thread p sums and zeroes partition p's replicas and adds the fields to its own five words
+//          with plain adds (accumulation and flush never overlap, so the i32 tiles' atomics are safe too).
+// The row of the partial workspace is written once, from the back level, at the end of the kernel.
+// Between two front flushes a slot takes at most the workgroup's kFrontRecords records, so no field carries into
+// its neighbour:
+constexpr uint32_t kFrontFlushTiles = 32;
+constexpr uint64_t kFrontRecords = (uint64_t)kFrontFlushTiles * KTA_TILE_RECORDS;   // 2^15
+static_assert(kFrontRecords <= 0xFFFFu, "count, tombstones and null keys of a front interval fit 16 bits");
+static_assert(kFrontRecords + (kFrontRecords << 16) <= 0xFFFFFFFFull, "count | tombstones << 16 stays in W1's low dword");
+static_assert(kFrontRecords * (KTA_COMPACT_LEN_NONE - 1u) < (1ull << 31), "a front interval's u16 sizes sum below 2^31");
+
+struct PackedLds {
+    unsigned long long *W1, *W2;       // front level
+    unsigned long long *B;             // back level: column c of partition p at B[c * P + p]
+};
+
+__device__ __forceinline__ unsigned long long pack_dwords(uint32_t lo, uint32_t hi)
+{
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// The lane's 4 consecutive records of a tile (accumulate_quad's job).  The tile's two forms (q.compact) are uniform per
+// workgroup.  Extrema without branches: a record that does not count contributes the neutral value.
+// Here: the lengths' half — sizes, size extrema and the LDS adds — of records whose partitions pt and ok are known.
+template <bool LENS16>
+__device__ __forceinline__ void packed_quad_lens(const Quad &q, const uint32_t (&pt)[4], const bool (&ok)[4], uint32_t P,
+                                                 uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
+{
+    uint32_t tomb[4], knull[4], ks[4], vs[4];
+    if (LENS16) {
+        uint32_t ku[4], vu[4];
+        tile_u16x4((uint32_t)q.k.x, (uint32_t)q.k.y, ku);
+        tile_u16x4((uint32_t)q.k.z, (uint32_t)q.k.w, vu);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            knull[j] = ku[j] == KTA_COMPACT_LEN_NONE;
+            tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
+            ks[j] = knull[j] ? 0u : ku[j];
+            vs[j] = tomb[j] ? 0u : vu[j];
+        }
+    } else {
+        const int32_t kl[4] = {q.k.x, q.k.y, q.k.z, q.k.w}, vl[4] = {q.v.x, q.v.y, q.v.z, q.v.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            knull[j] = (uint32_t)kl[j] >> 31;      // as make_rec
+            tomb[j] = (uint32_t)vl[j] >> 31;
+            ks[j] = knull[j] ? 0u : (uint32_t)kl[j];
+            vs[j] = tomb[j] ? 0u : (uint32_t)vl[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {                  // metric.rs:249-251
+        const bool sized = ok[j] && !tomb[j];
+        const uint32_t sz = ks[j] + vs[j];         // < 2^32: both < 2^31
+        st.smin = min(st.smin, sized ? sz : 0xFFFFFFFFu);
+        st.smax = max(st.smax, sized ? sz : 0u);
+    }
+    const bool uniform = ok[0] && ok[1] && ok[2] && ok[3] && pt[0] == pt[1] && pt[0] == pt[2] && pt[0] == pt[3];
+    if (uniform) {
+        const uint32_t slot = (pt[0] << rep_log2) | rep;
+        const uint32_t tombs = tomb[0] + tomb[1] + tomb[2] + tomb[3];
+        const uint32_t knulls = knull[0] + knull[1] + knull[2] + knull[3];
+        if (LENS16) {
+            atomicAdd(&L.W1[slot], pack_dwords(4u | (tombs << 16), ks[0] + ks[1] + ks[2] + ks[3]));
+            atomicAdd(&L.W2[slot], pack_dwords(knulls, vs[0] + vs[1] + vs[2] + vs[3]));
+        } else {
+            atomicAdd(&L.W1[slot], (unsigned long long)(4u | (tombs << 16)));
+            atomicAdd(&L.W2[slot], (unsigned long long)knulls);
+            atomicAdd(&L.B[3u * P + pt[0]], (unsigned long long)ks[0] + ks[1] + ks[2] + ks[3]);
+            atomicAdd(&L.B[4u * P + pt[0]], (unsigned long long)vs[0] + vs[1] + vs[2] + vs[3]);
+        }
+        return;
+    }
+    // interleaved partitions: per-record atomics, spread over the replicas
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (!ok[j]) continue;
+        const uint32_t slot = (pt[j] << rep_log2) | rep;
+        if (LENS16) {
+            atomicAdd(&L.W1[slot], pack_dwords(1u | (tomb[j] << 16), ks[j]));
+            atomicAdd(&L.W2[slot], pack_dwords(knull[j], vs[j]));
+        } else {
+            atomicAdd(&L.W1[slot], (unsigned long long)(1u | (tomb[j] << 16)));
+            atomicAdd(&L.W2[slot], (unsigned long long)knull[j]);
+            atomicAdd(&L.B[3u * P + pt[j]], (unsigned long long)ks[j]);
+            atomicAdd(&L.B[4u * P + pt[j]], (unsigned long long)vs[j]);
+        }
+    }
+}
+
+// FORM: the tile's two forms when the caller knows them (kQuadCompact | kQuadLens16), else -1: read from the quad.
+template <int FORM>
+__device__ __forceinline__ void packed_quad(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2, uint32_t rep,
+                                            const PackedLds &L, LaneState &st)
+{
+    const uint32_t form = FORM >= 0 ? (uint32_t)FORM : q.compact;
+    uint32_t pt[4];
+    bool ok[4];
+    if (form & kQuadCompact) {
+        // The lane's least and largest offset first, one 64-bit ts_base + offset each per tile.  Offsets lie in [0, 2^31)
+        // and KTA_COMPACT_TS_NONE is INT32_MIN: above every offset as u32, below every one as i32, so it drops out of
+        // the unsigned min and the signed max by itself, and so does a record that does not count once it is given that
+        // value.  A counted record without a timestamp is t = 0 (metric.rs:209).
+        static_assert(KTA_COMPACT_TS_NONE == INT32_MIN, "the sentinel is neutral for min as u32 and for max as i32");
+        const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);   // the u16 marker of -1 is no partition, whatever P
+        int32_t o[4];
+        tile_u16x4((uint32_t)q.p.x, (uint32_t)q.p.y, pt);
+        tile_i32x4(q.t0.x, q.t0.y, o);
+        uint32_t lo = (uint32_t)KTA_COMPACT_TS_NONE;
+        int32_t hi = KTA_COMPACT_TS_NONE;
+        bool none = false;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            ok[j] = ((valid >> j) & 1u) && pt[j] < pc;
+            const int32_t oj = ok[j] ? o[j] : KTA_COMPACT_TS_NONE;
+            lo = min(lo, (uint32_t)oj);
+            hi = max(hi, oj);
+            none = none || (ok[j] && o[j] == KTA_COMPACT_TS_NONE);
+        }
+        const bool timed = hi >= 0;
+        const long long tlo = (long long)((uint64_t)q.base + lo), thi = (long long)((uint64_t)q.base + (uint32_t)hi);
+        st.tmin = (timed && tlo < st.tmin) ? tlo : st.tmin;
+        st.tmax = (timed && thi > st.tmax) ? thi : st.tmax;
+        st.tmin = (none && 0ll < st.tmin) ? 0ll : st.tmin;
+        st.tmax = (none && 0ll > st.tmax) ? 0ll : st.tmax;
+    } else {
+        const long long ts[4] = {q.t0.x, q.t0.y, q.t1.x, q.t1.y};
+        pt[0] = (uint32_t)q.p.x, pt[1] = (uint32_t)q.p.y, pt[2] = (uint32_t)q.p.z, pt[3] = (uint32_t)q.p.w;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            ok[j] = ((valid >> j) & 1u) && pt[j] < P;   // unsigned compare also rejects negative ids
+            const long long t = (ts[j] == -1ll) ? 0ll : ts[j];
+            st.tmin = (ok[j] && t < st.tmin) ? t : st.tmin;
+            st.tmax = (ok[j] && t > st.tmax) ? t : st.tmax;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) st.bad += (((valid >> j) & 1u) && !ok[j]) ? 1u : 0u;
+    if (form & kQuadLens16) packed_quad_lens<true>(q, pt, ok, P, rep_log2, rep, L, st);
+    else packed_quad_lens<false>(q, pt, ok, P, rep_log2, rep, L, st);
+}
+
+// A keyless allocation's tiles are compact with u16 lengths unless a value does not fit: straight code for that form,
+// one copy with the branches for the other three.
+__device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2, uint32_t rep,
+                                                  const PackedLds &L, LaneState &st)
+{
+    constexpr uint32_t both = kQuadCompact | kQuadLens16;
+    if ((q.compact & both) == both) packed_quad<(int)both>(q, valid, P, rep_log2, rep, L, st);
+    else packed_quad<-1>(q, valid, P, rep_log2, rep, L, st);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2,
+                                                               uint64_t *__restrict__ partials, uint32_t row_len)
+{
+    extern __shared__ unsigned long long lds[];
+    __shared__ long long s_red[kWG / 64][6];
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t slots = P << rep_log2;
+    const PackedLds L{lds, lds + slots, lds + 2 * slots};
+    for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
+    __syncthreads();
+
+    const uint32_t rep = tid & ((1u << rep_log2) - 1u);
+    LaneState st;
+    st.tmin = LLONG_MAX;
+    st.tmax = LLONG_MIN;
+    st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
+    st.smax = 0u;
+    st.bad = 0u;
+
+    auto front_flush = [&]() {
+        __syncthreads();
+        for (uint32_t p = tid; p < P; p += kWG) {
+            unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
+            for (uint32_t r = 0; r < (1u << rep_log2); r++) {
+                const uint32_t s = (p << rep_log2) | r;
+                w1 += L.W1[s];
+                w2 += L.W2[s];
+                L.W1[s] = 0ull;
+                L.W2[s] = 0ull;
+            }
+            L.B[p] += w1 & 0xFFFFull;
+            L.B[P + p] += (w1 >> 16) & 0xFFFFull;
+            L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
+            L.B[3u * P + p] += w1 >> 32;
+            L.B[4u * P + p] += w2 >> 32;
+        }
+        __syncthreads();
+    };
+
+    // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
+    const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
+    const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+    // the prefetch ring of kta_metrics_scan
+    uint32_t since_flush = 0;
+    uint64_t tile = blockIdx.x;
+    Quad cur, nxt, nx2;
+    if (tile < ntiles) load_tile_quad<NT>(cur, c, t0 + tile, tid);
+    if (kTilePrefetch == 2 && tile + gridDim.x < ntiles) load_tile_quad<NT>(nxt, c, t0 + tile + gridDim.x, tid);
+    while (tile < ntiles) { // uniform per workgroup
+        const uint64_t ntile = tile + gridDim.x;
+        const uint64_t ahead = tile + (uint64_t)kTilePrefetch * gridDim.x;
+        if (ahead < ntiles) load_tile_quad<NT>(kTilePrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid);
+
+        const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
+        uint32_t valid = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+        accumulate_packed(cur, valid, P, rep_log2, rep, L, st);
+
+        if (++since_flush == kFrontFlushTiles) {
+            front_flush();
+            since_flush = 0;
+        }
+        cur = nxt;
+        if (kTilePrefetch == 2) nxt = nx2;
+        tile = ntile;
+    }
+    front_flush();
+
+    uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
+    for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level)
+#pragma unroll
+        for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] = L.B[j * P + p];
+    write_scan_globals(st, s_red, row, P, tid);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1192,7 +1482,11 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
     pl.nontemporal = (analytics || timeline) ? true : (req_variant & 16) != 0;
     pl.variant = (analytics || timeline) ? 0u : (base == 9 ? 9u : 0u);
     pl.timeline_rows = timeline ? timeline_buckets + 3u : 0u;
-    const uint32_t arrays = 3u + (analytics ? 4u : 0u);
+    // the packed scan (kta_metrics_scan_packed): accumulating, tile-compact, no additive outputs — as long as its 56 B
+    // per partition (unreplicated) fit a workgroup's LDS; the few P beyond that keep kta_metrics_scan's 24 B
+    pl.packed = tiled && !analytics && !timeline && pl.variant == 0u &&
+                P * (16u + kScanCols * 8u) + 256u <= 160u * 1024u;
+    const uint32_t arrays = pl.packed ? 2u : 3u + (analytics ? 4u : 0u);
     const uint32_t hist_bytes = analytics ? 2u * kHistBuckets * kHistReps * 4u : 0u;
     // LDS budget per workgroup: 32 KiB (4 workgroups = 16 waves per CU can be resident); the
     // analytics kernel carries 7 arrays and gets 64 KiB (2 workgroups per CU) to keep the replication.
@@ -1202,7 +1496,8 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
     // off, the workgroups per CU stay.
     const uint32_t budget_kib = analytics ? (tiled ? 48u : 64u) : 32u;
     const uint32_t tl_bytes = pl.timeline_rows * 16u;
-    const uint32_t fixed = hist_bytes + tl_bytes;
+    // (packed: two front arrays, replicated, and the back level's five words per partition: 16 P R + 40 P bytes)
+    const uint32_t fixed = hist_bytes + tl_bytes + (pl.packed ? P * kScanCols * 8u : 0u);
     const uint32_t budget_slots = budget_kib * 1024u > fixed ? (budget_kib * 1024u - fixed) / (8u * arrays) : 0u;
     uint32_t rep_log2 = 0;
     while (rep_log2 < 6 && (P << (rep_log2 + 1)) <= budget_slots) rep_log2++;
@@ -1262,6 +1557,23 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
     }
     if (pl.analytics) {
         KTA_SCAN(0, true, true);
+        return hipGetLastError();
+    }
+    if (pl.packed) {
+        if (!c.hdr) return hipErrorInvalidValue;
+#define KTA_SCAN_PACKED(NT)                                                                                         \
+    do {                                                                                                            \
+        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed<NT>),        \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);     \
+            if (ea != hipSuccess) return ea;                                                                        \
+        }                                                                                                           \
+        hipLaunchKernelGGL((kta_metrics_scan_packed<NT>), grid, block, pl.lds_bytes, s, c, n, P, pl.rep_log2,        \
+                           partials, pl.row_len);                                                                   \
+    } while (0)
+        if (pl.nontemporal) KTA_SCAN_PACKED(true);
+        else KTA_SCAN_PACKED(false);
+#undef KTA_SCAN_PACKED
         return hipGetLastError();
     }
     switch (pl.variant) {

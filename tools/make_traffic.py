@@ -64,9 +64,9 @@ out = {"round": 14, "source": path,
 CSRC = "kafka_topic_analyzer_amd/csrc/"
 SCAN_SRC = "+".join(CSRC + f for f in ("kta_kernels.hip", "kta_tile.h"))
 n_scan = 1 << 30
-# the flagship's batch is tile-compact and keyless: the TILED instantiation, 10 B per record read where every
-# tile is compact with u16 lengths (config 4); the algorithmic bytes stay the 20 of the four fields
-SCAN = "kta_metrics_scan<0, true, false, true>"
+# the flagship's batch is tile-compact and keyless: the packed scan, 10 B per record read where
+# every tile is compact with u16 lengths (config 4); the algorithmic bytes stay the 20 of the four fields
+SCAN = "kta_metrics_scan_packed<true>"
 f, w = find(SCAN, "FETCH_SIZE", largest_grid=True), find(SCAN, "WRITE_SIZE", largest_grid=True)
 rd, wr = 2 * f[1] * KIB, w[1] * KIB
 scan_entry = {"kernel": SCAN.replace(" ", ""), "records_per_launch": n_scan,

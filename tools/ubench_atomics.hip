@@ -1,5 +1,8 @@
 // Developer microbenchmark (not product code): throughput of 64-bit atomicMax on random slots of a
 // table, by memory scope and working-set size.  Informs the alive-key pass design.
+//   ubench_atomics lds : instead, the rate of non-returning LDS adds (ds_add_u64 / ds_add_u32) in the metrics scan's
+//   geometry: 256 partitions x 4 lane replicas, 5 workgroups of 4 waves per CU.
+#include <string.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
@@ -39,8 +42,74 @@ __global__ __launch_bounds__(256) void k_plain(unsigned long long *table, uint64
     }
 }
 
-int main()
+// LDS adds on the scan's slots: slot = part << 2 | lane & 3 with `part` random in [0, 256) (MODE 0), or slot = thread
+// (MODE 1: no two lanes of a wave on one bank beyond what the width itself costs).  Each lane cycles through 16 slots it
+// drew before the timed loop, so the loop body is the adds and a counter.  T = unsigned long long or uint32_t.
+constexpr int kLdsSlots = 1024, kLdsDraws = 16;
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void k_lds_add(uint32_t iters, uint64_t seed, unsigned long long *sink)
 {
+    __shared__ T tab[kLdsSlots];
+    for (uint32_t i = threadIdx.x; i < kLdsSlots; i += 256) tab[i] = 0;
+    uint32_t slot[kLdsDraws];
+#pragma unroll
+    for (int j = 0; j < kLdsDraws; j++) {
+        const uint32_t part = (uint32_t)mix64(seed + ((uint64_t)blockIdx.x * 256 + threadIdx.x) * kLdsDraws + j) & 255u;
+        slot[j] = MODE == 0 ? (part << 2 | (threadIdx.x & 3u)) : ((threadIdx.x + 64u * j) & (kLdsSlots - 1));
+    }
+    __syncthreads();
+    for (uint32_t it = 0; it < iters; it++) {
+#pragma unroll
+        for (int j = 0; j < kLdsDraws; j++)
+            (void)__hip_atomic_fetch_add(&tab[slot[j]], (T)(it | 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    unsigned long long acc = 0;
+    for (uint32_t i = threadIdx.x; i < kLdsSlots; i += 256) acc += tab[i];
+    if (acc == 0x1234567) *sink = acc;
+}
+
+static int lds_main()
+{
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, 0) != hipSuccess) { printf("no device\n"); return 1; }
+    const int cus = prop.multiProcessorCount, per_cu = 5;
+    const double mhz = prop.clockRate / 1e3;
+    unsigned long long *sink;
+    hipMalloc(&sink, 8);
+    hipEvent_t a, b;
+    hipEventCreate(&a); hipEventCreate(&b);
+    const uint32_t iters = 4096;
+    printf("LDS adds, non-returning: %d CUs x %d workgroups x 4 waves, %u x %d instructions per wave, clock %.0f MHz\n", cus,
+           per_cu, iters, kLdsDraws, mhz);
+    const char *names[4] = {"ds_add_u64 scan slots (random part << 2 | lane & 3)", "ds_add_u64 slot = thread",
+                            "ds_add_u32 scan slots (random part << 2 | lane & 3)", "ds_add_u32 slot = thread"};
+    for (int mode = 0; mode < 4; mode++) {
+        float best = 1e9;
+        for (int rep = 0; rep < 4; rep++) {
+            hipEventRecord(a);
+            switch (mode) {
+            case 0: hipLaunchKernelGGL((k_lds_add<unsigned long long, 0>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            case 1: hipLaunchKernelGGL((k_lds_add<unsigned long long, 1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            case 2: hipLaunchKernelGGL((k_lds_add<uint32_t, 0>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            default: hipLaunchKernelGGL((k_lds_add<uint32_t, 1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            }
+            hipEventRecord(b);
+            if (hipEventSynchronize(b) != hipSuccess) { printf("kernel failed\n"); return 1; }
+            float ms; hipEventElapsedTime(&ms, a, b);
+            if (rep > 0 && ms < best) best = ms;   // (the first launch of each kernel loads its code)
+        }
+        const double per_cu_insts = (double)per_cu * 4 * iters * kLdsDraws;
+        const double ns = best * 1e6 / per_cu_insts;
+        printf("%-56s %8.3f ms  %6.2f ns per wave instruction per CU = %5.1f cycles at %.0f MHz\n", names[mode], best, ns,
+               ns * mhz / 1e3, mhz);
+    }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && !strcmp(argv[1], "lds")) return lds_main();
     const uint64_t n = 1ull << 26;
     unsigned long long *table, *sink;
     const uint64_t max_slots = 1ull << 32;
