@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -273,6 +273,15 @@ typedef struct kta_hot_key {
  *                        see plain i32 columns.  When a view into a keyless allocation is handed to a key-reading pass
  *                        together with key columns of the caller's own, the lengths of the tiles it touches are widened
  *                        in place first.
+ *   Tile summaries (kta_tile_sum): every allocation of kta_device_batch_alloc keeps one summary per tile BESIDE the
+ *   headers (not in them: kta_tile_hdr is unchanged).  A summary is trusted only next to a KTA_TILE_COMPACT header;
+ *   whoever writes a COMPACT header writes that tile's summary in the same step, and the summary is VALID only if that
+ *   step wrote all KTA_TILE_RECORDS records of the tile (the partial last tile of a fill gets a zero summary; all zero
+ *   means "no summary").  It holds what the writer knew anyway: the span of the tile's timestamps other than -1 (the
+ *   latest is ts_base + ts_span, modulo 2^64), its largest stored u16 partition, and whether it has timed and untimed
+ *   records.  The packed metrics scan takes a summarised tile's earliest and latest timestamp from it and does not
+ *   load the tile's timestamp offsets (6 B per record instead of 10).  A hand-built tile-compact kta_batch with its
+ *   own tile_hdr has no summaries.  kta_batch_tile_summaries reads them back.
  *   key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
  *   written by kta_synth_fill_device (compact tiles), kta_kafka_decode_device (raw tiles) and kta_batch_from_raw, and
  *   read back by kta_batch_to_raw; a raw-layout kta_batch whose column pointers lie inside a tile-compact allocation of
@@ -294,6 +303,15 @@ typedef struct kta_tile_hdr {
     uint32_t mode;     /* KTA_TILE_RAW / KTA_TILE_COMPACT: partition and ts_ms */
     uint32_t lens;     /* KTA_TILE_LENS_I32 / KTA_TILE_LENS_U16: key_len and val_len */
 } kta_tile_hdr;
+
+#define KTA_TILE_SUM_VALID 1u     /* the summary describes all 1024 records of the tile */
+#define KTA_TILE_SUM_TIMED 2u     /* the tile has a timestamp other than -1 */
+#define KTA_TILE_SUM_UNTIMED 4u   /* the tile has a timestamp of -1 */
+typedef struct kta_tile_sum {   /* of a KTA_TILE_COMPACT tile whose 1024 records one producer call wrote; all zero: none */
+    uint32_t ts_span;           /* hi - lo of the timestamps other than -1 (lo is tile_hdr.ts_base); < 2^31 */
+    uint16_t part_max;          /* the largest stored u16 partition (a record with id -1 makes it KTA_COMPACT_PART_NONE) */
+    uint16_t flags;             /* KTA_TILE_SUM_VALID | _TIMED | _UNTIMED */
+} kta_tile_sum;
 
 typedef struct kta_batch {
     int32_t *partition;
@@ -392,6 +410,16 @@ int kta_device_batch_free(kta_ctx *ctx, kta_batch *cols);
  * of the last tile it touches.  to_raw unpacks. */
 int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *host_cols, uint64_t n, const kta_batch *device_cols);
 int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, const kta_batch *host_cols);
+/* The tile summaries (kta_tile_sum, above) of the tiles of records [0, n) of a device batch: tiles_of(n) = ceil(n / 1024)
+ * entries to `out` (synchronous).  device_cols is an allocation of kta_device_batch_alloc or a view of one that starts on
+ * a tile boundary; KTA_ERR_INVALID for anything else (a batch without summaries).  An entry is meaningful only where
+ * the tile's header is KTA_TILE_COMPACT. */
+int kta_batch_tile_summaries(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, kta_tile_sum *out);
+/* Plain copies.  NOT a way to write the partition, ts_ms, key_len or val_len column of a tile-compact allocation
+ * (kta_device_batch_alloc): its tiles' headers and summaries describe the bytes their producer stored, and the scan trusts
+ * them — a summarised tile's stored partitions are not compared with P again, so partition bytes written behind a
+ * summary's back index the scan's LDS out of bounds.  Write such a batch with kta_batch_from_raw, kta_synth_fill_device or
+ * kta_kafka_decode_device only.  key_off, key_bytes and seq are plain in both layouts. */
 int kta_copy_to_device(kta_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);
 int kta_copy_to_host(kta_ctx *ctx, void *dst_host, const void *src_device, size_t bytes);
 
@@ -717,7 +745,8 @@ int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32
  * (avg -1 when none). */
 int kta_set_timing(kta_ctx *ctx, int enable);
 int kta_kernel_time_stats(kta_ctx *ctx, float avg_ms[3], uint64_t launches[3]);
-/* Launch-geometry knobs (0 = default): scan workgroups, scan kernel flavour (16 = non-temporal loads),
+/* Launch-geometry knobs (0 = default): scan workgroups, scan kernel flavour (16 = non-temporal loads; 32 = do not use
+ * tile summaries: every tile's timestamps are loaded),
  * alive workgroups, alive kernel: 0 plain atomicMax, 1 returning atomicMax + running alive count, 2 the
  * same walked backwards with a pre-read that skips superseded records, 3 (default) / 4 the partitioned
  * pass (hash + partition by the hash's top 10 / 9 bits, then per-bucket merge in LDS) for batches of 2^21

@@ -260,6 +260,14 @@ class HipMetricHandler:
             out["seq"] = a
         return out
 
+    def batch_tile_summaries(self, b: KtaBatch, n: int) -> np.ndarray:
+        """The tile summaries (kta_tile_sum) of the tiles of records [0, n) of a device batch: a structured array with the
+        fields ts_span (u32), part_max (u16) and flags (u16), one entry per tile."""
+        out = np.zeros((n + N.KTA_TILE_RECORDS - 1) // N.KTA_TILE_RECORDS,
+                       dtype=np.dtype([("ts_span", np.uint32), ("part_max", np.uint16), ("flags", np.uint16)]))
+        self._check(self._lib.kta_batch_tile_summaries(self._ctx, C.byref(b), n, _np_ptr(out)))
+        return out
+
     def upload_batch(self, cols: dict, with_keys: bool = False) -> Tuple[KtaBatch, int]:
         """numpy columns -> a new device batch (tests: bypasses the staging ring)."""
         n = len(cols["partition"])

@@ -82,6 +82,12 @@ KTA_LAYOUT_RAW, KTA_LAYOUT_TILE_COMPACT = 0, 1   # kta_batch.layout (include/kta
 KTA_TILE_RECORDS = 1024
 KTA_TILE_RAW, KTA_TILE_COMPACT = 0, 1             # kta_tile_hdr.mode
 KTA_TILE_LENS_I32, KTA_TILE_LENS_U16 = 0, 1        # kta_tile_hdr.lens
+KTA_TILE_SUM_VALID, KTA_TILE_SUM_TIMED, KTA_TILE_SUM_UNTIMED = 1, 2, 4   # kta_tile_sum.flags
+KTA_COMPACT_PART_NONE = 0xFFFF
+
+
+class KtaTileSum(C.Structure):
+    _fields_ = [("ts_span", C.c_uint32), ("part_max", C.c_uint16), ("flags", C.c_uint16)]
 
 
 class KtaBatch(C.Structure):
@@ -149,6 +155,7 @@ SIGNATURES = {
     "kta_device_batch_free": (C.c_int, [_P, C.POINTER(KtaBatch)]),
     "kta_batch_from_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
     "kta_batch_to_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
+    "kta_batch_tile_summaries": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.c_void_p]),
     "kta_copy_to_device": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_copy_to_host": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_set_compute_stream": (C.c_int, [_P, C.c_void_p]),

@@ -181,8 +181,9 @@ int alloc_device_batch(kta_ctx *ctx, uint64_t cap, uint64_t kcap, bool keys, boo
     const uint64_t ntiles = tiles_of(cap) ? tiles_of(cap) : 1;
     const uint64_t rows = ntiles * KTA_TILE_RECORDS;
     const size_t c4 = pad16(rows * 4 + 16), c8 = pad16(rows * 8 + 16);
-    KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * sizeof(kta_tile_hdr)));
-    KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * sizeof(kta_tile_hdr)));   // every tile raw
+    // (the tiles' summaries behind the headers: kta::tile_sums_behind)
+    KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * (sizeof(kta_tile_hdr) + sizeof(kta_tile_sum))));
+    KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * (sizeof(kta_tile_hdr) + sizeof(kta_tile_sum))));   // every tile raw, no summary
     KTA_HIP(ctx, hipMalloc((void **)&b->partition, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->key_len, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->val_len, c4));
@@ -241,7 +242,7 @@ kta_internal_columns columns_at(const kta_internal_columns &rb, uint64_t at)
 kta::ScanColumns scan_columns(const kta_internal_columns &rb, uint64_t at)
 {
     const kta_internal_columns r = columns_at(rb, at);
-    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0};
+    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.sum};
 }
 // (the key-reading passes take the lengths and the keys from the batch's own columns: plain i32 in both layouts)
 kta::SketchColumns sketch_columns(const kta_internal_columns &rb, const kta_batch *c, uint64_t at)
@@ -1059,6 +1060,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     std::vector<int32_t> part(nt * KTA_TILE_RECORDS, 0);
     std::vector<int64_t> ts(nt * KTA_TILE_RECORDS, 0);
     std::vector<kta_tile_hdr> hdr(nt);
+    std::vector<kta_tile_sum> sum(nt);
     std::vector<int32_t> klen, vlen;
     if (r.keyless) {
         klen.assign(nt * KTA_TILE_RECORDS, 0);
@@ -1067,7 +1069,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     for (uint64_t T = 0; T < nt; T++) {
         const uint64_t a = T * KTA_TILE_RECORDS, m = n - a < KTA_TILE_RECORDS ? n - a : KTA_TILE_RECORDS;
         hdr[T] = kta::tile_pack_host(h->partition + a, h->ts_ms + a, h->key_len + a, h->val_len + a, m, r.keyless, part.data() + a, ts.data() + a,
-                                     r.keyless ? klen.data() + a : nullptr, r.keyless ? vlen.data() + a : nullptr);
+                                     r.keyless ? klen.data() + a : nullptr, r.keyless ? vlen.data() + a : nullptr, &sum[T]);
     }
     if (r.keyless) {
         KTA_HIP(ctx, hipMemcpy(r.key_len + r.rec0, klen.data(), klen.size() * 4, hipMemcpyHostToDevice));
@@ -1076,6 +1078,24 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     KTA_HIP(ctx, hipMemcpy(r.partition + r.rec0, part.data(), part.size() * 4, hipMemcpyHostToDevice));
     KTA_HIP(ctx, hipMemcpy(r.ts_ms + r.rec0, ts.data(), ts.size() * 8, hipMemcpyHostToDevice));
     KTA_HIP(ctx, hipMemcpy(r.hdr + r.rec0 / KTA_TILE_RECORDS, hdr.data(), nt * sizeof(kta_tile_hdr), hipMemcpyHostToDevice));
+    if (r.sum) KTA_HIP(ctx, hipMemcpy(r.sum + r.rec0 / KTA_TILE_RECORDS, sum.data(), nt * sizeof(kta_tile_sum), hipMemcpyHostToDevice));
+    return KTA_OK;
+}
+
+int kta_batch_tile_summaries(kta_ctx *ctx, const kta_batch *d, uint64_t n, kta_tile_sum *out)
+{
+    if (!ctx || !d || !out) return KTA_ERR_INVALID;
+    if (!d->partition) return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    kta_internal_columns r{};
+    int rc = kta_internal_resolve(ctx, d, &r);
+    if (rc != KTA_OK) return rc;
+    if (!r.sum) return fail(ctx, KTA_ERR_INVALID, "the batch has no tile summaries (not an allocation of kta_device_batch_alloc)");
+    if (r.rec0 % KTA_TILE_RECORDS) return fail(ctx, KTA_ERR_INVALID, "tile summaries are read from a tile boundary");
+    if (r.rec0 + n > r.rows) return fail(ctx, KTA_ERR_CAPACITY, "more records than the allocation holds");
+    if (n == 0) return KTA_OK;
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpy(out, r.sum + r.rec0 / KTA_TILE_RECORDS, tiles_of(n) * sizeof(kta_tile_sum), hipMemcpyDeviceToHost));
     return KTA_OK;
 }
 
@@ -2012,14 +2032,15 @@ int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
 
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns *r)
 {
-    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false};
+    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false, 0, nullptr};
     uint64_t rec0 = 0;
     if (const kta_batch *e = find_allocation(ctx, c->partition, &kta_batch::partition, &rec0)) {
         if (e->partition + rec0 != c->partition) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
         if ((c->ts_ms && c->ts_ms != e->ts_ms + rec0) || (c->key_len && c->key_len != e->key_len + rec0) ||
             (c->val_len && c->val_len != e->val_len + rec0))
             return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
-        *r = kta_internal_columns{e->partition, e->key_len, e->val_len, e->ts_ms, e->tile_hdr, rec0, e->key_bytes == nullptr};
+        *r = kta_internal_columns{e->partition, e->key_len, e->val_len, e->ts_ms, e->tile_hdr, rec0, e->key_bytes == nullptr, allocation_rows(*e),
+                                  kta::tile_sums_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS)};
         return KTA_OK;
     }
     if (c->layout == KTA_LAYOUT_TILE_COMPACT) {

@@ -50,6 +50,9 @@ struct kta_internal_columns {
     kta_tile_hdr *hdr;
     uint64_t rec0;
     bool keyless;
+    uint64_t rows;       // records the allocation's columns hold (whole tiles); 0 unless an allocation of the context's
+    kta_tile_sum *sum;   // the allocation's tile summaries (kta_tile.h: behind its headers), entry t beside hdr[t]; null for
+                         // everything but an allocation of the context's: the raw layout, a hand-built batch's own tile_hdr
 };
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out);
 

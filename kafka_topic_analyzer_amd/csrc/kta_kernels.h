@@ -30,6 +30,7 @@ struct ScanColumns {
     const int64_t *ts_ms;
     const kta_tile_hdr *hdr;
     uint64_t rec0;
+    const kta_tile_sum *sum;   // the tiles' summaries beside hdr (kta_tile.h), or null: none.  Read by kta_metrics_scan_packed only.
 };
 
 struct AliveColumns {
@@ -69,6 +70,7 @@ struct ScanPlan {
     uint32_t rep_log2;     // LDS replication of each partition's slots
     uint32_t lds_bytes;    // dynamic LDS per workgroup
     uint32_t variant;      // 0 = accumulate (three 64-bit LDS atomics per record or quad), 9 = loads only (diagnostic)
+    bool summaries;        // packed: take a summarised tile's timestamp extrema from its summary (req_variant bit 32 clears it)
     bool packed;           // tile-compact, accumulating, no additive outputs: kta_metrics_scan_packed (two atomics, two
                            // levels of partials in LDS: lds_bytes = 16 P R + 40 P)
     bool nontemporal;      // stream the columns with non-temporal loads

@@ -63,8 +63,19 @@ constexpr uint32_t kFlushTiles = 256;          // 256 tiles x 1024 records = 2^1
 #ifndef KTA_SCAN_PREFETCH
 #define KTA_SCAN_PREFETCH 1
 #endif
+// Diagnostic build (tools/build_variant.sh <tag> -DKTA_PACKED_LOADS_ONLY=1): kta_metrics_scan_packed does its loads and
+// the register work, no LDS accumulation — the HBM bound of its own loads.  Its results are not the scan's.
+#ifndef KTA_PACKED_LOADS_ONLY
+#define KTA_PACKED_LOADS_ONLY 0
+#endif
 constexpr int kTilePrefetch = KTA_SCAN_PREFETCH;   // TILED: tiles a workgroup loads ahead of the one it accumulates (1 or 2)
 static_assert(kTilePrefetch == 1 || kTilePrefetch == 2, "the prefetch ring has two or three slots");
+// kta_metrics_scan_packed has a prefetch distance of its own (a summarised tile has 24 B per lane in flight, not 40).
+#ifndef KTA_PACKED_PREFETCH
+#define KTA_PACKED_PREFETCH 1
+#endif
+constexpr int kPackedPrefetch = KTA_PACKED_PREFETCH;
+static_assert(kPackedPrefetch == 1 || kPackedPrefetch == 2, "the prefetch ring has two or three slots");
 
 struct Quad {
     int4 p, k, v;
@@ -72,8 +83,11 @@ struct Quad {
     long long base;    // TILED: the tile's ts_base
     uint32_t compact;  // TILED: bit 0 = p.xy hold four u16 partitions, t0 four i32 timestamp offsets;
                        //        bit 1 = k holds four u16 key lengths (k.xy) and four u16 value lengths (k.zw)
+                       //        bit 2 (with bit 0; kta_metrics_scan_packed only) = the tile is summarised: every record of
+                       //        it counts, its timestamp offsets were NOT loaded, and t0.x / t0.y hold what the tile gives
+                       //        the earliest / the latest timestamp (uniform; from its kta_tile_sum)
 };
-constexpr uint32_t kQuadCompact = 1u, kQuadLens16 = 2u;
+constexpr uint32_t kQuadCompact = 1u, kQuadLens16 = 2u, kQuadSummed = 4u;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
@@ -117,10 +131,15 @@ __device__ __forceinline__ int4 load16(const void *col, uint64_t i)   // 16-byte
 
 // TILED: the lane's 4 records of allocation tile T.  One header load picks the length loads (lens) and the partition /
 // timestamp loads (mode).
-template <bool NT>
-__device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid)
+// SUM (kta_metrics_scan_packed; n: the batch's records, pc = min(P, KTA_COMPACT_PART_NONE)): the timestamps of a tile are
+// not loaded iff its summary is VALID, its header COMPACT, it lies wholly inside [rec0, rec0 + n) and its largest
+// partition counts — then every record of it counts and the tile's extrema are the summary's (kta_tile.h).  Uniform per
+// workgroup and tile, and decided here because the loads run a tile ahead of the accumulation.
+template <bool NT, bool SUM = false>
+__device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid, uint64_t n = 0, uint32_t pc = 0)
 {
     const kta_tile_hdr h = c.hdr[T];
+    const kta_tile_sum sm = SUM ? c.sum[T] : kta_tile_sum{0, 0, 0};   // (with the header: both uniform loads go out first)
     const uint64_t qi = T * (KTA_TILE_RECORDS / 4) + tid;
     const bool lens16 = h.lens == KTA_TILE_LENS_U16;
     q.k = load16<NT>(c.key_len, qi);     // u16 tile: group tid, both lengths of the lane's four records
@@ -139,9 +158,25 @@ __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, ui
     v2i p;
     if (NT) p = __builtin_nontemporal_load(reinterpret_cast<const v2i *>(c.partition) + ci);
     else p = reinterpret_cast<const v2i *>(c.partition)[ci];
-    const int4 o = load16<NT>(c.ts_ms, ci);
     q.p.x = p.x;
     q.p.y = p.y;
+    if (SUM) {
+        const kta_tile_sum &s = sm;
+        const uint64_t first = T * KTA_TILE_RECORDS;
+        if ((s.flags & KTA_TILE_SUM_VALID) && first >= c.rec0 && first + KTA_TILE_RECORDS <= c.rec0 + n && s.part_max < pc) {
+            // a counted record without a timestamp is t = 0 (metric.rs:209); ts_base + ts_span is modular, as tile_unpack_ts
+            const bool timed = (s.flags & KTA_TILE_SUM_TIMED) != 0, untimed = (s.flags & KTA_TILE_SUM_UNTIMED) != 0;
+            long long lo = timed ? (long long)h.ts_base : LLONG_MAX;
+            long long hi = timed ? (long long)((uint64_t)h.ts_base + s.ts_span) : LLONG_MIN;
+            lo = (untimed && 0ll < lo) ? 0ll : lo;
+            hi = (untimed && 0ll > hi) ? 0ll : hi;
+            q.t0.x = lo;
+            q.t0.y = hi;
+            q.compact = kQuadCompact | kQuadSummed | (lens16 ? kQuadLens16 : 0u);
+            return;
+        }
+    }
+    const int4 o = load16<NT>(c.ts_ms, ci);
     q.t0.x = (long long)(((uint64_t)(uint32_t)o.y << 32) | (uint32_t)o.x);
     q.t0.y = (long long)(((uint64_t)(uint32_t)o.w << 32) | (uint32_t)o.z);
     q.base = h.ts_base;
@@ -724,6 +759,9 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
 //          two barriers, thread p sums and zeroes partition p's replicas and adds the fields to its own five words
 //          with plain adds (accumulation and flush never overlap, so the i32 tiles' atomics are safe too).
 // The row of the partial workspace is written once, from the back level, at the end of the kernel.
+// Summarised tiles (kta_tile_sum, kta_tile.h): where the producer's summary says that every record of a whole compact tile
+// counts, the tile's timestamp offsets are not loaded (6 B per record instead of 10) and its two extrema come from the
+// summary (load_tile_quad<NT, true>, kQuadSummed); any other tile is read as before.
 // Between two front flushes a slot takes at most the workgroup's kFrontRecords records, so no field carries into
 // its neighbour:
 constexpr uint32_t kFrontFlushTiles = 32;
@@ -778,6 +816,10 @@ __device__ __forceinline__ void packed_quad_lens(const Quad &q, const uint32_t (
         st.smin = min(st.smin, sized ? sz : 0xFFFFFFFFu);
         st.smax = max(st.smax, sized ? sz : 0u);
     }
+#if KTA_PACKED_LOADS_ONLY
+    st.bad += pt[0] ^ pt[1] ^ pt[2] ^ pt[3];   // (keeps the partition loads alive)
+    return;
+#endif
     const bool uniform = ok[0] && ok[1] && ok[2] && ok[3] && pt[0] == pt[1] && pt[0] == pt[2] && pt[0] == pt[3];
     if (uniform) {
         const uint32_t slot = (pt[0] << rep_log2) | rep;
@@ -812,14 +854,23 @@ __device__ __forceinline__ void packed_quad_lens(const Quad &q, const uint32_t (
 }
 
 // FORM: the tile's two forms when the caller knows them (kQuadCompact | kQuadLens16), else -1: read from the quad.
-template <int FORM>
+// SUM: the kernel reads summaries (the other instantiation never sees a summarised quad and keeps the code of before).
+template <int FORM, bool SUM>
 __device__ __forceinline__ void packed_quad(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2, uint32_t rep,
                                             const PackedLds &L, LaneState &st)
 {
     const uint32_t form = FORM >= 0 ? (uint32_t)FORM : q.compact;
     uint32_t pt[4];
     bool ok[4];
-    if (form & kQuadCompact) {
+    if (SUM && (form & kQuadSummed)) {
+        // A summarised tile (load_tile_quad): every record counts, and the tile's extrema came with the quad — uniform
+        // values, and min / max are idempotent, so every lane folds them.
+        tile_u16x4((uint32_t)q.p.x, (uint32_t)q.p.y, pt);
+#pragma unroll
+        for (int j = 0; j < 4; j++) ok[j] = true;
+        st.tmin = q.t0.x < st.tmin ? q.t0.x : st.tmin;
+        st.tmax = q.t0.y > st.tmax ? q.t0.y : st.tmax;
+    } else if (form & kQuadCompact) {
         // The lane's least and largest offset first, one 64-bit ts_base + offset each per tile.  Offsets lie in [0, 2^31)
         // and KTA_COMPACT_TS_NONE is INT32_MIN: above every offset as u32, below every one as i32, so it drops out of
         // the unsigned min and the signed max by itself, and so does a record that does not count once it is given that
@@ -857,23 +908,29 @@ __device__ __forceinline__ void packed_quad(const Quad &q, uint32_t valid, uint3
             st.tmax = (ok[j] && t > st.tmax) ? t : st.tmax;
         }
     }
+    if (!(SUM && (form & kQuadSummed))) {
 #pragma unroll
-    for (int j = 0; j < 4; j++) st.bad += (((valid >> j) & 1u) && !ok[j]) ? 1u : 0u;
+        for (int j = 0; j < 4; j++) st.bad += (((valid >> j) & 1u) && !ok[j]) ? 1u : 0u;
+    }
     if (form & kQuadLens16) packed_quad_lens<true>(q, pt, ok, P, rep_log2, rep, L, st);
     else packed_quad_lens<false>(q, pt, ok, P, rep_log2, rep, L, st);
 }
 
 // A keyless allocation's tiles are compact with u16 lengths unless a value does not fit: straight code for that form,
-// one copy with the branches for the other three.
+// summarised and not, and one copy with the branches for the others.
+template <bool SUM>
 __device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid, uint32_t P, uint32_t rep_log2, uint32_t rep,
                                                   const PackedLds &L, LaneState &st)
 {
-    constexpr uint32_t both = kQuadCompact | kQuadLens16;
-    if ((q.compact & both) == both) packed_quad<(int)both>(q, valid, P, rep_log2, rep, L, st);
-    else packed_quad<-1>(q, valid, P, rep_log2, rep, L, st);
+    constexpr uint32_t both = kQuadCompact | kQuadLens16, summed = both | kQuadSummed;
+    if (SUM && q.compact == summed) packed_quad<(int)summed, SUM>(q, valid, P, rep_log2, rep, L, st);
+    else if ((q.compact & both) == both) packed_quad<(int)both, SUM>(q, valid, P, rep_log2, rep, L, st);
+    else packed_quad<-1, SUM>(q, valid, P, rep_log2, rep, L, st);
 }
 
-template <bool NT>
+// SUM: read the tiles' summaries (c.sum non-null).  The other instantiation is the kernel of before, for a batch without
+// summaries and for scan_variant bit 32.
+template <bool NT, bool SUM>
 __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2,
                                                                uint64_t *__restrict__ partials, uint32_t row_len)
 {
@@ -920,26 +977,27 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
     // the prefetch ring of kta_metrics_scan
     uint32_t since_flush = 0;
     uint64_t tile = blockIdx.x;
+    const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
     Quad cur, nxt, nx2;
-    if (tile < ntiles) load_tile_quad<NT>(cur, c, t0 + tile, tid);
-    if (kTilePrefetch == 2 && tile + gridDim.x < ntiles) load_tile_quad<NT>(nxt, c, t0 + tile + gridDim.x, tid);
+    if (tile < ntiles) load_tile_quad<NT, SUM>(cur, c, t0 + tile, tid, n, pc);
+    if (kPackedPrefetch == 2 && tile + gridDim.x < ntiles) load_tile_quad<NT, SUM>(nxt, c, t0 + tile + gridDim.x, tid, n, pc);
     while (tile < ntiles) { // uniform per workgroup
         const uint64_t ntile = tile + gridDim.x;
-        const uint64_t ahead = tile + (uint64_t)kTilePrefetch * gridDim.x;
-        if (ahead < ntiles) load_tile_quad<NT>(kTilePrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid);
+        const uint64_t ahead = tile + (uint64_t)kPackedPrefetch * gridDim.x;
+        if (ahead < ntiles) load_tile_quad<NT, SUM>(kPackedPrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid, n, pc);
 
         const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
         uint32_t valid = 0u;
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-        accumulate_packed(cur, valid, P, rep_log2, rep, L, st);
+        accumulate_packed<SUM>(cur, valid, P, rep_log2, rep, L, st);
 
         if (++since_flush == kFrontFlushTiles) {
             front_flush();
             since_flush = 0;
         }
         cur = nxt;
-        if (kTilePrefetch == 2) nxt = nx2;
+        if (kPackedPrefetch == 2) nxt = nx2;
         tile = ntile;
     }
     front_flush();
@@ -1475,8 +1533,9 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
                    uint32_t timeline_buckets)
 {
     ScanPlan pl;
-    // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads
+    // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads; +32 = no tile summaries
     const int base = req_variant & 15;
+    pl.summaries = (req_variant & 32) == 0;
     const bool timeline = timeline_buckets != 0u;
     pl.analytics = analytics;
     pl.nontemporal = (analytics || timeline) ? true : (req_variant & 16) != 0;
@@ -1561,18 +1620,25 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
     }
     if (pl.packed) {
         if (!c.hdr) return hipErrorInvalidValue;
-#define KTA_SCAN_PACKED(NT)                                                                                         \
+        ScanColumns cs = c;
+        if (!pl.summaries) cs.sum = nullptr;
+#define KTA_SCAN_PACKED(NT, SUM)                                                                                         \
     do {                                                                                                            \
         if (pl.lds_bytes > 48u * 1024u) {                                                                           \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed<NT>),        \
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed<NT, SUM>),        \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);     \
             if (ea != hipSuccess) return ea;                                                                        \
         }                                                                                                           \
-        hipLaunchKernelGGL((kta_metrics_scan_packed<NT>), grid, block, pl.lds_bytes, s, c, n, P, pl.rep_log2,        \
+        hipLaunchKernelGGL((kta_metrics_scan_packed<NT, SUM>), grid, block, pl.lds_bytes, s, cs, n, P, pl.rep_log2,       \
                            partials, pl.row_len);                                                                   \
     } while (0)
-        if (pl.nontemporal) KTA_SCAN_PACKED(true);
-        else KTA_SCAN_PACKED(false);
+        if (cs.sum) {
+            if (pl.nontemporal) KTA_SCAN_PACKED(true, true);
+            else KTA_SCAN_PACKED(false, true);
+        } else {
+            if (pl.nontemporal) KTA_SCAN_PACKED(true, false);
+            else KTA_SCAN_PACKED(false, false);
+        }
 #undef KTA_SCAN_PACKED
         return hipGetLastError();
     }

@@ -42,15 +42,16 @@ __global__ __launch_bounds__(kWG) void synth_fill_cols(kta_synth_spec sp, uint64
 // the raw fill.
 __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint64_t first, uint64_t n, int32_t *part,
                                                         int32_t *klen, int32_t *vlen, int64_t *ts, uint64_t *seq,
-                                                        kta_tile_hdr *hdr, uint64_t t0, uint32_t lens16)
+                                                        kta_tile_hdr *hdr, kta_tile_sum *sum, uint64_t t0, uint32_t lens16)
 {
-    __shared__ long long s_red[kWG / 64][3];
+    __shared__ long long s_red[kWG / 64][4];
     const uint32_t tid = threadIdx.x;
     const uint64_t ntiles = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
     for (uint64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
         int32_t p[4], kl[4], vl[4];
         int64_t t[4];
         long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;   // wide: bit 0 a partition id, bit 1 a length outside the u16 form
+        long long seen = 0;   // the summary's (real records only): bits 0-15 the largest stored u16 partition, bit 16 a timestamp of -1
         for (uint32_t j = 0; j < 4; j++) {
             const uint64_t i = T * KTA_TILE_RECORDS + 4u * tid + j;
             p[j] = -1;
@@ -61,27 +62,33 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             if (seq) seq[i] = first + i;
             wide |= kta::tile_part_fits(p[j]) ? 0 : 1;
             wide |= kta::tile_len_fits(kl[j]) && kta::tile_len_fits(vl[j]) ? 0 : 2;
+            const long long pm = kta::tile_pack_part(p[j]);
+            seen = (seen & 0x10000) | ((seen & 0xFFFF) > pm ? (seen & 0xFFFF) : pm) | (t[j] == -1 ? 0x10000 : 0);
             if (t[j] != -1) {
                 lo = t[j] < lo ? t[j] : lo;
                 hi = t[j] > hi ? t[j] : hi;
             }
         }
         for (int off = 32; off > 0; off >>= 1) {
-            const long long a = __shfl_xor(lo, off), b = __shfl_xor(hi, off), c = __shfl_xor(wide, off);
+            const long long a = __shfl_xor(lo, off), b = __shfl_xor(hi, off), c = __shfl_xor(wide, off), d = __shfl_xor(seen, off);
             lo = a < lo ? a : lo;
             hi = b > hi ? b : hi;
             wide |= c;
+            seen = ((seen | d) & 0x10000) | ((seen & 0xFFFF) > (d & 0xFFFF) ? (seen & 0xFFFF) : (d & 0xFFFF));
         }
         if ((tid & 63u) == 0u) {
             s_red[tid >> 6][0] = lo;
             s_red[tid >> 6][1] = hi;
             s_red[tid >> 6][2] = wide;
+            s_red[tid >> 6][3] = seen;
         }
         __syncthreads();
         for (uint32_t w = 0; w < kWG / 64; w++) {
             lo = s_red[w][0] < lo ? s_red[w][0] : lo;
             hi = s_red[w][1] > hi ? s_red[w][1] : hi;
             wide |= s_red[w][2];
+            const long long d = s_red[w][3];
+            seen = ((seen | d) & 0x10000) | ((seen & 0xFFFF) > (d & 0xFFFF) ? (seen & 0xFFFF) : (d & 0xFFFF));
         }
         __syncthreads();   // (s_red is reused by the next tile)
         int64_t base;
@@ -112,8 +119,12 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             reinterpret_cast<int4 *>(klen)[A / 4 + tid] = make_int4(kl[0], kl[1], kl[2], kl[3]);
             reinterpret_cast<int4 *>(vlen)[A / 4 + tid] = make_int4(vl[0], vl[1], vl[2], vl[3]);
         }
-        if (tid == 0)
+        if (tid == 0) {
             hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, u16 ? KTA_TILE_LENS_U16 : KTA_TILE_LENS_I32};
+            // the summary with the header (kta_tile.h): of a compact tile this call wrote whole, else none
+            const uint64_t m = n - T * KTA_TILE_RECORDS < KTA_TILE_RECORDS ? n - T * KTA_TILE_RECORDS : KTA_TILE_RECORDS;
+            if (sum) sum[t0 + T] = compact ? kta::tile_summary(lo, hi, (uint32_t)(seen & 0xFFFF), (seen & 0x10000) != 0, m) : kta_tile_sum{0, 0, 0};
+        }
     }
 }
 
@@ -293,7 +304,7 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
         // of the caller's own beside it
         const uint32_t lens16 = ac.keyless && !b->key_off && !b->key_bytes ? 1u : 0u;
         hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, ac.partition,
-                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, rec0 / KTA_TILE_RECORDS, lens16);
+                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, ac.sum, rec0 / KTA_TILE_RECORDS, lens16);
     } else {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);

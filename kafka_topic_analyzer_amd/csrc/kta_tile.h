@@ -29,6 +29,32 @@ KTA_TILE_HD inline bool tile_ts_fits(int64_t lo, int64_t hi, int64_t *base)
     return lo > hi || (uint64_t)hi - (uint64_t)lo <= (uint64_t)INT32_MAX;
 }
 
+// ---- a tile's summary (kta_tile_sum, kta_hip.h) -------------------------------------------------------------------
+// The one rule of validity: a summary is trusted only next to a KTA_TILE_COMPACT header; whoever writes a COMPACT header
+// writes that tile's summary in the same step; and the summary is VALID only if that step wrote all KTA_TILE_RECORDS
+// records of the tile — the partial last tile of a fill gets a zero summary ("none").  A header that turns RAW
+// (kta_tiles_to_raw) needs nothing more, and widening the lengths leaves partitions and timestamps, so the summary, as
+// they are.
+// The one address rule: the summaries of an allocation of ntiles tiles lie behind its ntiles headers, in the same device
+// allocation (alloc_device_batch), entry t next to header t.
+KTA_TILE_HD inline kta_tile_sum *tile_sums_behind(kta_tile_hdr *hdr, uint64_t ntiles)
+{
+    return reinterpret_cast<kta_tile_sum *>(hdr + ntiles);
+}
+static_assert(sizeof(kta_tile_sum) == 8 && sizeof(kta_tile_hdr) == 16, "a summary is one 8-byte word behind 16-byte headers");
+// The summary of a compact tile of m records: lo / hi as tile_ts_fits takes them, part_max the largest STORED u16 partition
+// (tile_pack_part) and untimed (a timestamp of -1) over the m records.
+KTA_TILE_HD inline kta_tile_sum tile_summary(int64_t lo, int64_t hi, uint32_t part_max, bool untimed, uint64_t m)
+{
+    kta_tile_sum s{0, 0, 0};
+    if (m != KTA_TILE_RECORDS) return s;
+    const bool timed = lo <= hi;
+    s.ts_span = timed ? (uint32_t)((uint64_t)hi - (uint64_t)lo) : 0u;
+    s.part_max = (uint16_t)part_max;
+    s.flags = (uint16_t)(KTA_TILE_SUM_VALID | (timed ? KTA_TILE_SUM_TIMED : 0u) | (untimed ? KTA_TILE_SUM_UNTIMED : 0u));
+    return s;
+}
+
 // ---- one value ----------------------------------------------------------------------------------------------------
 KTA_TILE_HD inline uint16_t tile_pack_part(int32_t p) { return p == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p; }
 KTA_TILE_HD inline int32_t tile_unpack_part(uint32_t u) { return u == KTA_COMPACT_PART_NONE ? -1 : (int32_t)u; }
@@ -70,14 +96,18 @@ KTA_TILE_HD inline void tile_i32x4(long long w0, long long w1, int32_t (&o)[4])
 // tile's own KTA_TILE_RECORDS elements of each column, what is not written keeps its value — and the tile's header.
 // lens16: the allocation has no key columns, so the lengths may take the u16 form.  klen == null: the lengths are not
 // the caller's business (a keyed allocation takes them with a plain copy), k / v are not read and lens stays 0.
+// sum (may be null): the tile's summary — zero unless the tile is compact and m is the whole tile.
 inline kta_tile_hdr tile_pack_host(const int32_t *p, const int64_t *t, const int32_t *k, const int32_t *v, uint64_t m, bool lens16,
-                                   int32_t *part, int64_t *ts, int32_t *klen, int32_t *vlen)
+                                   int32_t *part, int64_t *ts, int32_t *klen, int32_t *vlen, kta_tile_sum *sum = nullptr)
 {
     kta_tile_hdr h{0, KTA_TILE_RAW, KTA_TILE_LENS_I32};
     int64_t lo = INT64_MAX, hi = INT64_MIN, base = 0;
-    bool fits = true;
+    bool fits = true, untimed = false;
+    uint32_t part_max = 0;
+    if (sum) *sum = kta_tile_sum{0, 0, 0};
     for (uint64_t j = 0; j < m; j++) {
         fits = fits && tile_part_fits(p[j]);
+        untimed = untimed || t[j] == -1;
         if (t[j] == -1) continue;
         lo = t[j] < lo ? t[j] : lo;
         hi = t[j] > hi ? t[j] : hi;
@@ -88,9 +118,11 @@ inline kta_tile_hdr tile_pack_host(const int32_t *p, const int64_t *t, const int
         for (uint64_t j = 0; j < m; j++) {
             p16[tile_compact_at(j, 0)] = tile_pack_part(p[j]);
             o32[tile_compact_at(j, 0)] = tile_pack_ts(t[j], base);
+            part_max = tile_pack_part(p[j]) > part_max ? tile_pack_part(p[j]) : part_max;
         }
         h.ts_base = base;
         h.mode = KTA_TILE_COMPACT;
+        if (sum) *sum = tile_summary(lo, hi, part_max, untimed, m);
     } else {
         memcpy(part, p, m * 4);
         memcpy(ts, t, m * 8);
