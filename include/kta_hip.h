@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -239,6 +239,29 @@ typedef struct kta_hot_key {
  * kta_ts_order_max_partitions() partitions. */
 #define KTA_FLAG_TS_ORDER 32u
 #define KTA_TS_ORDER_HIST 63   /* hist[k]: late by 2^k <= d < 2^(k+1) ms */
+
+/* Partitioner (NOT in the reference, never printed by the reference report): is the topic keyed the way Kafka's default
+ * partitioner keys it, and how would its keyed records and bytes spread over Q partitions — exact, every word an
+ * integer.  Opt-in at kta_create.  The pass looks at every record that the metrics handler counts (which & 1, partition
+ * in [0, P)) and whose key is Some (key_len >= 0): the empty key and tombstones included — the key sketch's records.
+ * For each such record of partition p:
+ *   h = murmur2(key)          Kafka's org.apache.kafka.common.utils.Utils.murmur2: seed 0x9747b28c, m = 0x5bd1e995, r = 24,
+ *                             little-endian 4-byte words, the 1..3 tail bytes as there, final h ^= h>>13; h *= m; h ^= h>>15
+ *   t = h & 0x7fffffff        Utils.toPositive (NOT abs)
+ *   checked[p] += 1
+ *   placed[p]  += (t % P == p)                     the record lies where the Java default partitioner puts its key
+ *   target_records[t % Q] += 1
+ *   target_bytes[t % Q]   += key_len + max(val_len, 0)
+ * Q is the what-if partition count: P unless kta_set_repartition set another; kta_reset keeps it.
+ * Records with a null key, records with a partition outside [0, P) and records handed only to the alive-key handler
+ * (which == 2) touch nothing.
+ * The result vector is u64[2 P + 2 Q]: word 2p is checked[p], word 2p + 1 placed[p]; word 2P + 2q is target_records[q],
+ * word 2P + 2q + 1 target_bytes[q].  Every word is a SUM: the vectors of disjoint record sets add word by word, so the
+ * result is exact and independent of order, batching and sharding.  checked[p] equals the counter vector's
+ * key_non_null[p].  murmur2 of "21" is -973932308, of "foobar" -790332482, of "abc" 479470107, of the empty key 275646681
+ * (Kafka's UtilsTest).  kta_create refuses the flag above kta_partitioner_max_partitions() partitions, and
+ * kta_set_repartition a Q above it. */
+#define KTA_FLAG_PARTITIONER 0x40u   /* 64: bit 6 */
 
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
@@ -478,12 +501,15 @@ int kta_finish_device(kta_ctx *ctx);
  *                       all-reduce SUM (u64) over all of its 47 104 words (exemplars stay on their rank).
  *                       With KTA_FLAG_TS_ORDER the same grouped launch also reduces the timestamp-order snapshot:
  *                       all-reduce SUM (u64) over its first 2 P + 64 words and all-reduce MAX (i64) over its last P.
+ *                       With KTA_FLAG_PARTITIONER the same grouped launch also reduces the partitioner snapshot:
+ *                       all-reduce SUM (u64) over all of its 2 P + 2 Q words.
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
  *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch, kta_exchange_hot_keys:
  *                       the same for the analytics, the timeline, the key sketch, the hot keys)
  * Every rank of a job must be created with the same P AND the same KTA_FLAG_ANALYTICS, KTA_FLAG_KEY_SKETCH,
- * KTA_FLAG_HOT_KEYS and KTA_FLAG_TS_ORDER bits (and, for the timestamp order to be the topic's, every partition's records
- * must have gone through ONE rank in order: partition p on rank p % N), and
+ * KTA_FLAG_HOT_KEYS, KTA_FLAG_TS_ORDER and KTA_FLAG_PARTITIONER bits (and, for the timestamp order to be the topic's, every
+ * partition's records must have gone through ONE rank in order: partition p on rank p % N; with the partitioner pass,
+ * the same Q: kta_set_repartition), and
  * be given the same timeline configuration (or none on every rank): the collectives of a rank with analytics, a key
  * sketch or a timeline do not match those of a rank without, and nothing checks that the configurations agree.
  * RCCL is bound at run time (KTA_RCCL_LIBRARY, /opt/rocm/lib/librccl.so.1). */
@@ -640,6 +666,37 @@ int kta_ts_order_info(kta_ctx *ctx, uint64_t out[6]);
  * KTA_ERR_INVALID otherwise. */
 int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records);
 
+/* Partitioner (context created with KTA_FLAG_PARTITIONER; definition above KTA_FLAG_PARTITIONER).  The handlers then read
+ * key_off / key_bytes and val_len: the staging batches carry key columns as with count_alive_keys, and a device batch
+ * handed to the metrics handler without them is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_PARTITIONER)")
+ * before anything is launched.  kta_reset zeroes the vector and keeps Q; kta_finish_device snapshots the vector.  Every
+ * call below that takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming
+ * KTA_FLAG_PARTITIONER.
+ * The what-if partition count Q, 1 .. kta_partitioner_max_partitions() (KTA_ERR_INVALID otherwise, before anything is
+ * launched or allocated).  Accepted only while the context has been handed no record since kta_create / kta_reset, as
+ * kta_set_timeline; the vector, of 2 P + 2 Q words from then on, and its snapshot are zeroed. */
+int kta_set_repartition(kta_ctx *ctx, uint32_t q);
+/* The live accumulator, copied to out[n_u64] (n_u64 = 2 P + 2 Q; staged messages are flushed first). */
+int kta_get_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's vector on every rank.  The live accumulator is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_partitioner_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[2 P + 2 Q] (acc <- acc + other, every word, modulo 2^64): what the collective of
+ * the exchange implements.  KTA_ERR_INVALID for a P or Q of 0 or above the limit. */
+int kta_merge_partitioner(uint64_t *acc, const uint64_t *other, uint32_t n_partitions, uint32_t q);
+/* The largest P a KTA_FLAG_PARTITIONER context may have, and the largest Q (the pass keeps 8 P + 12 Q bytes in LDS). */
+int kta_partitioner_max_partitions(void);
+/* Work counters of the pass since kta_create / kta_reset (profiling; waits for the compute stream): out[0] keyed records,
+ * out[1] launches, out[2] LDS adds to the checked / placed words and out[3] to the target words, both after the lanes of
+ * an instruction that share a word were combined, out[4] workgroups launched, out[5] dynamic LDS bytes of a workgroup for
+ * this P and Q. */
+int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6]);
+/* Kafka's murmur2 of key[0, len) (host only; the source the device runs: csrc/kta_murmur2.h).  key may be null when
+ * len is 0. */
+uint32_t kta_murmur2(const void *key, size_t len);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -736,6 +793,30 @@ int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, 
  * Output buffer conventions as kta_render_report. */
 int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
                         size_t *out_len);
+
+/* The opt-in partitioner section that kta-analyzer prints last of all (after the hot keys) with --librdkafka
+ * kta.partitioner=murmur2, from a partitioner vector u64[2 P + 2 Q] and the counter vector u64[P * 7 + 8] of the same
+ * records (host only).  Percentages are %.2f, ratios %.2f, `-` where the denominator is 0.
+ *   `Partitioner check: keyed records on the partition Kafka's default partitioner (murmur2) gives their key
+ *    (kta.partitioner=murmur2; not part of the reference report)` — one line;
+ *   a table (P | Keyed records | On murmur2's partition | %) with a row per partition — `-` in the last two columns of a
+ *    partition without keyed records — and a Topic row;
+ *   `Records without a key: N (the default partitioner spreads them without a hash)`, N the sum of key_null;
+ *   the verdict, one of
+ *    `No record has a key: nothing to check.`                                                  (no keyed record)
+ *    `All keyed records lie on murmur2's partition: the topic is keyed as Kafka's default partitioner keys it.`
+ *    `No more keyed records lie on murmur2's partition than chance puts there (X % against 1/P = Y %): the topic was not
+ *     written by Kafka's default partitioner with P partitions.`       (P > 2 and placed * P <= 2 * checked; one line)
+ *    `X % of the keyed records lie on murmur2's partition: the topic is only partly keyed as Kafka's default partitioner
+ *     keys it.`                                                                                            (one line)
+ *   `Repartition what-if: the keyed records over Q = <Q> partitions by murmur2`;
+ *   a table (Target | Records | Records % | Bytes | Bytes %) over the Q targets, the shares of the sums over the targets;
+ *   `Largest / mean at Q = <Q>: records A, bytes B; the topic as it is (P = <P>): records C, bytes D` — A and B over the
+ *    targets, C over key_non_null[p], D over key_size_sum[p] + value_size_sum[p] of the counter vector;
+ *   a closing `=` rule.
+ * Output buffer conventions as kta_render_report. */
+int kta_render_partitioner(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, uint32_t q, char *out,
+                           size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

@@ -28,7 +28,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "decode_analytics", "merge_analytics", "render_analytics", "analytics_max_partitions", "render_timeline",
            "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys",
            "recover_hot_keys", "merge_hot_keys", "render_hot_keys", "render_ts_order", "merge_ts_order",
-           "ts_order_max_partitions", "split_ts_order"]
+           "ts_order_max_partitions", "split_ts_order", "render_partitioner", "merge_partitioner",
+           "partitioner_max_partitions", "split_partitioner", "murmur2"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -76,24 +77,27 @@ class HipMetricHandler:
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
-                 hot_keys: bool = False, ts_order: bool = False):
+                 hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
         timeline: (origin_ms, bucket_ms, n_buckets) — records, tombstones and bytes per time bucket (kta_set_timeline);
         key_sketch: a HyperLogLog sketch of the key hashes per partition (KTA_FLAG_KEY_SKETCH: estimate_distinct_keys);
         hot_keys: the topic-wide hot-key sketch (KTA_FLAG_HOT_KEYS: recover_hot_keys, hot_key_exemplars);
-        ts_order: the timestamp-order pass (KTA_FLAG_TS_ORDER: late records per partition, ts_order())."""
+        ts_order: the timestamp-order pass (KTA_FLAG_TS_ORDER: late records per partition, ts_order());
+        partitioner: the partitioner pass (KTA_FLAG_PARTITIONER: keyed records on murmur2's partition and their spread
+        over `repartition` partitions — n_partitions when None —, partitioner())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
         self.count_alive_keys = bool(count_alive_keys)
         self.key_sketch_on = bool(key_sketch)
         self.hot_keys_on = bool(hot_keys)
+        self.partitioner_on = bool(partitioner)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
-                        (N.KTA_FLAG_TS_ORDER if ts_order else 0) |
+                        (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -102,6 +106,13 @@ class HipMetricHandler:
         if timeline is not None:
             try:
                 self.set_timeline(*timeline)
+            except KtaError:
+                self.close()
+                raise
+        self.repartition = self.n_partitions if partitioner else 0
+        if partitioner and repartition is not None:
+            try:
+                self.set_repartition(repartition)
             except KtaError:
                 self.close()
                 raise
@@ -178,7 +189,7 @@ class HipMetricHandler:
         val_len = np.ascontiguousarray(val_len, dtype=np.int32)
         ts_ms = np.ascontiguousarray(ts_ms, dtype=np.int64)
         n = len(partition)
-        keys = self.count_alive_keys or self.key_sketch_on or self.hot_keys_on   # the staging batches carry the keys
+        keys = self.count_alive_keys or self.key_sketch_on or self.hot_keys_on or self.partitioner_on   # the staging batches carry the keys
         if keys:
             key_off = np.ascontiguousarray(key_off, dtype=np.uint32)
             key_bytes = np.ascontiguousarray(key_bytes, dtype=np.uint8)
@@ -504,6 +515,36 @@ class HipMetricHandler:
     def set_ts_order_chunk(self, records: int) -> None:
         """Tests: the records per chunk of the timestamp-order pass, a multiple of 64 (0: the default)."""
         self._check(self._lib.kta_set_ts_order_chunk(self._ctx, int(records)))
+
+    def set_repartition(self, q: int) -> None:
+        """The what-if partition count Q of the partitioner pass (kta_set_repartition): only while the context has been
+        handed no record since creation / reset()."""
+        self._check(self._lib.kta_set_repartition(self._ctx, int(q)))
+        self.repartition = int(q)
+
+    def _partitioner(self, fn) -> dict:
+        out = np.zeros(2 * self.n_partitions + 2 * self.repartition, dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), out.size))
+        return split_partitioner(out, self.n_partitions, self.repartition)
+
+    def partitioner(self) -> dict:
+        """The live partitioner vector as a dict of np.uint64 arrays: checked[P], placed[P], target_records[Q],
+        target_bytes[Q] (kta_get_partitioner; staged messages are flushed first); "vector" is the whole u64[2 P + 2 Q]."""
+        return self._partitioner(self._lib.kta_get_partitioner)
+
+    def exchange_partitioner(self) -> dict:
+        """As partitioner(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._partitioner(self._lib.kta_exchange_partitioner)
+
+    def partitioner_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the partitioner snapshot (for collectives: allreduce_partitioner_vector)."""
+        return self._device_vector(self._lib.kta_partitioner_result_vector)
+
+    def partitioner_info(self) -> dict:
+        """Work counters of the partitioner pass since creation / reset() (kta_partitioner_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_partitioner_info(self._ctx, C.byref(out)))
+        return dict(zip(("keyed_records", "launches", "partition_adds", "target_adds", "workgroups", "lds_bytes"), (int(x) for x in out)))
 
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
@@ -853,6 +894,55 @@ def render_ts_order(vec, counter_vec, n_partitions: int) -> str:
     if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
     return _render(N.load().kta_render_ts_order, _np_ptr(v), _np_ptr(c), n_partitions)
+
+
+def _partitioner_vec(vec, P: int, Q: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    if v.size != 2 * P + 2 * Q:
+        raise ValueError(f"a partitioner vector of {P} partitions and {Q} targets has {2 * P + 2 * Q} words, not {v.size}")
+    return v
+
+
+def split_partitioner(vec, n_partitions: int, repartition: int) -> dict:
+    """A partitioner vector u64[2 P + 2 Q] as a dict: checked[P], placed[P], target_records[Q], target_bytes[Q], and the
+    vector itself under "vector"."""
+    P = n_partitions
+    v = _partitioner_vec(vec, P, repartition)
+    return {"checked": v[0:2 * P:2].copy(), "placed": v[1:2 * P:2].copy(), "target_records": v[2 * P::2].copy(),
+            "target_bytes": v[2 * P + 1::2].copy(), "vector": v}
+
+
+def merge_partitioner(acc: np.ndarray, other, n_partitions: int, repartition: int) -> np.ndarray:
+    """kta_merge_partitioner, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    rc = N.load().kta_merge_partitioner(_np_ptr(_partitioner_vec(acc, n_partitions, repartition)),
+                                        _np_ptr(_partitioner_vec(other, n_partitions, repartition)), n_partitions, repartition)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_partitioner")
+    return acc
+
+
+def render_partitioner(vec, counter_vec, n_partitions: int, repartition: int) -> str:
+    """kta_render_partitioner: the section kta-analyzer prints with --librdkafka kta.partitioner=murmur2, from a partitioner
+    vector and the counter vector u64[P * 7 + 8] of the same records."""
+    v = _partitioner_vec(vec, n_partitions, repartition)
+    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
+    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    return _render(N.load().kta_render_partitioner, _np_ptr(v), _np_ptr(c), n_partitions, repartition)
+
+
+def partitioner_max_partitions() -> int:
+    """The largest P, and the largest Q, of a context with the partitioner pass."""
+    return int(N.load().kta_partitioner_max_partitions())
+
+
+def murmur2(key: bytes) -> int:
+    """Kafka's murmur2 of `key` as a u32 (kta_murmur2; host only)."""
+    key = bytes(key)
+    return int(N.load().kta_murmur2(key, len(key)))
 
 
 def ts_order_max_partitions() -> int:

@@ -58,6 +58,7 @@ KTA_SKETCH_REGISTERS = 1 << KTA_SKETCH_LOG2   # key sketch vector: u64[P * 4096]
 KTA_SKETCH_MAX_PARTITIONS = 16384
 KTA_FLAG_HOT_KEYS = 16
 KTA_FLAG_TS_ORDER = 32
+KTA_FLAG_PARTITIONER = 64         # partitioner vector: u64[2 P + 2 Q] = [P][2] checked, placed | [Q][2] target records, bytes
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -212,6 +213,16 @@ SIGNATURES = {
     "kta_ts_order_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
     "kta_set_ts_order_chunk": (C.c_int, [_P, C.c_uint64]),
     "kta_render_ts_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_set_repartition": (C.c_int, [_P, C.c_uint32]),
+    "kta_get_partitioner": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_partitioner": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_partitioner_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_partitioner": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "kta_partitioner_max_partitions": (C.c_int, []),
+    "kta_partitioner_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_murmur2": (C.c_uint32, [C.c_void_p, C.c_size_t]),
+    "kta_render_partitioner": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]),
     "kta_render_distinct_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),

@@ -18,7 +18,7 @@
 //                                        (include/kta_kafka.h), the host only walks batch headers
 // Extra knobs travel in --librdkafka as kta.* keys (kta.device=N, kta.gpus=N,
 // kta.batch=N, kta.write_dump=<path>, kta.per_message=1, kta.analytics=1, kta.timeline=<width>, kta.distinct_keys=1, kta.hot_keys=K,
-// kta.ts_order=1), so
+// kta.ts_order=1, kta.partitioner=murmur2, kta.repartition=Q), so
 // no flag is added or renamed.
 // kta.gpus=N (synthetic:// and segment:// sources) shards the topic's partitions over N GPUs, partition p on
 // rank p % N, one host thread + one context + one communicator rank per GPU (device (kta.device + r) mod the
@@ -38,6 +38,11 @@
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
+// kta.partitioner=murmur2 (every source, kta.per_message=1 and kta.gpus=N included; any other value is refused — crc32, the
+// hash of librdkafka's own default partitioner, may follow) runs the partitioner pass as well (KTA_FLAG_PARTITIONER; no
+// reference counterpart) and prints, last of all, how many keyed records lie on the partition Kafka's default partitioner
+// gives their key, and how the keyed records and bytes would spread over Q partitions: kta.repartition=Q (a decimal in
+// [1, kta_partitioner_max_partitions()]; needs kta.partitioner), P when it is not given.
 // kta.hot_keys=K (1 <= K <= 64; every source, kta.gpus=N included) keeps the hot-key sketch as well (KTA_FLAG_HOT_KEYS; no
 // reference counterpart) and prints, last of all, the at most K keys that hold 1/512 of the keyed records and more, with
 // bounds on their records and, where the device caught one, the key's bytes (with kta.gpus=N from the lowest rank that
@@ -103,6 +108,18 @@ std::vector<uint64_t> total_records(const kta::MessageMetrics &m, uint32_t P)
     std::vector<uint64_t> total(P);
     for (uint32_t p = 0; p < P; p++) total[p] = m.total((int32_t)p);
     return total;
+}
+
+// the per-partition words of the counter vector that the kta.partitioner section reads
+std::vector<uint64_t> partitioner_counters(const kta::MessageMetrics &m, uint32_t P)
+{
+    std::vector<uint64_t> c((size_t)P * KTA_NCOUNTERS + KTA_NGLOBALS, 0);
+    for (uint32_t p = 0; p < P; p++) {
+        uint64_t *r = c.data() + (size_t)p * KTA_NCOUNTERS;
+        r[KTA_C_KEY_NULL] = m.key_null((int32_t)p), r[KTA_C_KEY_NON_NULL] = m.key_non_null((int32_t)p);
+        r[KTA_C_KEY_SIZE_SUM] = m.key_size_sum((int32_t)p), r[KTA_C_VALUE_SIZE_SUM] = m.value_size_sum((int32_t)p);
+    }
+    return c;
 }
 
 // murmur3's finaliser: x = hot_fmix32(hash) places a key hash in the hot-key sketch (kta_hip.h)
@@ -241,6 +258,8 @@ struct ShardedJob {
     bool distinct_keys = false;                        // kta.distinct_keys=1: every rank's context, exchanged with the counters
     uint32_t hot_keys = 0;                             // kta.hot_keys=K: likewise; the exemplars stay on their ranks
     bool ts_order = false;                             // kta.ts_order=1: likewise (a partition's records stay on one rank)
+    bool partitioner = false;                          // kta.partitioner=murmur2: likewise
+    uint32_t repartition = 0;                          //   kta.repartition=Q (0: P)
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -255,10 +274,11 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
-                               (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u);
-        const bool keys = job.count_alive || job.distinct_keys || job.hot_keys;   // the staging batches carry key_off / key_bytes
+                               (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
+                               (job.partitioner ? KTA_FLAG_PARTITIONER : 0u);
+        const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
-                                                             job.batch, 0, flags, job.timeline);
+                                                             job.batch, 0, flags, job.timeline, job.repartition);
         kta_ctx *ctx = h->ctx();
         h->comm_create(job.nranks, rank, uid);
         if (job.synthetic) {
@@ -407,6 +427,8 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             }
             text += kta::render_hot_keys(h0->hot_keys()->data(), merged.data(), job.hot_keys);
         }
+        if (job.partitioner)
+            text += kta::render_partitioner(h0->partitioner()->data(), partitioner_counters(metrics, job.P).data(), job.P, h0->repartition());
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -517,6 +539,34 @@ int main(int argc, char **argv)
                     kta_ts_order_max_partitions());
             return 2;
         }
+    }
+    bool partitioner = false;
+    uint32_t repartition = 0;
+    if (cfg.count("kta.partitioner")) {
+        const std::string &v = cfg["kta.partitioner"];
+        if (v != "murmur2") {
+            fprintf(stderr, "kta.partitioner=%s: expected murmur2 (Kafka's default partitioner; the only hash there is so far)\n", v.c_str());
+            return 2;
+        }
+        partitioner = true;
+        if (P > (uint32_t)kta_partitioner_max_partitions()) {   // before any context, so before any kernel
+            fprintf(stderr, "kta.partitioner=murmur2: the topic has %u partitions, the partitioner pass admits at most %d\n", P,
+                    kta_partitioner_max_partitions());
+            return 2;
+        }
+    }
+    if (cfg.count("kta.repartition")) {
+        if (!partitioner) {
+            fprintf(stderr, "kta.repartition=%s: needs kta.partitioner=murmur2\n", cfg["kta.repartition"].c_str());
+            return 2;
+        }
+        const int64_t q = parse_decimal(cfg["kta.repartition"], 9);
+        if (q < 1 || q > kta_partitioner_max_partitions()) {
+            fprintf(stderr, "kta.repartition=%s: expected a partition count, 1 to %d\n", cfg["kta.repartition"].c_str(),
+                    kta_partitioner_max_partitions());
+            return 2;
+        }
+        repartition = (uint32_t)q;
     }
     uint32_t hot_keys = 0;
     if (cfg.count("kta.hot_keys")) {
@@ -648,6 +698,8 @@ int main(int argc, char **argv)
         job.distinct_keys = distinct_keys;
         job.hot_keys = hot_keys;
         job.ts_order = ts_order;
+        job.partitioner = partitioner;
+        job.repartition = repartition;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -665,8 +717,9 @@ int main(int argc, char **argv)
     try {
         handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
-                                                (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u),
-                                            timeline);
+                                                (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
+                                                (partitioner ? KTA_FLAG_PARTITIONER : 0u),
+                                            timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
         return 2;
@@ -734,7 +787,7 @@ int main(int argc, char **argv)
             kta_batch hb;
             check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
             uint64_t n = std::min<uint64_t>(hb.capacity, n_records - seq), kb = 0;
-            if (!count_alive && !distinct_keys && !hot_keys && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
+            if (!count_alive && !distinct_keys && !hot_keys && !partitioner && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
             int rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
             while (rc == KTA_ERR_CAPACITY && n > 1) {  // key bytes did not fit: shrink the batch
                 n /= 2;
@@ -778,7 +831,7 @@ int main(int argc, char **argv)
                 kta_batch hb;
                 check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
                 uint64_t n = std::min<uint64_t>(hb.capacity, db.n - done), kb = 0;
-                if (count_alive || distinct_keys || hot_keys) {  // re-pack this chunk's keys
+                if (count_alive || distinct_keys || hot_keys || partitioner) {  // re-pack this chunk's keys
                     uint64_t m = 0;
                     for (; m < n; m++) {
                         const uint64_t kl = db.key_len[done + m] > 0 ? (uint64_t)db.key_len[done + m] : 0;
@@ -844,6 +897,8 @@ int main(int argc, char **argv)
         if (distinct_keys) text += kta::render_distinct_keys(handler->key_sketch()->data(), keyed_records(metrics, P));
         if (ts_order) text += kta::render_ts_order(handler->ts_order()->data(), total_records(metrics, P));
         if (hot_keys) text += kta::render_hot_keys(handler->hot_keys()->data(), handler->hot_key_exemplars()->data(), hot_keys);
+        if (partitioner)
+            text += kta::render_partitioner(handler->partitioner()->data(), partitioner_counters(metrics, P).data(), P, handler->repartition());
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

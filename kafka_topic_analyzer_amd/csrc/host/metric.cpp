@@ -70,10 +70,11 @@ uint64_t MessageMetrics::smallest_message() const
 }
 
 HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device, uint64_t batch_capacity,
-                                   uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline)
+                                   uint64_t key_bytes_capacity, uint32_t flags, const TimelineConfig &timeline, uint32_t repartition)
     : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
       sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0),
-      tso_on_((flags & KTA_FLAG_TS_ORDER) != 0)
+      tso_on_((flags & KTA_FLAG_TS_ORDER) != 0), part_on_((flags & KTA_FLAG_PARTITIONER) != 0),
+      part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -91,6 +92,15 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
         rc = kta_set_timeline(ctx_, timeline_.origin_ms, timeline_.bucket_ms, timeline_.n_buckets);
         if (rc != KTA_OK) {
             const std::string msg = std::string("kta_set_timeline failed: ") + kta_last_error(ctx_);
+            kta_destroy(ctx_);
+            ctx_ = nullptr;
+            throw std::runtime_error(msg);
+        }
+    }
+    if (part_on_ && repartition) {
+        rc = kta_set_repartition(ctx_, repartition);
+        if (rc != KTA_OK) {
+            const std::string msg = std::string("kta_set_repartition failed: ") + kta_last_error(ctx_);
             kta_destroy(ctx_);
             ctx_ = nullptr;
             throw std::runtime_error(msg);
@@ -174,6 +184,10 @@ void HipMetricHandler::read_analytics()
     if (tso_on_) {
         ovec_.assign(3 * (size_t)P_ + 64, 0);
         check(kta_exchange_ts_order(ctx_, ovec_.data(), ovec_.size()), "kta_exchange_ts_order");
+    }
+    if (part_on_) {
+        pvec_.assign(2 * (size_t)P_ + 2 * (size_t)part_q_, 0);
+        check(kta_exchange_partitioner(ctx_, pvec_.data(), pvec_.size()), "kta_exchange_partitioner");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

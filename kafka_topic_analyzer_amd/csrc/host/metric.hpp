@@ -108,7 +108,8 @@ private:
 class HipMetricHandler : public MetricHandler {
 public:
     HipMetricHandler(int32_t n_partitions, bool count_alive_keys, int device = 0, uint64_t batch_capacity = 0,
-                     uint64_t key_bytes_capacity = 0, uint32_t flags = 0, const TimelineConfig &timeline = TimelineConfig{});
+                     uint64_t key_bytes_capacity = 0, uint32_t flags = 0, const TimelineConfig &timeline = TimelineConfig{},
+                     uint32_t repartition = 0 /* KTA_FLAG_PARTITIONER: the what-if partition count Q; 0: P */);
     ~HipMetricHandler() override;
     HipMetricHandler(const HipMetricHandler &) = delete;
     HipMetricHandler &operator=(const HipMetricHandler &) = delete;
@@ -141,6 +142,10 @@ public:
     // With KTA_FLAG_TS_ORDER: the timestamp-order vector u64[3 P + 64] of the snapshot finish() / exchange() took (after
     // exchange(), the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *ts_order() const { return tso_on_ ? &ovec_ : nullptr; }
+    // With KTA_FLAG_PARTITIONER: the partitioner vector u64[2 P + 2 Q] of the snapshot finish() / exchange() took (after
+    // exchange(), the whole job's); nullptr without the flag.
+    const std::vector<uint64_t> *partitioner() const { return part_on_ ? &pvec_ : nullptr; }
+    uint32_t repartition() const { return part_q_; }
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -167,6 +172,9 @@ private:
     std::vector<kta_hot_exemplar> hex_;
     bool tso_on_ = false;
     std::vector<uint64_t> ovec_;
+    bool part_on_ = false;
+    uint32_t part_q_ = 0;
+    std::vector<uint64_t> pvec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -193,5 +201,8 @@ std::string render_ts_order(const uint64_t *vec, const std::vector<uint64_t> &re
 // the opt-in section kta-analyzer prints last with kta.hot_keys=K (kta_render_hot_keys): vec u64[2 * 1024 * 23],
 // exemplars [2 * 1024] or null; empty for a vector kta_hot_keys_recover refuses
 std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys);
+// the opt-in section kta-analyzer prints last of all with kta.partitioner=murmur2 (kta_render_partitioner): vec
+// u64[2 P + 2 Q], counters u64[P * 7 + 8] (the counter vector of the same records; its globals are not read)
+std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q);
 
 }  // namespace kta

@@ -305,6 +305,71 @@ std::string render_ts_order(const uint64_t *vec, const std::vector<uint64_t> &re
     return o;
 }
 
+// The opt-in partitioner section (kta.partitioner=murmur2): no reference counterpart, printed last of all.  vec: u64[2 P + 2 Q]
+// (kta_hip.h), counters: the counter vector's per-partition words.
+std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q)
+{
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    auto pct = [](uint64_t count, uint64_t of) {
+        if (!of) return std::string("-");
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", (double)count * 100.0 / (double)of);
+        return std::string(buf);
+    };
+    // largest / mean of n values whose sum is `sum`
+    auto skew = [](uint64_t largest, uint64_t sum, uint32_t n) {
+        if (!sum) return std::string("-");
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", (double)largest * (double)n / (double)sum);
+        return std::string(buf);
+    };
+    std::string o;
+    o += "Partitioner check: keyed records on the partition Kafka's default partitioner (murmur2) gives their key "
+         "(kta.partitioner=murmur2; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Keyed records", "On murmur2's partition", "%"});
+    uint64_t checked_all = 0, placed_all = 0, no_key = 0, keyed_most = 0, keyed_sum = 0, bytes_most = 0, bytes_sum = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t checked = vec[2 * (size_t)p], placed = vec[2 * (size_t)p + 1];
+        const uint64_t *c = counters + (size_t)p * KTA_NCOUNTERS;
+        const uint64_t bytes = c[KTA_C_KEY_SIZE_SUM] + c[KTA_C_VALUE_SIZE_SUM];
+        checked_all += checked, placed_all += placed, no_key += c[KTA_C_KEY_NULL];
+        keyed_sum += c[KTA_C_KEY_NON_NULL], keyed_most = std::max(keyed_most, c[KTA_C_KEY_NON_NULL]);
+        bytes_sum += bytes, bytes_most = std::max(bytes_most, bytes);
+        rows.push_back({std::to_string(p), u(checked), checked ? u(placed) : "-", pct(placed, checked)});
+    }
+    rows.push_back({"Topic", u(checked_all), checked_all ? u(placed_all) : "-", pct(placed_all, checked_all)});
+    o += pretty_table(rows);
+    o += "Records without a key: " + u(no_key) + " (the default partitioner spreads them without a hash)\n";
+    if (checked_all == 0) {
+        o += "No record has a key: nothing to check.\n";
+    } else if (placed_all == checked_all) {
+        o += "All keyed records lie on murmur2's partition: the topic is keyed as Kafka's default partitioner keys it.\n";
+    } else if (P > 2 && (unsigned __int128)placed_all * P <= (unsigned __int128)checked_all * 2) {
+        o += "No more keyed records lie on murmur2's partition than chance puts there (" + pct(placed_all, checked_all) + " % against 1/P = " +
+             pct(1, P) + " %): the topic was not written by Kafka's default partitioner with " + u(P) + " partitions.\n";
+    } else {
+        o += pct(placed_all, checked_all) + " % of the keyed records lie on murmur2's partition: the topic is only partly keyed as "
+             "Kafka's default partitioner keys it.\n";
+    }
+    o += "Repartition what-if: the keyed records over Q = " + u(Q) + " partitions by murmur2\n";
+    const uint64_t *t = vec + 2 * (size_t)P;
+    uint64_t rec_sum = 0, rec_most = 0, tb_sum = 0, tb_most = 0;
+    for (uint32_t q = 0; q < Q; q++) {
+        rec_sum += t[2 * (size_t)q], rec_most = std::max(rec_most, t[2 * (size_t)q]);
+        tb_sum += t[2 * (size_t)q + 1], tb_most = std::max(tb_most, t[2 * (size_t)q + 1]);
+    }
+    rows.clear();
+    rows.push_back({"Target", "Records", "Records %", "Bytes", "Bytes %"});
+    for (uint32_t q = 0; q < Q; q++)
+        rows.push_back({std::to_string(q), u(t[2 * (size_t)q]), pct(t[2 * (size_t)q], rec_sum), u(t[2 * (size_t)q + 1]), pct(t[2 * (size_t)q + 1], tb_sum)});
+    o += pretty_table(rows);
+    o += "Largest / mean at Q = " + u(Q) + ": records " + skew(rec_most, rec_sum, Q) + ", bytes " + skew(tb_most, tb_sum, Q) +
+         "; the topic as it is (P = " + u(P) + "): records " + skew(keyed_most, keyed_sum, P) + ", bytes " + skew(bytes_most, bytes_sum, P) + "\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
 static uint32_t fmix32(uint32_t x)
 {
@@ -390,6 +455,21 @@ extern "C" int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_
     std::vector<uint64_t> records(n_partitions);
     for (uint32_t p = 0; p < n_partitions; p++) records[p] = counter_vec[(size_t)p * KTA_NCOUNTERS + KTA_C_TOTAL];
     const std::string text = kta::render_ts_order(vec, records);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_partitioner(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, uint32_t q, char *out,
+                                      size_t out_cap, size_t *out_len)
+{
+    const uint32_t lim = (uint32_t)kta_partitioner_max_partitions();
+    if (!vec || !counter_vec || !out_len || n_partitions == 0 || n_partitions > lim || q == 0 || q > lim) return KTA_ERR_INVALID;
+    const std::string text = kta::render_partitioner(vec, counter_vec, n_partitions, q);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

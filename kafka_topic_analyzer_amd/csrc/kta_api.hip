@@ -5,6 +5,7 @@
 #include "../../include/kta_hip.h"
 #include "kta_internal.h"
 #include "kta_kernels.h"
+#include "kta_murmur2.h"
 
 #include <limits.h>
 #include <math.h>
@@ -86,6 +87,12 @@ struct kta_ctx {
     DeviceBuf<int64_t> d_tso_hi, d_tso_ws;
     uint64_t tso_launches = 0, tso_chunks = 0, tso_last_chunk = 0;
     uint64_t tso_chunk = 0;          // kta_set_ts_order_chunk (tests); 0: by the slice's length
+    // partitioner (KTA_FLAG_PARTITIONER): d_part u64[2 P + 2 Q] the live vector, d_part_out its snapshot, d_part_stats the
+    // kernel's work counters (kta_partitioner_info); part_q the what-if partition count (kta_set_repartition; P at first)
+    bool part = false;
+    uint32_t part_q = 0;
+    DeviceBuf<uint64_t> d_part, d_part_out, d_part_stats;
+    uint64_t part_launches = 0, part_workgroups = 0;
     DeviceBuf<uint64_t> d_vec;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     DeviceBuf<uint64_t> d_vec_out;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -253,7 +260,7 @@ kta::SketchColumns sketch_columns(const kta_internal_columns &rb, const kta_batc
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// Before a pass that reads plain i32 lengths next to keys (the alive-key pass, the key sketch, the hot keys) runs over
+// Before a pass that reads plain i32 lengths next to keys (the alive-key pass, the key sketch, the hot keys, the partitioner) runs over
 // records [0, n) of c: when c's length columns lie in a keyless allocation — a view of it handed over with key columns
 // of the caller's own —, the u16 tiles the range touches are widened in place (exact; one small pass, and none when the
 // lengths are the caller's own or a keyed allocation's).
@@ -321,6 +328,22 @@ int run_hot_keys(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &r
     });
 }
 
+// The partitioner pass over a batch whose metric columns were resolved to rb, in launches of at most 2^30 records (the
+// u32 fields of its LDS counters).
+int run_partitioner(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n)
+{
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < kta::kPartitionerLaunchMax ? n - at : kta::kPartitionerLaunchMax;
+        uint32_t wgs = 0;
+        KTA_HIP(ctx, kta::launch_partitioner(kta::PartitionerColumns{sketch_columns(rb, c, at), c->val_len + at}, take, ctx->P, ctx->part_q,
+                                             ctx->d_part.get(), ctx->d_part_stats.get(), ctx->cu_count, &wgs, ctx->s_compute));
+        ctx->part_launches++;
+        ctx->part_workgroups += wgs;
+        at += take;
+    }
+    return KTA_OK;
+}
+
 // The timestamp-order pass over a batch whose metric columns were resolved to rb: chunk maxima, prefix, apply per slice,
 // in order.  A slice is as many chunks as the workspace has rows for P partitions; the chunk is the slice over
 // kTsOrderChunks (enough waves to fill the device a few times over), a multiple of 256 records, or the tests' own.
@@ -380,6 +403,8 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
     if ((which & 1) && ctx->hot && (!c->key_off || !c->key_bytes))
         return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_HOT_KEYS)");
+    if ((which & 1) && ctx->part && (!c->key_off || !c->key_bytes))
+        return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_PARTITIONER)");
     // Table state: which kernels take the batch is decided before anything is launched (the fused pass below depends on it).
     // 3 = the partitioned pass for batches of >= 2^21 records (13: for batches of any size — tests), with the automatic
     // fall-back to the single-kernel filtered update (2) for batches of mostly unique keys; 1 / 2 / 8 / 9 = the
@@ -420,7 +445,7 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         int rc = kta_internal_resolve(ctx, c, &rb);
         if (rc != KTA_OK) return rc;
     }
-    if (((which & 2) && ctx->alive) || ((which & 1) && (ctx->sketch || ctx->hot))) {
+    if (((which & 2) && ctx->alive) || ((which & 1) && (ctx->sketch || ctx->hot || ctx->part))) {
         int rc = widen_lens_for_keys(ctx, c, n);
         if (rc != KTA_OK) return rc;
     }
@@ -553,6 +578,10 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
         int rc = run_hot_keys(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
     }
+    if ((which & 1) && ctx->part) {     // likewise
+        int rc = run_partitioner(ctx, c, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     return KTA_OK;
 }
 
@@ -577,6 +606,11 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_hi.get(), 0xFF, (size_t)ctx->P * sizeof(int64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->tso_launches = ctx->tso_chunks = ctx->tso_last_chunk = 0;
+    }
+    if (ctx->part) {                    // (Q stays)
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_part.get(), 0, kta::partitioner_len(ctx->P, ctx->part_q) * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
+        ctx->part_launches = ctx->part_workgroups = 0;
     }
     ctx->handed_records = false;
     if (ctx->alive) {
@@ -644,6 +678,8 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
     rv[KTA_RV_KEY_SKETCH] = ResultVector{ctx->d_sketch_out.get(), ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0, 0, false};
     rv[KTA_RV_HOT_KEYS] = ResultVector{ctx->d_hot_out.get(), ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, false};
     rv[KTA_RV_TS_ORDER] = ResultVector{ctx->d_tso_out.get(), ctx->tso ? kta::ts_order_len(ctx->P) : 0, ctx->tso ? 2 * (size_t)ctx->P + 64 : 0, true};
+    const size_t plen = ctx->part ? kta::partitioner_len(ctx->P, ctx->part_q) : 0;
+    rv[KTA_RV_PARTITIONER] = ResultVector{ctx->part ? ctx->d_part_out.get() : nullptr, plen, plen, false};
 }
 
 static ResultVector result_vector(kta_ctx *ctx, int kind)
@@ -673,6 +709,10 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
 {
     if (!cfg || !out) return fail(nullptr, KTA_ERR_INVALID, "kta_create: null argument");
     *out = nullptr;
+    // (before the general bound, which is the same number today: the message names the pass that sets this one)
+    if ((cfg->flags & KTA_FLAG_PARTITIONER) && cfg->n_partitions > kta_partitioner_max_partitions())
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_PARTITIONER admits at most " + std::to_string(kta_partitioner_max_partitions()) +
+                                                  " partitions (the pass keeps its counters in LDS)");
     if (cfg->n_partitions <= 0 || cfg->n_partitions > 4096)
         return fail(nullptr, KTA_ERR_INVALID, "n_partitions must be in [1, 4096]");
     if ((cfg->flags & KTA_FLAG_ANALYTICS) && cfg->n_partitions > kta_analytics_max_partitions())
@@ -709,6 +749,8 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->sketch = (cfg->flags & KTA_FLAG_KEY_SKETCH) != 0;
     ctx->hot = (cfg->flags & KTA_FLAG_HOT_KEYS) != 0;
     ctx->tso = (cfg->flags & KTA_FLAG_TS_ORDER) != 0;
+    ctx->part = (cfg->flags & KTA_FLAG_PARTITIONER) != 0;
+    ctx->part_q = ctx->part ? ctx->P : 0u;
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
@@ -770,6 +812,13 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_tso_ws.alloc(kta::kTsOrderWorkspaceWords));
         KTA_TRY(ctx->d_tso_stats.alloc(3));
     }
+    if (ctx->part) {
+        const size_t words = kta::partitioner_len(ctx->P, ctx->part_q);
+        KTA_TRY(ctx->d_part.alloc(words));
+        KTA_TRY(ctx->d_part_out.alloc(words));
+        KTA_TRY(hipMemset(ctx->d_part_out.get(), 0, words * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_part_stats.alloc(3));
+    }
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_TRY(ctx->d_table.alloc(kta::kAliveSlots));
@@ -813,7 +862,7 @@ static int ensure_stage(kta_ctx *ctx, Stage &st)
 {
     if (st.host_slab) return KTA_OK;
     const uint64_t cap = ctx->batch_capacity, kcap = ctx->key_bytes_capacity;
-    const bool keys = ctx->alive || ctx->sketch || ctx->hot, seq = ctx->alive && ctx->stage_seq;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot || ctx->part, seq = ctx->alive && ctx->stage_seq;
     size_t off = 0, o_part, o_klen, o_vlen, o_ts, o_koff = 0, o_seq = 0, o_kb = 0;
     o_part = off; off += pad16(cap * 4);
     o_klen = off; off += pad16(cap * 4);
@@ -869,7 +918,7 @@ int kta_batch_submit(kta_ctx *ctx, uint64_t n, uint64_t n_key_bytes, uint64_t ba
 {
     if (!ctx) return KTA_ERR_INVALID;
     if (!ctx->acquired) return fail(ctx, KTA_ERR_INVALID, "kta_batch_submit without kta_batch_acquire");
-    const bool keys = ctx->alive || ctx->sketch || ctx->hot;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot || ctx->part;
     if (n > ctx->batch_capacity || (keys && n_key_bytes > ctx->key_bytes_capacity))
         return fail(ctx, KTA_ERR_CAPACITY, "batch larger than the staging capacity");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
@@ -932,7 +981,7 @@ int kta_handle_message(kta_ctx *ctx, int32_t partition, int64_t ts_ms, const voi
     if (key_len > INT32_MAX || val_len > INT32_MAX)
         return fail(ctx, KTA_ERR_INVALID, "key/value length above i32 range");
     if (!key) key_len = -1; // m.key() is None iff librdkafka's key pointer is null
-    const bool keys = ctx->alive || ctx->sketch || ctx->hot;
+    const bool keys = ctx->alive || ctx->sketch || ctx->hot || ctx->part;
     const uint64_t kb = (keys && key_len > 0) ? (uint64_t)key_len : 0;
     if (kb > ctx->key_bytes_capacity) return fail(ctx, KTA_ERR_CAPACITY, "key larger than key_bytes_capacity");
     if (ctx->fill_n > 0 && (ctx->fill_n == ctx->batch_capacity || ctx->fill_kb + kb > ctx->key_bytes_capacity)) {
@@ -976,6 +1025,7 @@ int kta_replay_messages(kta_ctx *ctx, const kta_batch *c, uint64_t n)
     if (ctx->alive && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (count_alive_keys)");
     if (ctx->sketch && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_KEY_SKETCH)");
     if (ctx->hot && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_HOT_KEYS)");
+    if (ctx->part && (!c->key_off || !c->key_bytes)) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_PARTITIONER)");
     // through a pointer the compiler cannot see through: the loop pays the call a foreign caller pays per message
     static int (*volatile entry)(kta_ctx *, int32_t, int64_t, const void *, int64_t, int64_t) = kta_handle_message;
     static const uint8_t no_bytes[1] = {0};
@@ -1184,7 +1234,8 @@ int kta_finish_device(kta_ctx *ctx)
     ResultVector rv[KTA_RV_KINDS];
     kta_internal_result_vectors(ctx, rv);
     // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
-    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get()};
+    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get(),
+                                                 ctx->d_part.get()};
     for (int k = 0; k < KTA_RV_KINDS; k++)
         if (rv[k].out && live[k])
             KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -1655,6 +1706,98 @@ int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records)
     return KTA_OK;
 }
 
+static const char *const kNoPart = "context was created without KTA_FLAG_PARTITIONER";
+
+static int part_words(kta_ctx *ctx, size_t n_u64)
+{
+    return check_words(ctx, "partitioner vector", kta::partitioner_len(ctx->P, ctx->part_q), n_u64);
+}
+
+int kta_partitioner_max_partitions(void) { return (int)kta::kPartitionerMaxPartitions; }
+
+uint32_t kta_murmur2(const void *key, size_t len)
+{
+    // the words in place, the tail bytes from a copy (the device's tail word may end 3 bytes past the key)
+    const uint8_t *k = static_cast<const uint8_t *>(key);
+    uint32_t h = kta::kMurmur2Seed ^ (uint32_t)len;
+    const size_t words = len >> 2;
+    for (size_t d = 0; d < words; d++) h = kta::murmur2_word(h, kta::murmur2_load32(k + 4 * d));
+    uint8_t tail[4] = {0};
+    if (len & 3u) memcpy(tail, k + 4 * words, len & 3u);
+    return kta::murmur2_finish(h, kta::murmur2_load32(tail), (uint32_t)len);
+}
+
+int kta_set_repartition(kta_ctx *ctx, uint32_t q)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    if (q < 1 || q > kta::kPartitionerMaxPartitions)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_repartition: Q must be in [1, " + std::to_string(kta::kPartitionerMaxPartitions) + "]");
+    if (ctx->handed_records || ctx->fill_n)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_repartition: the context has been handed records since kta_create / kta_reset");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t words = kta::partitioner_len(ctx->P, q);
+    if (q != ctx->part_q) {
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+        KTA_HIP(ctx, ctx->d_part.alloc(words));
+        KTA_HIP(ctx, ctx->d_part_out.alloc(words));
+        ctx->part_q = q;
+    }
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_part.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_out.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    return KTA_OK;
+}
+
+int kta_get_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    int rc = part_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_part.get(), out, n_u64);
+}
+
+int kta_exchange_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    int rc = part_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_words(ctx, ctx->d_part_out.get(), out, n_u64);
+}
+
+int kta_partitioner_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    return hand_out(result_vector(ctx, KTA_RV_PARTITIONER), device_ptr, n_u64);
+}
+
+int kta_merge_partitioner(uint64_t *acc, const uint64_t *other, uint32_t P, uint32_t q)
+{
+    if (!acc || !other || P == 0 || P > kta::kPartitionerMaxPartitions || q == 0 || q > kta::kPartitionerMaxPartitions) return KTA_ERR_INVALID;
+    const size_t words = kta::partitioner_len(P, q);
+    merge_words(acc, other, words, words, false);
+    return KTA_OK;
+}
+
+int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t st[3];
+    int rc = read_words(ctx, ctx->d_part_stats.get(), st, 3);
+    uint32_t plan[3];
+    kta::partitioner_lds_plan(ctx->P, ctx->part_q, plan);
+    out[0] = st[0], out[1] = ctx->part_launches, out[2] = st[1], out[3] = st[2], out[4] = ctx->part_workgroups, out[5] = plan[0];
+    return rc;
+}
+
 namespace {
 
 // a^-1 mod 2^32 of an odd a, by Newton's iteration (each step doubles the correct low bits: 3, 6, 12, 24, 48)
@@ -1997,7 +2140,7 @@ void **kta_internal_comm_slot(kta_ctx *ctx, void (*free_fn)(void *))
     ctx->comm_free = free_fn;
     return &ctx->comm_state;
 }
-bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch || ctx->hot; }
+bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch || ctx->hot || ctx->part; }
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }

@@ -30,7 +30,7 @@ hipStream_t kta_internal_stream(kta_ctx *ctx);
 hipStream_t kta_internal_copy_stream(kta_ctx *ctx);
 bool kta_internal_timing(kta_ctx *ctx);
 uint32_t kta_internal_partitions(kta_ctx *ctx);
-bool kta_internal_want_keys(kta_ctx *ctx);   // -c, the key sketch or the hot keys: the handlers read key_off / key_bytes
+bool kta_internal_want_keys(kta_ctx *ctx);   // -c, the key sketch, the hot keys or the partitioner: the handlers read key_off / key_bytes
 bool kta_internal_count_alive(kta_ctx *ctx);
 bool kta_internal_alive_table(kta_ctx *ctx);
 uint64_t *kta_internal_table(kta_ctx *ctx);
@@ -68,12 +68,14 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns 
 //   key sketch  P*4096             none           all    (u64)
 //   hot keys    2*1024*23          all            none
 //   ts order    3*P + 64           2*P + 64       P      (i64)
+//   partitioner 2*P + 2*Q          all            none
 struct ResultVector {
     uint64_t *out;     // the snapshot (device); null: the context has no such section
     size_t words, sum_words;
     bool max_signed;
 };
-enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_KINDS };
+enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_PARTITIONER,
+       KTA_RV_KINDS };
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);
 
 // ---- errors -------------------------------------------------------------------------------------------------------

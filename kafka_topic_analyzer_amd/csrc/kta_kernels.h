@@ -279,4 +279,20 @@ struct TsOrderState {
 // chunk maxima, prefix, apply.
 hipError_t launch_ts_order(const ScanColumns &c, uint64_t n, uint64_t chunk, uint32_t P, const TsOrderState &st, hipStream_t s);
 
+// Partitioner (KTA_FLAG_PARTITIONER, kta_partitioner.hip): the live vector u64[2 P + 2 Q] = [P][2] checked, placed |
+// [Q][2] target_records, target_bytes, every word a sum that the workgroups of launch_partitioner add their LDS counters to.
+constexpr uint32_t kPartitionerMaxPartitions = 4096;        // P and Q each: 8 P + 12 Q bytes of LDS, 80 KiB up there
+constexpr uint64_t kPartitionerLaunchMax = 1ull << 30;      // records per launch: the u32 fields in LDS cannot overflow
+inline size_t partitioner_len(uint32_t P, uint32_t Q) { return 2 * (size_t)P + 2 * (size_t)Q; }
+struct PartitionerColumns {
+    SketchColumns k;            // what the key sketch reads
+    const int32_t *val_len;     // the batch's record 0, plain i32 (both layouts), as k.key_len
+};
+// the pass over records [0, n) of c, n <= kPartitionerLaunchMax; stats: u64[3] += keyed records, LDS adds to the partition
+// words, LDS adds to the target words (after combining); *workgroups = the grid
+hipError_t launch_partitioner(const PartitionerColumns &c, uint64_t n, uint32_t P, uint32_t Q, uint64_t *acc, uint64_t *stats,
+                              int cu_count, uint32_t *workgroups, hipStream_t s);
+// out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P and Q (kta_partitioner_info)
+void partitioner_lds_plan(uint32_t P, uint32_t Q, uint32_t out[3]);
+
 } // namespace kta

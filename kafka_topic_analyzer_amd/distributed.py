@@ -98,6 +98,14 @@ def allreduce_ts_order_vector(ovec, n_partitions: int, group=None) -> None:
     _allreduce_sum_max(ovec, 2 * n_partitions + 64, group)
 
 
+def allreduce_partitioner_vector(pvec, n_partitions: int, repartition: int, group=None) -> None:
+    """In-place exchange of an int64 view of the partitioner SNAPSHOT (kta_partitioner_result_vector: device tensor, or a CPU
+    tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_PARTITIONER: all-reduce SUM over
+    all of its 2 P + 2 Q words (i64 wrap == u64 wrap).  Every rank must have the same Q."""
+    assert pvec.numel() == 2 * n_partitions + 2 * repartition
+    _allreduce_sum_max(pvec, pvec.numel(), group)
+
+
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
