@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the record filter (kta_set_filter, kta_filter_info, kta_set_filter_slice, kta_filter_host, kta_filter_tile_host, kta_render_filter), only added entry points; the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -263,6 +263,31 @@ typedef struct kta_hot_key {
  * kta_set_repartition a Q above it. */
 #define KTA_FLAG_PARTITIONER 0x40u   /* 64: bit 6 */
 
+/* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
+ * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
+ * both hold:
+ *   - its partition is in the set, when a set is given; a partition outside [0, P) is in no set;
+ *   - from_ms <= ts_ms < to_ms, when a bound is given (INT64_MIN / INT64_MAX: no bound on that side): the comparison is on
+ *     the raw i64 milliseconds, before any / 1000.  A record with ts_ms == -1 (not available) fails as soon as either
+ *     bound is set; without bounds it passes.
+ * Without a set, a record whose partition is outside [0, P) passes the partition test, and is counted and reported as a
+ * bad partition exactly as without a filter.
+ * THE CONTRACT: for every handler and every opt-in pass, a filtered context is left in exactly the state of an unfiltered
+ * context that was handed only the passing records — in the same order, with the same sequence numbers (a record keeps
+ * the seq it had: its seq column's, or base_seq + its index in the batch it came in).  That covers the counter vector and
+ * the alive set in both states, KTA_G_RECORDS and the extrema included, every opt-in result vector, and
+ * KTA_ERR_TIMESTAMP_RANGE / KTA_ERR_BAD_PARTITION: a record that is filtered out can cause neither.
+ * How: every submission path (the staging ring behind kta_batch_submit, kta_handle_message and kta_replay_messages;
+ * kta_submit_device[_ex]; the Kafka decode) ends in one function, and there a filtered context compacts the batch in
+ * record order into a scratch batch of its own (raw layout, keys zero-copy) before the existing passes, which are
+ * unchanged, see a shorter batch.  The batch is taken in slices of at most 2^26 records; a slice costs three launches
+ * (count per 1024-record tile, prefix of the counts, scatter) and ONE HOST WAIT on the compute stream, for the prefix's
+ * total: the plans of the passes behind need the record count on the host.  A filtered submit is therefore not
+ * asynchronous.  A tile of a kta_device_batch_alloc allocation is decided from its 24 bytes of header and summary
+ * (kta_tile_sum) where they say that none or all of its records pass; a slice of which nothing passes launches nothing
+ * more, and one of which everything passes is handed on as it is (neither is scattered).  The scratch batch grows to the largest slice seen (20 B per record, 24 with
+ * key columns, 8 more in the table state).  Without a filter nothing is launched, allocated or waited for. */
+
 /* One batch of decoded records as struct-of-arrays columns.  What the reference's
  * handlers read from a BorrowedMessage (metric.rs:208-209, 218, 233, 291-293):
  *   partition[i]  m.partition()                                          i32
@@ -445,6 +470,29 @@ int kta_batch_tile_summaries(kta_ctx *ctx, const kta_batch *device_cols, uint64_
  * kta_kafka_decode_device only.  key_off, key_bytes and seq are plain in both layouts. */
 int kta_copy_to_device(kta_ctx *ctx, void *dst_device, const void *src_host, size_t bytes);
 int kta_copy_to_host(kta_ctx *ctx, void *dst_host, const void *src_device, size_t bytes);
+
+/* ---- record filter (definition above kta_batch) ---------------------------------------------------------------- */
+/* from_ms == INT64_MIN / to_ms == INT64_MAX: no bound on that side.  partition_bitmap == NULL: all partitions; else bit
+ * p & 31 of word p / 32 is partition p, n_words >= 1 words are read, and a bit at or beyond P is KTA_ERR_INVALID, as is
+ * from_ms >= to_ms and a set on a context of more than 2^19 partitions.  Neither bound and no set: the context has no
+ * filter (again).  Accepted only while the context has been handed no record since kta_create / kta_reset, as
+ * kta_set_timeline is; kta_reset keeps the filter and zeroes kta_filter_info's counts. */
+int kta_set_filter(kta_ctx *ctx, int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_words);
+/* Since kta_create / kta_reset (staged messages are flushed first): out[0] records seen, out[1] records passed, out[2]
+ * tiles decided by their summary as "none passes", out[3] tiles decided by their summary as "all pass", out[4] tiles
+ * read record by record, out[5] slices.  All zero on a context without a filter. */
+int kta_filter_info(kta_ctx *ctx, uint64_t out[6]);
+/* Tuning and tests: the records of a slice, a multiple of 1024, at most 2^26 (0: the default, 2^26). */
+int kta_set_filter_slice(kta_ctx *ctx, uint64_t records);
+/* The same predicate over HOST columns (host only, no context, no device): the indices of the passing records of
+ * [0, n), ascending, to indices_out (may be NULL: count only) and their number to *n_out.  A bitmap has at least
+ * ceil(n_partitions / 32) words. */
+int kta_filter_host(const int32_t *partition, const int64_t *ts_ms, uint64_t n, uint32_t n_partitions, int64_t from_ms, int64_t to_ms,
+                    const uint32_t *partition_bitmap, uint32_t n_words, uint64_t *indices_out, uint64_t *n_out);
+/* What one tile's header and summary decide (host only): 0 the tile's records are read, 1 none passes, 2 all pass; negative:
+ * an error.  whole: the tile's 1024 records all belong to the slice. */
+int kta_filter_tile_host(uint32_t n_partitions, int64_t from_ms, int64_t to_ms, int has_partition_set, const kta_tile_hdr *hdr,
+                         const kta_tile_sum *sum, int whole);
 
 /* Run the context's kernels on a caller-owned HIP stream (e.g. the stream RCCL collectives are issued
  * on), so that submit -> collective -> next submit needs no host synchronisation.  NULL restores the
@@ -817,6 +865,19 @@ int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32
  * Output buffer conventions as kta_render_report. */
 int kta_render_partitioner(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, uint32_t q, char *out,
                            size_t out_cap, size_t *out_len);
+/* The section kta-analyzer prints after everything else when a filter was given (--librdkafka kta.from=<epoch seconds>,
+ * kta.to=<epoch seconds>, kta.partitions=0,3-5); not part of the reference report:
+ *   `Record filter: everything above describes the records that passed, and no others (kta.from, kta.to, kta.partitions;
+ *    not part of the reference report)`;
+ *   a table (Filter | Value) with the rows `From (timestamp >=)` and `To (timestamp <)` — `<seconds> s (<ms> ms)`, with
+ *    three decimals where the bound is not a whole second, `-` without the bound —, `Partitions` — the set as ascending
+ *    ranges `0,3-5`, `all` without one, `none` for the empty set —, `Records seen`, `Records passed` (kta_filter_info's
+ *    first two words, summed over the ranks of a sharded run) and `Passed %` (two decimals; `-` when nothing was seen);
+ *   a closing `=` rule.
+ * partition_bitmap: NULL, or ceil(n_partitions / 32) words as kta_set_filter takes them.  Output buffer conventions as
+ * kta_render_report. */
+int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
+                      uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 
 /* ---- profiling hooks --------------------------------------------------------------- */
 /* With kta_set_timing(ctx, 1) every kernel launch is bracketed by a pair of HIP events recorded

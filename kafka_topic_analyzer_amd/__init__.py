@@ -546,6 +546,27 @@ class HipMetricHandler:
         self._check(self._lib.kta_partitioner_info(self._ctx, C.byref(out)))
         return dict(zip(("keyed_records", "launches", "partition_adds", "target_adds", "workgroups", "lds_bytes"), (int(x) for x in out)))
 
+    def set_filter(self, from_ms: Optional[int] = None, to_ms: Optional[int] = None, partitions=None) -> None:
+        """Analyse only the records with from_ms <= ts_ms < to_ms (None: no bound on that side) whose partition is one of
+        `partitions` (None: all).  Only before the first record; reset() keeps it (kta_set_filter).  All None: no filter."""
+        bitmap, words = None, 0
+        if partitions is not None:
+            bitmap = partition_bitmap(partitions, self.n_partitions)
+            words = len(bitmap)
+        self._check(self._lib.kta_set_filter(self._ctx, N.KTA_FILTER_NO_FROM if from_ms is None else int(from_ms),
+                                             N.KTA_FILTER_NO_TO if to_ms is None else int(to_ms),
+                                             None if bitmap is None else _np_ptr(bitmap), words))
+
+    def set_filter_slice(self, records: int) -> None:
+        """Tuning / tests: the filter's slice, a multiple of 1024 records (0: the default)."""
+        self._check(self._lib.kta_set_filter_slice(self._ctx, records))
+
+    def filter_info(self) -> dict:
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_filter_info(self._ctx, C.byref(out)))
+        return {"seen": int(out[0]), "passed": int(out[1]), "tiles_summary_none": int(out[2]), "tiles_summary_all": int(out[3]),
+                "tiles_read": int(out[4]), "slices": int(out[5])}
+
     def alive_export_entries(self) -> Tuple[int, int, int]:
         """(device ptr slots u32[n], device ptr values u64[n], n): the entries ever written."""
         ps, pv, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
@@ -934,6 +955,15 @@ def render_partitioner(vec, counter_vec, n_partitions: int, repartition: int) ->
     return _render(N.load().kta_render_partitioner, _np_ptr(v), _np_ptr(c), n_partitions, repartition)
 
 
+def render_filter(n_partitions: int, seen: int, passed: int, from_ms: Optional[int] = None, to_ms: Optional[int] = None,
+                  partitions=None) -> str:
+    """kta_render_filter: the section kta-analyzer prints after everything else with --librdkafka kta.from / kta.to /
+    kta.partitions, from the filter as given and the first two counts of filter_info()."""
+    bm = None if partitions is None else partition_bitmap(partitions, n_partitions)
+    return _render(N.load().kta_render_filter, N.KTA_FILTER_NO_FROM if from_ms is None else int(from_ms),
+                   N.KTA_FILTER_NO_TO if to_ms is None else int(to_ms), None if bm is None else _np_ptr(bm), n_partitions, seen, passed)
+
+
 def partitioner_max_partitions() -> int:
     """The largest P, and the largest Q, of a context with the partitioner pass."""
     return int(N.load().kta_partitioner_max_partitions())
@@ -943,6 +973,36 @@ def murmur2(key: bytes) -> int:
     """Kafka's murmur2 of `key` as a u32 (kta_murmur2; host only)."""
     key = bytes(key)
     return int(N.load().kta_murmur2(key, len(key)))
+
+
+def partition_bitmap(partitions, n_partitions: int) -> np.ndarray:
+    """The u32 bitmap kta_set_filter and kta_filter_host take: bit p & 31 of word p // 32 for every p of `partitions`.
+    A partition outside [0, 2^32) cannot be written down and raises; one at or beyond n_partitions is the library's to refuse."""
+    ps = [int(p) for p in partitions]
+    if any(p < 0 or p >= 2**32 for p in ps):
+        raise ValueError("a partition of a filter's set must be >= 0")
+    words = max((n_partitions + 31) // 32, max(ps, default=0) // 32 + 1, 1)
+    bm = np.zeros(words, dtype=np.uint32)
+    for p in ps:
+        bm[p // 32] |= np.uint32(1 << (p % 32))
+    return bm
+
+
+def filter_host(partition, ts_ms, n_partitions: int, from_ms: Optional[int] = None, to_ms: Optional[int] = None,
+                partitions=None) -> np.ndarray:
+    """The indices of the records that a filter passes, ascending (kta_filter_host: the library's own predicate on the host)."""
+    lib = N.load()
+    p = np.ascontiguousarray(partition, dtype=np.int32)
+    t = np.ascontiguousarray(ts_ms, dtype=np.int64)
+    bm = None if partitions is None else partition_bitmap(partitions, n_partitions)
+    idx = np.zeros(len(p), dtype=np.uint64)
+    m = C.c_uint64(0)
+    rc = lib.kta_filter_host(_np_ptr(p), _np_ptr(t), len(p), n_partitions, N.KTA_FILTER_NO_FROM if from_ms is None else int(from_ms),
+                             N.KTA_FILTER_NO_TO if to_ms is None else int(to_ms), None if bm is None else _np_ptr(bm),
+                             0 if bm is None else len(bm), _np_ptr(idx), C.byref(m))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_filter_host")
+    return idx[:m.value].copy()
 
 
 def ts_order_max_partitions() -> int:

@@ -85,6 +85,8 @@ KTA_TILE_RAW, KTA_TILE_COMPACT = 0, 1             # kta_tile_hdr.mode
 KTA_TILE_LENS_I32, KTA_TILE_LENS_U16 = 0, 1        # kta_tile_hdr.lens
 KTA_TILE_SUM_VALID, KTA_TILE_SUM_TIMED, KTA_TILE_SUM_UNTIMED = 1, 2, 4   # kta_tile_sum.flags
 KTA_COMPACT_PART_NONE = 0xFFFF
+KTA_FILTER_NO_FROM, KTA_FILTER_NO_TO = -2**63, 2**63 - 1   # kta_set_filter: no bound on that side (INT64_MIN / INT64_MAX)
+KTA_FILTER_TILE_READ, KTA_FILTER_TILE_NONE, KTA_FILTER_TILE_ALL = 0, 1, 2   # kta_filter_tile_host
 
 
 class KtaTileSum(C.Structure):
@@ -221,8 +223,16 @@ SIGNATURES = {
     "kta_partitioner_max_partitions": (C.c_int, []),
     "kta_partitioner_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
     "kta_murmur2": (C.c_uint32, [C.c_void_p, C.c_size_t]),
+    "kta_set_filter": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32]),
+    "kta_filter_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_set_filter_slice": (C.c_int, [_P, C.c_uint64]),
+    "kta_filter_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32,
+                                  C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kta_filter_tile_host": (C.c_int, [C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "kta_render_partitioner": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
                                          C.POINTER(C.c_size_t)]),
+    "kta_render_filter": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
     "kta_render_distinct_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
     "kta_export_alive_bitmap": (C.c_int, [_P, C.c_void_p]),

@@ -43,6 +43,12 @@
 // reference counterpart) and prints, last of all, how many keyed records lie on the partition Kafka's default partitioner
 // gives their key, and how the keyed records and bytes would spread over Q partitions: kta.repartition=Q (a decimal in
 // [1, kta_partitioner_max_partitions()]; needs kta.partitioner), P when it is not given.
+// kta.from=<epoch seconds>, kta.to=<epoch seconds> (the unit of kta.timeline.start) and kta.partitions=0,3-5 (every source,
+// kta.per_message=1 and kta.gpus=N included: every rank gets the same filter) analyse only the records with
+// from <= timestamp < to of the partitions named (kta_set_filter): the report and every opt-in section describe those
+// records and no others, and one more section after everything else says what the filter was and how many records it
+// was shown and let pass (summed over the ranks).  The items of kta.partitions are separated by commas, which also separate
+// --librdkafka's pairs: a piece without '=' that follows kta.partitions and is a number or a range belongs to it.
 // kta.hot_keys=K (1 <= K <= 64; every source, kta.gpus=N included) keeps the hot-key sketch as well (KTA_FLAG_HOT_KEYS; no
 // reference counterpart) and prints, last of all, the at most K keys that hold 1/512 of the keyed records and more, with
 // bounds on their records and, where the device caught one, the key's bytes (with kta.gpus=N from the lowest rank that
@@ -93,6 +99,41 @@ int64_t parse_decimal(const std::string &v, size_t digits)
         if (ch < '0' || ch > '9') return -1;
     return strtoll(v.c_str(), nullptr, 10);
 }
+
+// kta.from / kta.to / kta.partitions as kta_set_filter takes them
+struct FilterConfig {
+    bool on = false, has_set = false;
+    int64_t from_ms = INT64_MIN, to_ms = INT64_MAX;
+    std::vector<uint32_t> bitmap;   // ceil(P / 32) words
+};
+
+bool is_partition_item(const std::string &v)
+{
+    if (v.empty()) return false;
+    for (char ch : v)
+        if ((ch < '0' || ch > '9') && ch != '-') return false;
+    return true;
+}
+
+// kta.partitions=0,3-5: numbers and inclusive ranges below P; false when malformed
+bool parse_partitions(const std::string &v, uint32_t P, std::vector<uint32_t> *bitmap)
+{
+    bitmap->assign((P + 31u) / 32u, 0u);
+    size_t pos = 0;
+    while (true) {
+        const size_t comma = v.find(',', pos);
+        const std::string item = v.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+        const size_t dash = item.find('-');
+        const int64_t lo = parse_decimal(item.substr(0, dash), 9);
+        const int64_t hi = dash == std::string::npos ? lo : parse_decimal(item.substr(dash + 1), 9);
+        if (lo < 0 || hi < lo || hi >= (int64_t)P) return false;
+        for (int64_t p = lo; p <= hi; p++) (*bitmap)[(size_t)p >> 5] |= 1u << (p & 31);
+        if (comma == std::string::npos) return true;
+        pos = comma + 1;
+    }
+}
+
+void apply_filter(kta_ctx *ctx, const FilterConfig &f);
 
 // key_non_null of partitions [0, P): the keyed records of the kta.distinct_keys section
 std::vector<uint64_t> keyed_records(const kta::MessageMetrics &m, uint32_t P)
@@ -222,12 +263,20 @@ std::map<std::string, std::string> parse_librdkafka(const Args &a)
     if (!a.has_librdkafka) return m;
     size_t pos = 0;
     const std::string &s = a.librdkafka;
+    std::string last_key;
     while (true) {
         size_t comma = s.find(',', pos);
         std::string kv = s.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
         size_t eq = kv.find('=');
+        if (eq == std::string::npos && last_key == "kta.partitions" && is_partition_item(kv)) {   // kta.partitions=0,3-5: the next item
+            m[last_key] += "," + kv;
+            if (comma == std::string::npos) break;
+            pos = comma + 1;
+            continue;
+        }
         if (eq == std::string::npos)
             rust_panic("called `Option::unwrap()` on a `None` value", "src/main.rs:89:48");
+        last_key = kv.substr(0, eq);
         size_t eq2 = kv.find('=', eq + 1);
         m[kv.substr(0, eq)] = kv.substr(eq + 1, eq2 == std::string::npos ? std::string::npos : eq2 - eq - 1);
         if (comma == std::string::npos) break;
@@ -242,6 +291,11 @@ void check(int rc, kta_ctx *ctx, const char *what)
         fprintf(stderr, "%s failed: %s\n", what, kta_last_error(ctx));
         exit(2);
     }
+}
+
+void apply_filter(kta_ctx *ctx, const FilterConfig &f)
+{
+    if (f.on) check(kta_set_filter(ctx, f.from_ms, f.to_ms, f.has_set ? f.bitmap.data() : nullptr, (uint32_t)f.bitmap.size()), ctx, "kta_set_filter");
 }
 
 // ---- kta.gpus=N: one rank per GPU ------------------------------------------------------------------------
@@ -260,6 +314,7 @@ struct ShardedJob {
     bool ts_order = false;                             // kta.ts_order=1: likewise (a partition's records stay on one rank)
     bool partitioner = false;                          // kta.partitioner=murmur2: likewise
     uint32_t repartition = 0;                          //   kta.repartition=Q (0: P)
+    FilterConfig filter;                               // kta.from / kta.to / kta.partitions: the same on every rank
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -268,7 +323,7 @@ struct ShardedJob {
 
 // What one rank consumes: the partitions p with p % nranks == rank, every record with its GLOBAL sequence
 // number (the position the single-GPU run consumes it at), then the exchange.
-void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta::HipMetricHandler **out)
+void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta::HipMetricHandler **out, int64_t *filter_counts /* [2] */)
 {
     try {
         // a rank's records are not consecutive in consumption order: global sequence numbers, table state
@@ -280,6 +335,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
         kta_ctx *ctx = h->ctx();
+        apply_filter(ctx, job.filter);
         h->comm_create(job.nranks, rank, uid);
         if (job.synthetic) {
             // every rank enumerates the whole topic in consumption order and keeps its partitions
@@ -340,6 +396,12 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
             }
         }
         h->exchange(!job.synthetic);
+        if (job.filter.on) {   // records seen and passed, summed over the ranks
+            uint64_t info[6];
+            check(kta_filter_info(ctx, info), ctx, "kta_filter_info");
+            filter_counts[0] = (int64_t)info[0], filter_counts[1] = (int64_t)info[1];
+            check(kta_comm_allreduce_i64(ctx, filter_counts, 2, 0), ctx, "kta_comm_allreduce_i64");
+        }
         *out = h;
     } catch (const kta::RustPanic &p) {
         // Every rank sees the job's extrema after the exchange, so all of them end here — and exit() is not to be
@@ -380,7 +442,8 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
     fflush(stdout);
     std::vector<kta::HipMetricHandler *> handlers(job.nranks, nullptr);
     std::vector<std::thread> threads;
-    for (int r = 0; r < job.nranks; r++) threads.emplace_back(run_rank, std::cref(job), r, uid, ndev, &handlers[r]);
+    std::vector<int64_t> filter_counts(2 * (size_t)job.nranks, 0);
+    for (int r = 0; r < job.nranks; r++) threads.emplace_back(run_rank, std::cref(job), r, uid, ndev, &handlers[r], &filter_counts[2 * (size_t)r]);
     for (auto &t : threads) t.join();
     if (g_rank_panicked) rust_panic(g_rank_panic_msg, g_rank_panic_loc);           // once, from the main thread
     fprintf(stderr, "done\n");                                                     // kafka.rs:136 (spinner)
@@ -429,6 +492,9 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         }
         if (job.partitioner)
             text += kta::render_partitioner(h0->partitioner()->data(), partitioner_counters(metrics, job.P).data(), job.P, h0->repartition());
+        if (job.filter.on)
+            text += kta::render_filter(job.filter.from_ms, job.filter.to_ms, job.filter.has_set ? job.filter.bitmap.data() : nullptr, job.P,
+                                       (uint64_t)filter_counts[0], (uint64_t)filter_counts[1]);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -624,6 +690,29 @@ int main(int argc, char **argv)
         timeline = kta::TimelineConfig{origin, width, (uint32_t)n};
     }
 
+    FilterConfig filter;   // kta.from / kta.to / kta.partitions: refused here, before any context, when malformed
+    for (const char *key : {"kta.from", "kta.to"}) {
+        if (!cfg.count(key)) continue;
+        const int64_t sec = parse_decimal(cfg[key], 15);
+        if (sec < 0) {
+            fprintf(stderr, "%s=%s: expected unix seconds >= 0\n", key, cfg[key].c_str());
+            return 2;
+        }
+        (key[4] == 'f' ? filter.from_ms : filter.to_ms) = sec * 1000;
+        filter.on = true;
+    }
+    if (filter.from_ms >= filter.to_ms) {
+        fprintf(stderr, "kta.from=%s,kta.to=%s: expected kta.from below kta.to\n", cfg["kta.from"].c_str(), cfg["kta.to"].c_str());
+        return 2;
+    }
+    if (cfg.count("kta.partitions")) {
+        if (!parse_partitions(cfg["kta.partitions"], P, &filter.bitmap)) {
+            fprintf(stderr, "kta.partitions=%s: expected partitions and ranges of the topic's %u, such as 0,3-5\n", cfg["kta.partitions"].c_str(), P);
+            return 2;
+        }
+        filter.on = filter.has_set = true;
+    }
+
     // librdkafka options are forwarded as in the reference (kafka.rs:38-42); the one this build can
     // honour for raw segments is check.crcs (default false): verify every batch's CRC-32C on the GPU
     const bool check_crcs = cfg.count("check.crcs") && cfg["check.crcs"] == "true";
@@ -700,6 +789,7 @@ int main(int argc, char **argv)
         job.ts_order = ts_order;
         job.partitioner = partitioner;
         job.repartition = repartition;
+        job.filter = filter;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -725,6 +815,7 @@ int main(int argc, char **argv)
         return 2;
     }
     kta_ctx *ctx = handler->ctx();
+    apply_filter(ctx, filter);
     if (segment) check(kta_kafka_set_check_crcs(ctx, check_crcs ? 1 : 0), ctx, "kta_kafka_set_check_crcs");
 
     if (!kafka) {
@@ -899,6 +990,11 @@ int main(int argc, char **argv)
         if (hot_keys) text += kta::render_hot_keys(handler->hot_keys()->data(), handler->hot_key_exemplars()->data(), hot_keys);
         if (partitioner)
             text += kta::render_partitioner(handler->partitioner()->data(), partitioner_counters(metrics, P).data(), P, handler->repartition());
+        if (filter.on) {
+            uint64_t info[6];
+            check(kta_filter_info(ctx, info), ctx, "kta_filter_info");
+            text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, info[0], info[1]);
+        }
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -204,5 +204,8 @@ std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exempla
 // the opt-in section kta-analyzer prints last of all with kta.partitioner=murmur2 (kta_render_partitioner): vec
 // u64[2 P + 2 Q], counters u64[P * 7 + 8] (the counter vector of the same records; its globals are not read)
 std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q);
+// the section kta-analyzer prints after everything else when a filter was given (kta.from, kta.to, kta.partitions;
+// kta_render_filter): bitmap null or ceil(P / 32) words as kta_set_filter takes them; the counts are kta_filter_info's
+std::string render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *bitmap, uint32_t P, uint64_t seen, uint64_t passed);
 
 }  // namespace kta

@@ -370,6 +370,56 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
     return o;
 }
 
+// The section of a filtered run (kta.from, kta.to, kta.partitions): no reference counterpart, printed after everything else.
+// The filter as given — bounds in epoch seconds as the keys take them, the set as ascending ranges — then the records
+// the run was handed and the records that passed.  bitmap null: no set; else ceil(P / 32) words (kta_set_filter).
+std::string render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *bitmap, uint32_t P, uint64_t seen, uint64_t passed)
+{
+    auto bound = [](int64_t ms) {
+        std::string t = std::to_string(ms / 1000);
+        if (ms % 1000) {                                    // (set through the library, not the keys: whole milliseconds)
+            char buf[8];
+            snprintf(buf, sizeof buf, ".%03d", (int)((ms % 1000 + 1000) % 1000));
+            t += buf;
+        }
+        return t + " s (" + std::to_string(ms) + " ms)";
+    };
+    std::string set = "all";
+    if (bitmap) {
+        set.clear();
+        for (uint32_t p = 0; p < P;) {
+            if (!((bitmap[p >> 5] >> (p & 31u)) & 1u)) { p++; continue; }
+            uint32_t q = p;
+            while (q + 1 < P && ((bitmap[(q + 1) >> 5] >> ((q + 1) & 31u)) & 1u)) q++;
+            if (!set.empty()) set += ",";
+            set += std::to_string(p);
+            if (q > p) set += "-" + std::to_string(q);
+            p = q + 1;
+        }
+        if (set.empty()) set = "none";
+    }
+    std::string share = "-";
+    if (seen) {
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", (double)passed * 100.0 / (double)seen);
+        share = buf;
+    }
+    std::string o;
+    o += "Record filter: everything above describes the records that passed, and no others "
+         "(kta.from, kta.to, kta.partitions; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"Filter", "Value"});
+    rows.push_back({"From (timestamp >=)", from_ms == INT64_MIN ? "-" : bound(from_ms)});
+    rows.push_back({"To (timestamp <)", to_ms == INT64_MAX ? "-" : bound(to_ms)});
+    rows.push_back({"Partitions", set});
+    rows.push_back({"Records seen", std::to_string(seen)});
+    rows.push_back({"Records passed", std::to_string(passed)});
+    rows.push_back({"Passed %", share});
+    o += pretty_table(rows);
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
 static uint32_t fmix32(uint32_t x)
 {
@@ -470,6 +520,20 @@ extern "C" int kta_render_partitioner(const uint64_t *vec, const uint64_t *count
     const uint32_t lim = (uint32_t)kta_partitioner_max_partitions();
     if (!vec || !counter_vec || !out_len || n_partitions == 0 || n_partitions > lim || q == 0 || q > lim) return KTA_ERR_INVALID;
     const std::string text = kta::render_partitioner(vec, counter_vec, n_partitions, q);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
+                                 uint64_t passed, char *out, size_t out_cap, size_t *out_len)
+{
+    if (!out_len || n_partitions == 0 || from_ms >= to_ms) return KTA_ERR_INVALID;
+    const std::string text = kta::render_filter(from_ms, to_ms, partition_bitmap, n_partitions, seen, passed);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

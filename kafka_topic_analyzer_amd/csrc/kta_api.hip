@@ -93,6 +93,19 @@ struct kta_ctx {
     uint32_t part_q = 0;
     DeviceBuf<uint64_t> d_part, d_part_out, d_part_stats;
     uint64_t part_launches = 0, part_workgroups = 0;
+    // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
+    // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
+    // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
+    bool filter = false;
+    kta::FilterSpec filter_spec{INT64_MIN, INT64_MAX, 0, 0};
+    uint64_t filter_slice = kta::kFilterSlice;
+    DeviceBuf<uint32_t> d_filter_bitmap, d_filter_count;
+    DeviceBuf<uint64_t> d_filter_offset, d_filter_stats;
+    PinnedBuf<uint64_t> h_filter_total;
+    uint64_t *d_filter_total = nullptr;   // h_filter_total as the device addresses it
+    DeviceBuf<uint8_t> d_filter_scratch;
+    kta_batch filter_scratch{};      // column pointers into d_filter_scratch
+    uint64_t filter_seen = 0, filter_passed = 0, filter_slices = 0;
     DeviceBuf<uint64_t> d_vec;      // u64[P*7 + KTA_NGLOBALS]: the live accumulator
     DeviceBuf<uint64_t> d_vec_out;  // its snapshot (kta_finish_device): what kta_result_vector hands out and the
                                     // exchange reduces in place — the accumulator itself is never reduced
@@ -390,7 +403,7 @@ int grow_alive_workspace(kta_ctx *ctx, const kta::AlivePartitionPlan &pl)
 }
 
 // Launch the handlers over device-resident columns on the compute stream.
-int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
+int run_handlers(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
 {
     if (n == 0) return KTA_OK;
     const kta::TimelineArgs *tl = ctx->timeline ? &ctx->tl : nullptr;
@@ -585,6 +598,100 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     return KTA_OK;
 }
 
+// The scratch batch of the filter, large enough for `cap` records: partition, key_len, val_len, ts_ms, and key_off / seq
+// where the context reads them (released, after the compute stream has drained, before it is allocated again).
+int grow_filter_scratch(kta_ctx *ctx, uint64_t cap, bool keys, bool seq)
+{
+    kta_batch &b = ctx->filter_scratch;
+    if (b.capacity >= cap && (!keys || b.key_off) && (!seq || b.seq)) return KTA_OK;
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    cap = (cap + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS * KTA_TILE_RECORDS;
+    memset(&b, 0, sizeof b);
+    const size_t c4 = pad16(cap * 4), c8 = pad16(cap * 8);
+    KTA_HIP(ctx, ctx->d_filter_scratch.alloc(3 * c4 + c8 + (keys ? c4 : 0) + (seq ? c8 : 0)));
+    uint8_t *base = ctx->d_filter_scratch.get();
+    b.ts_ms = reinterpret_cast<int64_t *>(base), base += c8;
+    if (seq) b.seq = reinterpret_cast<uint64_t *>(base), base += c8;
+    b.partition = reinterpret_cast<int32_t *>(base), base += c4;
+    b.key_len = reinterpret_cast<int32_t *>(base), base += c4;
+    b.val_len = reinterpret_cast<int32_t *>(base), base += c4;
+    if (keys) b.key_off = reinterpret_cast<uint32_t *>(base);
+    b.capacity = cap;
+    return KTA_OK;
+}
+
+// A filtered context's batch (kta_set_filter): slice by slice, the passing records are compacted in order into the scratch
+// batch — count per tile, prefix, ONE host wait for the slice's total, because the plans of the passes behind need the
+// record count on the host, then the scatter — and the handlers get the scratch batch.  A slice nothing of which passes
+// launches nothing more; a slice all of which passes is handed on as it is, as a view at its record offset, unscattered.
+int run_filtered_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
+{
+    if (!c->partition || !c->key_len || !c->val_len || !c->ts_ms) return fail(ctx, KTA_ERR_INVALID, "metric columns missing (the filter reads them)");
+    if (!aligned16(c->partition) || !aligned16(c->key_len) || !aligned16(c->val_len) || !aligned16(c->ts_ms))
+        return fail(ctx, KTA_ERR_INVALID, "device columns must be 16-byte aligned");
+    const bool keys = c->key_off && c->key_bytes;
+    const bool seq = ctx->alive && ctx->alive_table;
+    kta_internal_columns rb{};
+    int rc = kta_internal_resolve(ctx, c, &rb);
+    if (rc != KTA_OK) return rc;
+    if (rb.rows && rb.rec0 + n > rb.rows) return fail(ctx, KTA_ERR_INVALID, "the batch ends behind its allocation");
+    if (!ctx->d_filter_count) {
+        KTA_HIP(ctx, ctx->d_filter_count.alloc(kta::kFilterCountWords));
+        KTA_HIP(ctx, ctx->d_filter_offset.alloc(kta::kFilterMaxTiles + 1));
+        KTA_HIP(ctx, ctx->h_filter_total.alloc(1));
+        KTA_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&ctx->d_filter_total), ctx->h_filter_total.get(), 0));
+    }
+    // a hand-built tile-compact batch (its own tile_hdr) has no views: only its first slice can be handed on as it is
+    const bool viewable = !rb.hdr || rb.rows != 0;
+    ctx->handed_records = true;
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < ctx->filter_slice ? n - at : ctx->filter_slice;
+        rc = grow_filter_scratch(ctx, take, keys, seq);
+        if (rc != KTA_OK) return rc;
+        const kta_internal_columns r = columns_at(rb, at);
+        const kta_batch &sb = ctx->filter_scratch;
+        const kta::FilterSource src{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.sum, r.hdr ? r.rec0 : 0,
+                                    keys ? c->key_off + at : nullptr, c->seq ? c->seq + at : nullptr, base_seq + at};
+        const kta::FilterDest dst{sb.partition, sb.key_len, sb.val_len, sb.ts_ms, keys ? sb.key_off : nullptr, seq ? sb.seq : nullptr, sb.capacity};
+        const kta::FilterWorkspace ws{ctx->d_filter_count.get(), ctx->d_filter_offset.get(), ctx->d_filter_stats.get(), ctx->d_filter_total};
+        KTA_HIP(ctx, kta::launch_filter_count(src, take, ctx->filter_spec, ctx->d_filter_bitmap.get(), ws, ctx->s_compute));
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // the one wait of the slice: the prefix kernel wrote the total to pinned memory
+        const uint64_t m = *static_cast<volatile uint64_t *>(ctx->h_filter_total.get());
+        if (m > take || m > sb.capacity) return fail(ctx, KTA_ERR_CAPACITY, "filter: a slice's total exceeds the scratch batch");
+        ctx->filter_seen += take, ctx->filter_passed += m, ctx->filter_slices++;
+        const bool hand_on = m == take && (viewable || at == 0);
+        if (m && !hand_on)
+            KTA_HIP(ctx, kta::launch_filter_scatter(src, take, ctx->filter_spec, ctx->d_filter_bitmap.get(), ws, dst, ctx->s_compute));
+        if (hand_on) {
+            kta_batch v = *c;
+            if (at) {
+                v.partition += at, v.key_len += at, v.val_len += at, v.ts_ms += at;
+                if (v.key_off) v.key_off += at;
+                if (v.seq) v.seq += at;
+                v.capacity = c->capacity > at ? c->capacity - at : 0;
+            }
+            rc = run_handlers(ctx, &v, take, base_seq + at, which);
+        } else if (m) {
+            kta_batch v = sb;
+            v.key_bytes = keys ? c->key_bytes : nullptr;
+            v.key_bytes_capacity = c->key_bytes_capacity;
+            rc = run_handlers(ctx, &v, m, base_seq + at, which);
+        }
+        if (rc != KTA_OK) return rc;
+        at += take;
+    }
+    return KTA_OK;
+}
+
+// Every submission path ends here: the staging ring (kta_batch_submit, and through it kta_handle_message, kta_flush and
+// kta_replay_messages), kta_submit_device[_ex] and, through that, the Kafka decode.  Without a filter nothing is added.
+int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
+{
+    if (n == 0) return KTA_OK;
+    if (!ctx->filter) return run_handlers(ctx, c, n, base_seq, which);
+    return run_filtered_batch(ctx, c, n, base_seq, which);
+}
+
 int reset_state(kta_ctx *ctx)
 {
     KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec.get(), ctx->P, ctx->d_avec.get(), ctx->s_compute));
@@ -613,6 +720,8 @@ int reset_state(kta_ctx *ctx)
         ctx->part_launches = ctx->part_workgroups = 0;
     }
     ctx->handed_records = false;
+    if (ctx->d_filter_stats) KTA_HIP(ctx, hipMemsetAsync(ctx->d_filter_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
+    ctx->filter_seen = ctx->filter_passed = ctx->filter_slices = 0;   // (the filter itself stays)
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_HIP(ctx, hipMemsetAsync(ctx->d_table.get(), 0, kta::kAliveSlots * sizeof(uint64_t), ctx->s_compute));
@@ -1796,6 +1905,87 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
     kta::partitioner_lds_plan(ctx->P, ctx->part_q, plan);
     out[0] = st[0], out[1] = ctx->part_launches, out[2] = st[1], out[3] = st[2], out[4] = ctx->part_workgroups, out[5] = plan[0];
     return rc;
+}
+
+// ---- record filter (kta_filter.h holds the rules, kta_filter.hip the kernels) ------------------------------------------
+
+int kta_set_filter(kta_ctx *ctx, int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_words)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (from_ms >= to_ms) return fail(ctx, KTA_ERR_INVALID, "kta_set_filter: from_ms must be below to_ms");
+    if (partition_bitmap && n_words == 0) return fail(ctx, KTA_ERR_INVALID, "kta_set_filter: a partition bitmap of no words");
+    if (ctx->handed_records || ctx->fill_n)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_filter: the context has been handed records since kta_create / kta_reset");
+    const uint32_t words = kta::filter_bitmap_words(ctx->P);
+    std::vector<uint32_t> set(words, 0u);
+    if (partition_bitmap) {
+        if ((size_t)words * 4 > kta::kFilterBitmapBytes)
+            return fail(ctx, KTA_ERR_INVALID, "kta_set_filter: a partition set needs P <= " + std::to_string(kta::kFilterBitmapBytes * 8u));
+        for (uint32_t w = 0; w < n_words; w++) {
+            const uint32_t valid = w >= words ? 0u : (w + 1 == words && (ctx->P & 31u)) ? (1u << (ctx->P & 31u)) - 1u : 0xFFFFFFFFu;
+            if (partition_bitmap[w] & ~valid) return fail(ctx, KTA_ERR_INVALID, "kta_set_filter: the bitmap names a partition at or beyond P");
+            if (w < words) set[w] = partition_bitmap[w];
+        }
+    }
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    if (!ctx->d_filter_stats) {
+        KTA_HIP(ctx, ctx->d_filter_stats.alloc(3));
+        KTA_HIP(ctx, hipMemset(ctx->d_filter_stats.get(), 0, 3 * sizeof(uint64_t)));
+    }
+    if (partition_bitmap) {
+        if (!ctx->d_filter_bitmap) KTA_HIP(ctx, ctx->d_filter_bitmap.alloc(words));
+        KTA_HIP(ctx, hipMemcpy(ctx->d_filter_bitmap.get(), set.data(), (size_t)words * 4, hipMemcpyHostToDevice));
+    }
+    ctx->filter_spec = kta::FilterSpec{from_ms, to_ms, ctx->P, partition_bitmap ? 1u : 0u};
+    ctx->filter = partition_bitmap || kta::filter_timed(ctx->filter_spec);   // no bound and no set: no filter
+    return KTA_OK;
+}
+
+int kta_set_filter_slice(kta_ctx *ctx, uint64_t records)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (records == 0) records = kta::kFilterSlice;
+    if (records % KTA_TILE_RECORDS || records > kta::kFilterSlice)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_filter_slice: a multiple of 1024 records, at most 2^26");
+    ctx->filter_slice = records;
+    return KTA_OK;
+}
+
+int kta_filter_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    uint64_t st[3] = {0, 0, 0};
+    if (ctx->d_filter_stats) rc = read_words(ctx, ctx->d_filter_stats.get(), st, 3);
+    out[0] = ctx->filter_seen, out[1] = ctx->filter_passed, out[2] = st[0], out[3] = st[1], out[4] = st[2], out[5] = ctx->filter_slices;
+    return rc;
+}
+
+int kta_filter_host(const int32_t *partition, const int64_t *ts_ms, uint64_t n, uint32_t n_partitions, int64_t from_ms, int64_t to_ms,
+                    const uint32_t *partition_bitmap, uint32_t n_words, uint64_t *indices_out, uint64_t *n_out)
+{
+    if ((n && (!partition || !ts_ms)) || !n_out || from_ms >= to_ms) return KTA_ERR_INVALID;
+    if (partition_bitmap && n_words < kta::filter_bitmap_words(n_partitions)) return KTA_ERR_INVALID;
+    const kta::FilterSpec f{from_ms, to_ms, n_partitions, partition_bitmap ? 1u : 0u};
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (!kta::filter_record_passes(f, partition_bitmap, partition[i], ts_ms[i])) continue;
+        if (indices_out) indices_out[m] = i;
+        m++;
+    }
+    *n_out = m;
+    return KTA_OK;
+}
+
+int kta_filter_tile_host(uint32_t n_partitions, int64_t from_ms, int64_t to_ms, int has_partition_set, const kta_tile_hdr *hdr,
+                         const kta_tile_sum *sum, int whole)
+{
+    if (!hdr || !sum || from_ms >= to_ms) return KTA_ERR_INVALID;
+    const kta::FilterSpec f{from_ms, to_ms, n_partitions, has_partition_set ? 1u : 0u};
+    return (int)kta::filter_tile_decide(f, *hdr, *sum, whole != 0);
 }
 
 namespace {

@@ -7,6 +7,7 @@
 
 #include "kta_hip.h"
 #include "kta_tile.h"
+#include "kta_filter.h"
 
 namespace kta {
 
@@ -294,5 +295,44 @@ hipError_t launch_partitioner(const PartitionerColumns &c, uint64_t n, uint32_t 
                               int cu_count, uint32_t *workgroups, hipStream_t s);
 // out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P and Q (kta_partitioner_info)
 void partitioner_lds_plan(uint32_t P, uint32_t Q, uint32_t out[3]);
+
+// Record filter (kta_set_filter, kta_filter.hip; the rules are kta_filter.h's): one slice of a device batch, compacted in
+// record order into a raw-layout scratch batch by three launches (count per tile, prefix of the counts, scatter).
+constexpr uint64_t kFilterSlice = 1ull << 26;                                   // records per slice, at most
+constexpr uint64_t kFilterMaxTiles = kFilterSlice / KTA_TILE_RECORDS + 1;       // (+ 1: a view that starts inside a tile)
+constexpr uint64_t kFilterCountWords = 256 * 260;                                // the prefix kernel's 256 stretches of whole 16-byte words
+constexpr uint32_t kFilterBitmapBytes = 65536;                                  // the partition set in LDS: P <= 2^19
+struct FilterSource {
+    const int32_t *partition;   // as ScanColumns: with hdr, the allocation's record 0, and the slice's first record is a0;
+    const int32_t *key_len;     // without, the slice's own record 0 and a0 == 0
+    const int32_t *val_len;
+    const int64_t *ts_ms;
+    const kta_tile_hdr *hdr;
+    const kta_tile_sum *sum;    // null: no summaries, every tile is read
+    uint64_t a0;
+    const uint32_t *key_off;    // the slice's record 0 (plain in both layouts); null: no key columns
+    const uint64_t *seq;        // likewise; null: base_seq + i
+    uint64_t base_seq;          // of the slice's record 0
+};
+struct FilterDest {             // the scratch batch, raw layout
+    int32_t *partition, *key_len, *val_len;
+    int64_t *ts_ms;
+    uint32_t *key_off;          // null: not kept
+    uint64_t *seq;              // null: not kept
+    uint64_t capacity;          // records: no store goes at or past it
+};
+struct FilterWorkspace {
+    uint32_t *count;            // u32[kFilterCountWords]: a tile's count, and how it was decided in the high half
+    uint64_t *offset;           // u64[kFilterMaxTiles + 1]: the exclusive prefix, then the slice's total
+    uint64_t *stats;            // u64[3] += tiles decided "none" by summary, decided "all" by summary, read
+    uint64_t *total_host;       // one word of pinned host memory, as the device addresses it: the slice's total, written by
+                                // the prefix kernel itself (no copy command between the kernel and the host's wait)
+};
+// records [0, n) of c, n <= kFilterSlice.  launch_filter_count: the counts and their prefix; the total is
+// *ws.total_host (and ws.offset[filter_slice_tiles(c.a0, n)]) once the stream got there.  launch_filter_scatter: the passing records to `out`,
+// behind it on the same stream (a slice whose total is 0 or n does not need it).
+hipError_t launch_filter_count(const FilterSource &c, uint64_t n, const FilterSpec &f, const uint32_t *bitmap, const FilterWorkspace &ws, hipStream_t s);
+hipError_t launch_filter_scatter(const FilterSource &c, uint64_t n, const FilterSpec &f, const uint32_t *bitmap, const FilterWorkspace &ws,
+                                 const FilterDest &out, hipStream_t s);
 
 } // namespace kta
