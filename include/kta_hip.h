@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the record filter (kta_set_filter, kta_filter_info, kta_set_filter_slice, kta_filter_host, kta_filter_tile_host, kta_render_filter), only added entry points; the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the record filter (kta_set_filter, kta_filter_info, kta_set_filter_slice, kta_filter_host, kta_filter_tile_host, kta_render_filter), only added entry points; the compaction what-if (KTA_FLAG_COMPACTION, kta_compaction_replay, kta_get_compaction, kta_compaction_max_partitions, kta_compaction_info, kta_render_compaction), only added entry points and one flag bit; the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -262,6 +262,51 @@ typedef struct kta_hot_key {
  * (Kafka's UtilsTest).  kta_create refuses the flag above kta_partitioner_max_partitions() partitions, and
  * kta_set_repartition a Q above it. */
 #define KTA_FLAG_PARTITIONER 0x40u   /* 64: bit 6 */
+
+/* Compaction what-if (NOT in the reference, never printed by the reference report): the records and bytes that log
+ * compaction would keep, per partition — exact, every word an integer.  Opt-in at kta_create.  The flag needs
+ * count_alive_keys (KTA_ERR_INVALID with a message naming the flag otherwise) and implies KTA_FLAG_ALIVE_TABLE, as
+ * KTA_FLAG_SEQ_COLUMN does; kta_create refuses it above kta_compaction_max_partitions() partitions (at least 4096: the
+ * pass keeps 32 B per partition in LDS), and kta_comm_create with nranks > 1 refuses such a context (after kta_exchange
+ * only the owner of a hash range holds the merged entries).
+ * The FIRST PASS is unchanged: the context is an ordinary -c context in the table state, every hash slot of which holds
+ * ((seq + 1) << 1) | alive of its last writer.  A record survives compaction exactly when the value it would write is the
+ * value its slot holds, so one more pass over the same batches answers the question.
+ * REPLAY MODE (kta_compaction_replay).  Turning it on flushes the staged messages in the mode they were staged in, zeroes
+ * the compaction vector, saves the context's next sequence number and sets it to 0, and sets the mode; turning it off
+ * flushes what the replay staged and restores the sequence number.  While it is on, EVERY submission path — the staging
+ * ring behind kta_batch_submit / kta_handle_message / kta_replay_messages, kta_submit_device[_ex] whatever `which` says,
+ * the Kafka decode — hands its batches to the compaction pass and to nothing else, behind the record filter: a filtered
+ * context replays the passing records with the sequence numbers they kept.  The replay does not touch the counter vector,
+ * the alive table and its running count, or any other opt-in vector.  kta_reset zeroes the vector and turns the mode off.
+ * The caller replays the same records with the same sequence numbers it submitted the first time: same base_seq, same seq
+ * column, or the same order through the paths that number records themselves.
+ * For every record shown during replay, with s its sequence number (seq[i] if the batch has the column, else
+ * base_seq + i), h = fnv1a(key) (the -c hash) and v = ((s + 1) << 1) | (val_len >= 0):
+ *   key_len < 0       unkeyed += 1, nothing else (compaction goes by key)
+ *   table[h] == v     the record SURVIVES:
+ *                       partition p in [0, P), val_len >= 0:  live_records[p] += 1, live_key_bytes[p] += key_len,
+ *                                                             live_value_bytes[p] += val_len
+ *                       partition p in [0, P), val_len < 0:   tombstone_records[p] += 1, tombstone_key_bytes[p] += key_len
+ *                                                             (a tombstone the cleaner keeps until delete.retention.ms)
+ *                       partition outside [0, P):             live_outside += 1 if val_len >= 0, else tombstones_outside += 1
+ *   table[h] >  v     superseded: adds nothing
+ *   table[h] <  v     (0 included) unknown += 1: the table never saw this record, the replay does not match the first pass
+ * and every record shown adds 1 to replayed.
+ * The result vector is u64[5 P + 6], every word a SUM: word 5p + k is live_records, live_key_bytes, live_value_bytes,
+ * tombstone_records, tombstone_key_bytes of partition p; then replayed, unkeyed, unknown, live_outside,
+ * tombstones_outside and one reserved word that is 0.
+ * After a replay of everything the first pass was handed:
+ *   sum of live_records[p] + live_outside == alive keys (the context's running count, what kta_finish reports);
+ *   unknown == 0;
+ *   live_records[p] + tombstone_records[p] <= key_non_null[p].
+ * Caveats.  As with -c, two keys of one 32-bit hash are one key.  The slot is topic-wide, as in the reference: a key
+ * written to several partitions survives once here and once per partition in Kafka — exact for a topic in which every key
+ * lives in one partition, which the partitioner pass checks.  Two records with one sequence number and one hash are a
+ * caller's error: both survive. */
+#define KTA_FLAG_COMPACTION (0x80u)  /* 128: bit 7 */
+#define KTA_COMPACTION_WORDS 5       /* per partition */
+#define KTA_COMPACTION_GLOBALS 6
 
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
@@ -745,6 +790,22 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6]);
  * len is 0. */
 uint32_t kta_murmur2(const void *key, size_t len);
 
+/* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
+ * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
+ * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
+ * it.  Every call below that takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming
+ * KTA_FLAG_COMPACTION.
+ * Replay mode on (non-zero) or off (0); setting the mode it is in does nothing. */
+int kta_compaction_replay(kta_ctx *ctx, int on);
+/* The live vector, copied to out[n_u64] (n_u64 = 5 P + 6; staged messages are flushed first). */
+int kta_get_compaction(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The largest P a KTA_FLAG_COMPACTION context may have (the pass keeps 32 P bytes in LDS). */
+int kta_compaction_max_partitions(void);
+/* Work counters of the pass since kta_create / kta_reset (profiling; waits for the compute stream): out[0] keyed records
+ * looked at (one table read each), out[1] launches, out[2] workgroups launched, out[3] LDS adds (survivors only),
+ * out[4] dynamic LDS bytes of a workgroup for this P, out[5] reserved, 0. */
+int kta_compaction_info(kta_ctx *ctx, uint64_t out[6]);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -865,6 +926,24 @@ int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32
  * Output buffer conventions as kta_render_report. */
 int kta_render_partitioner(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, uint32_t q, char *out,
                            size_t out_cap, size_t *out_len);
+/* The opt-in compaction section that kta-analyzer prints after the partitioner section and before the filter section with
+ * -c --librdkafka kta.compaction=1, from a compaction vector u64[5 P + 6] and the counter vector u64[P * 7 + 8] of the
+ * first pass (host only).  Shares are %.2f, `n/a` where the denominator is 0.
+ *   `Compaction what-if: the records and bytes log compaction would keep (kta.compaction=1; not part of the reference
+ *    report)` — one line;
+ *   a table (P | Records | Kept | Live | Tombstones | Records reclaimed % | Bytes | Bytes kept | Bytes reclaimed %) with a
+ *    row per partition and a Topic row: Records is total_messages, Bytes key_size_sum + value_size_sum of the counter
+ *    vector, Kept = Live + Tombstones, Bytes kept = live key + live value + tombstone key bytes, reclaimed = 1 - kept / now;
+ *   `Records without a key: N (not kept: compaction goes by key)`, N the vector's unkeyed;
+ *   `Kept outside the partition range: L live, T tombstones` when either is non-zero;
+ *   `Keys are counted by 32-bit hash slot, topic-wide, as "Alive keys" is: a key written to several partitions is kept once.`;
+ *   a closing `=` rule.
+ * When unknown != 0, or replayed differs from the counter vector's records plus bad-partition records, the replay did not
+ * match the first pass: the section is the first line, `The replay did not match the first pass: replayed R of N records,
+ * U of them unknown to the table. Nothing is reported.` and the rule, and the call returns KTA_ERR_INVALID (the text is
+ * still written).  Output buffer conventions as kta_render_report. */
+int kta_render_compaction(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
+                          size_t *out_len);
 /* The section kta-analyzer prints after everything else when a filter was given (--librdkafka kta.from=<epoch seconds>,
  * kta.to=<epoch seconds>, kta.partitions=0,3-5); not part of the reference report:
  *   `Record filter: everything above describes the records that passed, and no others (kta.from, kta.to, kta.partitions;

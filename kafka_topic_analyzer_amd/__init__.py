@@ -29,7 +29,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "timeline_max_partitions", "estimate_distinct_keys", "merge_key_sketch", "render_distinct_keys",
            "recover_hot_keys", "merge_hot_keys", "render_hot_keys", "render_ts_order", "merge_ts_order",
            "ts_order_max_partitions", "split_ts_order", "render_partitioner", "merge_partitioner",
-           "partitioner_max_partitions", "split_partitioner", "murmur2"]
+           "partitioner_max_partitions", "split_partitioner", "murmur2", "render_compaction", "split_compaction",
+           "compaction_max_partitions"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -77,7 +78,8 @@ class HipMetricHandler:
                  batch_capacity: int = 0, key_bytes_capacity: int = 0, n_staging: int = 0,
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
-                 hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None):
+                 hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
+                 compaction: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -86,7 +88,9 @@ class HipMetricHandler:
         hot_keys: the topic-wide hot-key sketch (KTA_FLAG_HOT_KEYS: recover_hot_keys, hot_key_exemplars);
         ts_order: the timestamp-order pass (KTA_FLAG_TS_ORDER: late records per partition, ts_order());
         partitioner: the partitioner pass (KTA_FLAG_PARTITIONER: keyed records on murmur2's partition and their spread
-        over `repartition` partitions — n_partitions when None —, partitioner())."""
+        over `repartition` partitions — n_partitions when None —, partitioner());
+        compaction: the compaction what-if (KTA_FLAG_COMPACTION; needs count_alive_keys and implies alive_table: replay the
+        records inside compaction_replay(), then compaction())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -94,10 +98,12 @@ class HipMetricHandler:
         self.key_sketch_on = bool(key_sketch)
         self.hot_keys_on = bool(hot_keys)
         self.partitioner_on = bool(partitioner)
+        self.compaction_on = bool(compaction)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
+                        (N.KTA_FLAG_COMPACTION if compaction else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -546,6 +552,25 @@ class HipMetricHandler:
         self._check(self._lib.kta_partitioner_info(self._ctx, C.byref(out)))
         return dict(zip(("keyed_records", "launches", "partition_adds", "target_adds", "workgroups", "lds_bytes"), (int(x) for x in out)))
 
+    def compaction_replay(self, on: bool = True):
+        """Replay mode of the compaction what-if on or off (kta_compaction_replay): while it is on every submission path
+        hands its batches to the compaction pass and to nothing else.  Either a pair of calls, or
+        `with h.compaction_replay(): ...`, which turns the mode off at the end."""
+        self._check(self._lib.kta_compaction_replay(self._ctx, 1 if on else 0))
+        return _CompactionReplay(self)
+
+    def compaction(self) -> dict:
+        """The live compaction vector as a dict (split_compaction; kta_get_compaction; staged messages are flushed first)."""
+        out = np.zeros(N.KTA_COMPACTION_WORDS * self.n_partitions + N.KTA_COMPACTION_GLOBALS, dtype=np.uint64)
+        self._check(self._lib.kta_get_compaction(self._ctx, _np_ptr(out), out.size))
+        return split_compaction(out, self.n_partitions)
+
+    def compaction_info(self) -> dict:
+        """Work counters of the compaction pass since creation / reset() (kta_compaction_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_compaction_info(self._ctx, C.byref(out)))
+        return dict(zip(("keyed_records", "launches", "workgroups", "lds_adds", "lds_bytes", "reserved"), (int(x) for x in out)))
+
     def set_filter(self, from_ms: Optional[int] = None, to_ms: Optional[int] = None, partitions=None) -> None:
         """Analyse only the records with from_ms <= ts_ms < to_ms (None: no bound on that side) whose partition is one of
         `partitions` (None: all).  Only before the first record; reset() keeps it (kta_set_filter).  All None: no filter."""
@@ -953,6 +978,70 @@ def render_partitioner(vec, counter_vec, n_partitions: int, repartition: int) ->
     if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
     return _render(N.load().kta_render_partitioner, _np_ptr(v), _np_ptr(c), n_partitions, repartition)
+
+
+class _CompactionReplay:
+    """What HipMetricHandler.compaction_replay returns: as a context manager it turns replay mode off at the end."""
+
+    def __init__(self, handler):
+        self._h = handler
+
+    def __enter__(self):
+        return self._h
+
+    def __exit__(self, *exc):
+        self._h.compaction_replay(False)
+        return False
+
+
+_COMPACTION_GLOBALS = ("replayed", "unkeyed", "unknown", "live_outside", "tombstones_outside")
+
+
+def _compaction_vec(vec, P: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    words = N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS
+    if v.size != words:
+        raise ValueError(f"a compaction vector of {P} partitions has {words} words, not {v.size}")
+    return v
+
+
+def split_compaction(vec, n_partitions: int) -> dict:
+    """A compaction vector u64[5 P + 6] as a dict: live_records[P], live_key_bytes[P], live_value_bytes[P],
+    tombstone_records[P], tombstone_key_bytes[P], the globals replayed, unkeyed, unknown, live_outside, tombstones_outside as
+    ints, and the vector itself under "vector"."""
+    P, W = n_partitions, N.KTA_COMPACTION_WORDS
+    v = _compaction_vec(vec, P)
+    d = {name: v[k:W * P:W].copy() for k, name in enumerate(("live_records", "live_key_bytes", "live_value_bytes", "tombstone_records",
+                                                              "tombstone_key_bytes"))}
+    d.update({name: int(v[W * P + k]) for k, name in enumerate(_COMPACTION_GLOBALS)})
+    d["vector"] = v
+    return d
+
+
+def render_compaction(vec, counter_vec, n_partitions: int) -> str:
+    """kta_render_compaction: the section kta-analyzer prints with -c --librdkafka kta.compaction=1, from a compaction vector
+    and the first pass's counter vector u64[P * 7 + 8].  KtaError (KTA_ERR_INVALID) when the replay did not match the first
+    pass; the section that says so is the error's `text`."""
+    v = _compaction_vec(vec, n_partitions)
+    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
+    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    fn = N.load().kta_render_compaction
+    n = C.c_size_t()
+    fn(_np_ptr(v), _np_ptr(c), n_partitions, None, 0, C.byref(n))
+    buf = C.create_string_buffer(n.value + 1)
+    rc = fn(_np_ptr(v), _np_ptr(c), n_partitions, buf, len(buf), C.byref(n))
+    if rc != N.KTA_OK:
+        err = KtaError(rc, "kta_render_compaction: the replay did not match the first pass")
+        err.text = buf.value.decode()
+        raise err
+    return buf.value.decode()
+
+
+def compaction_max_partitions() -> int:
+    """The largest P of a context with the compaction what-if."""
+    return int(N.load().kta_compaction_max_partitions())
 
 
 def render_filter(n_partitions: int, seen: int, passed: int, from_ms: Optional[int] = None, to_ms: Optional[int] = None,

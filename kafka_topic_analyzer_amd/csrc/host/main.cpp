@@ -49,6 +49,10 @@
 // records and no others, and one more section after everything else says what the filter was and how many records it
 // was shown and let pass (summed over the ranks).  The items of kta.partitions are separated by commas, which also separate
 // --librdkafka's pairs: a piece without '=' that follows kta.partitions and is a number or a range belongs to it.
+// kta.compaction=1 (0: off; with -c; synthetic://, segment:// and dump:// sources, one GPU, not with kta.per_message=1) answers
+// what log compaction would keep (KTA_FLAG_COMPACTION; no reference counterpart): after the first pass the source is fed a
+// second time in replay mode, and a section with the records and bytes kept per partition is printed after the
+// partitioner section and before the filter section.
 // kta.hot_keys=K (1 <= K <= 64; every source, kta.gpus=N included) keeps the hot-key sketch as well (KTA_FLAG_HOT_KEYS; no
 // reference counterpart) and prints, last of all, the at most K keys that hold 1/512 of the keyed records and more, with
 // bounds on their records and, where the device caught one, the key's bytes (with kta.gpus=N from the lowest rank that
@@ -531,6 +535,32 @@ int main(int argc, char **argv)
     bool synthetic = b.rfind("synthetic://", 0) == 0, dump = b.rfind("dump://", 0) == 0;
     const bool segment = b.rfind("segment://", 0) == 0;
     const bool kafka = !synthetic && !dump && !segment;   // a broker list: the reference's own path
+    // kta.compaction: what needs no partition count is refused here, before a broker or a device is asked for anything
+    bool compaction = false;
+    if (cfg.count("kta.compaction")) {
+        const std::string &v = cfg["kta.compaction"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.compaction=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        compaction = v == "1";
+        if (compaction && !count_alive) {
+            fprintf(stderr, "kta.compaction=1: needs -c (the pass reads the alive-key table)\n");
+            return 2;
+        }
+        if (compaction && gpus > 1) {
+            fprintf(stderr, "kta.compaction=1: not with kta.gpus=%d (after the exchange a rank holds only its hash range's entries)\n", gpus);
+            return 2;
+        }
+        if (compaction && cfg.count("kta.per_message") && cfg["kta.per_message"] == "1") {
+            fprintf(stderr, "kta.compaction=1: not with kta.per_message=1\n");
+            return 2;
+        }
+        if (compaction && kafka) {
+            fprintf(stderr, "kta.compaction=1: needs a synthetic://, segment:// or dump:// source (a broker's topic cannot be read a second time here)\n");
+            return 2;
+        }
+    }
     kta::TopicAnalyzer *topic_analyzer = nullptr;
     std::map<int32_t, int64_t> kafka_start, kafka_end;
     if (kafka) {
@@ -620,6 +650,10 @@ int main(int argc, char **argv)
                     kta_partitioner_max_partitions());
             return 2;
         }
+    }
+    if (compaction && P > (uint32_t)kta_compaction_max_partitions()) {   // before any context, so before any kernel
+        fprintf(stderr, "kta.compaction=1: the topic has %u partitions, the compaction pass admits at most %d\n", P, kta_compaction_max_partitions());
+        return 2;
     }
     if (cfg.count("kta.repartition")) {
         if (!partitioner) {
@@ -808,7 +842,7 @@ int main(int argc, char **argv)
         handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
-                                                (partitioner ? KTA_FLAG_PARTITIONER : 0u),
+                                                (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -873,76 +907,96 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
-    } else if (synthetic) {
-        while (seq < n_records) {
-            kta_batch hb;
-            check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
-            uint64_t n = std::min<uint64_t>(hb.capacity, n_records - seq), kb = 0;
-            if (!count_alive && !distinct_keys && !hot_keys && !partitioner && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
-            int rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
-            while (rc == KTA_ERR_CAPACITY && n > 1) {  // key bytes did not fit: shrink the batch
-                n /= 2;
-                rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
+    }
+    // The synthetic://, segment:// and dump:// feed loops: once for the first pass, and with kta.compaction=1 a second time
+    // in replay mode, with the sequence numbers of the first.  Returns an exit code, 0 to go on.
+    auto feed = [&](bool replay) -> int {
+        seq = 0;
+        if (replay && reader) {   // the dump from its first batch again
+            delete reader;
+            reader = new kta::DumpReader(b.substr(strlen("dump://")));
+            kta::DumpHeader again;
+            if (!reader->ok() || !reader->read_header(&again)) {
+                fprintf(stderr, "kta.compaction=1: cannot read topic dump '%s' a second time\n", b.c_str() + 7);
+                return 2;
             }
-            check(rc, ctx, "kta_synth_fill_host");
-            if (write_dump) {
-                kta::DumpBatch db;
-                db.n = n; db.n_key_bytes = hb.key_bytes ? kb : 0;
-                db.partition.assign(hb.partition, hb.partition + n);
-                db.key_len.assign(hb.key_len, hb.key_len + n);
-                db.val_len.assign(hb.val_len, hb.val_len + n);
-                db.ts_ms.assign(hb.ts_ms, hb.ts_ms + n);
-                if (hb.key_off) db.key_off.assign(hb.key_off, hb.key_off + n); else db.key_off.assign(n, 0);
-                if (hb.key_bytes) db.key_bytes.assign(hb.key_bytes, hb.key_bytes + kb);
-                to_write.push_back(std::move(db));
-            }
-            check(kta_batch_submit(ctx, n, kb, seq), ctx, "kta_batch_submit");
-            seq += n;
         }
-    } else if (segment) {
-        for (uint32_t p = 0; p < P; p++) {
-            if (segment_bytes[p].empty()) continue;
-            kta_kafka_index_stats ist;
-            check(kta_kafka_consume(ctx, segment_bytes[p].data(), segment_bytes[p].size(), (int32_t)p, &ist), ctx,
-                  "kta_kafka_consume");
-            if (ist.n_compressed || ist.n_old_magic)
-                fprintf(stderr, "[WARN] Kafka error: partition %u: %llu unknown-codec and %llu pre-v2 batches skipped\n", p,
-                        (unsigned long long)ist.n_compressed, (unsigned long long)ist.n_old_magic);   // kafka.rs:95-97
-            seq += ist.n_records;
-        }
-    } else {
-        kta::DumpBatch db;
-        for (uint64_t bi = 0; bi < hdr.n_batches; bi++) {
-            if (!reader->read_batch(&db)) {
-                fprintf(stderr, "[WARN] Kafka error: truncated topic dump\n");      // kafka.rs:95-97: warn and go on
-                break;
-            }
-            uint64_t done = 0;
-            while (done < db.n) {
+        if (synthetic) {
+            while (seq < n_records) {
                 kta_batch hb;
                 check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
-                uint64_t n = std::min<uint64_t>(hb.capacity, db.n - done), kb = 0;
-                if (count_alive || distinct_keys || hot_keys || partitioner) {  // re-pack this chunk's keys
-                    uint64_t m = 0;
-                    for (; m < n; m++) {
-                        const uint64_t kl = db.key_len[done + m] > 0 ? (uint64_t)db.key_len[done + m] : 0;
-                        if (kb + kl > hb.key_bytes_capacity) break;
-                        hb.key_off[m] = (uint32_t)kb;
-                        if (kl) memcpy(hb.key_bytes + kb, db.key_bytes.data() + db.key_off[done + m], kl);
-                        kb += kl;
-                    }
-                    n = m;
-                    if (n == 0) { fprintf(stderr, "key larger than the staging capacity\n"); return 2; }
+                uint64_t n = std::min<uint64_t>(hb.capacity, n_records - seq), kb = 0;
+                if (!count_alive && !distinct_keys && !hot_keys && !partitioner && !write_dump) { hb.key_off = nullptr; hb.key_bytes = nullptr; }
+                int rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
+                while (rc == KTA_ERR_CAPACITY && n > 1) {  // key bytes did not fit: shrink the batch
+                    n /= 2;
+                    rc = kta_synth_fill_host(&spec, seq, n, &hb, &kb);
                 }
-                memcpy(hb.partition, db.partition.data() + done, 4 * n);
-                memcpy(hb.key_len, db.key_len.data() + done, 4 * n);
-                memcpy(hb.val_len, db.val_len.data() + done, 4 * n);
-                memcpy(hb.ts_ms, db.ts_ms.data() + done, 8 * n);
+                check(rc, ctx, "kta_synth_fill_host");
+                if (write_dump && !replay) {
+                    kta::DumpBatch db;
+                    db.n = n; db.n_key_bytes = hb.key_bytes ? kb : 0;
+                    db.partition.assign(hb.partition, hb.partition + n);
+                    db.key_len.assign(hb.key_len, hb.key_len + n);
+                    db.val_len.assign(hb.val_len, hb.val_len + n);
+                    db.ts_ms.assign(hb.ts_ms, hb.ts_ms + n);
+                    if (hb.key_off) db.key_off.assign(hb.key_off, hb.key_off + n); else db.key_off.assign(n, 0);
+                    if (hb.key_bytes) db.key_bytes.assign(hb.key_bytes, hb.key_bytes + kb);
+                    to_write.push_back(std::move(db));
+                }
                 check(kta_batch_submit(ctx, n, kb, seq), ctx, "kta_batch_submit");
                 seq += n;
-                done += n;
+            }
+        } else if (segment) {
+            for (uint32_t p = 0; p < P; p++) {
+                if (segment_bytes[p].empty()) continue;
+                kta_kafka_index_stats ist;
+                check(kta_kafka_consume(ctx, segment_bytes[p].data(), segment_bytes[p].size(), (int32_t)p, &ist), ctx,
+                      "kta_kafka_consume");
+                if (!replay && (ist.n_compressed || ist.n_old_magic))
+                    fprintf(stderr, "[WARN] Kafka error: partition %u: %llu unknown-codec and %llu pre-v2 batches skipped\n", p,
+                            (unsigned long long)ist.n_compressed, (unsigned long long)ist.n_old_magic);   // kafka.rs:95-97
+                seq += ist.n_records;
+            }
+        } else {
+            kta::DumpBatch db;
+            for (uint64_t bi = 0; bi < hdr.n_batches; bi++) {
+                if (!reader->read_batch(&db)) {
+                    if (!replay) fprintf(stderr, "[WARN] Kafka error: truncated topic dump\n");      // kafka.rs:95-97: warn and go on
+                    break;
+                }
+                uint64_t done = 0;
+                while (done < db.n) {
+                    kta_batch hb;
+                    check(kta_batch_acquire(ctx, &hb), ctx, "kta_batch_acquire");
+                    uint64_t n = std::min<uint64_t>(hb.capacity, db.n - done), kb = 0;
+                    if (count_alive || distinct_keys || hot_keys || partitioner) {  // re-pack this chunk's keys
+                        uint64_t m = 0;
+                        for (; m < n; m++) {
+                            const uint64_t kl = db.key_len[done + m] > 0 ? (uint64_t)db.key_len[done + m] : 0;
+                            if (kb + kl > hb.key_bytes_capacity) break;
+                            hb.key_off[m] = (uint32_t)kb;
+                            if (kl) memcpy(hb.key_bytes + kb, db.key_bytes.data() + db.key_off[done + m], kl);
+                            kb += kl;
+                        }
+                        n = m;
+                        if (n == 0) { fprintf(stderr, "key larger than the staging capacity\n"); return 2; }
+                    }
+                    memcpy(hb.partition, db.partition.data() + done, 4 * n);
+                    memcpy(hb.key_len, db.key_len.data() + done, 4 * n);
+                    memcpy(hb.val_len, db.val_len.data() + done, 4 * n);
+                    memcpy(hb.ts_ms, db.ts_ms.data() + done, 8 * n);
+                    check(kta_batch_submit(ctx, n, kb, seq), ctx, "kta_batch_submit");
+                    seq += n;
+                    done += n;
+                }
             }
         }
+        return 0;
+    };
+    if (!kafka && !(synthetic && per_message)) {
+        const int rc = feed(false);
+        if (rc) return rc;
     }
     if (!kafka) fprintf(stderr, "done\n");                                          // kafka.rs:136 (spinner)
 
@@ -959,6 +1013,23 @@ int main(int argc, char **argv)
         (void)kta_kafka_crc_errors(ctx, &crc_errors);
         fprintf(stderr, "[WARN] Kafka error: %llu record(s) of corrupt batches were not delivered (%llu CRC failure(s))\n",
                 (unsigned long long)handler->undelivered_records(), (unsigned long long)crc_errors);
+    }
+    // kta.compaction=1: whatever the report prints from the first pass has been read (the snapshot finish() took, the CRC
+    // errors, the undelivered records; the filter's counts are read here) before the replay starts
+    uint64_t filter_info[6] = {0, 0, 0, 0, 0, 0};
+    if (filter.on) check(kta_filter_info(ctx, filter_info), ctx, "kta_filter_info");
+    std::vector<uint64_t> compaction_vec;
+    if (compaction) {
+        try {
+            handler->replay_compaction(true);
+            const int rc = feed(true);
+            if (rc) return rc;
+            handler->replay_compaction(false);
+            compaction_vec = handler->compaction();
+        } catch (const std::exception &e) {
+            fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
     }
     const kta::MessageMetrics &metrics = handler->metrics();
     if (synthetic)
@@ -990,11 +1061,20 @@ int main(int argc, char **argv)
         if (hot_keys) text += kta::render_hot_keys(handler->hot_keys()->data(), handler->hot_key_exemplars()->data(), hot_keys);
         if (partitioner)
             text += kta::render_partitioner(handler->partitioner()->data(), partitioner_counters(metrics, P).data(), P, handler->repartition());
-        if (filter.on) {
-            uint64_t info[6];
-            check(kta_filter_info(ctx, info), ctx, "kta_filter_info");
-            text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, info[0], info[1]);
+        if (compaction) {
+            std::vector<uint64_t> cv = partitioner_counters(metrics, P);
+            uint64_t records = 0;
+            for (uint32_t p = 0; p < P; p++) {
+                cv[(size_t)p * KTA_NCOUNTERS + KTA_C_TOTAL] = metrics.total((int32_t)p);
+                records += metrics.total((int32_t)p);
+            }
+            cv[(size_t)P * KTA_NCOUNTERS + KTA_G_RECORDS] = records;
+            cv[(size_t)P * KTA_NCOUNTERS + KTA_G_BAD_PARTITION] = handler->undelivered_records();
+            text += kta::render_compaction(compaction_vec.data(), cv.data(), P);
         }
+        if (filter.on)
+            text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, filter_info[0],
+                                       filter_info[1]);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -146,6 +146,15 @@ void HipMetricHandler::finish(bool tolerate_undelivered)
     read_analytics();
 }
 
+void HipMetricHandler::replay_compaction(bool on) { check(kta_compaction_replay(ctx_, on ? 1 : 0), "kta_compaction_replay"); }
+
+std::vector<uint64_t> HipMetricHandler::compaction()
+{
+    std::vector<uint64_t> v((size_t)KTA_COMPACTION_WORDS * (size_t)P_ + KTA_COMPACTION_GLOBALS, 0);
+    check(kta_get_compaction(ctx_, v.data(), v.size()), "kta_get_compaction");
+    return v;
+}
+
 void HipMetricHandler::comm_create(int nranks, int rank, const uint8_t *unique_id)
 {
     check(kta_comm_create(ctx_, nranks, rank, unique_id), "kta_comm_create");

@@ -146,6 +146,10 @@ public:
     // exchange(), the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *partitioner() const { return part_on_ ? &pvec_ : nullptr; }
     uint32_t repartition() const { return part_q_; }
+    // With KTA_FLAG_COMPACTION: replay mode on / off (kta_compaction_replay) — after finish(), feed the source a second time
+    // between replay_compaction(true) and replay_compaction(false) — and then the live compaction vector u64[5 P + 6].
+    void replay_compaction(bool on);
+    std::vector<uint64_t> compaction();
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -204,6 +208,10 @@ std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exempla
 // the opt-in section kta-analyzer prints last of all with kta.partitioner=murmur2 (kta_render_partitioner): vec
 // u64[2 P + 2 Q], counters u64[P * 7 + 8] (the counter vector of the same records; its globals are not read)
 std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q);
+// the opt-in section kta-analyzer prints with -c and kta.compaction=1 after the partitioner section and before the filter
+// section (kta_render_compaction): vec u64[5 P + 6], counters u64[P * 7 + 8] (the first pass's counter vector).  *matched
+// (when given): whether the replay matched the first pass; a section that says it did not otherwise
+std::string render_compaction(const uint64_t *vec, const uint64_t *counters, uint32_t P, bool *matched = nullptr);
 // the section kta-analyzer prints after everything else when a filter was given (kta.from, kta.to, kta.partitions;
 // kta_render_filter): bitmap null or ceil(P / 32) words as kta_set_filter takes them; the counts are kta_filter_info's
 std::string render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *bitmap, uint32_t P, uint64_t seen, uint64_t passed);

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "kta_compaction.h"
 #include "metric.hpp"
 
 namespace kta {
@@ -370,6 +371,55 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
     return o;
 }
 
+// The opt-in compaction section (-c with kta.compaction=1): no reference counterpart, printed after the partitioner section
+// and before the filter section.  vec: u64[5 P + 6] (kta_hip.h; the layout is kta_compaction.h's), counters: the first
+// pass's counter vector with its globals.
+std::string render_compaction(const uint64_t *vec, const uint64_t *counters, uint32_t P, bool *matched)
+{
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    // the share of `now` that is not kept
+    auto reclaimed = [](uint64_t kept, uint64_t now) {
+        if (!now) return std::string("n/a");
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", ((double)now - (double)kept) * 100.0 / (double)now);
+        return std::string(buf);
+    };
+    const uint64_t *g = vec + (size_t)kCompactionWords * P, *cg = counters + (size_t)P * KTA_NCOUNTERS;
+    const uint64_t shown = cg[KTA_G_RECORDS] + cg[KTA_G_BAD_PARTITION];
+    const bool ok = g[kCompactionUnknownRecords] == 0 && g[kCompactionReplayed] == shown;
+    if (matched) *matched = ok;
+    std::string o;
+    o += "Compaction what-if: the records and bytes log compaction would keep (kta.compaction=1; not part of the reference report)\n";
+    if (!ok) {
+        o += "The replay did not match the first pass: replayed " + u(g[kCompactionReplayed]) + " of " + u(shown) + " records, " +
+             u(g[kCompactionUnknownRecords]) + " of them unknown to the table. Nothing is reported.\n";
+        o += std::string(120, '=') + "\n";
+        return o;
+    }
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Records", "Kept", "Live", "Tombstones", "Records reclaimed %", "Bytes", "Bytes kept", "Bytes reclaimed %"});
+    uint64_t rec_all = 0, live_all = 0, tomb_all = 0, bytes_all = 0, kept_bytes_all = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t *w = vec + (size_t)kCompactionWords * p, *c = counters + (size_t)p * KTA_NCOUNTERS;
+        const uint64_t live = w[kCompactionLiveRecords], tomb = w[kCompactionTombstoneRecords];
+        const uint64_t kept_bytes = w[kCompactionLiveKeyBytes] + w[kCompactionLiveValueBytes] + w[kCompactionTombstoneKeyBytes];
+        const uint64_t bytes = c[KTA_C_KEY_SIZE_SUM] + c[KTA_C_VALUE_SIZE_SUM];
+        rec_all += c[KTA_C_TOTAL], live_all += live, tomb_all += tomb, bytes_all += bytes, kept_bytes_all += kept_bytes;
+        rows.push_back({std::to_string(p), u(c[KTA_C_TOTAL]), u(live + tomb), u(live), u(tomb), reclaimed(live + tomb, c[KTA_C_TOTAL]), u(bytes),
+                        u(kept_bytes), reclaimed(kept_bytes, bytes)});
+    }
+    rows.push_back({"Topic", u(rec_all), u(live_all + tomb_all), u(live_all), u(tomb_all), reclaimed(live_all + tomb_all, rec_all), u(bytes_all),
+                    u(kept_bytes_all), reclaimed(kept_bytes_all, bytes_all)});
+    o += pretty_table(rows);
+    o += "Records without a key: " + u(g[kCompactionUnkeyedRecords]) + " (not kept: compaction goes by key)\n";
+    if (g[kCompactionLiveOutsideRecords] || g[kCompactionTombstonesOutsideRecords])
+        o += "Kept outside the partition range: " + u(g[kCompactionLiveOutsideRecords]) + " live, " + u(g[kCompactionTombstonesOutsideRecords]) +
+             " tombstones\n";
+    o += "Keys are counted by 32-bit hash slot, topic-wide, as \"Alive keys\" is: a key written to several partitions is kept once.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // The section of a filtered run (kta.from, kta.to, kta.partitions): no reference counterpart, printed after everything else.
 // The filter as given — bounds in epoch seconds as the keys take them, the set as ascending ranges — then the records
 // the run was handed and the records that passed.  bitmap null: no set; else ceil(P / 32) words (kta_set_filter).
@@ -527,6 +577,21 @@ extern "C" int kta_render_partitioner(const uint64_t *vec, const uint64_t *count
         out[n] = 0;
     }
     return KTA_OK;
+}
+
+extern "C" int kta_render_compaction(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
+                                     size_t *out_len)
+{
+    if (!vec || !counter_vec || !out_len || n_partitions == 0 || (int)n_partitions > kta_compaction_max_partitions()) return KTA_ERR_INVALID;
+    bool matched = false;
+    const std::string text = kta::render_compaction(vec, counter_vec, n_partitions, &matched);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return matched ? KTA_OK : KTA_ERR_INVALID;
 }
 
 extern "C" int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,

@@ -3,6 +3,7 @@
 // Host code only; the kernels are in kta_kernels.hip.  There is no CPU fallback: every
 // entry point that computes anything needs a gfx950 device.
 #include "../../include/kta_hip.h"
+#include "kta_compaction.h"
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
@@ -93,6 +94,12 @@ struct kta_ctx {
     uint32_t part_q = 0;
     DeviceBuf<uint64_t> d_part, d_part_out, d_part_stats;
     uint64_t part_launches = 0, part_workgroups = 0;
+    // compaction what-if (KTA_FLAG_COMPACTION): d_comp u64[5 P + 6] the live vector, d_comp_stats the kernel's work counters
+    // (kta_compaction_info); comp_replay the mode (kta_compaction_replay), comp_saved_seq the first pass's next_seq while it is on
+    bool comp = false, comp_replay = false;
+    uint64_t comp_saved_seq = 0;
+    DeviceBuf<uint64_t> d_comp, d_comp_stats;
+    uint64_t comp_launches = 0, comp_workgroups = 0;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -357,6 +364,37 @@ int run_partitioner(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns
     return KTA_OK;
 }
 
+// The compaction pass over a batch whose metric columns were resolved to rb, in launches of at most 2^30 records (the
+// halves of its LDS word W0).
+int run_compaction(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n, uint64_t base_seq)
+{
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < kta::kCompactionLaunchMax ? n - at : kta::kCompactionLaunchMax;
+        uint32_t wgs = 0;
+        KTA_HIP(ctx, kta::launch_compaction(kta::CompactionColumns{sketch_columns(rb, c, at), c->val_len + at, c->seq ? c->seq + at : nullptr}, take,
+                                            base_seq + at, ctx->P, ctx->d_table.get(), ctx->d_comp.get(), ctx->d_comp_stats.get(), ctx->cu_count,
+                                            &wgs, ctx->s_compute));
+        ctx->comp_launches++;
+        ctx->comp_workgroups += wgs;
+        at += take;
+    }
+    return KTA_OK;
+}
+
+// A batch of the replay (kta_compaction_replay): the compaction pass and nothing else, whatever `which` says.
+int run_replayed_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq)
+{
+    // every refusal comes before the first launch
+    if (!c->partition || !c->key_len || !c->val_len) return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
+    if (!c->key_off || !c->key_bytes) return fail(ctx, KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)");
+    kta_internal_columns rb{};
+    int rc = kta_internal_resolve(ctx, c, &rb);
+    if (rc != KTA_OK) return rc;
+    rc = widen_lens_for_keys(ctx, c, n);
+    if (rc != KTA_OK) return rc;
+    return run_compaction(ctx, c, rb, n, base_seq);
+}
+
 // The timestamp-order pass over a batch whose metric columns were resolved to rb: chunk maxima, prefix, apply per slice,
 // in order.  A slice is as many chunks as the workspace has rows for P partitions; the chunk is the slice over
 // kTsOrderChunks (enough waves to fill the device a few times over), a multiple of 256 records, or the tests' own.
@@ -406,6 +444,7 @@ int grow_alive_workspace(kta_ctx *ctx, const kta::AlivePartitionPlan &pl)
 int run_handlers(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq, int which)
 {
     if (n == 0) return KTA_OK;
+    if (ctx->comp_replay) return run_replayed_batch(ctx, c, n, base_seq);   // behind the filter: the passing records, the numbers they kept
     const kta::TimelineArgs *tl = ctx->timeline ? &ctx->tl : nullptr;
     const uint32_t tl_buckets = ctx->timeline ? ctx->tl.n_buckets : 0u;
     hipEvent_t a = nullptr, b = nullptr;
@@ -719,6 +758,13 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->part_launches = ctx->part_workgroups = 0;
     }
+    if (ctx->comp) {
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp.get(), 0, kta::compaction_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
+        ctx->comp_launches = ctx->comp_workgroups = 0;
+        ctx->comp_replay = false;
+        ctx->comp_saved_seq = 0;
+    }
     ctx->handed_records = false;
     if (ctx->d_filter_stats) KTA_HIP(ctx, hipMemsetAsync(ctx->d_filter_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
     ctx->filter_seen = ctx->filter_passed = ctx->filter_slices = 0;   // (the filter itself stays)
@@ -822,6 +868,11 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     if ((cfg->flags & KTA_FLAG_PARTITIONER) && cfg->n_partitions > kta_partitioner_max_partitions())
         return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_PARTITIONER admits at most " + std::to_string(kta_partitioner_max_partitions()) +
                                                   " partitions (the pass keeps its counters in LDS)");
+    if ((cfg->flags & KTA_FLAG_COMPACTION) && !cfg->count_alive_keys)
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_COMPACTION needs count_alive_keys (the pass reads the last-writer table)");
+    if ((cfg->flags & KTA_FLAG_COMPACTION) && cfg->n_partitions > kta_compaction_max_partitions())
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_COMPACTION admits at most " + std::to_string(kta_compaction_max_partitions()) +
+                                                  " partitions (the pass keeps 32 B per partition in LDS)");
     if (cfg->n_partitions <= 0 || cfg->n_partitions > 4096)
         return fail(nullptr, KTA_ERR_INVALID, "n_partitions must be in [1, 4096]");
     if ((cfg->flags & KTA_FLAG_ANALYTICS) && cfg->n_partitions > kta_analytics_max_partitions())
@@ -860,12 +911,13 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->tso = (cfg->flags & KTA_FLAG_TS_ORDER) != 0;
     ctx->part = (cfg->flags & KTA_FLAG_PARTITIONER) != 0;
     ctx->part_q = ctx->part ? ctx->P : 0u;
+    ctx->comp = (cfg->flags & KTA_FLAG_COMPACTION) != 0;
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
     }
     ctx->stage_seq = (cfg->flags & KTA_FLAG_SEQ_COLUMN) != 0;
-    ctx->alive_table = ctx->alive && (cfg->flags & (KTA_FLAG_SEQ_COLUMN | KTA_FLAG_ALIVE_TABLE)) != 0;
+    ctx->alive_table = ctx->alive && (cfg->flags & (KTA_FLAG_SEQ_COLUMN | KTA_FLAG_ALIVE_TABLE | KTA_FLAG_COMPACTION)) != 0;
     ctx->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     ctx->batch_capacity = cfg->batch_capacity ? cfg->batch_capacity : (1ull << 22);
     ctx->key_bytes_capacity = cfg->key_bytes_capacity ? cfg->key_bytes_capacity : 64ull * ctx->batch_capacity;
@@ -927,6 +979,10 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_part_out.alloc(words));
         KTA_TRY(hipMemset(ctx->d_part_out.get(), 0, words * sizeof(uint64_t)));
         KTA_TRY(ctx->d_part_stats.alloc(3));
+    }
+    if (ctx->comp) {
+        KTA_TRY(ctx->d_comp.alloc(kta::compaction_len(ctx->P)));
+        KTA_TRY(ctx->d_comp_stats.alloc(3));
     }
     if (ctx->alive) {
         if (ctx->alive_table) {
@@ -1907,6 +1963,57 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
     return rc;
 }
 
+// ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
+
+static const char *const kNoComp = "context was created without KTA_FLAG_COMPACTION";
+
+int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
+
+int kta_compaction_replay(kta_ctx *ctx, int on)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    const bool want = on != 0;
+    if (want == ctx->comp_replay) return KTA_OK;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);   // what was staged goes where it was staged for
+    if (rc != KTA_OK) return rc;
+    if (want) {
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp.get(), 0, kta::compaction_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        ctx->comp_saved_seq = ctx->next_seq;
+        ctx->next_seq = 0;
+    } else {
+        ctx->next_seq = ctx->comp_saved_seq;
+    }
+    ctx->comp_replay = want;
+    return KTA_OK;
+}
+
+int kta_get_compaction(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    int rc = check_words(ctx, "compaction vector", kta::compaction_len(ctx->P), n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_comp.get(), out, n_u64);
+}
+
+int kta_compaction_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    uint64_t st[3];
+    int rc = read_words(ctx, ctx->d_comp_stats.get(), st, 3);
+    uint32_t plan[3];
+    kta::compaction_lds_plan(ctx->P, plan);
+    out[0] = st[0], out[1] = ctx->comp_launches, out[2] = ctx->comp_workgroups, out[3] = st[1], out[4] = plan[0], out[5] = 0;
+    return rc;
+}
+
 // ---- record filter (kta_filter.h holds the rules, kta_filter.hip the kernels) ------------------------------------------
 
 int kta_set_filter(kta_ctx *ctx, int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_words)
@@ -2334,6 +2441,7 @@ bool kta_internal_want_keys(kta_ctx *ctx) { return ctx->alive || ctx->sketch || 
 uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }
+bool kta_internal_compaction(kta_ctx *ctx) { return ctx->comp; }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {
     *out = kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()};

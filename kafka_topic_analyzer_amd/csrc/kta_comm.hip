@@ -302,6 +302,9 @@ int kta_comm_create(kta_ctx *ctx, int nranks, int rank, const uint8_t id[KTA_COM
     if (*slot) return fail(ctx, KTA_ERR_INVALID, "kta_comm_create: the context already has a communicator");
     if (nranks > 1 && kta_internal_count_alive(ctx) && !kta_internal_alive_table(ctx))
         return fail(ctx, KTA_ERR_INVALID, "kta_comm_create: a -c rank of a sharded run needs KTA_FLAG_ALIVE_TABLE (global sequence numbers)");
+    if (nranks > 1 && kta_internal_compaction(ctx))
+        return fail(ctx, KTA_ERR_INVALID, "kta_comm_create: a KTA_FLAG_COMPACTION context cannot be a rank of a sharded run (after the exchange only "
+                                          "the owner of a hash range holds the merged entries)");
     KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
     CommState *st = new CommState();
     st->nranks = nranks;

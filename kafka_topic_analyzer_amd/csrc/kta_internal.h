@@ -33,6 +33,7 @@ uint32_t kta_internal_partitions(kta_ctx *ctx);
 bool kta_internal_want_keys(kta_ctx *ctx);   // -c, the key sketch, the hot keys or the partitioner: the handlers read key_off / key_bytes
 bool kta_internal_count_alive(kta_ctx *ctx);
 bool kta_internal_alive_table(kta_ctx *ctx);
+bool kta_internal_compaction(kta_ctx *ctx);    // KTA_FLAG_COMPACTION
 uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);

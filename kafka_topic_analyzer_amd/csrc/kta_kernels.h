@@ -296,6 +296,21 @@ hipError_t launch_partitioner(const PartitionerColumns &c, uint64_t n, uint32_t 
 // out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P and Q (kta_partitioner_info)
 void partitioner_lds_plan(uint32_t P, uint32_t Q, uint32_t out[3]);
 
+// Compaction what-if (KTA_FLAG_COMPACTION, kta_compaction.hip; the rule and the vector's layout are kta_compaction.h's): the
+// live vector u64[5 P + 6], every word a sum that the workgroups of launch_compaction add their LDS words to.
+constexpr uint32_t kCompactionMaxPartitions = 4096;         // 32 P bytes of LDS, 128 KiB up there
+struct CompactionColumns {
+    SketchColumns k;            // what the key sketch reads
+    const int32_t *val_len;     // the batch's record 0, plain i32 (both layouts), as k.key_len
+    const uint64_t *seq;        // null: record i has the sequence number base_seq + i
+};
+// the replay of records [0, n) of c against the last-writer table, n <= kCompactionLaunchMax; stats: u64[3] += keyed
+// records looked at, LDS adds, reserved; *workgroups = the grid
+hipError_t launch_compaction(const CompactionColumns &c, uint64_t n, uint64_t base_seq, uint32_t P, const uint64_t *table, uint64_t *acc,
+                             uint64_t *stats, int cu_count, uint32_t *workgroups, hipStream_t s);
+// out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P (kta_compaction_info)
+void compaction_lds_plan(uint32_t P, uint32_t out[3]);
+
 // Record filter (kta_set_filter, kta_filter.hip; the rules are kta_filter.h's): one slice of a device batch, compacted in
 // record order into a raw-layout scratch batch by three launches (count per tile, prefix of the counts, scatter).
 constexpr uint64_t kFilterSlice = 1ull << 26;                                   // records per slice, at most

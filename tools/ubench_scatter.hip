@@ -2,10 +2,14 @@
 //   (1) scattered writes of 2^26 8-byte pairs into a 1 GiB workspace, by write granularity: 8 B per lane at
 //       random places, aligned 32 B / 64 B / 128 B blocks written by one lane or by a lane group;
 //   (2) LDS atomic throughput: 32- and 64-bit add / max / CAS on random slots of a 64 KiB table.
+//   ubench_scatter reads : instead, (3) plain 8-byte reads at random slots of a u64[2^32] table (32 GiB, the alive-key
+//       table's size: every read a 64-byte line of its own, beyond L2), 2^28 of them, 1 or 4 independent reads per lane
+//       in flight — what the compaction pass's table read is held against.  One line per variant.
 // hipcc --offload-arch=gfx950 -O3 tools/ubench_scatter.hip -o tools/ubench_scatter
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z)
 {
@@ -64,6 +68,23 @@ __global__ __launch_bounds__(512) void k_lds(uint64_t iters, uint64_t seed, unsi
     if (acc == 0x123456789ull) *sink = acc;
 }
 
+// PER independent 8-byte reads per lane and trip, every one at a random slot of table[0, mask]
+template <int PER>
+__global__ __launch_bounds__(256) void k_reads(const unsigned long long *__restrict__ table, uint64_t mask, uint64_t n, uint64_t seed,
+                                               unsigned long long *sink)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256 * PER;
+    unsigned long long acc = 0;
+    for (uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * PER; i + PER <= n; i += stride) {
+        unsigned long long v[PER];
+#pragma unroll
+        for (int k = 0; k < PER; k++) v[k] = table[mix64(seed + i + k) & mask];
+#pragma unroll
+        for (int k = 0; k < PER; k++) acc += v[k];
+    }
+    if (acc == 0x123456789ull) *sink = acc;
+}
+
 template <typename F>
 float time_ms(F f, int reps)
 {
@@ -83,8 +104,25 @@ float time_ms(F f, int reps)
     return best;
 }
 
-int main()
+int reads_main()
 {
+    const uint64_t slots = 1ull << 32, n = 1ull << 28;
+    unsigned long long *table, *sink;
+    if (hipMalloc(&table, slots * 8) != hipSuccess) { printf("alloc failed\n"); return 1; }
+    hipMalloc(&sink, 8);
+    hipMemset(table, 0, slots * 8);
+    const int grid = 256 * 8;
+    float ms = time_ms([&](int r) { hipLaunchKernelGGL((k_reads<1>), dim3(grid), dim3(256), 0, 0, table, slots - 1, n, (uint64_t)(3 + r), sink); }, 3);
+    printf("reads %-46s %7.3f ms  %6.2f G reads/s\n", "8 B at random slots of 32 GiB, 1 per lane and trip", ms, n / ms / 1e6);
+    ms = time_ms([&](int r) { hipLaunchKernelGGL((k_reads<4>), dim3(grid), dim3(256), 0, 0, table, slots - 1, n, (uint64_t)(3 + r), sink); }, 3);
+    printf("reads %-46s %7.3f ms  %6.2f G reads/s\n", "8 B at random slots of 32 GiB, 4 per lane and trip", ms, n / ms / 1e6);
+    hipFree(table);
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1 && !strcmp(argv[1], "reads")) return reads_main();
     const uint64_t ws_words = 1ull << 27;    // 1 GiB workspace
     const uint64_t n_words = 1ull << 26;     // 512 MiB of pairs
     unsigned long long *ws, *sink;
