@@ -135,6 +135,22 @@ __device__ __forceinline__ int4 load16(const void *col, uint64_t i)   // 16-byte
 // not loaded iff its summary is VALID, its header COMPACT, it lies wholly inside [rec0, rec0 + n) and its largest
 // partition counts — then every record of it counts and the tile's extrema are the summary's (kta_tile.h).  Uniform per
 // workgroup and tile, and decided here because the loads run a tile ahead of the accumulation.
+// The rule itself, from uniform values alone (h: a COMPACT header): whether tile T is summarised for this scan, and if
+// so what it gives the earliest (lo) and the latest (hi) timestamp.
+__device__ __forceinline__ bool tile_summed(const kta_tile_hdr &h, const kta_tile_sum &s, uint64_t T, const ScanColumns &c, uint64_t n,
+                                            uint32_t pc, long long &lo, long long &hi)
+{
+    const uint64_t first = T * KTA_TILE_RECORDS;
+    if (!((s.flags & KTA_TILE_SUM_VALID) && first >= c.rec0 && first + KTA_TILE_RECORDS <= c.rec0 + n && s.part_max < pc)) return false;
+    // a counted record without a timestamp is t = 0 (metric.rs:209); ts_base + ts_span is modular, as tile_unpack_ts
+    const bool timed = (s.flags & KTA_TILE_SUM_TIMED) != 0, untimed = (s.flags & KTA_TILE_SUM_UNTIMED) != 0;
+    lo = timed ? (long long)h.ts_base : LLONG_MAX;
+    hi = timed ? (long long)((uint64_t)h.ts_base + s.ts_span) : LLONG_MIN;
+    lo = (untimed && 0ll < lo) ? 0ll : lo;
+    hi = (untimed && 0ll > hi) ? 0ll : hi;
+    return true;
+}
+
 template <bool NT, bool SUM = false>
 __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid, uint64_t n = 0, uint32_t pc = 0)
 {
@@ -161,15 +177,8 @@ __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, ui
     q.p.x = p.x;
     q.p.y = p.y;
     if (SUM) {
-        const kta_tile_sum &s = sm;
-        const uint64_t first = T * KTA_TILE_RECORDS;
-        if ((s.flags & KTA_TILE_SUM_VALID) && first >= c.rec0 && first + KTA_TILE_RECORDS <= c.rec0 + n && s.part_max < pc) {
-            // a counted record without a timestamp is t = 0 (metric.rs:209); ts_base + ts_span is modular, as tile_unpack_ts
-            const bool timed = (s.flags & KTA_TILE_SUM_TIMED) != 0, untimed = (s.flags & KTA_TILE_SUM_UNTIMED) != 0;
-            long long lo = timed ? (long long)h.ts_base : LLONG_MAX;
-            long long hi = timed ? (long long)((uint64_t)h.ts_base + s.ts_span) : LLONG_MIN;
-            lo = (untimed && 0ll < lo) ? 0ll : lo;
-            hi = (untimed && 0ll > hi) ? 0ll : hi;
+        long long lo, hi;
+        if (tile_summed(h, sm, T, c, n, pc, lo, hi)) {
             q.t0.x = lo;
             q.t0.y = hi;
             q.compact = kQuadCompact | kQuadSummed | (lens16 ? kQuadLens16 : 0u);
@@ -464,6 +473,8 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, u
 // The workgroup's extrema and bad-partition count into the globals of its partial row: wave shuffle tree, then the
 // four waves through LDS (kta_metrics_scan_packed's; kta_metrics_scan keeps its own copy of these lines, so that its
 // instantiations compile to the instructions they had before there was a second kernel).
+// MERGE: the row holds the globals of another kernel's workgroup already (kta_metrics_scan_packed_rest): fold into them.
+template <bool MERGE = false>
 __device__ __forceinline__ void write_scan_globals(const LaneState &st, long long (&s_red)[kWG / 64][6], uint64_t *row, uint32_t P,
                                                    uint32_t tid)
 {
@@ -495,6 +506,15 @@ __device__ __forceinline__ void write_scan_globals(const LaneState &st, long lon
             bad += s_red[w][4];
         }
         uint64_t *g = row + (uint64_t)P * kScanCols;
+        if (MERGE) {   // (the row's smallest size is LLONG_MAX where there was none: above every size)
+            const long long gtmin = (long long)g[SG_TMIN], gtmax = (long long)g[SG_TMAX];
+            const long long gsmin = (long long)g[SG_SMIN], gsmax = (long long)g[SG_SMAX];
+            tmin = gtmin < tmin ? gtmin : tmin;
+            tmax = gtmax > tmax ? gtmax : tmax;
+            smin = gsmin < smin ? gsmin : smin;
+            smax = gsmax > smax ? gsmax : smax;
+            bad += (long long)g[SG_BAD];
+        }
         g[SG_TMIN] = (uint64_t)tmin;
         g[SG_TMAX] = (uint64_t)tmax;
         g[SG_SMIN] = (smin == 0xFFFFFFFFll) ? (uint64_t)LLONG_MAX : (uint64_t)smin;
@@ -928,8 +948,264 @@ __device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid,
     else packed_quad<-1, SUM>(q, valid, P, rep_log2, rep, L, st);
 }
 
-// SUM: read the tiles' summaries (c.sum non-null).  The other instantiation is the kernel of before, for a batch without
-// summaries and for scan_variant bit 32.
+// ---- the lean loop of the summarised compact / u16 tiles (SUM kernels) ---------------------------------------------
+// The flagship's tiles are all of one kind: compact, u16 lengths, summarised.  Such a tile needs no per-record mask, no
+// bad-partition count and no timestamps: 6 vector registers per lane (a Quad has 20) and two uniform extrema.  The lean
+// loop keeps a ring of such slots, unrolled (no rotation moves), and the tiles' headers and summaries one tile further
+// ahead than the vector loads in scalar registers, so that no vector load waits for a scalar miss of its own tile.
+// Any other tile (cut by rec0 or n, raw, i32 lengths, part_max >= pc, no VALID summary) is left to the loop of before:
+// see the kernel.
+#ifndef KTA_LEAN_PREFETCH
+#define KTA_LEAN_PREFETCH 1
+#endif
+constexpr int kLeanPrefetch = KTA_LEAN_PREFETCH;   // tiles the lean loop loads ahead of the one it accumulates (1 or 2)
+static_assert(kLeanPrefetch == 1 || kLeanPrefetch == 2, "the lean ring has two or three slots");
+
+struct LeanSlot {
+    v2i p;    // four u16 partitions
+    int4 k;   // four u16 key lengths (x, y), four u16 value lengths (z, w)
+};
+constexpr uint64_t kTileColBytes = (uint64_t)KTA_TILE_RECORDS * 4u;   // a tile's own bytes of an i32 column
+
+// whether the lean loop takes tile T (uniform), and its extrema if so
+__device__ __forceinline__ bool lean_tile(const kta_tile_hdr &h, const kta_tile_sum &s, uint64_t T, const ScanColumns &c, uint64_t n,
+                                          uint32_t pc, long long &lo, long long &hi)
+{
+    return h.mode == KTA_TILE_COMPACT && h.lens == KTA_TILE_LENS_U16 && tile_summed(h, s, T, c, n, pc, lo, hi);
+}
+
+// the tile's base is uniform, the lane's byte offsets (8 * tid, 16 * tid) constant over the loop
+template <bool NT>
+__device__ __forceinline__ void lean_load(LeanSlot &s, const ScanColumns &c, uint64_t T, uint32_t off8, uint32_t off16)
+{
+    const char *pb = reinterpret_cast<const char *>(c.partition) + T * kTileColBytes;
+    const char *kb = reinterpret_cast<const char *>(c.key_len) + T * kTileColBytes;
+    const v2i *pp = reinterpret_cast<const v2i *>(pb + off8);
+    const v4i *kp = reinterpret_cast<const v4i *>(kb + off16);
+    s.p = NT ? __builtin_nontemporal_load(pp) : *pp;
+    const v4i k = NT ? __builtin_nontemporal_load(kp) : *kp;
+    s.k = make_int4(k.x, k.y, k.z, k.w);
+}
+
+// packed_quad_lens<true> of four records that all count; the timestamps' extrema are the caller's (uniform)
+__device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
+{
+    uint32_t pt[4], ku[4], vu[4], tomb[4], knull[4], ks[4], vs[4];
+    tile_u16x4((uint32_t)s.p.x, (uint32_t)s.p.y, pt);
+    tile_u16x4((uint32_t)s.k.x, (uint32_t)s.k.y, ku);
+    tile_u16x4((uint32_t)s.k.z, (uint32_t)s.k.w, vu);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        knull[j] = ku[j] == KTA_COMPACT_LEN_NONE;
+        tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
+        ks[j] = knull[j] ? 0u : ku[j];
+        vs[j] = tomb[j] ? 0u : vu[j];
+    }
+    uint32_t lo[4], hi[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {                  // metric.rs:249-251
+        const uint32_t sz = ks[j] + vs[j];
+        lo[j] = tomb[j] ? 0xFFFFFFFFu : sz;
+        hi[j] = tomb[j] ? 0u : sz;
+    }
+    st.smin = min(min(min(lo[0], lo[1]), min(lo[2], lo[3])), st.smin);
+    st.smax = max(max(max(hi[0], hi[1]), max(hi[2], hi[3])), st.smax);
+#if KTA_PACKED_LOADS_ONLY
+    st.bad += pt[0] ^ pt[1] ^ pt[2] ^ pt[3];   // (keeps the partition loads alive)
+    return;
+#endif
+    if (pt[0] == pt[1] && pt[0] == pt[2] && pt[0] == pt[3]) {
+        const uint32_t slot = (pt[0] << rep_log2) | rep;
+        const uint32_t tombs = tomb[0] + tomb[1] + tomb[2] + tomb[3];
+        const uint32_t knulls = knull[0] + knull[1] + knull[2] + knull[3];
+        atomicAdd(&L.W1[slot], pack_dwords(4u | (tombs << 16), ks[0] + ks[1] + ks[2] + ks[3]));
+        atomicAdd(&L.W2[slot], pack_dwords(knulls, vs[0] + vs[1] + vs[2] + vs[3]));
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t slot = (pt[j] << rep_log2) | rep;
+        atomicAdd(&L.W1[slot], pack_dwords(1u | (tomb[j] << 16), ks[j]));
+        atomicAdd(&L.W2[slot], pack_dwords(knull[j], vs[j]));
+    }
+}
+
+// The lean kernel's workgroup: its LDS words and lane state, the front flush, the row (the lines of
+// kta_metrics_scan_packed<NT, false>, which keeps its own so that it compiles as it did).
+struct PackedWg {
+    PackedLds L;
+    uint32_t P, rep_log2, rep, tid;
+    LaneState st;
+
+    __device__ __forceinline__ PackedWg(unsigned long long *lds, uint32_t P_, uint32_t rep_log2_) : P(P_), rep_log2(rep_log2_)
+    {
+        tid = threadIdx.x;
+        const uint32_t slots = P << rep_log2;
+        L = PackedLds{lds, lds + slots, lds + 2 * slots};
+        for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
+        __syncthreads();
+        rep = tid & ((1u << rep_log2) - 1u);
+        st.tmin = LLONG_MAX;
+        st.tmax = LLONG_MIN;
+        st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
+        st.smax = 0u;
+        st.bad = 0u;
+    }
+    __device__ __forceinline__ void front_flush() const
+    {
+        __syncthreads();
+        for (uint32_t p = tid; p < P; p += kWG) {
+            unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
+            for (uint32_t r = 0; r < (1u << rep_log2); r++) {
+                const uint32_t s = (p << rep_log2) | r;
+                w1 += L.W1[s];
+                w2 += L.W2[s];
+                L.W1[s] = 0ull;
+                L.W2[s] = 0ull;
+            }
+            L.B[p] += w1 & 0xFFFFull;
+            L.B[P + p] += (w1 >> 16) & 0xFFFFull;
+            L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
+            L.B[3u * P + p] += w1 >> 32;
+            L.B[4u * P + p] += w2 >> 32;
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void write_row(uint64_t *row, long long (&s_red)[kWG / 64][6]) const
+    {
+        for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level)
+#pragma unroll
+            for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] = L.B[j * P + p];
+        write_scan_globals(st, s_red, row, P, tid);
+    }
+};
+
+// The lean kernel of a summary-reading scan (kta_metrics_scan_packed<NT, true>); kta_metrics_scan_packed_rest is launched
+// behind it with the same grid.
+// Its loop takes the summarised compact / u16 tiles (lean_tile) through a ring of LeanSlots, unrolled, with the next
+// undecided tile's header and summary already requested (scalar loads: a step ahead of the vector loads they decide on),
+// and folds their timestamp extrema into two uniform words.  Every decision is made from uniform values: header,
+// summary, rec0, n, P.  A tile that does not qualify is not accumulated here.  Its step — tile = workgroup + step x grid
+// — goes on the row's list (kLeanListed steps at most, in three of the row's globals that no fold reads) and the ring
+// goes on behind it; where the list is full the workgroup ends at that tile and hands it and all that follow over.
+// The workgroup of the same index in kta_metrics_scan_packed_rest takes the listed tiles and the handed-over ones
+// through the loop over whole Quads and adds them to the row; with an empty list it reads three words and ends.  So a
+// cut first or last tile, or one raw tile in a thousand, leaves its workgroup in the lean loop, and a batch of which no
+// tile qualifies runs in the loop it ran in before.
+constexpr uint32_t kLeanListed = 4;
+constexpr uint32_t kScanListA = 5, kScanHandover = 6, kScanListB = 7;   // (SG_NREC's word, unused by the scans, and the two behind it)
+// entry i of the list (a step + 1, 0: none): four 32-bit halves of two row words, filled in ascending order
+__device__ __forceinline__ uint32_t lean_list_entry(uint64_t list_a, uint64_t list_b, uint32_t i)
+{
+    return (uint32_t)((i < 2 ? list_a : list_b) >> (32u * (i & 1u)));
+}
+
+template <bool NT>
+__device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t n, uint32_t P, uint32_t rep_log2,
+                                                 uint64_t *__restrict__ partials, uint32_t row_len, unsigned long long *lds,
+                                                 long long (&s_red)[kWG / 64][6])
+{
+    PackedWg wg(lds, P, rep_log2);
+    const uint32_t tid = wg.tid;
+    // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
+    const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
+    const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+    uint32_t since_flush = 0;
+    uint64_t tile = blockIdx.x;
+    const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
+    const uint64_t last = t0 + ntiles - 1;
+    const uint64_t G = gridDim.x;
+    uint64_t end = ntiles;                    // this kernel's tiles end here: the batch's end, or the handed-over tile
+    uint64_t issued = tile;                   // the next tile to decide on and load: kLeanPrefetch steps ahead of `tile`
+    uint32_t istep = 0, listed = 0;           // issued = workgroup + istep x grid; entries on the list
+    uint64_t list_a = 0, list_b = 0;          // the list: four steps + 1, 32 bits each
+    uint64_t handover = 0;                    // the step the rest kernel takes everything from, + 1
+    long long u_tmin = LLONG_MAX, u_tmax = LLONG_MIN;   // the lean tiles' extrema: uniform, in scalar registers
+    kta_tile_hdr ah;                          // header and summary of tile `issued`, requested a step before they are
+    uint2 as;                                 // used (the summary as its two dwords: taking the u16 fields apart
+                                              // belongs to the use, not to the load)
+    // (the index is clamped, not the load skipped — a skipped load merges with the old value, and the merge waits —
+    // so nothing past the batch's last tile is read)
+    auto look_ahead = [&]() {
+        const uint64_t T = t0 + issued < last ? t0 + issued : last;
+        ah = c.hdr[T], as = reinterpret_cast<const uint2 *>(c.sum)[T];
+    };
+    // One step of the ring's front: decide on tile `issued` and load it into slot s; v: the slot holds a lean tile.
+    // The loads go out whatever the decision (of a tile that is not lean or lies past the end — then the batch's last
+    // tile again — they fetch bytes of the tile's own that nobody uses): a slot is then waited for behind the same
+    // number of younger loads on every path, and the wait can let those stay in flight.
+    auto issue = [&](LeanSlot &s, bool &v) {
+        const uint64_t T = t0 + issued < last ? t0 + issued : last;
+        const bool in = issued < end;
+        long long lo = LLONG_MAX, hi = LLONG_MIN;
+        const kta_tile_sum sm{as.x, (uint16_t)(as.y & 0xFFFFu), (uint16_t)(as.y >> 16)};
+        v = lean_tile(ah, sm, T, c, n, pc, lo, hi) && in;
+        lean_load<NT>(s, c, T, 8u * tid, 16u * tid);
+        u_tmin = (v && lo < u_tmin) ? lo : u_tmin;
+        u_tmax = (v && hi > u_tmax) ? hi : u_tmax;
+        if (in && !v) {
+            if (listed == kLeanListed) {
+                handover = (uint64_t)istep + 1;
+                end = issued;
+            } else {
+                const uint64_t e = (uint64_t)(istep + 1u) << (32u * (listed & 1u));
+                if (listed < 2) list_a |= e;
+                else list_b |= e;
+                listed++;
+            }
+        }
+        issued += G;
+        istep++;
+        look_ahead();
+    };
+    auto take = [&](const LeanSlot &s, bool v) {
+        if (v) {
+            lean_quad(s, rep_log2, wg.rep, wg.L, wg.st);
+            if (++since_flush == kFrontFlushTiles) {
+                wg.front_flush();
+                since_flush = 0;
+            }
+        }
+        tile += G;
+    };
+    // the ring, unrolled: no rotation moves, one exit
+    LeanSlot s0, s1, s2;
+    bool v0 = false, v1 = false, v2 = false;
+    if (tile < ntiles) {   // (else there is no tile to clamp to)
+        look_ahead();
+        issue(s0, v0);
+        if (kLeanPrefetch == 2) issue(s1, v1);
+    }
+    while (tile < end) {
+        if (kLeanPrefetch == 2) {
+            issue(s2, v2);
+            take(s0, v0);
+            issue(s0, v0);
+            take(s1, v1);
+            issue(s1, v1);
+            take(s2, v2);
+        } else {
+            issue(s1, v1);
+            take(s0, v0);
+            issue(s0, v0);
+            take(s1, v1);
+        }
+    }
+    wg.front_flush();
+    wg.st.tmin = u_tmin < wg.st.tmin ? u_tmin : wg.st.tmin;
+    wg.st.tmax = u_tmax > wg.st.tmax ? u_tmax : wg.st.tmax;
+    uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
+    wg.write_row(row, s_red);
+    if (tid == 0) {   // (behind the zeroes write_scan_globals put there)
+        uint64_t *g = row + (uint64_t)P * kScanCols;
+        g[kScanListA] = list_a;
+        g[kScanHandover] = handover;
+        g[kScanListB] = list_b;
+    }
+}
+
+// SUM = true: the lean kernel.  SUM = false: the packed scan's loop over whole Quads, for a batch without summaries and
+// for scan_variant bit 32 (its lines are kept as they were, so that it compiles to the instructions it had).
 template <bool NT, bool SUM>
 __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2,
                                                                uint64_t *__restrict__ partials, uint32_t row_len)
@@ -937,6 +1213,10 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
     extern __shared__ unsigned long long lds[];
     __shared__ long long s_red[kWG / 64][6];
 
+    if constexpr (SUM) {
+        packed_scan_lean<NT>(c, n, P, rep_log2, partials, row_len, lds, s_red);
+        return;
+    }
     const uint32_t tid = threadIdx.x;
     const uint32_t slots = P << rep_log2;
     const PackedLds L{lds, lds + slots, lds + 2 * slots};
@@ -1007,6 +1287,110 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
 #pragma unroll
         for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] = L.B[j * P + p];
     write_scan_globals(st, s_red, row, P, tid);
+}
+
+// The tiles the lean kernel's workgroup of the same index left (see there): the listed ones, then every tile from the
+// handed-over step on, through the loop over Quads with one tile loaded ahead; added to the row.
+// The tiles are read WITHOUT their summaries, as kta_metrics_scan_packed<NT, false> reads them — right for every tile,
+// 4 B per record more for a summarised one among the handed-over, and the faster loop where nothing is summarised (the
+// summary-reading loop over Quads was 5 % slower there): the listed tiles never are, and the handed-over ones rarely.
+template <bool NT>
+__global__ __launch_bounds__(kWG) void kta_metrics_scan_packed_rest(ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2,
+                                                                    uint64_t *__restrict__ partials, uint32_t row_len)
+{
+    extern __shared__ unsigned long long lds[];
+    __shared__ long long s_red[kWG / 64][6];
+
+    uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
+    uint64_t *g = row + (uint64_t)P * kScanCols;
+    const uint64_t list_a = g[kScanListA], list_b = g[kScanListB], handover = g[kScanHandover];   // uniform
+    if ((list_a | list_b | handover) == 0) return;   // (write_scan_globals zeroes the three words, behind barriers)
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t slots = P << rep_log2;
+    const PackedLds L{lds, lds + slots, lds + 2 * slots};
+    for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
+    __syncthreads();
+
+    const uint32_t rep = tid & ((1u << rep_log2) - 1u);
+    LaneState st;
+    st.tmin = LLONG_MAX;
+    st.tmax = LLONG_MIN;
+    st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
+    st.smax = 0u;
+    st.bad = 0u;
+
+    auto front_flush = [&]() {
+        __syncthreads();
+        for (uint32_t p = tid; p < P; p += kWG) {
+            unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
+            for (uint32_t r = 0; r < (1u << rep_log2); r++) {
+                const uint32_t s = (p << rep_log2) | r;
+                w1 += L.W1[s];
+                w2 += L.W2[s];
+                L.W1[s] = 0ull;
+                L.W2[s] = 0ull;
+            }
+            L.B[p] += w1 & 0xFFFFull;
+            L.B[P + p] += (w1 >> 16) & 0xFFFFull;
+            L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
+            L.B[3u * P + p] += w1 >> 32;
+            L.B[4u * P + p] += w2 >> 32;
+        }
+        __syncthreads();
+    };
+
+    const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
+    const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+    const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
+    uint32_t since_flush = 0;
+    Quad cur, nxt;
+    // Listed steps that end right before the handed-over one are taken with it (a batch of which no tile qualifies lists
+    // its first four tiles and hands over the fifth: the ring then starts at the first).
+    uint64_t first = handover;   // the step the ring starts at, + 1
+    uint32_t nlist = 0;
+    for (uint32_t li = 0; li < kLeanListed; li++) nlist += lean_list_entry(list_a, list_b, li) != 0u;
+    while (first > 1 && nlist > 0 && lean_list_entry(list_a, list_b, nlist - 1u) == (uint32_t)(first - 1)) {
+        first--;
+        nlist--;
+    }
+    // the other listed tiles, one at a time (four at most, in ascending order)
+    for (uint32_t li = 0; li < nlist; li++) {
+        const uint64_t tile = blockIdx.x + (uint64_t)(lean_list_entry(list_a, list_b, li) - 1u) * gridDim.x;
+        load_tile_quad<NT, false>(cur, c, t0 + tile, tid, n, pc);
+        const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
+        uint32_t valid = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+        accumulate_packed<false>(cur, valid, P, rep_log2, rep, L, st);   // (four tiles: no front flush is due)
+        since_flush++;
+    }
+    // the handed-over tiles, through the ring of Quads: kta_metrics_scan_packed<NT, false>'s loop
+    uint64_t tile = first ? blockIdx.x + (first - 1) * gridDim.x : ntiles;
+    if (tile < ntiles) load_tile_quad<NT, false>(cur, c, t0 + tile, tid, n, pc);
+    while (tile < ntiles) { // uniform per workgroup
+        const uint64_t ntile = tile + gridDim.x;
+        if (ntile < ntiles) load_tile_quad<NT, false>(nxt, c, t0 + ntile, tid, n, pc);
+
+        const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
+        uint32_t valid = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+        accumulate_packed<false>(cur, valid, P, rep_log2, rep, L, st);
+
+        if (++since_flush == kFrontFlushTiles) {
+            front_flush();
+            since_flush = 0;
+        }
+        cur = nxt;
+        tile = ntile;
+    }
+    front_flush();
+
+    for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level, added to the lean kernel's)
+#pragma unroll
+        for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] += L.B[j * P + p];
+    write_scan_globals<true>(st, s_red, row, P, tid);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1632,14 +2016,31 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
         hipLaunchKernelGGL((kta_metrics_scan_packed<NT, SUM>), grid, block, pl.lds_bytes, s, cs, n, P, pl.rep_log2,       \
                            partials, pl.row_len);                                                                   \
     } while (0)
+#define KTA_SCAN_PACKED_REST(NT)                                                                                    \
+    do {                                                                                                            \
+        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed_rest<NT>),  \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);     \
+            if (ea != hipSuccess) return ea;                                                                        \
+        }                                                                                                           \
+        hipLaunchKernelGGL((kta_metrics_scan_packed_rest<NT>), grid, block, pl.lds_bytes, s, cs, n, P, pl.rep_log2, \
+                           partials, pl.row_len);                                                                   \
+    } while (0)
         if (cs.sum) {
+            // the lean kernel, then — same grid, same rows — the tiles its workgroups left (none, where every tile is
+            // summarised, compact and u16: a workgroup of the second kernel then reads one word and ends)
             if (pl.nontemporal) KTA_SCAN_PACKED(true, true);
             else KTA_SCAN_PACKED(false, true);
+            hipError_t el = hipGetLastError();
+            if (el != hipSuccess) return el;
+            if (pl.nontemporal) KTA_SCAN_PACKED_REST(true);
+            else KTA_SCAN_PACKED_REST(false);
         } else {
             if (pl.nontemporal) KTA_SCAN_PACKED(true, false);
             else KTA_SCAN_PACKED(false, false);
         }
 #undef KTA_SCAN_PACKED
+#undef KTA_SCAN_PACKED_REST
         return hipGetLastError();
     }
     switch (pl.variant) {
