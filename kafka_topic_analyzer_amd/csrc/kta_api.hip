@@ -1,6 +1,7 @@
 // kta_api.hip — the extern "C" boundary of libkta_hip.so (include/kta_hip.h): context,
 // pinned struct-of-arrays staging ring, H2D/compute streams, result decode.
-// Host code only; the kernels are in kta_kernels.hip.  There is no CPU fallback: every
+// Host code only; the kernels are in the other .hip files (the scan: kta_kernels.hip; the alive table's single-kernel
+// family: kta_alive_table.hip), behind the launchers of kta_kernels.h.  There is no CPU fallback: every
 // entry point that computes anything needs a gfx950 device.
 #include "../../include/kta_hip.h"
 #include "kta_compaction.h"

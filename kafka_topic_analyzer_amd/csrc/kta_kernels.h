@@ -1,5 +1,6 @@
 // kta_kernels.h — internal launch interface between the C-ABI layer (kta_api.hip) and the
-// gfx950 kernels (kta_kernels.hip).  Not part of the public ABI.
+// gfx950 kernels: the metrics scan and its fold (kta_kernels.hip) and the single-kernel alive-table family
+// (kta_alive_table.hip).  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,13 +1,12 @@
 // kta_kernels.hip — hand-written gfx950 (MI355X / CDNA4) kernels for the per-record
-// metric-accumulation hot path of kafka-topic-analyzer.  Integer/byte work, HBM-bound:
+// metric-accumulation hot path of kafka-topic-analyzer: the metrics scan (K1, K1p), the fold of its partial rows (K5),
+// the tile expansion and the result vector's initialisation, with their launchers.  Integer/byte work, HBM-bound:
 // no MFMA.  wave = 64 lanes, 256-thread workgroups, 16 B/lane coalesced loads,
 // LDS-staged per-workgroup partial counters, deterministic integer reductions.
+// (The single-kernel alive-table family is kta_alive_table.hip.)
 //
 // Reference semantics (paths under /root/reference):
 //   kta_metrics_scan   src/metric.rs:207-252  MessageMetrics::handle_message
-//   kta_alive_update   src/metric.rs:289-304  LogCompactionInMemoryMetrics::handle_message
-//                      src/metric.rs:256-260  fnv1a        src/fnv32.rs:92-101  FnvHasher::write
-//   kta_alive_count    src/metric.rs:282-284  sum_all_alive
 #include "kta_kernels.h"
 
 #include <limits.h>
@@ -151,6 +150,16 @@ __device__ __forceinline__ bool tile_summed(const kta_tile_hdr &h, const kta_til
     return true;
 }
 
+// TILED: the lane's four records of a tile lie at a .. a + 3 of the batch (a wraps where the tile begins below rec0);
+// bit j = record j is one of the batch's n
+__device__ __forceinline__ uint32_t quad_valid(uint64_t a, uint64_t n)
+{
+    uint32_t valid = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+    return valid;
+}
+
 template <bool NT, bool SUM = false>
 __device__ __forceinline__ void load_tile_quad(Quad &q, const ScanColumns &c, uint64_t T, uint32_t tid, uint64_t n = 0, uint32_t pc = 0)
 {
@@ -230,10 +239,12 @@ __device__ __forceinline__ void quad_lens(const Quad &q, int4 &k, int4 &v)
     }
 }
 
+// A lane's extrema and bad-partition count; a new one has seen nothing.
 struct LaneState {
-    long long tmin, tmax;
-    uint32_t smin, smax;
-    uint32_t bad;
+    long long tmin = LLONG_MAX, tmax = LLONG_MIN;
+    uint32_t smin = 0xFFFFFFFFu;   // never a real size (max real size is 2^32-2)
+    uint32_t smax = 0u;
+    uint32_t bad = 0u;
 };
 
 constexpr uint32_t kHistBuckets = 34; // [0] None, [1] length 0, [2+k] 2^k <= length < 2^(k+1)
@@ -471,8 +482,7 @@ __device__ __forceinline__ void accumulate_quad(const Quad &q, uint32_t valid, u
 }
 
 // The workgroup's extrema and bad-partition count into the globals of its partial row: wave shuffle tree, then the
-// four waves through LDS (kta_metrics_scan_packed's; kta_metrics_scan keeps its own copy of these lines, so that its
-// instantiations compile to the instructions they had before there was a second kernel).
+// four waves through LDS.  The end of every scan kernel.
 // MERGE: the row holds the globals of another kernel's workgroup already (kta_metrics_scan_packed_rest): fold into them.
 template <bool MERGE = false>
 __device__ __forceinline__ void write_scan_globals(const LaneState &st, long long (&s_red)[kWG / 64][6], uint64_t *row, uint32_t P,
@@ -573,11 +583,6 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
 
     const uint32_t rep = tid & ((1u << rep_log2) - 1u);
     LaneState st;
-    st.tmin = LLONG_MAX;
-    st.tmax = LLONG_MIN;
-    st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
-    st.smax = 0u;
-    st.bad = 0u;
 
     uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
     bool first_flush = true;
@@ -663,9 +668,7 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
             if (ahead < ntiles) load_tile_quad<NT>(kTilePrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid);
 
             const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
-            uint32_t valid = 0u;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
+            const uint32_t valid = quad_valid(a, n);
             accumulate_quad<VARIANT, ANALYTICS, TIMELINE, true>(cur, valid, P, rep_log2, rep, L, st, ta, T);
 
             if (++since_flush == kFlushTiles) {
@@ -724,45 +727,7 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan(ScanColumns c, uint64_t 
     }
 
     flush();
-
-    // per-workgroup extrema: wave shuffle tree, then 4 waves through LDS
-    long long tmin = st.tmin, tmax = st.tmax;
-    long long smin = (long long)st.smin, smax = (long long)st.smax, bad = (long long)st.bad;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const long long a = __shfl_xor(tmin, off), b = __shfl_xor(tmax, off);
-        const long long cmin = __shfl_xor(smin, off), cmax = __shfl_xor(smax, off);
-        const long long d = __shfl_xor(bad, off);
-        tmin = a < tmin ? a : tmin;
-        tmax = b > tmax ? b : tmax;
-        smin = cmin < smin ? cmin : smin;
-        smax = cmax > smax ? cmax : smax;
-        bad += d;
-    }
-    const uint32_t wave = tid >> 6;
-    if ((tid & 63u) == 0u) {
-        s_red[wave][0] = tmin; s_red[wave][1] = tmax; s_red[wave][2] = smin;
-        s_red[wave][3] = smax; s_red[wave][4] = bad;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (uint32_t w = 1; w < kWG / 64; w++) {
-            tmin = s_red[w][0] < tmin ? s_red[w][0] : tmin;
-            tmax = s_red[w][1] > tmax ? s_red[w][1] : tmax;
-            smin = s_red[w][2] < smin ? s_red[w][2] : smin;
-            smax = s_red[w][3] > smax ? s_red[w][3] : smax;
-            bad += s_red[w][4];
-        }
-        uint64_t *g = row + (uint64_t)P * kScanCols;
-        g[SG_TMIN] = (uint64_t)tmin;
-        g[SG_TMAX] = (uint64_t)tmax;
-        g[SG_SMIN] = (smin == 0xFFFFFFFFll) ? (uint64_t)LLONG_MAX : (uint64_t)smin;
-        g[SG_SMAX] = (uint64_t)smax;
-        g[SG_BAD] = (uint64_t)bad;
-        g[SG_NREC] = 0;
-        g[6] = 0;
-        g[7] = 0;
-    }
+    write_scan_globals(st, s_red, row, P, tid);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1030,8 +995,8 @@ __device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, 
     }
 }
 
-// The lean kernel's workgroup: its LDS words and lane state, the front flush, the row (the lines of
-// kta_metrics_scan_packed<NT, false>, which keeps its own so that it compiles as it did).
+// The workgroup of every packed scan kernel: its LDS words, carved out of the dynamic LDS and zeroed, its lane state,
+// the front flush and the row.
 struct PackedWg {
     PackedLds L;
     uint32_t P, rep_log2, rep, tid;
@@ -1045,12 +1010,8 @@ struct PackedWg {
         for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
         __syncthreads();
         rep = tid & ((1u << rep_log2) - 1u);
-        st.tmin = LLONG_MAX;
-        st.tmax = LLONG_MIN;
-        st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
-        st.smax = 0u;
-        st.bad = 0u;
     }
+    // front level into back level: thread p sums and zeroes partition p's replicas, between two barriers
     __device__ __forceinline__ void front_flush() const
     {
         __syncthreads();
@@ -1071,12 +1032,18 @@ struct PackedWg {
         }
         __syncthreads();
     }
+    // the row, from the back level (behind the last front_flush).  MERGE: added to what another kernel's workgroup wrote.
+    template <bool MERGE = false>
     __device__ __forceinline__ void write_row(uint64_t *row, long long (&s_red)[kWG / 64][6]) const
     {
         for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level)
 #pragma unroll
-            for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] = L.B[j * P + p];
-        write_scan_globals(st, s_red, row, P, tid);
+            for (uint32_t j = 0; j < kScanCols; j++) {
+                uint64_t &o = row[(uint64_t)p * kScanCols + j];
+                if (MERGE) o += L.B[j * P + p];
+                else o = L.B[j * P + p];
+            }
+        write_scan_globals<MERGE>(st, s_red, row, P, tid);
     }
 };
 
@@ -1205,7 +1172,7 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
 }
 
 // SUM = true: the lean kernel.  SUM = false: the packed scan's loop over whole Quads, for a batch without summaries and
-// for scan_variant bit 32 (its lines are kept as they were, so that it compiles to the instructions it had).
+// for scan_variant bit 32.
 template <bool NT, bool SUM>
 __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2,
                                                                uint64_t *__restrict__ partials, uint32_t row_len)
@@ -1217,40 +1184,8 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
         packed_scan_lean<NT>(c, n, P, rep_log2, partials, row_len, lds, s_red);
         return;
     }
-    const uint32_t tid = threadIdx.x;
-    const uint32_t slots = P << rep_log2;
-    const PackedLds L{lds, lds + slots, lds + 2 * slots};
-    for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
-    __syncthreads();
-
-    const uint32_t rep = tid & ((1u << rep_log2) - 1u);
-    LaneState st;
-    st.tmin = LLONG_MAX;
-    st.tmax = LLONG_MIN;
-    st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
-    st.smax = 0u;
-    st.bad = 0u;
-
-    auto front_flush = [&]() {
-        __syncthreads();
-        for (uint32_t p = tid; p < P; p += kWG) {
-            unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
-            for (uint32_t r = 0; r < (1u << rep_log2); r++) {
-                const uint32_t s = (p << rep_log2) | r;
-                w1 += L.W1[s];
-                w2 += L.W2[s];
-                L.W1[s] = 0ull;
-                L.W2[s] = 0ull;
-            }
-            L.B[p] += w1 & 0xFFFFull;
-            L.B[P + p] += (w1 >> 16) & 0xFFFFull;
-            L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
-            L.B[3u * P + p] += w1 >> 32;
-            L.B[4u * P + p] += w2 >> 32;
-        }
-        __syncthreads();
-    };
-
+    PackedWg wg(lds, P, rep_log2);
+    const uint32_t tid = wg.tid;
     // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
     const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
     const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
@@ -1267,26 +1202,19 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
         if (ahead < ntiles) load_tile_quad<NT, SUM>(kPackedPrefetch == 2 ? nx2 : nxt, c, t0 + ahead, tid, n, pc);
 
         const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
-        uint32_t valid = 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-        accumulate_packed<SUM>(cur, valid, P, rep_log2, rep, L, st);
+        const uint32_t valid = quad_valid(a, n);
+        accumulate_packed<SUM>(cur, valid, P, rep_log2, wg.rep, wg.L, wg.st);
 
         if (++since_flush == kFrontFlushTiles) {
-            front_flush();
+            wg.front_flush();
             since_flush = 0;
         }
         cur = nxt;
         if (kPackedPrefetch == 2) nxt = nx2;
         tile = ntile;
     }
-    front_flush();
-
-    uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
-    for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level)
-#pragma unroll
-        for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] = L.B[j * P + p];
-    write_scan_globals(st, s_red, row, P, tid);
+    wg.front_flush();
+    wg.write_row(partials + (uint64_t)blockIdx.x * row_len, s_red);
 }
 
 // The tiles the lean kernel's workgroup of the same index left (see there): the listed ones, then every tile from the
@@ -1306,40 +1234,8 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed_rest(ScanColumns 
     const uint64_t list_a = g[kScanListA], list_b = g[kScanListB], handover = g[kScanHandover];   // uniform
     if ((list_a | list_b | handover) == 0) return;   // (write_scan_globals zeroes the three words, behind barriers)
 
-    const uint32_t tid = threadIdx.x;
-    const uint32_t slots = P << rep_log2;
-    const PackedLds L{lds, lds + slots, lds + 2 * slots};
-    for (uint32_t i = tid; i < 2 * slots + kScanCols * P; i += kWG) lds[i] = 0ull;
-    __syncthreads();
-
-    const uint32_t rep = tid & ((1u << rep_log2) - 1u);
-    LaneState st;
-    st.tmin = LLONG_MAX;
-    st.tmax = LLONG_MIN;
-    st.smin = 0xFFFFFFFFu; // never a real size (max real size is 2^32-2)
-    st.smax = 0u;
-    st.bad = 0u;
-
-    auto front_flush = [&]() {
-        __syncthreads();
-        for (uint32_t p = tid; p < P; p += kWG) {
-            unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
-            for (uint32_t r = 0; r < (1u << rep_log2); r++) {
-                const uint32_t s = (p << rep_log2) | r;
-                w1 += L.W1[s];
-                w2 += L.W2[s];
-                L.W1[s] = 0ull;
-                L.W2[s] = 0ull;
-            }
-            L.B[p] += w1 & 0xFFFFull;
-            L.B[P + p] += (w1 >> 16) & 0xFFFFull;
-            L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
-            L.B[3u * P + p] += w1 >> 32;
-            L.B[4u * P + p] += w2 >> 32;
-        }
-        __syncthreads();
-    };
-
+    PackedWg wg(lds, P, rep_log2);
+    const uint32_t tid = wg.tid;
     const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
     const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
     const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
@@ -1359,10 +1255,8 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed_rest(ScanColumns 
         const uint64_t tile = blockIdx.x + (uint64_t)(lean_list_entry(list_a, list_b, li) - 1u) * gridDim.x;
         load_tile_quad<NT, false>(cur, c, t0 + tile, tid, n, pc);
         const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
-        uint32_t valid = 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-        accumulate_packed<false>(cur, valid, P, rep_log2, rep, L, st);   // (four tiles: no front flush is due)
+        const uint32_t valid = quad_valid(a, n);
+        accumulate_packed<false>(cur, valid, P, rep_log2, wg.rep, wg.L, wg.st);   // (four tiles: no front flush is due)
         since_flush++;
     }
     // the handed-over tiles, through the ring of Quads: kta_metrics_scan_packed<NT, false>'s loop
@@ -1373,24 +1267,18 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed_rest(ScanColumns 
         if (ntile < ntiles) load_tile_quad<NT, false>(nxt, c, t0 + ntile, tid, n, pc);
 
         const uint64_t a = (t0 + tile) * KTA_TILE_RECORDS + 4u * tid - c.rec0;   // (wraps below rec0)
-        uint32_t valid = 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) valid |= (a + j < n) ? 1u << j : 0u;
-        accumulate_packed<false>(cur, valid, P, rep_log2, rep, L, st);
+        const uint32_t valid = quad_valid(a, n);
+        accumulate_packed<false>(cur, valid, P, rep_log2, wg.rep, wg.L, wg.st);
 
         if (++since_flush == kFrontFlushTiles) {
-            front_flush();
+            wg.front_flush();
             since_flush = 0;
         }
         cur = nxt;
         tile = ntile;
     }
-    front_flush();
-
-    for (uint32_t p = tid; p < P; p += kWG)        // (thread p's own words of the back level, added to the lean kernel's)
-#pragma unroll
-        for (uint32_t j = 0; j < kScanCols; j++) row[(uint64_t)p * kScanCols + j] += L.B[j * P + p];
-    write_scan_globals<true>(st, s_red, row, P, tid);
+    wg.front_flush();
+    wg.write_row<true>(row, s_red);   // (added to the lean kernel's)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1551,365 +1439,6 @@ __global__ void kta_init_vector(uint64_t *vec, uint32_t P, uint64_t *avec)
 }
 
 // ---------------------------------------------------------------------------------------
-// K2 + K3  FNV + last-writer-wins alive table
-// ---------------------------------------------------------------------------------------
-// fnv32.rs:92-101: h = 0x811c9dc5; for each byte: h ^= byte; h *= 0x811c9dc5 (wrapping).
-// The multiplier is the offset basis, not the FNV prime.
-
-constexpr uint32_t kFnvInit = 0x811c9dc5u;
-constexpr uint32_t kFnvMul = 0x811c9dc5u;
-
-__device__ __forceinline__ uint32_t fnv_step(uint32_t h, uint32_t byte) { return (h ^ byte) * kFnvMul; }
-
-// Hash `len` bytes starting at byte pointer k (any alignment) with aligned 4-byte loads.
-// Reads only whole dwords that overlap the key, so it may touch up to 3 bytes before and
-// after the key inside the same 4-byte words (the key blob is allocated padded to 16 B).
-__device__ __forceinline__ uint32_t fnv32_global(const uint8_t *k, uint32_t len)
-{
-    uint32_t h = kFnvInit;
-    if (len == 0) return h;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(k);
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-    uint32_t skip = (uint32_t)(a & 3u);
-    uint32_t word = *w++;
-    word >>= 8u * skip;
-    uint32_t avail = 4u - skip;
-    while (true) {
-        const uint32_t take = len < avail ? len : avail;
-        if (take == 4u) {
-            h = fnv_step(h, word & 0xFFu);
-            h = fnv_step(h, (word >> 8) & 0xFFu);
-            h = fnv_step(h, (word >> 16) & 0xFFu);
-            h = fnv_step(h, word >> 24);
-        } else {
-            for (uint32_t j = 0; j < take; j++) {
-                h = fnv_step(h, word & 0xFFu);
-                word >>= 8;
-            }
-        }
-        len -= take;
-        if (len == 0) break;
-        word = *w++;
-        avail = 4u;
-    }
-    return h;
-}
-
-// table[h] = max(table[h], ((seq+1) << 1) | alive): the entry with the largest sequence
-// number is the last writer in consumption order, which is exactly what sequential
-// BitSet insert/remove leaves behind (metric.rs:273-280, 291-303).  0 == never written.
-__global__ __launch_bounds__(kWG) void kta_alive_update(AliveColumns c, uint64_t n, uint64_t base_seq,
-                                                        unsigned long long *__restrict__ table, WrittenList wl)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
-        const int32_t kl = c.key_len[i];
-        if (kl < 0) continue; // key None: ignored (metric.rs:302)
-        const uint32_t h = fnv32_global(c.key_bytes + c.key_off[i], (uint32_t)kl);
-        const uint64_t s = c.seq ? c.seq[i] : base_seq + i;
-        const unsigned long long v = ((unsigned long long)(s + 1) << 1) | (c.val_len[i] >= 0 ? 1ull : 0ull);
-        note_new_slot(wl, atomicMax(&table[h], v) == 0ull, h);
-    }
-}
-
-// Variant with a RUNNING alive count.  atomicMax returns the previous entry; when this record
-// replaces it (v > old) the number of alive slots changes by flag(v) - flag(old).  Updates to one
-// address are serialised by the memory-side atomic unit, so over any interleaving the deltas
-// telescope to flag(final) - flag(initial): the running sum is exactly sum_all_alive()
-// (metric.rs:282-284) without scanning the 32 GiB table.
-__global__ __launch_bounds__(kWG) void kta_alive_update_counting(AliveColumns c, uint64_t n, uint64_t base_seq,
-                                                                 unsigned long long *__restrict__ table,
-                                                                 long long *__restrict__ running, WrittenList wl)
-{
-    __shared__ long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    long long delta = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
-        const int32_t kl = c.key_len[i];
-        if (kl < 0) continue;
-        const uint32_t h = fnv32_global(c.key_bytes + c.key_off[i], (uint32_t)kl);
-        const uint64_t s = c.seq ? c.seq[i] : base_seq + i;
-        const unsigned long long v = ((unsigned long long)(s + 1) << 1) | (c.val_len[i] >= 0 ? 1ull : 0ull);
-        const unsigned long long old = atomicMax(&table[h], v);
-        note_new_slot(wl, old == 0ull, h);
-        if (v > old) delta += (long long)(v & 1ull) - (long long)(old & 1ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) delta += __shfl_xor(delta, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = delta;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long *>(running), (unsigned long long)t);
-    }
-}
-
-// Variant 2: the counting kernel with a pre-read and the batch walked from its END.  A record only needs
-// the table if no later record owns its slot yet; walking the batch backwards lets the LAST record of a
-// key arrive first, so the earlier ones (a compacted topic repeats its keys) find a larger entry with a
-// plain load and skip the memory-side atomic, which is the scarce resource (section 3.3 of DESIGN.md).
-// Exactness does not depend on the order or on what the load sees: entries only grow, so `seen >= v`
-// proves that a later record has already been applied, and a stale smaller value merely costs the atomic.
-__global__ __launch_bounds__(kWG) void kta_alive_update_filtered(AliveColumns c, uint64_t n, uint64_t base_seq,
-                                                                 unsigned long long *__restrict__ table,
-                                                                 long long *__restrict__ running,
-                                                                 const uint32_t *__restrict__ only_if, WrittenList wl)
-{
-    __shared__ long long s_w[kWG / 64];
-    if (only_if && *only_if == 0u) return;   // stands in for the partitioned pass only when that gave the batch up
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    long long delta = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * kWG + threadIdx.x; j < n; j += stride) {
-        const uint64_t i = n - 1 - j;                      // highest sequence numbers first
-        const int32_t kl = c.key_len[i];
-        if (kl < 0) continue;
-        const uint32_t h = fnv32_global(c.key_bytes + c.key_off[i], (uint32_t)kl);
-        const uint64_t s = c.seq ? c.seq[i] : base_seq + i;
-        const unsigned long long v = ((unsigned long long)(s + 1) << 1) | (c.val_len[i] >= 0 ? 1ull : 0ull);
-        const unsigned long long seen = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen >= v) continue;
-        const unsigned long long old = atomicMax(&table[h], v);
-        note_new_slot(wl, old == 0ull, h);
-        if (v > old) delta += (long long)(v & 1ull) - (long long)(old & 1ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) delta += __shfl_xor(delta, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = delta;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long *>(running), (unsigned long long)t);
-    }
-}
-
-// Ablation kernels (alive_variant 8 / 9): hash only (h -> scratch) and table update only
-// (h <- scratch).  Used to attribute time; the pair is also a valid two-phase implementation.
-__global__ __launch_bounds__(kWG) void kta_alive_hash_only(AliveColumns c, uint64_t n, uint32_t *__restrict__ hout)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
-        const int32_t kl = c.key_len[i];
-        hout[i] = kl < 0 ? 0u : fnv32_global(c.key_bytes + c.key_off[i], (uint32_t)kl);
-    }
-}
-
-__global__ __launch_bounds__(kWG) void kta_alive_apply_only(AliveColumns c, uint64_t n, uint64_t base_seq,
-                                                            const uint32_t *__restrict__ hin,
-                                                            unsigned long long *__restrict__ table, WrittenList wl)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
-        if (c.key_len[i] < 0) continue;
-        const uint64_t s = c.seq ? c.seq[i] : base_seq + i;
-        const unsigned long long v = ((unsigned long long)(s + 1) << 1) | (c.val_len[i] >= 0 ? 1ull : 0ull);
-        note_new_slot(wl, atomicMax(&table[hin[i]], v) == 0ull, hin[i]);
-    }
-}
-
-__global__ __launch_bounds__(kWG) void kta_fnv32(const uint8_t *key_bytes, const uint32_t *key_off,
-                                                 const int32_t *key_len, uint64_t n, uint32_t *out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x;
-    if (i >= n) return;
-    const int32_t kl = key_len[i];
-    out[i] = kl < 0 ? 0u : fnv32_global(key_bytes + key_off[i], (uint32_t)kl);
-}
-
-// K4: popcount of the alive bits.  16 B/lane streaming read of the u64 table.
-__global__ __launch_bounds__(kWG) void kta_alive_count(const ulonglong2 *__restrict__ table2,
-                                                       uint64_t n_pairs, unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    unsigned long long cnt = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n_pairs; i += stride) {
-        const ulonglong2 e = table2[i];
-        cnt += (e.x & 1ull) + (e.y & 1ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-// Alive bits of the slots [lo, hi) only (any bounds): what the owner of a hash range counts after the
-// hash-range exchange of a multi-GPU run.  8 B/lane.
-__global__ __launch_bounds__(kWG) void kta_alive_count_span(const uint64_t *__restrict__ table, uint64_t lo,
-                                                            uint64_t hi, unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    unsigned long long cnt = 0;
-    for (uint64_t i = lo + (uint64_t)blockIdx.x * kWG + threadIdx.x; i < hi; i += stride) cnt += table[i] & 1ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-// The same, but only when the written list is no longer complete (see launch_written_alive_count).
-__global__ __launch_bounds__(kWG) void kta_alive_count_span_if_overflowed(WrittenList wl, const uint64_t *__restrict__ table, uint64_t lo,
-                                                                          uint64_t hi, unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    if (*wl.n <= wl.cap) return;
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    unsigned long long cnt = 0;
-    for (uint64_t i = lo + (uint64_t)blockIdx.x * kWG + threadIdx.x; i < hi; i += stride) cnt += table[i] & 1ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-// Compact export of the entries ever written (value != 0): (slot u32, value u64) pairs.  A shard's
-// table holds at most one entry per distinct key hash it has seen, so this is what partition-sharded
-// GPUs exchange instead of the 32 GiB table.  Each workgroup sweeps a contiguous slab, stages hits in
-// LDS and reserves output space with ONE device atomic per flush (not per hit).
-constexpr uint32_t kExportStage = 2048;
-
-__global__ __launch_bounds__(kWG) void kta_alive_export(const unsigned long long *__restrict__ table,
-                                                        uint64_t n_slots, uint32_t slot_base,
-                                                        uint32_t *__restrict__ out_slots,
-                                                        unsigned long long *__restrict__ out_vals,
-                                                        unsigned long long *__restrict__ counter, uint64_t cap)
-{
-    __shared__ uint32_t s_slot[kExportStage];
-    __shared__ unsigned long long s_val[kExportStage];
-    __shared__ uint32_t s_n;
-    __shared__ unsigned long long s_base;
-    const uint64_t per = (n_slots + gridDim.x - 1) / gridDim.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * per;
-    const uint64_t hi = lo + per < n_slots ? lo + per : n_slots;
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    for (uint64_t base = lo; base < hi; base += kWG * 4) {     // uniform trip count per workgroup
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint64_t i = base + (uint64_t)u * kWG + threadIdx.x;
-            const unsigned long long v = i < hi ? table[i] : 0ull;
-            if (v) {
-                const uint32_t at = atomicAdd(&s_n, 1u);         // LDS counter; stage holds 2048 >= 4 * 256
-                s_slot[at] = slot_base + (uint32_t)i;
-                s_val[at] = v;
-            }
-        }
-        __syncthreads();
-        const uint32_t n = s_n;
-        if (n > kExportStage - kWG * 4 || base + kWG * 4 >= hi) {  // flush when the next round might overflow
-            if (threadIdx.x == 0 && n) s_base = atomicAdd(counter, (unsigned long long)n);
-            __syncthreads();
-            for (uint32_t k = threadIdx.x; k < n; k += kWG)
-                if (s_base + k < cap) {
-                    out_slots[s_base + k] = s_slot[k];
-                    out_vals[s_base + k] = s_val[k];
-                }
-            __syncthreads();
-            if (threadIdx.x == 0) s_n = 0;
-        }
-        __syncthreads();
-    }
-}
-
-// Merge foreign entries: table[slot] = max(table[slot], value), keeping the running alive count exact
-// (same telescoping argument as kta_alive_update_counting).
-__global__ __launch_bounds__(kWG) void kta_alive_import(const uint32_t *__restrict__ slots,
-                                                        const unsigned long long *__restrict__ vals, uint64_t n,
-                                                        unsigned long long *__restrict__ table,
-                                                        long long *__restrict__ running, WrittenList wl)
-{
-    __shared__ long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    long long delta = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
-        const unsigned long long v = vals[i];
-        if (!v) continue;
-        const unsigned long long old = atomicMax(&table[slots[i]], v);
-        note_new_slot(wl, old == 0ull, slots[i]);
-        if (v > old) delta += (long long)(v & 1ull) - (long long)(old & 1ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) delta += __shfl_xor(delta, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = delta;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(reinterpret_cast<unsigned long long *>(running), (unsigned long long)t);
-    }
-}
-
-// number of entries ever written (value != 0)
-__global__ __launch_bounds__(kWG) void kta_alive_count_written(const ulonglong2 *__restrict__ table2, uint64_t n_pairs,
-                                                               unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    unsigned long long cnt = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n_pairs; i += stride) {
-        const ulonglong2 e = table2[i];
-        cnt += (e.x != 0ull) + (e.y != 0ull);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-// entries ever written in the slots [lo, hi) (any bounds)
-__global__ __launch_bounds__(kWG) void kta_alive_count_written_span(const uint64_t *__restrict__ table, uint64_t lo,
-                                                                    uint64_t hi, unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    unsigned long long cnt = 0;
-    for (uint64_t i = lo + (uint64_t)blockIdx.x * kWG + threadIdx.x; i < hi; i += stride) cnt += table[i] != 0ull;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-// table -> bitmap: one wave turns 64 consecutive entries into one u64 of bits via ballot.
-__global__ __launch_bounds__(kWG) void kta_alive_bitmap(const unsigned long long *__restrict__ table,
-                                                        uint64_t n_slots,
-                                                        unsigned long long *__restrict__ bitmap64)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * kWG;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n_slots; i += stride) {
-        const unsigned long long m = __ballot((table[i] & 1ull) != 0ull);
-        if ((threadIdx.x & 63u) == 0u) bitmap64[i >> 6] = m;
-    }
-}
-
-// ---------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------
 
@@ -1966,90 +1495,55 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
     return pl;
 }
 
+// One scan kernel on the plan's grid.  More than 48 KiB of dynamic LDS must be opted into, per kernel.
+template <typename... Extra>
+static hipError_t launch_scan_kernel(void (*kernel)(ScanColumns, uint64_t, uint32_t, uint32_t, uint64_t *, uint32_t, Extra...),
+                                     const ScanPlan &pl, const ScanColumns &c, uint64_t n, uint32_t P, uint64_t *partials,
+                                     hipStream_t s, const Extra &...extra)
+{
+    if (pl.lds_bytes > 48u * 1024u) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)pl.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(pl.workgroups), dim3(kWG), pl.lds_bytes, s, c, n, P, pl.rep_log2, partials, pl.row_len,
+                       extra...);
+    return hipGetLastError();
+}
+
 hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_t n, uint32_t P,
                                uint64_t *partials, hipStream_t s, const TimelineArgs *tl)
 {
-    dim3 grid(pl.workgroups), block(kWG);
     if (pl.timeline_rows && (!tl || tl->n_buckets + 3u != pl.timeline_rows)) return hipErrorInvalidValue;
-    // > 64 KiB of dynamic LDS (P > ~2700) must be opted into per kernel
-#define KTA_SCAN_T(V, NT, AN, TL, ...)                                                                              \
-    do {                                                                                                            \
-        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
-            hipError_t ea = hipFuncSetAttribute(                                                                    \
-                reinterpret_cast<const void *>(&kta_metrics_scan<V, NT, AN, TL __VA_OPT__(, ) __VA_ARGS__>),        \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);                                     \
-            if (ea != hipSuccess) return ea;                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL((kta_metrics_scan<V, NT, AN, TL __VA_OPT__(, ) __VA_ARGS__>), grid, block, pl.lds_bytes,  \
-                           s, c, n, P, pl.rep_log2, partials, pl.row_len __VA_OPT__(, *tl));                        \
-    } while (0)
-#define KTA_SCAN(V, NT, AN)                                  \
-    do {                                                     \
-        if (c.hdr) KTA_SCAN_T(V, NT, AN, true);              \
-        else KTA_SCAN_T(V, NT, AN, false);                   \
-    } while (0)
+    const bool tiled = c.hdr != nullptr, nt = pl.nontemporal;
+    const auto launch = [&](auto kernel, const ScanColumns &cols, const auto &...extra) {
+        return launch_scan_kernel(kernel, pl, cols, n, P, partials, s, extra...);
+    };
     if (pl.timeline_rows) {   // (plan_scan: accumulating, non-temporal)
-        if (pl.analytics) {
-            if (c.hdr) KTA_SCAN_T(0, true, true, true, TimelineArgs);
-            else KTA_SCAN_T(0, true, true, false, TimelineArgs);
-        } else {
-            if (c.hdr) KTA_SCAN_T(0, true, false, true, TimelineArgs);
-            else KTA_SCAN_T(0, true, false, false, TimelineArgs);
-        }
-        return hipGetLastError();
+        if (pl.analytics)
+            return tiled ? launch(kta_metrics_scan<0, true, true, true, TimelineArgs>, c, *tl)
+                         : launch(kta_metrics_scan<0, true, true, false, TimelineArgs>, c, *tl);
+        return tiled ? launch(kta_metrics_scan<0, true, false, true, TimelineArgs>, c, *tl)
+                     : launch(kta_metrics_scan<0, true, false, false, TimelineArgs>, c, *tl);
     }
-    if (pl.analytics) {
-        KTA_SCAN(0, true, true);
-        return hipGetLastError();
-    }
+    if (pl.analytics) return tiled ? launch(kta_metrics_scan<0, true, true, true>, c) : launch(kta_metrics_scan<0, true, true, false>, c);
     if (pl.packed) {
-        if (!c.hdr) return hipErrorInvalidValue;
+        if (!tiled) return hipErrorInvalidValue;
         ScanColumns cs = c;
         if (!pl.summaries) cs.sum = nullptr;
-#define KTA_SCAN_PACKED(NT, SUM)                                                                                         \
-    do {                                                                                                            \
-        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed<NT, SUM>),        \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);     \
-            if (ea != hipSuccess) return ea;                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL((kta_metrics_scan_packed<NT, SUM>), grid, block, pl.lds_bytes, s, cs, n, P, pl.rep_log2,       \
-                           partials, pl.row_len);                                                                   \
-    } while (0)
-#define KTA_SCAN_PACKED_REST(NT)                                                                                    \
-    do {                                                                                                            \
-        if (pl.lds_bytes > 48u * 1024u) {                                                                           \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_metrics_scan_packed_rest<NT>),  \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);     \
-            if (ea != hipSuccess) return ea;                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL((kta_metrics_scan_packed_rest<NT>), grid, block, pl.lds_bytes, s, cs, n, P, pl.rep_log2, \
-                           partials, pl.row_len);                                                                   \
-    } while (0)
-        if (cs.sum) {
-            // the lean kernel, then — same grid, same rows — the tiles its workgroups left (none, where every tile is
-            // summarised, compact and u16: a workgroup of the second kernel then reads one word and ends)
-            if (pl.nontemporal) KTA_SCAN_PACKED(true, true);
-            else KTA_SCAN_PACKED(false, true);
-            hipError_t el = hipGetLastError();
-            if (el != hipSuccess) return el;
-            if (pl.nontemporal) KTA_SCAN_PACKED_REST(true);
-            else KTA_SCAN_PACKED_REST(false);
-        } else {
-            if (pl.nontemporal) KTA_SCAN_PACKED(true, false);
-            else KTA_SCAN_PACKED(false, false);
-        }
-#undef KTA_SCAN_PACKED
-#undef KTA_SCAN_PACKED_REST
-        return hipGetLastError();
+        if (!cs.sum) return nt ? launch(kta_metrics_scan_packed<true, false>, cs) : launch(kta_metrics_scan_packed<false, false>, cs);
+        // the lean kernel, then — same grid, same rows — the tiles its workgroups left (none, where every tile is
+        // summarised, compact and u16: a workgroup of the second kernel then reads one word and ends)
+        const hipError_t el = nt ? launch(kta_metrics_scan_packed<true, true>, cs) : launch(kta_metrics_scan_packed<false, true>, cs);
+        if (el != hipSuccess) return el;
+        return nt ? launch(kta_metrics_scan_packed_rest<true>, cs) : launch(kta_metrics_scan_packed_rest<false>, cs);
     }
-    switch (pl.variant) {
-    case 9: if (pl.nontemporal) KTA_SCAN(9, true, false); else KTA_SCAN(9, false, false); break;
-    default: if (pl.nontemporal) KTA_SCAN(0, true, false); else KTA_SCAN(0, false, false); break;
+    if (pl.variant == 9) {
+        if (nt) return tiled ? launch(kta_metrics_scan<9, true, false, true>, c) : launch(kta_metrics_scan<9, true, false, false>, c);
+        return tiled ? launch(kta_metrics_scan<9, false, false, true>, c) : launch(kta_metrics_scan<9, false, false, false>, c);
     }
-#undef KTA_SCAN
-#undef KTA_SCAN_T
-    return hipGetLastError();
+    if (nt) return tiled ? launch(kta_metrics_scan<0, true, false, true>, c) : launch(kta_metrics_scan<0, true, false, false>, c);
+    return tiled ? launch(kta_metrics_scan<0, false, false, true>, c) : launch(kta_metrics_scan<0, false, false, false>, c);
 }
 
 hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_t P, uint64_t *vec,
@@ -2076,232 +1570,6 @@ hipError_t launch_init_vector(uint64_t *vec, uint32_t P, uint64_t *avec, hipStre
 {
     const uint32_t n = P * 7 + 1;
     hipLaunchKernelGGL(kta_init_vector, dim3((n + 255) / 256), dim3(256), 0, s, vec, P, avec);
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_update(const AliveColumns &c, uint64_t n, uint64_t base_seq, uint64_t *table,
-                               int workgroups, int variant, uint32_t *scratch, int64_t *running, hipStream_t s,
-                               const uint32_t *only_if, const WrittenList &wl)
-{
-    uint64_t wgs = (n + kWG - 1) / kWG;
-    const uint64_t cap = workgroups > 0 ? (uint64_t)workgroups : 256ull * 8ull;
-    if (wgs > cap) wgs = cap;
-    if (wgs < 1) wgs = 1;
-    unsigned long long *t = reinterpret_cast<unsigned long long *>(table);
-    if (variant == 8 && scratch) {
-        hipLaunchKernelGGL(kta_alive_hash_only, dim3((uint32_t)wgs), dim3(kWG), 0, s, c, n, scratch);
-    } else if (variant == 9 && scratch) {
-        hipLaunchKernelGGL(kta_alive_apply_only, dim3((uint32_t)wgs), dim3(kWG), 0, s, c, n, base_seq, scratch, t, wl);
-    } else if (variant == 2 && running) {
-        hipLaunchKernelGGL(kta_alive_update_filtered, dim3((uint32_t)wgs), dim3(kWG), 0, s, c, n, base_seq, t,
-                           reinterpret_cast<long long *>(running), only_if, wl);
-    } else if (variant == 1 && running) {
-        hipLaunchKernelGGL(kta_alive_update_counting, dim3((uint32_t)wgs), dim3(kWG), 0, s, c, n, base_seq, t,
-                           reinterpret_cast<long long *>(running), wl);
-    } else {
-        hipLaunchKernelGGL(kta_alive_update, dim3((uint32_t)wgs), dim3(kWG), 0, s, c, n, base_seq, t, wl);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_count(const uint64_t *table, uint64_t n_slots, uint64_t *out, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kta_alive_count, dim3(256 * 8), dim3(kWG), 0, s,
-                       reinterpret_cast<const ulonglong2 *>(table), n_slots / 2,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_count_span(const uint64_t *table, uint64_t lo, uint64_t hi, uint64_t *out, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess || lo >= hi) return e;
-    hipLaunchKernelGGL(kta_alive_count_span, dim3(256 * 8), dim3(kWG), 0, s, table, lo, hi,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_count_written_span(const uint64_t *table, uint64_t lo, uint64_t hi, uint64_t *out, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess || lo >= hi) return e;
-    hipLaunchKernelGGL(kta_alive_count_written_span, dim3(256 * 8), dim3(kWG), 0, s, table, lo, hi,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_count_written(const uint64_t *table, uint64_t n_slots, uint64_t *out, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kta_alive_count_written, dim3(256 * 8), dim3(kWG), 0, s,
-                       reinterpret_cast<const ulonglong2 *>(table), n_slots / 2,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_export(const uint64_t *table, uint64_t n_slots, uint32_t *out_slots, uint64_t *out_vals,
-                               uint64_t *counter, uint64_t cap, hipStream_t s)
-{
-    return launch_alive_export_span(table, 0, n_slots, out_slots, out_vals, counter, cap, s);
-}
-
-hipError_t launch_alive_export_span(const uint64_t *table, uint64_t lo, uint64_t hi, uint32_t *out_slots,
-                                    uint64_t *out_vals, uint64_t *counter, uint64_t cap, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(counter, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess || lo >= hi) return e;
-    const uint64_t n_slots = hi - lo;
-    hipLaunchKernelGGL(kta_alive_export, dim3(256 * 16), dim3(kWG), 0, s,
-                       reinterpret_cast<const unsigned long long *>(table + lo), n_slots, (uint32_t)lo, out_slots,
-                       reinterpret_cast<unsigned long long *>(out_vals),
-                       reinterpret_cast<unsigned long long *>(counter), cap);
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_import(const uint32_t *slots, const uint64_t *vals, uint64_t n, uint64_t *table,
-                               int64_t *running, const WrittenList &wl, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    uint64_t wgs = (n + kWG - 1) / kWG;
-    if (wgs > 256 * 8) wgs = 256 * 8;
-    hipLaunchKernelGGL(kta_alive_import, dim3((uint32_t)wgs), dim3(kWG), 0, s, slots,
-                       reinterpret_cast<const unsigned long long *>(vals), n,
-                       reinterpret_cast<unsigned long long *>(table), reinterpret_cast<long long *>(running), wl);
-    return hipGetLastError();
-}
-
-// ---- the exchange over the written list -----------------------------------------------------------------
-constexpr int kMaxOwners = 64;
-
-// The list's length is read on the device (the host does not wait for it): a list that overflowed its capacity says so
-// in *overflow, and the counts then cover its first `cap` entries only — the host, which reads the flag together with the
-// counts, falls back to the sweeps.
-__global__ __launch_bounds__(kWG) void kta_written_count(WrittenList wl, uint32_t nranks, unsigned long long *counts, unsigned long long *overflow)
-{
-    __shared__ uint32_t s_c[kMaxOwners];
-    if (threadIdx.x < kMaxOwners) s_c[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t have = *wl.n, n = have < wl.cap ? have : wl.cap;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && have > wl.cap) *overflow = 1ull;
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kWG)
-        atomicAdd(&s_c[(uint32_t)(((uint64_t)wl.slots[i] * nranks) >> 32)], 1u);
-    __syncthreads();
-    if (threadIdx.x < nranks && s_c[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_c[threadIdx.x]);
-}
-
-// Every workgroup takes a contiguous piece of the list, counts its entries per owner in LDS, reserves their places
-// in the owners' lists with ONE device atomic per owner, and writes (slot, table[slot]).
-__global__ __launch_bounds__(kWG) void kta_written_export(WrittenList wl, const unsigned long long *__restrict__ table,
-                                                          uint32_t nranks, uint32_t skip_rank,
-                                                          const unsigned long long *__restrict__ owner_at,
-                                                          unsigned long long *__restrict__ cursors, uint32_t *__restrict__ out_slots,
-                                                          unsigned long long *__restrict__ out_vals)
-{
-    __shared__ uint32_t s_c[kMaxOwners];
-    __shared__ unsigned long long s_base[kMaxOwners];
-    const uint64_t have = *wl.n, n = have < wl.cap ? have : wl.cap;     // (the length is read on the device, as in kta_written_count)
-    const uint64_t per = (n + gridDim.x - 1) / gridDim.x;
-    const uint64_t lo = (uint64_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-    constexpr uint64_t kChunk = (uint64_t)kWG * 8;
-    for (uint64_t c0 = lo; c0 < hi; c0 += kChunk) {                    // uniform trip count per workgroup
-        if (threadIdx.x < kMaxOwners) s_c[threadIdx.x] = 0;
-        __syncthreads();
-        uint32_t slot[8], own[8], at[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const uint64_t i = c0 + (uint64_t)u * kWG + threadIdx.x;
-            slot[u] = i < hi ? wl.slots[i] : 0u;
-            own[u] = i < hi ? (uint32_t)(((uint64_t)slot[u] * nranks) >> 32) : skip_rank;
-            at[u] = own[u] != skip_rank ? atomicAdd(&s_c[own[u]], 1u) : 0u;
-        }
-        __syncthreads();
-        if (threadIdx.x < nranks && s_c[threadIdx.x]) s_base[threadIdx.x] = atomicAdd(&cursors[threadIdx.x], (unsigned long long)s_c[threadIdx.x]);
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            if (own[u] == skip_rank) continue;
-            const unsigned long long k = owner_at[own[u]] + s_base[own[u]] + at[u];
-            out_slots[k] = slot[u];
-            out_vals[k] = table[slot[u]];
-        }
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kWG) void kta_written_alive_count(WrittenList wl, const unsigned long long *__restrict__ table,
-                                                               uint64_t lo, uint64_t hi, unsigned long long *out)
-{
-    __shared__ unsigned long long s_w[kWG / 64];
-    unsigned long long cnt = 0;
-    const uint64_t len = *wl.n;                           // (may have grown by the import that ran just before)
-    if (len > wl.cap) return;                             // the list is not complete: kta_alive_count_span_if_overflowed counts
-    for (uint64_t i = (uint64_t)blockIdx.x * kWG + threadIdx.x; i < len; i += (uint64_t)gridDim.x * kWG) {
-        const uint64_t slot = wl.slots[i];
-        if (slot >= lo && slot < hi) cnt += table[slot] & 1ull;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWG / 64; w++) t += s_w[w];
-        if (t) atomicAdd(out, t);
-    }
-}
-
-hipError_t launch_written_count(const WrittenList &wl, int nranks, uint64_t *counts, uint64_t *overflow, hipStream_t s)
-{
-    // (one LDS counter per owner: kta_comm.hip takes the sweeps — launch_alive_count_written_span / _export_span — for more
-    // than kMaxOwners ranks and never comes here with them)
-    if (nranks > kMaxOwners) return hipErrorInvalidValue;
-    // (the grid does not depend on the list's length, which only the device knows: 4 workgroups per CU walk it)
-    hipLaunchKernelGGL(kta_written_count, dim3(1024), dim3(kWG), 0, s, wl, (uint32_t)nranks,
-                       reinterpret_cast<unsigned long long *>(counts), reinterpret_cast<unsigned long long *>(overflow));
-    return hipGetLastError();
-}
-
-hipError_t launch_written_export(const WrittenList &wl, const uint64_t *table, int nranks, int skip_rank,
-                                 const uint64_t *owner_at, uint64_t *cursors, uint32_t *out_slots, uint64_t *out_vals, hipStream_t s)
-{
-    if (nranks > kMaxOwners) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kta_written_export, dim3(1024), dim3(kWG), 0, s, wl, reinterpret_cast<const unsigned long long *>(table),
-                       (uint32_t)nranks, (uint32_t)skip_rank, reinterpret_cast<const unsigned long long *>(owner_at),
-                       reinterpret_cast<unsigned long long *>(cursors), out_slots, reinterpret_cast<unsigned long long *>(out_vals));
-    return hipGetLastError();
-}
-
-// The owner's count of its hash range over the written list — or, when the list has overflowed by now (the import may
-// have added to it; only the device knows), over the range itself: both kernels are launched, one of them returns at once.
-hipError_t launch_written_alive_count(const WrittenList &wl, const uint64_t *table, uint64_t lo, uint64_t hi,
-                                      uint64_t *out, hipStream_t s)
-{
-    hipError_t e = hipMemsetAsync(out, 0, sizeof(uint64_t), s);
-    if (e != hipSuccess || lo >= hi) return e;
-    hipLaunchKernelGGL(kta_written_alive_count, dim3(1024), dim3(kWG), 0, s, wl,
-                       reinterpret_cast<const unsigned long long *>(table), lo, hi, reinterpret_cast<unsigned long long *>(out));
-    hipLaunchKernelGGL(kta_alive_count_span_if_overflowed, dim3(256 * 8), dim3(kWG), 0, s, wl, table, lo, hi,
-                       reinterpret_cast<unsigned long long *>(out));
-    return hipGetLastError();
-}
-
-hipError_t launch_alive_bitmap(const uint64_t *table, uint64_t n_slots, uint32_t *bitmap, hipStream_t s)
-{
-    hipLaunchKernelGGL(kta_alive_bitmap, dim3(256 * 8), dim3(kWG), 0, s,
-                       reinterpret_cast<const unsigned long long *>(table), n_slots,
-                       reinterpret_cast<unsigned long long *>(bitmap));
-    return hipGetLastError();
-}
-
-hipError_t launch_fnv32(const uint8_t *key_bytes, const uint32_t *key_off, const int32_t *key_len,
-                        uint64_t n, uint32_t *out, hipStream_t s)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(kta_fnv32, dim3((uint32_t)((n + kWG - 1) / kWG)), dim3(kWG), 0, s, key_bytes,
-                       key_off, key_len, n, out);
     return hipGetLastError();
 }
 

@@ -185,6 +185,19 @@ def test_no_tile_qualifies():
     _three(200, cols, workgroups=(3,), expect_hdrs=[LEAN] * ntiles, lean_tiles=["part_max"] * ntiles)
 
 
+@pytest.mark.parametrize("P", [3, 256])
+def test_every_tile_handed_over_across_a_front_flush(P):
+    """One workgroup, one tile more than a front interval, two partitions more in the data than the handler has: the
+    second kernel's ring starts at the first tile and meets its own front flush (variant 48: the kernel without
+    summaries does); then the same through a view that cuts the first and the last tile."""
+    ntiles = FT + 1
+    n = ntiles * T
+    cols = _topic(n, P + 2, seed=52)
+    assert all(cols["partition"][t * T:(t + 1) * T].max() >= P for t in range(ntiles))
+    _three(P, cols, workgroups=(1,), expect_hdrs=[LEAN] * ntiles, lean_tiles=["part_max"] * ntiles)
+    _three(P, cols, workgroups=(1,), views=((4, n - 4 - T + 37),))
+
+
 # ---- fields at their limits, one slot ---------------------------------------------------------------------------------
 # plan_scan replicates a partition's front slots 2^r times while 16 P 2^r + 40 P bytes fit 32 KiB: a single replica
 # (r = 0) from the least P with 16 * 2 P + 40 P > 32768 on.
