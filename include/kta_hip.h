@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define KTA_ABI_VERSION 7   /* 7: the record filter (kta_set_filter, kta_filter_info, kta_set_filter_slice, kta_filter_host, kta_filter_tile_host, kta_render_filter), only added entry points; the compaction what-if (KTA_FLAG_COMPACTION, kta_compaction_replay, kta_get_compaction, kta_compaction_max_partitions, kta_compaction_info, kta_render_compaction), only added entry points and one flag bit; the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
+#define KTA_ABI_VERSION 7   /* 7: the opt-in size percentiles (KTA_FLAG_SIZE_QUANTILES, kta_get_size_quantiles, kta_exchange_size_quantiles, kta_size_quantiles_result_vector, kta_merge_size_quantiles, kta_size_quantiles_max_partitions, kta_size_quantiles_info, kta_set_size_quantiles_slice, kta_size_bin, kta_size_bin_bounds, kta_size_quantile, kta_render_size_percentiles; kta_exchange reduces its snapshot), only added entry points and a flag bit; the record filter (kta_set_filter, kta_filter_info, kta_set_filter_slice, kta_filter_host, kta_filter_tile_host, kta_render_filter), only added entry points; the compaction what-if (KTA_FLAG_COMPACTION, kta_compaction_replay, kta_get_compaction, kta_compaction_max_partitions, kta_compaction_info, kta_render_compaction), only added entry points and one flag bit; the opt-in partitioner pass (KTA_FLAG_PARTITIONER, kta_set_repartition, kta_get_partitioner, kta_exchange_partitioner, kta_partitioner_result_vector, kta_merge_partitioner, kta_partitioner_max_partitions, kta_partitioner_info, kta_render_partitioner, kta_murmur2; kta_exchange reduces its snapshot), only added entry points and a flag bit; tile summaries beside the tile headers (kta_tile_sum, kta_batch_tile_summaries, bit 32 of kta_set_tuning's scan_variant), only an added entry point and library-owned storage: kta_tile_hdr and kta_batch are unchanged; the opt-in timestamp order (KTA_FLAG_TS_ORDER, kta_get_ts_order, kta_exchange_ts_order, kta_ts_order_result_vector, kta_merge_ts_order, kta_ts_order_max_partitions, kta_ts_order_info, kta_set_ts_order_chunk, kta_render_ts_order; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in hot keys (KTA_FLAG_HOT_KEYS, kta_get_hot_keys, kta_exchange_hot_keys, kta_hot_keys_result_vector, kta_merge_hot_keys, kta_hot_keys_recover, kta_get_hot_key_exemplars, kta_hot_keys_info, kta_set_hot_flush_rounds, kta_render_hot_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in key sketch (KTA_FLAG_KEY_SKETCH, kta_get_key_sketch, kta_exchange_key_sketch, kta_key_sketch_result_vector, kta_merge_key_sketch, kta_key_sketch_estimate, kta_key_sketch_info, kta_render_distinct_keys; kta_exchange reduces its snapshot), only added entry points and a flag bit; the opt-in timeline (kta_set_timeline, kta_timeline_max_partitions, kta_get_timeline, kta_timeline_vector, kta_exchange_timeline, kta_timeline_result_vector, kta_render_timeline; kta_exchange reduces its snapshot), only added entry points (the version stays 7: no existing layout or call changed); kta_batch.tile_hdr / layout appended to the struct (the tile-compact device layout, kta_tile_hdr: a zero-initialised kta_batch is the raw layout of before), kta_batch_from_raw, kta_batch_to_raw; the analytics vector has a snapshot that kta_exchange reduces (kta_exchange_analytics, kta_analytics_result_vector), kta_decode_analytics, kta_merge_analytics, kta_render_analytics, kta_analytics_max_partitions; a KTA_FLAG_ANALYTICS context with more partitions than the scan's LDS plan admits is refused by kta_create; 6: kta_replay_messages, kta_handle_message_stats, kta_zstd_inflate_host_small (kta_kafka.h); the table state takes the fused pass; kta_kafka_set_variant takes 0, 1, 2, 10, 11 only (the other geometries went in round 5); 5: kta_set_fuse, kta_alive_pass_info; 4: KTA_FLAG_ALIVE_TABLE, the default -c state is the bit set (submission order); 3: kta_comm_* / kta_exchange*, kta_result_vector is a snapshot; 2: kta_kafka_batch_desc.scratch_end */
 
 /* status codes */
 #define KTA_OK 0
@@ -307,6 +307,37 @@ typedef struct kta_hot_key {
 #define KTA_FLAG_COMPACTION (0x80u)  /* 128: bit 7 */
 #define KTA_COMPACTION_WORDS 5       /* per partition */
 #define KTA_COMPACTION_GLOBALS 6
+
+/* Size percentiles (NOT in the reference, never printed by the reference report): per partition a histogram fine enough
+ * to read percentiles of the key, value and message sizes from — exact counts, every word an integer.  Opt-in at
+ * kta_create.  For every record that the metrics handler counts (which & 1, partition in [0, P)) three quantities are
+ * binned:
+ *   K = key_len                      if key_len >= 0
+ *   V = val_len                      if val_len >= 0
+ *   M = max(key_len, 0) + val_len    if val_len >= 0, as u32: the reference's message_size of a non-tombstone
+ *                                    (metric.rs:212-251), the quantity whose smallest and largest the report prints
+ * The bin of a u32 v, KTA_SIZE_BINS = 464 of them (csrc/kta_size_bins.h is the code):
+ *   v < 32:     bin(v) = v
+ *   otherwise:  e = 31 - clz(v),  bin(v) = 32 + 16 (e - 5) + ((v >> (e - 4)) & 15)
+ *   lo(b) = b for b < 32, else (16 + (b - 32) % 16) << ((b - 32) / 16 + 1);  hi(b) = lo(b + 1) - 1, hi(463) = 2^32 - 1
+ * Sizes below 32 are exact; above that a bin is at most 1/16 of its lower bound wide.
+ * The vector is u64[P * 3 * 464 + 8], every word a SUM, so the vectors of disjoint record sets add word by word and the
+ * result is exact and independent of order, batching and sharding.  Word (p * 3 + q) * 464 + b holds partition p, quantity
+ * q (K = 0, V = 1, M = 2), bin b.  The eight globals behind them: records counted; records with a partition outside
+ * [0, P) (they touch nothing else); keyed records; non-tombstones; four words that are zero.
+ * Identities with the counter vector of the same records:
+ *   sum_b K[p][b] == key_non_null[p];   sum_b V[p][b] == sum_b M[p][b] == alive[p];
+ *   global 1 == KTA_G_RECORDS;          global 2 == KTA_G_BAD_PARTITION.
+ * Read-off (kta_size_quantile): nearest rank, r = max(1, ceil(num * N / den)) with the product in 128 bits and N the
+ * histogram's count; the answer is the first bin whose running count reaches r, as its lo and hi.  The printed value is
+ * hi: an upper bound that is exact below 32 and at most 6.25 % high above.
+ * Records handed only to the alive-key handler (which == 2) and the batches of a compaction replay touch nothing; a
+ * filtered context bins the passing records.  kta_create refuses the flag above kta_size_quantiles_max_partitions()
+ * partitions. */
+#define KTA_FLAG_SIZE_QUANTILES 0x100U   /* 256: bit 8 */
+#define KTA_SIZE_BINS 464
+#define KTA_SIZE_QUANTITIES 3            /* K, V, M */
+#define KTA_SIZE_GLOBALS 8
 
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
@@ -596,6 +627,8 @@ int kta_finish_device(kta_ctx *ctx);
  *                       all-reduce SUM (u64) over its first 2 P + 64 words and all-reduce MAX (i64) over its last P.
  *                       With KTA_FLAG_PARTITIONER the same grouped launch also reduces the partitioner snapshot:
  *                       all-reduce SUM (u64) over all of its 2 P + 2 Q words.
+ *                       With KTA_FLAG_SIZE_QUANTILES the same grouped launch also reduces the size-percentile snapshot:
+ *                       all-reduce SUM (u64) over all of its P * 3 * 464 + 8 words (every rank needs the flag).
  *   kta_exchange_result the decoded snapshot: after kta_exchange the whole job's result on every rank
  *                       (kta_exchange_analytics, kta_exchange_timeline, kta_exchange_key_sketch, kta_exchange_hot_keys:
  *                       the same for the analytics, the timeline, the key sketch, the hot keys)
@@ -790,6 +823,39 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6]);
  * len is 0. */
 uint32_t kta_murmur2(const void *key, size_t len);
 
+/* Size percentiles (context created with KTA_FLAG_SIZE_QUANTILES; definition above KTA_FLAG_SIZE_QUANTILES).  The pass reads
+ * partition, key_len and val_len in the tiles' own forms — no key columns, no timestamps, and nothing is widened for it.
+ * kta_reset zeroes the vector; kta_finish_device snapshots it.  Every call below that takes a context fails on one without
+ * the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_SIZE_QUANTILES.
+ * The live accumulator, copied to out[n_u64] (n_u64 = P * 3 * 464 + 8; staged messages are flushed first). */
+int kta_get_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's vector on every rank.  The live accumulator is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_size_quantiles_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[P * 3 * 464 + 8] (acc <- acc + other, every word, modulo 2^64): what the collective
+ * of the exchange implements.  KTA_ERR_INVALID for a P of 0 or above the limit. */
+int kta_merge_size_quantiles(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* The largest P a KTA_FLAG_SIZE_QUANTILES context may have (a workgroup's LDS holds the counters of 28 partitions, and
+ * every such slice of the topic streams the batch again). */
+int kta_size_quantiles_max_partitions(void);
+/* The pass's plan for this context and its work (profiling; staged messages are flushed first, waits for the compute
+ * stream): out[0] S, the partitions of a slice, out[1] slices = ceil(P / S), out[2] dynamic LDS bytes of a workgroup,
+ * out[3] threads of a workgroup, out[4] workgroups of the last launch (all slices), out[5] LDS adds issued since kta_create
+ * / kta_reset, after the lanes of an instruction that share a word were combined. */
+int kta_size_quantiles_info(kta_ctx *ctx, uint64_t out[6]);
+/* Tests: S, the partitions of a slice, 1 .. 28 (0: the plan's own; more than P: P).  The result does not depend on it. */
+int kta_set_size_quantiles_slice(kta_ctx *ctx, uint32_t partitions);
+/* The bin of a size (host only; the source the device runs: csrc/kta_size_bins.h). */
+uint32_t kta_size_bin(uint32_t size);
+/* The least and the largest size of bin `bin` < KTA_SIZE_BINS (host only). */
+int kta_size_bin_bounds(uint32_t bin, uint64_t *lo, uint64_t *hi);
+/* The num/den quantile (num <= den, den > 0) of one histogram u64[KTA_SIZE_BINS] by nearest rank (host only): returns 1 and
+ * the bounds of the answer's bin, 0 when the histogram is empty ("none": *lo and *hi are not written), KTA_ERR_INVALID for
+ * bad arguments. */
+int kta_size_quantile(const uint64_t *hist464, uint64_t num, uint64_t den, uint64_t *lo, uint64_t *hi);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -926,6 +992,20 @@ int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_vec, uint32
  * Output buffer conventions as kta_render_report. */
 int kta_render_partitioner(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, uint32_t q, char *out,
                            size_t out_cap, size_t *out_len);
+/* The opt-in size-percentile section that kta-analyzer prints after the report's closing rule (and after the analytics
+ * section) with --librdkafka kta.percentiles=1, from a size vector u64[P * 3 * 464 + 8] and the counter vector
+ * u64[P * 7 + 8] of the same records (host only):
+ *   `Size percentiles per partition, in bytes (kta.percentiles=1; not part of the reference report)` — one line;
+ *   three times a line `Key sizes` / `Value sizes` / `Message sizes (key + value of the non-tombstones)` and a table
+ *    (P | Count | p50 | p90 | p99 | p99.9 | Max) with a row per partition and a last row `All`, the sum over the
+ *    partitions: Count is the histogram's count, a percentile the hi of kta_size_quantile's bin at 50/100, 90/100, 99/100,
+ *    999/1000, Max the hi of the last bin that is not empty; `-` where the count is zero;
+ *   `Sizes below 32 B are exact; a size of 32 B and more is the upper end of its bin, at most 6.25 % wide.`;
+ *   a closing `=` rule.
+ * KTA_ERR_INVALID, and nothing written, when the identities above KTA_FLAG_SIZE_QUANTILES do not hold between the two
+ * vectors.  Output buffer conventions as kta_render_report. */
+int kta_render_size_percentiles(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
+                                size_t *out_len);
 /* The opt-in compaction section that kta-analyzer prints after the partitioner section and before the filter section with
  * -c --librdkafka kta.compaction=1, from a compaction vector u64[5 P + 6] and the counter vector u64[P * 7 + 8] of the
  * first pass (host only).  Shares are %.2f, `n/a` where the denominator is 0.

@@ -30,7 +30,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "recover_hot_keys", "merge_hot_keys", "render_hot_keys", "render_ts_order", "merge_ts_order",
            "ts_order_max_partitions", "split_ts_order", "render_partitioner", "merge_partitioner",
            "partitioner_max_partitions", "split_partitioner", "murmur2", "render_compaction", "split_compaction",
-           "compaction_max_partitions"]
+           "compaction_max_partitions", "split_size_quantiles", "merge_size_quantiles", "render_size_percentiles", "size_bin",
+           "size_bin_bounds", "size_quantile", "size_quantiles_max_partitions"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -79,7 +80,7 @@ class HipMetricHandler:
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
-                 compaction: bool = False):
+                 compaction: bool = False, size_quantiles: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -90,7 +91,9 @@ class HipMetricHandler:
         partitioner: the partitioner pass (KTA_FLAG_PARTITIONER: keyed records on murmur2's partition and their spread
         over `repartition` partitions — n_partitions when None —, partitioner());
         compaction: the compaction what-if (KTA_FLAG_COMPACTION; needs count_alive_keys and implies alive_table: replay the
-        records inside compaction_replay(), then compaction())."""
+        records inside compaction_replay(), then compaction());
+        size_quantiles: the size-percentile pass (KTA_FLAG_SIZE_QUANTILES: a 464-bin histogram of the key, value and message
+        sizes per partition, size_quantiles())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -99,11 +102,12 @@ class HipMetricHandler:
         self.hot_keys_on = bool(hot_keys)
         self.partitioner_on = bool(partitioner)
         self.compaction_on = bool(compaction)
+        self.size_quantiles_on = bool(size_quantiles)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
-                        (N.KTA_FLAG_COMPACTION if compaction else 0) |
+                        (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -552,6 +556,35 @@ class HipMetricHandler:
         self._check(self._lib.kta_partitioner_info(self._ctx, C.byref(out)))
         return dict(zip(("keyed_records", "launches", "partition_adds", "target_adds", "workgroups", "lds_bytes"), (int(x) for x in out)))
 
+    def _size_quantiles(self, fn) -> dict:
+        out = np.zeros(self.n_partitions * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS, dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), out.size))
+        return split_size_quantiles(out, self.n_partitions)
+
+    def size_quantiles(self) -> dict:
+        """The live size vector as a dict of np.uint64 arrays: key[P][464], value[P][464], message[P][464], the globals
+        records, bad_partition, keyed, alive (kta_get_size_quantiles; staged messages are flushed first); "vector" is the
+        whole u64[P * 3 * 464 + 8]."""
+        return self._size_quantiles(self._lib.kta_get_size_quantiles)
+
+    def exchange_size_quantiles(self) -> dict:
+        """As size_quantiles(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._size_quantiles(self._lib.kta_exchange_size_quantiles)
+
+    def size_quantiles_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the size-percentile snapshot (for collectives: allreduce_size_quantiles_vector)."""
+        return self._device_vector(self._lib.kta_size_quantiles_result_vector)
+
+    def size_quantiles_info(self) -> dict:
+        """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_size_quantiles_info(self._ctx, C.byref(out)))
+        return dict(zip(("slice", "slices", "lds_bytes", "threads", "workgroups", "lds_adds"), (int(x) for x in out)))
+
+    def set_size_quantiles_slice(self, partitions: int) -> None:
+        """Tests: the partitions of a slice of the size-percentile pass, 1 .. 28 (0: the plan's own)."""
+        self._check(self._lib.kta_set_size_quantiles_slice(self._ctx, int(partitions)))
+
     def compaction_replay(self, on: bool = True):
         """Replay mode of the compaction what-if on or off (kta_compaction_replay): while it is on every submission path
         hands its batches to the compaction pass and to nothing else.  Either a pair of calls, or
@@ -978,6 +1011,79 @@ def render_partitioner(vec, counter_vec, n_partitions: int, repartition: int) ->
     if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
     return _render(N.load().kta_render_partitioner, _np_ptr(v), _np_ptr(c), n_partitions, repartition)
+
+
+def _size_quantiles_vec(vec, P: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    words = P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS
+    if v.size != words:
+        raise ValueError(f"a size vector of {P} partitions has {words} words, not {v.size}")
+    return v
+
+
+def split_size_quantiles(vec, n_partitions: int) -> dict:
+    """A size vector u64[P * 3 * 464 + 8] as a dict: key[P][464], value[P][464], message[P][464], the globals records,
+    bad_partition, keyed, alive, and the vector itself under "vector"."""
+    P = n_partitions
+    v = _size_quantiles_vec(vec, P)
+    h = v[:P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS].reshape(P, N.KTA_SIZE_QUANTITIES, N.KTA_SIZE_BINS)
+    g = v[P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS:]
+    return {"key": h[:, 0, :].copy(), "value": h[:, 1, :].copy(), "message": h[:, 2, :].copy(), "records": int(g[0]),
+            "bad_partition": int(g[1]), "keyed": int(g[2]), "alive": int(g[3]), "vector": v}
+
+
+def merge_size_quantiles(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_size_quantiles, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    rc = N.load().kta_merge_size_quantiles(_np_ptr(_size_quantiles_vec(acc, n_partitions)), _np_ptr(_size_quantiles_vec(other, n_partitions)),
+                                           n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_size_quantiles")
+    return acc
+
+
+def render_size_percentiles(vec, counter_vec, n_partitions: int) -> str:
+    """kta_render_size_percentiles: the section kta-analyzer prints with --librdkafka kta.percentiles=1, from a size vector
+    and the counter vector u64[P * 7 + 8] of the same records (KtaError when the two do not describe the same records)."""
+    v = _size_quantiles_vec(vec, n_partitions)
+    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
+    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    return _render(N.load().kta_render_size_percentiles, _np_ptr(v), _np_ptr(c), n_partitions)
+
+
+def size_bin(size: int) -> int:
+    """kta_size_bin: the bin, 0 .. 463, of a size 0 .. 2^32 - 1."""
+    return int(N.load().kta_size_bin(int(size)))
+
+
+def size_bin_bounds(b: int) -> Tuple[int, int]:
+    """kta_size_bin_bounds: the least and the largest size of bin b."""
+    lo, hi = C.c_uint64(), C.c_uint64()
+    rc = N.load().kta_size_bin_bounds(int(b), C.byref(lo), C.byref(hi))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_size_bin_bounds")
+    return int(lo.value), int(hi.value)
+
+
+def size_quantile(hist, num: int, den: int) -> Optional[Tuple[int, int]]:
+    """kta_size_quantile: the bounds (lo, hi) of the bin that holds the num/den quantile of a histogram u64[464] by nearest
+    rank; None for an empty histogram."""
+    h = np.ascontiguousarray(np.asarray(hist).reshape(-1), np.uint64)
+    if h.size != N.KTA_SIZE_BINS:
+        raise ValueError(f"a size histogram has {N.KTA_SIZE_BINS} bins, not {h.size}")
+    lo, hi = C.c_uint64(), C.c_uint64()
+    rc = N.load().kta_size_quantile(_np_ptr(h), int(num), int(den), C.byref(lo), C.byref(hi))
+    if rc < 0:
+        raise KtaError(rc, "kta_size_quantile")
+    return (int(lo.value), int(hi.value)) if rc == 1 else None
+
+
+def size_quantiles_max_partitions() -> int:
+    """The largest P of a context with the size-percentile pass."""
+    return int(N.load().kta_size_quantiles_max_partitions())
 
 
 class _CompactionReplay:

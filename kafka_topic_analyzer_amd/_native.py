@@ -61,6 +61,8 @@ KTA_FLAG_TS_ORDER = 32
 KTA_FLAG_PARTITIONER = 64         # partitioner vector: u64[2 P + 2 Q] = [P][2] checked, placed | [Q][2] target records, bytes
 KTA_FLAG_COMPACTION = 128         # compaction vector: u64[5 P + 6] = [P][5] live records, key bytes, value bytes, tombstones, their key bytes | 6 globals
 KTA_COMPACTION_WORDS, KTA_COMPACTION_GLOBALS = 5, 6
+KTA_FLAG_SIZE_QUANTILES = 256     # size vector: u64[P * 3 * 464 + 8] = [P][3: key, value, message][464 bins] | 8 globals
+KTA_SIZE_BINS, KTA_SIZE_QUANTITIES, KTA_SIZE_GLOBALS = 464, 3, 8
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -224,6 +226,17 @@ SIGNATURES = {
     "kta_merge_partitioner": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "kta_partitioner_max_partitions": (C.c_int, []),
     "kta_partitioner_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_get_size_quantiles": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_size_quantiles": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_size_quantiles_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_size_quantiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_size_quantiles_max_partitions": (C.c_int, []),
+    "kta_size_quantiles_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_set_size_quantiles_slice": (C.c_int, [_P, C.c_uint32]),
+    "kta_size_bin": (C.c_uint32, [C.c_uint32]),
+    "kta_size_bin_bounds": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kta_size_quantile": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_murmur2": (C.c_uint32, [C.c_void_p, C.c_size_t]),
     "kta_compaction_replay": (C.c_int, [_P, C.c_int]),
     "kta_get_compaction": (C.c_int, [_P, C.c_void_p, C.c_size_t]),

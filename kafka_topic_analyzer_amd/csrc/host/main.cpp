@@ -35,6 +35,9 @@
 // kta.distinct_keys=1 (every source, kta.gpus=N included) keeps a HyperLogLog sketch of the key hashes per partition as well
 // (KTA_FLAG_KEY_SKETCH; no reference counterpart) and prints the estimated distinct keys per partition and of the topic in a
 // section of its own after the report (and the analytics and the timeline).
+// kta.percentiles=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the size-percentile pass as well
+// (KTA_FLAG_SIZE_QUANTILES; no reference counterpart) and prints, after the report's closing rule and the analytics, p50,
+// p90, p99, p99.9 and the largest of the key, value and message sizes per partition and of the topic.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -318,7 +321,8 @@ struct ShardedJob {
     bool ts_order = false;                             // kta.ts_order=1: likewise (a partition's records stay on one rank)
     bool partitioner = false;                          // kta.partitioner=murmur2: likewise
     uint32_t repartition = 0;                          //   kta.repartition=Q (0: P)
-    FilterConfig filter;                               // kta.from / kta.to / kta.partitions: the same on every rank
+    bool percentiles = false;                          // kta.percentiles=1: likewise
+    FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -334,7 +338,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
-                               (job.partitioner ? KTA_FLAG_PARTITIONER : 0u);
+                               (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -467,6 +471,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         std::string text = kta::render_report(job.topic, duration_secs, metrics, h0->log_compaction(), partitions,
                                               job.start_offsets, job.end_offsets);
         if (job.analytics) text += kta::render_analytics(*h0->analytics());   // the exchanged snapshot, printed once
+        if (job.percentiles) text += kta::render_size_percentiles(h0->size_quantiles()->data(), job.P);   // likewise
         if (job.timeline.n_buckets)
             text += kta::render_timeline(h0->timeline()->data(), job.timeline.origin_ms, job.timeline.bucket_ms,
                                          job.timeline.n_buckets);
@@ -621,6 +626,20 @@ int main(int argc, char **argv)
         fprintf(stderr, "kta.distinct_keys=1: the topic has %u partitions, the key sketch admits at most %d "
                         "(4096 registers per partition)\n", P, KTA_SKETCH_MAX_PARTITIONS);
         return 2;
+    }
+    bool percentiles = false;
+    if (cfg.count("kta.percentiles")) {
+        const std::string &v = cfg["kta.percentiles"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.percentiles=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        percentiles = v == "1";
+        if (percentiles && P > (uint32_t)kta_size_quantiles_max_partitions()) {   // before any context, so before any kernel
+            fprintf(stderr, "kta.percentiles=1: the topic has %u partitions, the size-percentile pass admits at most %d\n", P,
+                    kta_size_quantiles_max_partitions());
+            return 2;
+        }
     }
     bool ts_order = false;
     if (cfg.count("kta.ts_order")) {
@@ -823,6 +842,7 @@ int main(int argc, char **argv)
         job.ts_order = ts_order;
         job.partitioner = partitioner;
         job.repartition = repartition;
+        job.percentiles = percentiles;
         job.filter = filter;
         job.batch = batch;
         job.P = P;
@@ -842,7 +862,8 @@ int main(int argc, char **argv)
         handler = new kta::HipMetricHandler((int32_t)P, count_alive, device, batch, 0,
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
-                                                (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u),
+                                                (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
+                                                (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1054,6 +1075,7 @@ int main(int argc, char **argv)
         std::string text = kta::render_report(args.topic, duration_secs, metrics, handler->log_compaction(),
                                               partitions, start_offsets, end_offsets);
         if (analytics) text += kta::render_analytics(*handler->analytics());
+        if (percentiles) text += kta::render_size_percentiles(handler->size_quantiles()->data(), P);
         if (timeline.n_buckets)
             text += kta::render_timeline(handler->timeline()->data(), timeline.origin_ms, timeline.bucket_ms, timeline.n_buckets);
         if (distinct_keys) text += kta::render_distinct_keys(handler->key_sketch()->data(), keyed_records(metrics, P));

@@ -74,7 +74,7 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
     : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
       sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0),
       tso_on_((flags & KTA_FLAG_TS_ORDER) != 0), part_on_((flags & KTA_FLAG_PARTITIONER) != 0),
-      part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u)
+      part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u), sizeq_on_((flags & KTA_FLAG_SIZE_QUANTILES) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -197,6 +197,10 @@ void HipMetricHandler::read_analytics()
     if (part_on_) {
         pvec_.assign(2 * (size_t)P_ + 2 * (size_t)part_q_, 0);
         check(kta_exchange_partitioner(ctx_, pvec_.data(), pvec_.size()), "kta_exchange_partitioner");
+    }
+    if (sizeq_on_) {
+        qvec_.assign((size_t)P_ * KTA_SIZE_QUANTITIES * KTA_SIZE_BINS + KTA_SIZE_GLOBALS, 0);
+        check(kta_exchange_size_quantiles(ctx_, qvec_.data(), qvec_.size()), "kta_exchange_size_quantiles");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

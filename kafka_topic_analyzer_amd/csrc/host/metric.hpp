@@ -146,6 +146,9 @@ public:
     // exchange(), the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *partitioner() const { return part_on_ ? &pvec_ : nullptr; }
     uint32_t repartition() const { return part_q_; }
+    // With KTA_FLAG_SIZE_QUANTILES: the size vector u64[P * 3 * 464 + 8] of the snapshot finish() / exchange() took (after
+    // exchange(), the whole job's); nullptr without the flag.
+    const std::vector<uint64_t> *size_quantiles() const { return sizeq_on_ ? &qvec_ : nullptr; }
     // With KTA_FLAG_COMPACTION: replay mode on / off (kta_compaction_replay) — after finish(), feed the source a second time
     // between replay_compaction(true) and replay_compaction(false) — and then the live compaction vector u64[5 P + 6].
     void replay_compaction(bool on);
@@ -179,6 +182,8 @@ private:
     bool part_on_ = false;
     uint32_t part_q_ = 0;
     std::vector<uint64_t> pvec_;
+    bool sizeq_on_ = false;
+    std::vector<uint64_t> qvec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -208,6 +213,9 @@ std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exempla
 // the opt-in section kta-analyzer prints last of all with kta.partitioner=murmur2 (kta_render_partitioner): vec
 // u64[2 P + 2 Q], counters u64[P * 7 + 8] (the counter vector of the same records; its globals are not read)
 std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q);
+// the opt-in section kta-analyzer prints with kta.percentiles=1 after the report's closing rule and the analytics
+// (kta_render_size_percentiles): vec u64[P * 3 * 464 + 8]
+std::string render_size_percentiles(const uint64_t *vec, uint32_t P);
 // the opt-in section kta-analyzer prints with -c and kta.compaction=1 after the partitioner section and before the filter
 // section (kta_render_compaction): vec u64[5 P + 6], counters u64[P * 7 + 8] (the first pass's counter vector).  *matched
 // (when given): whether the replay matched the first pass; a section that says it did not otherwise

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "kta_compaction.h"
+#include "kta_size_bins.h"
 #include "metric.hpp"
 
 namespace kta {
@@ -371,6 +372,45 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
     return o;
 }
 
+// The opt-in size-percentile section (kta.percentiles=1): no reference counterpart, printed after the report's closing rule
+// and the analytics section.  vec: u64[P * 3 * 464 + 8] (kta_hip.h; the layout and the read-off are kta_size_bins.h's).
+std::string render_size_percentiles(const uint64_t *vec, uint32_t P)
+{
+    static const char *const kTitles[kSizeQuantities] = {"Key sizes", "Value sizes", "Message sizes (key + value of the non-tombstones)"};
+    static const uint64_t kQuantiles[4][2] = {{50, 100}, {90, 100}, {99, 100}, {999, 1000}};
+    auto row_of = [](const std::string &name, const uint64_t *hist) {
+        uint64_t count = 0;
+        uint32_t last = 0;
+        for (uint32_t b = 0; b < kSizeBins; b++)
+            if (hist[b]) count += hist[b], last = b;
+        std::vector<std::string> row{name, std::to_string(count)};
+        for (const auto &q : kQuantiles) {
+            uint32_t bin = 0;
+            row.push_back(size_quantile(hist, q[0], q[1], &bin) ? std::to_string(size_bin_hi(bin)) : "-");
+        }
+        row.push_back(count ? std::to_string(size_bin_hi(last)) : "-");
+        return row;
+    };
+    std::string o;
+    o += "Size percentiles per partition, in bytes (kta.percentiles=1; not part of the reference report)\n";
+    for (uint32_t q = 0; q < kSizeQuantities; q++) {
+        o += std::string(kTitles[q]) + "\n";
+        std::vector<std::vector<std::string>> rows;
+        rows.push_back({"P", "Count", "p50", "p90", "p99", "p99.9", "Max"});
+        std::vector<uint64_t> all(kSizeBins, 0);
+        for (uint32_t p = 0; p < P; p++) {
+            const uint64_t *hist = vec + size_quantiles_word(p, q, 0);
+            for (uint32_t b = 0; b < kSizeBins; b++) all[b] += hist[b];
+            rows.push_back(row_of(std::to_string(p), hist));
+        }
+        rows.push_back(row_of("All", all.data()));
+        o += pretty_table(rows);
+    }
+    o += "Sizes below 32 B are exact; a size of 32 B and more is the upper end of its bin, at most 6.25 % wide.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // The opt-in compaction section (-c with kta.compaction=1): no reference counterpart, printed after the partitioner section
 // and before the filter section.  vec: u64[5 P + 6] (kta_hip.h; the layout is kta_compaction.h's), counters: the first
 // pass's counter vector with its globals.
@@ -570,6 +610,24 @@ extern "C" int kta_render_partitioner(const uint64_t *vec, const uint64_t *count
     const uint32_t lim = (uint32_t)kta_partitioner_max_partitions();
     if (!vec || !counter_vec || !out_len || n_partitions == 0 || n_partitions > lim || q == 0 || q > lim) return KTA_ERR_INVALID;
     const std::string text = kta::render_partitioner(vec, counter_vec, n_partitions, q);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_size_percentiles(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
+                                           size_t *out_len)
+{
+    if (!vec || !counter_vec || !out_len || n_partitions == 0 || (int)n_partitions > kta_size_quantiles_max_partitions()) return KTA_ERR_INVALID;
+    // a vector that does not describe the counter vector's records is refused
+    if (!kta::size_quantiles_match(vec, counter_vec, n_partitions, KTA_NCOUNTERS, KTA_C_KEY_NON_NULL, KTA_C_ALIVE, KTA_G_RECORDS,
+                                   KTA_G_BAD_PARTITION))
+        return KTA_ERR_INVALID;
+    const std::string text = kta::render_size_percentiles(vec, n_partitions);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

@@ -8,6 +8,7 @@
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
+#include "kta_size_bins.h"
 
 #include <limits.h>
 #include <math.h>
@@ -101,6 +102,13 @@ struct kta_ctx {
     uint64_t comp_saved_seq = 0;
     DeviceBuf<uint64_t> d_comp, d_comp_stats;
     uint64_t comp_launches = 0, comp_workgroups = 0;
+    // size percentiles (KTA_FLAG_SIZE_QUANTILES): d_sizeq u64[P * 3 * 464 + 8] the live vector, d_sizeq_out its snapshot,
+    // d_sizeq_stats the kernel's work counters (kta_size_quantiles_info); sizeq_slice the tests' S (kta_set_size_quantiles_slice;
+    // 0: the plan's), sizeq_variant the launch form (KTA_SIZEQ_VARIANT: 0, or the diagnostics 1 and 9 of tools/bench_size_quantiles.py)
+    bool sizeq = false;
+    DeviceBuf<uint64_t> d_sizeq, d_sizeq_out, d_sizeq_stats;
+    uint32_t sizeq_slice = 0, sizeq_last_workgroups = 0;
+    int sizeq_variant = 0;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -365,6 +373,22 @@ int run_partitioner(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns
     return KTA_OK;
 }
 
+// The size-percentile pass over a batch whose metric columns were resolved to rb, in launches of at most 2^30 records (the
+// u32 counters of its LDS slices).  It reads the tiles' own forms: nothing is widened for it.
+constexpr size_t kSizeqStatWords = 8;
+int run_size_quantiles(kta_ctx *ctx, const kta_internal_columns &rb, uint64_t n)
+{
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t take = n - at < kta::kSizeQuantilesLaunchMax ? n - at : kta::kSizeQuantilesLaunchMax;
+        uint32_t wgs = 0;
+        KTA_HIP(ctx, kta::launch_size_quantiles(scan_columns(rb, at), take, ctx->P, ctx->sizeq_slice, ctx->sizeq_variant, ctx->d_sizeq.get(),
+                                                ctx->d_sizeq_stats.get(), ctx->cu_count, &wgs, ctx->s_compute));
+        ctx->sizeq_last_workgroups = wgs;
+        at += take;
+    }
+    return KTA_OK;
+}
+
 // The compaction pass over a batch whose metric columns were resolved to rb, in launches of at most 2^30 records (the
 // halves of its LDS word W0).
 int run_compaction(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n, uint64_t base_seq)
@@ -497,6 +521,8 @@ int run_handlers(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq
     if (which & 1) {
         int rc = kta_internal_resolve(ctx, c, &rb);
         if (rc != KTA_OK) return rc;
+        // (the size-percentile pass loads whole 16-byte groups of an allocation's tiles)
+        if (ctx->sizeq && rb.rows && rb.rec0 + n > rb.rows) return fail(ctx, KTA_ERR_INVALID, "the batch ends behind its allocation (KTA_FLAG_SIZE_QUANTILES)");
     }
     if (((which & 2) && ctx->alive) || ((which & 1) && (ctx->sketch || ctx->hot || ctx->part))) {
         int rc = widen_lens_for_keys(ctx, c, n);
@@ -635,6 +661,10 @@ int run_handlers(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq
         int rc = run_partitioner(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
     }
+    if ((which & 1) && ctx->sizeq) {    // likewise; partition and the lengths in the tiles' own forms, no keys
+        int rc = run_size_quantiles(ctx, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     return KTA_OK;
 }
 
@@ -766,6 +796,11 @@ int reset_state(kta_ctx *ctx)
         ctx->comp_replay = false;
         ctx->comp_saved_seq = 0;
     }
+    if (ctx->sizeq) {                   // (a forced slice stays)
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sizeq.get(), 0, kta::size_quantiles_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sizeq_stats.get(), 0, kSizeqStatWords * sizeof(uint64_t), ctx->s_compute));
+        ctx->sizeq_last_workgroups = 0;
+    }
     ctx->handed_records = false;
     if (ctx->d_filter_stats) KTA_HIP(ctx, hipMemsetAsync(ctx->d_filter_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
     ctx->filter_seen = ctx->filter_passed = ctx->filter_slices = 0;   // (the filter itself stays)
@@ -836,6 +871,8 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
     rv[KTA_RV_TS_ORDER] = ResultVector{ctx->d_tso_out.get(), ctx->tso ? kta::ts_order_len(ctx->P) : 0, ctx->tso ? 2 * (size_t)ctx->P + 64 : 0, true};
     const size_t plen = ctx->part ? kta::partitioner_len(ctx->P, ctx->part_q) : 0;
     rv[KTA_RV_PARTITIONER] = ResultVector{ctx->part ? ctx->d_part_out.get() : nullptr, plen, plen, false};
+    const size_t qlen = ctx->sizeq ? kta::size_quantiles_len(ctx->P) : 0;
+    rv[KTA_RV_SIZE_QUANTILES] = ResultVector{ctx->sizeq ? ctx->d_sizeq_out.get() : nullptr, qlen, qlen, false};
 }
 
 static ResultVector result_vector(kta_ctx *ctx, int kind)
@@ -869,6 +906,9 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     if ((cfg->flags & KTA_FLAG_PARTITIONER) && cfg->n_partitions > kta_partitioner_max_partitions())
         return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_PARTITIONER admits at most " + std::to_string(kta_partitioner_max_partitions()) +
                                                   " partitions (the pass keeps its counters in LDS)");
+    if ((cfg->flags & KTA_FLAG_SIZE_QUANTILES) && cfg->n_partitions > kta_size_quantiles_max_partitions())
+        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_SIZE_QUANTILES admits at most " + std::to_string(kta_size_quantiles_max_partitions()) +
+                                                  " partitions (every slice of 28 partitions streams the batch again)");
     if ((cfg->flags & KTA_FLAG_COMPACTION) && !cfg->count_alive_keys)
         return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_COMPACTION needs count_alive_keys (the pass reads the last-writer table)");
     if ((cfg->flags & KTA_FLAG_COMPACTION) && cfg->n_partitions > kta_compaction_max_partitions())
@@ -913,6 +953,11 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->part = (cfg->flags & KTA_FLAG_PARTITIONER) != 0;
     ctx->part_q = ctx->part ? ctx->P : 0u;
     ctx->comp = (cfg->flags & KTA_FLAG_COMPACTION) != 0;
+    ctx->sizeq = (cfg->flags & KTA_FLAG_SIZE_QUANTILES) != 0;
+    {
+        const char *qv = getenv("KTA_SIZEQ_VARIANT");   // A/B switch of tools/bench_size_quantiles.py: 1 a launch per slice, 9 loads only
+        ctx->sizeq_variant = qv && (qv[0] == '1' || qv[0] == '9') && !qv[1] ? qv[0] - '0' : 0;
+    }
     {
         const char *nf = getenv("KTA_NO_FUSE");      // A/B switch of bench.py and the tests: the two handlers as two passes
         ctx->fuse_handlers = !(nf && nf[0] == '1');
@@ -984,6 +1029,13 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     if (ctx->comp) {
         KTA_TRY(ctx->d_comp.alloc(kta::compaction_len(ctx->P)));
         KTA_TRY(ctx->d_comp_stats.alloc(3));
+    }
+    if (ctx->sizeq) {
+        const size_t words = kta::size_quantiles_len(ctx->P);
+        KTA_TRY(ctx->d_sizeq.alloc(words));
+        KTA_TRY(ctx->d_sizeq_out.alloc(words));
+        KTA_TRY(hipMemset(ctx->d_sizeq_out.get(), 0, words * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_sizeq_stats.alloc(kSizeqStatWords));
     }
     if (ctx->alive) {
         if (ctx->alive_table) {
@@ -1401,7 +1453,7 @@ int kta_finish_device(kta_ctx *ctx)
     kta_internal_result_vectors(ctx, rv);
     // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
     const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get(),
-                                                 ctx->d_part.get()};
+                                                 ctx->d_part.get(), ctx->d_sizeq.get()};
     for (int k = 0; k < KTA_RV_KINDS; k++)
         if (rv[k].out && live[k])
             KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -1961,6 +2013,97 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
     uint32_t plan[3];
     kta::partitioner_lds_plan(ctx->P, ctx->part_q, plan);
     out[0] = st[0], out[1] = ctx->part_launches, out[2] = st[1], out[3] = st[2], out[4] = ctx->part_workgroups, out[5] = plan[0];
+    return rc;
+}
+
+// ---- size percentiles (kta_size_bins.h holds the rule, kta_size_quantiles.hip the kernel) -------------------------------
+
+static const char *const kNoSizeq = "context was created without KTA_FLAG_SIZE_QUANTILES";
+
+static int sizeq_words(kta_ctx *ctx, size_t n_u64)
+{
+    return check_words(ctx, "size-percentile vector", kta::size_quantiles_len(ctx->P), n_u64);
+}
+
+int kta_size_quantiles_max_partitions(void) { return (int)kta::kSizeQuantilesMaxPartitions; }
+
+uint32_t kta_size_bin(uint32_t size) { return kta::size_bin(size); }
+
+int kta_size_bin_bounds(uint32_t bin, uint64_t *lo, uint64_t *hi)
+{
+    if (bin >= kta::kSizeBins || !lo || !hi) return KTA_ERR_INVALID;
+    *lo = kta::size_bin_lo(bin), *hi = kta::size_bin_hi(bin);
+    return KTA_OK;
+}
+
+int kta_size_quantile(const uint64_t *hist, uint64_t num, uint64_t den, uint64_t *lo, uint64_t *hi)
+{
+    if (!hist || !lo || !hi || den == 0 || num > den) return KTA_ERR_INVALID;
+    uint32_t bin = 0;
+    if (!kta::size_quantile(hist, num, den, &bin)) return 0;
+    *lo = kta::size_bin_lo(bin), *hi = kta::size_bin_hi(bin);
+    return 1;
+}
+
+int kta_get_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    int rc = sizeq_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_sizeq.get(), out, n_u64);
+}
+
+int kta_exchange_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    int rc = sizeq_words(ctx, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_words(ctx, ctx->d_sizeq_out.get(), out, n_u64);
+}
+
+int kta_size_quantiles_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    return hand_out(result_vector(ctx, KTA_RV_SIZE_QUANTILES), device_ptr, n_u64);
+}
+
+int kta_merge_size_quantiles(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    if (!acc || !other || P == 0 || P > kta::kSizeQuantilesMaxPartitions) return KTA_ERR_INVALID;
+    const size_t words = kta::size_quantiles_len(P);
+    merge_words(acc, other, words, words, false);
+    return KTA_OK;
+}
+
+int kta_set_size_quantiles_slice(kta_ctx *ctx, uint32_t partitions)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    if (partitions > kta::kSizeQuantilesMaxSlice)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_size_quantiles_slice: at most " + std::to_string(kta::kSizeQuantilesMaxSlice) + " partitions (0: the default)");
+    ctx->sizeq_slice = partitions;
+    return KTA_OK;
+}
+
+int kta_size_quantiles_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    uint64_t adds = 0;
+    rc = read_words(ctx, ctx->d_sizeq_stats.get(), &adds, 1);
+    uint32_t plan[5];
+    kta::size_quantiles_plan(ctx->P, ctx->sizeq_slice, plan);
+    out[0] = plan[0], out[1] = plan[1], out[2] = plan[2], out[3] = plan[3], out[4] = ctx->sizeq_last_workgroups, out[5] = adds;
     return rc;
 }
 

@@ -312,6 +312,21 @@ hipError_t launch_compaction(const CompactionColumns &c, uint64_t n, uint64_t ba
 // out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P (kta_compaction_info)
 void compaction_lds_plan(uint32_t P, uint32_t out[3]);
 
+// Size percentiles (KTA_FLAG_SIZE_QUANTILES, kta_size_quantiles.hip; the bin rule and the vector's layout are
+// kta_size_bins.h's): the live vector u64[P * 3 * 464 + 8], every word a sum that the workgroups of launch_size_quantiles add
+// their LDS counters to.
+constexpr uint32_t kSizeQuantilesMaxSlice = 28;             // partitions of a slice at most: 28 * 5568 B = 152.25 KiB of LDS
+constexpr uint32_t kSizeQuantilesMaxPartitions = 1024;      // 37 slices, each of which streams the batch; an 11 MiB vector
+constexpr uint64_t kSizeQuantilesLaunchMax = 1ull << 30;    // records per launch: the u32 counters in LDS cannot overflow
+// the pass over records [0, n) of c (partition, key_len, val_len in the tiles' own forms; ts_ms is not read),
+// n <= kSizeQuantilesLaunchMax.  forced_slice: the tests' S (0: the plan's).  variant 0: the slices are the grid's second
+// dimension; 1: one launch per slice; 9: the loads alone (both diagnostics).  stats: u64[8], word 0 += LDS adds issued
+// (after combining); *workgroups = the workgroups launched
+hipError_t launch_size_quantiles(const ScanColumns &c, uint64_t n, uint32_t P, uint32_t forced_slice, int variant, uint64_t *acc, uint64_t *stats,
+                                 int cu_count, uint32_t *workgroups, hipStream_t s);
+// out = {S, slices, dynamic LDS bytes, threads, workgroups per CU} of the launch for P (kta_size_quantiles_info)
+void size_quantiles_plan(uint32_t P, uint32_t forced_slice, uint32_t out[5]);
+
 // Record filter (kta_set_filter, kta_filter.hip; the rules are kta_filter.h's): one slice of a device batch, compacted in
 // record order into a raw-layout scratch batch by three launches (count per tile, prefix of the counts, scatter).
 constexpr uint64_t kFilterSlice = 1ull << 26;                                   // records per slice, at most

@@ -106,6 +106,14 @@ def allreduce_partitioner_vector(pvec, n_partitions: int, repartition: int, grou
     _allreduce_sum_max(pvec, pvec.numel(), group)
 
 
+def allreduce_size_quantiles_vector(qvec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the size-percentile SNAPSHOT (kta_size_quantiles_result_vector: device tensor, or
+    a CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_SIZE_QUANTILES: all-reduce SUM
+    over all of its P * 3 * 464 + 8 words (i64 wrap == u64 wrap)."""
+    assert qvec.numel() == n_partitions * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS
+    _allreduce_sum_max(qvec, qvec.numel(), group)
+
+
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
