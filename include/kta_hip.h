@@ -406,6 +406,18 @@ typedef struct kta_hot_key {
  *   records.  The packed metrics scan takes a summarised tile's earliest and latest timestamp from it and does not
  *   load the tile's timestamp offsets (6 B per record instead of 10).  A hand-built tile-compact kta_batch with its
  *   own tile_hdr has no summaries.  kta_batch_tile_summaries reads them back.
+ *   Scan planes: a KTA_TILE_COMPACT tile uses only the first 4 KiB of its 8 KiB of the ts_ms column.  Bytes
+ *   [4096, 8192) may hold the tile's scan plane: record j of the tile as the u32 at byte 4096 + 4 j,
+ *   partition | key << 8 | val << 16 — partition in [0, 256) (no marker: a tile with an id of -1 or >= 256 has no plane),
+ *   key the key length in [0, 255) or 0xFF for -1, val the value length in [0, 65535) or KTA_COMPACT_LEN_NONE for -1.
+ *   The plane REPEATS what the u16 / i32 forms of the tile hold — those are written exactly as without it, and every
+ *   reader but the packed metrics scan reads them —; the scan reads 4 B per record of a tile with a plane instead of 6,
+ *   in one stream.  A tile has a plane exactly when its mark is 1: the marks are a u32 per tile that the allocation
+ *   keeps beside the summaries.  A mark is trusted only next to a KTA_TILE_COMPACT header and a VALID summary; whoever
+ *   writes a tile's summary writes its mark, 0 or 1, in the same step, and the plane before it; the mark is 1 only for a
+ *   compact tile of all 1024 records in which every record fits.  A header that turns raw needs nothing more, and
+ *   widening the lengths touches neither the ts_ms bytes nor the values.  The plane does not depend on `lens`: tiles
+ *   of keyed allocations have planes too.  kta_batch_tile_planes reads the marks back.
  *   key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
  *   written by kta_synth_fill_device (compact tiles), kta_kafka_decode_device (raw tiles) and kta_batch_from_raw, and
  *   read back by kta_batch_to_raw; a raw-layout kta_batch whose column pointers lie inside a tile-compact allocation of
@@ -539,6 +551,9 @@ int kta_batch_to_raw(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, con
  * a tile boundary; KTA_ERR_INVALID for anything else (a batch without summaries).  An entry is meaningful only where
  * the tile's header is KTA_TILE_COMPACT. */
 int kta_batch_tile_summaries(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, kta_tile_sum *out);
+/* Its twin for the plane marks (scan planes, above): tiles_of(n) u32 to `out`, 1 where the tile has a plane.  The same
+ * batches, the same errors; an entry is meaningful only where the tile's header is KTA_TILE_COMPACT and its summary VALID. */
+int kta_batch_tile_planes(kta_ctx *ctx, const kta_batch *device_cols, uint64_t n, uint32_t *out);
 /* Plain copies.  NOT a way to write the partition, ts_ms, key_len or val_len column of a tile-compact allocation
  * (kta_device_batch_alloc): its tiles' headers and summaries describe the bytes their producer stored, and the scan trusts
  * them — a summarised tile's stored partitions are not compared with P again, so partition bytes written behind a
@@ -1047,7 +1062,8 @@ int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_
 int kta_set_timing(kta_ctx *ctx, int enable);
 int kta_kernel_time_stats(kta_ctx *ctx, float avg_ms[3], uint64_t launches[3]);
 /* Launch-geometry knobs (0 = default): scan workgroups, scan kernel flavour (16 = non-temporal loads; 32 = do not use
- * tile summaries: every tile's timestamps are loaded),
+ * tile summaries: every tile's timestamps are loaded; 64 = ignore the plane marks: a summarised tile is read in its
+ * u16 form, 6 B per record),
  * alive workgroups, alive kernel: 0 plain atomicMax, 1 returning atomicMax + running alive count, 2 the
  * same walked backwards with a pre-read that skips superseded records, 3 (default) / 4 the partitioned
  * pass (hash + partition by the hash's top 10 / 9 bits, then per-bucket merge in LDS) for batches of 2^21

@@ -289,6 +289,13 @@ class HipMetricHandler:
         self._check(self._lib.kta_batch_tile_summaries(self._ctx, C.byref(b), n, _np_ptr(out)))
         return out
 
+    def batch_tile_planes(self, b: KtaBatch, n: int) -> np.ndarray:
+        """The plane marks (kta_batch_tile_planes) of the tiles of records [0, n) of a device batch: uint32, one per tile,
+        1 where the tile has a scan plane."""
+        out = np.zeros((n + N.KTA_TILE_RECORDS - 1) // N.KTA_TILE_RECORDS, dtype=np.uint32)
+        self._check(self._lib.kta_batch_tile_planes(self._ctx, C.byref(b), n, _np_ptr(out)))
+        return out
+
     def upload_batch(self, cols: dict, with_keys: bool = False) -> Tuple[KtaBatch, int]:
         """numpy columns -> a new device batch (tests: bypasses the staging ring)."""
         n = len(cols["partition"])

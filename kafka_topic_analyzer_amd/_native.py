@@ -163,6 +163,7 @@ SIGNATURES = {
     "kta_batch_from_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
     "kta_batch_to_raw": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.POINTER(KtaBatch)]),
     "kta_batch_tile_summaries": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.c_void_p]),
+    "kta_batch_tile_planes": (C.c_int, [_P, C.POINTER(KtaBatch), C.c_uint64, C.c_void_p]),
     "kta_copy_to_device": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_copy_to_host": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kta_set_compute_stream": (C.c_int, [_P, C.c_void_p]),

@@ -217,9 +217,9 @@ int alloc_device_batch(kta_ctx *ctx, uint64_t cap, uint64_t kcap, bool keys, boo
     const uint64_t ntiles = tiles_of(cap) ? tiles_of(cap) : 1;
     const uint64_t rows = ntiles * KTA_TILE_RECORDS;
     const size_t c4 = pad16(rows * 4 + 16), c8 = pad16(rows * 8 + 16);
-    // (the tiles' summaries behind the headers: kta::tile_sums_behind)
-    KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * (sizeof(kta_tile_hdr) + sizeof(kta_tile_sum))));
-    KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * (sizeof(kta_tile_hdr) + sizeof(kta_tile_sum))));   // every tile raw, no summary
+    // (the tiles' summaries behind the headers, their plane marks behind those: kta::tile_sums_behind, tile_marks_behind)
+    KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * kta::kTileSideBytes));
+    KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * kta::kTileSideBytes));   // every tile raw, no summary, no plane
     KTA_HIP(ctx, hipMalloc((void **)&b->partition, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->key_len, c4));
     KTA_HIP(ctx, hipMalloc((void **)&b->val_len, c4));
@@ -278,7 +278,7 @@ kta_internal_columns columns_at(const kta_internal_columns &rb, uint64_t at)
 kta::ScanColumns scan_columns(const kta_internal_columns &rb, uint64_t at)
 {
     const kta_internal_columns r = columns_at(rb, at);
-    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.sum};
+    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.sum, r.mark};
 }
 // (the key-reading passes take the lengths and the keys from the batch's own columns: plain i32 in both layouts)
 kta::SketchColumns sketch_columns(const kta_internal_columns &rb, const kta_batch *c, uint64_t at)
@@ -1329,6 +1329,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     std::vector<int64_t> ts(nt * KTA_TILE_RECORDS, 0);
     std::vector<kta_tile_hdr> hdr(nt);
     std::vector<kta_tile_sum> sum(nt);
+    std::vector<uint32_t> mark(nt, 0u);
     std::vector<int32_t> klen, vlen;
     if (r.keyless) {
         klen.assign(nt * KTA_TILE_RECORDS, 0);
@@ -1338,6 +1339,8 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
         const uint64_t a = T * KTA_TILE_RECORDS, m = n - a < KTA_TILE_RECORDS ? n - a : KTA_TILE_RECORDS;
         hdr[T] = kta::tile_pack_host(h->partition + a, h->ts_ms + a, h->key_len + a, h->val_len + a, m, r.keyless, part.data() + a, ts.data() + a,
                                      r.keyless ? klen.data() + a : nullptr, r.keyless ? vlen.data() + a : nullptr, &sum[T]);
+        // (the plane rides in the ts image that is uploaded whole anyway)
+        if (r.mark) mark[T] = kta::tile_plane_host(hdr[T], h->partition + a, h->key_len + a, h->val_len + a, m, ts.data() + a);
     }
     if (r.keyless) {
         KTA_HIP(ctx, hipMemcpy(r.key_len + r.rec0, klen.data(), klen.size() * 4, hipMemcpyHostToDevice));
@@ -1347,6 +1350,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     KTA_HIP(ctx, hipMemcpy(r.ts_ms + r.rec0, ts.data(), ts.size() * 8, hipMemcpyHostToDevice));
     KTA_HIP(ctx, hipMemcpy(r.hdr + r.rec0 / KTA_TILE_RECORDS, hdr.data(), nt * sizeof(kta_tile_hdr), hipMemcpyHostToDevice));
     if (r.sum) KTA_HIP(ctx, hipMemcpy(r.sum + r.rec0 / KTA_TILE_RECORDS, sum.data(), nt * sizeof(kta_tile_sum), hipMemcpyHostToDevice));
+    if (r.mark) KTA_HIP(ctx, hipMemcpy(r.mark + r.rec0 / KTA_TILE_RECORDS, mark.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice));
     return KTA_OK;
 }
 
@@ -1364,6 +1368,23 @@ int kta_batch_tile_summaries(kta_ctx *ctx, const kta_batch *d, uint64_t n, kta_t
     if (n == 0) return KTA_OK;
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     KTA_HIP(ctx, hipMemcpy(out, r.sum + r.rec0 / KTA_TILE_RECORDS, tiles_of(n) * sizeof(kta_tile_sum), hipMemcpyDeviceToHost));
+    return KTA_OK;
+}
+
+int kta_batch_tile_planes(kta_ctx *ctx, const kta_batch *d, uint64_t n, uint32_t *out)
+{
+    if (!ctx || !d || !out) return KTA_ERR_INVALID;
+    if (!d->partition) return fail(ctx, KTA_ERR_INVALID, "metric columns missing");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    kta_internal_columns r{};
+    int rc = kta_internal_resolve(ctx, d, &r);
+    if (rc != KTA_OK) return rc;
+    if (!r.mark) return fail(ctx, KTA_ERR_INVALID, "the batch has no plane marks (not an allocation of kta_device_batch_alloc)");
+    if (r.rec0 % KTA_TILE_RECORDS) return fail(ctx, KTA_ERR_INVALID, "plane marks are read from a tile boundary");
+    if (r.rec0 + n > r.rows) return fail(ctx, KTA_ERR_CAPACITY, "more records than the allocation holds");
+    if (n == 0) return KTA_OK;
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpy(out, r.mark + r.rec0 / KTA_TILE_RECORDS, tiles_of(n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return KTA_OK;
 }
 
@@ -2617,7 +2638,7 @@ int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
 
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns *r)
 {
-    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false, 0, nullptr};
+    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false, 0, nullptr, nullptr};
     uint64_t rec0 = 0;
     if (const kta_batch *e = find_allocation(ctx, c->partition, &kta_batch::partition, &rec0)) {
         if (e->partition + rec0 != c->partition) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
@@ -2625,7 +2646,8 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns 
             (c->val_len && c->val_len != e->val_len + rec0))
             return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
         *r = kta_internal_columns{e->partition, e->key_len, e->val_len, e->ts_ms, e->tile_hdr, rec0, e->key_bytes == nullptr, allocation_rows(*e),
-                                  kta::tile_sums_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS)};
+                                  kta::tile_sums_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS),
+                                  kta::tile_marks_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS)};
         return KTA_OK;
     }
     if (c->layout == KTA_LAYOUT_TILE_COMPACT) {

@@ -33,6 +33,7 @@ struct ScanColumns {
     const kta_tile_hdr *hdr;
     uint64_t rec0;
     const kta_tile_sum *sum;   // the tiles' summaries beside hdr (kta_tile.h), or null: none.  Read by kta_metrics_scan_packed only.
+    const uint32_t *mark;      // the tiles' plane marks beside sum (kta_tile.h), or null: none, or ignored (scan_variant bit 64)
 };
 
 struct AliveColumns {
@@ -73,6 +74,7 @@ struct ScanPlan {
     uint32_t lds_bytes;    // dynamic LDS per workgroup
     uint32_t variant;      // 0 = accumulate (three 64-bit LDS atomics per record or quad), 9 = loads only (diagnostic)
     bool summaries;        // packed: take a summarised tile's timestamp extrema from its summary (req_variant bit 32 clears it)
+    bool planes;           // packed: take a marked tile through its plane (req_variant bit 64 clears it)
     bool packed;           // tile-compact, accumulating, no additive outputs: kta_metrics_scan_packed (two atomics, two
                            // levels of partials in LDS: lds_bytes = 16 P R + 40 P)
     bool nontemporal;      // stream the columns with non-temporal loads

@@ -10,6 +10,7 @@
 #include "kta_kernels.h"
 
 #include <limits.h>
+#include <type_traits>
 
 namespace kta {
 
@@ -134,6 +135,16 @@ __device__ __forceinline__ int4 load16(const void *col, uint64_t i)   // 16-byte
 // not loaded iff its summary is VALID, its header COMPACT, it lies wholly inside [rec0, rec0 + n) and its largest
 // partition counts — then every record of it counts and the tile's extrema are the summary's (kta_tile.h).  Uniform per
 // workgroup and tile, and decided here because the loads run a tile ahead of the accumulation.
+// What a VALID summary s beside the COMPACT header h gives the earliest (lo) and the latest (hi) timestamp:
+__device__ __forceinline__ void tile_sum_extrema(const kta_tile_hdr &h, const kta_tile_sum &s, long long &lo, long long &hi)
+{
+    // a counted record without a timestamp is t = 0 (metric.rs:209); ts_base + ts_span is modular, as tile_unpack_ts
+    const bool timed = (s.flags & KTA_TILE_SUM_TIMED) != 0, untimed = (s.flags & KTA_TILE_SUM_UNTIMED) != 0;
+    lo = timed ? (long long)h.ts_base : LLONG_MAX;
+    hi = timed ? (long long)((uint64_t)h.ts_base + s.ts_span) : LLONG_MIN;
+    lo = (untimed && 0ll < lo) ? 0ll : lo;
+    hi = (untimed && 0ll > hi) ? 0ll : hi;
+}
 // The rule itself, from uniform values alone (h: a COMPACT header): whether tile T is summarised for this scan, and if
 // so what it gives the earliest (lo) and the latest (hi) timestamp.
 __device__ __forceinline__ bool tile_summed(const kta_tile_hdr &h, const kta_tile_sum &s, uint64_t T, const ScanColumns &c, uint64_t n,
@@ -141,12 +152,7 @@ __device__ __forceinline__ bool tile_summed(const kta_tile_hdr &h, const kta_til
 {
     const uint64_t first = T * KTA_TILE_RECORDS;
     if (!((s.flags & KTA_TILE_SUM_VALID) && first >= c.rec0 && first + KTA_TILE_RECORDS <= c.rec0 + n && s.part_max < pc)) return false;
-    // a counted record without a timestamp is t = 0 (metric.rs:209); ts_base + ts_span is modular, as tile_unpack_ts
-    const bool timed = (s.flags & KTA_TILE_SUM_TIMED) != 0, untimed = (s.flags & KTA_TILE_SUM_UNTIMED) != 0;
-    lo = timed ? (long long)h.ts_base : LLONG_MAX;
-    hi = timed ? (long long)((uint64_t)h.ts_base + s.ts_span) : LLONG_MIN;
-    lo = (untimed && 0ll < lo) ? 0ll : lo;
-    hi = (untimed && 0ll > hi) ? 0ll : hi;
+    tile_sum_extrema(h, s, lo, hi);
     return true;
 }
 
@@ -920,23 +926,36 @@ __device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid,
 // ahead than the vector loads in scalar registers, so that no vector load waits for a scalar miss of its own tile.
 // Any other tile (cut by rec0 or n, raw, i32 lengths, part_max >= pc, no VALID summary) is left to the loop of before:
 // see the kernel.
+// Plane tiles (kta_tile.h: a marked tile) go through the same loop in their own form (lean_run<NT, true>): the lane's
+// four records are the four dwords partition | key << 8 | val << 16 of the tile's plane — one 16-byte load, 4 B per
+// record in one stream, 4 vector registers per slot.  A ring holds tiles of ONE form, so that the wait for a slot is
+// exact; a workgroup that meets a summarised tile of the other form drains its ring and goes on in the other
+// instantiation (see packed_scan_lean), so a batch that mixes both keeps every summarised tile here.
 #ifndef KTA_LEAN_PREFETCH
 #define KTA_LEAN_PREFETCH 1
 #endif
-constexpr int kLeanPrefetch = KTA_LEAN_PREFETCH;   // tiles the lean loop loads ahead of the one it accumulates (1 or 2)
-static_assert(kLeanPrefetch == 1 || kLeanPrefetch == 2, "the lean ring has two or three slots");
+constexpr int kLeanPrefetch = KTA_LEAN_PREFETCH;   // tiles the lean loop loads ahead of the one it accumulates (1, 2 or 3)
+static_assert(kLeanPrefetch >= 1 && kLeanPrefetch <= 3, "the lean ring has two, three or four slots");
 
 struct LeanSlot {
     v2i p;    // four u16 partitions
     int4 k;   // four u16 key lengths (x, y), four u16 value lengths (z, w)
 };
+struct PlaneSlot {
+    int4 w;   // four plane words
+};
 constexpr uint64_t kTileColBytes = (uint64_t)KTA_TILE_RECORDS * 4u;   // a tile's own bytes of an i32 column
 
-// whether the lean loop takes tile T (uniform), and its extrema if so
-__device__ __forceinline__ bool lean_tile(const kta_tile_hdr &h, const kta_tile_sum &s, uint64_t T, const ScanColumns &c, uint64_t n,
-                                          uint32_t pc, long long &lo, long long &hi)
+// Whether the lean loop takes a tile (uniform) and in which form: tile_summed's rule with `whole` — the tile lies
+// wholly inside the batch — worked out by the caller from 32-bit tile indices (a 64-bit compare is a vector
+// instruction).  mark: the tile's, 0 where the marks are ignored.  A marked tile is a plane tile whatever the form of
+// its lengths; any other needs u16 lengths.  A taken tile's extrema are tile_sum_extrema's.
+__device__ __forceinline__ void lean_tile(const kta_tile_hdr &h, const kta_tile_sum &s, uint32_t mark, bool whole, uint32_t pc,
+                                          bool &lean, bool &plane)
 {
-    return h.mode == KTA_TILE_COMPACT && h.lens == KTA_TILE_LENS_U16 && tile_summed(h, s, T, c, n, pc, lo, hi);
+    const bool summed = whole && (s.flags & KTA_TILE_SUM_VALID) && s.part_max < pc && h.mode == KTA_TILE_COMPACT;
+    plane = summed && mark == 1u;
+    lean = summed && !plane && h.lens == KTA_TILE_LENS_U16;
 }
 
 // the tile's base is uniform, the lane's byte offsets (8 * tid, 16 * tid) constant over the loop
@@ -951,18 +970,24 @@ __device__ __forceinline__ void lean_load(LeanSlot &s, const ScanColumns &c, uin
     const v4i k = NT ? __builtin_nontemporal_load(kp) : *kp;
     s.k = make_int4(k.x, k.y, k.z, k.w);
 }
+template <bool NT>
+__device__ __forceinline__ void lean_load(PlaneSlot &s, const ScanColumns &c, uint64_t T, uint32_t, uint32_t off16)
+{
+    const char *tb = reinterpret_cast<const char *>(c.ts_ms) + T * (2u * kTileColBytes) + kTilePlaneOffset;
+    const v4i *wp = reinterpret_cast<const v4i *>(tb + off16);
+    const v4i w = NT ? __builtin_nontemporal_load(wp) : *wp;
+    s.w = make_int4(w.x, w.y, w.z, w.w);
+}
 
 // packed_quad_lens<true> of four records that all count; the timestamps' extrema are the caller's (uniform)
-__device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
+// (pt: the partitions; ku / vu: the lengths as stored, knull / tomb: whether they are the form's marker of -1)
+__device__ __forceinline__ void lean_quad_add(const uint32_t (&pt)[4], const uint32_t (&ku)[4], const uint32_t (&vu)[4],
+                                              const uint32_t (&knull)[4], const uint32_t (&tomb)[4], uint32_t rep_log2, uint32_t rep,
+                                              const PackedLds &L, LaneState &st)
 {
-    uint32_t pt[4], ku[4], vu[4], tomb[4], knull[4], ks[4], vs[4];
-    tile_u16x4((uint32_t)s.p.x, (uint32_t)s.p.y, pt);
-    tile_u16x4((uint32_t)s.k.x, (uint32_t)s.k.y, ku);
-    tile_u16x4((uint32_t)s.k.z, (uint32_t)s.k.w, vu);
+    uint32_t ks[4], vs[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        knull[j] = ku[j] == KTA_COMPACT_LEN_NONE;
-        tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
         ks[j] = knull[j] ? 0u : ku[j];
         vs[j] = tomb[j] ? 0u : vu[j];
     }
@@ -993,6 +1018,34 @@ __device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, 
         atomicAdd(&L.W1[slot], pack_dwords(1u | (tomb[j] << 16), ks[j]));
         atomicAdd(&L.W2[slot], pack_dwords(knull[j], vs[j]));
     }
+}
+__device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
+{
+    uint32_t pt[4], ku[4], vu[4], tomb[4], knull[4];
+    tile_u16x4((uint32_t)s.p.x, (uint32_t)s.p.y, pt);
+    tile_u16x4((uint32_t)s.k.x, (uint32_t)s.k.y, ku);
+    tile_u16x4((uint32_t)s.k.z, (uint32_t)s.k.w, vu);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        knull[j] = ku[j] == KTA_COMPACT_LEN_NONE;
+        tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
+    }
+    lean_quad_add(pt, ku, vu, knull, tomb, rep_log2, rep, L, st);
+}
+// the same of a plane slot: four words partition | key << 8 | val << 16 (kta_tile.h)
+__device__ __forceinline__ void lean_quad(const PlaneSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
+{
+    const uint32_t w[4] = {(uint32_t)s.w.x, (uint32_t)s.w.y, (uint32_t)s.w.z, (uint32_t)s.w.w};
+    uint32_t pt[4], ku[4], vu[4], tomb[4], knull[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        pt[j] = w[j] & 0xFFu;
+        ku[j] = (w[j] >> 8) & 0xFFu;
+        vu[j] = w[j] >> 16;
+        knull[j] = ku[j] == KTA_PLANE_KEY_NONE;
+        tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
+    }
+    lean_quad_add(pt, ku, vu, knull, tomb, rep_log2, rep, L, st);
 }
 
 // The workgroup of every packed scan kernel: its LDS words, carved out of the dynamic LDS and zeroed, its lane state,
@@ -1049,7 +1102,8 @@ struct PackedWg {
 
 // The lean kernel of a summary-reading scan (kta_metrics_scan_packed<NT, true>); kta_metrics_scan_packed_rest is launched
 // behind it with the same grid.
-// Its loop takes the summarised compact / u16 tiles (lean_tile) through a ring of LeanSlots, unrolled, with the next
+// Its loop (lean_run) takes the summarised tiles of one form — plane tiles, or compact / u16 tiles (lean_tile) —
+// through a ring of slots, unrolled, with the next
 // undecided tile's header and summary already requested (scalar loads: a step ahead of the vector loads they decide on),
 // and folds their timestamp extrema into two uniform words.  Every decision is made from uniform values: header,
 // summary, rec0, n, P.  A tile that does not qualify is not accumulated here.  Its step — tile = workgroup + step x grid
@@ -1067,84 +1121,106 @@ __device__ __forceinline__ uint32_t lean_list_entry(uint64_t list_a, uint64_t li
     return (uint32_t)((i < 2 ? list_a : list_b) >> (32u * (i & 1u)));
 }
 
-template <bool NT>
-__device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t n, uint32_t P, uint32_t rep_log2,
-                                                 uint64_t *__restrict__ partials, uint32_t row_len, unsigned long long *lds,
-                                                 long long (&s_red)[kWG / 64][6])
-{
-    PackedWg wg(lds, P, rep_log2);
-    const uint32_t tid = wg.tid;
-    // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
-    const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
-    const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+// What a workgroup of the lean kernel carries from one run of the loop to the next (uniform).
+// Tiles are counted from the batch's first (t0) in 32 bits: launch_metrics_scan keeps a batch of 2^31 tiles out.
+struct LeanRun {
+    uint32_t tile = 0;                  // the next tile to accumulate = workgroup + step x grid
+    uint32_t step = 0;
+    uint32_t end = 0;                   // this kernel's tiles end here: the batch's end, or the handed-over tile
+    uint32_t whole_lo = 0, whole_hi = 0;   // tiles [whole_lo, whole_hi) lie wholly inside the batch
+    uint32_t listed = 0;                // entries on the list
+    uint64_t list_a = 0, list_b = 0;    // the list: four steps + 1, 32 bits each
+    uint32_t handover = 0;              // the step the rest kernel takes everything from, + 1
     uint32_t since_flush = 0;
-    uint64_t tile = blockIdx.x;
-    const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
-    const uint64_t last = t0 + ntiles - 1;
-    const uint64_t G = gridDim.x;
-    uint64_t end = ntiles;                    // this kernel's tiles end here: the batch's end, or the handed-over tile
-    uint64_t issued = tile;                   // the next tile to decide on and load: kLeanPrefetch steps ahead of `tile`
-    uint32_t istep = 0, listed = 0;           // issued = workgroup + istep x grid; entries on the list
-    uint64_t list_a = 0, list_b = 0;          // the list: four steps + 1, 32 bits each
-    uint64_t handover = 0;                    // the step the rest kernel takes everything from, + 1
-    long long u_tmin = LLONG_MAX, u_tmax = LLONG_MIN;   // the lean tiles' extrema: uniform, in scalar registers
-    kta_tile_hdr ah;                          // header and summary of tile `issued`, requested a step before they are
-    uint2 as;                                 // used (the summary as its two dwords: taking the u16 fields apart
-                                              // belongs to the use, not to the load)
+};
+
+// One run of the lean loop over tiles of one form (PLANE: plane tiles, else compact / u16 tiles), from r.tile on, until
+// the workgroup's tiles end or a summarised tile of the OTHER form comes up: r.tile is then that tile, the ring is
+// drained, and the caller goes on in the other instantiation.
+template <bool NT, bool PLANE>
+__device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanColumns &c, uint64_t t0, uint32_t last, uint32_t pc,
+                                         uint32_t rep_log2)
+{
+    using Slot = typename std::conditional<PLANE, PlaneSlot, LeanSlot>::type;
+    const uint32_t tid = wg.tid;
+    const uint32_t G = gridDim.x;
+    uint32_t stop = r.end;                    // this run's tiles end here: r.end, or the tile of the other form
+    bool switched = false;
+    uint32_t issued = r.tile;                 // the next tile to decide on and load: kLeanPrefetch steps ahead of r.tile
+    uint32_t istep = r.step;                  // issued = workgroup + istep x grid
+    uint32_t sw_step = 0;
+    kta_tile_hdr ah;                          // header, summary and mark of tile `issued`, requested a step before they
+    uint2 as;                                 // are used (the summary as its two dwords: taking the u16 fields apart
+    uint32_t am = 0;                          // belongs to the use, not to the load); no marks: every mark is 0
     // (the index is clamped, not the load skipped — a skipped load merges with the old value, and the merge waits —
     // so nothing past the batch's last tile is read)
     auto look_ahead = [&]() {
-        const uint64_t T = t0 + issued < last ? t0 + issued : last;
+        const uint64_t T = t0 + (issued < last ? issued : last);
         ah = c.hdr[T], as = reinterpret_cast<const uint2 *>(c.sum)[T];
+        if (c.mark) am = c.mark[T];
     };
-    // One step of the ring's front: decide on tile `issued` and load it into slot s; v: the slot holds a lean tile.
-    // The loads go out whatever the decision (of a tile that is not lean or lies past the end — then the batch's last
+    // One step of the ring's front: decide on tile `issued` and load it into slot s; v: the slot holds a tile of this
+    // run's form.
+    // The loads go out whatever the decision (of a tile that is not taken or lies past the end — then the batch's last
     // tile again — they fetch bytes of the tile's own that nobody uses): a slot is then waited for behind the same
     // number of younger loads on every path, and the wait can let those stay in flight.
-    auto issue = [&](LeanSlot &s, bool &v) {
-        const uint64_t T = t0 + issued < last ? t0 + issued : last;
-        const bool in = issued < end;
-        long long lo = LLONG_MAX, hi = LLONG_MIN;
+    auto issue = [&](Slot &s, bool &v) {
+        const uint64_t T = t0 + (issued < last ? issued : last);
+        const bool in = issued < stop;
         const kta_tile_sum sm{as.x, (uint16_t)(as.y & 0xFFFFu), (uint16_t)(as.y >> 16)};
-        v = lean_tile(ah, sm, T, c, n, pc, lo, hi) && in;
+        bool lean, plane;
+        lean_tile(ah, sm, am, issued >= r.whole_lo && issued < r.whole_hi, pc, lean, plane);
+        v = (PLANE ? plane : lean) && in;
+        const bool other = (PLANE ? lean : plane) && in;
         lean_load<NT>(s, c, T, 8u * tid, 16u * tid);
-        u_tmin = (v && lo < u_tmin) ? lo : u_tmin;
-        u_tmax = (v && hi > u_tmax) ? hi : u_tmax;
-        if (in && !v) {
-            if (listed == kLeanListed) {
-                handover = (uint64_t)istep + 1;
-                end = issued;
+        if (other) {
+            switched = true;
+            sw_step = istep;
+            stop = issued;
+        } else if (in && !v) {
+            if (r.listed == kLeanListed) {
+                r.handover = istep + 1u;
+                r.end = stop = issued;
             } else {
-                const uint64_t e = (uint64_t)(istep + 1u) << (32u * (listed & 1u));
-                if (listed < 2) list_a |= e;
-                else list_b |= e;
-                listed++;
+                const uint64_t e = (uint64_t)(istep + 1u) << (32u * (r.listed & 1u));
+                if (r.listed < 2) r.list_a |= e;
+                else r.list_b |= e;
+                r.listed++;
             }
         }
         issued += G;
         istep++;
         look_ahead();
     };
-    auto take = [&](const LeanSlot &s, bool v) {
+    auto take = [&](const Slot &s, bool v) {
         if (v) {
             lean_quad(s, rep_log2, wg.rep, wg.L, wg.st);
-            if (++since_flush == kFrontFlushTiles) {
+            if (++r.since_flush == kFrontFlushTiles) {
                 wg.front_flush();
-                since_flush = 0;
+                r.since_flush = 0;
             }
         }
-        tile += G;
+        r.tile += G;
+        r.step++;
     };
     // the ring, unrolled: no rotation moves, one exit
-    LeanSlot s0, s1, s2;
-    bool v0 = false, v1 = false, v2 = false;
-    if (tile < ntiles) {   // (else there is no tile to clamp to)
-        look_ahead();
-        issue(s0, v0);
-        if (kLeanPrefetch == 2) issue(s1, v1);
-    }
-    while (tile < end) {
-        if (kLeanPrefetch == 2) {
+    Slot s0, s1, s2, s3;
+    bool v0 = false, v1 = false, v2 = false, v3 = false;
+    look_ahead();
+    issue(s0, v0);
+    if (kLeanPrefetch >= 2) issue(s1, v1);
+    if (kLeanPrefetch == 3) issue(s2, v2);
+    while (r.tile < stop) {
+        if (kLeanPrefetch == 3) {
+            issue(s3, v3);
+            take(s0, v0);
+            issue(s0, v0);
+            take(s1, v1);
+            issue(s1, v1);
+            take(s2, v2);
+            issue(s2, v2);
+            take(s3, v3);
+        } else if (kLeanPrefetch == 2) {
             issue(s2, v2);
             take(s0, v0);
             issue(s0, v0);
@@ -1158,16 +1234,58 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
             take(s1, v1);
         }
     }
+    // (the unrolled ring may have stepped past `stop`: slots issued at or behind it hold no tile)
+    if (switched) r.tile = blockIdx.x + sw_step * G, r.step = sw_step;
+}
+
+template <bool NT>
+__device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t n, uint32_t P, uint32_t rep_log2,
+                                                 uint64_t *__restrict__ partials, uint32_t row_len, unsigned long long *lds,
+                                                 long long (&s_red)[kWG / 64][6])
+{
+    PackedWg wg(lds, P, rep_log2);
+    const uint32_t tid = wg.tid;
+    // allocation tiles [t0, t0 + ntiles) hold the batch; record a of the allocation is the batch's iff a - rec0 < n
+    const uint64_t t0 = c.rec0 / KTA_TILE_RECORDS;
+    const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
+    const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
+    LeanRun r;
+    r.tile = blockIdx.x;
+    r.end = (uint32_t)ntiles;
+    r.whole_lo = c.rec0 % KTA_TILE_RECORDS ? 1u : 0u;
+    r.whole_hi = (uint32_t)((c.rec0 + n) / KTA_TILE_RECORDS - t0);
+    const uint32_t last = r.end - 1u;
+    // Runs of the two forms in turn (r.tile < ntiles: there is a tile to clamp to).  A run that begins at a tile of the
+    // other form ends at once, and the other one takes that tile, so every turn but the first takes a tile.  With marks
+    // the plane form goes first: the flagship's tiles are all marked.
+    bool plane = c.mark != nullptr;
+    while (r.tile < r.end) {
+        if (plane) lean_run<NT, true>(wg, r, c, t0, last, pc, rep_log2);
+        else lean_run<NT, false>(wg, r, c, t0, last, pc, rep_log2);
+        plane = !plane;
+    }
+    // The taken tiles' timestamp extrema, off the loop (where they were some thirty scalar and vector instructions per
+    // tile): every thread folds the summaries of some of the workgroup's tiles below r.end; the same rule decides again
+    // which of them were taken — a listed tile is one it refuses.
+    for (uint64_t i = blockIdx.x + (uint64_t)tid * gridDim.x; i < r.end; i += (uint64_t)kWG * gridDim.x) {
+        const kta_tile_hdr h = c.hdr[t0 + i];
+        const kta_tile_sum sm = c.sum[t0 + i];
+        const uint32_t mark = c.mark ? c.mark[t0 + i] : 0u;
+        bool lean, plane;
+        lean_tile(h, sm, mark, i >= r.whole_lo && i < r.whole_hi, pc, lean, plane);
+        long long lo, hi;
+        tile_sum_extrema(h, sm, lo, hi);
+        wg.st.tmin = ((lean || plane) && lo < wg.st.tmin) ? lo : wg.st.tmin;
+        wg.st.tmax = ((lean || plane) && hi > wg.st.tmax) ? hi : wg.st.tmax;
+    }
     wg.front_flush();
-    wg.st.tmin = u_tmin < wg.st.tmin ? u_tmin : wg.st.tmin;
-    wg.st.tmax = u_tmax > wg.st.tmax ? u_tmax : wg.st.tmax;
     uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
     wg.write_row(row, s_red);
     if (tid == 0) {   // (behind the zeroes write_scan_globals put there)
         uint64_t *g = row + (uint64_t)P * kScanCols;
-        g[kScanListA] = list_a;
-        g[kScanHandover] = handover;
-        g[kScanListB] = list_b;
+        g[kScanListA] = r.list_a;
+        g[kScanHandover] = r.handover;
+        g[kScanListB] = r.list_b;
     }
 }
 
@@ -1446,9 +1564,11 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
                    uint32_t timeline_buckets)
 {
     ScanPlan pl;
-    // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads; +32 = no tile summaries
+    // req_variant: low bits 0 = accumulate, 9 = loads only (diagnostic); +16 = non-temporal loads; +32 = no tile summaries;
+    // +64 = ignore the plane marks (a summarised tile is read in its u16 form)
     const int base = req_variant & 15;
     pl.summaries = (req_variant & 32) == 0;
+    pl.planes = (req_variant & 64) == 0;
     const bool timeline = timeline_buckets != 0u;
     pl.analytics = analytics;
     pl.nontemporal = (analytics || timeline) ? true : (req_variant & 16) != 0;
@@ -1482,7 +1602,8 @@ ScanPlan plan_scan(uint32_t P, uint64_t n, int cu_count, int req_workgroups, int
     // (a workgroup needing more than 40 KiB of LDS only fits twice per CU: use 2 per CU then)
     // Tile-compact layout: a lane has 56 B of a tile in flight instead of 80, and 3 per CU leave HBM short of
     // requests (2^30 records of config 4: 2.85 ms at 3 per CU, 2.44 at 4, 2.32 at 5, 2.66 at 6, 2.96 at 7) — 5 per
-    // CU, as far as the LDS of 160 KiB per CU lets them all be resident.
+    // CU, as far as the LDS of 160 KiB per CU lets them all be resident.  The plane form (4 B per record, 16 B per lane
+    // in flight) was swept again and keeps both (profiles/plane_scan.jsonl).
     uint32_t per_cu = pl.lds_bytes > 40u * 1024u ? 2u : 3u;
     if (tiled) {
         const uint32_t fit = (160u * 1024u) / (pl.lds_bytes + 256u);
@@ -1531,6 +1652,9 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
         if (!tiled) return hipErrorInvalidValue;
         ScanColumns cs = c;
         if (!pl.summaries) cs.sum = nullptr;
+        if (!pl.planes || !cs.sum) cs.mark = nullptr;
+        // (the lean kernel counts the batch's tiles, and a few grids ahead of them, in 32 bits)
+        if ((c.rec0 % KTA_TILE_RECORDS + n) / KTA_TILE_RECORDS >= (1ull << 31)) cs.sum = nullptr, cs.mark = nullptr;
         if (!cs.sum) return nt ? launch(kta_metrics_scan_packed<true, false>, cs) : launch(kta_metrics_scan_packed<false, false>, cs);
         // the lean kernel, then — same grid, same rows — the tiles its workgroups left (none, where every tile is
         // summarised, compact and u16: a workgroup of the second kernel then reads one word and ends)

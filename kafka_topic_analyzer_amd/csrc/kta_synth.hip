@@ -39,10 +39,11 @@ __global__ __launch_bounds__(kWG) void synth_fill_cols(kta_synth_spec sp, uint64
 // the four metric columns are reduced over the tile first — does every id fit a u16, do the timestamps span less than
 // 2^31 ms, and (lens16: the allocation has no key columns) does every length fit a u16 — and then stored compact or raw
 // into the allocation's tile t0 + T (part, klen, vlen, ts: the allocation's record 0), with its header.  One pass, as
-// the raw fill.
+// the raw fill.  A whole compact tile of which every record fits the scan plane (kta_tile.h) gets its plane, 4 B per
+// record more, and its mark with the summary.
 __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint64_t first, uint64_t n, int32_t *part,
                                                         int32_t *klen, int32_t *vlen, int64_t *ts, uint64_t *seq,
-                                                        kta_tile_hdr *hdr, kta_tile_sum *sum, uint64_t t0, uint32_t lens16)
+                                                        kta_tile_hdr *hdr, kta_tile_sum *sum, uint32_t *mark, uint64_t t0, uint32_t lens16)
 {
     __shared__ long long s_red[kWG / 64][4];
     const uint32_t tid = threadIdx.x;
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
     for (uint64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
         int32_t p[4], kl[4], vl[4];
         int64_t t[4];
-        long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;   // wide: bit 0 a partition id, bit 1 a length outside the u16 form
+        long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;   // wide: bit 0 a partition id, bit 1 a length outside the u16 form, bit 2 a record outside the plane's
         long long seen = 0;   // the summary's (real records only): bits 0-15 the largest stored u16 partition, bit 16 a timestamp of -1
         for (uint32_t j = 0; j < 4; j++) {
             const uint64_t i = T * KTA_TILE_RECORDS + 4u * tid + j;
@@ -62,6 +63,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             if (seq) seq[i] = first + i;
             wide |= kta::tile_part_fits(p[j]) ? 0 : 1;
             wide |= kta::tile_len_fits(kl[j]) && kta::tile_len_fits(vl[j]) ? 0 : 2;
+            wide |= kta::tile_plane_fits(p[j], kl[j], vl[j]) ? 0 : 4;
             const long long pm = kta::tile_pack_part(p[j]);
             seen = (seen & 0x10000) | ((seen & 0xFFFF) > pm ? (seen & 0xFFFF) : pm) | (t[j] == -1 ? 0x10000 : 0);
             if (t[j] != -1) {
@@ -119,7 +121,14 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             reinterpret_cast<int4 *>(klen)[A / 4 + tid] = make_int4(kl[0], kl[1], kl[2], kl[3]);
             reinterpret_cast<int4 *>(vlen)[A / 4 + tid] = make_int4(vl[0], vl[1], vl[2], vl[3]);
         }
+        // the plane: behind the offsets, in the second half of the tile's bytes of ts; only of a tile this call wrote whole
+        const bool plane = mark && compact && !(wide & 4) && n - T * KTA_TILE_RECORDS >= KTA_TILE_RECORDS;
+        if (plane)
+            reinterpret_cast<uint4 *>(ts)[A / 2 + kta::kTilePlaneOffset / 16u + tid] =
+                make_uint4(kta::tile_plane_pack(p[0], kl[0], vl[0]), kta::tile_plane_pack(p[1], kl[1], vl[1]),
+                           kta::tile_plane_pack(p[2], kl[2], vl[2]), kta::tile_plane_pack(p[3], kl[3], vl[3]));
         if (tid == 0) {
+            if (mark) mark[t0 + T] = plane ? 1u : 0u;
             hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, u16 ? KTA_TILE_LENS_U16 : KTA_TILE_LENS_I32};
             // the summary with the header (kta_tile.h): of a compact tile this call wrote whole, else none
             const uint64_t m = n - T * KTA_TILE_RECORDS < KTA_TILE_RECORDS ? n - T * KTA_TILE_RECORDS : KTA_TILE_RECORDS;
@@ -304,7 +313,7 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
         // of the caller's own beside it
         const uint32_t lens16 = ac.keyless && !b->key_off && !b->key_bytes ? 1u : 0u;
         hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, ac.partition,
-                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, ac.sum, rec0 / KTA_TILE_RECORDS, lens16);
+                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, ac.sum, ac.mark, rec0 / KTA_TILE_RECORDS, lens16);
     } else {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);

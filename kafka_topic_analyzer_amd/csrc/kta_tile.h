@@ -55,6 +55,41 @@ KTA_TILE_HD inline kta_tile_sum tile_summary(int64_t lo, int64_t hi, uint32_t pa
     return s;
 }
 
+// ---- a tile's scan plane (kta_hip.h) ------------------------------------------------------------------------------
+// A compact tile uses the first half of its 8 KiB of the ts_ms column; the plane is the second half: one dword per
+// record — partition | key << 8 | val << 16 — all that the metrics scan needs of a record whose timestamps the summary
+// covers, in one stream.  It repeats what the u16 / i32 forms hold; every other reader keeps reading those.
+// Which records fit: a partition in [0, 256) (no sentinel: a tile with an id of -1 has no plane), a key length in
+// [-1, 255) (0xFF is -1), a value length under tile_len_fits' rule (0xFFFF is -1).
+// The mark: a tile has a plane exactly when its mark is 1.  The rule of validity is the summaries' with one more
+// sentence: a mark is trusted only next to a KTA_TILE_COMPACT header and a VALID summary; whoever writes a tile's
+// summary writes its mark, 0 or 1, in the same step, and the plane before it.  The mark is 1 only for a compact tile of
+// all KTA_TILE_RECORDS records of which every one fits.  A header that turns RAW needs nothing more; widening the
+// lengths touches neither the ts_ms bytes nor the values.  The plane does not depend on `lens`: keyed allocations have
+// planes too.
+// The address rule: the marks, a u32 per tile, lie behind the summaries in the same device allocation.
+constexpr uint32_t KTA_PLANE_PARTS = 256u, KTA_PLANE_KEY_NONE = 0xFFu;
+constexpr uint32_t kTilePlaneOffset = KTA_TILE_RECORDS * 4u;   // the plane's first byte among the tile's bytes of ts_ms
+KTA_TILE_HD inline uint32_t *tile_marks_behind(kta_tile_hdr *hdr, uint64_t ntiles)
+{
+    return reinterpret_cast<uint32_t *>(tile_sums_behind(hdr, ntiles) + ntiles);
+}
+constexpr uint64_t kTileSideBytes = sizeof(kta_tile_hdr) + sizeof(kta_tile_sum) + sizeof(uint32_t);   // header, summary, mark
+KTA_TILE_HD inline bool tile_plane_fits(int32_t p, int32_t k, int32_t v)
+{
+    return p >= 0 && p < (int32_t)KTA_PLANE_PARTS && k >= -1 && k < (int32_t)KTA_PLANE_KEY_NONE && tile_len_fits(v);
+}
+// (of a record that fits: -1 is all ones, so the masks make the sentinels)
+KTA_TILE_HD inline uint32_t tile_plane_pack(int32_t p, int32_t k, int32_t v)
+{
+    return (uint32_t)p | (((uint32_t)k & 0xFFu) << 8) | ((uint32_t)v << 16);
+}
+KTA_TILE_HD inline int32_t tile_plane_part(uint32_t w) { return (int32_t)(w & 0xFFu); }
+KTA_TILE_HD inline int32_t tile_plane_key(uint32_t w) { return ((w >> 8) & 0xFFu) == KTA_PLANE_KEY_NONE ? -1 : (int32_t)((w >> 8) & 0xFFu); }
+KTA_TILE_HD inline int32_t tile_plane_val(uint32_t w) { return (w >> 16) == KTA_COMPACT_LEN_NONE ? -1 : (int32_t)(w >> 16); }
+// byte of the tile's own bytes of the ts_ms column where the word of record j of the tile sits
+KTA_TILE_HD inline uint32_t tile_plane_at(uint32_t j) { return kTilePlaneOffset + 4u * j; }
+
 // ---- one value ----------------------------------------------------------------------------------------------------
 KTA_TILE_HD inline uint16_t tile_pack_part(int32_t p) { return p == -1 ? (uint16_t)KTA_COMPACT_PART_NONE : (uint16_t)p; }
 KTA_TILE_HD inline int32_t tile_unpack_part(uint32_t u) { return u == KTA_COMPACT_PART_NONE ? -1 : (int32_t)u; }
@@ -160,6 +195,21 @@ inline void tile_unpack_host(const kta_tile_hdr &h, const int32_t *part, const i
         k[j - j0] = u16 ? tile_unpack_len(g16[tile_klen_slot((uint32_t)j)]) : klen[j];
         v[j - j0] = u16 ? tile_unpack_len(g16[tile_vlen_slot((uint32_t)j)]) : vlen[j];
     }
+}
+
+// The plane of the tile that tile_pack_host packed from the same records with header h: the mark, and — iff it is 1 —
+// the plane's words in bytes [kTilePlaneOffset, 2 kTilePlaneOffset) of the tile's ts image; nothing else is written.
+inline uint32_t tile_plane_host(const kta_tile_hdr &h, const int32_t *p, const int32_t *k, const int32_t *v, uint64_t m, int64_t *ts)
+{
+    if (h.mode != KTA_TILE_COMPACT || m != KTA_TILE_RECORDS) return 0u;
+    for (uint64_t j = 0; j < m; j++)
+        if (!tile_plane_fits(p[j], k[j], v[j])) return 0u;
+    unsigned char *plane = reinterpret_cast<unsigned char *>(ts);
+    for (uint64_t j = 0; j < m; j++) {
+        const uint32_t w = tile_plane_pack(p[j], k[j], v[j]);
+        memcpy(plane + tile_plane_at((uint32_t)j), &w, 4);
+    }
+    return 1u;
 }
 
 #ifdef __HIPCC__

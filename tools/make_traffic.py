@@ -64,9 +64,9 @@ out = {"round": 14, "source": path,
 CSRC = "kafka_topic_analyzer_amd/csrc/"
 SCAN_SRC = "+".join(CSRC + f for f in ("kta_kernels.hip", "kta_tile.h"))
 n_scan = 1 << 30
-# the flagship's batch is tile-compact and keyless: the packed scan, 6 B per record read where
-# every tile is compact with u16 lengths and summarised (config 4: the timestamps are not loaded); the algorithmic bytes
-# stay the 20 of the four fields
+# the flagship's batch is tile-compact and keyless: the packed scan, 4 B per record read where
+# every tile is summarised and has a scan plane (config 4: neither the timestamps nor the u16 forms are loaded); the
+# algorithmic bytes stay the 20 of the four fields
 SCAN = "kta_metrics_scan_packed<true, true>"
 f, w = find(SCAN, "FETCH_SIZE", largest_grid=True), find(SCAN, "WRITE_SIZE", largest_grid=True)
 rd, wr = 2 * f[1] * KIB, w[1] * KIB
@@ -74,8 +74,8 @@ scan_entry = {"kernel": SCAN.replace(" ", ""), "records_per_launch": n_scan,
               "algorithmic_bytes_per_launch": 20 * n_scan, "FETCH_SIZE_kib_avg": f[1], "WRITE_SIZE_kib_avg": w[1],
               "hbm_read_bytes_per_launch": rd, "hbm_write_bytes_per_launch": wr, "hbm_bytes_per_launch": rd + wr,
               "ratio_to_algorithmic": (rd + wr) / (20 * n_scan), "bytes_per_record": (rd + wr) / n_scan,
-              "note": "the batch is tile-compact and keyless (every tile of config 4 compact with u16 lengths and summarised: 6 B "
-                      "per record read, the timestamps are not loaded); the algorithmic bytes stay the 20 of the four fields",
+              "note": "the batch is tile-compact and keyless (every tile of config 4 summarised and with a scan plane: 4 B per "
+                      "record read, one dword of partition | key << 8 | val << 16); the algorithmic bytes stay the 20 of the four fields",
               **src(SCAN_SRC)}
 print("scan: read %.3f GB = %.2f B per record vs 20 B x 2^30 = %.3f GB" % (rd / 1e9, rd / n_scan, 20 * n_scan / 1e9), file=sys.stderr)
 if len(sys.argv) > 2 and sys.argv[2] == "--scan-only":
