@@ -871,6 +871,87 @@ int kta_size_bin_bounds(uint32_t bin, uint64_t *lo, uint64_t *hi);
  * bad arguments. */
 int kta_size_quantile(const uint64_t *hist464, uint64_t num, uint64_t den, uint64_t *lo, uint64_t *hi);
 
+/* Retention what-if (NOT in the reference; opt-in by call, like the timeline: kta_set_segments): the log segments of every
+ * partition under a model of cleanup.policy=delete, from which "with retention.ms=X and / or retention.bytes=Y, how many
+ * records and bytes does each partition keep" is answered on the host, exactly, for any number of policies after one pass.
+ * The broker deletes whole segments, oldest first, and stops at the first one that must stay — an order-dependent,
+ * per-partition, prefix-shaped rule; the pass computes, for every record, its position in its partition's log.
+ *
+ * Configuration: S = segment_bytes, 1 <= S <= 2^40 (any value, not only powers of two); M = rows_per_partition, 2 <= M and
+ * P * M <= 2^20; overhead = record_overhead, a u32 added to every record's model size.
+ * Records that take part: every record the metrics handler counts — `which & 1`, partition p in [0, P).  A record with a
+ * partition outside [0, P) adds 1 to a global word and touches nothing else.  Records handed only to the alive-key handler
+ * (which == 2) and the batches of a compaction replay touch nothing; a filtered context sees only the passing records.
+ * Per-partition running state, in consumption order (batches as submitted, records by index) — device state, whose end
+ * values are part of the result: C[p] records, B[p] bytes, T[p] tombstones, H[p] the largest timestamp among the records
+ * with ts_ms >= 0, stored as H + 1 with 0 for none.  For a record of partition p with the size
+ * z = overhead + max(key_len, 0) + max(val_len, 0) (as u64):
+ *     s      = min(floor(B[p] / S), M - 1)          the segment its first byte falls into
+ *     C[p] += 1;  B[p] += z;  T[p] += (val_len < 0);  if ts_ms >= 0: H[p] = max(H[p], ts_ms)
+ *     s_next = min(floor(B[p] / S), M - 1)
+ *     if s_next > s:   row[p][s] = { C[p], B[p], T[p], H[p] + 1 }      the record CLOSES segment s
+ * Exactly one record closes a given row.  A record larger than S skips rows: they stay all zero, an empty segment.  Row
+ * M - 1 never closes: it and the running state hold everything beyond the table.  H at a closing record is the running
+ * maximum over the whole partition up to there, not the segment's own: "segment k and all before it are older than the
+ * cut" is exactly "the running maximum at the end of k is older than the cut".
+ * The vector, u64[(P*M + P) * 4 + 8]: the rows [p*M + s][4], the totals [P][4] (the running state, H + 1 in word 3), eight
+ * globals: records counted, records with a partition outside [0, P), rows closed, S, M, overhead, two zero words.
+ * Merging: every word except the three configuration globals is a SUM; vectors merge exactly when every partition's records
+ * went through ONE context in order (non-owners hold zeros); the configuration globals must agree (kta_merge_segments
+ * refuses a mismatch).
+ * Identities with the counter vector of the same records: totals[p].C == total[p], totals[p].T == tombstones[p],
+ * totals[p].B - overhead * totals[p].C == key_size_sum[p] + value_size_sum[p], global 0 == KTA_G_RECORDS (which counts
+ * the records with a partition in [0, P) only), global 1 == KTA_G_BAD_PARTITION.
+ * The what-if (kta_retention_whatif), a pure host function of the vector, now_ms, retention_ms and retention_bytes (-1: the
+ * rule is off): per partition, walk the closed, non-empty rows oldest first.  A closed row k with end values E_k is deleted
+ * when every earlier closed row is deleted and at least one of
+ *     time: E_k.H exists and now_ms - E_k.H > retention_ms;     size: totals.B - E_k.B >= retention_bytes
+ * holds (the latter is what Kafka's `diff - segment.size >= 0` loop amounts to).  The walk stops at the first row neither
+ * rule takes; the open tail is the active segment, which the model never deletes.
+ * Model limits: the rolling rule is "the record's first byte falls into the segment", which is prefix-computable — not the
+ * broker's greedy "roll when the batch would not fit" — so a boundary can differ by at most one record per segment;
+ * segment.ms rolling is not modelled; sizes are key + value + overhead, not bytes on disk (no batch headers, no
+ * compression); a prefix without any timestamp is not deleted by time.  B is a u64 and is taken not to wrap.
+ *
+ * kta_set_segments turns the pass on (or re-configures it): refused (KTA_ERR_INVALID) once the context has been handed a
+ * record since kta_create / kta_reset, outside the bounds above, and with more than kta_segments_max_partitions()
+ * partitions.  kta_reset keeps the configuration and zeroes the vector with its running state. */
+int kta_set_segments(kta_ctx *ctx, uint64_t segment_bytes, uint32_t rows_per_partition, uint32_t record_overhead);
+/* u64 words of the vector for P partitions and M rows: (P*M + P) * 4 + 8, below 2^24 (0 outside the bounds). */
+uint32_t kta_segments_words(uint32_t n_partitions, uint32_t rows_per_partition);
+/* The live vector, copied to out[n_u64] (n_u64 = kta_segments_words(P, M); staged messages are flushed first). */
+int kta_get_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the
+ * whole job's vector on every rank — exact when every partition's records went through ONE rank in order, as kta.gpus=N
+ * shards (the timestamp-order pass's precondition).  The grouped launch of kta_exchange reduces every word with SUM but
+ * the last five (S, M, overhead, two zero words), which it reduces with MAX: equal on every rank, they stay what they
+ * are.  The live vector is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot: what collectives (distributed.py) reduce in place. */
+int kta_segments_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* The largest P a context with segments may have (a wave of the apply kernel keeps 41 B per partition in LDS). */
+int kta_segments_max_partitions(void);
+/* Work counters of the pass since kta_create / kta_reset (profiling; staged messages are flushed first, waits for the
+ * compute stream): out[0] chunks, out[1] records of the last launch triple's chunk, out[2] launch triples, out[3] chunks
+ * the apply kernel ran its wave step over, out[4] chunks it skipped because no partition crossed a segment boundary in
+ * them, out[5] colliding groups the wave step resolved. */
+int kta_segments_info(kta_ctx *ctx, uint64_t out[6]);
+/* Tests: records per chunk, a multiple of 64 (0: by the slice's length).  The result does not depend on it. */
+int kta_set_segments_chunk(kta_ctx *ctx, uint64_t records);
+/* Host-side merge of two vectors u64[kta_segments_words(P, M)] (acc <- acc + other, every word but S, M, overhead, modulo
+ * 2^64).  KTA_ERR_INVALID for bad bounds, and when the two configurations differ (acc is then as it was). */
+int kta_merge_segments(uint64_t *acc, const uint64_t *other, uint32_t n_partitions, uint32_t rows_per_partition);
+/* The what-if over a vector (pure host; needs no device): out[(P + 1)][KTA_RETENTION_WORDS], a row per partition and one
+ * for the topic (sums; its rule word is the OR of the partitions', its clamped word their count):
+ *   [0] segments (closed non-empty rows, + 1 if the open tail holds a record), [1] records, [2] bytes, [3] tombstones now,
+ *   [4] records, [5] bytes, [6] tombstones kept, [7] segments deleted, [8] rule: 0 nothing deleted, 1 the time rule reached
+ *   at least as far as the size rule, 2 the size rule further, [9] the partition outgrew its M rows
+ *   (floor(totals.B / S) >= M - 1: the last row holds the rest and is treated as active).
+ * retention_ms / retention_bytes: -1 turns the rule off; values below -1 are KTA_ERR_INVALID. */
+#define KTA_RETENTION_WORDS 10
+int kta_retention_whatif(const uint64_t *vec, uint32_t n_partitions, uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms,
+                         int64_t retention_bytes, uint64_t *out, size_t n_u64);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1039,6 +1120,22 @@ int kta_render_size_percentiles(const uint64_t *vec, const uint64_t *counter_vec
  * still written).  Output buffer conventions as kta_render_report. */
 int kta_render_compaction(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap,
                           size_t *out_len);
+/* The section kta-analyzer prints with --librdkafka kta.segments=<size> (1g, 512m, 64k or bytes; kta.segments.rows=M,
+ * default 1024, lowered so that P * M <= 2^20; kta.segments.overhead=B, default 0; kta.retention.ms=<duration> in the
+ * timeline's syntax, kta.retention.bytes=<size>, kta.retention.now=<unix seconds>, default the run's start time) after the
+ * partitioner and compaction sections and before the filter's, from a segment vector (definition above kta_set_segments);
+ * not part of the reference report:
+ *   `Retention what-if: model log segments of <S> bytes per partition (kta.segments), retention.ms=<ms>,
+ *    retention.bytes=<bytes>, now=<ms> ms (not part of the reference report)` — `-` for a rule that is off, and `no
+ *    retention policy given` in place of the three when both are;
+ *   a table (P | Segments | Records | Bytes | Records kept | Bytes kept | Reclaimed % | Rule), one row per partition and an
+ *    `All` row — Segments ends in `+` for a partition that outgrew its M rows, Reclaimed % has two decimals (`-` without
+ *    bytes), Rule is `time`, `size` or `-` (`time+size` in the All row when partitions differ) —, only the first four
+ *    columns when no policy is given;
+ *   a line counting the partitions that outgrew their rows, when there are any; the model-limits note; a closing `=` rule.
+ * KTA_ERR_INVALID for what kta_retention_whatif refuses.  Output buffer conventions as kta_render_report. */
+int kta_render_retention(const uint64_t *vec, uint32_t n_partitions, uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms,
+                         int64_t retention_bytes, char *out, size_t out_cap, size_t *out_len);
 /* The section kta-analyzer prints after everything else when a filter was given (--librdkafka kta.from=<epoch seconds>,
  * kta.to=<epoch seconds>, kta.partitions=0,3-5); not part of the reference report:
  *   `Record filter: everything above describes the records that passed, and no others (kta.from, kta.to, kta.partitions;

@@ -31,7 +31,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "ts_order_max_partitions", "split_ts_order", "render_partitioner", "merge_partitioner",
            "partitioner_max_partitions", "split_partitioner", "murmur2", "render_compaction", "split_compaction",
            "compaction_max_partitions", "split_size_quantiles", "merge_size_quantiles", "render_size_percentiles", "size_bin",
-           "size_bin_bounds", "size_quantile", "size_quantiles_max_partitions"]
+           "size_bin_bounds", "size_quantile", "size_quantiles_max_partitions", "segments_words", "segments_max_partitions",
+           "split_segments", "merge_segments", "retention_whatif", "RETENTION_COLUMNS", "render_retention"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -80,7 +81,7 @@ class HipMetricHandler:
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
-                 compaction: bool = False, size_quantiles: bool = False):
+                 compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -93,7 +94,9 @@ class HipMetricHandler:
         compaction: the compaction what-if (KTA_FLAG_COMPACTION; needs count_alive_keys and implies alive_table: replay the
         records inside compaction_replay(), then compaction());
         size_quantiles: the size-percentile pass (KTA_FLAG_SIZE_QUANTILES: a 464-bin histogram of the key, value and message
-        sizes per partition, size_quantiles())."""
+        sizes per partition, size_quantiles());
+        segments: (segment_bytes, rows_per_partition, record_overhead) — the segment pass of the retention what-if
+        (kta_set_segments: segments(), then retention_whatif on the vector)."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -116,6 +119,13 @@ class HipMetricHandler:
         if timeline is not None:
             try:
                 self.set_timeline(*timeline)
+            except KtaError:
+                self.close()
+                raise
+        self.segments_config = None
+        if segments is not None:
+            try:
+                self.set_segments(*segments)
             except KtaError:
                 self.close()
                 raise
@@ -528,6 +538,44 @@ class HipMetricHandler:
         out = (C.c_uint64 * 6)()
         self._check(self._lib.kta_ts_order_info(self._ctx, C.byref(out)))
         return dict(zip(("launches", "chunks", "instructions", "one_partition", "groups", "chunk_records"), (int(x) for x in out)))
+
+    def set_segments(self, segment_bytes: int, rows_per_partition: int, record_overhead: int = 0) -> None:
+        """kta_set_segments: turn the segment pass of the retention what-if on (before the first record since creation /
+        reset())."""
+        self._check(self._lib.kta_set_segments(self._ctx, int(segment_bytes), int(rows_per_partition), int(record_overhead)))
+        self.segments_config = (int(segment_bytes), int(rows_per_partition), int(record_overhead))
+
+    def _segments(self, fn) -> dict:
+        if self.segments_config is None:
+            raise KtaError(N.KTA_ERR_INVALID, "the handler has no segments (segments=...)")
+        M = self.segments_config[1]
+        out = np.zeros(segments_words(self.n_partitions, M), np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), len(out)))
+        return split_segments(out, self.n_partitions, M)
+
+    def segments(self) -> dict:
+        """The live segment vector (kta_get_segments; staged messages are flushed first) as split_segments gives it: "rows"
+        [P][M][4], "totals" [P][4], "globals" [8] and "vector", the whole u64[(P M + P) 4 + 8]."""
+        return self._segments(self._lib.kta_get_segments)
+
+    def exchange_segments(self) -> dict:
+        """As segments(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return self._segments(self._lib.kta_exchange_segments)
+
+    def segments_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the segment snapshot (for collectives: allreduce_segments_vector)."""
+        return self._device_vector(self._lib.kta_segments_result_vector)
+
+    def segments_info(self) -> dict:
+        """Work counters of the segment pass since creation / reset() (kta_segments_info)."""
+        out = (C.c_uint64 * 6)()
+        self._check(self._lib.kta_segments_info(self._ctx, C.byref(out)))
+        return {"chunks": out[0], "chunk_records": out[1], "launches": out[2], "chunks_applied": out[3], "chunks_skipped": out[4],
+                "groups": out[5]}
+
+    def set_segments_chunk(self, records: int) -> None:
+        """Tests: records per chunk of the segment pass (a multiple of 64; 0: the default)."""
+        self._check(self._lib.kta_set_segments_chunk(self._ctx, int(records)))
 
     def set_ts_order_chunk(self, records: int) -> None:
         """Tests: the records per chunk of the timestamp-order pass, a multiple of 64 (0: the default)."""
@@ -1205,6 +1253,70 @@ def filter_host(partition, ts_ms, n_partitions: int, from_ms: Optional[int] = No
     if rc != N.KTA_OK:
         raise KtaError(rc, "kta_filter_host")
     return idx[:m.value].copy()
+
+
+def segments_words(n_partitions: int, rows_per_partition: int) -> int:
+    """kta_segments_words: (P M + P) 4 + 8"""
+    w = int(N.load().kta_segments_words(int(n_partitions), int(rows_per_partition)))
+    if w == 0:
+        raise KtaError(N.KTA_ERR_INVALID, "kta_segments_words: P >= 1, M >= 2 and P * M <= 2^20")
+    return w
+
+
+def segments_max_partitions() -> int:
+    """The largest n_partitions a handler with segments may have (kta_segments_max_partitions)."""
+    return int(N.load().kta_segments_max_partitions())
+
+
+def _segments_vec(vec, P: int, M: int) -> np.ndarray:
+    v = np.ascontiguousarray(vec).view(np.uint64) if isinstance(vec, np.ndarray) else np.array(vec, dtype=np.uint64)
+    if v.shape != (segments_words(P, M),):
+        raise KtaError(N.KTA_ERR_INVALID, f"a segment vector of {P} partitions and {M} rows has {segments_words(P, M)} words")
+    return v
+
+
+def split_segments(vec, n_partitions: int, rows_per_partition: int) -> dict:
+    """The parts of a segment vector u64[(P M + P) 4 + 8] (views): "rows" [P][M][4] = {C, B, T, H + 1}, "totals" [P][4],
+    "globals" [8] = counted, outside [0, P), rows closed, S, M, overhead, 0, 0."""
+    P, M = int(n_partitions), int(rows_per_partition)
+    v = _segments_vec(vec, P, M)
+    return {"rows": v[:P * M * 4].reshape(P, M, 4), "totals": v[P * M * 4:(P * M + P) * 4].reshape(P, 4),
+            "globals": v[(P * M + P) * 4:], "vector": v}
+
+
+def merge_segments(acc: np.ndarray, other, n_partitions: int, rows_per_partition: int) -> np.ndarray:
+    """kta_merge_segments, in place on `acc` (contiguous uint64): SUM over every word but S, M and overhead, which must
+    agree (KtaError otherwise, acc unchanged)."""
+    a = _segments_vec(acc, n_partitions, rows_per_partition)
+    rc = N.load().kta_merge_segments(_np_ptr(a), _np_ptr(_segments_vec(other, n_partitions, rows_per_partition)), n_partitions,
+                                     rows_per_partition)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_segments: bad bounds, or the vectors' S / M / overhead differ")
+    return acc
+
+
+RETENTION_COLUMNS = ("segments", "records", "bytes", "tombstones", "records_kept", "bytes_kept", "tombstones_kept",
+                     "segments_deleted", "rule", "clamped")
+
+
+def retention_whatif(vec, n_partitions: int, rows_per_partition: int, now_ms: int, retention_ms: int = -1,
+                     retention_bytes: int = -1) -> np.ndarray:
+    """kta_retention_whatif (pure host): u64[P + 1][10], a row per partition and one for the topic, columns
+    RETENTION_COLUMNS; -1 turns a rule off."""
+    P, M = int(n_partitions), int(rows_per_partition)
+    v = _segments_vec(vec, P, M)
+    out = np.zeros((P + 1, len(RETENTION_COLUMNS)), np.uint64)
+    rc = N.load().kta_retention_whatif(_np_ptr(v), P, M, int(now_ms), int(retention_ms), int(retention_bytes), _np_ptr(out), out.size)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_retention_whatif: bad arguments, or not a segment vector of this shape")
+    return out
+
+
+def render_retention(vec, n_partitions: int, rows_per_partition: int, now_ms: int, retention_ms: int = -1, retention_bytes: int = -1) -> str:
+    """kta_render_retention: the section kta-analyzer prints with --librdkafka kta.segments=<size>, from a segment vector."""
+    v = _segments_vec(vec, n_partitions, rows_per_partition)
+    return _render(N.load().kta_render_retention, _np_ptr(v), int(n_partitions), int(rows_per_partition), int(now_ms), int(retention_ms),
+                   int(retention_bytes))
 
 
 def ts_order_max_partitions() -> int:

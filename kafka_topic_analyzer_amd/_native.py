@@ -238,6 +238,18 @@ SIGNATURES = {
     "kta_size_bin_bounds": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kta_size_quantile": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_set_segments": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "kta_segments_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "kta_get_segments": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_segments": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_segments_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_segments_max_partitions": (C.c_int, []),
+    "kta_segments_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_set_segments_chunk": (C.c_int, [_P, C.c_uint64]),
+    "kta_merge_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "kta_retention_whatif": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t]),
+    "kta_render_retention": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
     "kta_murmur2": (C.c_uint32, [C.c_void_p, C.c_size_t]),
     "kta_compaction_replay": (C.c_int, [_P, C.c_int]),
     "kta_get_compaction": (C.c_int, [_P, C.c_void_p, C.c_size_t]),

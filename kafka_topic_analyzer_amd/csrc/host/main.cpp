@@ -38,6 +38,11 @@
 // kta.percentiles=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the size-percentile pass as well
 // (KTA_FLAG_SIZE_QUANTILES; no reference counterpart) and prints, after the report's closing rule and the analytics, p50,
 // p90, p99, p99.9 and the largest of the key, value and message sizes per partition and of the topic.
+// kta.segments=<size> (1g, 512m, 64k or bytes; every source, kta.per_message=1 and kta.gpus=N included) runs the segment pass of
+// the retention what-if as well (kta_set_segments; no reference counterpart) and prints, after the partitioner and compaction
+// sections and before the filter's, every partition's model segments, records and bytes and — with kta.retention.ms=<duration>
+// and / or kta.retention.bytes=<size>, at kta.retention.now=<unix seconds> (default: the run's start) — what the policy would
+// keep.  kta.segments.rows=M (default 1024, lowered so that P * M <= 2^20) and kta.segments.overhead=B (default 0) set the model.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -106,6 +111,32 @@ int64_t parse_decimal(const std::string &v, size_t digits)
         if (ch < '0' || ch > '9') return -1;
     return strtoll(v.c_str(), nullptr, 10);
 }
+
+// a size as kta.segments and kta.retention.bytes take it: bytes, or a number of k / m / g (powers of 1024); -1 when malformed
+int64_t parse_size(const std::string &v)
+{
+    size_t i = 0;
+    while (i < v.size() && v[i] >= '0' && v[i] <= '9') i++;
+    if (i == 0 || i > 15) return -1;
+    const std::string unit = v.substr(i);
+    int shift = 0;
+    if (unit.empty()) shift = 0;
+    else if (unit == "k" || unit == "K") shift = 10;
+    else if (unit == "m" || unit == "M") shift = 20;
+    else if (unit == "g" || unit == "G") shift = 30;
+    else return -1;
+    const int64_t n = strtoll(v.substr(0, i).c_str(), nullptr, 10);
+    if (n > (INT64_MAX >> shift)) return -1;
+    return n << shift;
+}
+
+// kta.segments=<size> with kta.segments.rows / kta.segments.overhead, and the policy kta.retention.ms / .bytes / .now
+struct SegmentsConfig {
+    bool on = false;
+    uint64_t S = 0;
+    uint32_t M = 0, overhead = 0;
+    int64_t retention_ms = -1, retention_bytes = -1, now_ms = 0;
+};
 
 // kta.from / kta.to / kta.partitions as kta_set_filter takes them
 struct FilterConfig {
@@ -323,6 +354,7 @@ struct ShardedJob {
     uint32_t repartition = 0;                          //   kta.repartition=Q (0: P)
     bool percentiles = false;                          // kta.percentiles=1: likewise
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
+    SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
     std::vector<std::vector<uint8_t>> segment_bytes;   // segment:// : file k is partition k
     std::vector<uint64_t> base_seq;                    //   global sequence number of each partition's first record
@@ -343,6 +375,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
         kta_ctx *ctx = h->ctx();
+        if (job.segments.on) h->set_segments(job.segments.S, job.segments.M, job.segments.overhead);
         apply_filter(ctx, job.filter);
         h->comm_create(job.nranks, rank, uid);
         if (job.synthetic) {
@@ -501,6 +534,9 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         }
         if (job.partitioner)
             text += kta::render_partitioner(h0->partitioner()->data(), partitioner_counters(metrics, job.P).data(), job.P, h0->repartition());
+        if (job.segments.on)
+            text += kta::render_retention(h0->segments()->data(), job.P, job.segments.M, job.segments.now_ms, job.segments.retention_ms,
+                                          job.segments.retention_bytes);
         if (job.filter.on)
             text += kta::render_filter(job.filter.from_ms, job.filter.to_ms, job.filter.has_set ? job.filter.bitmap.data() : nullptr, job.P,
                                        (uint64_t)filter_counts[0], (uint64_t)filter_counts[1]);
@@ -743,6 +779,72 @@ int main(int argc, char **argv)
         timeline = kta::TimelineConfig{origin, width, (uint32_t)n};
     }
 
+    SegmentsConfig segments;   // kta.segments=<size> and the policy: refused here, before any context, when they cannot be had
+    for (const char *key : {"kta.retention.ms", "kta.retention.bytes", "kta.retention.now", "kta.segments.rows", "kta.segments.overhead"})
+        if (cfg.count(key) && !cfg.count("kta.segments")) {
+            fprintf(stderr, "%s=%s: needs kta.segments=<size> (the what-if is read off the model's segments)\n", key, cfg[key].c_str());
+            return 2;
+        }
+    if (cfg.count("kta.segments")) {
+        const int64_t size = parse_size(cfg["kta.segments"]);
+        if (size < 1 || size > (1ll << 40)) {
+            fprintf(stderr, "kta.segments=%s: expected a segment size of 1 byte to 1024g, such as 1g, 512m, 64k or a number of bytes\n",
+                    cfg["kta.segments"].c_str());
+            return 2;
+        }
+        if (P > (uint32_t)kta_segments_max_partitions()) {
+            fprintf(stderr, "kta.segments=%s: the topic has %u partitions, the segment pass admits at most %d\n", cfg["kta.segments"].c_str(), P,
+                    kta_segments_max_partitions());
+            return 2;
+        }
+        int64_t rows = std::min<int64_t>(1024, (1ll << 20) / (int64_t)P);
+        if (cfg.count("kta.segments.rows")) {
+            rows = parse_decimal(cfg["kta.segments.rows"], 7);
+            if (rows < 2 || rows * (int64_t)P > (1ll << 20)) {
+                fprintf(stderr, "kta.segments.rows=%s: expected the rows kept per partition, 2 to %lld for %u partitions\n",
+                        cfg["kta.segments.rows"].c_str(), (long long)((1ll << 20) / (int64_t)P), P);
+                return 2;
+            }
+        }
+        int64_t overhead = 0;
+        if (cfg.count("kta.segments.overhead")) {
+            overhead = parse_decimal(cfg["kta.segments.overhead"], 10);
+            if (overhead < 0 || overhead > (int64_t)UINT32_MAX) {
+                fprintf(stderr, "kta.segments.overhead=%s: expected a number of bytes below 2^32\n", cfg["kta.segments.overhead"].c_str());
+                return 2;
+            }
+        }
+        segments.on = true;
+        segments.S = (uint64_t)size, segments.M = (uint32_t)rows, segments.overhead = (uint32_t)overhead;
+        if (cfg.count("kta.retention.ms")) {
+            segments.retention_ms = parse_timeline_width(cfg["kta.retention.ms"]);
+            if (segments.retention_ms == 0) {
+                fprintf(stderr, "kta.retention.ms=%s: expected a duration such as 30s, 15m, 1h or 7d (a bare number is seconds)\n",
+                        cfg["kta.retention.ms"].c_str());
+                return 2;
+            }
+        }
+        if (cfg.count("kta.retention.bytes")) {
+            segments.retention_bytes = parse_size(cfg["kta.retention.bytes"]);
+            if (segments.retention_bytes < 0) {
+                fprintf(stderr, "kta.retention.bytes=%s: expected a size such as 10g, 512m, 64k or a number of bytes\n",
+                        cfg["kta.retention.bytes"].c_str());
+                return 2;
+            }
+        }
+        if (cfg.count("kta.retention.now")) {
+            const int64_t sec = parse_decimal(cfg["kta.retention.now"], 15);
+            if (sec < 0) {
+                fprintf(stderr, "kta.retention.now=%s: expected unix seconds >= 0\n", cfg["kta.retention.now"].c_str());
+                return 2;
+            }
+            segments.now_ms = sec * 1000;
+        } else {   // the run's start time, as the timeline takes it
+            segments.now_ms = (int64_t)std::chrono::duration_cast<std::chrono::milliseconds>(
+                                  std::chrono::system_clock::now().time_since_epoch()).count();
+        }
+    }
+
     FilterConfig filter;   // kta.from / kta.to / kta.partitions: refused here, before any context, when malformed
     for (const char *key : {"kta.from", "kta.to"}) {
         if (!cfg.count(key)) continue;
@@ -844,6 +946,7 @@ int main(int argc, char **argv)
         job.repartition = repartition;
         job.percentiles = percentiles;
         job.filter = filter;
+        job.segments = segments;
         job.batch = batch;
         job.P = P;
         job.spec = spec;
@@ -870,6 +973,12 @@ int main(int argc, char **argv)
         return 2;
     }
     kta_ctx *ctx = handler->ctx();
+    try {
+        if (segments.on) handler->set_segments(segments.S, segments.M, segments.overhead);
+    } catch (const std::exception &e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 2;
+    }
     apply_filter(ctx, filter);
     if (segment) check(kta_kafka_set_check_crcs(ctx, check_crcs ? 1 : 0), ctx, "kta_kafka_set_check_crcs");
 
@@ -1094,6 +1203,9 @@ int main(int argc, char **argv)
             cv[(size_t)P * KTA_NCOUNTERS + KTA_G_BAD_PARTITION] = handler->undelivered_records();
             text += kta::render_compaction(compaction_vec.data(), cv.data(), P);
         }
+        if (segments.on)
+            text += kta::render_retention(handler->segments()->data(), P, segments.M, segments.now_ms, segments.retention_ms,
+                                          segments.retention_bytes);
         if (filter.on)
             text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, filter_info[0],
                                        filter_info[1]);

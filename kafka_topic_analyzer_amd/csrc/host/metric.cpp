@@ -146,6 +146,12 @@ void HipMetricHandler::finish(bool tolerate_undelivered)
     read_analytics();
 }
 
+void HipMetricHandler::set_segments(uint64_t segment_bytes, uint32_t rows_per_partition, uint32_t record_overhead)
+{
+    check(kta_set_segments(ctx_, segment_bytes, rows_per_partition, record_overhead), "kta_set_segments");
+    seg_rows_ = rows_per_partition;
+}
+
 void HipMetricHandler::replay_compaction(bool on) { check(kta_compaction_replay(ctx_, on ? 1 : 0), "kta_compaction_replay"); }
 
 std::vector<uint64_t> HipMetricHandler::compaction()
@@ -201,6 +207,10 @@ void HipMetricHandler::read_analytics()
     if (sizeq_on_) {
         qvec_.assign((size_t)P_ * KTA_SIZE_QUANTITIES * KTA_SIZE_BINS + KTA_SIZE_GLOBALS, 0);
         check(kta_exchange_size_quantiles(ctx_, qvec_.data(), qvec_.size()), "kta_exchange_size_quantiles");
+    }
+    if (seg_rows_) {
+        gvec_.assign(kta_segments_words((uint32_t)P_, seg_rows_), 0);
+        check(kta_exchange_segments(ctx_, gvec_.data(), gvec_.size()), "kta_exchange_segments");
     }
     if (!analytics_on_) return;
     Analytics &a = analytics_;

@@ -149,6 +149,11 @@ public:
     // With KTA_FLAG_SIZE_QUANTILES: the size vector u64[P * 3 * 464 + 8] of the snapshot finish() / exchange() took (after
     // exchange(), the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *size_quantiles() const { return sizeq_on_ ? &qvec_ : nullptr; }
+    // The segment pass of the retention what-if (kta_set_segments): right after construction, before any record; then the
+    // segment vector u64[(P M + P) 4 + 8] of the snapshot finish() / exchange() took (after exchange(), the whole job's);
+    // nullptr without it.
+    void set_segments(uint64_t segment_bytes, uint32_t rows_per_partition, uint32_t record_overhead);
+    const std::vector<uint64_t> *segments() const { return seg_rows_ ? &gvec_ : nullptr; }
     // With KTA_FLAG_COMPACTION: replay mode on / off (kta_compaction_replay) — after finish(), feed the source a second time
     // between replay_compaction(true) and replay_compaction(false) — and then the live compaction vector u64[5 P + 6].
     void replay_compaction(bool on);
@@ -184,6 +189,8 @@ private:
     std::vector<uint64_t> pvec_;
     bool sizeq_on_ = false;
     std::vector<uint64_t> qvec_;
+    uint32_t seg_rows_ = 0;   // M; 0: no segments
+    std::vector<uint64_t> gvec_;
 };
 
 // chrono 0.4.19 `Display for DateTime<Utc>` (main.rs:132-133)
@@ -216,6 +223,9 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
 // the opt-in section kta-analyzer prints with kta.percentiles=1 after the report's closing rule and the analytics
 // (kta_render_size_percentiles): vec u64[P * 3 * 464 + 8]
 std::string render_size_percentiles(const uint64_t *vec, uint32_t P);
+// the opt-in section kta-analyzer prints with kta.segments=<size> after the partitioner and compaction sections and before
+// the filter's (kta_render_retention): vec u64[(P M + P) 4 + 8]; retention -1: the rule is off
+std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes);
 // the opt-in section kta-analyzer prints with -c and kta.compaction=1 after the partitioner section and before the filter
 // section (kta_render_compaction): vec u64[5 P + 6], counters u64[P * 7 + 8] (the first pass's counter vector).  *matched
 // (when given): whether the replay matched the first pass; a section that says it did not otherwise

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "kta_compaction.h"
+#include "kta_segments.h"
 #include "kta_size_bins.h"
 #include "metric.hpp"
 
@@ -307,6 +308,49 @@ std::string render_ts_order(const uint64_t *vec, const std::vector<uint64_t> &re
     return o;
 }
 
+// The opt-in retention section (kta.segments=<size>): no reference counterpart, printed after the partitioner and compaction
+// sections and before the filter's.  vec: u64[(P M + P) 4 + 8] (kta_hip.h); retention -1: the rule is off, and with both
+// off the segment columns alone.
+std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes)
+{
+    std::vector<uint64_t> w((size_t)(P + 1) * kRetWords);
+    if (kta_retention_whatif(vec, P, M, now_ms, retention_ms, retention_bytes, w.data(), w.size()) != KTA_OK) return std::string();
+    const uint64_t *g = vec + segments_globals_at(P, M);
+    const bool policy = retention_ms >= 0 || retention_bytes >= 0;
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    auto rule = [](int64_t v) { return v < 0 ? std::string("-") : std::to_string(v); };
+    std::string o = "Retention what-if: model log segments of " + u(g[kSegGlobalS]) + " bytes per partition (kta.segments), ";
+    if (policy) o += "retention.ms=" + rule(retention_ms) + ", retention.bytes=" + rule(retention_bytes) + ", now=" + std::to_string(now_ms) + " ms";
+    else o += "no retention policy given";
+    o += " (not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    if (policy) rows.push_back({"P", "Segments", "Records", "Bytes", "Records kept", "Bytes kept", "Reclaimed %", "Rule"});
+    else rows.push_back({"P", "Segments", "Records", "Bytes"});
+    for (uint32_t p = 0; p <= P; p++) {
+        const uint64_t *r = w.data() + (size_t)p * kRetWords;
+        const bool all = p == P;
+        std::vector<std::string> row{all ? "All" : std::to_string(p), u(r[kRetSegments]) + (!all && r[kRetClamped] ? "+" : ""), u(r[kRetRecords]),
+                                     u(r[kRetBytes])};
+        if (policy) {
+            char buf[32];
+            snprintf(buf, sizeof buf, "%.2f", r[kRetBytes] ? (double)(r[kRetBytes] - r[kRetBytesKept]) * 100.0 / (double)r[kRetBytes] : 0.0);
+            const char *const names[4] = {"-", "time", "size", "time+size"};
+            row.insert(row.end(), {u(r[kRetRecordsKept]), u(r[kRetBytesKept]), r[kRetBytes] ? buf : "-", names[r[kRetRule] & 3u]});
+        }
+        rows.push_back(row);
+    }
+    o += pretty_table(rows);
+    const uint64_t clamped = w[(size_t)P * kRetWords + kRetClamped];
+    if (clamped)
+        o += u(clamped) + " partition(s) outgrew the " + u(M) + " rows kept per partition (Segments ends in +): the last row holds the rest and "
+             "counts as the active segment (kta.segments.rows).\n";
+    o += "Model: a segment ends with the record whose bytes reach its size, so a boundary can differ from the broker's by one record per "
+         "segment; segment.ms is not modelled; a record's size is key + value + " + u(g[kSegGlobalOverhead]) + " bytes, not bytes on disk (no batch "
+         "headers, no compression); the active segment is never deleted, and a prefix without any timestamp is not deleted by time.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // The opt-in partitioner section (kta.partitioner=murmur2): no reference counterpart, printed last of all.  vec: u64[2 P + 2 Q]
 // (kta_hip.h), counters: the counter vector's per-partition words.
 std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, uint32_t P, uint32_t Q)
@@ -595,6 +639,21 @@ extern "C" int kta_render_ts_order(const uint64_t *vec, const uint64_t *counter_
     std::vector<uint64_t> records(n_partitions);
     for (uint32_t p = 0; p < n_partitions; p++) records[p] = counter_vec[(size_t)p * KTA_NCOUNTERS + KTA_C_TOTAL];
     const std::string text = kta::render_ts_order(vec, records);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_retention(const uint64_t *vec, uint32_t n_partitions, uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms,
+                                    int64_t retention_bytes, char *out, size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len) return KTA_ERR_INVALID;
+    const std::string text = kta::render_retention(vec, n_partitions, rows_per_partition, now_ms, retention_ms, retention_bytes);
+    if (text.empty()) return KTA_ERR_INVALID;   // (kta_retention_whatif refused the arguments)
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

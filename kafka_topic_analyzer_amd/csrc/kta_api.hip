@@ -8,6 +8,7 @@
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
+#include "kta_segments.h"
 #include "kta_size_bins.h"
 
 #include <limits.h>
@@ -90,6 +91,16 @@ struct kta_ctx {
     DeviceBuf<int64_t> d_tso_hi, d_tso_ws;
     uint64_t tso_launches = 0, tso_chunks = 0, tso_last_chunk = 0;
     uint64_t tso_chunk = 0;          // kta_set_ts_order_chunk (tests); 0: by the slice's length
+    // segments (kta_set_segments): d_seg u64[(P M + P) 4 + 8] the live vector, whose totals are the running state that carries
+    // over from batch to batch, d_seg_ws / d_seg_flags the workspace of a launch triple (allocated once), d_seg_stats the
+    // apply kernel's work counters (kta_segments_info)
+    bool seg = false;
+    uint64_t seg_S = 0;
+    uint32_t seg_M = 0, seg_overhead = 0;
+    DeviceBuf<uint64_t> d_seg, d_seg_out, d_seg_ws, d_seg_stats;   // (d_seg_out: the snapshot)
+    DeviceBuf<uint32_t> d_seg_flags;
+    uint64_t seg_launches = 0, seg_chunks = 0, seg_last_chunk = 0;
+    uint64_t seg_chunk = 0;          // kta_set_segments_chunk (tests); 0: by the slice's length
     // partitioner (KTA_FLAG_PARTITIONER): d_part u64[2 P + 2 Q] the live vector, d_part_out its snapshot, d_part_stats the
     // kernel's work counters (kta_partitioner_info); part_q the what-if partition count (kta_set_repartition; P at first)
     bool part = false;
@@ -444,6 +455,44 @@ int run_ts_order(kta_ctx *ctx, const kta_internal_columns &rb, uint64_t n)
     return KTA_OK;
 }
 
+// The segment pass over a batch whose metric columns were resolved to rb, as run_ts_order: chunk sums, prefix, apply per
+// slice, in order.  A slice is as many chunks as the workspace has rows for P partitions.
+int run_segments(kta_ctx *ctx, const kta_internal_columns &rb, uint64_t n)
+{
+    const kta::SegmentsState st{ctx->d_seg.get(), ctx->d_seg_ws.get(), ctx->d_seg_flags.get(), ctx->d_seg_stats.get(), ctx->seg_S, ctx->seg_M,
+                                ctx->seg_overhead};
+    const uint64_t max_rows = kta::kSegmentsWorkspaceWords / ((uint64_t)ctx->P * kta::kSegWords);
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t left = n - at;
+        uint64_t chunk = ctx->seg_chunk;
+        if (chunk == 0) {
+            chunk = ((left + kta::kSegmentsChunks - 1) / kta::kSegmentsChunks + 255) / 256 * 256;
+            if (chunk < kta::kSegmentsChunkMin) chunk = kta::kSegmentsChunkMin;
+        }
+        const uint64_t take = left / chunk >= max_rows ? max_rows * chunk : left;
+        KTA_HIP(ctx, kta::launch_segments(scan_columns(rb, at), take, chunk, ctx->P, st, ctx->s_compute));
+        ctx->seg_launches++;
+        ctx->seg_chunks += (take + chunk - 1) / chunk;
+        ctx->seg_last_chunk = chunk;
+        at += take;
+    }
+    return KTA_OK;
+}
+
+// The live segment vector as kta_set_segments and kta_reset leave it: zero but for the configuration globals.
+int clear_segments(kta_ctx *ctx)
+{
+    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
+    const uint64_t cfg[3] = {ctx->seg_S, ctx->seg_M, ctx->seg_overhead};
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_seg.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_seg.get() + kta::segments_globals_at(ctx->P, ctx->seg_M) + kta::kSegGlobalS, cfg, sizeof cfg,
+                                hipMemcpyHostToDevice, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (cfg is this frame's)
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_seg_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
+    ctx->seg_launches = ctx->seg_chunks = ctx->seg_last_chunk = 0;
+    return KTA_OK;
+}
+
 // The workspace of the partitioned alive pass, large enough for plan pl: the pairs, their counts and the pool grow
 // together (all three released, after the compute stream has drained, before any is allocated again); the pool's control
 // words and the fail lists are allocated once.
@@ -653,6 +702,10 @@ int run_handlers(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq
         int rc = run_ts_order(ctx, rb, n);
         if (rc != KTA_OK) return rc;
     }
+    if ((which & 1) && ctx->seg) {      // likewise; partition, ts_ms and the lengths in the tiles' own forms, no keys
+        int rc = run_segments(ctx, rb, n);
+        if (rc != KTA_OK) return rc;
+    }
     if ((which & 1) && ctx->hot) {      // a pass of its own, likewise
         int rc = run_hot_keys(ctx, c, rb, n);
         if (rc != KTA_OK) return rc;
@@ -784,6 +837,10 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->tso_launches = ctx->tso_chunks = ctx->tso_last_chunk = 0;
     }
+    if (ctx->seg) {                     // (the configuration stays)
+        int rc = clear_segments(ctx);
+        if (rc != KTA_OK) return rc;
+    }
     if (ctx->part) {                    // (Q stays)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part.get(), 0, kta::partitioner_len(ctx->P, ctx->part_q) * sizeof(uint64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
@@ -873,6 +930,9 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
     rv[KTA_RV_PARTITIONER] = ResultVector{ctx->part ? ctx->d_part_out.get() : nullptr, plen, plen, false};
     const size_t qlen = ctx->sizeq ? kta::size_quantiles_len(ctx->P) : 0;
     rv[KTA_RV_SIZE_QUANTILES] = ResultVector{ctx->sizeq ? ctx->d_sizeq_out.get() : nullptr, qlen, qlen, false};
+    // (the MAX suffix is S, M, overhead and the two zero words: equal on every rank, so the maximum is each rank's own)
+    const size_t slen = ctx->seg ? kta::segments_len(ctx->P, ctx->seg_M) : 0;
+    rv[KTA_RV_SEGMENTS] = ResultVector{ctx->seg ? ctx->d_seg_out.get() : nullptr, slen, ctx->seg ? slen - kta::kSegGlobals + kta::kSegGlobalS : 0, false};
 }
 
 static ResultVector result_vector(kta_ctx *ctx, int kind)
@@ -1474,7 +1534,7 @@ int kta_finish_device(kta_ctx *ctx)
     kta_internal_result_vectors(ctx, rv);
     // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
     const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get(),
-                                                 ctx->d_part.get(), ctx->d_sizeq.get()};
+                                                 ctx->d_part.get(), ctx->d_sizeq.get(), ctx->d_seg.get()};
     for (int k = 0; k < KTA_RV_KINDS; k++)
         if (rv[k].out && live[k])
             KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -1942,6 +2002,116 @@ int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records)
     if (records % 64 != 0 || records > (1ull << 32))
         return fail(ctx, KTA_ERR_INVALID, "a chunk is a multiple of 64 records, at most 2^32 (0: the default)");
     ctx->tso_chunk = records;
+    return KTA_OK;
+}
+
+static const char *const kNoSeg = "the context has no segments (kta_set_segments)";
+static_assert(kta::kRetWords == KTA_RETENTION_WORDS, "the what-if's row is said twice: kta_segments.h and kta_hip.h");
+
+int kta_segments_max_partitions(void) { return (int)kta::kSegmentsMaxPartitions; }
+
+uint32_t kta_segments_words(uint32_t P, uint32_t M) { return kta::segments_config_ok(1, M, P) ? (uint32_t)kta::segments_len(P, M) : 0u; }
+
+int kta_set_segments(kta_ctx *ctx, uint64_t segment_bytes, uint32_t rows_per_partition, uint32_t record_overhead)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (segment_bytes < 1 || segment_bytes > kta::kSegmentsMaxBytes)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_segments: segment_bytes must be in [1, 2^40]");
+    if (rows_per_partition < 2 || (uint64_t)rows_per_partition * ctx->P > kta::kSegmentsMaxRows)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_segments: rows_per_partition must be at least 2 and P * rows_per_partition at most 2^20");
+    if (ctx->P > kta::kSegmentsMaxPartitions)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_segments admits at most " + std::to_string(kta::kSegmentsMaxPartitions) + " partitions");
+    if (ctx->handed_records || ctx->fill_n)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_segments: the context has been handed records since kta_create / kta_reset");
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t words = kta::segments_len(ctx->P, rows_per_partition);
+    if (!ctx->seg || ctx->seg_M != rows_per_partition) {
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+        ctx->d_seg.reset();
+        ctx->d_seg_out.reset();
+        ctx->seg = false;
+        KTA_HIP(ctx, ctx->d_seg.alloc(words));
+        KTA_HIP(ctx, ctx->d_seg_out.alloc(words));
+    }
+    if (!ctx->d_seg_ws) {
+        KTA_HIP(ctx, ctx->d_seg_ws.alloc(kta::kSegmentsWorkspaceWords));
+        KTA_HIP(ctx, ctx->d_seg_flags.alloc(kta::kSegmentsWorkspaceWords / kta::kSegWords));
+        KTA_HIP(ctx, ctx->d_seg_stats.alloc(4));
+    }
+    ctx->seg_S = segment_bytes, ctx->seg_M = rows_per_partition, ctx->seg_overhead = record_overhead;
+    int rc = clear_segments(ctx);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_seg_out.get(), ctx->d_seg.get(), words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
+    ctx->seg = true;
+    return KTA_OK;
+}
+
+int kta_get_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    int rc = check_words(ctx, "segment vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_seg.get(), out, n_u64);
+}
+
+int kta_exchange_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    int rc = check_words(ctx, "segment vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return read_words(ctx, ctx->d_seg_out.get(), out, n_u64);
+}
+
+int kta_segments_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    return hand_out(result_vector(ctx, KTA_RV_SEGMENTS), device_ptr, n_u64);
+}
+
+int kta_segments_info(kta_ctx *ctx, uint64_t out[6])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    uint64_t st[4];
+    rc = read_words(ctx, ctx->d_seg_stats.get(), st, 4);
+    out[0] = ctx->seg_chunks, out[1] = ctx->seg_last_chunk, out[2] = ctx->seg_launches, out[3] = st[0], out[4] = st[1], out[5] = st[3];
+    return rc;
+}
+
+int kta_set_segments_chunk(kta_ctx *ctx, uint64_t records)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    if (records % 64 != 0 || records > (1ull << 31))
+        return fail(ctx, KTA_ERR_INVALID, "a chunk is a multiple of 64 records, at most 2^31 (0: the default)");
+    ctx->seg_chunk = records;
+    return KTA_OK;
+}
+
+int kta_merge_segments(uint64_t *acc, const uint64_t *other, uint32_t P, uint32_t M)
+{
+    if (!acc || !other || !kta::segments_config_ok(1, M, P)) return KTA_ERR_INVALID;
+    return kta::segments_merge(acc, other, P, M) ? KTA_OK : KTA_ERR_INVALID;
+}
+
+int kta_retention_whatif(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes, uint64_t *out,
+                         size_t n_u64)
+{
+    if (!vec || !out || !kta::segments_config_ok(1, M, P) || n_u64 != ((size_t)P + 1) * KTA_RETENTION_WORDS) return KTA_ERR_INVALID;
+    if (retention_ms < -1 || retention_bytes < -1) return KTA_ERR_INVALID;
+    const uint64_t *g = vec + kta::segments_globals_at(P, M);
+    if (g[kta::kSegGlobalM] != M || !kta::segments_config_ok(g[kta::kSegGlobalS], M, P)) return KTA_ERR_INVALID;   // not a vector of this shape
+    kta::retention_whatif(vec, P, M, now_ms, retention_ms, retention_bytes, out);
     return KTA_OK;
 }
 

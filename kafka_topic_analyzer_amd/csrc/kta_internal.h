@@ -72,13 +72,14 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns 
 //   ts order    3*P + 64           2*P + 64       P      (i64)
 //   partitioner 2*P + 2*Q          all            none
 //   size quant. P*3*464 + 8        all            none
+//   segments    (P*M + P)*4 + 8    all but 5      5      (u64: S, M, overhead and two zero words, equal on every rank)
 struct ResultVector {
     uint64_t *out;     // the snapshot (device); null: the context has no such section
     size_t words, sum_words;
     bool max_signed;
 };
 enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_PARTITIONER,
-       KTA_RV_SIZE_QUANTILES, KTA_RV_KINDS };
+       KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_KINDS };
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);
 
 // ---- errors -------------------------------------------------------------------------------------------------------

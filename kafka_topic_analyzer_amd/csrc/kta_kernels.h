@@ -283,6 +283,25 @@ struct TsOrderState {
 // chunk maxima, prefix, apply.
 hipError_t launch_ts_order(const ScanColumns &c, uint64_t n, uint64_t chunk, uint32_t P, const TsOrderState &st, hipStream_t s);
 
+// Segments (kta_set_segments, kta_segments.hip; the rule and the vector's layout are kta_segments.h's): the live vector
+// u64[(P M + P) 4 + 8], whose totals [P][4] are the running state that carries over from batch to batch, the workspace
+// u64[chunks][P][4] of one launch triple and a flag word per chunk.
+constexpr uint32_t kSegmentsMaxPartitions = 2048;           // the apply kernel's LDS plan: 41 B per partition and wave, one wave up there
+constexpr size_t kSegmentsWorkspaceWords = (size_t)1 << 23; // 64 MiB: chunks per launch triple = this / (4 P)
+constexpr uint64_t kSegmentsChunkMin = 1024;                // default chunk: the slice over kSegmentsChunks, at least this
+constexpr uint64_t kSegmentsChunks = 8192;
+struct SegmentsState {
+    uint64_t *vec;              // u64[segments_len(P, M)]
+    uint64_t *ws;               // u64[kSegmentsWorkspaceWords]
+    uint32_t *flags;            // u32[kSegmentsWorkspaceWords / 4]
+    uint64_t *stats;            // u64[4] += chunks applied, chunks skipped, instructions of one partition, colliding groups
+    uint64_t S;
+    uint32_t M, overhead;
+};
+// Records [0, n) of c in chunks of `chunk` records (a multiple of 64, at most 2^31; ceil(n / chunk) * 4 P <=
+// kSegmentsWorkspaceWords): chunk sums, prefix, apply.
+hipError_t launch_segments(const ScanColumns &c, uint64_t n, uint64_t chunk, uint32_t P, const SegmentsState &st, hipStream_t s);
+
 // Partitioner (KTA_FLAG_PARTITIONER, kta_partitioner.hip): the live vector u64[2 P + 2 Q] = [P][2] checked, placed |
 // [Q][2] target_records, target_bytes, every word a sum that the workgroups of launch_partitioner add their LDS counters to.
 constexpr uint32_t kPartitionerMaxPartitions = 4096;        // P and Q each: 8 P + 12 Q bytes of LDS, 80 KiB up there

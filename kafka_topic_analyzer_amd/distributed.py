@@ -114,6 +114,17 @@ def allreduce_size_quantiles_vector(qvec, n_partitions: int, group=None) -> None
     _allreduce_sum_max(qvec, qvec.numel(), group)
 
 
+def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
+    """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
+    tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM
+    over every word but the last five (i64 wrap == u64 wrap) and all-reduce MAX over those — S, M, overhead and two zero
+    words, which every rank must have alike.  Exact when every partition's records went through ONE rank in order
+    (partition p on rank p % N)."""
+    words = (n_partitions * rows_per_partition + n_partitions) * 4 + 8
+    assert gvec.numel() == words
+    _allreduce_sum_max(gvec, words - 5, group)
+
+
 def allreduce_key_sketch_vector(svec, group=None) -> None:
     """In-place exchange of an int64 view of the key sketch SNAPSHOT (kta_key_sketch_result_vector: device tensor, or a
     CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_KEY_SKETCH: all-reduce
