@@ -968,6 +968,52 @@ int kta_compaction_max_partitions(void);
  * out[4] dynamic LDS bytes of a workgroup for this P, out[5] reserved, 0. */
 int kta_compaction_info(kta_ctx *ctx, uint64_t out[6]);
 
+/* Compact,delete what-if (opt-in; joins the compaction replay with the segments of kta_set_segments): what a topic with
+ * cleanup.policy=compact,delete would keep.  During a replay (kta_compaction_replay) every record whose partition lies in
+ * [0, P) advances its partition's kept state {L, B, T, K}: with z the record's model size (as kta_set_segments defines it),
+ * B += z for every record — its position, the sum the first pass's segment state holds —, L += 1 and K += z for a live
+ * survivor, T += 1 and K += z for a tombstone that survives; unkeyed, superseded and unknown records add to B only.  A
+ * record that closes row s (the rule of kta_set_segments) stores the kept state as it is after that record in kept row
+ * [p][s].  The kept vector has the segment vector's shape u64[kta_segments_words(P, M)]: rows, totals — the running state,
+ * which carries from batch to batch within a replay —, then the globals: records taking part, records outside [0, P), rows
+ * closed, S, M, overhead, 0, 0.  With the first pass's segment vector and the replay's compaction vector it satisfies:
+ * globals 0-5 equal the segment vector's; totals.B and every closed row's B equal the segment vector's, and the same rows
+ * are closed; totals.L / totals.T are the compaction vector's live / tombstone records; totals.K = overhead * (L + T) + live
+ * key bytes + live value bytes + tombstone key bytes; L, T and K do not decrease down a partition's closed rows.
+ *
+ * kta_set_compact_delete: on (non-zero) or off (0).  KTA_ERR_INVALID for a context without KTA_FLAG_COMPACTION, without
+ * kta_set_segments, one that has been handed a record since kta_create / kta_reset, or with more than
+ * kta_compact_delete_max_partitions() partitions (the smaller of the two passes' bounds).  kta_set_segments turns it off:
+ * call it after.  kta_comm_create with nranks > 1 refuses such a context, as it refuses every KTA_FLAG_COMPACTION one.
+ * With the switch off a replay writes what it wrote before and nothing else.  kta_reset and kta_compaction_replay(ctx, 1)
+ * zero the kept vector but for its configuration words. */
+int kta_set_compact_delete(kta_ctx *ctx, int on);
+int kta_compact_delete_max_partitions(void);
+/* The live kept vector, copied to out[n_u64] (n_u64 = kta_segments_words(P, M); staged messages are flushed first). */
+int kta_get_compact_delete(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Work counters of the kept-row kernels since kta_set_compact_delete / kta_reset / the replay's start (profiling; waits for
+ * the compute stream): out[0] launches, out[1] chunks, out[2] chunks the apply kernel went through (the others closed no
+ * row), out[3] bytes of the class column (a byte per record of the largest replay slice, at most 128 MiB). */
+int kta_compact_delete_info(kta_ctx *ctx, uint64_t out[4]);
+/* The what-if (pure host; needs no device) from the first pass's segment vector, the replay's kept vector and the replay's
+ * compaction vector u64[5 P + 6].  Per partition the closed rows are walked oldest first, as kta_retention_whatif walks
+ * them; `last` is the last closed row, `klast` its kept row (zeros without one); the active segment A = totals - last of
+ * the segment vector is never cleaned and never deleted; the compacted log is klast plus A.  Row k is deleted by the time
+ * rule as in kta_retention_whatif (H is the first pass's running maximum over all records: a cleaned segment's own largest
+ * timestamp can only be older, so the model keeps at least what the broker keeps), by the size rule when retention_bytes
+ * >= 0 and (klast.K + A.B) - kept[k].K >= retention_bytes (compacted sizes).  Both take a prefix; `cut` is the last row
+ * deleted.  out[(P + 1)][KTA_COMPACT_DELETE_WORDS], a row per partition and one for the topic (sums; its rule word is the
+ * OR of the partitions', its clamped word their count):
+ *   [0] records, [1] bytes now; [2] records, [3] bytes after compaction alone: klast.L + klast.T + A.C, klast.K + A.B;
+ *   [4] records, [5] bytes under compact,delete: [2] - (kcut.L + kcut.T), [3] - kcut.K; [6] tombstones among [4]:
+ *   klast.T - kcut.T + A.T; [7] segments deleted; [8] rule and [9] clamped as kta_retention_whatif's [8] and [9].
+ * KTA_ERR_INVALID for bad arguments, and when an identity above fails or the compaction vector's unknown != 0: the replay
+ * did not match the first pass. */
+#define KTA_COMPACT_DELETE_WORDS 10
+int kta_compact_delete_whatif(const uint64_t *seg_vec, const uint64_t *kept_vec, const uint64_t *comp_vec, uint32_t n_partitions,
+                              uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes, uint64_t *out,
+                              size_t n_u64);
+
 /* ---- alive-key table access (tests, multi-GPU merge) ------------------------------ */
 /* Export the alive set as a 2^32-bit little-endian bitmap (bit h%32 of u32 word h/32;
  * 512 MiB) into host memory — the same layout as BitSet's storage (metric.rs:263). */
@@ -1136,6 +1182,23 @@ int kta_render_compaction(const uint64_t *vec, const uint64_t *counter_vec, uint
  * KTA_ERR_INVALID for what kta_retention_whatif refuses.  Output buffer conventions as kta_render_report. */
 int kta_render_retention(const uint64_t *vec, uint32_t n_partitions, uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms,
                          int64_t retention_bytes, char *out, size_t out_cap, size_t *out_len);
+/* The section kta-analyzer prints with -c --librdkafka kta.compaction=1,kta.segments=<size>,kta.compact_delete=1 (and the
+ * kta.retention.* keys) after the retention section and before the filter's, from the three vectors of
+ * kta_compact_delete_whatif; not part of the reference report:
+ *   `Compact,delete what-if: cleanup.policy=compact,delete over model log segments of <S> bytes per partition
+ *    (kta.compact_delete), retention.ms=<ms>, retention.bytes=<bytes>, now=<ms> ms; the active segment is not cleaned (not
+ *    part of the reference report)` — `-` for a rule that is off, for now as well when the time rule is off;
+ *   a table (P | Records | Bytes | Compacted records | Compacted bytes | Kept records | Kept bytes | Tombstones kept |
+ *    Reclaimed % | Rule), one row per partition and an `All` row — P ends in `+` for a partition that outgrew its M rows,
+ *    Reclaimed % = 1 - kept bytes / bytes with two decimals (`-` without bytes), Rule is `time`, `size` or `-` (`time+size`
+ *    in the All row when partitions differ);
+ *   the model-limits note; a closing `=` rule.
+ * When kta_compact_delete_whatif reports a mismatch the section is the first line, `The replay did not match the first
+ * pass. Nothing is reported.` and the rule, and the call returns KTA_ERR_INVALID (the text is still written); for other
+ * bad arguments KTA_ERR_INVALID and nothing is written.  Output buffer conventions as kta_render_report. */
+int kta_render_compact_delete(const uint64_t *seg_vec, const uint64_t *kept_vec, const uint64_t *comp_vec, uint32_t n_partitions,
+                              uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes, char *out,
+                              size_t out_cap, size_t *out_len);
 /* The section kta-analyzer prints after everything else when a filter was given (--librdkafka kta.from=<epoch seconds>,
  * kta.to=<epoch seconds>, kta.partitions=0,3-5); not part of the reference report:
  *   `Record filter: everything above describes the records that passed, and no others (kta.from, kta.to, kta.partitions;

@@ -32,7 +32,9 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "partitioner_max_partitions", "split_partitioner", "murmur2", "render_compaction", "split_compaction",
            "compaction_max_partitions", "split_size_quantiles", "merge_size_quantiles", "render_size_percentiles", "size_bin",
            "size_bin_bounds", "size_quantile", "size_quantiles_max_partitions", "segments_words", "segments_max_partitions",
-           "split_segments", "merge_segments", "retention_whatif", "RETENTION_COLUMNS", "render_retention"]
+           "split_segments", "merge_segments", "retention_whatif", "RETENTION_COLUMNS", "render_retention",
+           "compact_delete_max_partitions", "split_compact_delete", "compact_delete_whatif", "COMPACT_DELETE_COLUMNS",
+           "render_compact_delete"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -81,7 +83,8 @@ class HipMetricHandler:
                  now: Optional[Tuple[int, int]] = None, analytics: bool = False, alive_table: bool = False,
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
-                 compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None):
+                 compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
+                 compact_delete: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -96,7 +99,9 @@ class HipMetricHandler:
         size_quantiles: the size-percentile pass (KTA_FLAG_SIZE_QUANTILES: a 464-bin histogram of the key, value and message
         sizes per partition, size_quantiles());
         segments: (segment_bytes, rows_per_partition, record_overhead) — the segment pass of the retention what-if
-        (kta_set_segments: segments(), then retention_whatif on the vector)."""
+        (kta_set_segments: segments(), then retention_whatif on the vector);
+        compact_delete: the compact,delete what-if (kta_set_compact_delete; needs compaction=True and segments: the replay
+        also writes the kept vector, compact_delete(), for compact_delete_whatif)."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -126,6 +131,13 @@ class HipMetricHandler:
         if segments is not None:
             try:
                 self.set_segments(*segments)
+            except KtaError:
+                self.close()
+                raise
+        self.compact_delete_on = False
+        if compact_delete:
+            try:
+                self.set_compact_delete(True)
             except KtaError:
                 self.close()
                 raise
@@ -544,6 +556,28 @@ class HipMetricHandler:
         reset())."""
         self._check(self._lib.kta_set_segments(self._ctx, int(segment_bytes), int(rows_per_partition), int(record_overhead)))
         self.segments_config = (int(segment_bytes), int(rows_per_partition), int(record_overhead))
+        self.compact_delete_on = False   # (another configuration: kta_set_segments turns the compact,delete what-if off)
+
+    def set_compact_delete(self, on: bool = True) -> None:
+        """kta_set_compact_delete: the compact,delete what-if on or off (after set_segments, before the first record since
+        creation / reset(); needs compaction=True)."""
+        self._check(self._lib.kta_set_compact_delete(self._ctx, 1 if on else 0))
+        self.compact_delete_on = bool(on)
+
+    def compact_delete(self) -> dict:
+        """The live kept vector (kta_get_compact_delete; staged messages are flushed first) as split_compact_delete gives it."""
+        if self.segments_config is None:
+            raise KtaError(N.KTA_ERR_INVALID, "the handler has no segments (segments=...)")
+        M = self.segments_config[1]
+        out = np.zeros(segments_words(self.n_partitions, M), np.uint64)
+        self._check(self._lib.kta_get_compact_delete(self._ctx, _np_ptr(out), out.size))
+        return split_compact_delete(out, self.n_partitions, M)
+
+    def compact_delete_info(self) -> dict:
+        """Work counters of the kept-row kernels since the replay began (kta_compact_delete_info)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self._lib.kta_compact_delete_info(self._ctx, C.byref(out)))
+        return {"launches": int(out[0]), "chunks": int(out[1]), "chunks_applied": int(out[2]), "scratch_bytes": int(out[3])}
 
     def _segments(self, fn) -> dict:
         if self.segments_config is None:
@@ -1317,6 +1351,55 @@ def render_retention(vec, n_partitions: int, rows_per_partition: int, now_ms: in
     v = _segments_vec(vec, n_partitions, rows_per_partition)
     return _render(N.load().kta_render_retention, _np_ptr(v), int(n_partitions), int(rows_per_partition), int(now_ms), int(retention_ms),
                    int(retention_bytes))
+
+
+def compact_delete_max_partitions() -> int:
+    """The largest n_partitions a handler with the compact,delete what-if may have (kta_compact_delete_max_partitions)."""
+    return int(N.load().kta_compact_delete_max_partitions())
+
+
+def split_compact_delete(vec, n_partitions: int, rows_per_partition: int) -> dict:
+    """The parts of a kept vector u64[(P M + P) 4 + 8] (views): "rows" [P][M][4] = {L, B, T, K}, "totals" [P][4], "globals"
+    [8] = counted, outside [0, P), rows closed, S, M, overhead, 0, 0."""
+    return split_segments(vec, n_partitions, rows_per_partition)
+
+
+COMPACT_DELETE_COLUMNS = ("records", "bytes", "compacted_records", "compacted_bytes", "kept_records", "kept_bytes", "kept_tombstones",
+                          "segments_deleted", "rule", "clamped")
+
+
+def compact_delete_whatif(seg_vec, kept_vec, comp_vec, n_partitions: int, rows_per_partition: int, now_ms: int, retention_ms: int = -1,
+                          retention_bytes: int = -1) -> np.ndarray:
+    """kta_compact_delete_whatif (pure host) from the first pass's segment vector, the replay's kept vector and the replay's
+    compaction vector: u64[P + 1][10], a row per partition and one for the topic, columns COMPACT_DELETE_COLUMNS; -1 turns
+    a rule off.  KtaError (KTA_ERR_INVALID) for bad arguments and when the replay did not match the first pass."""
+    P, M = int(n_partitions), int(rows_per_partition)
+    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _compaction_vec(comp_vec, P)
+    out = np.zeros((P + 1, len(COMPACT_DELETE_COLUMNS)), np.uint64)
+    rc = N.load().kta_compact_delete_whatif(_np_ptr(s), _np_ptr(k), _np_ptr(c), P, M, int(now_ms), int(retention_ms), int(retention_bytes),
+                                            _np_ptr(out), out.size)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_compact_delete_whatif: bad arguments, or the replay did not match the first pass")
+    return out
+
+
+def render_compact_delete(seg_vec, kept_vec, comp_vec, n_partitions: int, rows_per_partition: int, now_ms: int, retention_ms: int = -1,
+                          retention_bytes: int = -1) -> str:
+    """kta_render_compact_delete: the section kta-analyzer prints with kta.compact_delete=1.  KtaError (KTA_ERR_INVALID) when
+    the replay did not match the first pass; the section that says so is the error's `text` ("" for other bad arguments)."""
+    P, M = int(n_partitions), int(rows_per_partition)
+    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _compaction_vec(comp_vec, P)
+    fn = N.load().kta_render_compact_delete
+    args = (_np_ptr(s), _np_ptr(k), _np_ptr(c), P, M, int(now_ms), int(retention_ms), int(retention_bytes))
+    n = C.c_size_t()
+    fn(*args, None, 0, C.byref(n))
+    buf = C.create_string_buffer(n.value + 1)
+    rc = fn(*args, buf, len(buf), C.byref(n))
+    if rc != N.KTA_OK:
+        err = KtaError(rc, "kta_render_compact_delete: bad arguments, or the replay did not match the first pass")
+        err.text = buf.value.decode()
+        raise err
+    return buf.value.decode()
 
 
 def ts_order_max_partitions() -> int:

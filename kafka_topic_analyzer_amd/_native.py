@@ -255,6 +255,14 @@ SIGNATURES = {
     "kta_get_compaction": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
     "kta_compaction_max_partitions": (C.c_int, []),
     "kta_compaction_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),
+    "kta_set_compact_delete": (C.c_int, [_P, C.c_int]),
+    "kta_compact_delete_max_partitions": (C.c_int, []),
+    "kta_get_compact_delete": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_compact_delete_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4)]),
+    "kta_compact_delete_whatif": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_size_t]),
+    "kta_render_compact_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_render_compaction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_set_filter": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32]),
     "kta_filter_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 6)]),

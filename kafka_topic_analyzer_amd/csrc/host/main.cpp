@@ -57,6 +57,9 @@
 // records and no others, and one more section after everything else says what the filter was and how many records it
 // was shown and let pass (summed over the ranks).  The items of kta.partitions are separated by commas, which also separate
 // --librdkafka's pairs: a piece without '=' that follows kta.partitions and is a number or a range belongs to it.
+// kta.compact_delete=1 (0: off; with kta.compaction=1 and kta.segments=<size>; it inherits the compaction knob's refusals) joins
+// the two what-ifs: the replay also counts the survivors per model segment (kta_set_compact_delete), and a section after the
+// retention section says what cleanup.policy=compact,delete would keep under the kta.retention.* policy.
 // kta.compaction=1 (0: off; with -c; synthetic://, segment:// and dump:// sources, one GPU, not with kta.per_message=1) answers
 // what log compaction would keep (KTA_FLAG_COMPACTION; no reference counterpart): after the first pass the source is fed a
 // second time in replay mode, and a section with the records and bytes kept per partition is printed after the
@@ -602,6 +605,24 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    // kta.compact_delete: the join of the two what-ifs needs both of them (and so inherits the compaction knob's refusals above)
+    bool compact_delete = false;
+    if (cfg.count("kta.compact_delete")) {
+        const std::string &v = cfg["kta.compact_delete"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.compact_delete=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        compact_delete = v == "1";
+        if (compact_delete && !compaction) {
+            fprintf(stderr, "kta.compact_delete=1: needs kta.compaction=1 (the survivors come from the compaction replay)\n");
+            return 2;
+        }
+        if (compact_delete && !cfg.count("kta.segments")) {
+            fprintf(stderr, "kta.compact_delete=1: needs kta.segments=<size> (the survivors are counted per model segment)\n");
+            return 2;
+        }
+    }
     kta::TopicAnalyzer *topic_analyzer = nullptr;
     std::map<int32_t, int64_t> kafka_start, kafka_end;
     if (kafka) {
@@ -975,6 +996,7 @@ int main(int argc, char **argv)
     kta_ctx *ctx = handler->ctx();
     try {
         if (segments.on) handler->set_segments(segments.S, segments.M, segments.overhead);
+        if (compact_delete) handler->set_compact_delete(true);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
         return 2;
@@ -1148,7 +1170,7 @@ int main(int argc, char **argv)
     // errors, the undelivered records; the filter's counts are read here) before the replay starts
     uint64_t filter_info[6] = {0, 0, 0, 0, 0, 0};
     if (filter.on) check(kta_filter_info(ctx, filter_info), ctx, "kta_filter_info");
-    std::vector<uint64_t> compaction_vec;
+    std::vector<uint64_t> compaction_vec, kept_vec;
     if (compaction) {
         try {
             handler->replay_compaction(true);
@@ -1156,6 +1178,7 @@ int main(int argc, char **argv)
             if (rc) return rc;
             handler->replay_compaction(false);
             compaction_vec = handler->compaction();
+            if (compact_delete) kept_vec = handler->compact_delete();
         } catch (const std::exception &e) {
             fprintf(stderr, "%s\n", e.what());
             return 2;
@@ -1206,6 +1229,9 @@ int main(int argc, char **argv)
         if (segments.on)
             text += kta::render_retention(handler->segments()->data(), P, segments.M, segments.now_ms, segments.retention_ms,
                                           segments.retention_bytes);
+        if (compact_delete)
+            text += kta::render_compact_delete(handler->segments()->data(), kept_vec.data(), compaction_vec.data(), P, segments.M, segments.now_ms,
+                                               segments.retention_ms, segments.retention_bytes);
         if (filter.on)
             text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, filter_info[0],
                                        filter_info[1]);

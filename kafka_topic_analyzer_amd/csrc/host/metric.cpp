@@ -161,6 +161,15 @@ std::vector<uint64_t> HipMetricHandler::compaction()
     return v;
 }
 
+void HipMetricHandler::set_compact_delete(bool on) { check(kta_set_compact_delete(ctx_, on ? 1 : 0), "kta_set_compact_delete"); }
+
+std::vector<uint64_t> HipMetricHandler::compact_delete()
+{
+    std::vector<uint64_t> v(kta_segments_words(P_, seg_rows_), 0);
+    check(kta_get_compact_delete(ctx_, v.data(), v.size()), "kta_get_compact_delete");
+    return v;
+}
+
 void HipMetricHandler::comm_create(int nranks, int rank, const uint8_t *unique_id)
 {
     check(kta_comm_create(ctx_, nranks, rank, unique_id), "kta_comm_create");

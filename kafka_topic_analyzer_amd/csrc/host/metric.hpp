@@ -158,6 +158,10 @@ public:
     // between replay_compaction(true) and replay_compaction(false) — and then the live compaction vector u64[5 P + 6].
     void replay_compaction(bool on);
     std::vector<uint64_t> compaction();
+    // The compact,delete what-if (kta_set_compact_delete): after set_segments, before any record, with KTA_FLAG_COMPACTION;
+    // then, behind the replay, the live kept vector u64[(P M + P) 4 + 8].
+    void set_compact_delete(bool on);
+    std::vector<uint64_t> compact_delete();
     const MessageMetrics &metrics() const { return metrics_; }
     const LogCompactionInMemoryMetrics *log_compaction() const { return alive_ ? &lc_ : nullptr; }
     kta_ctx *ctx() { return ctx_; }
@@ -230,6 +234,11 @@ std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_
 // section (kta_render_compaction): vec u64[5 P + 6], counters u64[P * 7 + 8] (the first pass's counter vector).  *matched
 // (when given): whether the replay matched the first pass; a section that says it did not otherwise
 std::string render_compaction(const uint64_t *vec, const uint64_t *counters, uint32_t P, bool *matched = nullptr);
+// The opt-in compact,delete section (kta.compact_delete=1; kta_render_compact_delete), printed after the retention section
+// and before the filter's: seg / kept u64[(P M + P) 4 + 8], comp u64[5 P + 6].  *matched: false when the replay did not match
+// the first pass (the section then says so).  Empty: arguments kta_compact_delete_whatif refuses for another reason.
+std::string render_compact_delete(const uint64_t *seg, const uint64_t *kept, const uint64_t *comp, uint32_t P, uint32_t M, int64_t now_ms,
+                                  int64_t retention_ms, int64_t retention_bytes, bool *matched = nullptr);
 // the section kta-analyzer prints after everything else when a filter was given (kta.from, kta.to, kta.partitions;
 // kta_render_filter): bitmap null or ceil(P / 32) words as kta_set_filter takes them; the counts are kta_filter_info's
 std::string render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *bitmap, uint32_t P, uint64_t seen, uint64_t passed);

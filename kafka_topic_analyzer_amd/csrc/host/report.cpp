@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "kta_compact_delete.h"
 #include "kta_compaction.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
@@ -504,6 +505,58 @@ std::string render_compaction(const uint64_t *vec, const uint64_t *counters, uin
     return o;
 }
 
+// The opt-in compact,delete section (kta.compact_delete=1): no reference counterpart, printed after the retention section and
+// before the filter's.  seg / kept: u64[(P M + P) 4 + 8], comp: u64[5 P + 6] (kta_hip.h); retention -1: the rule is off.
+std::string render_compact_delete(const uint64_t *seg, const uint64_t *kept, const uint64_t *comp, uint32_t P, uint32_t M, int64_t now_ms,
+                                  int64_t retention_ms, int64_t retention_bytes, bool *matched)
+{
+    if (matched) *matched = false;
+    if (!seg || !kept || !comp || !segments_config_ok(1, M, P) || P > kCompactDeleteMaxPartitions || retention_ms < -1 || retention_bytes < -1)
+        return std::string();
+    const uint64_t *g = seg + segments_globals_at(P, M);
+    if (g[kSegGlobalM] != M || !segments_config_ok(g[kSegGlobalS], M, P)) return std::string();
+    auto u = [](uint64_t v) { return std::to_string(v); };
+    auto rule = [](int64_t v) { return v < 0 ? std::string("-") : std::to_string(v); };
+    std::string o = "Compact,delete what-if: cleanup.policy=compact,delete over model log segments of " + u(g[kSegGlobalS]) +
+                    " bytes per partition (kta.compact_delete), retention.ms=" + rule(retention_ms) + ", retention.bytes=" + rule(retention_bytes) +
+                    ", now=" + (retention_ms < 0 ? std::string("-") : std::to_string(now_ms)) +
+                    " ms; the active segment is not cleaned (not part of the reference report)\n";
+    std::vector<uint64_t> w((size_t)(P + 1) * kCdWords);
+    if (kta_compact_delete_whatif(seg, kept, comp, P, M, now_ms, retention_ms, retention_bytes, w.data(), w.size()) != KTA_OK) {
+        o += "The replay did not match the first pass. Nothing is reported.\n";
+        o += std::string(120, '=') + "\n";
+        return o;
+    }
+    if (matched) *matched = true;
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Records", "Bytes", "Compacted records", "Compacted bytes", "Kept records", "Kept bytes", "Tombstones kept", "Reclaimed %",
+                    "Rule"});
+    for (uint32_t p = 0; p <= P; p++) {
+        const uint64_t *r = w.data() + (size_t)p * kCdWords;
+        const bool all = p == P;
+        char buf[32];
+        snprintf(buf, sizeof buf, "%.2f", r[kCdBytes] ? ((double)r[kCdBytes] - (double)r[kCdKeptBytes]) * 100.0 / (double)r[kCdBytes] : 0.0);
+        const char *const names[4] = {"-", "time", "size", "time+size"};
+        rows.push_back({all ? "All" : std::to_string(p) + (r[kCdClamped] ? "+" : ""), u(r[kCdRecords]), u(r[kCdBytes]), u(r[kCdCompactedRecords]),
+                        u(r[kCdCompactedBytes]), u(r[kCdKeptRecords]), u(r[kCdKeptBytes]), u(r[kCdKeptTombstones]), r[kCdBytes] ? buf : "-",
+                        names[r[kCdRule] & 3u]});
+    }
+    o += pretty_table(rows);
+    const uint64_t clamped = w[(size_t)P * kCdWords + kCdClamped];
+    if (clamped)
+        o += u(clamped) + " partition(s) outgrew the " + u(M) + " rows kept per partition (P ends in +): the last row holds the rest and counts as "
+             "the active segment (kta.segments.rows).\n";
+    o += "Model: a segment ends with the record whose bytes reach its size, so a boundary can differ from the broker's by one record per "
+         "segment; segment.ms is not modelled; a record's size is key + value + " + u(g[kSegGlobalOverhead]) + " bytes, not bytes on disk (no batch "
+         "headers, no compression); the active segment is never cleaned and never deleted, and a prefix without any timestamp is not deleted by "
+         "time. Keys are counted by 32-bit hash slot, topic-wide, as \"Alive keys\" is: a key written to several partitions is kept once. The "
+         "time rule uses the largest timestamp of all records up to a segment's end, cleaned away or not, so it keeps at least what the broker "
+         "keeps. delete.retention.ms, min.compaction.lag.ms and min.cleanable.dirty.ratio are not modelled: every tombstone that survives is "
+         "kept, and every closed segment counts as cleaned.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // The section of a filtered run (kta.from, kta.to, kta.partitions): no reference counterpart, printed after everything else.
 // The filter as given — bounds in epoch seconds as the keys take them, the set as ascending ranges — then the records
 // the run was handed and the records that passed.  bitmap null: no set; else ceil(P / 32) words (kta_set_filter).
@@ -703,6 +756,24 @@ extern "C" int kta_render_compaction(const uint64_t *vec, const uint64_t *counte
     bool matched = false;
     const std::string text = kta::render_compaction(vec, counter_vec, n_partitions, &matched);
     *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return matched ? KTA_OK : KTA_ERR_INVALID;
+}
+
+extern "C" int kta_render_compact_delete(const uint64_t *seg_vec, const uint64_t *kept_vec, const uint64_t *comp_vec, uint32_t n_partitions,
+                                         uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes, char *out,
+                                         size_t out_cap, size_t *out_len)
+{
+    if (!out_len) return KTA_ERR_INVALID;
+    bool matched = false;
+    const std::string text = kta::render_compact_delete(seg_vec, kept_vec, comp_vec, n_partitions, rows_per_partition, now_ms, retention_ms,
+                                                        retention_bytes, &matched);
+    *out_len = text.size();
+    if (text.empty()) return KTA_ERR_INVALID;
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());
         memcpy(out, text.data(), n);

@@ -4,6 +4,7 @@
 // family: kta_alive_table.hip), behind the launchers of kta_kernels.h.  There is no CPU fallback: every
 // entry point that computes anything needs a gfx950 device.
 #include "../../include/kta_hip.h"
+#include "kta_compact_delete.h"
 #include "kta_compaction.h"
 #include "kta_internal.h"
 #include "kta_kernels.h"
@@ -113,6 +114,14 @@ struct kta_ctx {
     uint64_t comp_saved_seq = 0;
     DeviceBuf<uint64_t> d_comp, d_comp_stats;
     uint64_t comp_launches = 0, comp_workgroups = 0;
+    // compact,delete what-if (kta_set_compact_delete): d_kept u64[(P M + P) 4 + 8] the kept vector the replay writes, whose totals
+    // are its running state, d_cd_cls the class column of one replay slice (a byte per record; grows to the largest slice
+    // seen, at most 128 MiB), d_cd_stats the kept-apply kernel's work counters (kta_compact_delete_info).  The workspace and
+    // the flags of the launch triple are the segment pass's: the two never run at the same time.
+    bool cd = false;
+    DeviceBuf<uint64_t> d_kept, d_cd_stats;
+    DeviceBuf<uint8_t> d_cd_cls;
+    uint64_t cd_launches = 0, cd_chunks = 0;
     // size percentiles (KTA_FLAG_SIZE_QUANTILES): d_sizeq u64[P * 3 * 464 + 8] the live vector, d_sizeq_out its snapshot,
     // d_sizeq_stats the kernel's work counters (kta_size_quantiles_info); sizeq_slice the tests' S (kta_set_size_quantiles_slice;
     // 0: the plan's), sizeq_variant the launch form (KTA_SIZEQ_VARIANT: 0, or the diagnostics 1 and 9 of tools/bench_size_quantiles.py)
@@ -417,7 +426,59 @@ int run_compaction(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns 
     return KTA_OK;
 }
 
-// A batch of the replay (kta_compaction_replay): the compaction pass and nothing else, whatever `which` says.
+// The replay of a context with kta_set_compact_delete on: per slice the compaction launch, which also writes the slice's class
+// column, then the kept-row triple over the same records.  The chunk is run_segments' (kta_set_segments_chunk included);
+// a slice is as many chunks as the workspace has rows for, and no more records than the class column's 128 MiB hold.
+int run_compact_delete(kta_ctx *ctx, const kta_batch *c, const kta_internal_columns &rb, uint64_t n, uint64_t base_seq)
+{
+    const kta::SegmentsState st{ctx->d_kept.get(), ctx->d_seg_ws.get(), ctx->d_seg_flags.get(), ctx->d_cd_stats.get(), ctx->seg_S, ctx->seg_M,
+                                ctx->seg_overhead};
+    const uint64_t max_rows = kta::kSegmentsWorkspaceWords / ((uint64_t)ctx->P * kta::kSegWords);
+    for (uint64_t at = 0; at < n;) {
+        const uint64_t left = n - at;
+        uint64_t chunk = ctx->seg_chunk;
+        if (chunk == 0) {
+            chunk = ((left + kta::kSegmentsChunks - 1) / kta::kSegmentsChunks + 255) / 256 * 256;
+            if (chunk < kta::kSegmentsChunkMin) chunk = kta::kSegmentsChunkMin;
+        }
+        uint64_t take = left / chunk >= max_rows ? max_rows * chunk : left;
+        if (take > kta::kCompactDeleteScratchBytes)
+            take = chunk <= kta::kCompactDeleteScratchBytes ? kta::kCompactDeleteScratchBytes / chunk * chunk : kta::kCompactDeleteScratchBytes;
+        if (ctx->d_cd_cls.size() < take) {
+            KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (an earlier slice may still read the old column)
+            KTA_HIP(ctx, ctx->d_cd_cls.alloc(take));
+        }
+        uint32_t wgs = 0;
+        KTA_HIP(ctx, kta::launch_compaction(kta::CompactionColumns{sketch_columns(rb, c, at), c->val_len + at, c->seq ? c->seq + at : nullptr}, take,
+                                            base_seq + at, ctx->P, ctx->d_table.get(), ctx->d_comp.get(), ctx->d_comp_stats.get(), ctx->cu_count,
+                                            &wgs, ctx->s_compute, ctx->d_cd_cls.get()));
+        ctx->comp_launches++;
+        ctx->comp_workgroups += wgs;
+        KTA_HIP(ctx, kta::launch_kept_rows(scan_columns(rb, at), ctx->d_cd_cls.get(), take, chunk, ctx->P, st, ctx->s_compute));
+        ctx->cd_launches += 3;
+        ctx->cd_chunks += (take + chunk - 1) / chunk;
+        at += take;
+    }
+    return KTA_OK;
+}
+
+// The live kept vector as kta_set_compact_delete, kta_reset and kta_compaction_replay(ctx, 1) leave it: zero but for the
+// configuration globals.
+int clear_kept(kta_ctx *ctx)
+{
+    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
+    const uint64_t cfg[3] = {ctx->seg_S, ctx->seg_M, ctx->seg_overhead};
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_kept.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_kept.get() + kta::segments_globals_at(ctx->P, ctx->seg_M) + kta::kSegGlobalS, cfg, sizeof cfg,
+                                hipMemcpyHostToDevice, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (cfg is this frame's)
+    KTA_HIP(ctx, hipMemsetAsync(ctx->d_cd_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
+    ctx->cd_launches = ctx->cd_chunks = 0;
+    return KTA_OK;
+}
+
+// A batch of the replay (kta_compaction_replay): the compaction pass — with kta_set_compact_delete, the kept rows behind it —
+// and nothing else, whatever `which` says.
 int run_replayed_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq)
 {
     // every refusal comes before the first launch
@@ -428,6 +489,7 @@ int run_replayed_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t ba
     if (rc != KTA_OK) return rc;
     rc = widen_lens_for_keys(ctx, c, n);
     if (rc != KTA_OK) return rc;
+    if (ctx->cd) return run_compact_delete(ctx, c, rb, n, base_seq);
     return run_compaction(ctx, c, rb, n, base_seq);
 }
 
@@ -852,6 +914,10 @@ int reset_state(kta_ctx *ctx)
         ctx->comp_launches = ctx->comp_workgroups = 0;
         ctx->comp_replay = false;
         ctx->comp_saved_seq = 0;
+    }
+    if (ctx->cd) {                      // (the switch stays)
+        int rc = clear_kept(ctx);
+        if (rc != KTA_OK) return rc;
     }
     if (ctx->sizeq) {                   // (a forced slice stays)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sizeq.get(), 0, kta::size_quantiles_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
@@ -2039,6 +2105,7 @@ int kta_set_segments(kta_ctx *ctx, uint64_t segment_bytes, uint32_t rows_per_par
         KTA_HIP(ctx, ctx->d_seg_stats.alloc(4));
     }
     ctx->seg_S = segment_bytes, ctx->seg_M = rows_per_partition, ctx->seg_overhead = record_overhead;
+    ctx->cd = false;                    // (the kept vector has the old configuration's shape: kta_set_compact_delete comes after this)
     int rc = clear_segments(ctx);
     if (rc != KTA_OK) return rc;
     KTA_HIP(ctx, hipMemcpyAsync(ctx->d_seg_out.get(), ctx->d_seg.get(), words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
@@ -2315,6 +2382,10 @@ int kta_compaction_replay(kta_ctx *ctx, int on)
     if (rc != KTA_OK) return rc;
     if (want) {
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp.get(), 0, kta::compaction_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        if (ctx->cd) {
+            rc = clear_kept(ctx);
+            if (rc != KTA_OK) return rc;
+        }
         ctx->comp_saved_seq = ctx->next_seq;
         ctx->next_seq = 0;
     } else {
@@ -2347,6 +2418,81 @@ int kta_compaction_info(kta_ctx *ctx, uint64_t out[6])
     kta::compaction_lds_plan(ctx->P, plan);
     out[0] = st[0], out[1] = ctx->comp_launches, out[2] = ctx->comp_workgroups, out[3] = st[1], out[4] = plan[0], out[5] = 0;
     return rc;
+}
+
+// ---- compact,delete what-if (kta_compact_delete.h holds the rule; the kernels are kta_compaction.hip's and kta_segments.hip's) ----
+
+static const char *const kNoCd = "the context has no compact,delete what-if (kta_set_compact_delete)";
+static_assert(kta::kCdWords == KTA_COMPACT_DELETE_WORDS, "the what-if's row is said twice: kta_compact_delete.h and kta_hip.h");
+static_assert(kta::kCompactDeleteMaxPartitions == (kta::kSegmentsMaxPartitions < kta::kCompactionMaxPartitions ? kta::kSegmentsMaxPartitions
+                                                                                                               : kta::kCompactionMaxPartitions),
+              "the smaller of the two passes' bounds");
+
+int kta_compact_delete_max_partitions(void) { return (int)kta::kCompactDeleteMaxPartitions; }
+
+int kta_set_compact_delete(kta_ctx *ctx, int on)
+{
+    if (!ctx) return KTA_ERR_INVALID;
+    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    if (ctx->handed_records || ctx->fill_n || ctx->comp_replay)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_compact_delete: the context has been handed records since kta_create / kta_reset");
+    if (ctx->P > kta::kCompactDeleteMaxPartitions)
+        return fail(ctx, KTA_ERR_INVALID, "kta_set_compact_delete admits at most " + std::to_string(kta::kCompactDeleteMaxPartitions) + " partitions");
+    if (!on) {
+        ctx->cd = false;
+        return KTA_OK;
+    }
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
+    if (ctx->d_kept.size() != words) {
+        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+        KTA_HIP(ctx, ctx->d_kept.alloc(words));
+    }
+    if (!ctx->d_cd_stats) KTA_HIP(ctx, ctx->d_cd_stats.alloc(4));
+    int rc = clear_kept(ctx);
+    if (rc != KTA_OK) return rc;
+    ctx->cd = true;
+    return KTA_OK;
+}
+
+int kta_get_compact_delete(kta_ctx *ctx, uint64_t *out, size_t n_u64)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->cd) return fail(ctx, KTA_ERR_INVALID, kNoCd);
+    int rc = check_words(ctx, "kept vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, ctx->d_kept.get(), out, n_u64);
+}
+
+int kta_compact_delete_info(kta_ctx *ctx, uint64_t out[4])
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->cd) return fail(ctx, KTA_ERR_INVALID, kNoCd);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    uint64_t st[4];
+    rc = read_words(ctx, ctx->d_cd_stats.get(), st, 4);
+    out[0] = ctx->cd_launches, out[1] = ctx->cd_chunks, out[2] = st[0], out[3] = ctx->d_cd_cls.size();
+    return rc;
+}
+
+int kta_compact_delete_whatif(const uint64_t *seg_vec, const uint64_t *kept_vec, const uint64_t *comp_vec, uint32_t P, uint32_t M, int64_t now_ms,
+                              int64_t retention_ms, int64_t retention_bytes, uint64_t *out, size_t n_u64)
+{
+    if (!seg_vec || !kept_vec || !comp_vec || !out || !kta::segments_config_ok(1, M, P) || P > kta::kCompactDeleteMaxPartitions ||
+        n_u64 != ((size_t)P + 1) * KTA_COMPACT_DELETE_WORDS)
+        return KTA_ERR_INVALID;
+    if (retention_ms < -1 || retention_bytes < -1) return KTA_ERR_INVALID;
+    const uint64_t *g = seg_vec + kta::segments_globals_at(P, M);
+    if (g[kta::kSegGlobalM] != M || !kta::segments_config_ok(g[kta::kSegGlobalS], M, P)) return KTA_ERR_INVALID;   // not a vector of this shape
+    if (!kta::compact_delete_identities_hold(seg_vec, kept_vec, comp_vec, P, M)) return KTA_ERR_INVALID;   // the replay did not match the first pass
+    kta::compact_delete_whatif(seg_vec, kept_vec, P, M, now_ms, retention_ms, retention_bytes, out);
+    return KTA_OK;
 }
 
 // ---- record filter (kta_filter.h holds the rules, kta_filter.hip the kernels) ------------------------------------------

@@ -17,6 +17,7 @@
 //                     2^30 records, so no half of W0 overflows and nothing is flushed before the end: there the workgroup
 //                     sums the replicas and adds the non-zero words to the live u64 vector.  The globals are popcounts
 //                     of ballots, kept per wave in scalar registers.
+#include "kta_compact_delete.h"
 #include "kta_compaction.h"
 #include "kta_key_stream.h"
 
@@ -76,11 +77,19 @@ struct PendingStep {
     int32_t pt[4];
     uint32_t in;           // bit j: record 64 j + lane of the step lies in the batch
 };
+// (CLASS: with the step's first record)
+template <bool CLASS> struct PendingStepOf : PendingStep {};
+template <> struct PendingStepOf<true> : PendingStep {
+    uint64_t at;
+};
 
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionColumns c, uint64_t n, uint64_t base_seq, uint32_t P, uint32_t rep_log2,
-                                                                    const unsigned long long *__restrict__ table, unsigned long long *acc,
-                                                                    unsigned long long *stats)
+// The kernel's text.  CLASS: every record's class byte (kta_compact_delete.h: 0 not kept, 1 live, 2 tombstone kept) goes to
+// cls[record], one plain byte store where the record is classified — what the kept-row kernels of the compact,delete
+// what-if read (kta_segments.hip).  Without it nothing of cls is looked at and the text is the one the kernel always had.
+template <int THREADS, bool CLASS>
+__device__ __forceinline__ void compaction_survivors(CompactionColumns c, uint64_t n, uint64_t base_seq, uint32_t P, uint32_t rep_log2,
+                                                     const unsigned long long *__restrict__ table, unsigned long long *acc,
+                                                     unsigned long long *stats, uint8_t *__restrict__ cls)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_part[];    // [P << rep][4]
     __shared__ unsigned long long s_glob[kCompactionGlobals + kCompStats];
@@ -98,11 +107,13 @@ __global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionCo
     uint32_t n_replayed = 0, n_unkeyed = 0, n_unknown = 0, n_live_out = 0, n_tomb_out = 0, n_keyed = 0, n_adds = 0;
 
     // the step whose slot loads were issued an iteration ago: its classes, its survivors into LDS
-    auto settle = [&](const PendingStep &pd) {
+    auto settle = [&](const PendingStepOf<CLASS> &pd) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const bool in = (pd.in >> j) & 1u;
             const CompactionClass k = compaction_classify(pd.entry[j], pd.sq[j], pd.kl[j], pd.vl[j], pd.pt[j], P);
+            if constexpr (CLASS)
+                if (in) cls[pd.at + 64u * j + lane] = kept_class_byte(k);
             n_replayed += (uint32_t)__popcll(__ballot(in));
             n_unkeyed += (uint32_t)__popcll(__ballot(in && k == kCompactionUnkeyed));
             n_unknown += (uint32_t)__popcll(__ballot(in && k == kCompactionUnknown));
@@ -131,7 +142,7 @@ __global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionCo
     uint64_t cur_sq[4];
     load_keyed_cols<kCompStep>(c.k, step, nsteps, n, lane, cur);
     load_val_seq4(c, base_seq, step, nsteps, n, lane, cur_vl, cur_sq);
-    PendingStep pd;
+    PendingStepOf<CLASS> pd;
     bool pending = false;                            // (uniform)
     while (step < nsteps) {
         uint4 keys[4];
@@ -145,8 +156,9 @@ __global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionCo
         uint32_t h[4];
         hash_keys4(h, keys, c.k.key_bytes, cur.kl, cur.ko);
         // this step's slots, requested now and looked at in the next iteration (key None: slot 0, discarded)
-        PendingStep now;
+        PendingStepOf<CLASS> now;
         now.in = 0u;
+        if constexpr (CLASS) now.at = step * kCompStep;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             now.entry[j] = table[cur.kl[j] >= 0 ? h[j] : 0u];
@@ -191,6 +203,23 @@ __global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionCo
     if (threadIdx.x < kCompStats && s_glob[kCompactionGlobals + threadIdx.x]) atomicAdd(stats + threadIdx.x, s_glob[kCompactionGlobals + threadIdx.x]);
 }
 
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void kta_compaction_survivors(CompactionColumns c, uint64_t n, uint64_t base_seq, uint32_t P, uint32_t rep_log2,
+                                                                    const unsigned long long *__restrict__ table, unsigned long long *acc,
+                                                                    unsigned long long *stats)
+{
+    compaction_survivors<THREADS, false>(c, n, base_seq, P, rep_log2, table, acc, stats, nullptr);
+}
+
+// the same with the class column (cls: u8[n], every byte written)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void kta_compaction_survivors_class(CompactionColumns c, uint64_t n, uint64_t base_seq, uint32_t P,
+                                                                          uint32_t rep_log2, const unsigned long long *__restrict__ table,
+                                                                          unsigned long long *acc, unsigned long long *stats, uint8_t *__restrict__ cls)
+{
+    compaction_survivors<THREADS, true>(c, n, base_seq, P, rep_log2, table, acc, stats, cls);
+}
+
 } // namespace
 
 void compaction_lds_plan(uint32_t P, uint32_t out[3])
@@ -200,7 +229,7 @@ void compaction_lds_plan(uint32_t P, uint32_t out[3])
 }
 
 hipError_t launch_compaction(const CompactionColumns &c, uint64_t n, uint64_t base_seq, uint32_t P, const uint64_t *table, uint64_t *acc,
-                             uint64_t *stats, int cu_count, uint32_t *workgroups, hipStream_t s)
+                             uint64_t *stats, int cu_count, uint32_t *workgroups, hipStream_t s, uint8_t *cls)
 {
     *workgroups = 0;
     if (n == 0) return hipSuccess;
@@ -213,7 +242,17 @@ hipError_t launch_compaction(const CompactionColumns &c, uint64_t n, uint64_t ba
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
     const unsigned long long *t = reinterpret_cast<const unsigned long long *>(table);
     unsigned long long *a = reinterpret_cast<unsigned long long *>(acc), *st = reinterpret_cast<unsigned long long *>(stats);
-    if (pl.threads == 256) {
+    if (cls) {
+        if (pl.threads == 256) {
+            hipLaunchKernelGGL(kta_compaction_survivors_class<256>, dim3(grid), dim3(256), pl.lds_bytes, s, c, n, base_seq, P, pl.rep_log2, t, a, st, cls);
+        } else {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_compaction_survivors_class<1024>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kta_compaction_survivors_class<1024>, dim3(grid), dim3(1024), pl.lds_bytes, s, c, n, base_seq, P, pl.rep_log2, t, a, st,
+                               cls);
+        }
+    } else if (pl.threads == 256) {
         hipLaunchKernelGGL(kta_compaction_survivors<256>, dim3(grid), dim3(256), pl.lds_bytes, s, c, n, base_seq, P, pl.rep_log2, t, a, st);
     } else {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&kta_compaction_survivors<1024>),

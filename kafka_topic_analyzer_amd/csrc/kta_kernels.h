@@ -301,6 +301,10 @@ struct SegmentsState {
 // Records [0, n) of c in chunks of `chunk` records (a multiple of 64, at most 2^31; ceil(n / chunk) * 4 P <=
 // kSegmentsWorkspaceWords): chunk sums, prefix, apply.
 hipError_t launch_segments(const ScanColumns &c, uint64_t n, uint64_t chunk, uint32_t P, const SegmentsState &st, hipStream_t s);
+// The kept rows of the compact,delete what-if (kta_set_compact_delete; the rule and the vector's layout are
+// kta_compact_delete.h's): the same triple over st.vec = the kept vector, with cls u8[n] the records' class bytes, which
+// launch_compaction wrote.  The timestamp column is not read.  st.stats: u64[4] as above.
+hipError_t launch_kept_rows(const ScanColumns &c, const uint8_t *cls, uint64_t n, uint64_t chunk, uint32_t P, const SegmentsState &st, hipStream_t s);
 
 // Partitioner (KTA_FLAG_PARTITIONER, kta_partitioner.hip): the live vector u64[2 P + 2 Q] = [P][2] checked, placed |
 // [Q][2] target_records, target_bytes, every word a sum that the workgroups of launch_partitioner add their LDS counters to.
@@ -327,9 +331,10 @@ struct CompactionColumns {
     const uint64_t *seq;        // null: record i has the sequence number base_seq + i
 };
 // the replay of records [0, n) of c against the last-writer table, n <= kCompactionLaunchMax; stats: u64[3] += keyed
-// records looked at, LDS adds, reserved; *workgroups = the grid
+// records looked at, LDS adds, reserved; *workgroups = the grid.  cls (null: none): u8[n], gets every record's class byte
+// (kta_compact_delete.h) — another instantiation of the kernel.
 hipError_t launch_compaction(const CompactionColumns &c, uint64_t n, uint64_t base_seq, uint32_t P, const uint64_t *table, uint64_t *acc,
-                             uint64_t *stats, int cu_count, uint32_t *workgroups, hipStream_t s);
+                             uint64_t *stats, int cu_count, uint32_t *workgroups, hipStream_t s, uint8_t *cls = nullptr);
 // out = {dynamic LDS bytes, threads, workgroups per CU} of the launch for P (kta_compaction_info)
 void compaction_lds_plan(uint32_t P, uint32_t out[3]);
 

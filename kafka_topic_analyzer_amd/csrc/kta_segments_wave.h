@@ -14,6 +14,11 @@
 // No lane pays a 64-bit division unless its partition reaches a boundary in this instruction: nxt[p], beside run[p], is
 // the next offset at which the partition's segment changes (segments_next_boundary of run[p].B); a lane whose B stays
 // below it closes nothing, and only the lane that writes run[p] past it works out the next one.
+//
+// KEPT (the compact,delete what-if's kept rows, kta_compact_delete.h): the same step over the words {L, B, T, K} — the
+// count contribution is the flag `counted` instead of the constant 1, `tomb` says "a tombstone that survives", and the
+// fourth word is the SUM of the values handed in as h1 (the record's size where it survives, else 0) instead of their
+// maximum.  Positions (B, nxt, closes) are the same in both instantiations.
 // (Whoever includes this — inside a namespace of its own — has included kta_segments.h before.)
 #pragma once
 
@@ -36,6 +41,8 @@
 __device__ __forceinline__ bool seg_takes_part(int32_t p, uint32_t P) { return (uint32_t)p < P; }
 
 __device__ __forceinline__ uint64_t seg_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+// how the fourth word combines: the maximum, or (KEPT) the sum
+template <bool KEPT> __device__ __forceinline__ uint64_t seg_join(uint64_t a, uint64_t b) { return KEPT ? a + b : seg_max(a, b); }
 
 __device__ __forceinline__ uint64_t seg_shfl_up(uint64_t v, uint32_t off)
 {
@@ -48,19 +55,19 @@ __device__ __forceinline__ uint64_t seg_shfl_up(uint64_t v, uint32_t off)
 struct SegPrefix {
     uint64_t b;     // bytes
     uint32_t ct;    // records | tombstones << 16
-    uint64_t h;     // H + 1 (0: none)
+    uint64_t h;     // H + 1 (0: none); KEPT: kept bytes
 };
-__device__ __forceinline__ SegPrefix seg_own(bool in, uint64_t z, bool tomb, uint64_t h1)
+__device__ __forceinline__ SegPrefix seg_own(bool in, uint64_t z, bool tomb, uint64_t h1, bool counted = true)
 {
-    return in ? SegPrefix{z, 1u | (tomb ? 1u << 16 : 0u), h1} : SegPrefix{0, 0, 0};
+    return in ? SegPrefix{z, (counted ? 1u : 0u) | (tomb ? 1u << 16 : 0u), h1} : SegPrefix{0, 0, 0};
 }
-__device__ __forceinline__ void seg_prefix(uint32_t lane, SegPrefix &a)
+template <bool KEPT = false> __device__ __forceinline__ void seg_prefix(uint32_t lane, SegPrefix &a)
 {
 #pragma unroll
     for (uint32_t off = 1; off < 64; off <<= 1) {
         const uint64_t tb = seg_shfl_up(a.b, off), th = seg_shfl_up(a.h, off);
         const uint32_t tc = KTA_SHFL_UP(a.ct, off);
-        if (lane >= off) a.b += tb, a.ct += tc, a.h = seg_max(a.h, th);
+        if (lane >= off) a.b += tb, a.ct += tc, a.h = seg_join<KEPT>(a.h, th);
     }
 }
 
@@ -72,18 +79,20 @@ struct SegAt {
 };
 
 // seed: run[p] and nxt[p] as they were before the instruction; a: the lane's inclusive prefix; z: its record's size
+template <bool KEPT = false>
 __device__ __forceinline__ void seg_place(const uint64_t (&seed)[kta::kSegWords], uint64_t nx, const SegPrefix &a, uint64_t z, uint64_t S, uint32_t M,
                                           SegAt &at)
 {
     at.v[kta::kSegC] = seed[kta::kSegC] + (a.ct & 0xFFFFu);
     at.v[kta::kSegB] = seed[kta::kSegB] + a.b;
     at.v[kta::kSegT] = seed[kta::kSegT] + (a.ct >> 16);
-    at.v[kta::kSegH1] = seg_max(seed[kta::kSegH1], a.h);
+    at.v[kta::kSegH1] = seg_join<KEPT>(seed[kta::kSegH1], a.h);
     at.closes = false;
     at.row = 0;
     if (at.v[kta::kSegB] >= nx) at.closes = kta::segments_closes(at.v[kta::kSegB] - z, at.v[kta::kSegB], S, M, &at.row);
 }
 // run[p] = seed + a, a the prefix of the partition's last lane; nxt[p] follows when B got past it
+template <bool KEPT = false>
 __device__ __forceinline__ void seg_advance(uint64_t *run_p, uint64_t *nxt_p, const uint64_t (&seed)[kta::kSegWords], uint64_t nx,
                                             const SegPrefix &a, uint64_t S, uint32_t M)
 {
@@ -91,23 +100,24 @@ __device__ __forceinline__ void seg_advance(uint64_t *run_p, uint64_t *nxt_p, co
     run_p[kta::kSegC] = seed[kta::kSegC] + (a.ct & 0xFFFFu);
     run_p[kta::kSegB] = b;
     run_p[kta::kSegT] = seed[kta::kSegT] + (a.ct >> 16);
-    run_p[kta::kSegH1] = seg_max(seed[kta::kSegH1], a.h);
+    run_p[kta::kSegH1] = seg_join<KEPT>(seed[kta::kSegH1], a.h);
     if (b >= nx) *nxt_p = kta::segments_next_boundary(b, S, M);
 }
 
 // the lanes `in` — all of partition pg — as one group (every lane of the wave takes the steps)
+template <bool KEPT = false>
 __device__ __forceinline__ void seg_group(uint64_t *run, uint64_t *nxt, uint32_t lane, bool in, uint32_t pg, uint64_t z, bool tomb, uint64_t h1,
-                                          uint64_t S, uint32_t M, SegAt &at)
+                                          uint64_t S, uint32_t M, SegAt &at, bool counted = true)
 {
-    SegPrefix a = seg_own(in, z, tomb, h1);
-    seg_prefix(lane, a);
+    SegPrefix a = seg_own(in, z, tomb, h1, counted);
+    seg_prefix<KEPT>(lane, a);
     uint64_t seed[kta::kSegWords];
 #pragma unroll
     for (uint32_t k = 0; k < kta::kSegWords; k++) seed[k] = run[(size_t)pg * kta::kSegWords + k];
     const uint64_t nx = nxt[pg];
-    if (in) seg_place(seed, nx, a, z, S, M, at);
+    if (in) seg_place<KEPT>(seed, nx, a, z, S, M, at);
     KTA_SEG_LDS_ORDER();
-    if (lane == 63) seg_advance(run + (size_t)pg * kta::kSegWords, nxt + pg, seed, nx, a, S, M);   // (lane 63's prefix is the group's sum)
+    if (lane == 63) seg_advance<KEPT>(run + (size_t)pg * kta::kSegWords, nxt + pg, seed, nx, a, S, M);   // (lane 63's prefix is the group's sum)
     KTA_SEG_LDS_ORDER();
 }
 
@@ -115,15 +125,17 @@ __device__ __forceinline__ void seg_group(uint64_t *run, uint64_t *nxt, uint32_t
 // contents).  on: the lane holds a record of partition p that takes part, of size z, a tombstone or not, with the
 // timestamp word h1 (the values of the other lanes are not looked at).  at: what a lane that is on gets (untouched
 // otherwise).  n_one / n_groups (the same on every lane) count the instructions that took the one-partition path and the
-// colliding groups resolved.  Every lane of the wave must call it.
+// colliding groups resolved.  Every lane of the wave must call it.  KEPT: see the head of this file.
+template <bool KEPT = false>
 __device__ __forceinline__ void seg_wave_step(uint64_t *run, uint64_t *nxt, uint8_t *tag, uint32_t lane, bool on, uint32_t p, uint64_t z, bool tomb,
-                                              uint64_t h1, uint64_t S, uint32_t M, SegAt &at, uint32_t &n_one, uint32_t &n_groups)
+                                              uint64_t h1, uint64_t S, uint32_t M, SegAt &at, uint32_t &n_one, uint32_t &n_groups,
+                                              bool counted = true)
 {
     const uint64_t live = KTA_BALLOT64(on);
     if (live == 0) return;
     const uint32_t p0 = KTA_READLANE(p, (uint32_t)__builtin_ctzll(live));
     if (KTA_BALLOT64(on && p != p0) == 0) {
-        seg_group(run, nxt, lane, on, p0, z, tomb, h1, S, M, at);
+        seg_group<KEPT>(run, nxt, lane, on, p0, z, tomb, h1, S, M, at, counted);
         n_one++;
         return;
     }
@@ -137,19 +149,19 @@ __device__ __forceinline__ void seg_wave_step(uint64_t *run, uint64_t *nxt, uint
         const uint32_t pg = KTA_READLANE(p, (uint32_t)__builtin_ctzll(todo));
         const bool in = on && p == pg;
         const uint64_t grp = KTA_BALLOT64(in);
-        seg_group(run, nxt, lane, in, pg, z, tomb, h1, S, M, at);
+        seg_group<KEPT>(run, nxt, lane, in, pg, z, tomb, h1, S, M, at, counted);
         grouped |= grp;
         todo &= ~grp;
         n_groups++;
     }
     if (on && !((grouped >> lane) & 1ull)) {            // alone in its partition
-        const SegPrefix a = seg_own(true, z, tomb, h1);
+        const SegPrefix a = seg_own(true, z, tomb, h1, counted);
         uint64_t seed[kta::kSegWords];
 #pragma unroll
         for (uint32_t k = 0; k < kta::kSegWords; k++) seed[k] = run[(size_t)p * kta::kSegWords + k];
         const uint64_t nx = nxt[p];
-        seg_place(seed, nx, a, z, S, M, at);
-        seg_advance(run + (size_t)p * kta::kSegWords, nxt + p, seed, nx, a, S, M);
+        seg_place<KEPT>(seed, nx, a, z, S, M, at);
+        seg_advance<KEPT>(run + (size_t)p * kta::kSegWords, nxt + p, seed, nx, a, S, M);
     }
     KTA_SEG_LDS_ORDER();
 }
