@@ -75,6 +75,60 @@ def _host_batch(cols: dict) -> KtaBatch:
     return hb
 
 
+# Every section's result vector, said once: the u64 words by the section's shape (P; Q, M or n_buckets where it has one) and
+# what a length error calls a vector of that shape.  The handler's read-backs, the split_* / render_* / merge_* functions
+# and the what-ifs all size and check their vectors here.
+_SECTIONS = {
+    "counters": (lambda P: P * N.KTA_NCOUNTERS + N.KTA_NGLOBALS, "a counter vector of {} partitions"),
+    "analytics": (lambda P: N.KTA_ANALYTICS_HIST + 4 * P, "an analytics vector of {} partitions"),
+    "timeline": (lambda n_buckets: (n_buckets + 3) * N.KTA_TIMELINE_COLS, "a timeline of {} buckets"),
+    "key_sketch": (lambda P: P * N.KTA_SKETCH_REGISTERS, "a key sketch of {} partitions"),
+    "hot_keys": (lambda: N.KTA_HOT_VECTOR_WORDS, "a hot-key vector"),
+    "ts_order": (lambda P: 3 * P + 64, "a timestamp-order vector of {} partitions"),
+    "partitioner": (lambda P, Q: 2 * P + 2 * Q, "a partitioner vector of {} partitions and {} targets"),
+    "size_quantiles": (lambda P: P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS, "a size vector of {} partitions"),
+    "segments": (lambda P, M: segments_words(P, M), "a segment vector of {} partitions and {} rows"),
+    "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
+    "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
+}
+
+
+def _section_words(name: str, *shape) -> int:
+    return _SECTIONS[name][0](*shape)
+
+
+def _u64_vec(vec, words: int, what: str) -> np.ndarray:
+    """`vec` flat, contiguous and as uint64 (an int64 array is viewed, not converted: a merge works in place on it), with
+    `words` words; `what` names the vector in the ValueError."""
+    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
+    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
+    if v.size != words:
+        raise ValueError(f"{what} has {words} words, not {v.size}")
+    return v
+
+
+def _section_vec(name: str, vec, *shape) -> np.ndarray:
+    return _u64_vec(vec, _section_words(name, *shape), _SECTIONS[name][1].format(*shape))
+
+
+def _counter_vec(vec, P: int) -> np.ndarray:
+    """The counter vector u64[P * 7 + 8] a render_* function takes beside its section's."""
+    c = np.ascontiguousarray(np.asarray(vec).reshape(-1)).view(np.uint64)
+    if c.size != _section_words("counters", P):
+        raise ValueError(f"a counter vector of {P} partitions has {_section_words('counters', P)} words")
+    return c
+
+
+def _merge(name: str, acc: np.ndarray, other, *shape) -> np.ndarray:
+    """kta_merge_<name>(acc, other, *shape), in place on `acc` (contiguous uint64 / int64)."""
+    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
+        raise TypeError("acc must be a contiguous uint64 / int64 array")
+    rc = getattr(N.load(), "kta_merge_" + name)(_np_ptr(_section_vec(name, acc, *shape)), _np_ptr(_section_vec(name, other, *shape)), *shape)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_merge_" + name)
+    return acc
+
+
 class HipMetricHandler:
     """Owns one `kta_ctx`.  `handle_message` == MetricHandler::handle_message (kafka.rs:18-20)."""
 
@@ -408,6 +462,30 @@ class HipMetricHandler:
         self._check(fn(self._ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def _shape(self, name: str) -> Optional[tuple]:
+        """The shape of section `name` in this handler, the arguments of its row of _SECTIONS; None: a timeline that was
+        never configured."""
+        P = self.n_partitions
+        if name == "timeline":
+            return (self.timeline_config[2],) if self.timeline_config else None
+        if name in ("segments", "compact_delete"):
+            if self.segments_config is None:
+                raise KtaError(N.KTA_ERR_INVALID, "the handler has no segments (segments=...)")
+            return (P, self.segments_config[1])
+        if name == "partitioner":
+            return (P, self.repartition)
+        if name == "hot_keys":
+            return ()
+        return (P,)
+
+    def _read_section(self, name: str, fn) -> np.ndarray:
+        """What a `(kta_ctx *, uint64_t *out, size_t n_u64)` read-back of section `name` (kta_get_* / kta_exchange_*) answers."""
+        shape = self._shape(name)
+        words = 0 if shape is None else _section_words(name, *shape)   # (no words: the library says that the section is off)
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        self._check(fn(self._ctx, _np_ptr(out), words))
+        return out if words else out[:0]
+
     def result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the counter vector (for collectives)."""
         return self._device_vector(self._lib.kta_result_vector)
@@ -445,20 +523,14 @@ class HipMetricHandler:
         self._check(self._lib.kta_set_timeline(self._ctx, int(origin_ms), int(bucket_ms), int(n_buckets)))
         self.timeline_config = (int(origin_ms), int(bucket_ms), int(n_buckets))
 
-    def _timeline(self, fn) -> np.ndarray:
-        n = (self.timeline_config[2] + 3) * N.KTA_TIMELINE_COLS if self.timeline_config else 0
-        out = np.zeros(max(n, 1), dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), n))
-        return out.reshape(-1, N.KTA_TIMELINE_COLS)
-
     def timeline(self) -> np.ndarray:
         """The live timeline, np.uint64[n_buckets + 3, 3]: rows [no timestamp, before, buckets..., after] of
         [records, tombstones, bytes] (kta_get_timeline; staged messages are flushed first)."""
-        return self._timeline(self._lib.kta_get_timeline)
+        return self._read_section("timeline", self._lib.kta_get_timeline).reshape(-1, N.KTA_TIMELINE_COLS)
 
     def exchange_timeline(self) -> np.ndarray:
         """As timeline(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._timeline(self._lib.kta_exchange_timeline)
+        return self._read_section("timeline", self._lib.kta_exchange_timeline).reshape(-1, N.KTA_TIMELINE_COLS)
 
     def timeline_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the live timeline."""
@@ -468,19 +540,14 @@ class HipMetricHandler:
         """(device pointer, length in u64) of the timeline snapshot (for collectives: allreduce_timeline_vector)."""
         return self._device_vector(self._lib.kta_timeline_result_vector)
 
-    def _key_sketch(self, fn) -> np.ndarray:
-        out = np.zeros((self.n_partitions, N.KTA_SKETCH_REGISTERS), dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), out.size))
-        return out
-
     def key_sketch(self) -> np.ndarray:
         """The live key sketch, np.uint64[P, 4096]: register j of partition p (kta_get_key_sketch; staged messages are
         flushed first)."""
-        return self._key_sketch(self._lib.kta_get_key_sketch)
+        return self._read_section("key_sketch", self._lib.kta_get_key_sketch).reshape(self.n_partitions, N.KTA_SKETCH_REGISTERS)
 
     def exchange_key_sketch(self) -> np.ndarray:
         """As key_sketch(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._key_sketch(self._lib.kta_exchange_key_sketch)
+        return self._read_section("key_sketch", self._lib.kta_exchange_key_sketch).reshape(self.n_partitions, N.KTA_SKETCH_REGISTERS)
 
     def key_sketch_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the key sketch snapshot (for collectives: allreduce_key_sketch_vector)."""
@@ -492,19 +559,14 @@ class HipMetricHandler:
         self._check(self._lib.kta_key_sketch_info(self._ctx, C.byref(out)))
         return {"keyed": int(out[0]), "reads": int(out[1]), "atomics": int(out[2]), "launches": int(out[3])}
 
-    def _hot_keys(self, fn) -> np.ndarray:
-        out = np.zeros((N.KTA_HOT_ROWS, N.KTA_HOT_CELLS, N.KTA_HOT_WORDS), dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), out.size))
-        return out
-
     def hot_keys(self) -> np.ndarray:
         """The live hot-key vector, np.uint64[2, 1024, 23]: per row and cell the total and the 22 bit counts
         (kta_get_hot_keys; staged messages are flushed first)."""
-        return self._hot_keys(self._lib.kta_get_hot_keys)
+        return self._read_section("hot_keys", self._lib.kta_get_hot_keys).reshape(N.KTA_HOT_ROWS, N.KTA_HOT_CELLS, N.KTA_HOT_WORDS)
 
     def exchange_hot_keys(self) -> np.ndarray:
         """As hot_keys(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._hot_keys(self._lib.kta_exchange_hot_keys)
+        return self._read_section("hot_keys", self._lib.kta_exchange_hot_keys).reshape(N.KTA_HOT_ROWS, N.KTA_HOT_CELLS, N.KTA_HOT_WORDS)
 
     def hot_keys_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the hot-key snapshot (for collectives: allreduce_hot_keys_vector)."""
@@ -527,19 +589,14 @@ class HipMetricHandler:
         self._check(self._lib.kta_get_hot_key_exemplars(self._ctx, _np_ptr(out), out.size))
         return out
 
-    def _ts_order(self, fn) -> dict:
-        out = np.zeros(3 * self.n_partitions + 64, dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), out.size))
-        return split_ts_order(out, self.n_partitions)
-
     def ts_order(self) -> dict:
         """The live timestamp-order vector as a dict of np.uint64 arrays: late[P], late_ms_sum[P], max_late_ms[P], hist[63],
         timed (kta_get_ts_order; staged messages are flushed first); "vector" is the whole u64[3 P + 64]."""
-        return self._ts_order(self._lib.kta_get_ts_order)
+        return split_ts_order(self._read_section("ts_order", self._lib.kta_get_ts_order), self.n_partitions)
 
     def exchange_ts_order(self) -> dict:
         """As ts_order(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._ts_order(self._lib.kta_exchange_ts_order)
+        return split_ts_order(self._read_section("ts_order", self._lib.kta_exchange_ts_order), self.n_partitions)
 
     def ts_order_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the timestamp-order snapshot (for collectives: allreduce_ts_order_vector)."""
@@ -566,12 +623,7 @@ class HipMetricHandler:
 
     def compact_delete(self) -> dict:
         """The live kept vector (kta_get_compact_delete; staged messages are flushed first) as split_compact_delete gives it."""
-        if self.segments_config is None:
-            raise KtaError(N.KTA_ERR_INVALID, "the handler has no segments (segments=...)")
-        M = self.segments_config[1]
-        out = np.zeros(segments_words(self.n_partitions, M), np.uint64)
-        self._check(self._lib.kta_get_compact_delete(self._ctx, _np_ptr(out), out.size))
-        return split_compact_delete(out, self.n_partitions, M)
+        return split_compact_delete(self._read_section("compact_delete", self._lib.kta_get_compact_delete), *self._shape("compact_delete"))
 
     def compact_delete_info(self) -> dict:
         """Work counters of the kept-row kernels since the replay began (kta_compact_delete_info)."""
@@ -579,22 +631,14 @@ class HipMetricHandler:
         self._check(self._lib.kta_compact_delete_info(self._ctx, C.byref(out)))
         return {"launches": int(out[0]), "chunks": int(out[1]), "chunks_applied": int(out[2]), "scratch_bytes": int(out[3])}
 
-    def _segments(self, fn) -> dict:
-        if self.segments_config is None:
-            raise KtaError(N.KTA_ERR_INVALID, "the handler has no segments (segments=...)")
-        M = self.segments_config[1]
-        out = np.zeros(segments_words(self.n_partitions, M), np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), len(out)))
-        return split_segments(out, self.n_partitions, M)
-
     def segments(self) -> dict:
         """The live segment vector (kta_get_segments; staged messages are flushed first) as split_segments gives it: "rows"
         [P][M][4], "totals" [P][4], "globals" [8] and "vector", the whole u64[(P M + P) 4 + 8]."""
-        return self._segments(self._lib.kta_get_segments)
+        return split_segments(self._read_section("segments", self._lib.kta_get_segments), *self._shape("segments"))
 
     def exchange_segments(self) -> dict:
         """As segments(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._segments(self._lib.kta_exchange_segments)
+        return split_segments(self._read_section("segments", self._lib.kta_exchange_segments), *self._shape("segments"))
 
     def segments_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the segment snapshot (for collectives: allreduce_segments_vector)."""
@@ -621,19 +665,14 @@ class HipMetricHandler:
         self._check(self._lib.kta_set_repartition(self._ctx, int(q)))
         self.repartition = int(q)
 
-    def _partitioner(self, fn) -> dict:
-        out = np.zeros(2 * self.n_partitions + 2 * self.repartition, dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), out.size))
-        return split_partitioner(out, self.n_partitions, self.repartition)
-
     def partitioner(self) -> dict:
         """The live partitioner vector as a dict of np.uint64 arrays: checked[P], placed[P], target_records[Q],
         target_bytes[Q] (kta_get_partitioner; staged messages are flushed first); "vector" is the whole u64[2 P + 2 Q]."""
-        return self._partitioner(self._lib.kta_get_partitioner)
+        return split_partitioner(self._read_section("partitioner", self._lib.kta_get_partitioner), *self._shape("partitioner"))
 
     def exchange_partitioner(self) -> dict:
         """As partitioner(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._partitioner(self._lib.kta_exchange_partitioner)
+        return split_partitioner(self._read_section("partitioner", self._lib.kta_exchange_partitioner), *self._shape("partitioner"))
 
     def partitioner_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the partitioner snapshot (for collectives: allreduce_partitioner_vector)."""
@@ -645,20 +684,15 @@ class HipMetricHandler:
         self._check(self._lib.kta_partitioner_info(self._ctx, C.byref(out)))
         return dict(zip(("keyed_records", "launches", "partition_adds", "target_adds", "workgroups", "lds_bytes"), (int(x) for x in out)))
 
-    def _size_quantiles(self, fn) -> dict:
-        out = np.zeros(self.n_partitions * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS, dtype=np.uint64)
-        self._check(fn(self._ctx, _np_ptr(out), out.size))
-        return split_size_quantiles(out, self.n_partitions)
-
     def size_quantiles(self) -> dict:
         """The live size vector as a dict of np.uint64 arrays: key[P][464], value[P][464], message[P][464], the globals
         records, bad_partition, keyed, alive (kta_get_size_quantiles; staged messages are flushed first); "vector" is the
         whole u64[P * 3 * 464 + 8]."""
-        return self._size_quantiles(self._lib.kta_get_size_quantiles)
+        return split_size_quantiles(self._read_section("size_quantiles", self._lib.kta_get_size_quantiles), self.n_partitions)
 
     def exchange_size_quantiles(self) -> dict:
         """As size_quantiles(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
-        return self._size_quantiles(self._lib.kta_exchange_size_quantiles)
+        return split_size_quantiles(self._read_section("size_quantiles", self._lib.kta_exchange_size_quantiles), self.n_partitions)
 
     def size_quantiles_result_vector(self) -> Tuple[int, int]:
         """(device pointer, length in u64) of the size-percentile snapshot (for collectives: allreduce_size_quantiles_vector)."""
@@ -683,9 +717,7 @@ class HipMetricHandler:
 
     def compaction(self) -> dict:
         """The live compaction vector as a dict (split_compaction; kta_get_compaction; staged messages are flushed first)."""
-        out = np.zeros(N.KTA_COMPACTION_WORDS * self.n_partitions + N.KTA_COMPACTION_GLOBALS, dtype=np.uint64)
-        self._check(self._lib.kta_get_compaction(self._ctx, _np_ptr(out), out.size))
-        return split_compaction(out, self.n_partitions)
+        return split_compaction(self._read_section("compaction", self._lib.kta_get_compaction), self.n_partitions)
 
     def compaction_info(self) -> dict:
         """Work counters of the compaction pass since creation / reset() (kta_compaction_info)."""
@@ -873,16 +905,9 @@ def _analytics_dict(a: "N.KtaAnalytics", parts: dict) -> dict:
             "value_size_hist": np.array(a.value_size_hist[:], dtype=np.uint64), **parts}
 
 
-def _analytics_vec(vec, P: int) -> np.ndarray:
-    v = np.ascontiguousarray(vec).view(np.uint64) if np.asarray(vec).dtype == np.int64 else np.ascontiguousarray(vec, np.uint64)
-    if v.size != N.KTA_ANALYTICS_HIST + 4 * P:
-        raise ValueError(f"an analytics vector of {P} partitions has {N.KTA_ANALYTICS_HIST + 4 * P} words, not {v.size}")
-    return v
-
-
 def decode_analytics(vec, n_partitions: int) -> dict:
     """kta_decode_analytics: an analytics vector u64[2*34 + 4*P] -> the dict HipMetricHandler.analytics() returns."""
-    v = _analytics_vec(vec, n_partitions)
+    v = _section_vec("analytics", vec, n_partitions)
     a = N.KtaAnalytics()
     out = _analytics_arrays(n_partitions)
     rc = N.load().kta_decode_analytics(_np_ptr(v), n_partitions, C.byref(a), *[_np_ptr(out[k]) for k in _PART_KEYS])
@@ -893,13 +918,7 @@ def decode_analytics(vec, n_partitions: int) -> dict:
 
 def merge_analytics(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
     """kta_merge_analytics, in place on `acc` (uint64 or int64): SUM over the histograms, signed MAX over the extrema."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    a = _analytics_vec(acc, n_partitions)
-    rc = N.load().kta_merge_analytics(_np_ptr(a), _np_ptr(_analytics_vec(other, n_partitions)), n_partitions)
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_analytics")
-    return acc
+    return _merge("analytics", acc, other, n_partitions)
 
 
 def _render(fn, *args) -> str:
@@ -916,7 +935,7 @@ def _render(fn, *args) -> str:
 
 def render_analytics(vec, n_partitions: int) -> str:
     """kta_render_analytics: the section kta-analyzer prints after the report with --librdkafka kta.analytics=1."""
-    v = _analytics_vec(vec, n_partitions)
+    v = _section_vec("analytics", vec, n_partitions)
     return _render(N.load().kta_render_analytics, _np_ptr(v), n_partitions)
 
 
@@ -928,9 +947,7 @@ def analytics_max_partitions() -> int:
 def render_timeline(vec, origin_ms: int, bucket_ms: int, n_buckets: int) -> str:
     """kta_render_timeline: the section kta-analyzer prints after the report with --librdkafka kta.timeline=<width>,
     from a timeline vector (u64[(n_buckets + 3) * 3], or its [n_buckets + 3, 3] shape)."""
-    v = np.ascontiguousarray(np.asarray(vec).reshape(-1)).view(np.uint64)
-    if v.size != (n_buckets + 3) * N.KTA_TIMELINE_COLS:
-        raise ValueError(f"a timeline of {n_buckets} buckets has {(n_buckets + 3) * N.KTA_TIMELINE_COLS} words, not {v.size}")
+    v = _section_vec("timeline", vec, n_buckets)
     return _render(N.load().kta_render_timeline, _np_ptr(v), origin_ms, bucket_ms, n_buckets)
 
 
@@ -939,18 +956,10 @@ def timeline_max_partitions(n_buckets: int, analytics: bool = False) -> int:
     return int(N.load().kta_timeline_max_partitions(N.KTA_FLAG_ANALYTICS if analytics else 0, n_buckets))
 
 
-def _sketch_vec(vec, P: int) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    if v.size != P * N.KTA_SKETCH_REGISTERS:
-        raise ValueError(f"a key sketch of {P} partitions has {P * N.KTA_SKETCH_REGISTERS} words, not {v.size}")
-    return v
-
-
 def estimate_distinct_keys(vec, n_partitions: int) -> Tuple[np.ndarray, float]:
     """kta_key_sketch_estimate: a key sketch (u64[P * 4096] or [P, 4096]) -> (per-partition estimates float64[P], the
     topic-wide estimate of the register-wise max over the partitions)."""
-    v = _sketch_vec(vec, n_partitions)
+    v = _section_vec("key_sketch", vec, n_partitions)
     per = np.zeros(n_partitions, np.float64)
     topic = C.c_double()
     rc = N.load().kta_key_sketch_estimate(_np_ptr(v), n_partitions, _np_ptr(per), C.byref(topic))
@@ -961,22 +970,13 @@ def estimate_distinct_keys(vec, n_partitions: int) -> Tuple[np.ndarray, float]:
 
 def merge_key_sketch(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
     """kta_merge_key_sketch, in place on `acc` (contiguous uint64 / int64): the register-wise max."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    a = _sketch_vec(acc, n_partitions)
-    rc = N.load().kta_merge_key_sketch(_np_ptr(a), _np_ptr(_sketch_vec(other, n_partitions)), n_partitions)
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_key_sketch")
-    return acc
+    return _merge("key_sketch", acc, other, n_partitions)
 
 
 def render_distinct_keys(sketch_vec, counter_vec, n_partitions: int) -> str:
     """kta_render_distinct_keys: the section kta-analyzer prints after the report with --librdkafka kta.distinct_keys=1,
     from a key sketch and the counter vector u64[P * 7 + 8] of the same records."""
-    v = _sketch_vec(sketch_vec, n_partitions)
-    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
-    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
-        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    v, c = _section_vec("key_sketch", sketch_vec, n_partitions), _counter_vec(counter_vec, n_partitions)
     return _render(N.load().kta_render_distinct_keys, _np_ptr(v), _np_ptr(c), n_partitions)
 
 
@@ -984,18 +984,10 @@ HOT_EXEMPLAR_DTYPE = np.dtype([("hash", np.uint32), ("key_len", np.uint32), ("va
                                ("bytes", np.uint8, (N.KTA_HOT_EXEMPLAR_BYTES,))])
 
 
-def _hot_vec(vec) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    if v.size != N.KTA_HOT_VECTOR_WORDS:
-        raise ValueError(f"a hot-key vector has {N.KTA_HOT_VECTOR_WORDS} words, not {v.size}")
-    return v
-
-
 def recover_hot_keys(vec, max_keys: int = N.KTA_HOT_MAX_REPORTED) -> Tuple[list, int]:
     """kta_hot_keys_recover: a hot-key vector -> ([(hash, upper, lower), ...] by upper descending then hash, at most
     max_keys of them, the keyed records)."""
-    v = _hot_vec(vec)
+    v = _section_vec("hot_keys", vec)
     out = (N.KtaHotKey * max(int(max_keys), 1))()
     n, keyed = C.c_uint32(), C.c_uint64()
     rc = N.load().kta_hot_keys_recover(_np_ptr(v), int(max_keys), C.byref(out), C.byref(n), C.byref(keyed))
@@ -1006,18 +998,13 @@ def recover_hot_keys(vec, max_keys: int = N.KTA_HOT_MAX_REPORTED) -> Tuple[list,
 
 def merge_hot_keys(acc: np.ndarray, other) -> np.ndarray:
     """kta_merge_hot_keys, in place on `acc` (contiguous uint64 / int64): the word-wise sum."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    rc = N.load().kta_merge_hot_keys(_np_ptr(_hot_vec(acc)), _np_ptr(_hot_vec(other)))
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_hot_keys")
-    return acc
+    return _merge("hot_keys", acc, other)
 
 
 def render_hot_keys(vec, exemplars=None, max_keys: int = 10) -> str:
     """kta_render_hot_keys: the section kta-analyzer prints last with --librdkafka kta.hot_keys=K, from a hot-key vector
     and an exemplar table (HipMetricHandler.hot_key_exemplars(), or None)."""
-    v = _hot_vec(vec)
+    v = _section_vec("hot_keys", vec)
     ex = None
     if exemplars is not None:
         ex = np.ascontiguousarray(exemplars, dtype=HOT_EXEMPLAR_DTYPE)
@@ -1026,19 +1013,11 @@ def render_hot_keys(vec, exemplars=None, max_keys: int = 10) -> str:
     return _render(N.load().kta_render_hot_keys, _np_ptr(v), _np_ptr(ex) if ex is not None else None, int(max_keys))
 
 
-def _ts_order_vec(vec, P: int) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    if v.size != 3 * P + 64:
-        raise ValueError(f"a timestamp-order vector of {P} partitions has {3 * P + 64} words, not {v.size}")
-    return v
-
-
 def split_ts_order(vec, n_partitions: int) -> dict:
     """A timestamp-order vector u64[3 P + 64] as a dict: late[P], late_ms_sum[P], hist[63], timed, max_late_ms[P], and the
     vector itself under "vector"."""
     P = n_partitions
-    v = _ts_order_vec(vec, P)
+    v = _section_vec("ts_order", vec, P)
     return {"late": v[0:2 * P:2].copy(), "late_ms_sum": v[1:2 * P:2].copy(), "hist": v[2 * P:2 * P + N.KTA_TS_ORDER_HIST].copy(),
             "timed": int(v[2 * P + N.KTA_TS_ORDER_HIST]), "max_late_ms": v[2 * P + 64:].copy(), "vector": v}
 
@@ -1046,76 +1025,42 @@ def split_ts_order(vec, n_partitions: int) -> dict:
 def merge_ts_order(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
     """kta_merge_ts_order, in place on `acc` (contiguous uint64 / int64): SUM over the first 2 P + 64 words, MAX over the
     last P.  Exact when every partition's records went through one of the two contexts, in order."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    rc = N.load().kta_merge_ts_order(_np_ptr(_ts_order_vec(acc, n_partitions)), _np_ptr(_ts_order_vec(other, n_partitions)), n_partitions)
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_ts_order")
-    return acc
+    return _merge("ts_order", acc, other, n_partitions)
 
 
 def render_ts_order(vec, counter_vec, n_partitions: int) -> str:
     """kta_render_ts_order: the section kta-analyzer prints with --librdkafka kta.ts_order=1, from a timestamp-order vector
     and the counter vector u64[P * 7 + 8] of the same records."""
-    v = _ts_order_vec(vec, n_partitions)
-    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
-    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
-        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    v, c = _section_vec("ts_order", vec, n_partitions), _counter_vec(counter_vec, n_partitions)
     return _render(N.load().kta_render_ts_order, _np_ptr(v), _np_ptr(c), n_partitions)
-
-
-def _partitioner_vec(vec, P: int, Q: int) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    if v.size != 2 * P + 2 * Q:
-        raise ValueError(f"a partitioner vector of {P} partitions and {Q} targets has {2 * P + 2 * Q} words, not {v.size}")
-    return v
 
 
 def split_partitioner(vec, n_partitions: int, repartition: int) -> dict:
     """A partitioner vector u64[2 P + 2 Q] as a dict: checked[P], placed[P], target_records[Q], target_bytes[Q], and the
     vector itself under "vector"."""
     P = n_partitions
-    v = _partitioner_vec(vec, P, repartition)
+    v = _section_vec("partitioner", vec, P, repartition)
     return {"checked": v[0:2 * P:2].copy(), "placed": v[1:2 * P:2].copy(), "target_records": v[2 * P::2].copy(),
             "target_bytes": v[2 * P + 1::2].copy(), "vector": v}
 
 
 def merge_partitioner(acc: np.ndarray, other, n_partitions: int, repartition: int) -> np.ndarray:
     """kta_merge_partitioner, in place on `acc` (contiguous uint64 / int64): every word a sum."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    rc = N.load().kta_merge_partitioner(_np_ptr(_partitioner_vec(acc, n_partitions, repartition)),
-                                        _np_ptr(_partitioner_vec(other, n_partitions, repartition)), n_partitions, repartition)
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_partitioner")
-    return acc
+    return _merge("partitioner", acc, other, n_partitions, repartition)
 
 
 def render_partitioner(vec, counter_vec, n_partitions: int, repartition: int) -> str:
     """kta_render_partitioner: the section kta-analyzer prints with --librdkafka kta.partitioner=murmur2, from a partitioner
     vector and the counter vector u64[P * 7 + 8] of the same records."""
-    v = _partitioner_vec(vec, n_partitions, repartition)
-    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
-    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
-        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    v, c = _section_vec("partitioner", vec, n_partitions, repartition), _counter_vec(counter_vec, n_partitions)
     return _render(N.load().kta_render_partitioner, _np_ptr(v), _np_ptr(c), n_partitions, repartition)
-
-
-def _size_quantiles_vec(vec, P: int) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    words = P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS
-    if v.size != words:
-        raise ValueError(f"a size vector of {P} partitions has {words} words, not {v.size}")
-    return v
 
 
 def split_size_quantiles(vec, n_partitions: int) -> dict:
     """A size vector u64[P * 3 * 464 + 8] as a dict: key[P][464], value[P][464], message[P][464], the globals records,
     bad_partition, keyed, alive, and the vector itself under "vector"."""
     P = n_partitions
-    v = _size_quantiles_vec(vec, P)
+    v = _section_vec("size_quantiles", vec, P)
     h = v[:P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS].reshape(P, N.KTA_SIZE_QUANTITIES, N.KTA_SIZE_BINS)
     g = v[P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS:]
     return {"key": h[:, 0, :].copy(), "value": h[:, 1, :].copy(), "message": h[:, 2, :].copy(), "records": int(g[0]),
@@ -1124,22 +1069,13 @@ def split_size_quantiles(vec, n_partitions: int) -> dict:
 
 def merge_size_quantiles(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
     """kta_merge_size_quantiles, in place on `acc` (contiguous uint64 / int64): every word a sum."""
-    if acc.dtype not in (np.uint64, np.int64) or not acc.flags.c_contiguous:
-        raise TypeError("acc must be a contiguous uint64 / int64 array")
-    rc = N.load().kta_merge_size_quantiles(_np_ptr(_size_quantiles_vec(acc, n_partitions)), _np_ptr(_size_quantiles_vec(other, n_partitions)),
-                                           n_partitions)
-    if rc != N.KTA_OK:
-        raise KtaError(rc, "kta_merge_size_quantiles")
-    return acc
+    return _merge("size_quantiles", acc, other, n_partitions)
 
 
 def render_size_percentiles(vec, counter_vec, n_partitions: int) -> str:
     """kta_render_size_percentiles: the section kta-analyzer prints with --librdkafka kta.percentiles=1, from a size vector
     and the counter vector u64[P * 7 + 8] of the same records (KtaError when the two do not describe the same records)."""
-    v = _size_quantiles_vec(vec, n_partitions)
-    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
-    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
-        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    v, c = _section_vec("size_quantiles", vec, n_partitions), _counter_vec(counter_vec, n_partitions)
     return _render(N.load().kta_render_size_percentiles, _np_ptr(v), _np_ptr(c), n_partitions)
 
 
@@ -1192,21 +1128,12 @@ class _CompactionReplay:
 _COMPACTION_GLOBALS = ("replayed", "unkeyed", "unknown", "live_outside", "tombstones_outside")
 
 
-def _compaction_vec(vec, P: int) -> np.ndarray:
-    a = np.ascontiguousarray(np.asarray(vec).reshape(-1))
-    v = a.view(np.uint64) if a.dtype == np.int64 else np.ascontiguousarray(a, np.uint64)
-    words = N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS
-    if v.size != words:
-        raise ValueError(f"a compaction vector of {P} partitions has {words} words, not {v.size}")
-    return v
-
-
 def split_compaction(vec, n_partitions: int) -> dict:
     """A compaction vector u64[5 P + 6] as a dict: live_records[P], live_key_bytes[P], live_value_bytes[P],
     tombstone_records[P], tombstone_key_bytes[P], the globals replayed, unkeyed, unknown, live_outside, tombstones_outside as
     ints, and the vector itself under "vector"."""
     P, W = n_partitions, N.KTA_COMPACTION_WORDS
-    v = _compaction_vec(vec, P)
+    v = _section_vec("compaction", vec, P)
     d = {name: v[k:W * P:W].copy() for k, name in enumerate(("live_records", "live_key_bytes", "live_value_bytes", "tombstone_records",
                                                               "tombstone_key_bytes"))}
     d.update({name: int(v[W * P + k]) for k, name in enumerate(_COMPACTION_GLOBALS)})
@@ -1218,10 +1145,7 @@ def render_compaction(vec, counter_vec, n_partitions: int) -> str:
     """kta_render_compaction: the section kta-analyzer prints with -c --librdkafka kta.compaction=1, from a compaction vector
     and the first pass's counter vector u64[P * 7 + 8].  KtaError (KTA_ERR_INVALID) when the replay did not match the first
     pass; the section that says so is the error's `text`."""
-    v = _compaction_vec(vec, n_partitions)
-    c = np.ascontiguousarray(np.asarray(counter_vec).reshape(-1)).view(np.uint64)
-    if c.size != n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS:
-        raise ValueError(f"a counter vector of {n_partitions} partitions has {n_partitions * N.KTA_NCOUNTERS + N.KTA_NGLOBALS} words")
+    v, c = _section_vec("compaction", vec, n_partitions), _counter_vec(counter_vec, n_partitions)
     fn = N.load().kta_render_compaction
     n = C.c_size_t()
     fn(_np_ptr(v), _np_ptr(c), n_partitions, None, 0, C.byref(n))
@@ -1374,7 +1298,7 @@ def compact_delete_whatif(seg_vec, kept_vec, comp_vec, n_partitions: int, rows_p
     compaction vector: u64[P + 1][10], a row per partition and one for the topic, columns COMPACT_DELETE_COLUMNS; -1 turns
     a rule off.  KtaError (KTA_ERR_INVALID) for bad arguments and when the replay did not match the first pass."""
     P, M = int(n_partitions), int(rows_per_partition)
-    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _compaction_vec(comp_vec, P)
+    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _section_vec("compaction", comp_vec, P)
     out = np.zeros((P + 1, len(COMPACT_DELETE_COLUMNS)), np.uint64)
     rc = N.load().kta_compact_delete_whatif(_np_ptr(s), _np_ptr(k), _np_ptr(c), P, M, int(now_ms), int(retention_ms), int(retention_bytes),
                                             _np_ptr(out), out.size)
@@ -1388,7 +1312,7 @@ def render_compact_delete(seg_vec, kept_vec, comp_vec, n_partitions: int, rows_p
     """kta_render_compact_delete: the section kta-analyzer prints with kta.compact_delete=1.  KtaError (KTA_ERR_INVALID) when
     the replay did not match the first pass; the section that says so is the error's `text` ("" for other bad arguments)."""
     P, M = int(n_partitions), int(rows_per_partition)
-    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _compaction_vec(comp_vec, P)
+    s, k, c = _segments_vec(seg_vec, P, M), _segments_vec(kept_vec, P, M), _section_vec("compaction", comp_vec, P)
     fn = N.load().kta_render_compact_delete
     args = (_np_ptr(s), _np_ptr(k), _np_ptr(c), P, M, int(now_ms), int(retention_ms), int(retention_bytes))
     n = C.c_size_t()

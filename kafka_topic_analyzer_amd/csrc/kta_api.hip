@@ -462,21 +462,6 @@ int run_compact_delete(kta_ctx *ctx, const kta_batch *c, const kta_internal_colu
     return KTA_OK;
 }
 
-// The live kept vector as kta_set_compact_delete, kta_reset and kta_compaction_replay(ctx, 1) leave it: zero but for the
-// configuration globals.
-int clear_kept(kta_ctx *ctx)
-{
-    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
-    const uint64_t cfg[3] = {ctx->seg_S, ctx->seg_M, ctx->seg_overhead};
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_kept.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
-    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_kept.get() + kta::segments_globals_at(ctx->P, ctx->seg_M) + kta::kSegGlobalS, cfg, sizeof cfg,
-                                hipMemcpyHostToDevice, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (cfg is this frame's)
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_cd_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
-    ctx->cd_launches = ctx->cd_chunks = 0;
-    return KTA_OK;
-}
-
 // A batch of the replay (kta_compaction_replay): the compaction pass — with kta_set_compact_delete, the kept rows behind it —
 // and nothing else, whatever `which` says.
 int run_replayed_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base_seq)
@@ -538,20 +523,6 @@ int run_segments(kta_ctx *ctx, const kta_internal_columns &rb, uint64_t n)
         ctx->seg_last_chunk = chunk;
         at += take;
     }
-    return KTA_OK;
-}
-
-// The live segment vector as kta_set_segments and kta_reset leave it: zero but for the configuration globals.
-int clear_segments(kta_ctx *ctx)
-{
-    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
-    const uint64_t cfg[3] = {ctx->seg_S, ctx->seg_M, ctx->seg_overhead};
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_seg.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
-    KTA_HIP(ctx, hipMemcpyAsync(ctx->d_seg.get() + kta::segments_globals_at(ctx->P, ctx->seg_M) + kta::kSegGlobalS, cfg, sizeof cfg,
-                                hipMemcpyHostToDevice, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (cfg is this frame's)
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_seg_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
-    ctx->seg_launches = ctx->seg_chunks = ctx->seg_last_chunk = 0;
     return KTA_OK;
 }
 
@@ -877,50 +848,249 @@ int run_device_batch(kta_ctx *ctx, const kta_batch *c, uint64_t n, uint64_t base
     return run_filtered_batch(ctx, c, n, base_seq, which);
 }
 
+// ---- result sections ------------------------------------------------------------------------------------------------
+// The shape of a section's vector (kta_internal.h has the table): its length and the SUM prefix of its merge rule, as
+// functions of the section's own shape.  The context's table below and the context-free kta_merge_* both read them here.
+struct Shape {
+    size_t words, sum_words;
+    bool max_signed;
+};
+Shape all_sum(size_t words) { return Shape{words, words, false}; }
+Shape counters_shape(uint32_t P)
+{
+    const size_t nc = (size_t)P * KTA_NCOUNTERS;
+    return Shape{nc + KTA_NGLOBALS, nc + KTA_NSUM_GLOBALS, true};
+}
+Shape analytics_shape(uint32_t P) { return Shape{kta::analytics_len(P), kta::kAnalyticsHist, true}; }
+Shape timeline_shape(uint32_t n_buckets) { return all_sum(kta::timeline_len(n_buckets)); }
+Shape key_sketch_shape(uint32_t P) { return Shape{(size_t)P * kta::kSketchRegs, 0, false}; }
+Shape hot_keys_shape() { return all_sum(KTA_HOT_VECTOR_WORDS); }
+Shape ts_order_shape(uint32_t P) { return Shape{kta::ts_order_len(P), 2 * (size_t)P + 64, true}; }
+Shape partitioner_shape(uint32_t P, uint32_t Q) { return all_sum(kta::partitioner_len(P, Q)); }
+Shape size_quantiles_shape(uint32_t P) { return all_sum(kta::size_quantiles_len(P)); }
+// (the MAX suffix is S, M, overhead and the two zero words: equal on every rank, so the maximum is each rank's own; the
+// kept vector has the segments' shape)
+Shape segments_shape(uint32_t P, uint32_t M)
+{
+    const size_t words = kta::segments_len(P, M);
+    return Shape{words, words - kta::kSegGlobals + kta::kSegGlobalS, false};
+}
+Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
+
+// what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
+static_assert(kta::kAnalyticsHist == 2 * KTA_HIST_BUCKETS, "the two histograms: kta_kernels.h and kta_hip.h");
+static_assert(kta::kTimelineCols == KTA_TIMELINE_COLS && kta::kSketchRegs == KTA_SKETCH_REGISTERS, "kta_kernels.h and kta_hip.h");
+static_assert(KTA_HOT_VECTOR_WORDS == 2 * 1024 * 23, "the hot-key vector: kta_internal.h's table and kta_hip.h");
+static_assert(KTA_TS_ORDER_HIST + 1 == 64, "the 64 words between a timestamp-order vector's sums and its maxima: hist[63] and timed");
+static_assert(kta::kSizePartitionWords == KTA_SIZE_QUANTITIES * KTA_SIZE_BINS && kta::kSizeGlobals == KTA_SIZE_GLOBALS, "kta_size_bins.h and kta_hip.h");
+static_assert(kta::kCompactionWords == KTA_COMPACTION_WORDS && kta::kCompactionGlobals == KTA_COMPACTION_GLOBALS, "kta_compaction.h and kta_hip.h");
+static_assert(kta::kRetWords == KTA_RETENTION_WORDS, "the what-if's row is said twice: kta_segments.h and kta_hip.h");
+static_assert(kta::kCdWords == KTA_COMPACT_DELETE_WORDS, "the what-if's row is said twice: kta_compact_delete.h and kta_hip.h");
+
+// One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
+// and out point at the context's owners, allocated or not.
+struct Section {
+    bool on;
+    DeviceBuf<uint64_t> *live;   // the live accumulator; null: it is no u64 vector (the key sketch's u32 registers)
+    DeviceBuf<uint64_t> *out;    // the snapshot kta_finish_device takes; null: the section is live only
+    Shape shape;                 // as the section is configured now
+    bool zero_is_empty;          // reset_state clears the live vector with zeros; false: by a line of its own there
+    const char *noun;            // check_words: "the <noun> has N u64 words, not M"
+    const char *off;             // kta_last_error of every entry point of the section while it is off
+};
+
+void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
+{
+    const uint32_t P = ctx->P;
+    s[KTA_RV_COUNTERS] = Section{true, &ctx->d_vec, &ctx->d_vec_out, counters_shape(P), false, "counter vector", ""};
+    s[KTA_RV_ANALYTICS] = Section{ctx->analytics, &ctx->d_avec, &ctx->d_avec_out, analytics_shape(P), false, "analytics vector",
+                                  "context was created without KTA_FLAG_ANALYTICS"};
+    s[KTA_RV_TIMELINE] = Section{ctx->timeline, &ctx->d_tvec, &ctx->d_tvec_out, timeline_shape(ctx->tl.n_buckets), true, "timeline",
+                                 "the context has no timeline (kta_set_timeline)"};
+    s[KTA_RV_KEY_SKETCH] = Section{ctx->sketch, nullptr, &ctx->d_sketch_out, key_sketch_shape(P), false, "key sketch",
+                                   "context was created without KTA_FLAG_KEY_SKETCH"};
+    s[KTA_RV_HOT_KEYS] = Section{ctx->hot, &ctx->d_hot, &ctx->d_hot_out, hot_keys_shape(), true, "hot-key vector",
+                                 "context was created without KTA_FLAG_HOT_KEYS"};
+    s[KTA_RV_TS_ORDER] = Section{ctx->tso, &ctx->d_tso, &ctx->d_tso_out, ts_order_shape(P), true, "timestamp-order vector",
+                                 "context was created without KTA_FLAG_TS_ORDER"};
+    s[KTA_RV_PARTITIONER] = Section{ctx->part, &ctx->d_part, &ctx->d_part_out, partitioner_shape(P, ctx->part_q), true, "partitioner vector",
+                                    "context was created without KTA_FLAG_PARTITIONER"};
+    s[KTA_RV_SIZE_QUANTILES] = Section{ctx->sizeq, &ctx->d_sizeq, &ctx->d_sizeq_out, size_quantiles_shape(P), true, "size-percentile vector",
+                                       "context was created without KTA_FLAG_SIZE_QUANTILES"};
+    s[KTA_RV_SEGMENTS] = Section{ctx->seg, &ctx->d_seg, &ctx->d_seg_out, segments_shape(P, ctx->seg_M), false, "segment vector",
+                                 "the context has no segments (kta_set_segments)"};
+    s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
+                                    "context was created without KTA_FLAG_COMPACTION"};
+    s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
+                              "the context has no compact,delete what-if (kta_set_compact_delete)"};
+}
+
+Section section(kta_ctx *ctx, int kind)
+{
+    Section s[KTA_SEC_KINDS];
+    sections_of(ctx, s);
+    return s[kind];
+}
+
+// the refusal of an entry point whose section is off
+int section_off(kta_ctx *ctx, int kind) { return fail(ctx, KTA_ERR_INVALID, section(ctx, kind).off); }
+
+// `words` u64 words of a vector on the device (a live accumulator or a snapshot), once the compute stream has reached them.
+int read_words(kta_ctx *ctx, const uint64_t *d_src, uint64_t *host, size_t words)
+{
+    KTA_HIP(ctx, hipMemcpyAsync(host, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    return KTA_OK;
+}
+
+// the caller's buffer for the vector called `name` has its length
+int check_words(kta_ctx *ctx, const char *name, size_t words, size_t n_u64)
+{
+    if (n_u64 == words) return KTA_OK;
+    return fail(ctx, KTA_ERR_INVALID, std::string("the ") + name + " has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
+}
+
+// How every read-back of a section into the caller's u64[n_u64] begins: the arguments, the section on, the buffer's
+// length, the device.  *s: the section's row.
+int begin_read(kta_ctx *ctx, int kind, const uint64_t *out, size_t n_u64, Section *s)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    *s = section(ctx, kind);
+    if (!s->on) return fail(ctx, KTA_ERR_INVALID, s->off);
+    int rc = check_words(ctx, s->noun, s->shape.words, n_u64);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    return KTA_OK;
+}
+
+// kta_get_<section>: the live vector, staged messages flushed first
+int get_section(kta_ctx *ctx, int kind, uint64_t *out, size_t n_u64)
+{
+    Section s;
+    int rc = begin_read(ctx, kind, out, n_u64, &s);
+    if (rc != KTA_OK) return rc;
+    rc = kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    return read_words(ctx, s.live->get(), out, n_u64);
+}
+
+// kta_exchange_<section>: the snapshot as it is (nothing is flushed)
+int exchange_section(kta_ctx *ctx, int kind, uint64_t *out, size_t n_u64)
+{
+    Section s;
+    int rc = begin_read(ctx, kind, out, n_u64, &s);
+    return rc != KTA_OK ? rc : read_words(ctx, s.out->get(), out, n_u64);
+}
+
+// kta_<section>_result_vector (snapshot) and kta_<section>_vector (the live vector): the device pointer and the length
+int section_vector(kta_ctx *ctx, int kind, bool snapshot, void **device_ptr, size_t *n_u64)
+{
+    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
+    const Section s = section(ctx, kind);
+    if (!s.on) return fail(ctx, KTA_ERR_INVALID, s.off);
+    *device_ptr = (snapshot ? s.out : s.live)->get();
+    *n_u64 = s.shape.words;
+    return KTA_OK;
+}
+
+// kta_merge_<section>: acc = acc (+) other by the rule of the result vectors, SUM over [0, sum_words), MAX over the rest
+int merge_section(uint64_t *acc, const uint64_t *other, bool bounds_ok, const Shape &sh)
+{
+    if (!acc || !other || !bounds_ok) return KTA_ERR_INVALID;
+    for (size_t i = 0; i < sh.sum_words; i++) acc[i] += other[i];
+    for (size_t i = sh.sum_words; i < sh.words; i++)
+        if (sh.max_signed ? (int64_t)other[i] > (int64_t)acc[i] : other[i] > acc[i]) acc[i] = other[i];
+    return KTA_OK;
+}
+
+// Both vectors of a section cleared, and (alloc_section) allocated at `words` first: what kta_create does for every
+// section that is on and a configuration call for the one it gives another shape.  Each owner is released before either
+// is allocated again, after the compute stream has drained.
+int clear_section(kta_ctx *ctx, const Section &s, size_t words)
+{
+    if (s.live) KTA_HIP(ctx, hipMemsetAsync(s.live->get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    if (s.out) KTA_HIP(ctx, hipMemsetAsync(s.out->get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    return KTA_OK;
+}
+int alloc_section(kta_ctx *ctx, const Section &s, size_t words)
+{
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    if (s.live) s.live->reset();
+    if (s.out) s.out->reset();
+    const std::string what = std::string("allocating the ") + s.noun;   // (a failure names the section, as its own lines once did)
+    if (s.live) KTA_HIP_AS(ctx, s.live->alloc(words), what.c_str());
+    if (s.out) KTA_HIP_AS(ctx, s.out->alloc(words), (what + "'s snapshot").c_str());
+    return clear_section(ctx, s, words);
+}
+
+// A live vector of the segments' shape (the segment vector, the kept vector) as its configuration call, kta_reset and,
+// for the kept vector, kta_compaction_replay(ctx, 1) leave it: zero but for the configuration globals; its pass's four
+// work counters zero.
+int clear_segment_vector(kta_ctx *ctx, uint64_t *vec, uint64_t *stats)
+{
+    const uint64_t cfg[3] = {ctx->seg_S, ctx->seg_M, ctx->seg_overhead};
+    KTA_HIP(ctx, hipMemsetAsync(vec, 0, kta::segments_len(ctx->P, ctx->seg_M) * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, hipMemcpyAsync(vec + kta::segments_globals_at(ctx->P, ctx->seg_M) + kta::kSegGlobalS, cfg, sizeof cfg, hipMemcpyHostToDevice,
+                                ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));   // (cfg is this frame's)
+    KTA_HIP(ctx, hipMemsetAsync(stats, 0, 4 * sizeof(uint64_t), ctx->s_compute));
+    return KTA_OK;
+}
+int clear_segments(kta_ctx *ctx)
+{
+    ctx->seg_launches = ctx->seg_chunks = ctx->seg_last_chunk = 0;
+    return clear_segment_vector(ctx, ctx->d_seg.get(), ctx->d_seg_stats.get());
+}
+int clear_kept(kta_ctx *ctx)
+{
+    ctx->cd_launches = ctx->cd_chunks = 0;
+    return clear_segment_vector(ctx, ctx->d_kept.get(), ctx->d_cd_stats.get());
+}
+
 int reset_state(kta_ctx *ctx)
 {
-    KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec.get(), ctx->P, ctx->d_avec.get(), ctx->s_compute));
-    if (ctx->timeline)   // the configuration stays
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec.get(), 0, kta::timeline_len(ctx->tl.n_buckets) * sizeof(uint64_t), ctx->s_compute));
-    if (ctx->sketch) {
+    // Every live vector whose empty value is zeros; the configurations (timeline, Q, segments, forced slices) stay.  Below:
+    // the vectors with another empty value, and what a section keeps beside its vector.
+    Section sec[KTA_SEC_KINDS];
+    sections_of(ctx, sec);
+    for (const Section &s : sec)
+        if (s.on && s.live && s.zero_is_empty)
+            KTA_HIP(ctx, hipMemsetAsync(s.live->get(), 0, s.shape.words * sizeof(uint64_t), ctx->s_compute));
+    KTA_HIP(ctx, kta::launch_init_vector(ctx->d_vec.get(), ctx->P, ctx->d_avec.get(), ctx->s_compute));   // counters, analytics: the extrema
+    if (ctx->sketch) {                  // (the live registers are u32)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch.get(), 0, (size_t)ctx->P * kta::kSketchRegs * sizeof(uint32_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sketch_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->sketch_launches = 0;
     }
     if (ctx->hot) {
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot.get(), 0, KTA_HOT_VECTOR_WORDS * sizeof(uint64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_slots.get(), 0, kHotSlotsN * sizeof(kta_hot_exemplar), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hot_stats.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
         ctx->hot_launches = ctx->hot_workgroups = 0;
     }
     if (ctx->tso) {                     // (hi: every byte 0xFF is -1, none)
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso.get(), 0, kta::ts_order_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_hi.get(), 0xFF, (size_t)ctx->P * sizeof(int64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_tso_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->tso_launches = ctx->tso_chunks = ctx->tso_last_chunk = 0;
     }
-    if (ctx->seg) {                     // (the configuration stays)
+    if (ctx->seg) {                     // (its globals hold the configuration)
         int rc = clear_segments(ctx);
         if (rc != KTA_OK) return rc;
     }
-    if (ctx->part) {                    // (Q stays)
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_part.get(), 0, kta::partitioner_len(ctx->P, ctx->part_q) * sizeof(uint64_t), ctx->s_compute));
+    if (ctx->part) {
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->part_launches = ctx->part_workgroups = 0;
     }
     if (ctx->comp) {
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp.get(), 0, kta::compaction_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->comp_launches = ctx->comp_workgroups = 0;
         ctx->comp_replay = false;
         ctx->comp_saved_seq = 0;
     }
-    if (ctx->cd) {                      // (the switch stays)
+    if (ctx->cd) {                      // (the switch stays; likewise)
         int rc = clear_kept(ctx);
         if (rc != KTA_OK) return rc;
     }
-    if (ctx->sizeq) {                   // (a forced slice stays)
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_sizeq.get(), 0, kta::size_quantiles_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+    if (ctx->sizeq) {
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_sizeq_stats.get(), 0, kSizeqStatWords * sizeof(uint64_t), ctx->s_compute));
         ctx->sizeq_last_workgroups = 0;
     }
@@ -949,63 +1119,16 @@ int reset_state(kta_ctx *ctx)
     return KTA_OK;
 }
 
-// One snapshot as a *_result_vector entry point hands it out.
-int hand_out(const ResultVector &v, void **device_ptr, size_t *n_u64)
-{
-    *device_ptr = v.out;
-    *n_u64 = v.words;
-    return KTA_OK;
-}
-
-// `words` u64 words of a vector on the device (a live accumulator or a snapshot), once the compute stream has reached them.
-int read_words(kta_ctx *ctx, const uint64_t *d_src, uint64_t *host, size_t words)
-{
-    KTA_HIP(ctx, hipMemcpyAsync(host, d_src, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->s_compute));
-    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-    return KTA_OK;
-}
-
-// the caller's buffer for the vector called `name` has its length
-int check_words(kta_ctx *ctx, const char *name, size_t words, size_t n_u64)
-{
-    if (n_u64 == words) return KTA_OK;
-    return fail(ctx, KTA_ERR_INVALID, std::string("the ") + name + " has " + std::to_string(words) + " u64 words, not " + std::to_string(n_u64));
-}
-
-// acc = acc (+) other by the rule of the result vectors: SUM over [0, sum_words), MAX over the rest
-void merge_words(uint64_t *acc, const uint64_t *other, size_t words, size_t sum_words, bool max_signed)
-{
-    for (size_t i = 0; i < sum_words; i++) acc[i] += other[i];
-    for (size_t i = sum_words; i < words; i++)
-        if (max_signed ? (int64_t)other[i] > (int64_t)acc[i] : other[i] > acc[i]) acc[i] = other[i];
-}
-
 } // namespace
 
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
 {
-    const size_t nc = (size_t)ctx->P * KTA_NCOUNTERS, alen = kta::analytics_len(ctx->P);
-    const size_t tlen = ctx->timeline ? kta::timeline_len(ctx->tl.n_buckets) : 0;
-    rv[KTA_RV_COUNTERS] = ResultVector{ctx->d_vec_out.get(), nc + KTA_NGLOBALS, nc + KTA_NSUM_GLOBALS, true};
-    rv[KTA_RV_ANALYTICS] = ResultVector{ctx->d_avec_out.get(), ctx->analytics ? alen : 0, ctx->analytics ? kta::kAnalyticsHist : 0, true};
-    rv[KTA_RV_TIMELINE] = ResultVector{ctx->timeline ? ctx->d_tvec_out.get() : nullptr, tlen, tlen, false};
-    rv[KTA_RV_KEY_SKETCH] = ResultVector{ctx->d_sketch_out.get(), ctx->sketch ? (size_t)ctx->P * kta::kSketchRegs : 0, 0, false};
-    rv[KTA_RV_HOT_KEYS] = ResultVector{ctx->d_hot_out.get(), ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, ctx->hot ? (size_t)KTA_HOT_VECTOR_WORDS : 0, false};
-    rv[KTA_RV_TS_ORDER] = ResultVector{ctx->d_tso_out.get(), ctx->tso ? kta::ts_order_len(ctx->P) : 0, ctx->tso ? 2 * (size_t)ctx->P + 64 : 0, true};
-    const size_t plen = ctx->part ? kta::partitioner_len(ctx->P, ctx->part_q) : 0;
-    rv[KTA_RV_PARTITIONER] = ResultVector{ctx->part ? ctx->d_part_out.get() : nullptr, plen, plen, false};
-    const size_t qlen = ctx->sizeq ? kta::size_quantiles_len(ctx->P) : 0;
-    rv[KTA_RV_SIZE_QUANTILES] = ResultVector{ctx->sizeq ? ctx->d_sizeq_out.get() : nullptr, qlen, qlen, false};
-    // (the MAX suffix is S, M, overhead and the two zero words: equal on every rank, so the maximum is each rank's own)
-    const size_t slen = ctx->seg ? kta::segments_len(ctx->P, ctx->seg_M) : 0;
-    rv[KTA_RV_SEGMENTS] = ResultVector{ctx->seg ? ctx->d_seg_out.get() : nullptr, slen, ctx->seg ? slen - kta::kSegGlobals + kta::kSegGlobalS : 0, false};
-}
-
-static ResultVector result_vector(kta_ctx *ctx, int kind)
-{
-    ResultVector rv[KTA_RV_KINDS];
-    kta_internal_result_vectors(ctx, rv);
-    return rv[kind];
+    Section sec[KTA_SEC_KINDS];
+    sections_of(ctx, sec);
+    for (int k = 0; k < KTA_RV_KINDS; k++) {
+        const Section &s = sec[k];
+        rv[k] = s.on ? ResultVector{s.out->get(), s.shape.words, s.shape.sum_words, s.shape.max_signed} : ResultVector{nullptr, 0, 0, false};
+    }
 }
 
 extern "C" {
@@ -1028,30 +1151,40 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
 {
     if (!cfg || !out) return fail(nullptr, KTA_ERR_INVALID, "kta_create: null argument");
     *out = nullptr;
-    // (before the general bound, which is the same number today: the message names the pass that sets this one)
-    if ((cfg->flags & KTA_FLAG_PARTITIONER) && cfg->n_partitions > kta_partitioner_max_partitions())
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_PARTITIONER admits at most " + std::to_string(kta_partitioner_max_partitions()) +
-                                                  " partitions (the pass keeps its counters in LDS)");
-    if ((cfg->flags & KTA_FLAG_SIZE_QUANTILES) && cfg->n_partitions > kta_size_quantiles_max_partitions())
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_SIZE_QUANTILES admits at most " + std::to_string(kta_size_quantiles_max_partitions()) +
-                                                  " partitions (every slice of 28 partitions streams the batch again)");
-    if ((cfg->flags & KTA_FLAG_COMPACTION) && !cfg->count_alive_keys)
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_COMPACTION needs count_alive_keys (the pass reads the last-writer table)");
-    if ((cfg->flags & KTA_FLAG_COMPACTION) && cfg->n_partitions > kta_compaction_max_partitions())
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_COMPACTION admits at most " + std::to_string(kta_compaction_max_partitions()) +
-                                                  " partitions (the pass keeps 32 B per partition in LDS)");
-    if (cfg->n_partitions <= 0 || cfg->n_partitions > 4096)
-        return fail(nullptr, KTA_ERR_INVALID, "n_partitions must be in [1, 4096]");
-    if ((cfg->flags & KTA_FLAG_ANALYTICS) && cfg->n_partitions > kta_analytics_max_partitions())
-        return fail(nullptr, KTA_ERR_INVALID,
-                    "KTA_FLAG_ANALYTICS admits at most " + std::to_string(kta_analytics_max_partitions()) +
-                        " partitions (the analytics scan keeps 4 extrema per partition in LDS)");
-    if ((cfg->flags & KTA_FLAG_KEY_SKETCH) && cfg->n_partitions > KTA_SKETCH_MAX_PARTITIONS)
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_KEY_SKETCH admits at most " + std::to_string(KTA_SKETCH_MAX_PARTITIONS) +
-                                                  " partitions (a u64 snapshot of 4096 registers per partition)");
-    if ((cfg->flags & KTA_FLAG_TS_ORDER) && cfg->n_partitions > kta_ts_order_max_partitions())
-        return fail(nullptr, KTA_ERR_INVALID, "KTA_FLAG_TS_ORDER admits at most " + std::to_string(kta_ts_order_max_partitions()) +
-                                                  " partitions (a wave of the apply kernel keeps its running maxima in LDS)");
+    // What a flag asks of the configuration, in the order it is checked: the partitions it admits and, where the pass
+    // reads the alive-key state, count_alive_keys (checked first).  Refusals carry the flag's name and the reason.
+    struct FlagBound {
+        uint32_t flag;
+        const char *name;
+        int (*most)(void);
+        const char *reason;
+        const char *needs_alive;   // null: the flag works without count_alive_keys
+    };
+    // (before the general bound, which is the same number today for some: the message names the pass that sets this one)
+    static const FlagBound kBeforeGeneral[] = {
+        {KTA_FLAG_PARTITIONER, "KTA_FLAG_PARTITIONER", kta_partitioner_max_partitions, "the pass keeps its counters in LDS", nullptr},
+        {KTA_FLAG_SIZE_QUANTILES, "KTA_FLAG_SIZE_QUANTILES", kta_size_quantiles_max_partitions, "every slice of 28 partitions streams the batch again",
+         nullptr},
+        {KTA_FLAG_COMPACTION, "KTA_FLAG_COMPACTION", kta_compaction_max_partitions, "the pass keeps 32 B per partition in LDS",
+         "the pass reads the last-writer table"},
+    };
+    static const FlagBound kAfterGeneral[] = {
+        {KTA_FLAG_ANALYTICS, "KTA_FLAG_ANALYTICS", kta_analytics_max_partitions, "the analytics scan keeps 4 extrema per partition in LDS", nullptr},
+        {KTA_FLAG_KEY_SKETCH, "KTA_FLAG_KEY_SKETCH", [] { return KTA_SKETCH_MAX_PARTITIONS; }, "a u64 snapshot of 4096 registers per partition", nullptr},
+        {KTA_FLAG_TS_ORDER, "KTA_FLAG_TS_ORDER", kta_ts_order_max_partitions, "a wave of the apply kernel keeps its running maxima in LDS", nullptr},
+    };
+    // the refusal of a flag's row, "" when the configuration meets it
+    auto refusal = [cfg](const FlagBound &b) -> std::string {
+        if (!(cfg->flags & b.flag)) return "";
+        if (b.needs_alive && !cfg->count_alive_keys) return std::string(b.name) + " needs count_alive_keys (" + b.needs_alive + ")";
+        if (cfg->n_partitions <= b.most()) return "";
+        return std::string(b.name) + " admits at most " + std::to_string(b.most()) + " partitions (" + b.reason + ")";
+    };
+    for (const FlagBound &b : kBeforeGeneral)
+        if (const std::string why = refusal(b); !why.empty()) return fail(nullptr, KTA_ERR_INVALID, why);
+    if (cfg->n_partitions <= 0 || cfg->n_partitions > 4096) return fail(nullptr, KTA_ERR_INVALID, "n_partitions must be in [1, 4096]");
+    for (const FlagBound &b : kAfterGeneral)
+        if (const std::string why = refusal(b); !why.empty()) return fail(nullptr, KTA_ERR_INVALID, why);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -1112,57 +1245,34 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->s_compute = ctx->s_own.get();
     KTA_TRY(hipStreamCreateWithFlags(ctx->s_copy.put(), hipStreamNonBlocking));
     KTA_TRY(hipEventCreateWithFlags(ctx->ev_copied.put(), hipEventDisableTiming));
-    const size_t vec_words = (size_t)ctx->P * KTA_NCOUNTERS + KTA_NGLOBALS;
-    KTA_TRY(ctx->d_vec.alloc(vec_words));
-    KTA_TRY(ctx->d_vec_out.alloc(vec_words));
+    // every section that is on: its live vector and its snapshot, both zero (kta_reset below gives the live ones their empty values)
+    Section sec[KTA_SEC_KINDS];
+    sections_of(ctx, sec);
+    for (const Section &s : sec) {
+        if (s.on) rc = alloc_section(ctx, s, s.shape.words);
+        if (rc != KTA_OK) return bail(rc);
+    }
+    // what a section keeps beside the two
     ctx->max_rows = (uint32_t)ctx->cu_count * 8u;
     KTA_TRY(ctx->d_partials.alloc((size_t)ctx->max_rows * kta::scan_row_len(ctx->P, ctx->analytics)));
-    if (ctx->analytics) {
-        KTA_TRY(ctx->d_avec.alloc(kta::analytics_len(ctx->P)));
-        KTA_TRY(ctx->d_avec_out.alloc(kta::analytics_len(ctx->P)));
-    }
     if (ctx->sketch) {
-        const size_t regs = (size_t)ctx->P * kta::kSketchRegs;
-        KTA_TRY(ctx->d_sketch.alloc(regs));
-        KTA_TRY(ctx->d_sketch_out.alloc(regs));
-        KTA_TRY(hipMemset(ctx->d_sketch_out.get(), 0, regs * sizeof(uint64_t)));
+        KTA_TRY(ctx->d_sketch.alloc((size_t)ctx->P * kta::kSketchRegs));
         KTA_TRY(ctx->d_sketch_floor.alloc(kta::kSketchFloorBytes));
         KTA_TRY(ctx->d_sketch_stats.alloc(3));
     }
     if (ctx->hot) {
-        KTA_TRY(ctx->d_hot.alloc(KTA_HOT_VECTOR_WORDS));
-        KTA_TRY(ctx->d_hot_out.alloc(KTA_HOT_VECTOR_WORDS));
-        KTA_TRY(hipMemset(ctx->d_hot_out.get(), 0, KTA_HOT_VECTOR_WORDS * sizeof(uint64_t)));
         KTA_TRY(ctx->d_hot_slots.alloc(kHotSlotsN));
         KTA_TRY(ctx->d_hot_ctl.alloc(2 * kHotSlotsN + kHotSlotsN / 32));
         KTA_TRY(ctx->d_hot_stats.alloc(4));
     }
     if (ctx->tso) {
-        KTA_TRY(ctx->d_tso.alloc(kta::ts_order_len(ctx->P)));
-        KTA_TRY(ctx->d_tso_out.alloc(kta::ts_order_len(ctx->P)));
-        KTA_TRY(hipMemset(ctx->d_tso_out.get(), 0, kta::ts_order_len(ctx->P) * sizeof(uint64_t)));
         KTA_TRY(ctx->d_tso_hi.alloc(ctx->P));
         KTA_TRY(ctx->d_tso_ws.alloc(kta::kTsOrderWorkspaceWords));
         KTA_TRY(ctx->d_tso_stats.alloc(3));
     }
-    if (ctx->part) {
-        const size_t words = kta::partitioner_len(ctx->P, ctx->part_q);
-        KTA_TRY(ctx->d_part.alloc(words));
-        KTA_TRY(ctx->d_part_out.alloc(words));
-        KTA_TRY(hipMemset(ctx->d_part_out.get(), 0, words * sizeof(uint64_t)));
-        KTA_TRY(ctx->d_part_stats.alloc(3));
-    }
-    if (ctx->comp) {
-        KTA_TRY(ctx->d_comp.alloc(kta::compaction_len(ctx->P)));
-        KTA_TRY(ctx->d_comp_stats.alloc(3));
-    }
-    if (ctx->sizeq) {
-        const size_t words = kta::size_quantiles_len(ctx->P);
-        KTA_TRY(ctx->d_sizeq.alloc(words));
-        KTA_TRY(ctx->d_sizeq_out.alloc(words));
-        KTA_TRY(hipMemset(ctx->d_sizeq_out.get(), 0, words * sizeof(uint64_t)));
-        KTA_TRY(ctx->d_sizeq_stats.alloc(kSizeqStatWords));
-    }
+    if (ctx->part) KTA_TRY(ctx->d_part_stats.alloc(3));
+    if (ctx->comp) KTA_TRY(ctx->d_comp_stats.alloc(3));
+    if (ctx->sizeq) KTA_TRY(ctx->d_sizeq_stats.alloc(kSizeqStatWords));
     if (ctx->alive) {
         if (ctx->alive_table) {
             KTA_TRY(ctx->d_table.alloc(kta::kAliveSlots));
@@ -1596,17 +1706,15 @@ int kta_finish_device(kta_ctx *ctx)
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    ResultVector rv[KTA_RV_KINDS];
-    kta_internal_result_vectors(ctx, rv);
-    // every snapshot is a copy of its live accumulator, but the key sketch's: its registers are u32, and a kernel widens them
-    const uint64_t *const live[KTA_RV_KINDS] = {ctx->d_vec.get(), ctx->d_avec.get(), ctx->d_tvec.get(), nullptr, ctx->d_hot.get(), ctx->d_tso.get(),
-                                                 ctx->d_part.get(), ctx->d_sizeq.get(), ctx->d_seg.get()};
-    for (int k = 0; k < KTA_RV_KINDS; k++)
-        if (rv[k].out && live[k])
-            KTA_HIP(ctx, hipMemcpyAsync(rv[k].out, live[k], rv[k].words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
+    // every snapshot is a copy of its live vector ...
+    Section sec[KTA_SEC_KINDS];
+    sections_of(ctx, sec);
+    for (const Section &s : sec)
+        if (s.on && s.live && s.out)
+            KTA_HIP(ctx, hipMemcpyAsync(s.out->get(), s.live->get(), s.shape.words * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->s_compute));
+    // ... but the key sketch's: its live registers are u32, and a kernel widens them
     if (ctx->sketch)
-        KTA_HIP(ctx, kta::launch_key_sketch_widen(ctx->d_sketch.get(), (uint64_t)ctx->P * kta::kSketchRegs, ctx->d_sketch_out.get(),
-                                                  ctx->s_compute));
+        KTA_HIP(ctx, kta::launch_key_sketch_widen(ctx->d_sketch.get(), sec[KTA_RV_KEY_SKETCH].shape.words, ctx->d_sketch_out.get(), ctx->s_compute));
     if (ctx->alive) {
         uint64_t *dst = ctx->d_vec_out.get() + (size_t)ctx->P * KTA_NCOUNTERS + KTA_G_ALIVE_KEYS;
         if (ctx->running_valid)  // exact running count (every update so far ran a counting kernel): no table scan
@@ -1624,8 +1732,7 @@ int kta_finish_device(kta_ctx *ctx)
 
 int kta_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    return hand_out(result_vector(ctx, KTA_RV_COUNTERS), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_COUNTERS, true, device_ptr, n_u64);
 }
 
 int kta_decode_vector(const uint64_t *vec, uint32_t P, int count_alive_keys, kta_result *out,
@@ -1665,10 +1772,7 @@ int kta_decode_vector(const uint64_t *vec, uint32_t P, int count_alive_keys, kta
 
 int kta_merge_vectors(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
-    if (!acc || !other || P == 0) return KTA_ERR_INVALID;
-    const size_t nc = (size_t)P * KTA_NCOUNTERS;
-    merge_words(acc, other, nc + KTA_NGLOBALS, nc + KTA_NSUM_GLOBALS, true);
-    return KTA_OK;
+    return merge_section(acc, other, P != 0, counters_shape(P));
 }
 
 int kta_finish(kta_ctx *ctx, kta_result *out, uint64_t *counters_out)
@@ -1683,9 +1787,9 @@ int kta_exchange_result(kta_ctx *ctx, kta_result *out, uint64_t *counters_out)
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const ResultVector v = result_vector(ctx, KTA_RV_COUNTERS);
-    std::vector<uint64_t> host(v.words);
-    int rc = read_words(ctx, v.out, host.data(), v.words);
+    const Section s = section(ctx, KTA_RV_COUNTERS);
+    std::vector<uint64_t> host(s.shape.words);
+    int rc = read_words(ctx, s.out->get(), host.data(), host.size());
     if (rc != KTA_OK) return rc;
     rc = kta_decode_vector(host.data(), ctx->P, ctx->alive ? 1 : 0, out, counters_out);
     if (rc == KTA_ERR_BAD_PARTITION) {
@@ -1702,11 +1806,7 @@ int kta_exchange_result(kta_ctx *ctx, kta_result *out, uint64_t *counters_out)
 
 int kta_analytics_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    *device_ptr = ctx->d_avec.get();
-    *n_u64 = kta::analytics_len(ctx->P);
-    return KTA_OK;
+    return section_vector(ctx, KTA_RV_ANALYTICS, false, device_ptr, n_u64);
 }
 
 int kta_decode_analytics(const uint64_t *vec, uint32_t P, kta_analytics *out, int64_t *part_min_ts_sec,
@@ -1731,17 +1831,22 @@ int kta_decode_analytics(const uint64_t *vec, uint32_t P, kta_analytics *out, in
 
 int kta_merge_analytics(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
-    if (!acc || !other || P == 0) return KTA_ERR_INVALID;
-    merge_words(acc, other, kta::analytics_len(P), kta::kAnalyticsHist, true);
-    return KTA_OK;
+    return merge_section(acc, other, P != 0, analytics_shape(P));
 }
 
-// the analytics vector at `d_vec` (the live accumulator or its snapshot) copied to the host and decoded
-static int read_analytics(kta_ctx *ctx, const uint64_t *d_vec, kta_analytics *out, int64_t *part_min_ts_sec,
-                          int64_t *part_max_ts_sec, uint64_t *part_smallest, uint64_t *part_largest)
+// The analytics read-back is struct-shaped: the section's live vector (staged messages flushed first) or its snapshot,
+// copied to the host and decoded.  The buffers and the guard are its row's.
+static int read_analytics(kta_ctx *ctx, bool snapshot, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
+                          uint64_t *part_smallest, uint64_t *part_largest)
 {
-    std::vector<uint64_t> host(kta::analytics_len(ctx->P));
-    int rc = read_words(ctx, d_vec, host.data(), host.size());
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    const Section s = section(ctx, KTA_RV_ANALYTICS);
+    if (!s.on) return fail(ctx, KTA_ERR_INVALID, s.off);
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = snapshot ? KTA_OK : kta_flush(ctx);
+    if (rc != KTA_OK) return rc;
+    std::vector<uint64_t> host(s.shape.words);
+    rc = read_words(ctx, (snapshot ? s.out : s.live)->get(), host.data(), host.size());
     if (rc != KTA_OK) return rc;
     return kta_decode_analytics(host.data(), ctx->P, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
@@ -1749,28 +1854,18 @@ static int read_analytics(kta_ctx *ctx, const uint64_t *d_vec, kta_analytics *ou
 int kta_get_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
                       uint64_t *part_smallest, uint64_t *part_largest)
 {
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_analytics(ctx, ctx->d_avec.get(), out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+    return read_analytics(ctx, false, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
 
 int kta_exchange_analytics(kta_ctx *ctx, kta_analytics *out, int64_t *part_min_ts_sec, int64_t *part_max_ts_sec,
                            uint64_t *part_smallest, uint64_t *part_largest)
 {
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_analytics(ctx, ctx->d_avec_out.get(), out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
+    return read_analytics(ctx, true, out, part_min_ts_sec, part_max_ts_sec, part_smallest, part_largest);
 }
 
 int kta_analytics_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->analytics) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_ANALYTICS");
-    return hand_out(result_vector(ctx, KTA_RV_ANALYTICS), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_ANALYTICS, true, device_ptr, n_u64);
 }
 
 // The largest P whose scan plan (raw and tile-compact) with `timeline_buckets` (0: none) fits one workgroup's LDS on
@@ -1815,17 +1910,12 @@ int kta_set_timeline(kta_ctx *ctx, int64_t origin_ms, int64_t bucket_ms, uint32_
                                               " buckets admits at most " + std::to_string(pmax) + " partitions" +
                                               (ctx->analytics ? " with KTA_FLAG_ANALYTICS" : ""));
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t words = kta::timeline_len(n_buckets);
-    if (!ctx->timeline || ctx->tl.n_buckets != n_buckets) {
-        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-        ctx->d_tvec.reset();
-        ctx->d_tvec_out.reset();
-        ctx->timeline = false;
-        KTA_HIP(ctx, ctx->d_tvec.alloc(words));
-        KTA_HIP(ctx, ctx->d_tvec_out.alloc(words));
-    }
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_tvec_out.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    const Section s = section(ctx, KTA_RV_TIMELINE);
+    const size_t words = timeline_shape(n_buckets).words;
+    const bool fits = ctx->timeline && ctx->tl.n_buckets == n_buckets;
+    if (!fits) ctx->timeline = false;   // (until both vectors have the new length)
+    int rc = fits ? clear_section(ctx, s, words) : alloc_section(ctx, s, words);
+    if (rc != KTA_OK) return rc;
     ctx->tl.origin = origin_ms;
     ctx->tl.width = (unsigned long long)bucket_ms;
     ctx->tl.span = (unsigned long long)bucket_ms * n_buckets;
@@ -1836,90 +1926,40 @@ int kta_set_timeline(kta_ctx *ctx, int64_t origin_ms, int64_t bucket_ms, uint32_
     return KTA_OK;
 }
 
-static int timeline_copy(kta_ctx *ctx, const uint64_t *d_src, uint64_t *out, size_t n_u64)
-{
-    if (!out) return KTA_ERR_INVALID;
-    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    const size_t words = kta::timeline_len(ctx->tl.n_buckets);
-    int rc = check_words(ctx, "timeline", words, n_u64);
-    return rc != KTA_OK ? rc : read_words(ctx, d_src, out, words);
-}
-
-int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return timeline_copy(ctx, ctx->d_tvec.get(), out, n_u64);
-}
-
-int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return timeline_copy(ctx, ctx->d_tvec_out.get(), out, n_u64);
-}
-
-int kta_timeline_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
-{
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    *device_ptr = ctx->d_tvec.get();
-    *n_u64 = kta::timeline_len(ctx->tl.n_buckets);
-    return KTA_OK;
-}
-
+int kta_get_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_TIMELINE, out, n_u64); }
+int kta_exchange_timeline(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_TIMELINE, out, n_u64); }
+int kta_timeline_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64) { return section_vector(ctx, KTA_RV_TIMELINE, false, device_ptr, n_u64); }
 int kta_timeline_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->timeline) return fail(ctx, KTA_ERR_INVALID, "the context has no timeline (kta_set_timeline)");
-    return hand_out(result_vector(ctx, KTA_RV_TIMELINE), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_TIMELINE, true, device_ptr, n_u64);
 }
 
-static const char *const kNoSketch = "context was created without KTA_FLAG_KEY_SKETCH";
-
-static int sketch_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "key sketch", (size_t)ctx->P * kta::kSketchRegs, n_u64); }
-
+// The key sketch is the section table's one exception: its live registers are u32, so the live read-back widens them on
+// the host (and kta_finish_device launches a kernel that widens them into the snapshot).
 int kta_get_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
 {
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
-    int rc = sketch_words(ctx, n_u64);
+    Section s;
+    int rc = begin_read(ctx, KTA_RV_KEY_SKETCH, out, n_u64, &s);
     if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
     rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    std::vector<uint32_t> host(n_u64);   // the live registers are u32
+    std::vector<uint32_t> host(n_u64);
     KTA_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_sketch.get(), n_u64 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->s_compute));
     KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
     for (size_t i = 0; i < n_u64; i++) out[i] = host[i];
     return KTA_OK;
 }
 
-int kta_exchange_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
-    int rc = sketch_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_sketch_out.get(), out, n_u64);
-}
-
+int kta_exchange_key_sketch(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_KEY_SKETCH, out, n_u64); }
 int kta_key_sketch_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
-    return hand_out(result_vector(ctx, KTA_RV_KEY_SKETCH), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_KEY_SKETCH, true, device_ptr, n_u64);
 }
 
 int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sketch) return fail(ctx, KTA_ERR_INVALID, kNoSketch);
+    if (!ctx->sketch) return section_off(ctx, KTA_RV_KEY_SKETCH);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = read_words(ctx, ctx->d_sketch_stats.get(), out, 3);
     out[3] = ctx->sketch_launches;
@@ -1928,48 +1968,20 @@ int kta_key_sketch_info(kta_ctx *ctx, uint64_t out[4])
 
 int kta_merge_key_sketch(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
-    if (!acc || !other || P == 0 || P > KTA_SKETCH_MAX_PARTITIONS) return KTA_ERR_INVALID;
-    merge_words(acc, other, (size_t)P * KTA_SKETCH_REGISTERS, 0, false);
-    return KTA_OK;
+    return merge_section(acc, other, P != 0 && P <= KTA_SKETCH_MAX_PARTITIONS, key_sketch_shape(P));
 }
 
-static const char *const kNoHot = "context was created without KTA_FLAG_HOT_KEYS";
-
-static int hot_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "hot-key vector", KTA_HOT_VECTOR_WORDS, n_u64); }
-
-int kta_get_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
-    int rc = hot_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_hot.get(), out, n_u64);
-}
-
-int kta_exchange_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
-    int rc = hot_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_hot_out.get(), out, n_u64);
-}
-
+int kta_get_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_HOT_KEYS, out, n_u64); }
+int kta_exchange_hot_keys(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_HOT_KEYS, out, n_u64); }
 int kta_hot_keys_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
-    return hand_out(result_vector(ctx, KTA_RV_HOT_KEYS), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_HOT_KEYS, true, device_ptr, n_u64);
 }
 
 int kta_get_hot_key_exemplars(kta_ctx *ctx, kta_hot_exemplar *out, size_t n_slots)
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    if (!ctx->hot) return section_off(ctx, KTA_RV_HOT_KEYS);
     if (n_slots != kHotSlotsN)
         return fail(ctx, KTA_ERR_INVALID, "the exemplar table has " + std::to_string(kHotSlotsN) + " slots, not " + std::to_string(n_slots));
     KTA_HIP(ctx, hipSetDevice(ctx->device));
@@ -1983,7 +1995,7 @@ int kta_get_hot_key_exemplars(kta_ctx *ctx, kta_hot_exemplar *out, size_t n_slot
 int kta_hot_keys_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    if (!ctx->hot) return section_off(ctx, KTA_RV_HOT_KEYS);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t st[4];
     int rc = read_words(ctx, ctx->d_hot_stats.get(), st, 4);
@@ -1994,66 +2006,33 @@ int kta_hot_keys_info(kta_ctx *ctx, uint64_t out[6])
 int kta_set_hot_flush_rounds(kta_ctx *ctx, uint32_t rounds)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->hot) return fail(ctx, KTA_ERR_INVALID, kNoHot);
+    if (!ctx->hot) return section_off(ctx, KTA_RV_HOT_KEYS);
     if (rounds > kta::kHotFlushRoundsMax)
         return fail(ctx, KTA_ERR_INVALID, "a workgroup flushes after at most " + std::to_string(kta::kHotFlushRoundsMax) + " rounds");
     ctx->hot_flush_rounds = rounds;
     return KTA_OK;
 }
 
-int kta_merge_hot_keys(uint64_t *acc, const uint64_t *other)
-{
-    if (!acc || !other) return KTA_ERR_INVALID;
-    merge_words(acc, other, KTA_HOT_VECTOR_WORDS, KTA_HOT_VECTOR_WORDS, false);
-    return KTA_OK;
-}
-
-static const char *const kNoTso = "context was created without KTA_FLAG_TS_ORDER";
-
-static int tso_words(kta_ctx *ctx, size_t n_u64) { return check_words(ctx, "timestamp-order vector", kta::ts_order_len(ctx->P), n_u64); }
+int kta_merge_hot_keys(uint64_t *acc, const uint64_t *other) { return merge_section(acc, other, true, hot_keys_shape()); }
 
 int kta_ts_order_max_partitions(void) { return (int)kta::kTsOrderMaxPartitions; }
 
-int kta_get_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
-    int rc = tso_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_tso.get(), out, n_u64);
-}
-
-int kta_exchange_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
-    int rc = tso_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_tso_out.get(), out, n_u64);
-}
-
+int kta_get_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_TS_ORDER, out, n_u64); }
+int kta_exchange_ts_order(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_TS_ORDER, out, n_u64); }
 int kta_ts_order_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
-    return hand_out(result_vector(ctx, KTA_RV_TS_ORDER), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_TS_ORDER, true, device_ptr, n_u64);
 }
 
 int kta_merge_ts_order(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
-    if (!acc || !other || P == 0 || P > kta::kTsOrderMaxPartitions) return KTA_ERR_INVALID;
-    merge_words(acc, other, kta::ts_order_len(P), 2 * (size_t)P + 64, true);
-    return KTA_OK;
+    return merge_section(acc, other, P != 0 && P <= kta::kTsOrderMaxPartitions, ts_order_shape(P));
 }
 
 int kta_ts_order_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    if (!ctx->tso) return section_off(ctx, KTA_RV_TS_ORDER);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t st[3];
     int rc = read_words(ctx, ctx->d_tso_stats.get(), st, 3);
@@ -2064,15 +2043,12 @@ int kta_ts_order_info(kta_ctx *ctx, uint64_t out[6])
 int kta_set_ts_order_chunk(kta_ctx *ctx, uint64_t records)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->tso) return fail(ctx, KTA_ERR_INVALID, kNoTso);
+    if (!ctx->tso) return section_off(ctx, KTA_RV_TS_ORDER);
     if (records % 64 != 0 || records > (1ull << 32))
         return fail(ctx, KTA_ERR_INVALID, "a chunk is a multiple of 64 records, at most 2^32 (0: the default)");
     ctx->tso_chunk = records;
     return KTA_OK;
 }
-
-static const char *const kNoSeg = "the context has no segments (kta_set_segments)";
-static_assert(kta::kRetWords == KTA_RETENTION_WORDS, "the what-if's row is said twice: kta_segments.h and kta_hip.h");
 
 int kta_segments_max_partitions(void) { return (int)kta::kSegmentsMaxPartitions; }
 
@@ -2090,14 +2066,11 @@ int kta_set_segments(kta_ctx *ctx, uint64_t segment_bytes, uint32_t rows_per_par
     if (ctx->handed_records || ctx->fill_n)
         return fail(ctx, KTA_ERR_INVALID, "kta_set_segments: the context has been handed records since kta_create / kta_reset");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t words = kta::segments_len(ctx->P, rows_per_partition);
+    const size_t words = segments_shape(ctx->P, rows_per_partition).words;
     if (!ctx->seg || ctx->seg_M != rows_per_partition) {
-        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-        ctx->d_seg.reset();
-        ctx->d_seg_out.reset();
-        ctx->seg = false;
-        KTA_HIP(ctx, ctx->d_seg.alloc(words));
-        KTA_HIP(ctx, ctx->d_seg_out.alloc(words));
+        ctx->seg = false;               // (until both vectors have the new length)
+        int rc = alloc_section(ctx, section(ctx, KTA_RV_SEGMENTS), words);
+        if (rc != KTA_OK) return rc;
     }
     if (!ctx->d_seg_ws) {
         KTA_HIP(ctx, ctx->d_seg_ws.alloc(kta::kSegmentsWorkspaceWords));
@@ -2113,39 +2086,17 @@ int kta_set_segments(kta_ctx *ctx, uint64_t segment_bytes, uint32_t rows_per_par
     return KTA_OK;
 }
 
-int kta_get_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
-    int rc = check_words(ctx, "segment vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_seg.get(), out, n_u64);
-}
-
-int kta_exchange_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
-    int rc = check_words(ctx, "segment vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_seg_out.get(), out, n_u64);
-}
-
+int kta_get_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_SEGMENTS, out, n_u64); }
+int kta_exchange_segments(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_SEGMENTS, out, n_u64); }
 int kta_segments_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
-    return hand_out(result_vector(ctx, KTA_RV_SEGMENTS), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_SEGMENTS, true, device_ptr, n_u64);
 }
 
 int kta_segments_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    if (!ctx->seg) return section_off(ctx, KTA_RV_SEGMENTS);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
@@ -2158,7 +2109,7 @@ int kta_segments_info(kta_ctx *ctx, uint64_t out[6])
 int kta_set_segments_chunk(kta_ctx *ctx, uint64_t records)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    if (!ctx->seg) return section_off(ctx, KTA_RV_SEGMENTS);
     if (records % 64 != 0 || records > (1ull << 31))
         return fail(ctx, KTA_ERR_INVALID, "a chunk is a multiple of 64 records, at most 2^31 (0: the default)");
     ctx->seg_chunk = records;
@@ -2182,13 +2133,6 @@ int kta_retention_whatif(const uint64_t *vec, uint32_t P, uint32_t M, int64_t no
     return KTA_OK;
 }
 
-static const char *const kNoPart = "context was created without KTA_FLAG_PARTITIONER";
-
-static int part_words(kta_ctx *ctx, size_t n_u64)
-{
-    return check_words(ctx, "partitioner vector", kta::partitioner_len(ctx->P, ctx->part_q), n_u64);
-}
-
 int kta_partitioner_max_partitions(void) { return (int)kta::kPartitionerMaxPartitions; }
 
 uint32_t kta_murmur2(const void *key, size_t len)
@@ -2206,65 +2150,38 @@ uint32_t kta_murmur2(const void *key, size_t len)
 int kta_set_repartition(kta_ctx *ctx, uint32_t q)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    if (!ctx->part) return section_off(ctx, KTA_RV_PARTITIONER);
     if (q < 1 || q > kta::kPartitionerMaxPartitions)
         return fail(ctx, KTA_ERR_INVALID, "kta_set_repartition: Q must be in [1, " + std::to_string(kta::kPartitionerMaxPartitions) + "]");
     if (ctx->handed_records || ctx->fill_n)
         return fail(ctx, KTA_ERR_INVALID, "kta_set_repartition: the context has been handed records since kta_create / kta_reset");
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t words = kta::partitioner_len(ctx->P, q);
-    if (q != ctx->part_q) {
-        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-        KTA_HIP(ctx, ctx->d_part.alloc(words));
-        KTA_HIP(ctx, ctx->d_part_out.alloc(words));
-        ctx->part_q = q;
-    }
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_part.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
-    KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_out.get(), 0, words * sizeof(uint64_t), ctx->s_compute));
+    const Section s = section(ctx, KTA_RV_PARTITIONER);
+    const size_t words = partitioner_shape(ctx->P, q).words;
+    if (q == ctx->part_q) return clear_section(ctx, s, words);
+    int rc = alloc_section(ctx, s, words);
+    if (rc != KTA_OK) return rc;
+    ctx->part_q = q;
     return KTA_OK;
 }
 
-int kta_get_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
-    int rc = part_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_part.get(), out, n_u64);
-}
-
-int kta_exchange_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
-    int rc = part_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_part_out.get(), out, n_u64);
-}
-
+int kta_get_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_PARTITIONER, out, n_u64); }
+int kta_exchange_partitioner(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_PARTITIONER, out, n_u64); }
 int kta_partitioner_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
-    return hand_out(result_vector(ctx, KTA_RV_PARTITIONER), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_PARTITIONER, true, device_ptr, n_u64);
 }
 
 int kta_merge_partitioner(uint64_t *acc, const uint64_t *other, uint32_t P, uint32_t q)
 {
-    if (!acc || !other || P == 0 || P > kta::kPartitionerMaxPartitions || q == 0 || q > kta::kPartitionerMaxPartitions) return KTA_ERR_INVALID;
-    const size_t words = kta::partitioner_len(P, q);
-    merge_words(acc, other, words, words, false);
-    return KTA_OK;
+    const uint32_t most = kta::kPartitionerMaxPartitions;
+    return merge_section(acc, other, P != 0 && P <= most && q != 0 && q <= most, partitioner_shape(P, q));
 }
 
 int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->part) return fail(ctx, KTA_ERR_INVALID, kNoPart);
+    if (!ctx->part) return section_off(ctx, KTA_RV_PARTITIONER);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t st[3];
     int rc = read_words(ctx, ctx->d_part_stats.get(), st, 3);
@@ -2275,13 +2192,6 @@ int kta_partitioner_info(kta_ctx *ctx, uint64_t out[6])
 }
 
 // ---- size percentiles (kta_size_bins.h holds the rule, kta_size_quantiles.hip the kernel) -------------------------------
-
-static const char *const kNoSizeq = "context was created without KTA_FLAG_SIZE_QUANTILES";
-
-static int sizeq_words(kta_ctx *ctx, size_t n_u64)
-{
-    return check_words(ctx, "size-percentile vector", kta::size_quantiles_len(ctx->P), n_u64);
-}
 
 int kta_size_quantiles_max_partitions(void) { return (int)kta::kSizeQuantilesMaxPartitions; }
 
@@ -2303,47 +2213,22 @@ int kta_size_quantile(const uint64_t *hist, uint64_t num, uint64_t den, uint64_t
     return 1;
 }
 
-int kta_get_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
-    int rc = sizeq_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_sizeq.get(), out, n_u64);
-}
-
-int kta_exchange_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
-    int rc = sizeq_words(ctx, n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    return read_words(ctx, ctx->d_sizeq_out.get(), out, n_u64);
-}
-
+int kta_get_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_SIZE_QUANTILES, out, n_u64); }
+int kta_exchange_size_quantiles(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_SIZE_QUANTILES, out, n_u64); }
 int kta_size_quantiles_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
 {
-    if (!ctx || !device_ptr || !n_u64) return KTA_ERR_INVALID;
-    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
-    return hand_out(result_vector(ctx, KTA_RV_SIZE_QUANTILES), device_ptr, n_u64);
+    return section_vector(ctx, KTA_RV_SIZE_QUANTILES, true, device_ptr, n_u64);
 }
 
 int kta_merge_size_quantiles(uint64_t *acc, const uint64_t *other, uint32_t P)
 {
-    if (!acc || !other || P == 0 || P > kta::kSizeQuantilesMaxPartitions) return KTA_ERR_INVALID;
-    const size_t words = kta::size_quantiles_len(P);
-    merge_words(acc, other, words, words, false);
-    return KTA_OK;
+    return merge_section(acc, other, P != 0 && P <= kta::kSizeQuantilesMaxPartitions, size_quantiles_shape(P));
 }
 
 int kta_set_size_quantiles_slice(kta_ctx *ctx, uint32_t partitions)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    if (!ctx->sizeq) return section_off(ctx, KTA_RV_SIZE_QUANTILES);
     if (partitions > kta::kSizeQuantilesMaxSlice)
         return fail(ctx, KTA_ERR_INVALID, "kta_set_size_quantiles_slice: at most " + std::to_string(kta::kSizeQuantilesMaxSlice) + " partitions (0: the default)");
     ctx->sizeq_slice = partitions;
@@ -2353,7 +2238,7 @@ int kta_set_size_quantiles_slice(kta_ctx *ctx, uint32_t partitions)
 int kta_size_quantiles_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->sizeq) return fail(ctx, KTA_ERR_INVALID, kNoSizeq);
+    if (!ctx->sizeq) return section_off(ctx, KTA_RV_SIZE_QUANTILES);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
@@ -2367,21 +2252,20 @@ int kta_size_quantiles_info(kta_ctx *ctx, uint64_t out[6])
 
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
 
-static const char *const kNoComp = "context was created without KTA_FLAG_COMPACTION";
-
 int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
 
 int kta_compaction_replay(kta_ctx *ctx, int on)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    if (!ctx->comp) return section_off(ctx, KTA_SEC_COMPACTION);
     const bool want = on != 0;
     if (want == ctx->comp_replay) return KTA_OK;
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);   // what was staged goes where it was staged for
     if (rc != KTA_OK) return rc;
     if (want) {
-        KTA_HIP(ctx, hipMemsetAsync(ctx->d_comp.get(), 0, kta::compaction_len(ctx->P) * sizeof(uint64_t), ctx->s_compute));
+        rc = clear_section(ctx, section(ctx, KTA_SEC_COMPACTION), compaction_shape(ctx->P).words);
+        if (rc != KTA_OK) return rc;
         if (ctx->cd) {
             rc = clear_kept(ctx);
             if (rc != KTA_OK) return rc;
@@ -2395,22 +2279,12 @@ int kta_compaction_replay(kta_ctx *ctx, int on)
     return KTA_OK;
 }
 
-int kta_get_compaction(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
-    int rc = check_words(ctx, "compaction vector", kta::compaction_len(ctx->P), n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_comp.get(), out, n_u64);
-}
+int kta_get_compaction(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_SEC_COMPACTION, out, n_u64); }
 
 int kta_compaction_info(kta_ctx *ctx, uint64_t out[6])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
+    if (!ctx->comp) return section_off(ctx, KTA_SEC_COMPACTION);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     uint64_t st[3];
     int rc = read_words(ctx, ctx->d_comp_stats.get(), st, 3);
@@ -2422,8 +2296,6 @@ int kta_compaction_info(kta_ctx *ctx, uint64_t out[6])
 
 // ---- compact,delete what-if (kta_compact_delete.h holds the rule; the kernels are kta_compaction.hip's and kta_segments.hip's) ----
 
-static const char *const kNoCd = "the context has no compact,delete what-if (kta_set_compact_delete)";
-static_assert(kta::kCdWords == KTA_COMPACT_DELETE_WORDS, "the what-if's row is said twice: kta_compact_delete.h and kta_hip.h");
 static_assert(kta::kCompactDeleteMaxPartitions == (kta::kSegmentsMaxPartitions < kta::kCompactionMaxPartitions ? kta::kSegmentsMaxPartitions
                                                                                                                : kta::kCompactionMaxPartitions),
               "the smaller of the two passes' bounds");
@@ -2433,8 +2305,8 @@ int kta_compact_delete_max_partitions(void) { return (int)kta::kCompactDeleteMax
 int kta_set_compact_delete(kta_ctx *ctx, int on)
 {
     if (!ctx) return KTA_ERR_INVALID;
-    if (!ctx->comp) return fail(ctx, KTA_ERR_INVALID, kNoComp);
-    if (!ctx->seg) return fail(ctx, KTA_ERR_INVALID, kNoSeg);
+    if (!ctx->comp) return section_off(ctx, KTA_SEC_COMPACTION);
+    if (!ctx->seg) return section_off(ctx, KTA_RV_SEGMENTS);
     if (ctx->handed_records || ctx->fill_n || ctx->comp_replay)
         return fail(ctx, KTA_ERR_INVALID, "kta_set_compact_delete: the context has been handed records since kta_create / kta_reset");
     if (ctx->P > kta::kCompactDeleteMaxPartitions)
@@ -2444,34 +2316,22 @@ int kta_set_compact_delete(kta_ctx *ctx, int on)
         return KTA_OK;
     }
     KTA_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t words = kta::segments_len(ctx->P, ctx->seg_M);
-    if (ctx->d_kept.size() != words) {
-        KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
-        KTA_HIP(ctx, ctx->d_kept.alloc(words));
-    }
+    const Section s = section(ctx, KTA_SEC_KEPT);   // (live only: the one vector)
+    int rc = ctx->d_kept.size() != s.shape.words ? alloc_section(ctx, s, s.shape.words) : KTA_OK;
+    if (rc != KTA_OK) return rc;
     if (!ctx->d_cd_stats) KTA_HIP(ctx, ctx->d_cd_stats.alloc(4));
-    int rc = clear_kept(ctx);
+    rc = clear_kept(ctx);
     if (rc != KTA_OK) return rc;
     ctx->cd = true;
     return KTA_OK;
 }
 
-int kta_get_compact_delete(kta_ctx *ctx, uint64_t *out, size_t n_u64)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->cd) return fail(ctx, KTA_ERR_INVALID, kNoCd);
-    int rc = check_words(ctx, "kept vector", kta::segments_len(ctx->P, ctx->seg_M), n_u64);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipSetDevice(ctx->device));
-    rc = kta_flush(ctx);
-    if (rc != KTA_OK) return rc;
-    return read_words(ctx, ctx->d_kept.get(), out, n_u64);
-}
+int kta_get_compact_delete(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_SEC_KEPT, out, n_u64); }
 
 int kta_compact_delete_info(kta_ctx *ctx, uint64_t out[4])
 {
     if (!ctx || !out) return KTA_ERR_INVALID;
-    if (!ctx->cd) return fail(ctx, KTA_ERR_INVALID, kNoCd);
+    if (!ctx->cd) return section_off(ctx, KTA_SEC_KEPT);
     KTA_HIP(ctx, hipSetDevice(ctx->device));
     int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;

@@ -59,9 +59,11 @@ struct kta_internal_columns {
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out);
 
 // ---- result vectors -----------------------------------------------------------------------------------------------
-// Every section of the result has a snapshot that kta_finish_device takes and kta_exchange reduces in place: words
-// [0, sum_words) with u64 SUM, words [sum_words, words) with MAX (i64 when max_signed, else u64).  A new opt-in
-// section adds a kind here and a row in kta_internal_result_vectors.
+// Every section of the result is a u64 vector of the shape below.  The kinds before KTA_RV_KINDS have a snapshot that
+// kta_finish_device takes and kta_exchange reduces in place: words [0, sum_words) with u64 SUM, words [sum_words, words)
+// with MAX (i64 when max_signed, else u64).  The kinds behind it are live only: read back, never exchanged.  A new opt-in
+// section adds a kind here and a row in kta_api.hip's section table (sections_of), which is all the host layer reads:
+// create, reset, the snapshot, the read-back and kta_internal_result_vectors go by that row.
 //
 //   kind        u64 words          SUM prefix     MAX suffix
 //   counters    P*7 + 8            P*7 + 4        4      (i64)
@@ -73,13 +75,17 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns 
 //   partitioner 2*P + 2*Q          all            none
 //   size quant. P*3*464 + 8        all            none
 //   segments    (P*M + P)*4 + 8    all but 5      5      (u64: S, M, overhead and two zero words, equal on every rank)
+//   compaction  5*P + 6            (live only: the replay's vector, kta_get_compaction)
+//   kept        (P*M + P)*4 + 8    (live only: the replay's kept vector, kta_get_compact_delete; the segments' shape)
 struct ResultVector {
     uint64_t *out;     // the snapshot (device); null: the context has no such section
     size_t words, sum_words;
     bool max_signed;
 };
 enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_PARTITIONER,
-       KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_KINDS };
+       KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_KINDS,
+       KTA_SEC_COMPACTION = KTA_RV_KINDS, KTA_SEC_KEPT, KTA_SEC_KINDS };
+// The snapshot kinds of the section table; a section that is off has out == nullptr and words == 0.
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);
 
 // ---- errors -------------------------------------------------------------------------------------------------------

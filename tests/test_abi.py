@@ -227,3 +227,47 @@ def test_missing_rccl_is_an_error_not_a_crash(tmp_path):
                PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+# Every kta_merge_* but kta_merge_segments (its own rule: kta::segments_merge, tests/test_segments_host.py) at P = 3, Q = 5:
+# (the entry point, its arguments behind the two vectors, u64 words, the SUM prefix, the MAX suffix signed) — the numbers
+# as the table in csrc/kta_internal.h gives them, typed in here.
+_MERGE_P, _MERGE_Q = 3, 5
+MERGE_RULES = [
+    ("kta_merge_vectors", (_MERGE_P,), 3 * 7 + 8, 3 * 7 + 4, True),
+    ("kta_merge_analytics", (_MERGE_P,), 68 + 4 * 3, 68, True),
+    ("kta_merge_key_sketch", (_MERGE_P,), 3 * 4096, 0, False),
+    ("kta_merge_hot_keys", (), 2 * 1024 * 23, 2 * 1024 * 23, False),
+    ("kta_merge_ts_order", (_MERGE_P,), 3 * 3 + 64, 2 * 3 + 64, True),
+    ("kta_merge_partitioner", (_MERGE_P, _MERGE_Q), 2 * 3 + 2 * 5, 2 * 3 + 2 * 5, False),
+    ("kta_merge_size_quantiles", (_MERGE_P,), 3 * 3 * 464 + 8, 3 * 3 * 464 + 8, False),
+]
+
+
+@pytest.mark.parametrize("entry,args,words,sum_words,signed", MERGE_RULES, ids=[r[0] for r in MERGE_RULES])
+def test_merge_is_sum_over_the_prefix_and_max_over_the_suffix(entry, args, words, sum_words, signed):
+    """On random u64 words (every bit: sums wrap, and a signed maximum orders them otherwise than an unsigned one), with
+    guard words behind the vector that the merge must leave alone."""
+    rng = np.random.default_rng(words + sum_words)
+    guard = 16
+    acc = rng.integers(0, 1 << 64, words + guard, dtype=np.uint64)
+    other = rng.integers(0, 1 << 64, words + guard, dtype=np.uint64)
+    want = acc.copy()
+    want[:sum_words] = acc[:sum_words] + other[:sum_words]          # (uint64: modulo 2^64, as the library's)
+    a, o = acc[sum_words:words], other[sum_words:words]
+    want[sum_words:words] = np.maximum(a.view(np.int64), o.view(np.int64)).view(np.uint64) if signed else np.maximum(a, o)
+    keep = other.copy()
+    assert getattr(N.load(), entry)(acc.ctypes.data, other.ctypes.data, *args) == N.KTA_OK
+    assert np.array_equal(acc, want) and np.array_equal(other, keep)
+
+
+@pytest.mark.parametrize("P", [1, 3, 1000])
+def test_ts_order_vector_is_3p_plus_64_words_of_which_the_last_p_are_maxima(P):
+    """include/kta_hip.h says u64[3 P + 64], SUM over the first 2 P + 64: the library's length function and the prefix its
+    merge uses agree with that.  1 (+) 1 is 2 where the merge sums, 1 where it takes the maximum, and the words behind the
+    vector stay 0."""
+    acc = np.zeros(3 * P + 64 + 16, np.uint64)
+    acc[:3 * P + 64] = 1
+    other = np.ones(acc.size, np.uint64)
+    assert N.load().kta_merge_ts_order(acc.ctypes.data, other.ctypes.data, P) == N.KTA_OK
+    assert (acc[:2 * P + 64] == 2).all() and (acc[2 * P + 64:3 * P + 64] == 1).all() and not acc[3 * P + 64:].any()
