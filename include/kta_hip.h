@@ -339,6 +339,50 @@ typedef struct kta_hot_key {
 #define KTA_SIZE_QUANTITIES 3            /* K, V, M */
 #define KTA_SIZE_GLOBALS 8
 
+/* Record batches (NOT in the reference, which never sees a batch): what the headers of the Kafka v2 record batches say that
+ * the raw-log decode delivers (kta_kafka.h: kta_kafka_decode_device, and through it kta_kafka_blob_submit and
+ * kta_kafka_consume) — does the producer batch, what does compression buy, what wrote the log and what has the cleaner
+ * already removed.  Opt-in at kta_create.  Every word is exact; only the number of producers READ OFF the sketch's registers
+ * is an estimate (HyperLogLog, 2^10 registers, standard error 1.04 / sqrt(1024) = 3.25 %).  csrc/kta_record_batches.h is the
+ * code of everything below.
+ * Per batch, from its descriptor (read after the call's inflate and decode kernels: status is final, payload_end -
+ * payload_off the exact inflated size) and from the header bytes partitionLeaderEpoch (12), attributes (21),
+ * lastOffsetDelta (23) and producerId (43), big endian at any alignment:
+ *   codec 0..4 (none, gzip, Snappy, LZ4, zstd); wire = batch_bytes; recbytes = batch_bytes - 61;
+ *   payload = payload_end - payload_off (= recbytes for codec 0); span_ms = clamp(max_ts_ms - base_ts_ms, 0, 2^31 - 1);
+ *   extent = max(lastOffsetDelta + 1, n_records); bin(x) = 0 for x == 0, else min(31, 1 + floor(log2 x)).
+ * The vector is u64[20 P + 1524]: words [0, 16 P + 500) are SUMS, the rest unsigned MAXIMA.
+ *   partition p, 16 words at 16 p: batches, records, wire, payload, compressed batches, recbytes and payload of the
+ *     compressed batches, extent, transactional, idempotent (producerId >= 0), LogAppendTime, span_ms, failed, three zeros;
+ *   codec c, 100 words at 16 P + 100 c: batches, records, recbytes, payload, then three histograms of 32 bins by
+ *     bin(n_records), bin(wire), bin(span_ms);
+ *   partition p, 4 maxima at 16 P + 500 + 4 p: the largest n_records, wire, partitionLeaderEpoch + 1 (0: none seen, or
+ *     epoch -1) and span_ms;
+ *   the producer sketch, 1024 words at 20 P + 500: over the idempotent batches, h = splitmix64(producerId), register
+ *     h >> 54, rank 1 + clz(h << 10 | 1 << 9), kept by MAX.
+ * A FAILED batch (status != 0: a bad CRC under check.crcs, bad framing, a stream that does not inflate) adds 1 to its
+ * partition's `failed` and nothing else anywhere.  A batch whose partition is outside [0, P) is left out entirely (its
+ * records land in KTA_G_BAD_PARTITION).  Control batches, batches without records, unknown codecs (5..7) and magic 0/1
+ * message sets get no descriptor and are not in these numbers: kta_kafka_index_stats counts them.
+ * Identities: the sums over the codecs of batches, records and payload equal the sums over the partitions of words 0, 1
+ * and 3; words 4, 5 and 6 summed over the partitions equal batches, recbytes and payload summed over codecs 1..4; each
+ * histogram of a codec sums to its batches; and, in a run with no failed batch and no filter, the records summed over the
+ * partitions equal the counter vector's total_messages (tombstones included) over the partitions.
+ * Composition.  During a compaction replay (kta_compaction_replay) the source is read a second time and the pass is
+ * skipped: batches are counted once.  With a filter (kta_set_filter) a batch is counted iff its partition is selected and
+ * its [base_ts_ms, max_ts_ms] overlaps the window, base_ts_ms < to_ms && max_ts_ms >= from_ms with an absent bound open:
+ * the batches that overlap the window, not the records that pass.
+ * With the flag off no kernel is launched and nothing is allocated. */
+#define KTA_FLAG_RECORD_BATCHES 0x200U   /* 512: bit 9 (the suffix in capitals, as bit 8 has it) */
+#define KTA_RB_PARTITION_WORDS 16
+#define KTA_RB_CODECS 5
+#define KTA_RB_CODEC_WORDS 100
+#define KTA_RB_HIST_BINS 32
+#define KTA_RB_MAX_WORDS 4
+#define KTA_RB_SKETCH_REGISTERS 1024
+#define KTA_RB_WORDS(P) (20u * (size_t)(P) + 1524u)
+#define KTA_RB_SUM_WORDS(P) (16u * (size_t)(P) + 500u)
+
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
  * both hold:
@@ -952,6 +996,31 @@ int kta_merge_segments(uint64_t *acc, const uint64_t *other, uint32_t n_partitio
 int kta_retention_whatif(const uint64_t *vec, uint32_t n_partitions, uint32_t rows_per_partition, int64_t now_ms, int64_t retention_ms,
                          int64_t retention_bytes, uint64_t *out, size_t n_u64);
 
+/* Record batches (context created with KTA_FLAG_RECORD_BATCHES; definition above KTA_FLAG_RECORD_BATCHES).  kta_reset zeroes
+ * the vector; kta_finish_device snapshots it; kta_exchange reduces the snapshot (SUM prefix, MAX suffix).  Every call below
+ * that takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_RECORD_BATCHES.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_RB_WORDS(P); staged messages are flushed first). */
+int kta_get_record_batches(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the whole
+ * job's vector on every rank.  The live accumulator is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_record_batches(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot (what collectives reduce in place), and of the live vector. */
+int kta_record_batches_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+int kta_record_batches_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[KTA_RB_WORDS(P)]: acc <- acc + other over the SUM prefix, max(acc, other) behind it.
+ * KTA_ERR_INVALID for a P outside [1, 4096]. */
+int kta_merge_record_batches(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* The number of distinct producer ids read off a vector's sketch (host only): HyperLogLog's estimate with linear counting
+ * while it is small and registers are empty; 0 for an empty sketch. */
+int kta_record_batches_estimate_producers(const uint64_t *vec, uint32_t n_partitions, double *out);
+/* 1 when the identities between the words of one vector hold, 0 when not (host only). */
+int kta_record_batches_identities(const uint64_t *vec, uint32_t n_partitions);
+/* The same rule on the host, for tests (the product accumulates on the device only): the batches that kta_kafka_index_host
+ * finds in bytes[0, len) of `partition` are added to vec[KTA_RB_WORDS(P)].  inflated: one exact inflated size per
+ * descriptor, or NULL to take the index's own value (exact for no codec, gzip and Snappy; a bound for LZ4 and zstd). */
+int kta_record_batches_host(const uint8_t *bytes, uint64_t len, int32_t partition, const uint64_t *inflated, uint64_t *vec,
+                            uint32_t n_partitions);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1210,6 +1279,22 @@ int kta_render_compact_delete(const uint64_t *seg_vec, const uint64_t *kept_vec,
  *   a closing `=` rule.
  * partition_bitmap: NULL, or ceil(n_partitions / 32) words as kta_set_filter takes them.  Output buffer conventions as
  * kta_render_report. */
+/* The opt-in record-batch section that kta-analyzer prints behind every other section with --librdkafka
+ * kta.record_batches=1, from a record-batch vector (host only):
+ *   a title line saying that it is not part of the reference report;
+ *   a table (P | Batches | Rec/batch | Largest | B/batch | Largest | Span ms | Compressed % | Ratio | Holes | Holes % |
+ *    Idempotent % | Transactional % | LogAppendTime % | Epoch | Failed) with a row per partition and a `Topic` row: the means
+ *    and shares with two decimals, Ratio = payload / recbytes of the compressed batches, Holes = extent - records and its
+ *    share of the extent, Epoch the highest leader epoch (`-` when none);
+ *   a table per codec (Codec | Batches | Records | Bytes on disk | Inflated bytes | Ratio | Rec/batch p50 | p90 | B/batch p50
+ *    | p90): the percentiles are the upper ends of their histogram bins;
+ *   `Producers (estimated, +/- 3.25 %): N`;
+ *   the notes: what is not counted, with skipped[0..2] = the host index's control batches, magic 0/1 sets and batches of an
+ *    unknown codec summed over the run (NULL: zeros), and, when `filtered`, that the batches are those that overlap the
+ *    window; a closing `=` rule.
+ * A ratio, mean or share whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
+int kta_render_record_batches(const uint64_t *vec, uint32_t n_partitions, int filtered, const uint64_t *skipped, char *out,
+                              size_t out_cap, size_t *out_len);
 int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
                       uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 

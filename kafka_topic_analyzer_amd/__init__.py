@@ -34,7 +34,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "size_bin_bounds", "size_quantile", "size_quantiles_max_partitions", "segments_words", "segments_max_partitions",
            "split_segments", "merge_segments", "retention_whatif", "RETENTION_COLUMNS", "render_retention",
            "compact_delete_max_partitions", "split_compact_delete", "compact_delete_whatif", "COMPACT_DELETE_COLUMNS",
-           "render_compact_delete"]
+           "render_compact_delete", "split_record_batches", "merge_record_batches", "render_record_batches", "estimate_producers",
+           "record_batches_identities", "record_batches_host", "RECORD_BATCH_COLUMNS", "RECORD_BATCH_CODECS"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -88,6 +89,7 @@ _SECTIONS = {
     "partitioner": (lambda P, Q: 2 * P + 2 * Q, "a partitioner vector of {} partitions and {} targets"),
     "size_quantiles": (lambda P: P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS, "a size vector of {} partitions"),
     "segments": (lambda P, M: segments_words(P, M), "a segment vector of {} partitions and {} rows"),
+    "record_batches": (lambda P: 20 * P + 1524, "a record-batch vector of {} partitions"),
     "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
     "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
 }
@@ -138,7 +140,7 @@ class HipMetricHandler:
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
                  compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
-                 compact_delete: bool = False):
+                 compact_delete: bool = False, record_batches: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -155,7 +157,9 @@ class HipMetricHandler:
         segments: (segment_bytes, rows_per_partition, record_overhead) — the segment pass of the retention what-if
         (kta_set_segments: segments(), then retention_whatif on the vector);
         compact_delete: the compact,delete what-if (kta_set_compact_delete; needs compaction=True and segments: the replay
-        also writes the kept vector, compact_delete(), for compact_delete_whatif)."""
+        also writes the kept vector, compact_delete(), for compact_delete_whatif);
+        record_batches: the record-batch section (KTA_FLAG_RECORD_BATCHES: what the batch headers of the raw-log decode say,
+        get_record_batches())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -165,11 +169,13 @@ class HipMetricHandler:
         self.partitioner_on = bool(partitioner)
         self.compaction_on = bool(compaction)
         self.size_quantiles_on = bool(size_quantiles)
+        self.record_batches_on = bool(record_batches)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
                         (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
+                        (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -259,7 +265,9 @@ class HipMetricHandler:
             kb = np.ascontiguousarray(cols["key_bytes"], dtype=np.uint8)
             keep += [ko, kb]
             b.key_off, b.key_bytes = ko.ctypes.data, kb.ctypes.data
-        m = len(keep[0]) if n is None else n
+        m = len(keep[0]) if n is None else int(n)
+        if m < 0 or any(m > len(a) for a in keep[:4]) or (len(keep) > 4 and m > len(keep[4])):   # the native loop reads m of each
+            raise ValueError(f"replay_messages: n = {m} is not in [0, {min(len(a) for a in keep[:4])}], the records the columns hold")
         self._check(self._lib.kta_replay_messages(self._ctx, C.byref(b), m))
 
     def handle_message_stats(self) -> dict:
@@ -698,6 +706,31 @@ class HipMetricHandler:
         """(device pointer, length in u64) of the size-percentile snapshot (for collectives: allreduce_size_quantiles_vector)."""
         return self._device_vector(self._lib.kta_size_quantiles_result_vector)
 
+    def get_record_batches(self) -> dict:
+        """The live record-batch vector as split_record_batches gives it (kta_get_record_batches; staged messages are
+        flushed first)."""
+        return split_record_batches(self._read_section("record_batches", self._lib.kta_get_record_batches), self.n_partitions)
+
+    def exchange_record_batches(self) -> dict:
+        """As get_record_batches(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return split_record_batches(self._read_section("record_batches", self._lib.kta_exchange_record_batches), self.n_partitions)
+
+    def record_batches_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the record-batch snapshot (for collectives: allreduce_record_batches_vector)."""
+        return self._device_vector(self._lib.kta_record_batches_result_vector)
+
+    def record_batches_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live record-batch vector."""
+        return self._device_vector(self._lib.kta_record_batches_vector)
+
+    def record_batches_info(self) -> dict:
+        """The record-batch pass's work since creation (kta_record_batches_info); kernel_ms is the mean duration of the
+        launches timed since the previous call, None without one (set_timing(True))."""
+        out, ms = (C.c_uint64 * 4)(), C.c_float()
+        self._check(self._lib.kta_record_batches_info(self._ctx, C.byref(out), C.byref(ms)))
+        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
+                "kernel_ms": float(ms.value) if out[3] else None}
+
     def size_quantiles_info(self) -> dict:
         """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""
         out = (C.c_uint64 * 6)()
@@ -1077,6 +1110,70 @@ def render_size_percentiles(vec, counter_vec, n_partitions: int) -> str:
     and the counter vector u64[P * 7 + 8] of the same records (KtaError when the two do not describe the same records)."""
     v, c = _section_vec("size_quantiles", vec, n_partitions), _counter_vec(counter_vec, n_partitions)
     return _render(N.load().kta_render_size_percentiles, _np_ptr(v), _np_ptr(c), n_partitions)
+
+
+RECORD_BATCH_COLUMNS = ("batches", "records", "wire", "payload", "compressed", "compressed_recbytes", "compressed_payload", "extent",
+                        "transactional", "idempotent", "log_append_time", "span_ms", "failed")
+RECORD_BATCH_CODECS = ("none", "gzip", "snappy", "lz4", "zstd")
+
+
+def split_record_batches(vec, n_partitions: int) -> dict:
+    """A record-batch vector u64[20 P + 1524] as a dict, split by its layout (kta_hip.h, above KTA_FLAG_RECORD_BATCHES):
+    "partitions" [P][16] (columns RECORD_BATCH_COLUMNS, then three zeros); "codecs" [5][4] batches, records, recbytes,
+    payload (rows RECORD_BATCH_CODECS) with "hist_records", "hist_wire" and "hist_span" [5][32]; "maxima" [P][4] the largest
+    n_records, wire, leader epoch + 1 and span_ms; "sketch" [1024]; "producers" the estimate; the vector under "vector"."""
+    P = n_partitions
+    v = _section_vec("record_batches", vec, P)
+    c = v[16 * P:16 * P + 500].reshape(N.KTA_RB_CODECS, N.KTA_RB_CODEC_WORDS)
+    return {"partitions": v[:16 * P].reshape(P, 16).copy(), "codecs": c[:, :4].copy(), "hist_records": c[:, 4:36].copy(),
+            "hist_wire": c[:, 36:68].copy(), "hist_span": c[:, 68:100].copy(),
+            "maxima": v[16 * P + 500:20 * P + 500].reshape(P, 4).copy(), "sketch": v[20 * P + 500:].copy(),
+            "producers": estimate_producers(v, P), "vector": v}
+
+
+def merge_record_batches(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_record_batches, in place on `acc` (contiguous uint64 / int64): sums over the first 16 P + 500 words, unsigned
+    maxima behind them."""
+    return _merge("record_batches", acc, other, n_partitions)
+
+
+def estimate_producers(vec, n_partitions: int) -> float:
+    """kta_record_batches_estimate_producers: the distinct producer ids read off a record-batch vector's sketch (standard
+    error 3.25 %; exact linear counting while few registers are set)."""
+    out = C.c_double()
+    rc = N.load().kta_record_batches_estimate_producers(_np_ptr(_section_vec("record_batches", vec, n_partitions)), n_partitions, C.byref(out))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_record_batches_estimate_producers")
+    return float(out.value)
+
+
+def record_batches_identities(vec, n_partitions: int) -> bool:
+    """kta_record_batches_identities: whether the identities between the words of one record-batch vector hold."""
+    rc = N.load().kta_record_batches_identities(_np_ptr(_section_vec("record_batches", vec, n_partitions)), n_partitions)
+    if rc < 0:
+        raise KtaError(rc, "kta_record_batches_identities")
+    return rc == 1
+
+
+def record_batches_host(blob: bytes, partition: int, n_partitions: int, inflated=None, vec=None) -> np.ndarray:
+    """kta_record_batches_host: the section's rule over the batches of `blob` on the host, added to `vec` (a new vector when
+    None).  inflated: the exact inflated size of every batch that gets a descriptor, or None for the index's own value."""
+    v = np.zeros(_section_words("record_batches", n_partitions), np.uint64) if vec is None else _section_vec("record_batches", vec, n_partitions)
+    inf = None if inflated is None else np.ascontiguousarray(inflated, np.uint64)
+    rc = N.load().kta_record_batches_host(bytes(blob), len(blob), int(partition), None if inf is None else _np_ptr(inf), _np_ptr(v), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_record_batches_host")
+    return v
+
+
+def render_record_batches(vec, n_partitions: int, filtered: bool = False, skipped=None) -> str:
+    """kta_render_record_batches: the section kta-analyzer prints with --librdkafka kta.record_batches=1.  skipped: the
+    host index's (control batches, magic 0/1 sets, unknown codecs) over the run, zeros when None."""
+    v = _section_vec("record_batches", vec, n_partitions)
+    sk = None if skipped is None else np.ascontiguousarray(skipped, np.uint64)
+    if sk is not None and sk.size != 3:
+        raise ValueError("skipped has three words: control batches, magic 0/1 sets, unknown codecs")
+    return _render(N.load().kta_render_record_batches, _np_ptr(v), n_partitions, 1 if filtered else 0, None if sk is None else _np_ptr(sk))
 
 
 def size_bin(size: int) -> int:

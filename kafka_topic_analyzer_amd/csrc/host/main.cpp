@@ -43,6 +43,9 @@
 // sections and before the filter's, every partition's model segments, records and bytes and — with kta.retention.ms=<duration>
 // and / or kta.retention.bytes=<size>, at kta.retention.now=<unix seconds> (default: the run's start) — what the policy would
 // keep.  kta.segments.rows=M (default 1024, lowered so that P * M <= 2^20) and kta.segments.overhead=B (default 0) set the model.
+// kta.record_batches=1 (0: off; segment:// sources only, kta.gpus=N and -c included, not with kta.per_message=1: the other
+// sources deliver records, not batches) runs the record-batch pass as well (KTA_FLAG_RECORD_BATCHES) and prints its section
+// behind every other one: records and bytes per batch, compression per codec, offset holes, producers.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -356,6 +359,8 @@ struct ShardedJob {
     bool partitioner = false;                          // kta.partitioner=murmur2: likewise
     uint32_t repartition = 0;                          //   kta.repartition=Q (0: P)
     bool percentiles = false;                          // kta.percentiles=1: likewise
+    bool record_batches = false;                       // kta.record_batches=1: likewise (segment:// only)
+    uint64_t rb_skipped[3] = {0, 0, 0};                //   control batches, magic 0/1 sets, unknown codecs: the host index's, whole topic
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
@@ -373,7 +378,8 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
         const uint32_t flags = (job.count_alive ? (job.synthetic ? KTA_FLAG_SEQ_COLUMN : KTA_FLAG_ALIVE_TABLE) : 0u) |
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
-                               (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u);
+                               (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) |
+                               (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -543,6 +549,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
         if (job.filter.on)
             text += kta::render_filter(job.filter.from_ms, job.filter.to_ms, job.filter.has_set ? job.filter.bitmap.data() : nullptr, job.P,
                                        (uint64_t)filter_counts[0], (uint64_t)filter_counts[1]);
+        if (job.record_batches) text += kta::render_record_batches(h0->record_batches()->data(), job.P, job.filter.on, job.rb_skipped);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -579,6 +586,21 @@ int main(int argc, char **argv)
     bool synthetic = b.rfind("synthetic://", 0) == 0, dump = b.rfind("dump://", 0) == 0;
     const bool segment = b.rfind("segment://", 0) == 0;
     const bool kafka = !synthetic && !dump && !segment;   // a broker list: the reference's own path
+    // kta.record_batches: the section is about batches, and only raw log segments have them
+    bool record_batches = false;
+    if (cfg.count("kta.record_batches")) {
+        const std::string &v = cfg["kta.record_batches"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.record_batches=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        record_batches = v == "1";
+        if (record_batches && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
+            fprintf(stderr, "kta.record_batches=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
+                            "list and kta.per_message=1 deliver records, not batches)\n");
+            return 2;
+        }
+    }
     // kta.compaction: what needs no partition count is refused here, before a broker or a device is asked for anything
     bool compaction = false;
     if (cfg.count("kta.compaction")) {
@@ -906,6 +928,7 @@ int main(int argc, char **argv)
     std::vector<std::vector<uint8_t>> segment_bytes;
     std::vector<uint64_t> segment_base_seq;   // records of the partitions before each one (consumption order: file by file)
     uint64_t segment_records = 0;
+    uint64_t rb_skipped[3] = {0, 0, 0};       // kta.record_batches=1: what the host index counts and the section cannot
     if (segment) {  // watermarks = first / last offset found in each partition's segment (kafka.rs:60-72)
         for (uint32_t p = 0; p < P; p++) {
             std::vector<uint8_t> bytes;
@@ -934,6 +957,7 @@ int main(int argc, char **argv)
             }
             segment_base_seq.push_back(segment_records);
             if (rc == KTA_OK) segment_records += ist.n_records;
+            if (rc == KTA_OK) rb_skipped[0] += ist.n_control_batches, rb_skipped[1] += ist.n_old_magic, rb_skipped[2] += ist.n_compressed;
             segment_bytes.push_back(std::move(bytes));
         }
     }
@@ -966,6 +990,8 @@ int main(int argc, char **argv)
         job.partitioner = partitioner;
         job.repartition = repartition;
         job.percentiles = percentiles;
+        job.record_batches = record_batches;
+        std::copy(rb_skipped, rb_skipped + 3, job.rb_skipped);
         job.filter = filter;
         job.segments = segments;
         job.batch = batch;
@@ -987,7 +1013,7 @@ int main(int argc, char **argv)
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                                 (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
-                                                (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u),
+                                                (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1235,6 +1261,7 @@ int main(int argc, char **argv)
         if (filter.on)
             text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, filter_info[0],
                                        filter_info[1]);
+        if (record_batches) text += kta::render_record_batches(handler->record_batches()->data(), P, filter.on, rb_skipped);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -74,7 +74,8 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
     : P_(n_partitions), alive_(count_alive_keys), analytics_on_((flags & KTA_FLAG_ANALYTICS) != 0), timeline_(timeline),
       sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0),
       tso_on_((flags & KTA_FLAG_TS_ORDER) != 0), part_on_((flags & KTA_FLAG_PARTITIONER) != 0),
-      part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u), sizeq_on_((flags & KTA_FLAG_SIZE_QUANTILES) != 0)
+      part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u), sizeq_on_((flags & KTA_FLAG_SIZE_QUANTILES) != 0),
+      rb_on_((flags & KTA_FLAG_RECORD_BATCHES) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -216,6 +217,10 @@ void HipMetricHandler::read_analytics()
     if (sizeq_on_) {
         qvec_.assign((size_t)P_ * KTA_SIZE_QUANTITIES * KTA_SIZE_BINS + KTA_SIZE_GLOBALS, 0);
         check(kta_exchange_size_quantiles(ctx_, qvec_.data(), qvec_.size()), "kta_exchange_size_quantiles");
+    }
+    if (rb_on_) {
+        bvec_.assign(KTA_RB_WORDS(P_), 0);
+        check(kta_exchange_record_batches(ctx_, bvec_.data(), bvec_.size()), "kta_exchange_record_batches");
     }
     if (seg_rows_) {
         gvec_.assign(kta_segments_words((uint32_t)P_, seg_rows_), 0);

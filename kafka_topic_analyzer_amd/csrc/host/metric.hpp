@@ -149,6 +149,8 @@ public:
     // With KTA_FLAG_SIZE_QUANTILES: the size vector u64[P * 3 * 464 + 8] of the snapshot finish() / exchange() took (after
     // exchange(), the whole job's); nullptr without the flag.
     const std::vector<uint64_t> *size_quantiles() const { return sizeq_on_ ? &qvec_ : nullptr; }
+    // With KTA_FLAG_RECORD_BATCHES: the record-batch vector u64[20 P + 1524] of that snapshot; nullptr without the flag.
+    const std::vector<uint64_t> *record_batches() const { return rb_on_ ? &bvec_ : nullptr; }
     // The segment pass of the retention what-if (kta_set_segments): right after construction, before any record; then the
     // segment vector u64[(P M + P) 4 + 8] of the snapshot finish() / exchange() took (after exchange(), the whole job's);
     // nullptr without it.
@@ -193,6 +195,8 @@ private:
     std::vector<uint64_t> pvec_;
     bool sizeq_on_ = false;
     std::vector<uint64_t> qvec_;
+    bool rb_on_ = false;
+    std::vector<uint64_t> bvec_;
     uint32_t seg_rows_ = 0;   // M; 0: no segments
     std::vector<uint64_t> gvec_;
 };
@@ -227,6 +231,8 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
 // the opt-in section kta-analyzer prints with kta.percentiles=1 after the report's closing rule and the analytics
 // (kta_render_size_percentiles): vec u64[P * 3 * 464 + 8]
 std::string render_size_percentiles(const uint64_t *vec, uint32_t P);
+// (kta_render_record_batches): vec u64[20 P + 1524]; skipped: control batches, magic 0/1 sets, unknown codecs of the run
+std::string render_record_batches(const uint64_t *vec, uint32_t P, bool filtered, const uint64_t skipped[3]);
 // the opt-in section kta-analyzer prints with kta.segments=<size> after the partitioner and compaction sections and before
 // the filter's (kta_render_retention): vec u64[(P M + P) 4 + 8]; retention -1: the rule is off
 std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes);

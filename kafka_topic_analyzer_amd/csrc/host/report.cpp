@@ -10,6 +10,7 @@
 
 #include "kta_compact_delete.h"
 #include "kta_compaction.h"
+#include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
 #include "metric.hpp"
@@ -607,6 +608,85 @@ std::string render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *bitmap
     return o;
 }
 
+// The opt-in record-batch section (kta.record_batches=1): no reference counterpart, printed after everything else.  vec:
+// u64[20 P + 1524] (kta_hip.h; the layout is kta_record_batches.h's).  skipped: the host index's control batches, magic 0/1
+// sets and batches of an unknown codec over the run.  A figure whose denominator is 0 is `n/a`.
+std::string render_record_batches(const uint64_t *vec, uint32_t P, bool filtered, const uint64_t skipped[3])
+{
+    auto ratio = [](uint64_t num, uint64_t den, double scale) -> std::string {
+        if (den == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)num * scale / (double)den);
+        return buf;
+    };
+    // the upper end of the bin in which a histogram reaches num/den of its count (nearest rank)
+    auto bin_quantile = [](const uint64_t *hist, uint64_t num, uint64_t den) -> std::string {
+        uint64_t count = 0;
+        for (uint32_t b = 0; b < kRbHistBins; b++) count += hist[b];
+        if (count == 0) return "n/a";
+        uint64_t rank = (count * num + den - 1) / den, run = 0;
+        if (rank == 0) rank = 1;
+        for (uint32_t b = 0; b < kRbHistBins; b++) {
+            run += hist[b];
+            if (run >= rank) return b == 0 ? "0" : (b == kRbHistBins - 1 ? ">=" + std::to_string(1ull << 30) : std::to_string((1ull << b) - 1));
+        }
+        return "n/a";
+    };
+    auto row_of = [&](const std::string &name, const uint64_t *w, const uint64_t *mx) {
+        const uint64_t batches = w[kRbBatches], holes = w[kRbExtent] - w[kRbRecords];
+        return std::vector<std::string>{name,
+                                        std::to_string(batches),
+                                        ratio(w[kRbRecords], batches, 1.0),
+                                        std::to_string(mx[kRbMaxRecords]),
+                                        ratio(w[kRbWire], batches, 1.0),
+                                        std::to_string(mx[kRbMaxWire]),
+                                        ratio(w[kRbSpanMs], batches, 1.0),
+                                        ratio(w[kRbCompressed], batches, 100.0),
+                                        ratio(w[kRbCompressedPayload], w[kRbCompressedRecbytes], 1.0),
+                                        std::to_string(holes),
+                                        ratio(holes, w[kRbExtent], 100.0),
+                                        ratio(w[kRbIdempotent], batches, 100.0),
+                                        ratio(w[kRbTransactional], batches, 100.0),
+                                        ratio(w[kRbLogAppendTime], batches, 100.0),
+                                        mx[kRbMaxEpoch1] ? std::to_string(mx[kRbMaxEpoch1] - 1) : "-",
+                                        std::to_string(w[kRbFailed])};
+    };
+    std::string o;
+    o += "Record batches: what the batch headers of the log say (kta.record_batches=1; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Batches", "Rec/batch", "Largest", "B/batch", "Largest", "Span ms", "Compressed %", "Ratio", "Holes", "Holes %",
+                    "Idempotent %", "Transactional %", "LogAppendTime %", "Epoch", "Failed"});
+    uint64_t all[kRbPartitionWords] = {}, all_mx[kRbMaxWords] = {};
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t *w = vec + (size_t)kRbPartitionWords * p, *mx = vec + rb_max_at(P, p);
+        for (uint32_t k = 0; k < kRbPartitionWords; k++) all[k] += w[k];
+        for (uint32_t k = 0; k < kRbMaxWords; k++) all_mx[k] = std::max(all_mx[k], mx[k]);
+        rows.push_back(row_of(std::to_string(p), w, mx));
+    }
+    rows.push_back(row_of("Topic", all, all_mx));
+    o += pretty_table(rows);
+    static const char *const kCodecNames[kRbCodecs] = {"none", "gzip", "snappy", "lz4", "zstd"};
+    rows.clear();
+    rows.push_back({"Codec", "Batches", "Records", "Bytes on disk", "Inflated bytes", "Ratio", "Rec/batch p50", "p90", "B/batch p50", "p90"});
+    for (uint32_t c = 0; c < kRbCodecs; c++) {
+        const uint64_t *cw = vec + rb_codec_at(P, c);
+        rows.push_back({kCodecNames[c], std::to_string(cw[kRbCodecBatches]), std::to_string(cw[kRbCodecRecords]), std::to_string(cw[kRbCodecRecbytes]),
+                        std::to_string(cw[kRbCodecPayload]), ratio(cw[kRbCodecPayload], cw[kRbCodecRecbytes], 1.0),
+                        bin_quantile(cw + kRbCodecHistRecords, 50, 100), bin_quantile(cw + kRbCodecHistRecords, 90, 100),
+                        bin_quantile(cw + kRbCodecHistWire, 50, 100), bin_quantile(cw + kRbCodecHistWire, 90, 100)});
+    }
+    o += pretty_table(rows);
+    o += "Percentiles are the upper ends of power-of-two bins; bytes on disk and inflated bytes are the records alone, without the 61-byte headers.\n";
+    char buf[96];
+    snprintf(buf, sizeof buf, "Producers (estimated from the idempotent batches, +/- %.2f %%): %.0f\n", kRbStdError * 100.0, rb_estimate(vec + rb_sketch_at(P)));
+    o += buf;
+    o += "Not counted: control batches (" + std::to_string(skipped[0]) + "), magic 0/1 message sets (" + std::to_string(skipped[1]) +
+         "), batches of an unknown codec (" + std::to_string(skipped[2]) + ") and batches without records; a failed batch adds to Failed alone.\n";
+    if (filtered) o += "With the record filter: these are the batches that overlap the window on the selected partitions, not the records that passed.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
 static uint32_t fmix32(uint32_t x)
 {
@@ -740,6 +820,21 @@ extern "C" int kta_render_size_percentiles(const uint64_t *vec, const uint64_t *
                                    KTA_G_BAD_PARTITION))
         return KTA_ERR_INVALID;
     const std::string text = kta::render_size_percentiles(vec, n_partitions);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_record_batches(const uint64_t *vec, uint32_t n_partitions, int filtered, const uint64_t *skipped, char *out,
+                                         size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || n_partitions == 0 || n_partitions > 4096) return KTA_ERR_INVALID;
+    static const uint64_t kNone[3] = {0, 0, 0};
+    const std::string text = kta::render_record_batches(vec, n_partitions, filtered != 0, skipped ? skipped : kNone);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

@@ -9,6 +9,7 @@
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
+#include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
 
@@ -129,6 +130,10 @@ struct kta_ctx {
     DeviceBuf<uint64_t> d_sizeq, d_sizeq_out, d_sizeq_stats;
     uint32_t sizeq_slice = 0, sizeq_last_workgroups = 0;
     int sizeq_variant = 0;
+    // record batches (KTA_FLAG_RECORD_BATCHES): d_rb u64[20 P + 1524] the live vector that kta_kafka.hip's decode call adds to
+    // (kta_internal_record_batches), d_rb_out its snapshot
+    bool rb = false;
+    DeviceBuf<uint64_t> d_rb, d_rb_out;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -875,6 +880,7 @@ Shape segments_shape(uint32_t P, uint32_t M)
     const size_t words = kta::segments_len(P, M);
     return Shape{words, words - kta::kSegGlobals + kta::kSegGlobalS, false};
 }
+Shape record_batches_shape(uint32_t P) { return Shape{kta::rb_len(P), kta::rb_sum_words(P), false}; }
 Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
 
 // what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
@@ -886,6 +892,13 @@ static_assert(kta::kSizePartitionWords == KTA_SIZE_QUANTITIES * KTA_SIZE_BINS &&
 static_assert(kta::kCompactionWords == KTA_COMPACTION_WORDS && kta::kCompactionGlobals == KTA_COMPACTION_GLOBALS, "kta_compaction.h and kta_hip.h");
 static_assert(kta::kRetWords == KTA_RETENTION_WORDS, "the what-if's row is said twice: kta_segments.h and kta_hip.h");
 static_assert(kta::kCdWords == KTA_COMPACT_DELETE_WORDS, "the what-if's row is said twice: kta_compact_delete.h and kta_hip.h");
+static_assert(kta::kRbPartitionWords == KTA_RB_PARTITION_WORDS && kta::kRbCodecs == KTA_RB_CODECS && kta::kRbCodecWords == KTA_RB_CODEC_WORDS &&
+                  kta::kRbHistBins == KTA_RB_HIST_BINS && kta::kRbMaxWords == KTA_RB_MAX_WORDS && kta::kRbSketchRegs == KTA_RB_SKETCH_REGISTERS,
+              "kta_record_batches.h and kta_hip.h");
+static_assert(KTA_RB_WORDS(7) == 20 * 7 + 1524 && KTA_RB_SUM_WORDS(7) == 16 * 7 + 500 &&
+                  kta::kRbPartitionWords * 7 + kta::kRbCodecTable == KTA_RB_SUM_WORDS(7) &&
+                  KTA_RB_SUM_WORDS(7) + kta::kRbMaxWords * 7 + kta::kRbSketchRegs == KTA_RB_WORDS(7),
+              "the record-batch vector's length: kta_record_batches.h and kta_hip.h");
 
 // One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
 // and out point at the context's owners, allocated or not.
@@ -919,6 +932,8 @@ void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
                                        "context was created without KTA_FLAG_SIZE_QUANTILES"};
     s[KTA_RV_SEGMENTS] = Section{ctx->seg, &ctx->d_seg, &ctx->d_seg_out, segments_shape(P, ctx->seg_M), false, "segment vector",
                                  "the context has no segments (kta_set_segments)"};
+    s[KTA_RV_RECORD_BATCHES] = Section{ctx->rb, &ctx->d_rb, &ctx->d_rb_out, record_batches_shape(P), true, "record-batch vector",
+                                       "context was created without KTA_FLAG_RECORD_BATCHES"};
     s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
                                     "context was created without KTA_FLAG_COMPACTION"};
     s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
@@ -1213,6 +1228,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->part_q = ctx->part ? ctx->P : 0u;
     ctx->comp = (cfg->flags & KTA_FLAG_COMPACTION) != 0;
     ctx->sizeq = (cfg->flags & KTA_FLAG_SIZE_QUANTILES) != 0;
+    ctx->rb = (cfg->flags & KTA_FLAG_RECORD_BATCHES) != 0;
     {
         const char *qv = getenv("KTA_SIZEQ_VARIANT");   // A/B switch of tools/bench_size_quantiles.py: 1 a launch per slice, 9 loads only
         ctx->sizeq_variant = qv && (qv[0] == '1' || qv[0] == '9') && !qv[1] ? qv[0] - '0' : 0;
@@ -2250,6 +2266,56 @@ int kta_size_quantiles_info(kta_ctx *ctx, uint64_t out[6])
     return rc;
 }
 
+// ---- record batches (kta_record_batches.h holds the rule, kta_record_batches.hip the kernel, kta_kafka.hip the launch) ----
+
+int kta_get_record_batches(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_RECORD_BATCHES, out, n_u64); }
+int kta_exchange_record_batches(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_RECORD_BATCHES, out, n_u64); }
+int kta_record_batches_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_RECORD_BATCHES, true, device_ptr, n_u64);
+}
+int kta_record_batches_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_RECORD_BATCHES, false, device_ptr, n_u64);
+}
+
+int kta_merge_record_batches(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    return merge_section(acc, other, P != 0 && P <= 4096, record_batches_shape(P));
+}
+
+int kta_record_batches_estimate_producers(const uint64_t *vec, uint32_t P, double *out)
+{
+    if (!vec || !out || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    *out = kta::rb_estimate(vec + kta::rb_sketch_at(P));
+    return KTA_OK;
+}
+
+int kta_record_batches_identities(const uint64_t *vec, uint32_t P)
+{
+    if (!vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    return kta::rb_identities_hold(vec, P) ? 1 : 0;
+}
+
+int kta_record_batches_host(const uint8_t *bytes, uint64_t len, int32_t partition, const uint64_t *inflated, uint64_t *vec, uint32_t P)
+{
+    if (!bytes || !vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    kta_kafka_index_stats st;
+    int rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, nullptr, 0, &st);
+    if (rc != KTA_OK && rc != KTA_ERR_CAPACITY) return rc;
+    std::vector<kta_kafka_batch_desc> descs(st.n_batches);
+    rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, descs.data(), descs.size(), &st);
+    if (rc != KTA_OK) return rc;
+    for (size_t i = 0; i < descs.size(); i++) {
+        kta_kafka_batch_desc d = descs[i];
+        if (inflated && (d.flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD))) d.payload_end = d.payload_off + inflated[i];
+        if (!kta::rb_counted(kta::rb_no_filter(), P, d.partition, d.base_ts_ms, d.max_ts_ms)) continue;
+        const bool inside = kta::rb_header_inside(d.byte_off, len);
+        kta::rb_accumulate(vec, P, (uint32_t)d.partition, inside && d.status == 0 ? kta::rb_batch(d, kta::rb_fields(bytes + d.byte_off)) : kta::rb_failed_batch());
+    }
+    return KTA_OK;
+}
+
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
 
 int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
@@ -2783,6 +2849,13 @@ uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }
 bool kta_internal_compaction(kta_ctx *ctx) { return ctx->comp; }
+bool kta_internal_record_batches(kta_ctx *ctx, kta_internal_rb *out)
+{
+    const bool f = ctx->filter;
+    *out = kta_internal_rb{ctx->rb, ctx->d_rb.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
+                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
+    return ctx->rb && !ctx->comp_replay;
+}
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {
     *out = kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()};

@@ -14,9 +14,11 @@
 #include <vector>
 
 #include "kta_hip.h"
+#include "kta_kafka.h"
 
 namespace kta {
 struct WrittenList;   // kta_kernels.h
+struct RbFilter;      // kta_record_batches.h
 }
 
 // ---- the context, as the other translation units see it (defined in kta_api.hip) ----------------------------------
@@ -38,6 +40,24 @@ uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);
 uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
+// The record-batch section (KTA_FLAG_RECORD_BATCHES) as the decode call sees it.  Returns whether the pass runs now: the flag
+// on and no compaction replay (the replay reads the source a second time; batches are counted once).  on: the flag alone.
+// from_ms / to_ms / bitmap: the context's filter (kta_set_filter: INT64_MIN / INT64_MAX no bound; the partition set on the
+// device, null without one).
+struct kta_internal_rb {
+    bool on;
+    uint64_t *vec;   // the live vector (device)
+    int64_t from_ms, to_ms;
+    const uint32_t *bitmap;
+    int cu_count;
+};
+bool kta_internal_record_batches(kta_ctx *ctx, kta_internal_rb *out);
+// The pass over `n` descriptors (device memory, after the call's inflate and decode kernels) and the blob they index
+// (kta_record_batches.hip); f.bitmap on the device.  *workgroups = the grid.
+namespace kta {
+hipError_t launch_record_batches(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint64_t blob_len, uint32_t P,
+                                 const RbFilter &f, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s);
+}
 // Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
 // allocation that the range overlaps become raw (partition, ts_ms and, in a keyless allocation, the lengths), on the
 // compute stream.
@@ -75,6 +95,7 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns 
 //   partitioner 2*P + 2*Q          all            none
 //   size quant. P*3*464 + 8        all            none
 //   segments    (P*M + P)*4 + 8    all but 5      5      (u64: S, M, overhead and two zero words, equal on every rank)
+//   rec.batches 20*P + 1524        16*P + 500     4*P + 1024 (u64: the partitions' maxima and the producer sketch)
 //   compaction  5*P + 6            (live only: the replay's vector, kta_get_compaction)
 //   kept        (P*M + P)*4 + 8    (live only: the replay's kept vector, kta_get_compact_delete; the segments' shape)
 struct ResultVector {
@@ -83,7 +104,7 @@ struct ResultVector {
     bool max_signed;
 };
 enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_PARTITIONER,
-       KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_KINDS,
+       KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_RECORD_BATCHES, KTA_RV_KINDS,
        KTA_SEC_COMPACTION = KTA_RV_KINDS, KTA_SEC_KEPT, KTA_SEC_KINDS };
 // The snapshot kinds of the section table; a section that is off has out == nullptr and words == 0.
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);

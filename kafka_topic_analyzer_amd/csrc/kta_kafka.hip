@@ -28,6 +28,7 @@
 #include "kta_zstd.h"
 #include "kta_records.h"
 #include "kta_internal.h"
+#include "kta_record_batches.h"
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -1162,6 +1163,9 @@ struct KafkaState {
     int cur = 0;
     bool acquired = false;
     TimerPool<2> timers{1024};      // kind 0: the CRC kernel, 1: the decode
+    TimerPool<1> rb_timers{1024};   // the record-batch pass (kta_record_batches_info)
+    uint64_t rb_launches = 0, rb_batches = 0;
+    uint32_t rb_workgroups = 0;     // of the last launch
 };
 
 void free_out(kta_batch &o)
@@ -1636,6 +1640,16 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
 #undef KTA_DECODE_COOP
     KTA_HIP(ctx, hipGetLastError());
     if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+    // The record-batch section (KTA_FLAG_RECORD_BATCHES): the descriptors are final here — status, the inflated sizes — and
+    // they and the blob are still alive.  Off, or during a compaction replay (the source is read a second time): nothing runs.
+    if (kta_internal_rb rb{}; kta_internal_record_batches(ctx, &rb)) {
+        if (timing) { int rc = st->rb_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        KTA_HIP_AS(ctx, kta::launch_record_batches(d_descs, n_batches, blob_device, blob_len, kta_internal_partitions(ctx),
+                                                   kta::RbFilter{rb.from_ms, rb.to_ms, rb.bitmap}, rb.vec, rb.cu_count, &st->rb_workgroups, s),
+                   "kta_record_batches");
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+        st->rb_launches++, st->rb_batches += n_batches;
+    }
     KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
         KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -1876,6 +1890,23 @@ int kta_kafka_set_variant(kta_ctx *ctx, int variant)
 {
     if (!ctx || !(variant == 0 || variant == 1 || variant == 2 || variant == 10 || variant == 11)) return KTA_ERR_INVALID;
     state_of(ctx)->variant = variant;
+    return KTA_OK;
+}
+
+int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_rb rb{};
+    (void)kta_internal_record_batches(ctx, &rb);
+    if (!rb.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_RECORD_BATCHES");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KafkaState *st = state_of(ctx);
+    float ms = -1.f;
+    uint64_t timed = 0;
+    int rc = st->rb_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    out[0] = st->rb_launches, out[1] = st->rb_batches, out[2] = st->rb_workgroups, out[3] = timed;
+    if (avg_ms) *avg_ms = ms;
     return KTA_OK;
 }
 

@@ -114,6 +114,15 @@ def allreduce_size_quantiles_vector(qvec, n_partitions: int, group=None) -> None
     _allreduce_sum_max(qvec, qvec.numel(), group)
 
 
+def allreduce_record_batches_vector(bvec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the record-batch SNAPSHOT (kta_record_batches_result_vector: device tensor, or a
+    CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_RECORD_BATCHES: all-reduce SUM
+    over the first 16 P + 500 words (i64 wrap == u64 wrap) and all-reduce MAX over the 4 P + 1024 words behind them — counts,
+    bytes, leader epochs + 1, clamped spans and sketch ranks, all below 2^63, so signed MAX == unsigned MAX."""
+    assert bvec.numel() == 20 * n_partitions + 1524
+    _allreduce_sum_max(bvec, 16 * n_partitions + 500, group)
+
+
 def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
     """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
     tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM
