@@ -383,6 +383,41 @@ typedef struct kta_hot_key {
 #define KTA_RB_WORDS(P) (20u * (size_t)(P) + 1524u)
 #define KTA_RB_SUM_WORDS(P) (16u * (size_t)(P) + 500u)
 
+/* Payload (NOT in the reference, which never looks inside a value): what lies inside the records that the raw-log decode
+ * delivers (kta_kafka.h: kta_kafka_decode_device, and through it kta_kafka_blob_submit and kta_kafka_consume) — the class of
+ * every value, the schema-registry ids of the values in Confluent's wire format, and the record headers.  Opt-in at
+ * kta_create.  Every word is exact and a SUM.  csrc/kta_payload.h is the code of everything below.
+ * A record COUNTS when its batch's descriptor has status 0 after the call's inflate and decode kernels, its framing and that
+ * of every record in front of it in the batch is good, its partition lies in [0, P) and, under kta_set_filter, it passes the
+ * filter (its timestamp as the decode gives it: base_ts_ms + delta, or max_ts_ms under LogAppendTime).
+ * Value class, exactly one: null (length -1); empty (0); framed (length >= 5 and byte 0 == 0x00: the id is bytes 1..4, big
+ * endian); json (byte 0 is `{` or `[`); other.
+ * Headers: headersCount varint, then per header keyLen varint | key | valueLen varint (-1: null) | value, up to the record's
+ * end as its length prefix gives it.  BAD when the count or a key length is negative, a value length is below -1, a varint
+ * runs on past ten bytes, a field overruns the record or the walk does not end exactly at the record's end (so also when
+ * the section is absent).  A record with bad headers adds 1 to bad_headers and nothing to another header word or to the
+ * histogram; its value counts all the same.
+ * The vector is u64[24 P + 16 + 2 * 1024 * 34]:
+ *   partition p, 24 words at 24 p: records; null, empty, framed, json, other records; the value bytes of the five classes;
+ *     with_headers, headers, header_key_bytes, header_value_bytes, header_null_values, bad_headers, header_wire_bytes (the
+ *     bytes from the headersCount varint to the record's end); six zeros;
+ *   16 words at 24 P: records by their number of headers, 0 .. 14 and >= 15, over the topic;
+ *   the schema-id table at 24 P + 16: two rows of 1024 cells of 34 words — T records, B value bytes, 32 bit counters.  A
+ *     framed record with id x adds 1 to T, its value length to B and 1 to the counter of every set bit of x, in cell
+ *     x & 1023 of row 0 and in cell fmix32(x) & 1023 of row 1 (murmur3's finaliser).
+ * kta_payload_schema_ids reads the ids off the table; kta_payload_identities states the identities between the words.
+ * Composition.  During a compaction replay (kta_compaction_replay) the source is read a second time and the pass is skipped:
+ * records are counted once.  Failed batches (status != 0) add nothing; the record-batch section counts them.
+ * With the flag off no kernel is launched and nothing is allocated. */
+#define KTA_FLAG_PAYLOAD 0x400U          /* 1024: bit 10 */
+#define KTA_PAYLOAD_PARTITION_WORDS 24
+#define KTA_PAYLOAD_CLASSES 5            /* null, empty, framed, json, other */
+#define KTA_PAYLOAD_HIST_BINS 16
+#define KTA_PAYLOAD_ROWS 2
+#define KTA_PAYLOAD_CELLS 1024
+#define KTA_PAYLOAD_CELL_WORDS 34
+#define KTA_PAYLOAD_WORDS(P) (24u * (size_t)(P) + 16u + 2u * 1024u * 34u)
+
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
  * both hold:
@@ -1021,6 +1056,38 @@ int kta_record_batches_identities(const uint64_t *vec, uint32_t n_partitions);
 int kta_record_batches_host(const uint8_t *bytes, uint64_t len, int32_t partition, const uint64_t *inflated, uint64_t *vec,
                             uint32_t n_partitions);
 
+/* Payload (context created with KTA_FLAG_PAYLOAD; definition above KTA_FLAG_PAYLOAD).  kta_reset zeroes the vector;
+ * kta_finish_device snapshots it; kta_exchange reduces the snapshot (all SUM).  Every call below that takes a context fails
+ * on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_PAYLOAD.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_PAYLOAD_WORDS(P); staged messages are flushed first). */
+int kta_get_payload(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes, copied to out[n_u64]: after kta_exchange the whole
+ * job's vector on every rank.  The live accumulator is never reduced, so a second exchange counts nothing twice. */
+int kta_exchange_payload(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot (what collectives reduce in place), and of the live vector. */
+int kta_payload_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+int kta_payload_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[KTA_PAYLOAD_WORDS(P)]: acc <- acc + other.  KTA_ERR_INVALID for a P outside [1, 4096]. */
+int kta_merge_payload(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* 1 when the identities between the words of one vector hold, 0 when not (host only): the class counts sum to the records
+ * and the bytes of null and empty are 0, per partition; the histogram sums to records - bad_headers and its bin 0 equals
+ * records - with_headers - bad_headers, over the topic; each table row's T and B sum to the framed records and bytes; no bit
+ * counter exceeds its cell's T.  counter_vec: NULL, or the counter vector u64[7 P + 8] of the same UNFILTERED run without
+ * failed batches: records == total_messages (which includes the tombstones) and null == tombstones, per partition. */
+int kta_payload_identities(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions);
+/* The schema ids read off a vector's table (host only), sorted by records (most first), then bytes, then id: *n of them,
+ * the first min(*n, cap) in ids / records / bytes (cap 0: the arrays may be NULL).  A cell is PURE when T > 0, every bit
+ * counter is 0 or T and the id so spelled maps to this cell in this row; a pure cell gives its id's exact records and bytes.
+ * A recovered id is peeled — subtracted from its cell in the other row — and the rows are looked at again until nothing
+ * changes (an invertible Bloom lookup table: what it lists is exact).  *unresolved_records / *unresolved_bytes (may be NULL):
+ * what then remains in row 0, the records in cells that hold several ids — reported, never guessed at. */
+int kta_payload_schema_ids(const uint64_t *vec, uint32_t n_partitions, uint32_t *ids, uint64_t *records, uint64_t *bytes, size_t cap,
+                           size_t *n, uint64_t *unresolved_records, uint64_t *unresolved_bytes);
+/* The same rule on the host, for tests and the CPU suite (the product accumulates on the device only): the records of the
+ * batches that kta_kafka_index_host finds in bytes[0, len) of `partition` are added to vec[KTA_PAYLOAD_WORDS(P)];
+ * compressed batches are inflated with kta_*_inflate_host.  A partition outside [0, P) adds nothing.  No filter. */
+int kta_payload_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t n_partitions);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1295,6 +1362,19 @@ int kta_render_compact_delete(const uint64_t *seg_vec, const uint64_t *kept_vec,
  * A ratio, mean or share whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
 int kta_render_record_batches(const uint64_t *vec, uint32_t n_partitions, int filtered, const uint64_t *skipped, char *out,
                               size_t out_cap, size_t *out_len);
+/* The opt-in payload section that kta-analyzer prints behind every other section with --librdkafka kta.payload=1, from a
+ * payload vector (host only):
+ *   a title line saying that it is not part of the reference report;
+ *   a table (P | Records | Null % | Empty % | Framed % | JSON % | Other % | With headers | Headers/rec | Header bytes % | Bad
+ *    headers) with a row per partition and a `Topic` row: the shares of the records with two decimals, Headers/rec = headers
+ *    over the records whose headers are good, Header bytes % = header_wire_bytes over key + value + header_wire_bytes with
+ *    key + value = the counter vector's key_size_sum + value_size_sum (counter_vec NULL: `n/a`);
+ *   the histogram of headers per record (Headers | Records), bins 0 .. 14 and >= 15;
+ *   the schema ids (Schema id | Records | Bytes | B/record) sorted by records, at most 64 rows, then `... and K more`, then
+ *    the unresolved remainder when it is not zero;
+ *   a note with the section's limits, and a closing `=` rule.
+ * A share or mean whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
+int kta_render_payload(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
 int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
                       uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 

@@ -35,7 +35,8 @@
  * `check.crcs` defaults to false and the reference does not set it (src/kafka.rs:28-36).
  * What the batch headers themselves say — records per batch, bytes on disk against inflated bytes per codec, idempotent and
  * transactional producers, leader epochs, offset holes — is accumulated on the device by the opt-in record-batch section
- * (KTA_FLAG_RECORD_BATCHES, kta_hip.h), from the descriptors and the headers of every decode call.
+ * (KTA_FLAG_RECORD_BATCHES, kta_hip.h), from the descriptors and the headers of every decode call; what lies inside the
+ * records — value formats, schema-registry ids, record headers — by the opt-in payload section (KTA_FLAG_PAYLOAD).
  */
 #ifndef KTA_KAFKA_H
 #define KTA_KAFKA_H
@@ -211,6 +212,11 @@ int kta_kafka_time_stats(kta_ctx *ctx, float avg_ms[2], uint64_t launches[2]);
  * batches handed to it, out[2] workgroups of the last launch, out[3] launches timed since the previous call; *avg_ms
  * (may be NULL) their mean duration, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute stream. */
 int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
+
+/* The payload pass (KTA_FLAG_PAYLOAD, kta_hip.h) since the context was created: out[0] launches, out[1] batches handed to
+ * it, out[2] workgroups of the last launch, out[3] launches timed since the previous call; *avg_ms (may be NULL) their mean
+ * duration, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute stream. */
+int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
 
 #ifdef __cplusplus
 }

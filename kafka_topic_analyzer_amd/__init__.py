@@ -35,7 +35,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "split_segments", "merge_segments", "retention_whatif", "RETENTION_COLUMNS", "render_retention",
            "compact_delete_max_partitions", "split_compact_delete", "compact_delete_whatif", "COMPACT_DELETE_COLUMNS",
            "render_compact_delete", "split_record_batches", "merge_record_batches", "render_record_batches", "estimate_producers",
-           "record_batches_identities", "record_batches_host", "RECORD_BATCH_COLUMNS", "RECORD_BATCH_CODECS"]
+           "record_batches_identities", "record_batches_host", "RECORD_BATCH_COLUMNS", "RECORD_BATCH_CODECS", "split_payload", "merge_payload",
+           "payload_identities", "payload_schema_ids", "payload_host", "render_payload", "PAYLOAD_COLUMNS", "PAYLOAD_CLASSES"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -90,6 +91,7 @@ _SECTIONS = {
     "size_quantiles": (lambda P: P * N.KTA_SIZE_QUANTITIES * N.KTA_SIZE_BINS + N.KTA_SIZE_GLOBALS, "a size vector of {} partitions"),
     "segments": (lambda P, M: segments_words(P, M), "a segment vector of {} partitions and {} rows"),
     "record_batches": (lambda P: 20 * P + 1524, "a record-batch vector of {} partitions"),
+    "payload": (lambda P: 24 * P + 16 + 2 * 1024 * 34, "a payload vector of {} partitions"),
     "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
     "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
 }
@@ -140,7 +142,7 @@ class HipMetricHandler:
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
                  compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
-                 compact_delete: bool = False, record_batches: bool = False):
+                 compact_delete: bool = False, record_batches: bool = False, payload: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -159,7 +161,9 @@ class HipMetricHandler:
         compact_delete: the compact,delete what-if (kta_set_compact_delete; needs compaction=True and segments: the replay
         also writes the kept vector, compact_delete(), for compact_delete_whatif);
         record_batches: the record-batch section (KTA_FLAG_RECORD_BATCHES: what the batch headers of the raw-log decode say,
-        get_record_batches())."""
+        get_record_batches());
+        payload: the payload section (KTA_FLAG_PAYLOAD: value formats, schema-registry ids and record headers of the records of
+        the raw-log decode, get_payload())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -170,12 +174,13 @@ class HipMetricHandler:
         self.compaction_on = bool(compaction)
         self.size_quantiles_on = bool(size_quantiles)
         self.record_batches_on = bool(record_batches)
+        self.payload_on = bool(payload)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
                         (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
-                        (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) |
+                        (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) | (N.KTA_FLAG_PAYLOAD if payload else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -731,6 +736,30 @@ class HipMetricHandler:
         return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
                 "kernel_ms": float(ms.value) if out[3] else None}
 
+    def get_payload(self) -> dict:
+        """The live payload vector as split_payload gives it (kta_get_payload; staged messages are flushed first)."""
+        return split_payload(self._read_section("payload", self._lib.kta_get_payload), self.n_partitions)
+
+    def exchange_payload(self) -> dict:
+        """As get_payload(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return split_payload(self._read_section("payload", self._lib.kta_exchange_payload), self.n_partitions)
+
+    def payload_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the payload snapshot (for collectives: allreduce_payload_vector)."""
+        return self._device_vector(self._lib.kta_payload_result_vector)
+
+    def payload_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live payload vector."""
+        return self._device_vector(self._lib.kta_payload_vector)
+
+    def payload_info(self) -> dict:
+        """The payload pass's work since creation (kta_payload_info); kernel_ms is the mean duration of the launches timed
+        since the previous call, None without one (set_timing(True))."""
+        out, ms = (C.c_uint64 * 4)(), C.c_float()
+        self._check(self._lib.kta_payload_info(self._ctx, C.byref(out), C.byref(ms)))
+        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
+                "kernel_ms": float(ms.value) if out[3] else None}
+
     def size_quantiles_info(self) -> dict:
         """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""
         out = (C.c_uint64 * 6)()
@@ -1174,6 +1203,76 @@ def render_record_batches(vec, n_partitions: int, filtered: bool = False, skippe
     if sk is not None and sk.size != 3:
         raise ValueError("skipped has three words: control batches, magic 0/1 sets, unknown codecs")
     return _render(N.load().kta_render_record_batches, _np_ptr(v), n_partitions, 1 if filtered else 0, None if sk is None else _np_ptr(sk))
+
+
+PAYLOAD_CLASSES = ("null", "empty", "framed", "json", "other")
+PAYLOAD_COLUMNS = ("records",) + PAYLOAD_CLASSES + tuple(c + "_bytes" for c in PAYLOAD_CLASSES) + \
+    ("with_headers", "headers", "header_key_bytes", "header_value_bytes", "header_null_values", "bad_headers", "header_wire_bytes")
+
+
+def split_payload(vec, n_partitions: int) -> dict:
+    """A payload vector u64[24 P + 16 + 2 * 1024 * 34] as a dict, split by its layout (kta_hip.h, above KTA_FLAG_PAYLOAD):
+    "partitions" [P][24] (columns PAYLOAD_COLUMNS, then six zeros); "headers_hist" [16]; "table" [2][1024][34] (T, B, 32 bit
+    counters); "schema_ids" what payload_schema_ids reads off it; the vector under "vector"."""
+    P = n_partitions
+    v = _section_vec("payload", vec, P)
+    return {"partitions": v[:24 * P].reshape(P, 24).copy(), "headers_hist": v[24 * P:24 * P + 16].copy(),
+            "table": v[24 * P + 16:].reshape(2, 1024, 34).copy(), "schema_ids": payload_schema_ids(v, P), "vector": v}
+
+
+def merge_payload(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_payload, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    return _merge("payload", acc, other, n_partitions)
+
+
+def payload_identities(vec, n_partitions: int, counter_vec=None) -> bool:
+    """kta_payload_identities: whether the identities between the words of one payload vector hold; with counter_vec (the
+    counter vector u64[7 P + 8] of the same unfiltered run without failed batches) also records == total_messages and
+    null == tombstones per partition."""
+    c = None if counter_vec is None else np.ascontiguousarray(counter_vec, np.uint64)
+    if c is not None and c.size != 7 * n_partitions + 8:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {7 * n_partitions + 8} words, not {c.size}")
+    rc = N.load().kta_payload_identities(_np_ptr(_section_vec("payload", vec, n_partitions)), None if c is None else _np_ptr(c), n_partitions)
+    if rc < 0:
+        raise KtaError(rc, "kta_payload_identities")
+    return rc == 1
+
+
+def payload_schema_ids(vec, n_partitions: int) -> dict:
+    """kta_payload_schema_ids: the schema ids read off a payload vector's table — "ids" [(id, records, bytes)] sorted by
+    records (most first), exact; "unresolved_records" / "unresolved_bytes": what remains in cells that hold several ids."""
+    v = _section_vec("payload", vec, n_partitions)
+    lib, n, ur, ub = N.load(), C.c_size_t(), C.c_uint64(), C.c_uint64()
+    rc = lib.kta_payload_schema_ids(_np_ptr(v), n_partitions, None, None, None, 0, C.byref(n), C.byref(ur), C.byref(ub))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_payload_schema_ids")
+    cap = max(n.value, 1)
+    ids, rec, byt = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    rc = lib.kta_payload_schema_ids(_np_ptr(v), n_partitions, _np_ptr(ids), _np_ptr(rec), _np_ptr(byt), cap, C.byref(n), C.byref(ur), C.byref(ub))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_payload_schema_ids")
+    return {"ids": [(int(ids[i]), int(rec[i]), int(byt[i])) for i in range(n.value)], "unresolved_records": int(ur.value),
+            "unresolved_bytes": int(ub.value)}
+
+
+def payload_host(blob: bytes, partition: int, n_partitions: int, vec=None) -> np.ndarray:
+    """kta_payload_host: the section's rule over the records of `blob` on the host (compressed batches inflated), added to
+    `vec` (a new vector when None)."""
+    v = np.zeros(_section_words("payload", n_partitions), np.uint64) if vec is None else _section_vec("payload", vec, n_partitions)
+    rc = N.load().kta_payload_host(bytes(blob), len(blob), int(partition), _np_ptr(v), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_payload_host")
+    return v
+
+
+def render_payload(vec, n_partitions: int, counter_vec=None) -> str:
+    """kta_render_payload: the section kta-analyzer prints with --librdkafka kta.payload=1.  counter_vec: the counter vector
+    (its key and value size sums give the header bytes' share), `n/a` in that column when None."""
+    v = _section_vec("payload", vec, n_partitions)
+    c = None if counter_vec is None else np.ascontiguousarray(counter_vec, np.uint64)
+    if c is not None and c.size != 7 * n_partitions + 8:
+        raise ValueError(f"a counter vector of {n_partitions} partitions has {7 * n_partitions + 8} words, not {c.size}")
+    return _render(N.load().kta_render_payload, _np_ptr(v), None if c is None else _np_ptr(c), n_partitions)
 
 
 def size_bin(size: int) -> int:

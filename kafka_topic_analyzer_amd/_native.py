@@ -66,6 +66,9 @@ KTA_SIZE_BINS, KTA_SIZE_QUANTITIES, KTA_SIZE_GLOBALS = 464, 3, 8
 # record-batch vector: u64[20 P + 1524] = [P][16] sums | [5 codecs][100] sums and histograms | [P][4] maxima | 1024 sketch registers
 KTA_FLAG_RECORD_BATCHES = 512
 KTA_RB_PARTITION_WORDS, KTA_RB_CODECS, KTA_RB_CODEC_WORDS, KTA_RB_HIST_BINS, KTA_RB_MAX_WORDS, KTA_RB_SKETCH_REGISTERS = 16, 5, 100, 32, 4, 1024
+# payload vector: u64[24 P + 16 + 2 * 1024 * 34] = [P][24] sums | 16 histogram bins | [2 rows][1024 cells][34: T, B, 32 bit counters]
+KTA_FLAG_PAYLOAD = 1024
+KTA_PAYLOAD_PARTITION_WORDS, KTA_PAYLOAD_CLASSES, KTA_PAYLOAD_HIST_BINS, KTA_PAYLOAD_ROWS, KTA_PAYLOAD_CELLS, KTA_PAYLOAD_CELL_WORDS = 24, 5, 16, 2, 1024, 34
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -250,6 +253,17 @@ SIGNATURES = {
     "kta_record_batches_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "kta_record_batches_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
     "kta_render_record_batches": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_get_payload": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_payload": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_payload_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_payload_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_payload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_payload_identities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_payload_schema_ids": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "kta_payload_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint32]),
+    "kta_payload_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
+    "kta_render_payload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_set_segments": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kta_segments_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),

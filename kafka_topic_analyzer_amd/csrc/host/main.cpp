@@ -46,6 +46,9 @@
 // kta.record_batches=1 (0: off; segment:// sources only, kta.gpus=N and -c included, not with kta.per_message=1: the other
 // sources deliver records, not batches) runs the record-batch pass as well (KTA_FLAG_RECORD_BATCHES) and prints its section
 // behind every other one: records and bytes per batch, compression per codec, offset holes, producers.
+// kta.payload=1 (0: off; segment:// sources only, kta.gpus=N and -c included, not with kta.per_message=1: the pass reads the record
+// bytes of the raw log) runs the payload pass as well (KTA_FLAG_PAYLOAD) and prints its section behind every other one: value
+// formats, schema-registry ids, record headers.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -361,6 +364,7 @@ struct ShardedJob {
     bool percentiles = false;                          // kta.percentiles=1: likewise
     bool record_batches = false;                       // kta.record_batches=1: likewise (segment:// only)
     uint64_t rb_skipped[3] = {0, 0, 0};                //   control batches, magic 0/1 sets, unknown codecs: the host index's, whole topic
+    bool payload = false;                              // kta.payload=1: likewise (segment:// only)
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
@@ -379,7 +383,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) |
-                               (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u);
+                               (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) | (job.payload ? KTA_FLAG_PAYLOAD : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -550,6 +554,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             text += kta::render_filter(job.filter.from_ms, job.filter.to_ms, job.filter.has_set ? job.filter.bitmap.data() : nullptr, job.P,
                                        (uint64_t)filter_counts[0], (uint64_t)filter_counts[1]);
         if (job.record_batches) text += kta::render_record_batches(h0->record_batches()->data(), job.P, job.filter.on, job.rb_skipped);
+        if (job.payload) text += kta::render_payload(h0->payload()->data(), partitioner_counters(metrics, job.P).data(), job.P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -598,6 +603,21 @@ int main(int argc, char **argv)
         if (record_batches && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
             fprintf(stderr, "kta.record_batches=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
                             "list and kta.per_message=1 deliver records, not batches)\n");
+            return 2;
+        }
+    }
+    // kta.payload: the section is about the record bytes, and only raw log segments hold them on the device
+    bool payload = false;
+    if (cfg.count("kta.payload")) {
+        const std::string &v = cfg["kta.payload"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.payload=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        payload = v == "1";
+        if (payload && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
+            fprintf(stderr, "kta.payload=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
+                            "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
             return 2;
         }
     }
@@ -991,6 +1011,7 @@ int main(int argc, char **argv)
         job.repartition = repartition;
         job.percentiles = percentiles;
         job.record_batches = record_batches;
+        job.payload = payload;
         std::copy(rb_skipped, rb_skipped + 3, job.rb_skipped);
         job.filter = filter;
         job.segments = segments;
@@ -1013,7 +1034,8 @@ int main(int argc, char **argv)
                                             (analytics ? KTA_FLAG_ANALYTICS : 0u) | (distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                                 (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
-                                                (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u),
+                                                (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) |
+                                                (payload ? KTA_FLAG_PAYLOAD : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1262,6 +1284,7 @@ int main(int argc, char **argv)
             text += kta::render_filter(filter.from_ms, filter.to_ms, filter.has_set ? filter.bitmap.data() : nullptr, P, filter_info[0],
                                        filter_info[1]);
         if (record_batches) text += kta::render_record_batches(handler->record_batches()->data(), P, filter.on, rb_skipped);
+        if (payload) text += kta::render_payload(handler->payload()->data(), partitioner_counters(metrics, P).data(), P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -75,7 +75,7 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
       sketch_on_((flags & KTA_FLAG_KEY_SKETCH) != 0), hot_on_((flags & KTA_FLAG_HOT_KEYS) != 0),
       tso_on_((flags & KTA_FLAG_TS_ORDER) != 0), part_on_((flags & KTA_FLAG_PARTITIONER) != 0),
       part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u), sizeq_on_((flags & KTA_FLAG_SIZE_QUANTILES) != 0),
-      rb_on_((flags & KTA_FLAG_RECORD_BATCHES) != 0)
+      rb_on_((flags & KTA_FLAG_RECORD_BATCHES) != 0), pl_on_((flags & KTA_FLAG_PAYLOAD) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -221,6 +221,10 @@ void HipMetricHandler::read_analytics()
     if (rb_on_) {
         bvec_.assign(KTA_RB_WORDS(P_), 0);
         check(kta_exchange_record_batches(ctx_, bvec_.data(), bvec_.size()), "kta_exchange_record_batches");
+    }
+    if (pl_on_) {
+        lvec_.assign(KTA_PAYLOAD_WORDS(P_), 0);
+        check(kta_exchange_payload(ctx_, lvec_.data(), lvec_.size()), "kta_exchange_payload");
     }
     if (seg_rows_) {
         gvec_.assign(kta_segments_words((uint32_t)P_, seg_rows_), 0);

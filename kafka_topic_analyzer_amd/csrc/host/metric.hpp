@@ -151,6 +151,8 @@ public:
     const std::vector<uint64_t> *size_quantiles() const { return sizeq_on_ ? &qvec_ : nullptr; }
     // With KTA_FLAG_RECORD_BATCHES: the record-batch vector u64[20 P + 1524] of that snapshot; nullptr without the flag.
     const std::vector<uint64_t> *record_batches() const { return rb_on_ ? &bvec_ : nullptr; }
+    // With KTA_FLAG_PAYLOAD: the payload vector u64[24 P + 69648] of that snapshot; nullptr without the flag.
+    const std::vector<uint64_t> *payload() const { return pl_on_ ? &lvec_ : nullptr; }
     // The segment pass of the retention what-if (kta_set_segments): right after construction, before any record; then the
     // segment vector u64[(P M + P) 4 + 8] of the snapshot finish() / exchange() took (after exchange(), the whole job's);
     // nullptr without it.
@@ -197,6 +199,8 @@ private:
     std::vector<uint64_t> qvec_;
     bool rb_on_ = false;
     std::vector<uint64_t> bvec_;
+    bool pl_on_ = false;
+    std::vector<uint64_t> lvec_;
     uint32_t seg_rows_ = 0;   // M; 0: no segments
     std::vector<uint64_t> gvec_;
 };
@@ -233,6 +237,8 @@ std::string render_partitioner(const uint64_t *vec, const uint64_t *counters, ui
 std::string render_size_percentiles(const uint64_t *vec, uint32_t P);
 // (kta_render_record_batches): vec u64[20 P + 1524]; skipped: control batches, magic 0/1 sets, unknown codecs of the run
 std::string render_record_batches(const uint64_t *vec, uint32_t P, bool filtered, const uint64_t skipped[3]);
+// (kta_render_payload): vec u64[24 P + 69648]; counters: the counter vector (key_size_sum, value_size_sum) or nullptr
+std::string render_payload(const uint64_t *vec, const uint64_t *counters, uint32_t P);
 // the opt-in section kta-analyzer prints with kta.segments=<size> after the partitioner and compaction sections and before
 // the filter's (kta_render_retention): vec u64[(P M + P) 4 + 8]; retention -1: the rule is off
 std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes);

@@ -10,6 +10,7 @@
 
 #include "kta_compact_delete.h"
 #include "kta_compaction.h"
+#include "kta_payload.h"
 #include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
@@ -687,6 +688,68 @@ std::string render_record_batches(const uint64_t *vec, uint32_t P, bool filtered
     return o;
 }
 
+// The opt-in payload section (kta.payload=1): no reference counterpart, printed after everything else.  vec: u64[24 P + 69648]
+// (kta_hip.h; the layout is kta_payload.h's).  counters: the counter vector (key_size_sum and value_size_sum are read), or
+// nullptr.  A figure whose denominator is 0 is `n/a`.
+std::string render_payload(const uint64_t *vec, const uint64_t *counters, uint32_t P)
+{
+    auto ratio = [](uint64_t num, uint64_t den, double scale) -> std::string {
+        if (den == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)num * scale / (double)den);
+        return buf;
+    };
+    auto row_of = [&](const std::string &name, const uint64_t *w, bool sized, uint64_t key_value) {
+        const uint64_t records = w[kPlRecords], wire = w[kPlHeaderWireBytes];
+        std::vector<std::string> r{name, std::to_string(records)};
+        for (uint32_t c = 0; c < kPlClasses; c++) r.push_back(ratio(w[kPlClass + c], records, 100.0));
+        r.push_back(std::to_string(w[kPlWithHeaders]));
+        r.push_back(ratio(w[kPlHeaders], records - w[kPlBadHeaders], 1.0));
+        r.push_back(sized ? ratio(wire, key_value + wire, 100.0) : "n/a");
+        r.push_back(std::to_string(w[kPlBadHeaders]));
+        return r;
+    };
+    std::string o;
+    o += "Payload: value formats, schema-registry ids and record headers (kta.payload=1; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Records", "Null %", "Empty %", "Framed %", "JSON %", "Other %", "With headers", "Headers/rec", "Header bytes %", "Bad headers"});
+    uint64_t all[kPlPartitionWords] = {}, all_kv = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const uint64_t *w = vec + (size_t)kPlPartitionWords * p;
+        const uint64_t kv = counters ? counters[(size_t)KTA_NCOUNTERS * p + KTA_C_KEY_SIZE_SUM] + counters[(size_t)KTA_NCOUNTERS * p + KTA_C_VALUE_SIZE_SUM] : 0;
+        for (uint32_t k = 0; k < kPlPartitionWords; k++) all[k] += w[k];
+        all_kv += kv;
+        rows.push_back(row_of(std::to_string(p), w, counters != nullptr, kv));
+    }
+    rows.push_back(row_of("Topic", all, counters != nullptr, all_kv));
+    o += pretty_table(rows);
+    rows.clear();
+    rows.push_back({"Headers", "Records"});
+    for (uint32_t b = 0; b < kPlHistBins; b++)
+        rows.push_back({b == kPlHistBins - 1 ? ">=" + std::to_string(b) : std::to_string(b), std::to_string(vec[payload_hist_at(P) + b])});
+    o += pretty_table(rows);
+    uint64_t unresolved_records = 0, unresolved_bytes = 0;
+    const std::vector<PayloadSchemaId> ids = payload_schema_ids(vec, P, &unresolved_records, &unresolved_bytes);
+    constexpr size_t kShown = 64;
+    if (ids.empty() && unresolved_records == 0) {
+        o += "Schema ids: none (no value begins with the byte 0x00 and is five bytes or longer)\n";
+    } else {
+        rows.clear();
+        rows.push_back({"Schema id", "Records", "Bytes", "B/record"});
+        for (size_t i = 0; i < ids.size() && i < kShown; i++)
+            rows.push_back({std::to_string(ids[i].id), std::to_string(ids[i].records), std::to_string(ids[i].bytes), ratio(ids[i].bytes, ids[i].records, 1.0)});
+        o += pretty_table(rows);
+        if (ids.size() > kShown) o += "... and " + std::to_string(ids.size() - kShown) + " more\n";
+        if (unresolved_records)
+            o += "Unresolved: " + std::to_string(unresolved_records) + " records, " + std::to_string(unresolved_bytes) +
+                 " bytes in table cells that hold several ids\n";
+    }
+    o += "Framed is a heuristic of two conditions (first byte 0x00, five bytes or more); the ids are the topic's, not a subject's; header names are "
+         "not listed; failed batches are not described.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 // murmur3's finaliser, as the device puts it behind the key hash (kta_hip.h, KTA_FLAG_KEY_SKETCH)
 static uint32_t fmix32(uint32_t x)
 {
@@ -835,6 +898,19 @@ extern "C" int kta_render_record_batches(const uint64_t *vec, uint32_t n_partiti
     if (!vec || !out_len || n_partitions == 0 || n_partitions > 4096) return KTA_ERR_INVALID;
     static const uint64_t kNone[3] = {0, 0, 0};
     const std::string text = kta::render_record_batches(vec, n_partitions, filtered != 0, skipped ? skipped : kNone);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
+
+extern "C" int kta_render_payload(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || n_partitions == 0 || n_partitions > 4096) return KTA_ERR_INVALID;
+    const std::string text = kta::render_payload(vec, counter_vec, n_partitions);
     *out_len = text.size();
     if (out && out_cap > 0) {
         const size_t n = std::min(out_cap - 1, text.size());

@@ -9,6 +9,7 @@
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
+#include "kta_payload.h"
 #include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
@@ -134,6 +135,10 @@ struct kta_ctx {
     // (kta_internal_record_batches), d_rb_out its snapshot
     bool rb = false;
     DeviceBuf<uint64_t> d_rb, d_rb_out;
+    // payload (KTA_FLAG_PAYLOAD): d_pl u64[24 P + 69648] the live vector that the decode call adds to (kta_internal_payload),
+    // d_pl_out its snapshot
+    bool pl = false;
+    DeviceBuf<uint64_t> d_pl, d_pl_out;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -881,6 +886,7 @@ Shape segments_shape(uint32_t P, uint32_t M)
     return Shape{words, words - kta::kSegGlobals + kta::kSegGlobalS, false};
 }
 Shape record_batches_shape(uint32_t P) { return Shape{kta::rb_len(P), kta::rb_sum_words(P), false}; }
+Shape payload_shape(uint32_t P) { return all_sum(kta::payload_len(P)); }
 Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
 
 // what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
@@ -899,6 +905,11 @@ static_assert(KTA_RB_WORDS(7) == 20 * 7 + 1524 && KTA_RB_SUM_WORDS(7) == 16 * 7 
                   kta::kRbPartitionWords * 7 + kta::kRbCodecTable == KTA_RB_SUM_WORDS(7) &&
                   KTA_RB_SUM_WORDS(7) + kta::kRbMaxWords * 7 + kta::kRbSketchRegs == KTA_RB_WORDS(7),
               "the record-batch vector's length: kta_record_batches.h and kta_hip.h");
+static_assert(kta::kPlPartitionWords == KTA_PAYLOAD_PARTITION_WORDS && kta::kPlHistBins == KTA_PAYLOAD_HIST_BINS && kta::kPlRows == KTA_PAYLOAD_ROWS &&
+                  kta::kPlCells == KTA_PAYLOAD_CELLS && kta::kPlCellWords == KTA_PAYLOAD_CELL_WORDS && kta::kPlClasses == KTA_PAYLOAD_CLASSES,
+              "kta_payload.h and kta_hip.h");
+static_assert(KTA_PAYLOAD_WORDS(7) == 24 * 7 + 16 + 2 * 1024 * 34 && kta::kPlPartitionWords * 7 + kta::kPlHistBins + kta::kPlTableWords == KTA_PAYLOAD_WORDS(7),
+              "the payload vector's length: kta_payload.h and kta_hip.h");
 
 // One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
 // and out point at the context's owners, allocated or not.
@@ -934,6 +945,7 @@ void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
                                  "the context has no segments (kta_set_segments)"};
     s[KTA_RV_RECORD_BATCHES] = Section{ctx->rb, &ctx->d_rb, &ctx->d_rb_out, record_batches_shape(P), true, "record-batch vector",
                                        "context was created without KTA_FLAG_RECORD_BATCHES"};
+    s[KTA_RV_PAYLOAD] = Section{ctx->pl, &ctx->d_pl, &ctx->d_pl_out, payload_shape(P), true, "payload vector", "context was created without KTA_FLAG_PAYLOAD"};
     s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
                                     "context was created without KTA_FLAG_COMPACTION"};
     s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
@@ -1229,6 +1241,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->comp = (cfg->flags & KTA_FLAG_COMPACTION) != 0;
     ctx->sizeq = (cfg->flags & KTA_FLAG_SIZE_QUANTILES) != 0;
     ctx->rb = (cfg->flags & KTA_FLAG_RECORD_BATCHES) != 0;
+    ctx->pl = (cfg->flags & KTA_FLAG_PAYLOAD) != 0;
     {
         const char *qv = getenv("KTA_SIZEQ_VARIANT");   // A/B switch of tools/bench_size_quantiles.py: 1 a launch per slice, 9 loads only
         ctx->sizeq_variant = qv && (qv[0] == '1' || qv[0] == '9') && !qv[1] ? qv[0] - '0' : 0;
@@ -2316,6 +2329,62 @@ int kta_record_batches_host(const uint8_t *bytes, uint64_t len, int32_t partitio
     return KTA_OK;
 }
 
+// ---- payload (kta_payload.h holds the rule, kta_payload.hip the kernel, kta_kafka.hip the launch) -------------------------
+
+int kta_get_payload(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_PAYLOAD, out, n_u64); }
+int kta_exchange_payload(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_PAYLOAD, out, n_u64); }
+int kta_payload_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64) { return section_vector(ctx, KTA_RV_PAYLOAD, true, device_ptr, n_u64); }
+int kta_payload_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64) { return section_vector(ctx, KTA_RV_PAYLOAD, false, device_ptr, n_u64); }
+int kta_merge_payload(uint64_t *acc, const uint64_t *other, uint32_t P) { return merge_section(acc, other, P != 0 && P <= 4096, payload_shape(P)); }
+
+int kta_payload_identities(const uint64_t *vec, const uint64_t *counter_vec, uint32_t P)
+{
+    if (!vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    return kta::payload_identities_hold(vec, P, counter_vec, KTA_NCOUNTERS) ? 1 : 0;
+}
+
+int kta_payload_schema_ids(const uint64_t *vec, uint32_t P, uint32_t *ids, uint64_t *records, uint64_t *bytes, size_t cap, size_t *n,
+                           uint64_t *unresolved_records, uint64_t *unresolved_bytes)
+{
+    if (!vec || !n || P == 0 || P > 4096 || (cap && (!ids || !records || !bytes))) return KTA_ERR_INVALID;
+    const std::vector<kta::PayloadSchemaId> found = kta::payload_schema_ids(vec, P, unresolved_records, unresolved_bytes);
+    *n = found.size();
+    for (size_t i = 0; i < found.size() && i < cap; i++) ids[i] = found[i].id, records[i] = found[i].records, bytes[i] = found[i].bytes;
+    return KTA_OK;
+}
+
+int kta_payload_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t P)
+{
+    if (!bytes || !vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    if (partition < 0 || (uint32_t)partition >= P) return KTA_OK;             // outside [0, P): adds nothing
+    kta_kafka_index_stats st;
+    int rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, nullptr, 0, &st);
+    if (rc != KTA_OK && rc != KTA_ERR_CAPACITY) return rc;
+    std::vector<kta_kafka_batch_desc> descs(st.n_batches);
+    rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, descs.data(), descs.size(), &st);
+    if (rc != KTA_OK) return rc;
+    std::vector<uint8_t> inflated;
+    for (const kta_kafka_batch_desc &d : descs) {
+        if (d.status != 0 || d.n_records <= 0 || d.byte_off > len || len - d.byte_off < d.batch_bytes || d.batch_bytes < KTA_KAFKA_BATCH_HEADER) continue;
+        auto passes = [](long long) { return true; };                           // (no context, no filter)
+        const uint8_t *src = bytes + d.byte_off + KTA_KAFKA_BATCH_HEADER;
+        const uint64_t n = d.batch_bytes - KTA_KAFKA_BATCH_HEADER;
+        if (!(d.flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD))) {
+            kta::payload_batch_host(vec, P, (uint32_t)partition, src, 0, n, (uint64_t)d.n_records, passes);
+            continue;
+        }
+        const uint64_t cap = d.payload_end > d.payload_off ? d.payload_end - d.payload_off : 0;   // the index's bound (exact for gzip and Snappy)
+        inflated.assign(cap + 64, 0);
+        const int64_t got = (d.flags & KTA_KB_SNAPPY) ? kta_snappy_inflate_host(src, n, inflated.data(), cap)
+                            : (d.flags & KTA_KB_LZ4)  ? kta_lz4_inflate_host(src, n, inflated.data(), cap)
+                            : (d.flags & KTA_KB_GZIP) ? kta_gzip_inflate_host(src, n, inflated.data(), cap)
+                                                      : kta_zstd_inflate_host(src, n, inflated.data(), cap);
+        if (got < 0) continue;                                                  // a stream that does not inflate: a failed batch
+        kta::payload_batch_host(vec, P, (uint32_t)partition, inflated.data(), 0, (uint64_t)got, (uint64_t)d.n_records, passes);
+    }
+    return KTA_OK;
+}
+
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
 
 int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
@@ -2855,6 +2924,13 @@ bool kta_internal_record_batches(kta_ctx *ctx, kta_internal_rb *out)
     *out = kta_internal_rb{ctx->rb, ctx->d_rb.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
                            f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
     return ctx->rb && !ctx->comp_replay;
+}
+bool kta_internal_payload(kta_ctx *ctx, kta_internal_pl *out)
+{
+    const bool f = ctx->filter;
+    *out = kta_internal_pl{ctx->pl, ctx->d_pl.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
+                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
+    return ctx->pl && !ctx->comp_replay;
 }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {

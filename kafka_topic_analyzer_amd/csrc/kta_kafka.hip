@@ -29,6 +29,7 @@
 #include "kta_records.h"
 #include "kta_internal.h"
 #include "kta_record_batches.h"
+#include "kta_payload.h"
 
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -1166,6 +1167,9 @@ struct KafkaState {
     TimerPool<1> rb_timers{1024};   // the record-batch pass (kta_record_batches_info)
     uint64_t rb_launches = 0, rb_batches = 0;
     uint32_t rb_workgroups = 0;     // of the last launch
+    TimerPool<1> pl_timers{1024};   // the payload pass (kta_payload_info)
+    uint64_t pl_launches = 0, pl_batches = 0;
+    uint32_t pl_workgroups = 0;     // of the last launch
 };
 
 void free_out(kta_batch &o)
@@ -1650,6 +1654,16 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
         if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
         st->rb_launches++, st->rb_batches += n_batches;
     }
+    // The payload section (KTA_FLAG_PAYLOAD): the same moment, for what lies inside the records — the blob's inflate area holds
+    // the inflated batches.  Off, or during a compaction replay: nothing runs.
+    if (kta_internal_pl pl{}; kta_internal_payload(ctx, &pl)) {
+        if (timing) { int rc = st->pl_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        KTA_HIP_AS(ctx, kta::launch_payload(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), pl.from_ms, pl.to_ms, pl.bitmap, pl.vec,
+                                            pl.cu_count, &st->pl_workgroups, s),
+                   "kta_payload");
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+        st->pl_launches++, st->pl_batches += n_batches;
+    }
     KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
         KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -1906,6 +1920,23 @@ int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
     int rc = st->rb_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
     if (rc != KTA_OK) return rc;
     out[0] = st->rb_launches, out[1] = st->rb_batches, out[2] = st->rb_workgroups, out[3] = timed;
+    if (avg_ms) *avg_ms = ms;
+    return KTA_OK;
+}
+
+int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_pl pl{};
+    (void)kta_internal_payload(ctx, &pl);
+    if (!pl.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_PAYLOAD");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KafkaState *st = state_of(ctx);
+    float ms = -1.f;
+    uint64_t timed = 0;
+    int rc = st->pl_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    out[0] = st->pl_launches, out[1] = st->pl_batches, out[2] = st->pl_workgroups, out[3] = timed;
     if (avg_ms) *avg_ms = ms;
     return KTA_OK;
 }

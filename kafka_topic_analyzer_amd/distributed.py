@@ -123,6 +123,14 @@ def allreduce_record_batches_vector(bvec, n_partitions: int, group=None) -> None
     _allreduce_sum_max(bvec, 16 * n_partitions + 500, group)
 
 
+def allreduce_payload_vector(lvec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the payload SNAPSHOT (kta_payload_result_vector: device tensor, or a CPU tensor in
+    the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_PAYLOAD: one all-reduce SUM over all
+    24 P + 16 + 2 * 1024 * 34 words (i64 wrap == u64 wrap)."""
+    assert lvec.numel() == 24 * n_partitions + 16 + 2 * 1024 * 34
+    _allreduce_sum_max(lvec, lvec.numel(), group)
+
+
 def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
     """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
     tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM
