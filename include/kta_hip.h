@@ -496,7 +496,11 @@ typedef struct kta_hot_key {
  *   writes a tile's summary writes its mark, 0 or 1, in the same step, and the plane before it; the mark is 1 only for a
  *   compact tile of all 1024 records in which every record fits.  A header that turns raw needs nothing more, and
  *   widening the lengths touches neither the ts_ms bytes nor the values.  The plane does not depend on `lens`: tiles
- *   of keyed allocations have planes too.  kta_batch_tile_planes reads the marks back.
+ *   of keyed allocations have planes too.  kta_batch_tile_planes reads the marks back.  Beside the marks the
+ *   allocation keeps two more u32 per tile, trusted only where the mark is 1 and written with it: the least and the
+ *   largest key_len + val_len of the tile's records that have a value (a key of -1 counts as 0; 0xFFFFFFFF / 0 when it
+ *   has none).  The scan takes a marked tile's size extrema from them and adds the plane's lengths as stored, markers
+ *   included; the counts of null keys and tombstones correct the two size sums when they leave the workgroup's LDS.
  *   key_off, key_bytes and seq are the same in both layouts.  The columns of a tile-compact batch are
  *   written by kta_synth_fill_device (compact tiles), kta_kafka_decode_device (raw tiles) and kta_batch_from_raw, and
  *   read back by kta_batch_to_raw; a raw-layout kta_batch whose column pointers lie inside a tile-compact allocation of

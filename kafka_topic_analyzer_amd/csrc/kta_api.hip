@@ -247,7 +247,8 @@ int alloc_device_batch(kta_ctx *ctx, uint64_t cap, uint64_t kcap, bool keys, boo
     const uint64_t ntiles = tiles_of(cap) ? tiles_of(cap) : 1;
     const uint64_t rows = ntiles * KTA_TILE_RECORDS;
     const size_t c4 = pad16(rows * 4 + 16), c8 = pad16(rows * 8 + 16);
-    // (the tiles' summaries behind the headers, their plane marks behind those: kta::tile_sums_behind, tile_marks_behind)
+    // (the tiles' summaries behind the headers, their plane marks behind those, the size extrema last: kta::tile_sums_behind,
+    // tile_marks_behind, tile_sizes_behind)
     KTA_HIP(ctx, hipMalloc((void **)&b->tile_hdr, ntiles * kta::kTileSideBytes));
     KTA_HIP(ctx, hipMemset(b->tile_hdr, 0, ntiles * kta::kTileSideBytes));   // every tile raw, no summary, no plane
     KTA_HIP(ctx, hipMalloc((void **)&b->partition, c4));
@@ -308,7 +309,7 @@ kta_internal_columns columns_at(const kta_internal_columns &rb, uint64_t at)
 kta::ScanColumns scan_columns(const kta_internal_columns &rb, uint64_t at)
 {
     const kta_internal_columns r = columns_at(rb, at);
-    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.sum, r.mark};
+    return kta::ScanColumns{r.partition, r.key_len, r.val_len, r.ts_ms, r.hdr, r.rec0, r.sum, r.mark, r.size};
 }
 // (the key-reading passes take the lengths and the keys from the batch's own columns: plain i32 in both layouts)
 kta::SketchColumns sketch_columns(const kta_internal_columns &rb, const kta_batch *c, uint64_t at)
@@ -1594,7 +1595,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     std::vector<int64_t> ts(nt * KTA_TILE_RECORDS, 0);
     std::vector<kta_tile_hdr> hdr(nt);
     std::vector<kta_tile_sum> sum(nt);
-    std::vector<uint32_t> mark(nt, 0u);
+    std::vector<uint32_t> mark(nt, 0u), size(2 * nt, 0u);
     std::vector<int32_t> klen, vlen;
     if (r.keyless) {
         klen.assign(nt * KTA_TILE_RECORDS, 0);
@@ -1605,7 +1606,7 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
         hdr[T] = kta::tile_pack_host(h->partition + a, h->ts_ms + a, h->key_len + a, h->val_len + a, m, r.keyless, part.data() + a, ts.data() + a,
                                      r.keyless ? klen.data() + a : nullptr, r.keyless ? vlen.data() + a : nullptr, &sum[T]);
         // (the plane rides in the ts image that is uploaded whole anyway)
-        if (r.mark) mark[T] = kta::tile_plane_host(hdr[T], h->partition + a, h->key_len + a, h->val_len + a, m, ts.data() + a);
+        if (r.mark) mark[T] = kta::tile_plane_host(hdr[T], h->partition + a, h->key_len + a, h->val_len + a, m, ts.data() + a, &size[2 * T]);
     }
     if (r.keyless) {
         KTA_HIP(ctx, hipMemcpy(r.key_len + r.rec0, klen.data(), klen.size() * 4, hipMemcpyHostToDevice));
@@ -1615,6 +1616,8 @@ int kta_batch_from_raw(kta_ctx *ctx, const kta_batch *h, uint64_t n, const kta_b
     KTA_HIP(ctx, hipMemcpy(r.ts_ms + r.rec0, ts.data(), ts.size() * 8, hipMemcpyHostToDevice));
     KTA_HIP(ctx, hipMemcpy(r.hdr + r.rec0 / KTA_TILE_RECORDS, hdr.data(), nt * sizeof(kta_tile_hdr), hipMemcpyHostToDevice));
     if (r.sum) KTA_HIP(ctx, hipMemcpy(r.sum + r.rec0 / KTA_TILE_RECORDS, sum.data(), nt * sizeof(kta_tile_sum), hipMemcpyHostToDevice));
+    // (the size extrema before the marks that vouch for them)
+    if (r.mark) KTA_HIP(ctx, hipMemcpy(r.size + 2 * (r.rec0 / KTA_TILE_RECORDS), size.data(), 2 * nt * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (r.mark) KTA_HIP(ctx, hipMemcpy(r.mark + r.rec0 / KTA_TILE_RECORDS, mark.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice));
     return KTA_OK;
 }
@@ -2963,7 +2966,7 @@ int kta_internal_prepare_raw(kta_ctx *ctx, const kta_batch *d, uint64_t n)
 
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns *r)
 {
-    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false, 0, nullptr, nullptr};
+    *r = kta_internal_columns{c->partition, c->key_len, c->val_len, c->ts_ms, nullptr, 0, false, 0, nullptr, nullptr, nullptr};
     uint64_t rec0 = 0;
     if (const kta_batch *e = find_allocation(ctx, c->partition, &kta_batch::partition, &rec0)) {
         if (e->partition + rec0 != c->partition) return fail(ctx, KTA_ERR_INVALID, "a view of a tile-compact batch must start at a record");
@@ -2972,7 +2975,8 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *c, kta_internal_columns 
             return fail(ctx, KTA_ERR_INVALID, "the columns of a view of a tile-compact batch start at different records");
         *r = kta_internal_columns{e->partition, e->key_len, e->val_len, e->ts_ms, e->tile_hdr, rec0, e->key_bytes == nullptr, allocation_rows(*e),
                                   kta::tile_sums_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS),
-                                  kta::tile_marks_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS)};
+                                  kta::tile_marks_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS),
+                                  kta::tile_sizes_behind(e->tile_hdr, allocation_rows(*e) / KTA_TILE_RECORDS)};
         return KTA_OK;
     }
     if (c->layout == KTA_LAYOUT_TILE_COMPACT) {

@@ -91,6 +91,7 @@ struct kta_internal_columns {
     kta_tile_sum *sum;   // the allocation's tile summaries (kta_tile.h: behind its headers), entry t beside hdr[t]; null for
                          // everything but an allocation of the context's: the raw layout, a hand-built batch's own tile_hdr
     uint32_t *mark;      // the allocation's plane marks (kta_tile.h: behind its summaries), entry t beside sum[t]; null where sum is
+    uint32_t *size;      // the allocation's size extrema (kta_tile.h: behind its marks), two words per tile; null where mark is
 };
 int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns *out);
 

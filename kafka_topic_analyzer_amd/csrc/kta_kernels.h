@@ -34,6 +34,7 @@ struct ScanColumns {
     uint64_t rec0;
     const kta_tile_sum *sum;   // the tiles' summaries beside hdr (kta_tile.h), or null: none.  Read by kta_metrics_scan_packed only.
     const uint32_t *mark;      // the tiles' plane marks beside sum (kta_tile.h), or null: none, or ignored (scan_variant bit 64)
+    const uint32_t *size;      // the tiles' size extrema, two words per tile (kta_tile.h); null wherever mark is
 };
 
 struct AliveColumns {

@@ -760,6 +760,9 @@ constexpr uint64_t kFrontRecords = (uint64_t)kFrontFlushTiles * KTA_TILE_RECORDS
 static_assert(kFrontRecords <= 0xFFFFu, "count, tombstones and null keys of a front interval fit 16 bits");
 static_assert(kFrontRecords + (kFrontRecords << 16) <= 0xFFFFFFFFull, "count | tombstones << 16 stays in W1's low dword");
 static_assert(kFrontRecords * (KTA_COMPACT_LEN_NONE - 1u) < (1ull << 31), "a front interval's u16 sizes sum below 2^31");
+// The plane form adds the lengths as stored, markers included (lean_quad(PlaneSlot)); front_flush(raw) takes them out again:
+static_assert(kFrontRecords * KTA_PLANE_KEY_NONE < (1ull << 23), "a front interval's raw plane key bytes sum below 2^23");
+static_assert(kFrontRecords * KTA_COMPACT_LEN_NONE < (1ull << 31), "a front interval's raw plane value words sum below 2^31");
 
 struct PackedLds {
     unsigned long long *W1, *W2;       // front level
@@ -1032,10 +1035,17 @@ __device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, 
     }
     lean_quad_add(pt, ku, vu, knull, tomb, rep_log2, rep, L, st);
 }
-// the same of a plane slot: four words partition | key << 8 | val << 16 (kta_tile.h)
+// A plane slot: four words partition | key << 8 | val << 16 (kta_tile.h).  RAW sums: the lengths are added as stored,
+// 0xFF for a key of -1 and 0xFFFF for a value of -1 included, and front_flush(raw) subtracts the markers by the
+// interval's counts of null keys and tombstones — no select per record.  No size extrema either: the tile's producer
+// wrote them (kta_tile.h) and packed_scan_lean folds them behind the loop.
 __device__ __forceinline__ void lean_quad(const PlaneSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
 {
     const uint32_t w[4] = {(uint32_t)s.w.x, (uint32_t)s.w.y, (uint32_t)s.w.z, (uint32_t)s.w.w};
+#if KTA_PACKED_LOADS_ONLY
+    st.bad += w[0] ^ w[1] ^ w[2] ^ w[3];   // (keeps the loads alive)
+    return;
+#endif
     uint32_t pt[4], ku[4], vu[4], tomb[4], knull[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -1045,7 +1055,20 @@ __device__ __forceinline__ void lean_quad(const PlaneSlot &s, uint32_t rep_log2,
         knull[j] = ku[j] == KTA_PLANE_KEY_NONE;
         tomb[j] = vu[j] == KTA_COMPACT_LEN_NONE;
     }
-    lean_quad_add(pt, ku, vu, knull, tomb, rep_log2, rep, L, st);
+    if (pt[0] == pt[1] && pt[0] == pt[2] && pt[0] == pt[3]) {
+        const uint32_t slot = (pt[0] << rep_log2) | rep;
+        const uint32_t tombs = tomb[0] + tomb[1] + tomb[2] + tomb[3];
+        const uint32_t knulls = knull[0] + knull[1] + knull[2] + knull[3];
+        atomicAdd(&L.W1[slot], pack_dwords(4u | (tombs << 16), ku[0] + ku[1] + ku[2] + ku[3]));
+        atomicAdd(&L.W2[slot], pack_dwords(knulls, vu[0] + vu[1] + vu[2] + vu[3]));
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t slot = (pt[j] << rep_log2) | rep;
+        atomicAdd(&L.W1[slot], pack_dwords(1u | (tomb[j] << 16), ku[j]));
+        atomicAdd(&L.W2[slot], pack_dwords(knull[j], vu[j]));
+    }
 }
 
 // The workgroup of every packed scan kernel: its LDS words, carved out of the dynamic LDS and zeroed, its lane state,
@@ -1065,8 +1088,12 @@ struct PackedWg {
         rep = tid & ((1u << rep_log2) - 1u);
     }
     // front level into back level: thread p sums and zeroes partition p's replicas, between two barriers
-    __device__ __forceinline__ void front_flush() const
+    // raw: the interval's records were plane records, added with their markers (lean_quad(PlaneSlot)): the null keys'
+    // 0xFF and the tombstones' 0xFFFF leave the two size sums here, by the interval's own counts.  One rule per interval:
+    // a workgroup that changes form flushes first (packed_scan_lean).
+    __device__ __forceinline__ void front_flush(bool raw = false) const
     {
+        const unsigned long long key_none = raw ? KTA_PLANE_KEY_NONE : 0u, val_none = raw ? KTA_COMPACT_LEN_NONE : 0u;
         __syncthreads();
         for (uint32_t p = tid; p < P; p += kWG) {
             unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
@@ -1080,8 +1107,8 @@ struct PackedWg {
             L.B[p] += w1 & 0xFFFFull;
             L.B[P + p] += (w1 >> 16) & 0xFFFFull;
             L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
-            L.B[3u * P + p] += w1 >> 32;
-            L.B[4u * P + p] += w2 >> 32;
+            L.B[3u * P + p] += (w1 >> 32) - key_none * (w2 & 0xFFFFFFFFull);
+            L.B[4u * P + p] += (w2 >> 32) - val_none * ((w1 >> 16) & 0xFFFFull);
         }
         __syncthreads();
     }
@@ -1196,12 +1223,11 @@ __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanCol
         if (v) {
             lean_quad(s, rep_log2, wg.rep, wg.L, wg.st);
             if (++r.since_flush == kFrontFlushTiles) {
-                wg.front_flush();
+                wg.front_flush(PLANE);
                 r.since_flush = 0;
             }
         }
         r.tile += G;
-        r.step++;
     };
     // the ring, unrolled: no rotation moves, one exit
     Slot s0, s1, s2, s3;
@@ -1235,6 +1261,9 @@ __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanCol
         }
     }
     // (the unrolled ring may have stepped past `stop`: slots issued at or behind it hold no tile)
+    // (every take follows an issue and kLeanPrefetch issues went ahead: the step is not counted in the loop, whose
+    // scalar registers are all in use)
+    r.step = istep - (uint32_t)kLeanPrefetch;
     if (switched) r.tile = blockIdx.x + sw_step * G, r.step = sw_step;
 }
 
@@ -1262,6 +1291,12 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
     while (r.tile < r.end) {
         if (plane) lean_run<NT, true>(wg, r, c, t0, last, pc, rep_log2);
         else lean_run<NT, false>(wg, r, c, t0, last, pc, rep_log2);
+        // A front interval holds records of one form, so that front_flush has one rule for it: the run's last interval
+        // is flushed before a run of the other form adds to the same slots (and the last run's before the row is read).
+        if (r.since_flush) {
+            wg.front_flush(plane);
+            r.since_flush = 0;
+        }
         plane = !plane;
     }
     // The taken tiles' timestamp extrema, off the loop (where they were some thirty scalar and vector instructions per
@@ -1277,8 +1312,12 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
         tile_sum_extrema(h, sm, lo, hi);
         wg.st.tmin = ((lean || plane) && lo < wg.st.tmin) ? lo : wg.st.tmin;
         wg.st.tmax = ((lean || plane) && hi > wg.st.tmax) ? hi : wg.st.tmax;
+        if (plane) {   // (c.size is there wherever c.mark is)
+            wg.st.smin = min(wg.st.smin, c.size[2 * (t0 + i)]);
+            wg.st.smax = max(wg.st.smax, c.size[2 * (t0 + i) + 1]);
+        }
     }
-    wg.front_flush();
+    // (every run flushed its last interval, and thread p reads from the back level the words it wrote there itself)
     uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
     wg.write_row(row, s_red);
     if (tid == 0) {   // (behind the zeroes write_scan_globals put there)
@@ -1653,8 +1692,9 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
         ScanColumns cs = c;
         if (!pl.summaries) cs.sum = nullptr;
         if (!pl.planes || !cs.sum) cs.mark = nullptr;
+        if (!cs.mark) cs.size = nullptr;
         // (the lean kernel counts the batch's tiles, and a few grids ahead of them, in 32 bits)
-        if ((c.rec0 % KTA_TILE_RECORDS + n) / KTA_TILE_RECORDS >= (1ull << 31)) cs.sum = nullptr, cs.mark = nullptr;
+        if ((c.rec0 % KTA_TILE_RECORDS + n) / KTA_TILE_RECORDS >= (1ull << 31)) cs.sum = nullptr, cs.mark = nullptr, cs.size = nullptr;
         if (!cs.sum) return nt ? launch(kta_metrics_scan_packed<true, false>, cs) : launch(kta_metrics_scan_packed<false, false>, cs);
         // the lean kernel, then — same grid, same rows — the tiles its workgroups left (none, where every tile is
         // summarised, compact and u16: a workgroup of the second kernel then reads one word and ends)

@@ -40,12 +40,12 @@ __global__ __launch_bounds__(kWG) void synth_fill_cols(kta_synth_spec sp, uint64
 // 2^31 ms, and (lens16: the allocation has no key columns) does every length fit a u16 — and then stored compact or raw
 // into the allocation's tile t0 + T (part, klen, vlen, ts: the allocation's record 0), with its header.  One pass, as
 // the raw fill.  A whole compact tile of which every record fits the scan plane (kta_tile.h) gets its plane, 4 B per
-// record more, and its mark with the summary.
+// record more, its two size extrema (reduced over the tile with the rest) and then its mark with the summary.
 __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint64_t first, uint64_t n, int32_t *part,
                                                         int32_t *klen, int32_t *vlen, int64_t *ts, uint64_t *seq,
-                                                        kta_tile_hdr *hdr, kta_tile_sum *sum, uint32_t *mark, uint64_t t0, uint32_t lens16)
+                                                        kta_tile_hdr *hdr, kta_tile_sum *sum, uint32_t *mark, uint32_t *size, uint64_t t0, uint32_t lens16)
 {
-    __shared__ long long s_red[kWG / 64][4];
+    __shared__ long long s_red[kWG / 64][5];
     const uint32_t tid = threadIdx.x;
     const uint64_t ntiles = (n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS;
     for (uint64_t T = blockIdx.x; T < ntiles; T += gridDim.x) {
@@ -53,6 +53,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
         int64_t t[4];
         long long lo = LLONG_MAX, hi = LLONG_MIN, wide = 0;   // wide: bit 0 a partition id, bit 1 a length outside the u16 form, bit 2 a record outside the plane's
         long long seen = 0;   // the summary's (real records only): bits 0-15 the largest stored u16 partition, bit 16 a timestamp of -1
+        uint32_t slo = kta::kTileSizeMinNone, shi = kta::kTileSizeMaxNone;   // the size extrema (kta_tile.h; used only where the tile gets its mark)
         for (uint32_t j = 0; j < 4; j++) {
             const uint64_t i = T * KTA_TILE_RECORDS + 4u * tid + j;
             p[j] = -1;
@@ -64,6 +65,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             wide |= kta::tile_part_fits(p[j]) ? 0 : 1;
             wide |= kta::tile_len_fits(kl[j]) && kta::tile_len_fits(vl[j]) ? 0 : 2;
             wide |= kta::tile_plane_fits(p[j], kl[j], vl[j]) ? 0 : 4;
+            kta::tile_size_fold(kl[j], vl[j], slo, shi);
             const long long pm = kta::tile_pack_part(p[j]);
             seen = (seen & 0x10000) | ((seen & 0xFFFF) > pm ? (seen & 0xFFFF) : pm) | (t[j] == -1 ? 0x10000 : 0);
             if (t[j] != -1) {
@@ -77,12 +79,15 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             hi = b > hi ? b : hi;
             wide |= c;
             seen = ((seen | d) & 0x10000) | ((seen & 0xFFFF) > (d & 0xFFFF) ? (seen & 0xFFFF) : (d & 0xFFFF));
+            slo = min(slo, (uint32_t)__shfl_xor((int)slo, off));
+            shi = max(shi, (uint32_t)__shfl_xor((int)shi, off));
         }
         if ((tid & 63u) == 0u) {
             s_red[tid >> 6][0] = lo;
             s_red[tid >> 6][1] = hi;
             s_red[tid >> 6][2] = wide;
             s_red[tid >> 6][3] = seen;
+            s_red[tid >> 6][4] = (long long)(((unsigned long long)slo << 32) | shi);
         }
         __syncthreads();
         for (uint32_t w = 0; w < kWG / 64; w++) {
@@ -91,6 +96,9 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
             wide |= s_red[w][2];
             const long long d = s_red[w][3];
             seen = ((seen | d) & 0x10000) | ((seen & 0xFFFF) > (d & 0xFFFF) ? (seen & 0xFFFF) : (d & 0xFFFF));
+            const unsigned long long e = (unsigned long long)s_red[w][4];
+            slo = min(slo, (uint32_t)(e >> 32));
+            shi = max(shi, (uint32_t)e);
         }
         __syncthreads();   // (s_red is reused by the next tile)
         int64_t base;
@@ -128,6 +136,7 @@ __global__ __launch_bounds__(kWG) void synth_fill_tiles(kta_synth_spec sp, uint6
                 make_uint4(kta::tile_plane_pack(p[0], kl[0], vl[0]), kta::tile_plane_pack(p[1], kl[1], vl[1]),
                            kta::tile_plane_pack(p[2], kl[2], vl[2]), kta::tile_plane_pack(p[3], kl[3], vl[3]));
         if (tid == 0) {
+            if (plane) size[2 * (t0 + T)] = slo, size[2 * (t0 + T) + 1] = shi;   // (before the mark that vouches for them; mark != null: so is size)
             if (mark) mark[t0 + T] = plane ? 1u : 0u;
             hdr[t0 + T] = kta_tile_hdr{compact ? base : 0, compact ? KTA_TILE_COMPACT : KTA_TILE_RAW, u16 ? KTA_TILE_LENS_U16 : KTA_TILE_LENS_I32};
             // the summary with the header (kta_tile.h): of a compact tile this call wrote whole, else none
@@ -313,7 +322,7 @@ int kta_synth_fill_device(kta_ctx *ctx, const kta_synth_spec *spec, uint64_t fir
         // of the caller's own beside it
         const uint32_t lens16 = ac.keyless && !b->key_off && !b->key_bytes ? 1u : 0u;
         hipLaunchKernelGGL(synth_fill_tiles, dim3((uint32_t)(nt < 8192 ? nt : 8192)), dim3(kWG), 0, s, *spec, first, n, ac.partition,
-                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, ac.sum, ac.mark, rec0 / KTA_TILE_RECORDS, lens16);
+                           ac.key_len, ac.val_len, ac.ts_ms, b->seq, ahdr, ac.sum, ac.mark, ac.size, rec0 / KTA_TILE_RECORDS, lens16);
     } else {
         hipLaunchKernelGGL(synth_fill_cols, dim3(grid), dim3(kWG), 0, s, *spec, first, n, b->partition, b->key_len,
                            b->val_len, b->ts_ms, b->seq);

@@ -74,7 +74,26 @@ KTA_TILE_HD inline uint32_t *tile_marks_behind(kta_tile_hdr *hdr, uint64_t ntile
 {
     return reinterpret_cast<uint32_t *>(tile_sums_behind(hdr, ntiles) + ntiles);
 }
-constexpr uint64_t kTileSideBytes = sizeof(kta_tile_hdr) + sizeof(kta_tile_sum) + sizeof(uint32_t);   // header, summary, mark
+// The size extrema: two u32 per tile, size_min and size_max — the least and the largest key_len + val_len over the
+// tile's records that have a value (val_len != -1; a key of -1 counts as 0), 0xFFFFFFFF / 0 where it has none: what the
+// metrics scan would otherwise find record by record.  The rule of validity: the two words are trusted only where the
+// tile's mark is 1 (so only where the mark itself is trusted); whoever writes a mark of 1 writes the tile's two words in
+// the same step, before the mark.  A mark that is cleared, a header that turns RAW and widened lengths need nothing more.
+// The address rule: the words lie behind the marks in the same device allocation, tile t's at [2 t] and [2 t + 1].
+constexpr uint32_t kTileSizeMinNone = 0xFFFFFFFFu, kTileSizeMaxNone = 0u;
+KTA_TILE_HD inline uint32_t *tile_sizes_behind(kta_tile_hdr *hdr, uint64_t ntiles)
+{
+    return tile_marks_behind(hdr, ntiles) + ntiles;
+}
+constexpr uint64_t kTileSideBytes = sizeof(kta_tile_hdr) + sizeof(kta_tile_sum) + sizeof(uint32_t) + 2 * sizeof(uint32_t);   // header, summary, mark, size extrema
+// a record's share of its tile's size extrema (of a record that fits the plane): folded with min into lo, with max into hi
+KTA_TILE_HD inline void tile_size_fold(int32_t k, int32_t v, uint32_t &lo, uint32_t &hi)
+{
+    if (v == -1) return;
+    const uint32_t sz = (uint32_t)(k == -1 ? 0 : k) + (uint32_t)v;
+    lo = sz < lo ? sz : lo;
+    hi = sz > hi ? sz : hi;
+}
 KTA_TILE_HD inline bool tile_plane_fits(int32_t p, int32_t k, int32_t v)
 {
     return p >= 0 && p < (int32_t)KTA_PLANE_PARTS && k >= -1 && k < (int32_t)KTA_PLANE_KEY_NONE && tile_len_fits(v);
@@ -198,17 +217,22 @@ inline void tile_unpack_host(const kta_tile_hdr &h, const int32_t *part, const i
 }
 
 // The plane of the tile that tile_pack_host packed from the same records with header h: the mark, and — iff it is 1 —
-// the plane's words in bytes [kTilePlaneOffset, 2 kTilePlaneOffset) of the tile's ts image; nothing else is written.
-inline uint32_t tile_plane_host(const kta_tile_hdr &h, const int32_t *p, const int32_t *k, const int32_t *v, uint64_t m, int64_t *ts)
+// the plane's words in bytes [kTilePlaneOffset, 2 kTilePlaneOffset) of the tile's ts image and (sizes, may be null) the
+// tile's two size extrema; nothing else is written.
+inline uint32_t tile_plane_host(const kta_tile_hdr &h, const int32_t *p, const int32_t *k, const int32_t *v, uint64_t m, int64_t *ts,
+                                uint32_t *sizes = nullptr)
 {
     if (h.mode != KTA_TILE_COMPACT || m != KTA_TILE_RECORDS) return 0u;
     for (uint64_t j = 0; j < m; j++)
         if (!tile_plane_fits(p[j], k[j], v[j])) return 0u;
     unsigned char *plane = reinterpret_cast<unsigned char *>(ts);
+    uint32_t lo = kTileSizeMinNone, hi = kTileSizeMaxNone;
     for (uint64_t j = 0; j < m; j++) {
         const uint32_t w = tile_plane_pack(p[j], k[j], v[j]);
         memcpy(plane + tile_plane_at((uint32_t)j), &w, 4);
+        tile_size_fold(k[j], v[j], lo, hi);
     }
+    if (sizes) sizes[0] = lo, sizes[1] = hi;
     return 1u;
 }
 
