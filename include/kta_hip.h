@@ -418,6 +418,54 @@ typedef struct kta_hot_key {
 #define KTA_PAYLOAD_CELL_WORDS 34
 #define KTA_PAYLOAD_WORDS(P) (24u * (size_t)(P) + 16u + 2u * 1024u * 34u)
 
+/* Header names (NOT in the reference): a census of the names of the record headers that the raw-log decode delivers
+ * (kta_kafka.h: kta_kafka_decode_device, and through it kta_kafka_blob_submit and kta_kafka_consume).  Opt-in at kta_create,
+ * independent of KTA_FLAG_PAYLOAD.  Every word is exact and a SUM.  csrc/kta_header_names.h is the code of everything below.
+ * A record COUNTS under the payload section's rule (above KTA_FLAG_PAYLOAD: status 0, framing, partition in [0, P), the
+ * filter with LogAppendTime handled alike).  A counted record whose header section is BAD — the payload section's
+ * definition, csrc/kta_payload.h's payload_walk_headers — adds nothing here; a counted record whose section is good is
+ * LOOKED AT.  During a compaction replay the pass is skipped; failed batches add nothing.
+ * Every header occurrence of a record looked at: h = the FNV-32 of the name's bytes as -c hashes keys (fnv32.rs:76-101; two
+ * names of one hash are one name; an empty name is a name, of hash 0x811c9dc5).  The occurrence adds T += 1, L += name
+ * length, V += value length (0 for a null value), Z += 1 for a null value and 1 to the bit counter of every set bit of h,
+ * in cell h & 1023 of row 0 and in cell fmix32(h) & 1023 of row 1 (the payload table's cell rule).
+ * The vector is u64[KTA_HEADER_NAMES_WORDS], independent of P:
+ *   8 globals: occurrences, name bytes, value bytes, null values, records with at least one header, records looked at, two
+ *     zero words;
+ *   two rows of 1024 cells of 36 words at word 8: T, L, V, Z, 32 bit counters.
+ * The NAME TABLE beside it, kta_header_name[2][1024], slot 1024 r + c for cell c of row r: a slot whose state is
+ * KTA_HEADER_NAME_PUBLISHED holds the first min(name_len, 48) bytes of ONE occurrence's name whose hash is `hash` and maps
+ * to that cell in that row.  The first writer wins.  Best effort: no count depends on it, it is not snapshotted and not
+ * exchanged (it stays on its rank), kta_reset clears it.
+ * kta_header_names_list reads the names off the table; kta_header_names_identities states the identities.
+ * With the flag off no kernel is launched and nothing is allocated. */
+#define KTA_FLAG_HEADER_NAMES 0x800U     /* 2048: bit 11 */
+#define KTA_HEADER_NAMES_GLOBALS 8
+#define KTA_HEADER_NAMES_ROWS 2
+#define KTA_HEADER_NAMES_CELLS 1024
+#define KTA_HEADER_NAMES_CELL_WORDS 36
+#define KTA_HEADER_NAMES_WORDS (8u + 2u * 1024u * 36u)
+#define KTA_HEADER_NAMES_SLOTS (2u * 1024u)
+#define KTA_HEADER_NAME_BYTES 48
+#define KTA_HEADER_NAME_PUBLISHED 2u
+typedef struct kta_header_name {
+    uint32_t hash;
+    uint32_t name_len;       /* the name's whole length, also beyond 48 */
+    uint32_t state;          /* KTA_HEADER_NAME_PUBLISHED, or the slot says nothing */
+    uint32_t reserved;
+    uint8_t bytes[KTA_HEADER_NAME_BYTES];
+} kta_header_name;
+/* A row of kta_header_names_list: a recovered hash with its exact sums; name[0 .. min(name_len, 48)) when has_name. */
+typedef struct kta_header_name_row {
+    uint32_t hash;
+    uint32_t has_name;
+    uint64_t occurrences;
+    uint64_t name_len;       /* L / T */
+    uint64_t value_bytes;
+    uint64_t null_values;
+    uint8_t name[KTA_HEADER_NAME_BYTES];
+} kta_header_name_row;
+
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
  * both hold:
@@ -1092,6 +1140,38 @@ int kta_payload_schema_ids(const uint64_t *vec, uint32_t n_partitions, uint32_t 
  * compressed batches are inflated with kta_*_inflate_host.  A partition outside [0, P) adds nothing.  No filter. */
 int kta_payload_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t n_partitions);
 
+/* Header names (context created with KTA_FLAG_HEADER_NAMES; definition above KTA_FLAG_HEADER_NAMES).  kta_reset zeroes the
+ * vector and the name table; kta_finish_device snapshots the vector; kta_exchange reduces the snapshot (all SUM).  Every call
+ * below that takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_HEADER_NAMES.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_HEADER_NAMES_WORDS; staged messages are flushed first). */
+int kta_get_header_names(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes: after kta_exchange the whole job's vector on every rank. */
+int kta_exchange_header_names(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot (what collectives reduce in place), and of the live vector. */
+int kta_header_names_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+int kta_header_names_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[KTA_HEADER_NAMES_WORDS]: acc <- acc + other. */
+int kta_merge_header_names(uint64_t *acc, const uint64_t *other);
+/* This context's name table, copied to out[n_slots] (n_slots = KTA_HEADER_NAMES_SLOTS); a slot that is not published comes
+ * back zeroed. */
+int kta_get_header_name_table(kta_ctx *ctx, kta_header_name *out, size_t n_slots);
+/* 1 when the identities between the words of one vector hold, 0 when not (host only): the two zero words are zero; each
+ * row's T, L, V and Z sum to the globals; no bit counter exceeds its cell's T.  payload_vec: NULL, or the payload vector
+ * u64[KTA_PAYLOAD_WORDS(P)] of the same run: occurrences, name bytes, value bytes, null values and records with headers
+ * equal the sums over the partitions of headers, header_key_bytes, header_value_bytes, header_null_values and
+ * with_headers, and the records looked at equal records - bad_headers. */
+int kta_header_names_identities(const uint64_t *vec, const uint64_t *payload_vec, uint32_t n_partitions);
+/* The names read off a vector's table (host only) by the peel of kta_payload_schema_ids, where a pure cell's L must also be
+ * a multiple of its T: *n rows, the first min(*n, cap) in rows (cap 0: rows may be NULL), sorted by occurrences (most first),
+ * then value bytes, then hash.  table: NULL, or a name table kta_header_name[KTA_HEADER_NAMES_SLOTS]; a row has its name when
+ * a published slot of either of its cells holds its hash.  *unresolved_occurrences / *unresolved_value_bytes (may be NULL):
+ * what then remains in row 0, the occurrences in cells that hold several names — reported, never guessed at. */
+int kta_header_names_list(const uint64_t *vec, const kta_header_name *table, kta_header_name_row *rows, size_t cap, size_t *n,
+                          uint64_t *unresolved_occurrences, uint64_t *unresolved_value_bytes);
+/* The same rule on the host, for tests and the CPU suite, as kta_payload_host: added to vec[KTA_HEADER_NAMES_WORDS] and, when
+ * not NULL, to table[KTA_HEADER_NAMES_SLOTS] (first writer wins).  A partition outside [0, P) adds nothing.  No filter. */
+int kta_header_names_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, kta_header_name *table, uint32_t n_partitions);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1379,6 +1459,18 @@ int kta_render_record_batches(const uint64_t *vec, uint32_t n_partitions, int fi
  *   a note with the section's limits, and a closing `=` rule.
  * A share or mean whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
 int kta_render_payload(const uint64_t *vec, const uint64_t *counter_vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
+/* The opt-in header-name section that kta-analyzer prints behind the payload section's position with --librdkafka
+ * kta.headers=1, from a header-name vector and (or NULL) a name table (host only):
+ *   a title line that names the knob and says that it is not part of the reference report;
+ *   a line with the globals;
+ *   a table (# | Name | Hash | Occurrences | per record with headers | Name bytes | Value bytes | Mean value | Null values |
+ *    Share of header bytes) of the listed names, at most max_names rows, then `... and K more`: the name escaped as
+ *    kta_render_hot_keys escapes keys, `...` behind a name longer than 48 bytes, `#%08x` of the hash without an exemplar; per
+ *    record with headers = occurrences over the records with headers (a mean); Mean value = value bytes over the occurrences
+ *    whose value is not null; Share = the name's name + value bytes over the topic's;
+ *   a line for the unresolved remainder when there is one; a closing `=` rule.
+ * A figure whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
+int kta_render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names, char *out, size_t out_cap, size_t *out_len);
 int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
                       uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 

@@ -36,7 +36,8 @@
  * What the batch headers themselves say — records per batch, bytes on disk against inflated bytes per codec, idempotent and
  * transactional producers, leader epochs, offset holes — is accumulated on the device by the opt-in record-batch section
  * (KTA_FLAG_RECORD_BATCHES, kta_hip.h), from the descriptors and the headers of every decode call; what lies inside the
- * records — value formats, schema-registry ids, record headers — by the opt-in payload section (KTA_FLAG_PAYLOAD).
+ * records — value formats, schema-registry ids, record headers — by the opt-in payload section (KTA_FLAG_PAYLOAD); which
+ * header names those are by the opt-in header-name section (KTA_FLAG_HEADER_NAMES).
  */
 #ifndef KTA_KAFKA_H
 #define KTA_KAFKA_H
@@ -217,6 +218,12 @@ int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
  * it, out[2] workgroups of the last launch, out[3] launches timed since the previous call; *avg_ms (may be NULL) their mean
  * duration, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute stream. */
 int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
+
+/* The header-name pass (KTA_FLAG_HEADER_NAMES, kta_hip.h): out[0 .. 3] as kta_payload_info's, since the context was created;
+ * since creation / kta_reset: out[4] occurrences that found their cache slot held by another name and went straight to the
+ * table (the spill path), out[5] cache slots claimed, out[6] cache flushes in front of a workgroup's end; out[7] zero.
+ * *avg_ms as there.  Waits for the compute stream. */
+int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,9 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "compact_delete_max_partitions", "split_compact_delete", "compact_delete_whatif", "COMPACT_DELETE_COLUMNS",
            "render_compact_delete", "split_record_batches", "merge_record_batches", "render_record_batches", "estimate_producers",
            "record_batches_identities", "record_batches_host", "RECORD_BATCH_COLUMNS", "RECORD_BATCH_CODECS", "split_payload", "merge_payload",
-           "payload_identities", "payload_schema_ids", "payload_host", "render_payload", "PAYLOAD_COLUMNS", "PAYLOAD_CLASSES"]
+           "payload_identities", "payload_schema_ids", "payload_host", "render_payload", "PAYLOAD_COLUMNS", "PAYLOAD_CLASSES",
+           "split_header_names", "merge_header_names", "header_names_identities", "header_names_list", "header_names_host",
+           "render_header_names", "HEADER_NAME_DTYPE", "HEADER_NAMES_GLOBALS"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -92,6 +94,7 @@ _SECTIONS = {
     "segments": (lambda P, M: segments_words(P, M), "a segment vector of {} partitions and {} rows"),
     "record_batches": (lambda P: 20 * P + 1524, "a record-batch vector of {} partitions"),
     "payload": (lambda P: 24 * P + 16 + 2 * 1024 * 34, "a payload vector of {} partitions"),
+    "header_names": (lambda: N.KTA_HEADER_NAMES_WORDS, "a header-name vector"),
     "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
     "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
 }
@@ -142,7 +145,7 @@ class HipMetricHandler:
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
                  compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
-                 compact_delete: bool = False, record_batches: bool = False, payload: bool = False):
+                 compact_delete: bool = False, record_batches: bool = False, payload: bool = False, header_names: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -163,7 +166,9 @@ class HipMetricHandler:
         record_batches: the record-batch section (KTA_FLAG_RECORD_BATCHES: what the batch headers of the raw-log decode say,
         get_record_batches());
         payload: the payload section (KTA_FLAG_PAYLOAD: value formats, schema-registry ids and record headers of the records of
-        the raw-log decode, get_payload())."""
+        the raw-log decode, get_payload());
+        header_names: the header-name section (KTA_FLAG_HEADER_NAMES: a census of the names of the record headers of the raw-log
+        decode, header_names() and header_name_table())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -175,12 +180,14 @@ class HipMetricHandler:
         self.size_quantiles_on = bool(size_quantiles)
         self.record_batches_on = bool(record_batches)
         self.payload_on = bool(payload)
+        self.header_names_on = bool(header_names)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
                         (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
                         (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) | (N.KTA_FLAG_PAYLOAD if payload else 0) |
+                        (N.KTA_FLAG_HEADER_NAMES if header_names else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -487,7 +494,7 @@ class HipMetricHandler:
             return (P, self.segments_config[1])
         if name == "partitioner":
             return (P, self.repartition)
-        if name == "hot_keys":
+        if name in ("hot_keys", "header_names"):
             return ()
         return (P,)
 
@@ -759,6 +766,40 @@ class HipMetricHandler:
         self._check(self._lib.kta_payload_info(self._ctx, C.byref(out), C.byref(ms)))
         return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
                 "kernel_ms": float(ms.value) if out[3] else None}
+
+    def header_names(self) -> dict:
+        """The live header-name vector as split_header_names gives it, with this context's name table (kta_get_header_names;
+        staged messages are flushed first)."""
+        return split_header_names(self._read_section("header_names", self._lib.kta_get_header_names), self.header_name_table())
+
+    def exchange_header_names(self) -> dict:
+        """As header_names(), of the snapshot finish() / exchange() took: after exchange(), the whole job's vector; the name
+        table stays this context's own."""
+        return split_header_names(self._read_section("header_names", self._lib.kta_exchange_header_names), self.header_name_table())
+
+    def header_name_table(self) -> np.ndarray:
+        """This context's name table (kta_get_header_name_table): a structured array [2048] of HEADER_NAME_DTYPE; a slot that is
+        not published is all zeros."""
+        out = np.zeros(N.KTA_HEADER_NAMES_SLOTS, dtype=HEADER_NAME_DTYPE)
+        self._check(self._lib.kta_get_header_name_table(self._ctx, _np_ptr(out), out.size))
+        return out
+
+    def header_names_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the header-name snapshot (for collectives: allreduce_header_names_vector)."""
+        return self._device_vector(self._lib.kta_header_names_result_vector)
+
+    def header_names_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live header-name vector."""
+        return self._device_vector(self._lib.kta_header_names_vector)
+
+    def header_names_info(self) -> dict:
+        """The header-name pass's work (kta_header_names_info): launches, batches, workgroups and timed launches since creation;
+        spills (occurrences that went past the workgroup's cache), claims and early cache flushes since creation / reset();
+        kernel_ms as payload_info's."""
+        out, ms = (C.c_uint64 * 8)(), C.c_float()
+        self._check(self._lib.kta_header_names_info(self._ctx, C.byref(out), C.byref(ms)))
+        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]), "spills": int(out[4]),
+                "claims": int(out[5]), "cache_flushes": int(out[6]), "kernel_ms": float(ms.value) if out[3] else None}
 
     def size_quantiles_info(self) -> dict:
         """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""
@@ -1273,6 +1314,84 @@ def render_payload(vec, n_partitions: int, counter_vec=None) -> str:
     if c is not None and c.size != 7 * n_partitions + 8:
         raise ValueError(f"a counter vector of {n_partitions} partitions has {7 * n_partitions + 8} words, not {c.size}")
     return _render(N.load().kta_render_payload, _np_ptr(v), None if c is None else _np_ptr(c), n_partitions)
+
+
+HEADER_NAMES_GLOBALS = ("occurrences", "name_bytes", "value_bytes", "null_values", "with_headers", "looked")
+HEADER_NAME_DTYPE = np.dtype([("hash", np.uint32), ("name_len", np.uint32), ("state", np.uint32), ("reserved", np.uint32),
+                              ("bytes", np.uint8, (N.KTA_HEADER_NAME_BYTES,))])
+_HEADER_NAME_ROW_DTYPE = np.dtype([("hash", np.uint32), ("has_name", np.uint32), ("occurrences", np.uint64), ("name_len", np.uint64),
+                                   ("value_bytes", np.uint64), ("null_values", np.uint64), ("name", np.uint8, (N.KTA_HEADER_NAME_BYTES,))])
+
+
+def _name_table(table) -> Optional[np.ndarray]:
+    if table is None:
+        return None
+    t = np.ascontiguousarray(table, dtype=HEADER_NAME_DTYPE).reshape(-1)
+    if t.size != N.KTA_HEADER_NAMES_SLOTS:
+        raise ValueError(f"a name table has {N.KTA_HEADER_NAMES_SLOTS} slots, not {t.size}")
+    return t
+
+
+def split_header_names(vec, table=None) -> dict:
+    """A header-name vector u64[8 + 2 * 1024 * 36] as a dict, split by its layout (kta_hip.h, above KTA_FLAG_HEADER_NAMES): the
+    six globals by HEADER_NAMES_GLOBALS; "table" [2][1024][36] (T, L, V, Z, 32 bit counters); "names" what header_names_list
+    reads off it with the name table `table` (or None); the vector under "vector"."""
+    v = _section_vec("header_names", vec)
+    out = {name: int(v[i]) for i, name in enumerate(HEADER_NAMES_GLOBALS)}
+    out.update({"table": v[N.KTA_HEADER_NAMES_GLOBALS:].reshape(2, 1024, 36).copy(), "names": header_names_list(v, table), "vector": v})
+    return out
+
+
+def merge_header_names(acc: np.ndarray, other) -> np.ndarray:
+    """kta_merge_header_names, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    return _merge("header_names", acc, other)
+
+
+def header_names_identities(vec, payload_vec=None, n_partitions: int = 0) -> bool:
+    """kta_header_names_identities: whether the identities between the words of one header-name vector hold; with payload_vec
+    (the payload vector of the same run, of n_partitions partitions) also those between the two sections."""
+    p = None if payload_vec is None else _section_vec("payload", payload_vec, n_partitions)
+    rc = N.load().kta_header_names_identities(_np_ptr(_section_vec("header_names", vec)), None if p is None else _np_ptr(p), n_partitions)
+    if rc < 0:
+        raise KtaError(rc, "kta_header_names_identities")
+    return rc == 1
+
+
+def header_names_list(vec, table=None) -> dict:
+    """kta_header_names_list: the names read off a header-name vector's table — "names" [(hash, occurrences, name length,
+    value bytes, null values, name)] sorted by occurrences (most first), value bytes, hash; exact; name: the first 48 bytes at
+    most, or None without a published slot in `table`; "unresolved_occurrences" / "unresolved_value_bytes": what remains in
+    cells that hold several names."""
+    v, t = _section_vec("header_names", vec), _name_table(table)
+    lib, n, uo, ub = N.load(), C.c_size_t(), C.c_uint64(), C.c_uint64()
+    tp = None if t is None else _np_ptr(t)
+    rc = lib.kta_header_names_list(_np_ptr(v), tp, None, 0, C.byref(n), C.byref(uo), C.byref(ub))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_header_names_list")
+    rows = np.zeros(max(n.value, 1), dtype=_HEADER_NAME_ROW_DTYPE)
+    rc = lib.kta_header_names_list(_np_ptr(v), tp, _np_ptr(rows), rows.size, C.byref(n), C.byref(uo), C.byref(ub))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_header_names_list")
+    names = [(int(r["hash"]), int(r["occurrences"]), int(r["name_len"]), int(r["value_bytes"]), int(r["null_values"]),
+              bytes(r["name"][:min(int(r["name_len"]), N.KTA_HEADER_NAME_BYTES)]) if r["has_name"] else None) for r in rows[:n.value]]
+    return {"names": names, "unresolved_occurrences": int(uo.value), "unresolved_value_bytes": int(ub.value)}
+
+
+def header_names_host(blob: bytes, partition: int, n_partitions: int, vec=None, table=None):
+    """kta_header_names_host: the section's rule over the records of `blob` on the host (compressed batches inflated), added to
+    `vec` and `table` (new ones when None).  Returns (vec, table)."""
+    v = np.zeros(N.KTA_HEADER_NAMES_WORDS, np.uint64) if vec is None else _section_vec("header_names", vec)
+    t = np.zeros(N.KTA_HEADER_NAMES_SLOTS, dtype=HEADER_NAME_DTYPE) if table is None else _name_table(table)
+    rc = N.load().kta_header_names_host(bytes(blob), len(blob), int(partition), _np_ptr(v), _np_ptr(t), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_header_names_host")
+    return v, t
+
+
+def render_header_names(vec, table=None, max_names: int = 256) -> str:
+    """kta_render_header_names: the section kta-analyzer prints with --librdkafka kta.headers=1."""
+    t = _name_table(table)
+    return _render(N.load().kta_render_header_names, _np_ptr(_section_vec("header_names", vec)), None if t is None else _np_ptr(t), int(max_names))
 
 
 def size_bin(size: int) -> int:

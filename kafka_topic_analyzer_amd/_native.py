@@ -69,6 +69,10 @@ KTA_RB_PARTITION_WORDS, KTA_RB_CODECS, KTA_RB_CODEC_WORDS, KTA_RB_HIST_BINS, KTA
 # payload vector: u64[24 P + 16 + 2 * 1024 * 34] = [P][24] sums | 16 histogram bins | [2 rows][1024 cells][34: T, B, 32 bit counters]
 KTA_FLAG_PAYLOAD = 1024
 KTA_PAYLOAD_PARTITION_WORDS, KTA_PAYLOAD_CLASSES, KTA_PAYLOAD_HIST_BINS, KTA_PAYLOAD_ROWS, KTA_PAYLOAD_CELLS, KTA_PAYLOAD_CELL_WORDS = 24, 5, 16, 2, 1024, 34
+# header-name vector: u64[8 + 2 * 1024 * 36] = 8 globals | [2 rows][1024 cells][36: T, L, V, Z, 32 bit counters]; beside it the name table [2 * 1024]
+KTA_FLAG_HEADER_NAMES = 2048
+KTA_HEADER_NAMES_GLOBALS, KTA_HEADER_NAMES_ROWS, KTA_HEADER_NAMES_CELLS, KTA_HEADER_NAMES_CELL_WORDS = 8, 2, 1024, 36
+KTA_HEADER_NAMES_WORDS, KTA_HEADER_NAMES_SLOTS, KTA_HEADER_NAME_BYTES, KTA_HEADER_NAME_PUBLISHED = 8 + 2 * 1024 * 36, 2 * 1024, 48, 2
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -79,6 +83,16 @@ KTA_HOT_MAX_REPORTED = 64
 class KtaHotExemplar(C.Structure):
     _fields_ = [("hash", C.c_uint32), ("key_len", C.c_uint32), ("valid", C.c_uint32), ("pad", C.c_uint32),
                 ("bytes", C.c_uint8 * KTA_HOT_EXEMPLAR_BYTES)]
+
+
+class KtaHeaderName(C.Structure):
+    _fields_ = [("hash", C.c_uint32), ("name_len", C.c_uint32), ("state", C.c_uint32), ("reserved", C.c_uint32),
+                ("bytes", C.c_uint8 * KTA_HEADER_NAME_BYTES)]
+
+
+class KtaHeaderNameRow(C.Structure):
+    _fields_ = [("hash", C.c_uint32), ("has_name", C.c_uint32), ("occurrences", C.c_uint64), ("name_len", C.c_uint64),
+                ("value_bytes", C.c_uint64), ("null_values", C.c_uint64), ("name", C.c_uint8 * KTA_HEADER_NAME_BYTES)]
 
 
 class KtaHotKey(C.Structure):
@@ -264,6 +278,18 @@ SIGNATURES = {
     "kta_payload_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint32]),
     "kta_payload_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
     "kta_render_payload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_get_header_names": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_header_names": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_header_names_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_header_names_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_header_names": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kta_get_header_name_table": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_header_names_identities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_header_names_list": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64)]),
+    "kta_header_names_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_header_names_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 8), C.POINTER(C.c_float)]),
+    "kta_render_header_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_set_segments": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kta_segments_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),

@@ -49,6 +49,9 @@
 // kta.payload=1 (0: off; segment:// sources only, kta.gpus=N and -c included, not with kta.per_message=1: the pass reads the record
 // bytes of the raw log) runs the payload pass as well (KTA_FLAG_PAYLOAD) and prints its section behind every other one: value
 // formats, schema-registry ids, record headers.
+// kta.headers=1 (0: off; the same sources and refusals as kta.payload=1, with or without it) runs the header-name pass as well
+// (KTA_FLAG_HEADER_NAMES) and prints its section behind the payload section's position: the names of the record headers with
+// their occurrences, bytes and null values.  Under kta.gpus=N a listed name comes from the lowest rank that holds it.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -210,6 +213,8 @@ std::vector<uint64_t> partitioner_counters(const kta::MessageMetrics &m, uint32_
     return c;
 }
 
+constexpr uint32_t kHeaderNamesShown = 256;   // kta.headers=1: the rows of the section's table at most
+
 // murmur3's finaliser: x = hot_fmix32(hash) places a key hash in the hot-key sketch (kta_hip.h)
 uint32_t hot_fmix32(uint32_t x)
 {
@@ -365,6 +370,7 @@ struct ShardedJob {
     bool record_batches = false;                       // kta.record_batches=1: likewise (segment:// only)
     uint64_t rb_skipped[3] = {0, 0, 0};                //   control batches, magic 0/1 sets, unknown codecs: the host index's, whole topic
     bool payload = false;                              // kta.payload=1: likewise (segment:// only)
+    bool headers = false;                              // kta.headers=1: likewise (segment:// only); the name tables stay on their ranks
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
@@ -383,7 +389,8 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                                (job.analytics ? KTA_FLAG_ANALYTICS : 0u) | (job.distinct_keys ? KTA_FLAG_KEY_SKETCH : 0u) |
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) |
-                               (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) | (job.payload ? KTA_FLAG_PAYLOAD : 0u);
+                               (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) | (job.payload ? KTA_FLAG_PAYLOAD : 0u) |
+                               (job.headers ? KTA_FLAG_HEADER_NAMES : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -555,6 +562,29 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
                                        (uint64_t)filter_counts[0], (uint64_t)filter_counts[1]);
         if (job.record_batches) text += kta::render_record_batches(h0->record_batches()->data(), job.P, job.filter.on, job.rb_skipped);
         if (job.payload) text += kta::render_payload(h0->payload()->data(), partitioner_counters(metrics, job.P).data(), job.P);
+        if (job.headers) {
+            // a slot a lower rank published stays: every listed hash gets its name from the lowest rank that has it
+            std::vector<kta_header_name> merged = *h0->header_name_table();
+            size_t n = 0;
+            if (kta_header_names_list(h0->header_names()->data(), nullptr, nullptr, 0, &n, nullptr, nullptr) != KTA_OK) n = 0;
+            std::vector<kta_header_name_row> listed(n);
+            if (n && kta_header_names_list(h0->header_names()->data(), nullptr, listed.data(), n, &n, nullptr, nullptr) != KTA_OK) n = 0;
+            for (size_t r = 1; r < handlers.size(); r++) {
+                const std::vector<kta_header_name> &tab = *handlers[r]->header_name_table();
+                for (size_t k = 0; k < n; k++) {
+                    const uint32_t h = listed[k].hash;
+                    const size_t at[2] = {h & 1023u, KTA_HEADER_NAMES_CELLS + (hot_fmix32(h) & 1023u)};
+                    const bool have = (merged[at[0]].state == KTA_HEADER_NAME_PUBLISHED && merged[at[0]].hash == h) ||
+                                      (merged[at[1]].state == KTA_HEADER_NAME_PUBLISHED && merged[at[1]].hash == h);
+                    for (size_t a : at)
+                        if (!have && tab[a].state == KTA_HEADER_NAME_PUBLISHED && tab[a].hash == h) {
+                            merged[a] = tab[a];
+                            break;
+                        }
+                }
+            }
+            text += kta::render_header_names(h0->header_names()->data(), merged.data(), kHeaderNamesShown);
+        }
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -617,6 +647,21 @@ int main(int argc, char **argv)
         payload = v == "1";
         if (payload && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
             fprintf(stderr, "kta.payload=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
+                            "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
+            return 2;
+        }
+    }
+    // kta.headers: likewise
+    bool headers = false;
+    if (cfg.count("kta.headers")) {
+        const std::string &v = cfg["kta.headers"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.headers=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        headers = v == "1";
+        if (headers && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
+            fprintf(stderr, "kta.headers=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
                             "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
             return 2;
         }
@@ -1012,6 +1057,7 @@ int main(int argc, char **argv)
         job.percentiles = percentiles;
         job.record_batches = record_batches;
         job.payload = payload;
+        job.headers = headers;
         std::copy(rb_skipped, rb_skipped + 3, job.rb_skipped);
         job.filter = filter;
         job.segments = segments;
@@ -1035,7 +1081,7 @@ int main(int argc, char **argv)
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                                 (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
                                                 (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) |
-                                                (payload ? KTA_FLAG_PAYLOAD : 0u),
+                                                (payload ? KTA_FLAG_PAYLOAD : 0u) | (headers ? KTA_FLAG_HEADER_NAMES : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1285,6 +1331,7 @@ int main(int argc, char **argv)
                                        filter_info[1]);
         if (record_batches) text += kta::render_record_batches(handler->record_batches()->data(), P, filter.on, rb_skipped);
         if (payload) text += kta::render_payload(handler->payload()->data(), partitioner_counters(metrics, P).data(), P);
+        if (headers) text += kta::render_header_names(handler->header_names()->data(), handler->header_name_table()->data(), kHeaderNamesShown);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

@@ -10,6 +10,7 @@
 
 #include "kta_compact_delete.h"
 #include "kta_compaction.h"
+#include "kta_header_names.h"
 #include "kta_payload.h"
 #include "kta_record_batches.h"
 #include "kta_segments.h"
@@ -761,6 +762,26 @@ static uint32_t fmix32(uint32_t x)
     return x;
 }
 
+// The first min(len, kept) bytes of a key or a name as the sections print them: printable ASCII but the backslash as it is,
+// every other byte as \xHH; `...` behind one that was longer than what is kept.
+static std::string escaped_bytes(const uint8_t *bytes, uint64_t len, uint32_t kept)
+{
+    std::string t;
+    const uint32_t shown = (uint32_t)std::min<uint64_t>(len, kept);
+    for (uint32_t b = 0; b < shown; b++) {
+        const uint8_t ch = bytes[b];
+        if (ch >= 0x20 && ch < 0x7f && ch != '\\') {
+            t += (char)ch;
+        } else {
+            char buf[8];
+            snprintf(buf, sizeof buf, "\\x%02X", ch);
+            t += buf;
+        }
+    }
+    if (len > kept) t += "...";
+    return t;
+}
+
 // The opt-in hot-key section (kta.hot_keys=K): no reference counterpart, printed after every other section.
 std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys)
 {
@@ -782,20 +803,7 @@ std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exempla
         for (const kta_hot_exemplar *e : {exemplars + (x & 1023u), exemplars + KTA_HOT_CELLS + ((x >> 10) & 1023u)})
             if (!found && e->valid && e->hash == hash) found = e;
         if (!found) return std::string("-");
-        std::string t;
-        const uint32_t shown = std::min<uint32_t>(found->key_len, KTA_HOT_EXEMPLAR_BYTES);
-        for (uint32_t b = 0; b < shown; b++) {
-            const uint8_t ch = found->bytes[b];
-            if (ch >= 0x20 && ch < 0x7f && ch != '\\') {
-                t += (char)ch;
-            } else {
-                char buf[8];
-                snprintf(buf, sizeof buf, "\\x%02X", ch);
-                t += buf;
-            }
-        }
-        if (found->key_len > KTA_HOT_EXEMPLAR_BYTES) t += "...";
-        return t;
+        return escaped_bytes(found->bytes, found->key_len, KTA_HOT_EXEMPLAR_BYTES);
     };
     std::vector<std::vector<std::string>> rows;
     rows.push_back({"#", "Key", "Hash", "Records (at most)", "(at least)", "Share of keyed records"});
@@ -811,7 +819,62 @@ std::string render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exempla
     return o;
 }
 
+// The opt-in header-name section (kta.headers=1): no reference counterpart, printed behind the payload section's position.
+// vec: u64[73736] (kta_hip.h; the layout and the read-off are kta_header_names.h's); table: kta_header_name[2048] or nullptr.
+std::string render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names)
+{
+    auto ratio = [](uint64_t num, uint64_t den, double scale) -> std::string {
+        if (den == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)num * scale / (double)den);
+        return buf;
+    };
+    uint64_t unresolved = 0, unresolved_bytes = 0;
+    const std::vector<HnListed> names = hn_list(vec, reinterpret_cast<const HnSlot *>(table), &unresolved, &unresolved_bytes);
+    std::string o;
+    o += "Header names: a census of the record headers (kta.headers=1; not part of the reference report)\n";
+    o += std::to_string(vec[kHnOccurrences]) + " headers in " + std::to_string(vec[kHnWithHeaders]) + " of " + std::to_string(vec[kHnLooked]) +
+         " records looked at: " + std::to_string(vec[kHnNameBytes]) + " name bytes, " + std::to_string(vec[kHnValueBytes]) + " value bytes, " +
+         std::to_string(vec[kHnNullValues]) + " null values, " + std::to_string(names.size()) + " names listed\n";
+    if (!names.empty()) {
+        std::vector<std::vector<std::string>> rows;
+        rows.push_back({"#", "Name", "Hash", "Occurrences", "per record with headers", "Name bytes", "Value bytes", "Mean value", "Null values",
+                        "Share of header bytes"});
+        for (size_t i = 0; i < names.size() && i < max_names; i++) {
+            const HnListed &n = names[i];
+            char hash[16];
+            snprintf(hash, sizeof hash, "%08x", n.hash);
+            const uint64_t name_bytes = n.occurrences * n.name_len;
+            rows.push_back({std::to_string(i + 1), n.name ? escaped_bytes(n.name->bytes, n.name->name_len, kHnExemplarBytes) : std::string("#") + hash, hash,
+                            std::to_string(n.occurrences), ratio(n.occurrences, vec[kHnWithHeaders], 1.0), std::to_string(name_bytes),
+                            std::to_string(n.value_bytes), ratio(n.value_bytes, n.occurrences - n.null_values, 1.0), std::to_string(n.null_values),
+                            ratio(name_bytes + n.value_bytes, vec[kHnNameBytes] + vec[kHnValueBytes], 100.0)});
+        }
+        o += pretty_table(rows);
+        if (names.size() > max_names) o += "... and " + std::to_string(names.size() - max_names) + " more\n";
+    }
+    if (unresolved)
+        o += "Unresolved: " + std::to_string(unresolved) + " occurrences, " + std::to_string(unresolved_bytes) +
+             " value bytes in table cells that hold several names\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names, char *out, size_t out_cap,
+                                       size_t *out_len)
+{
+    if (!vec || !out_len || max_names == 0) return KTA_ERR_INVALID;
+    const std::string text = kta::render_header_names(vec, table, max_names);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_hot_keys(const uint64_t *vec, const kta_hot_exemplar *exemplars, uint32_t max_keys, char *out,
                                    size_t out_cap, size_t *out_len)

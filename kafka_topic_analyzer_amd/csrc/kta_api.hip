@@ -6,6 +6,7 @@
 #include "../../include/kta_hip.h"
 #include "kta_compact_delete.h"
 #include "kta_compaction.h"
+#include "kta_header_names.h"
 #include "kta_internal.h"
 #include "kta_kernels.h"
 #include "kta_murmur2.h"
@@ -139,6 +140,12 @@ struct kta_ctx {
     // d_pl_out its snapshot
     bool pl = false;
     DeviceBuf<uint64_t> d_pl, d_pl_out;
+    // header names (KTA_FLAG_HEADER_NAMES): d_hn u64[73736] the live vector that the decode call adds to
+    // (kta_internal_header_names), d_hn_out its snapshot, d_hn_names the name table beside it (not snapshotted, not exchanged),
+    // d_hn_info the pass's work counters
+    bool hn = false;
+    DeviceBuf<uint64_t> d_hn, d_hn_out, d_hn_info;
+    DeviceBuf<kta_header_name> d_hn_names;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -888,6 +895,7 @@ Shape segments_shape(uint32_t P, uint32_t M)
 }
 Shape record_batches_shape(uint32_t P) { return Shape{kta::rb_len(P), kta::rb_sum_words(P), false}; }
 Shape payload_shape(uint32_t P) { return all_sum(kta::payload_len(P)); }
+Shape header_names_shape() { return all_sum(kta::kHnWords); }
 Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
 
 // what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
@@ -911,6 +919,14 @@ static_assert(kta::kPlPartitionWords == KTA_PAYLOAD_PARTITION_WORDS && kta::kPlH
               "kta_payload.h and kta_hip.h");
 static_assert(KTA_PAYLOAD_WORDS(7) == 24 * 7 + 16 + 2 * 1024 * 34 && kta::kPlPartitionWords * 7 + kta::kPlHistBins + kta::kPlTableWords == KTA_PAYLOAD_WORDS(7),
               "the payload vector's length: kta_payload.h and kta_hip.h");
+static_assert(KTA_HEADER_NAMES_WORDS == kta::kHnWords && KTA_HEADER_NAMES_GLOBALS == kta::kHnGlobals && KTA_HEADER_NAMES_CELL_WORDS == kta::kHnCellWords &&
+                  KTA_HEADER_NAMES_SLOTS == kta::kHnSlots && KTA_HEADER_NAME_BYTES == kta::kHnExemplarBytes && KTA_HEADER_NAMES_ROWS == kta::kPlRows &&
+                  KTA_HEADER_NAMES_CELLS == kta::kPlCells,
+              "kta_header_names.h and kta_hip.h");
+static_assert(sizeof(kta_header_name) == sizeof(kta::HnSlot) && offsetof(kta_header_name, hash) == offsetof(kta::HnSlot, hash) &&
+                  offsetof(kta_header_name, name_len) == offsetof(kta::HnSlot, name_len) && offsetof(kta_header_name, state) == offsetof(kta::HnSlot, state) &&
+                  offsetof(kta_header_name, bytes) == offsetof(kta::HnSlot, bytes) && KTA_HEADER_NAME_PUBLISHED == kta::kHnPublished,
+              "a slot of the name table: kta_header_names.h and kta_hip.h");
 
 // One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
 // and out point at the context's owners, allocated or not.
@@ -947,6 +963,8 @@ void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
     s[KTA_RV_RECORD_BATCHES] = Section{ctx->rb, &ctx->d_rb, &ctx->d_rb_out, record_batches_shape(P), true, "record-batch vector",
                                        "context was created without KTA_FLAG_RECORD_BATCHES"};
     s[KTA_RV_PAYLOAD] = Section{ctx->pl, &ctx->d_pl, &ctx->d_pl_out, payload_shape(P), true, "payload vector", "context was created without KTA_FLAG_PAYLOAD"};
+    s[KTA_RV_HEADER_NAMES] = Section{ctx->hn, &ctx->d_hn, &ctx->d_hn_out, header_names_shape(), true, "header-name vector",
+                                      "context was created without KTA_FLAG_HEADER_NAMES"};
     s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
                                     "context was created without KTA_FLAG_COMPACTION"};
     s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
@@ -1104,6 +1122,10 @@ int reset_state(kta_ctx *ctx)
         int rc = clear_segments(ctx);
         if (rc != KTA_OK) return rc;
     }
+    if (ctx->hn) {                      // (the name table is cleared with the vector; the work counters as well)
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hn_names.get(), 0, kta::kHnSlots * sizeof(kta_header_name), ctx->s_compute));
+        KTA_HIP(ctx, hipMemsetAsync(ctx->d_hn_info.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
+    }
     if (ctx->part) {
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->part_launches = ctx->part_workgroups = 0;
@@ -1157,6 +1179,38 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
         const Section &s = sec[k];
         rv[k] = s.on ? ResultVector{s.out->get(), s.shape.words, s.shape.sum_words, s.shape.max_signed} : ResultVector{nullptr, 0, 0, false};
     }
+}
+
+// The batches of bytes[0, len) that count on the host, as kta_kafka_index_host finds them, compressed ones inflated:
+// batch(record bytes, their length, n_records) for each.  A stream that does not inflate is a failed batch: skipped.
+template <class OnBatch>
+static int host_batches(const uint8_t *bytes, uint64_t len, int32_t partition, OnBatch batch)
+{
+    kta_kafka_index_stats st;
+    int rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, nullptr, 0, &st);
+    if (rc != KTA_OK && rc != KTA_ERR_CAPACITY) return rc;
+    std::vector<kta_kafka_batch_desc> descs(st.n_batches);
+    rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, descs.data(), descs.size(), &st);
+    if (rc != KTA_OK) return rc;
+    std::vector<uint8_t> inflated;
+    for (const kta_kafka_batch_desc &d : descs) {
+        if (d.status != 0 || d.n_records <= 0 || d.byte_off > len || len - d.byte_off < d.batch_bytes || d.batch_bytes < KTA_KAFKA_BATCH_HEADER) continue;
+        const uint8_t *src = bytes + d.byte_off + KTA_KAFKA_BATCH_HEADER;
+        const uint64_t n = d.batch_bytes - KTA_KAFKA_BATCH_HEADER;
+        if (!(d.flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD))) {
+            batch(src, n, (uint64_t)d.n_records);
+            continue;
+        }
+        const uint64_t cap = d.payload_end > d.payload_off ? d.payload_end - d.payload_off : 0;   // the index's bound (exact for gzip and Snappy)
+        inflated.assign(cap + 64, 0);
+        const int64_t got = (d.flags & KTA_KB_SNAPPY) ? kta_snappy_inflate_host(src, n, inflated.data(), cap)
+                            : (d.flags & KTA_KB_LZ4)  ? kta_lz4_inflate_host(src, n, inflated.data(), cap)
+                            : (d.flags & KTA_KB_GZIP) ? kta_gzip_inflate_host(src, n, inflated.data(), cap)
+                                                      : kta_zstd_inflate_host(src, n, inflated.data(), cap);
+        if (got < 0) continue;
+        batch(inflated.data(), (uint64_t)got, (uint64_t)d.n_records);
+    }
+    return KTA_OK;
 }
 
 extern "C" {
@@ -1243,6 +1297,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->sizeq = (cfg->flags & KTA_FLAG_SIZE_QUANTILES) != 0;
     ctx->rb = (cfg->flags & KTA_FLAG_RECORD_BATCHES) != 0;
     ctx->pl = (cfg->flags & KTA_FLAG_PAYLOAD) != 0;
+    ctx->hn = (cfg->flags & KTA_FLAG_HEADER_NAMES) != 0;
     {
         const char *qv = getenv("KTA_SIZEQ_VARIANT");   // A/B switch of tools/bench_size_quantiles.py: 1 a launch per slice, 9 loads only
         ctx->sizeq_variant = qv && (qv[0] == '1' || qv[0] == '9') && !qv[1] ? qv[0] - '0' : 0;
@@ -1301,6 +1356,10 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_tso_stats.alloc(3));
     }
     if (ctx->part) KTA_TRY(ctx->d_part_stats.alloc(3));
+    if (ctx->hn) {
+        KTA_TRY(ctx->d_hn_names.alloc(kta::kHnSlots));
+        KTA_TRY(ctx->d_hn_info.alloc(4));
+    }
     if (ctx->comp) KTA_TRY(ctx->d_comp_stats.alloc(3));
     if (ctx->sizeq) KTA_TRY(ctx->d_sizeq_stats.alloc(kSizeqStatWords));
     if (ctx->alive) {
@@ -2360,32 +2419,70 @@ int kta_payload_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint
 {
     if (!bytes || !vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
     if (partition < 0 || (uint32_t)partition >= P) return KTA_OK;             // outside [0, P): adds nothing
-    kta_kafka_index_stats st;
-    int rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, nullptr, 0, &st);
-    if (rc != KTA_OK && rc != KTA_ERR_CAPACITY) return rc;
-    std::vector<kta_kafka_batch_desc> descs(st.n_batches);
-    rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, descs.data(), descs.size(), &st);
+    auto passes = [](long long) { return true; };                               // (no context, no filter)
+    return host_batches(bytes, len, partition, [&](const uint8_t *recs, uint64_t n, uint64_t n_records) {
+        kta::payload_batch_host(vec, P, (uint32_t)partition, recs, 0, n, n_records, passes);
+    });
+}
+
+// ---- header names (kta_header_names.h holds the rule, kta_header_names.hip the kernel, kta_kafka.hip the launch) ---------
+
+int kta_get_header_names(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_HEADER_NAMES, out, n_u64); }
+int kta_exchange_header_names(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_HEADER_NAMES, out, n_u64); }
+int kta_header_names_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_HEADER_NAMES, true, device_ptr, n_u64);
+}
+int kta_header_names_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64) { return section_vector(ctx, KTA_RV_HEADER_NAMES, false, device_ptr, n_u64); }
+int kta_merge_header_names(uint64_t *acc, const uint64_t *other) { return merge_section(acc, other, true, header_names_shape()); }
+
+int kta_get_header_name_table(kta_ctx *ctx, kta_header_name *out, size_t n_slots)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    if (!ctx->hn) return section_off(ctx, KTA_RV_HEADER_NAMES);
+    if (n_slots != kta::kHnSlots)
+        return fail(ctx, KTA_ERR_INVALID, "the name table has " + std::to_string(kta::kHnSlots) + " slots, not " + std::to_string(n_slots));
+    KTA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = kta_flush(ctx);
     if (rc != KTA_OK) return rc;
-    std::vector<uint8_t> inflated;
-    for (const kta_kafka_batch_desc &d : descs) {
-        if (d.status != 0 || d.n_records <= 0 || d.byte_off > len || len - d.byte_off < d.batch_bytes || d.batch_bytes < KTA_KAFKA_BATCH_HEADER) continue;
-        auto passes = [](long long) { return true; };                           // (no context, no filter)
-        const uint8_t *src = bytes + d.byte_off + KTA_KAFKA_BATCH_HEADER;
-        const uint64_t n = d.batch_bytes - KTA_KAFKA_BATCH_HEADER;
-        if (!(d.flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD))) {
-            kta::payload_batch_host(vec, P, (uint32_t)partition, src, 0, n, (uint64_t)d.n_records, passes);
-            continue;
-        }
-        const uint64_t cap = d.payload_end > d.payload_off ? d.payload_end - d.payload_off : 0;   // the index's bound (exact for gzip and Snappy)
-        inflated.assign(cap + 64, 0);
-        const int64_t got = (d.flags & KTA_KB_SNAPPY) ? kta_snappy_inflate_host(src, n, inflated.data(), cap)
-                            : (d.flags & KTA_KB_LZ4)  ? kta_lz4_inflate_host(src, n, inflated.data(), cap)
-                            : (d.flags & KTA_KB_GZIP) ? kta_gzip_inflate_host(src, n, inflated.data(), cap)
-                                                      : kta_zstd_inflate_host(src, n, inflated.data(), cap);
-        if (got < 0) continue;                                                  // a stream that does not inflate: a failed batch
-        kta::payload_batch_host(vec, P, (uint32_t)partition, inflated.data(), 0, (uint64_t)got, (uint64_t)d.n_records, passes);
+    KTA_HIP(ctx, hipMemcpyAsync(out, ctx->d_hn_names.get(), kta::kHnSlots * sizeof(kta_header_name), hipMemcpyDeviceToHost, ctx->s_compute));
+    KTA_HIP(ctx, hipStreamSynchronize(ctx->s_compute));
+    for (size_t i = 0; i < n_slots; i++)                                        // only published slots leave the library
+        if (out[i].state != KTA_HEADER_NAME_PUBLISHED) memset(&out[i], 0, sizeof out[i]);
+    return KTA_OK;
+}
+
+int kta_header_names_identities(const uint64_t *vec, const uint64_t *payload_vec, uint32_t P)
+{
+    if (!vec || (payload_vec && (P == 0 || P > 4096))) return KTA_ERR_INVALID;
+    return kta::hn_identities_hold(vec, payload_vec, P) ? 1 : 0;
+}
+
+int kta_header_names_list(const uint64_t *vec, const kta_header_name *table, kta_header_name_row *rows, size_t cap, size_t *n,
+                          uint64_t *unresolved_occurrences, uint64_t *unresolved_value_bytes)
+{
+    if (!vec || !n || (cap && !rows)) return KTA_ERR_INVALID;
+    const std::vector<kta::HnListed> found =
+        kta::hn_list(vec, reinterpret_cast<const kta::HnSlot *>(table), unresolved_occurrences, unresolved_value_bytes);
+    *n = found.size();
+    for (size_t i = 0; i < found.size() && i < cap; i++) {
+        kta_header_name_row &r = rows[i];
+        memset(&r, 0, sizeof r);
+        r.hash = found[i].hash, r.occurrences = found[i].occurrences, r.name_len = found[i].name_len, r.value_bytes = found[i].value_bytes;
+        r.null_values = found[i].null_values;
+        if (found[i].name) r.has_name = 1, memcpy(r.name, found[i].name->bytes, sizeof r.name);
     }
     return KTA_OK;
+}
+
+int kta_header_names_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, kta_header_name *table, uint32_t P)
+{
+    if (!bytes || !vec || P == 0 || P > 4096) return KTA_ERR_INVALID;
+    if (partition < 0 || (uint32_t)partition >= P) return KTA_OK;             // outside [0, P): adds nothing
+    auto passes = [](long long) { return true; };                               // (no context, no filter)
+    return host_batches(bytes, len, partition, [&](const uint8_t *recs, uint64_t n, uint64_t n_records) {
+        kta::hn_batch_host(vec, reinterpret_cast<kta::HnSlot *>(table), recs, 0, n, n_records, passes);
+    });
 }
 
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
@@ -2934,6 +3031,13 @@ bool kta_internal_payload(kta_ctx *ctx, kta_internal_pl *out)
     *out = kta_internal_pl{ctx->pl, ctx->d_pl.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
                            f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
     return ctx->pl && !ctx->comp_replay;
+}
+bool kta_internal_header_names(kta_ctx *ctx, kta_internal_hn *out)
+{
+    const bool f = ctx->filter;
+    *out = kta_internal_hn{ctx->hn, ctx->d_hn.get(), ctx->d_hn_names.get(), ctx->d_hn_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN,
+                           f ? ctx->filter_spec.to_ms : INT64_MAX, f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
+    return ctx->hn && !ctx->comp_replay;
 }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {

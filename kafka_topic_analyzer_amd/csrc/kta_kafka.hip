@@ -1170,6 +1170,9 @@ struct KafkaState {
     TimerPool<1> pl_timers{1024};   // the payload pass (kta_payload_info)
     uint64_t pl_launches = 0, pl_batches = 0;
     uint32_t pl_workgroups = 0;     // of the last launch
+    TimerPool<1> hn_timers{1024};   // the header-name pass (kta_header_names_info)
+    uint64_t hn_launches = 0, hn_batches = 0;
+    uint32_t hn_workgroups = 0;     // of the last launch
 };
 
 void free_out(kta_batch &o)
@@ -1664,6 +1667,15 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
         if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
         st->pl_launches++, st->pl_batches += n_batches;
     }
+    // The header-name section (KTA_FLAG_HEADER_NAMES): the same moment and the same bytes, for the names of the record headers.
+    if (kta_internal_hn hn{}; kta_internal_header_names(ctx, &hn)) {
+        if (timing) { int rc = st->hn_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        KTA_HIP_AS(ctx, kta::launch_header_names(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), hn.from_ms, hn.to_ms, hn.bitmap, hn.vec,
+                                                 hn.names, hn.info, hn.cu_count, &st->hn_workgroups, s),
+                   "kta_header_names");
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+        st->hn_launches++, st->hn_batches += n_batches;
+    }
     KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
         KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -1937,6 +1949,26 @@ int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
     int rc = st->pl_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
     if (rc != KTA_OK) return rc;
     out[0] = st->pl_launches, out[1] = st->pl_batches, out[2] = st->pl_workgroups, out[3] = timed;
+    if (avg_ms) *avg_ms = ms;
+    return KTA_OK;
+}
+
+int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_hn hn{};
+    (void)kta_internal_header_names(ctx, &hn);
+    if (!hn.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_HEADER_NAMES");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KafkaState *st = state_of(ctx);
+    float ms = -1.f;
+    uint64_t timed = 0, work[4] = {0, 0, 0, 0};
+    int rc = st->hn_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipMemcpyAsync(work, hn.info, sizeof work, hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
+    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
+    out[0] = st->hn_launches, out[1] = st->hn_batches, out[2] = st->hn_workgroups, out[3] = timed;
+    out[4] = work[0], out[5] = work[1], out[6] = work[2], out[7] = 0;
     if (avg_ms) *avg_ms = ms;
     return KTA_OK;
 }

@@ -124,6 +124,26 @@ KTA_PL_HD PayloadHeaders payload_walk_headers(Src &src, uint64_t pos, uint64_t e
     return h;
 }
 
+// The same walk, VISITING: visit(name position, name length, value length or -1 for a null value) for every header, in the
+// section's order.  For a section that payload_walk_headers found good (the header-name section, kta_header_names.h: validate,
+// then visit); on any other it returns false where the walk above returns bad, having visited the headers in front of that place.
+template <class Src, class Visit>
+KTA_PL_HD bool payload_visit_headers(Src &src, uint64_t pos, uint64_t end, Visit &&visit)
+{
+    long long count;
+    if (!payload_varlong(src, pos, end, count) || count < 0) return false;
+    for (long long i = 0; i < count; i++) {
+        long long kl, vl;
+        if (!payload_varlong(src, pos, end, kl) || kl < 0 || (uint64_t)kl > end - pos) return false;
+        const uint64_t name = pos;
+        pos += (uint64_t)kl;
+        if (!payload_varlong(src, pos, end, vl) || vl < -1 || (vl > 0 && (uint64_t)vl > end - pos)) return false;
+        visit(name, (uint64_t)kl, vl);
+        pos += vl > 0 ? (uint64_t)vl : 0;
+    }
+    return pos == end;
+}
+
 KTA_PL_HD uint32_t payload_hist_bin(uint64_t headers) { return headers < kPlHistBins - 1u ? (uint32_t)headers : kPlHistBins - 1u; }
 
 // ---- what one record adds (host form; the kernel adds the same words from registers) ------------------------------------
@@ -163,9 +183,9 @@ inline void payload_add(uint64_t *vec, uint32_t P, uint32_t partition, long long
 // The records of one batch's payload [pos, end) of `bytes` (uncompressed, or inflated), n_records of them, as the decode
 // walks them: length varint | attributes | timestampDelta | offsetDelta | keyLength | key | valueLength | value | headers.
 // The walk stops at the first record whose framing fails; the records in front of it count.  passes(ts_delta): the filter.
-template <class Passes>
-inline void payload_batch_host(uint64_t *vec, uint32_t P, uint32_t partition, const uint8_t *bytes, uint64_t pos, uint64_t end, uint64_t n_records,
-                               Passes passes)
+// record(val_len, value position, position behind the value, the record's end) for every record that counts.
+template <class Passes, class OnRecord>
+inline void payload_records_host(const uint8_t *bytes, uint64_t pos, uint64_t end, uint64_t n_records, Passes passes, OnRecord record)
 {
     PayloadBytes src{bytes};
     for (uint64_t r = 0; r < n_records; r++) {
@@ -182,9 +202,19 @@ inline void payload_batch_host(uint64_t *vec, uint32_t P, uint32_t partition, co
         if (pos >= rec_end || !payload_varlong(src, pos, rec_end, val_len)) return;
         if (val_len < -1 || (val_len > 0 && (uint64_t)val_len > rec_end - pos)) return;
         const uint64_t value = pos, after = pos + (val_len > 0 ? (uint64_t)val_len : 0);
-        if (passes(ts_delta)) payload_add(vec, P, partition, val_len, bytes + value, payload_walk_headers(src, after, rec_end), rec_end - after);
+        if (passes(ts_delta)) record(val_len, value, after, rec_end);
         pos = rec_end;
     }
+}
+
+template <class Passes>
+inline void payload_batch_host(uint64_t *vec, uint32_t P, uint32_t partition, const uint8_t *bytes, uint64_t pos, uint64_t end, uint64_t n_records,
+                               Passes passes)
+{
+    PayloadBytes src{bytes};
+    payload_records_host(bytes, pos, end, n_records, passes, [&](long long val_len, uint64_t value, uint64_t after, uint64_t rec_end) {
+        payload_add(vec, P, partition, val_len, bytes + value, payload_walk_headers(src, after, rec_end), rec_end - after);
+    });
 }
 
 // ---- the identities between the words of one vector --------------------------------------------------------------------
@@ -233,43 +263,54 @@ struct PayloadSchemaId {
     uint64_t records, bytes;
 };
 
-inline bool payload_cell_pure(const uint64_t *cell, uint32_t row, uint32_t index, uint32_t &id)
+// (bits: the cell's 32 bit counters; the words in front of them are sums that a key adds to, word 0 its T)
+inline bool payload_cell_pure(const uint64_t *cell, uint32_t row, uint32_t index, uint32_t &id, uint32_t bits = kPlCellBits)
 {
     const uint64_t t = cell[kPlCellT];
     if (t == 0) return false;
     id = 0;
     for (uint32_t k = 0; k < 32; k++) {
-        const uint64_t c = cell[kPlCellBits + k];
+        const uint64_t c = cell[bits + k];
         if (c != 0 && c != t) return false;
         if (c) id |= 1u << k;
     }
     return payload_cell(row, id) == index;
 }
 
-// Sorted by records (most first), then bytes, then id.
-inline std::vector<PayloadSchemaId> payload_schema_ids(const uint64_t *vec, uint32_t P, uint64_t *unresolved_records, uint64_t *unresolved_bytes)
+// The peel of a two-row table t[kPlRows][kPlCells][CW] (T, CW - 33 further sums, 32 bit counters) in place: found(id, cell) for
+// every recovered id, with the cell that spelled it, before the id is subtracted from both rows.  also_pure(cell): what a
+// table asks of a pure cell beyond the above.  What remains in the rows is what could not be told apart.
+template <uint32_t CW, class AlsoPure, class Found>
+inline void payload_peel(uint64_t *t, AlsoPure also_pure, Found found)
 {
-    std::vector<uint64_t> t(vec + payload_table_at(P), vec + payload_table_at(P) + kPlTableWords);
-    auto cell_of = [&](uint32_t row, uint32_t c) { return t.data() + ((size_t)row * kPlCells + c) * kPlCellWords; };
-    std::vector<PayloadSchemaId> out;
+    auto cell_of = [&](uint32_t row, uint32_t c) { return t + ((size_t)row * kPlCells + c) * CW; };
     for (bool changed = true; changed;) {
         changed = false;
         for (uint32_t row = 0; row < kPlRows; row++)
             for (uint32_t c = 0; c < kPlCells; c++) {
                 uint64_t *cell = cell_of(row, c);
                 uint32_t id;
-                if (!payload_cell_pure(cell, row, c, id)) continue;
+                if (!payload_cell_pure(cell, row, c, id, CW - 32u) || !also_pure(cell)) continue;
                 uint64_t *other = cell_of(1u - row, payload_cell(1u - row, id));
-                bool fits = other[kPlCellT] >= cell[kPlCellT] && other[kPlCellB] >= cell[kPlCellB];   // (always, in a vector the rule wrote)
-                for (uint32_t k = 0; k < 32 && fits; k++) fits = other[kPlCellBits + k] >= cell[kPlCellBits + k];
+                bool fits = true;                                               // (always, in a vector the rule wrote)
+                for (uint32_t k = 0; k < CW && fits; k++) fits = other[k] >= cell[k];
                 if (!fits) continue;
-                out.push_back(PayloadSchemaId{id, cell[kPlCellT], cell[kPlCellB]});
-                for (uint32_t k = 0; k < kPlCellWords; k++) other[k] -= cell[k], cell[k] = 0;
+                found(id, (const uint64_t *)cell);
+                for (uint32_t k = 0; k < CW; k++) other[k] -= cell[k], cell[k] = 0;
                 changed = true;
             }
     }
+}
+
+// Sorted by records (most first), then bytes, then id.
+inline std::vector<PayloadSchemaId> payload_schema_ids(const uint64_t *vec, uint32_t P, uint64_t *unresolved_records, uint64_t *unresolved_bytes)
+{
+    std::vector<uint64_t> t(vec + payload_table_at(P), vec + payload_table_at(P) + kPlTableWords);
+    std::vector<PayloadSchemaId> out;
+    payload_peel<kPlCellWords>(t.data(), [](const uint64_t *) { return true; },
+                               [&](uint32_t id, const uint64_t *cell) { out.push_back(PayloadSchemaId{id, cell[kPlCellT], cell[kPlCellB]}); });
     uint64_t ur = 0, ub = 0;
-    for (uint32_t c = 0; c < kPlCells; c++) ur += cell_of(0, c)[kPlCellT], ub += cell_of(0, c)[kPlCellB];
+    for (uint32_t c = 0; c < kPlCells; c++) ur += t[(size_t)c * kPlCellWords + kPlCellT], ub += t[(size_t)c * kPlCellWords + kPlCellB];
     if (unresolved_records) *unresolved_records = ur;
     if (unresolved_bytes) *unresolved_bytes = ub;
     std::sort(out.begin(), out.end(), [](const PayloadSchemaId &a, const PayloadSchemaId &b) {

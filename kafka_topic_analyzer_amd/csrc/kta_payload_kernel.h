@@ -1,5 +1,5 @@
 // kta_payload_kernel.h — the payload section's kernel (kta_payload, KTA_FLAG_PAYLOAD).  kta_payload.hip includes this file
-// INSIDE its unnamed namespace, behind kta_decode_coop.h (pin, load_block, KTA_READLANE); it has no includes of its own: the
+// INSIDE its unnamed namespace, behind kta_decode_coop.h (pin, load_block, KTA_READLANE); beside kta_wave_src.h it has no includes of its own: the
 // including file has included kta_filter.h, kta_kafka.h, kta_payload.h and kta_records.h (at file scope) and provides the
 // HIP runtime — or, for the CPU suite, tests/native/wave_emu.h, which runs the 64 lanes of a workgroup as fibers that meet at
 // __syncthreads / __any / __shfl_xor / ballots (tests/native/payload_emu.cpp, tests/test_payload_emu.py): the kernel below is
@@ -13,6 +13,8 @@
 #define KTA_UNI(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))
 #endif
 
+#include "kta_wave_src.h"       // BlockSrc, WindowSrc, group_sum, wave_sum (shared with kta_header_names_kernel.h)
+
 constexpr int kPlG = 4;                         // batches per wave
 constexpr uint32_t kPlW = 3072;                 // window bytes
 constexpr uint32_t kPlR = 16;                   // records per round of a group
@@ -21,46 +23,8 @@ constexpr uint32_t kPlNLoad = kPlW / (kPlL * 16);
 constexpr uint32_t kPlPer = kPlW / 1024;
 constexpr uint32_t kPlWavesPerCu = 12;           // resident workgroups per CU (the launch's grid is that many per CU at most)
 constexpr uint32_t kPlIdSlots = 16;             // the workgroup's cache of schema ids: (id, T, B) per slot, in LDS
-static_assert(kPlR == kPlL && kPlL == kPlHistBins && kta::rec::line_windows(kPlW), "one parse round; a lane per histogram bin; KiB loads");
+static_assert(kPlR == kPlL && kPlL == kWsL && kPlL == kPlHistBins && kta::rec::line_windows(kPlW), "one parse round; a lane per histogram bin; KiB loads");
 static_assert(kPlPartitionSums <= 64 && kPlCellWords <= 64, "a lane per word in the flushes");
-
-// A byte source over the blob: aligned 16-byte loads, one block cached (payload_walk_headers' Src).
-struct BlockSrc {
-    const uint4 *blocks;
-    uint64_t cached_idx;
-    uint4 cached;
-    __device__ __forceinline__ uint32_t at(uint64_t pos)
-    {
-        const uint64_t bi = pos >> 4;
-        if (bi != cached_idx) {
-            cached = blocks[bi];
-            cached_idx = bi;
-        }
-        const uint32_t w = (uint32_t)(pos >> 2) & 3u;
-        const uint32_t word = w == 0 ? cached.x : (w == 1 ? cached.y : (w == 2 ? cached.z : cached.w));
-        return (word >> ((uint32_t)(pos & 3u) * 8u)) & 0xFFu;
-    }
-};
-
-// The same over the window in LDS, for a record that lies inside it.
-struct WindowSrc {
-    const uint8_t *win;
-    uint64_t wbase;
-    __device__ __forceinline__ uint32_t at(uint64_t pos) const { return win[(uint32_t)(pos - wbase)]; }
-};
-
-__device__ __forceinline__ uint64_t group_sum(uint64_t v)   // over the kPlL lanes of a group (aligned, a power of two)
-{
-#pragma unroll
-    for (int m = (int)kPlL / 2; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
-    return v;
-}
 
 // What a lane has accumulated for the batches of ONE partition (acc_part; -1: nothing yet) since its last flush.
 struct PayloadAcc {

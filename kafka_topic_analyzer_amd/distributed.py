@@ -131,6 +131,14 @@ def allreduce_payload_vector(lvec, n_partitions: int, group=None) -> None:
     _allreduce_sum_max(lvec, lvec.numel(), group)
 
 
+def allreduce_header_names_vector(nvec, group=None) -> None:
+    """In-place exchange of an int64 view of the header-name SNAPSHOT (kta_header_names_result_vector: device tensor, or a CPU
+    tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_HEADER_NAMES: one all-reduce SUM over
+    all 8 + 2 * 1024 * 36 words (i64 wrap == u64 wrap).  The name tables stay on their ranks."""
+    assert nvec.numel() == 8 + 2 * 1024 * 36
+    _allreduce_sum_max(nvec, nvec.numel(), group)
+
+
 def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
     """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
     tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM
