@@ -466,6 +466,43 @@ typedef struct kta_header_name_row {
     uint8_t name[KTA_HEADER_NAME_BYTES];
 } kta_header_name_row;
 
+/* Value bytes (NOT in the reference): a histogram of the bytes of the VALUES of the records that the raw-log decode delivers
+ * (kta_kafka.h: kta_kafka_decode_device, and through it kta_kafka_blob_submit and kta_kafka_consume), per partition: would the
+ * topic compress, is it text or binary, zero-padded, or compressed or encrypted by its producer already?  Opt-in at
+ * kta_create, independent of every other flag.  Every word is exact and a SUM.  csrc/kta_value_bytes.h is the code of
+ * everything below.
+ * A record COUNTS under the payload section's rule (above KTA_FLAG_PAYLOAD: status 0, framing, partition in [0, P), the
+ * filter with LogAppendTime handled alike).  During a compaction replay the pass is skipped; failed batches add nothing;
+ * compressed batches are read in their inflated form: the section describes the uncompressed values.
+ * Every byte b at position i of a counted record's value (val_len > 0) adds 1 to bin b of its partition, and 1 to `repeats`
+ * when i > 0 and it equals the byte at i - 1 of the same value — never the byte in front of the value: not the length varint,
+ * not the key, not the record before it.
+ * The vector is u64[KTA_VALUE_BYTES_WORDS(P)], 264 words per partition: words 0 .. 255 the bins, 256 records (counted), 257
+ * values (those with val_len > 0), 258 bytes, 259 repeats, 260 .. 263 zero.  There are no P-independent words and no cap on P
+ * beyond what the vector costs.
+ * kta_value_bytes_summary reads one partition's words, or their sum over the topic, off: H0, the order-0 floor, the shares
+ * and a class.  The class is a HEURISTIC, the first that holds: none (no bytes), text (printable >= 95 % of the bytes), dense
+ * (at least 65 536 bytes and H0 >= 7.5 bits: compressed, encrypted or random already), binary.
+ * kta_value_bytes_identities states the identities.  With the flag off no kernel is launched and nothing is allocated. */
+#define KTA_FLAG_VALUE_BYTES 0x1000U     /* 4096: bit 12 */
+#define KTA_VALUE_BYTES_BINS 256
+#define KTA_VALUE_BYTES_PARTITION_WORDS 264
+#define KTA_VALUE_BYTES_WORDS(P) (264u * (size_t)(P))
+#define KTA_VALUE_BYTES_NONE 0u
+#define KTA_VALUE_BYTES_TEXT 1u
+#define KTA_VALUE_BYTES_DENSE 2u
+#define KTA_VALUE_BYTES_BINARY 3u
+/* What kta_value_bytes_summary reads off 264 words.  entropy_bits: H0 = - sum (c / B) log2(c / B) over the non-zero bins in
+ * ascending byte order, in double; 0 when B = 0.  floor_bytes: ceil(B H0 / 8), what an order-0 entropy coder alone could not
+ * go below.  printable: bins 0x20 .. 0x7E plus \t \n \r.  zero: bin 0.  high: bins >= 0x80.  top_byte / top_count: the most
+ * common byte (the lowest on a tie) and its count.  cls: KTA_VALUE_BYTES_NONE .. KTA_VALUE_BYTES_BINARY. */
+typedef struct kta_value_bytes_summary_t {
+    uint64_t records, values, bytes, repeats;
+    uint64_t distinct, floor_bytes, printable, zero, high, top_count;
+    double entropy_bits;
+    uint32_t top_byte, cls;
+} kta_value_bytes_summary_t;
+
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
  * both hold:
@@ -1172,6 +1209,30 @@ int kta_header_names_list(const uint64_t *vec, const kta_header_name *table, kta
  * not NULL, to table[KTA_HEADER_NAMES_SLOTS] (first writer wins).  A partition outside [0, P) adds nothing.  No filter. */
 int kta_header_names_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, kta_header_name *table, uint32_t n_partitions);
 
+/* Value bytes (context created with KTA_FLAG_VALUE_BYTES; definition above KTA_FLAG_VALUE_BYTES).  kta_reset zeroes the
+ * vector; kta_finish_device snapshots it; kta_exchange reduces the snapshot (all SUM).  Every call below that takes a context
+ * fails on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_VALUE_BYTES.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_VALUE_BYTES_WORDS(P); staged messages are flushed first). */
+int kta_get_value_bytes(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes: after kta_exchange the whole job's vector on every rank. */
+int kta_exchange_value_bytes(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot (what collectives reduce in place), and of the live vector. */
+int kta_value_bytes_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+int kta_value_bytes_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[KTA_VALUE_BYTES_WORDS(P)]: acc <- acc + other. */
+int kta_merge_value_bytes(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* 1 when the identities between the words of one vector hold, 0 when not (host only), per partition: the bins sum to bytes;
+ * repeats <= bytes - values; values <= records; words 260 .. 263 are zero.  payload_vec: NULL, or the payload vector
+ * u64[KTA_PAYLOAD_WORDS(P)] of the same run: records equal the payload's records, bytes the sum of its five class-byte words,
+ * values its framed + json + other.  counter_vec: NULL, or the counter vector of the same unfiltered run without failed
+ * batches, as kta_payload_identities takes it: records equal the total messages. */
+int kta_value_bytes_identities(const uint64_t *vec, uint32_t n_partitions, const uint64_t *payload_vec, const uint64_t *counter_vec);
+/* The read-off of words[KTA_VALUE_BYTES_PARTITION_WORDS]: one partition's words, or their sum over the topic (host only). */
+int kta_value_bytes_summary(const uint64_t *words, kta_value_bytes_summary_t *out);
+/* The same rule on the host, for tests and the CPU suite, as kta_payload_host: added to vec[KTA_VALUE_BYTES_WORDS(P)].  A
+ * partition outside [0, P) adds nothing.  No filter. */
+int kta_value_bytes_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t n_partitions);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1471,6 +1532,16 @@ int kta_render_payload(const uint64_t *vec, const uint64_t *counter_vec, uint32_
  *   a line for the unresolved remainder when there is one; a closing `=` rule.
  * A figure whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
 int kta_render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names, char *out, size_t out_cap, size_t *out_len);
+/* The opt-in value-byte section that kta-analyzer prints behind the header-name section's position with --librdkafka
+ * kta.value_bytes=1, from a value-byte vector (host only):
+ *   a title line that names the knob and says that it is not part of the reference report;
+ *   a table (P | Records | Values | Value bytes | H0 bits/byte | Order-0 floor % | Printable % | Zero % | High-bit % |
+ *    Repeat % | Distinct | Top byte | Class), a row per partition and a `Topic` row of their sum: H0 with two decimals; the
+ *    floor and the shares as percentages of the value bytes with two decimals; Top byte as 0xHH and its share;
+ *   a note: the class is a heuristic; H0 bounds an order-0 entropy coder alone — LZ matching, most of what gzip, LZ4 or
+ *    zstd win on JSON, is not in it; and a closing `=` rule.
+ * A share whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
+int kta_render_value_bytes(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
 int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
                       uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 

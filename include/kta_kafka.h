@@ -37,7 +37,8 @@
  * transactional producers, leader epochs, offset holes — is accumulated on the device by the opt-in record-batch section
  * (KTA_FLAG_RECORD_BATCHES, kta_hip.h), from the descriptors and the headers of every decode call; what lies inside the
  * records — value formats, schema-registry ids, record headers — by the opt-in payload section (KTA_FLAG_PAYLOAD); which
- * header names those are by the opt-in header-name section (KTA_FLAG_HEADER_NAMES).
+ * header names those are by the opt-in header-name section (KTA_FLAG_HEADER_NAMES); what bytes the values are made of — a
+ * histogram per partition, behind the payload and header-name passes — by the opt-in value-byte section (KTA_FLAG_VALUE_BYTES).
  */
 #ifndef KTA_KAFKA_H
 #define KTA_KAFKA_H
@@ -224,6 +225,12 @@ int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
  * table (the spill path), out[5] cache slots claimed, out[6] cache flushes in front of a workgroup's end; out[7] zero.
  * *avg_ms as there.  Waits for the compute stream. */
 int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms);
+
+/* The value-byte pass (KTA_FLAG_VALUE_BYTES, kta_hip.h): out[0] launches, out[1] batches, out[2] the workgroups of the last
+ * launch, since the context was created; out[3] the flushes of a workgroup's LDS bins in the middle of a pass because a
+ * 32-bit bin could overflow, since creation / kta_reset.  *avg_ms (may be NULL): the pass kernel's mean duration over the
+ * timed launches, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute stream. */
+int kta_value_bytes_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,8 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "record_batches_identities", "record_batches_host", "RECORD_BATCH_COLUMNS", "RECORD_BATCH_CODECS", "split_payload", "merge_payload",
            "payload_identities", "payload_schema_ids", "payload_host", "render_payload", "PAYLOAD_COLUMNS", "PAYLOAD_CLASSES",
            "split_header_names", "merge_header_names", "header_names_identities", "header_names_list", "header_names_host",
-           "render_header_names", "HEADER_NAME_DTYPE", "HEADER_NAMES_GLOBALS"]
+           "render_header_names", "HEADER_NAME_DTYPE", "HEADER_NAMES_GLOBALS", "split_value_bytes", "merge_value_bytes",
+           "value_bytes_identities", "value_bytes_summary", "value_bytes_host", "render_value_bytes", "VALUE_BYTES_CLASSES"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -95,6 +96,7 @@ _SECTIONS = {
     "record_batches": (lambda P: 20 * P + 1524, "a record-batch vector of {} partitions"),
     "payload": (lambda P: 24 * P + 16 + 2 * 1024 * 34, "a payload vector of {} partitions"),
     "header_names": (lambda: N.KTA_HEADER_NAMES_WORDS, "a header-name vector"),
+    "value_bytes": (lambda P: N.KTA_VALUE_BYTES_PARTITION_WORDS * P, "a value-byte vector of {} partitions"),
     "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
     "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
 }
@@ -145,7 +147,8 @@ class HipMetricHandler:
                  seq_column: bool = False, timeline: Optional[Tuple[int, int, int]] = None, key_sketch: bool = False,
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
                  compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
-                 compact_delete: bool = False, record_batches: bool = False, payload: bool = False, header_names: bool = False):
+                 compact_delete: bool = False, record_batches: bool = False, payload: bool = False, header_names: bool = False,
+                 value_bytes: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -168,7 +171,9 @@ class HipMetricHandler:
         payload: the payload section (KTA_FLAG_PAYLOAD: value formats, schema-registry ids and record headers of the records of
         the raw-log decode, get_payload());
         header_names: the header-name section (KTA_FLAG_HEADER_NAMES: a census of the names of the record headers of the raw-log
-        decode, header_names() and header_name_table())."""
+        decode, header_names() and header_name_table());
+        value_bytes: the value-byte section (KTA_FLAG_VALUE_BYTES: a byte histogram of the values of the records of the raw-log
+        decode per partition, value_bytes())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -181,13 +186,14 @@ class HipMetricHandler:
         self.record_batches_on = bool(record_batches)
         self.payload_on = bool(payload)
         self.header_names_on = bool(header_names)
+        self.value_bytes_on = bool(value_bytes)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
                         (N.KTA_FLAG_TS_ORDER if ts_order else 0) | (N.KTA_FLAG_PARTITIONER if partitioner else 0) |
                         (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
                         (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) | (N.KTA_FLAG_PAYLOAD if payload else 0) |
-                        (N.KTA_FLAG_HEADER_NAMES if header_names else 0) |
+                        (N.KTA_FLAG_HEADER_NAMES if header_names else 0) | (N.KTA_FLAG_VALUE_BYTES if value_bytes else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -801,6 +807,31 @@ class HipMetricHandler:
         return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]), "spills": int(out[4]),
                 "claims": int(out[5]), "cache_flushes": int(out[6]), "kernel_ms": float(ms.value) if out[3] else None}
 
+    def value_bytes(self) -> dict:
+        """The live value-byte vector as split_value_bytes gives it: the vector, the partitions' words and the summaries per
+        partition and of the topic (kta_get_value_bytes; staged messages are flushed first)."""
+        return split_value_bytes(self._read_section("value_bytes", self._lib.kta_get_value_bytes), self.n_partitions)
+
+    def exchange_value_bytes(self) -> dict:
+        """As value_bytes(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return split_value_bytes(self._read_section("value_bytes", self._lib.kta_exchange_value_bytes), self.n_partitions)
+
+    def value_bytes_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the value-byte snapshot (for collectives: allreduce_value_bytes_vector)."""
+        return self._device_vector(self._lib.kta_value_bytes_result_vector)
+
+    def value_bytes_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live value-byte vector."""
+        return self._device_vector(self._lib.kta_value_bytes_vector)
+
+    def value_bytes_info(self) -> dict:
+        """The value-byte pass's work (kta_value_bytes_info): launches, batches and workgroups since creation; mid_flushes, the
+        flushes of a workgroup's bins in the middle of a pass, since creation / reset(); kernel_ms as payload_info's."""
+        out, ms = (C.c_uint64 * 4)(), C.c_float()
+        self._check(self._lib.kta_value_bytes_info(self._ctx, C.byref(out), C.byref(ms)))
+        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "mid_flushes": int(out[3]),
+                "kernel_ms": float(ms.value) if ms.value >= 0 else None}
+
     def size_quantiles_info(self) -> dict:
         """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""
         out = (C.c_uint64 * 6)()
@@ -1392,6 +1423,67 @@ def render_header_names(vec, table=None, max_names: int = 256) -> str:
     """kta_render_header_names: the section kta-analyzer prints with --librdkafka kta.headers=1."""
     t = _name_table(table)
     return _render(N.load().kta_render_header_names, _np_ptr(_section_vec("header_names", vec)), None if t is None else _np_ptr(t), int(max_names))
+
+
+VALUE_BYTES_CLASSES = ("none", "text", "dense", "binary")
+
+
+def value_bytes_summary(words) -> dict:
+    """kta_value_bytes_summary: the read-off of one partition's 264 words of a value-byte vector, or of their sum over the
+    topic: records, values, bytes, repeats, distinct, entropy_bits (H0), floor_bytes, printable, zero, high, top_byte,
+    top_count and class (a heuristic: one of VALUE_BYTES_CLASSES)."""
+    w = _u64_vec(words, N.KTA_VALUE_BYTES_PARTITION_WORDS, "the words of one partition of a value-byte vector")
+    out = N.KtaValueBytesSummary()
+    rc = N.load().kta_value_bytes_summary(_np_ptr(w), C.byref(out))
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_value_bytes_summary")
+    d = {name: getattr(out, name) for name, _ in N.KtaValueBytesSummary._fields_ if name != "cls"}
+    d["class"] = VALUE_BYTES_CLASSES[out.cls]
+    return d
+
+
+def split_value_bytes(vec, n_partitions: int) -> dict:
+    """A value-byte vector u64[264 P] as a dict, split by its layout (kta_hip.h, above KTA_FLAG_VALUE_BYTES): "partitions"
+    [P][264] (256 bins, records, values, bytes, repeats, four zeros); "summaries" [P] and "topic" what value_bytes_summary reads
+    off each partition and off their sum; the vector under "vector"."""
+    P = n_partitions
+    v = _section_vec("value_bytes", vec, P)
+    parts = v.reshape(P, N.KTA_VALUE_BYTES_PARTITION_WORDS).copy()
+    return {"partitions": parts, "summaries": [value_bytes_summary(parts[p]) for p in range(P)],
+            "topic": value_bytes_summary(parts.sum(axis=0, dtype=np.uint64)), "vector": v}
+
+
+def merge_value_bytes(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_value_bytes, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    return _merge("value_bytes", acc, other, n_partitions)
+
+
+def value_bytes_identities(vec, n_partitions: int, payload_vec=None, counter_vec=None) -> bool:
+    """kta_value_bytes_identities: whether the identities between the words of one value-byte vector hold; with payload_vec
+    (the payload vector of the same run) also those between the two sections; with counter_vec (the counter vector
+    u64[7 P + 8] of the same unfiltered run without failed batches) also records == total_messages per partition."""
+    p = None if payload_vec is None else _section_vec("payload", payload_vec, n_partitions)
+    c = None if counter_vec is None else _counter_vec(counter_vec, n_partitions)
+    rc = N.load().kta_value_bytes_identities(_np_ptr(_section_vec("value_bytes", vec, n_partitions)), n_partitions,
+                                             None if p is None else _np_ptr(p), None if c is None else _np_ptr(c))
+    if rc < 0:
+        raise KtaError(rc, "kta_value_bytes_identities")
+    return rc == 1
+
+
+def value_bytes_host(blob: bytes, partition: int, n_partitions: int, vec=None) -> np.ndarray:
+    """kta_value_bytes_host: the section's rule over the records of `blob` on the host (compressed batches inflated), added to
+    `vec` (a new vector when None)."""
+    v = np.zeros(_section_words("value_bytes", n_partitions), np.uint64) if vec is None else _section_vec("value_bytes", vec, n_partitions)
+    rc = N.load().kta_value_bytes_host(bytes(blob), len(blob), int(partition), _np_ptr(v), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_value_bytes_host")
+    return v
+
+
+def render_value_bytes(vec, n_partitions: int) -> str:
+    """kta_render_value_bytes: the section kta-analyzer prints with --librdkafka kta.value_bytes=1."""
+    return _render(N.load().kta_render_value_bytes, _np_ptr(_section_vec("value_bytes", vec, n_partitions)), n_partitions)
 
 
 def size_bin(size: int) -> int:

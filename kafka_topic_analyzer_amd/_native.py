@@ -73,6 +73,10 @@ KTA_PAYLOAD_PARTITION_WORDS, KTA_PAYLOAD_CLASSES, KTA_PAYLOAD_HIST_BINS, KTA_PAY
 KTA_FLAG_HEADER_NAMES = 2048
 KTA_HEADER_NAMES_GLOBALS, KTA_HEADER_NAMES_ROWS, KTA_HEADER_NAMES_CELLS, KTA_HEADER_NAMES_CELL_WORDS = 8, 2, 1024, 36
 KTA_HEADER_NAMES_WORDS, KTA_HEADER_NAMES_SLOTS, KTA_HEADER_NAME_BYTES, KTA_HEADER_NAME_PUBLISHED = 8 + 2 * 1024 * 36, 2 * 1024, 48, 2
+# value-byte vector: u64[264 P] = [P][264: 256 bins, records, values, bytes, repeats, 4 zero words]
+KTA_FLAG_VALUE_BYTES = 4096
+KTA_VALUE_BYTES_BINS, KTA_VALUE_BYTES_PARTITION_WORDS = 256, 264
+KTA_VALUE_BYTES_NONE, KTA_VALUE_BYTES_TEXT, KTA_VALUE_BYTES_DENSE, KTA_VALUE_BYTES_BINARY = 0, 1, 2, 3
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -93,6 +97,12 @@ class KtaHeaderName(C.Structure):
 class KtaHeaderNameRow(C.Structure):
     _fields_ = [("hash", C.c_uint32), ("has_name", C.c_uint32), ("occurrences", C.c_uint64), ("name_len", C.c_uint64),
                 ("value_bytes", C.c_uint64), ("null_values", C.c_uint64), ("name", C.c_uint8 * KTA_HEADER_NAME_BYTES)]
+
+
+class KtaValueBytesSummary(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("values", C.c_uint64), ("bytes", C.c_uint64), ("repeats", C.c_uint64), ("distinct", C.c_uint64),
+                ("floor_bytes", C.c_uint64), ("printable", C.c_uint64), ("zero", C.c_uint64), ("high", C.c_uint64), ("top_count", C.c_uint64),
+                ("entropy_bits", C.c_double), ("top_byte", C.c_uint32), ("cls", C.c_uint32)]
 
 
 class KtaHotKey(C.Structure):
@@ -290,6 +300,16 @@ SIGNATURES = {
     "kta_header_names_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "kta_header_names_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 8), C.POINTER(C.c_float)]),
     "kta_render_header_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_get_value_bytes": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_value_bytes": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_value_bytes_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_value_bytes_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_value_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_value_bytes_identities": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "kta_value_bytes_summary": (C.c_int, [C.c_void_p, C.POINTER(KtaValueBytesSummary)]),
+    "kta_value_bytes_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint32]),
+    "kta_value_bytes_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
+    "kta_render_value_bytes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_set_segments": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kta_segments_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),

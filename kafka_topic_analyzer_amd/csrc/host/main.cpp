@@ -52,6 +52,9 @@
 // kta.headers=1 (0: off; the same sources and refusals as kta.payload=1, with or without it) runs the header-name pass as well
 // (KTA_FLAG_HEADER_NAMES) and prints its section behind the payload section's position: the names of the record headers with
 // their occurrences, bytes and null values.  Under kta.gpus=N a listed name comes from the lowest rank that holds it.
+// kta.value_bytes=1 (0: off; the same sources and refusals as kta.payload=1, with or without it) runs the value-byte pass as well
+// (KTA_FLAG_VALUE_BYTES) and prints its section behind the header-name section's position: per partition and for the topic a
+// byte histogram's read-off — H0, the order-0 floor, the printable, zero, high-bit and repeat shares and a class.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -371,6 +374,7 @@ struct ShardedJob {
     uint64_t rb_skipped[3] = {0, 0, 0};                //   control batches, magic 0/1 sets, unknown codecs: the host index's, whole topic
     bool payload = false;                              // kta.payload=1: likewise (segment:// only)
     bool headers = false;                              // kta.headers=1: likewise (segment:// only); the name tables stay on their ranks
+    bool value_bytes = false;                          // kta.value_bytes=1: likewise (segment:// only)
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
@@ -390,7 +394,7 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) |
                                (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) | (job.payload ? KTA_FLAG_PAYLOAD : 0u) |
-                               (job.headers ? KTA_FLAG_HEADER_NAMES : 0u);
+                               (job.headers ? KTA_FLAG_HEADER_NAMES : 0u) | (job.value_bytes ? KTA_FLAG_VALUE_BYTES : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -585,6 +589,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             }
             text += kta::render_header_names(h0->header_names()->data(), merged.data(), kHeaderNamesShown);
         }
+        if (job.value_bytes) text += kta::render_value_bytes(h0->value_bytes()->data(), job.P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -662,6 +667,21 @@ int main(int argc, char **argv)
         headers = v == "1";
         if (headers && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
             fprintf(stderr, "kta.headers=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
+                            "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
+            return 2;
+        }
+    }
+    // kta.value_bytes: likewise
+    bool value_bytes = false;
+    if (cfg.count("kta.value_bytes")) {
+        const std::string &v = cfg["kta.value_bytes"];
+        if (v != "0" && v != "1") {
+            fprintf(stderr, "kta.value_bytes=%s: expected 0 or 1\n", v.c_str());
+            return 2;
+        }
+        value_bytes = v == "1";
+        if (value_bytes && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
+            fprintf(stderr, "kta.value_bytes=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
                             "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
             return 2;
         }
@@ -1058,6 +1078,7 @@ int main(int argc, char **argv)
         job.record_batches = record_batches;
         job.payload = payload;
         job.headers = headers;
+        job.value_bytes = value_bytes;
         std::copy(rb_skipped, rb_skipped + 3, job.rb_skipped);
         job.filter = filter;
         job.segments = segments;
@@ -1081,7 +1102,8 @@ int main(int argc, char **argv)
                                                 (hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                                 (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
                                                 (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) |
-                                                (payload ? KTA_FLAG_PAYLOAD : 0u) | (headers ? KTA_FLAG_HEADER_NAMES : 0u),
+                                                (payload ? KTA_FLAG_PAYLOAD : 0u) | (headers ? KTA_FLAG_HEADER_NAMES : 0u) |
+                                                (value_bytes ? KTA_FLAG_VALUE_BYTES : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1332,6 +1354,7 @@ int main(int argc, char **argv)
         if (record_batches) text += kta::render_record_batches(handler->record_batches()->data(), P, filter.on, rb_skipped);
         if (payload) text += kta::render_payload(handler->payload()->data(), partitioner_counters(metrics, P).data(), P);
         if (headers) text += kta::render_header_names(handler->header_names()->data(), handler->header_name_table()->data(), kHeaderNamesShown);
+        if (value_bytes) text += kta::render_value_bytes(handler->value_bytes()->data(), P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

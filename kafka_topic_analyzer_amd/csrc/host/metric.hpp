@@ -157,6 +157,8 @@ public:
     // nullptr without the flag.
     const std::vector<uint64_t> *header_names() const { return hn_on_ ? &nvec_ : nullptr; }
     const std::vector<kta_header_name> *header_name_table() const { return hn_on_ ? &ntab_ : nullptr; }
+    // With KTA_FLAG_VALUE_BYTES: the value-byte vector u64[264 P] of that snapshot; nullptr without the flag.
+    const std::vector<uint64_t> *value_bytes() const { return vb_on_ ? &yvec_ : nullptr; }
     // The segment pass of the retention what-if (kta_set_segments): right after construction, before any record; then the
     // segment vector u64[(P M + P) 4 + 8] of the snapshot finish() / exchange() took (after exchange(), the whole job's);
     // nullptr without it.
@@ -208,6 +210,8 @@ private:
     bool hn_on_ = false;
     std::vector<uint64_t> nvec_;
     std::vector<kta_header_name> ntab_;
+    bool vb_on_ = false;
+    std::vector<uint64_t> yvec_;
     uint32_t seg_rows_ = 0;   // M; 0: no segments
     std::vector<uint64_t> gvec_;
 };
@@ -248,6 +252,8 @@ std::string render_record_batches(const uint64_t *vec, uint32_t P, bool filtered
 std::string render_payload(const uint64_t *vec, const uint64_t *counters, uint32_t P);
 // (kta_render_header_names): vec u64[73736]; table: a name table [2 * 1024] or nullptr; at most max_names rows
 std::string render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names);
+// (kta_render_value_bytes): vec u64[264 P]
+std::string render_value_bytes(const uint64_t *vec, uint32_t P);
 // the opt-in section kta-analyzer prints with kta.segments=<size> after the partitioner and compaction sections and before
 // the filter's (kta_render_retention): vec u64[(P M + P) 4 + 8]; retention -1: the rule is off
 std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes);

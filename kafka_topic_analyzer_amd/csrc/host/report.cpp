@@ -14,6 +14,7 @@
 #include "kta_payload.h"
 #include "kta_record_batches.h"
 #include "kta_segments.h"
+#include "kta_value_bytes.h"
 #include "kta_size_bins.h"
 #include "metric.hpp"
 
@@ -860,7 +861,58 @@ std::string render_header_names(const uint64_t *vec, const kta_header_name *tabl
     return o;
 }
 
+// The opt-in value-byte section (kta.value_bytes=1): no reference counterpart, printed behind the header-name section's
+// position.  vec: u64[264 P] (kta_hip.h; the layout and the read-off are kta_value_bytes.h's).
+std::string render_value_bytes(const uint64_t *vec, uint32_t P)
+{
+    auto percent = [](uint64_t num, uint64_t den) -> std::string {
+        if (den == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)num * 100.0 / (double)den);
+        return buf;
+    };
+    auto row_of = [&](const std::string &name, const uint64_t *words) {
+        const ValueBytesSummary s = value_bytes_summary(words);
+        char h0[48], top[64];
+        snprintf(h0, sizeof h0, "%.2f", s.entropy_bits);
+        snprintf(top, sizeof top, "0x%02X (%s%%)", s.top_byte, percent(s.top_count, s.bytes).c_str());
+        return std::vector<std::string>{name, std::to_string(s.records), std::to_string(s.values), std::to_string(s.bytes),
+                                        s.bytes ? std::string(h0) : std::string("n/a"), percent(s.floor_bytes, s.bytes), percent(s.printable, s.bytes),
+                                        percent(s.zero, s.bytes), percent(s.high, s.bytes), percent(s.repeats, s.bytes), std::to_string(s.distinct),
+                                        s.bytes ? std::string(top) : std::string("n/a"), value_bytes_class_name(s.cls)};
+    };
+    std::string o;
+    o += "Value bytes: a byte histogram of the record values (kta.value_bytes=1; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Records", "Values", "Value bytes", "H0 bits/byte", "Order-0 floor %", "Printable %", "Zero %", "High-bit %", "Repeat %",
+                    "Distinct", "Top byte", "Class"});
+    for (uint32_t p = 0; p < P; p++) rows.push_back(row_of(std::to_string(p), vec + (size_t)kVbPartitionWords * p));
+    uint64_t topic[kVbPartitionWords];
+    value_bytes_topic(vec, P, topic);
+    rows.push_back(row_of("Topic", topic));
+    o += pretty_table(rows);
+    o += "Class is a heuristic: text = at least 95% printable bytes; dense = at least 65536 bytes and H0 >= 7.5 (compressed, encrypted or random "
+         "already); binary otherwise.\n";
+    o += "H0 is the order-0 entropy of the value bytes: it bounds an entropy coder alone.  LZ matching, which is most of what gzip, LZ4 or zstd win "
+         "on JSON, is not in it.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_value_bytes(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || n_partitions == 0) return KTA_ERR_INVALID;
+    const std::string text = kta::render_value_bytes(vec, n_partitions);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names, char *out, size_t out_cap,
                                        size_t *out_len)

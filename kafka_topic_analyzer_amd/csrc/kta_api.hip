@@ -14,6 +14,7 @@
 #include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_size_bins.h"
+#include "kta_value_bytes.h"
 
 #include <limits.h>
 #include <math.h>
@@ -146,6 +147,12 @@ struct kta_ctx {
     bool hn = false;
     DeviceBuf<uint64_t> d_hn, d_hn_out, d_hn_info;
     DeviceBuf<kta_header_name> d_hn_names;
+    // value bytes (KTA_FLAG_VALUE_BYTES): d_vb u64[264 P] the live vector that the decode call adds to (kta_internal_value_bytes),
+    // d_vb_out its snapshot, d_vb_info the pass's work counters, vb_variant the launch form (KTA_VALUE_BYTES_VARIANT: 0, or 1
+    // of tools/bench_value_bytes.py)
+    bool vb = false;
+    int vb_variant = 0;
+    DeviceBuf<uint64_t> d_vb, d_vb_out, d_vb_info;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -896,6 +903,7 @@ Shape segments_shape(uint32_t P, uint32_t M)
 Shape record_batches_shape(uint32_t P) { return Shape{kta::rb_len(P), kta::rb_sum_words(P), false}; }
 Shape payload_shape(uint32_t P) { return all_sum(kta::payload_len(P)); }
 Shape header_names_shape() { return all_sum(kta::kHnWords); }
+Shape value_bytes_shape(uint32_t P) { return all_sum(kta::value_bytes_len(P)); }
 Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
 
 // what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
@@ -927,6 +935,11 @@ static_assert(sizeof(kta_header_name) == sizeof(kta::HnSlot) && offsetof(kta_hea
                   offsetof(kta_header_name, name_len) == offsetof(kta::HnSlot, name_len) && offsetof(kta_header_name, state) == offsetof(kta::HnSlot, state) &&
                   offsetof(kta_header_name, bytes) == offsetof(kta::HnSlot, bytes) && KTA_HEADER_NAME_PUBLISHED == kta::kHnPublished,
               "a slot of the name table: kta_header_names.h and kta_hip.h");
+static_assert(KTA_VALUE_BYTES_PARTITION_WORDS == kta::kVbPartitionWords && KTA_VALUE_BYTES_BINS == kta::kVbBins && KTA_VALUE_BYTES_WORDS(7) == 264 * 7,
+              "kta_value_bytes.h and kta_hip.h");
+static_assert(KTA_VALUE_BYTES_NONE == kta::kVbNone && KTA_VALUE_BYTES_TEXT == kta::kVbText && KTA_VALUE_BYTES_DENSE == kta::kVbDense &&
+                  KTA_VALUE_BYTES_BINARY == kta::kVbBinary,
+              "the classes: kta_value_bytes.h and kta_hip.h");
 
 // One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
 // and out point at the context's owners, allocated or not.
@@ -965,6 +978,8 @@ void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
     s[KTA_RV_PAYLOAD] = Section{ctx->pl, &ctx->d_pl, &ctx->d_pl_out, payload_shape(P), true, "payload vector", "context was created without KTA_FLAG_PAYLOAD"};
     s[KTA_RV_HEADER_NAMES] = Section{ctx->hn, &ctx->d_hn, &ctx->d_hn_out, header_names_shape(), true, "header-name vector",
                                       "context was created without KTA_FLAG_HEADER_NAMES"};
+    s[KTA_RV_VALUE_BYTES] = Section{ctx->vb, &ctx->d_vb, &ctx->d_vb_out, value_bytes_shape(P), true, "value-byte vector",
+                                     "context was created without KTA_FLAG_VALUE_BYTES"};
     s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
                                     "context was created without KTA_FLAG_COMPACTION"};
     s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
@@ -1126,6 +1141,7 @@ int reset_state(kta_ctx *ctx)
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hn_names.get(), 0, kta::kHnSlots * sizeof(kta_header_name), ctx->s_compute));
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_hn_info.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));
     }
+    if (ctx->vb) KTA_HIP(ctx, hipMemsetAsync(ctx->d_vb_info.get(), 0, 4 * sizeof(uint64_t), ctx->s_compute));   // (the work counters)
     if (ctx->part) {
         KTA_HIP(ctx, hipMemsetAsync(ctx->d_part_stats.get(), 0, 3 * sizeof(uint64_t), ctx->s_compute));
         ctx->part_launches = ctx->part_workgroups = 0;
@@ -1298,6 +1314,11 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->rb = (cfg->flags & KTA_FLAG_RECORD_BATCHES) != 0;
     ctx->pl = (cfg->flags & KTA_FLAG_PAYLOAD) != 0;
     ctx->hn = (cfg->flags & KTA_FLAG_HEADER_NAMES) != 0;
+    ctx->vb = (cfg->flags & KTA_FLAG_VALUE_BYTES) != 0;
+    {
+        const char *bv = getenv("KTA_VALUE_BYTES_VARIANT");   // A/B switch of tools/bench_value_bytes.py: 1 every byte its own LDS add, 2 all pairs
+        ctx->vb_variant = bv && (bv[0] == '1' || bv[0] == '2') && !bv[1] ? bv[0] - '0' : 0;
+    }
     {
         const char *qv = getenv("KTA_SIZEQ_VARIANT");   // A/B switch of tools/bench_size_quantiles.py: 1 a launch per slice, 9 loads only
         ctx->sizeq_variant = qv && (qv[0] == '1' || qv[0] == '9') && !qv[1] ? qv[0] - '0' : 0;
@@ -1360,6 +1381,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
         KTA_TRY(ctx->d_hn_names.alloc(kta::kHnSlots));
         KTA_TRY(ctx->d_hn_info.alloc(4));
     }
+    if (ctx->vb) KTA_TRY(ctx->d_vb_info.alloc(4));
     if (ctx->comp) KTA_TRY(ctx->d_comp_stats.alloc(3));
     if (ctx->sizeq) KTA_TRY(ctx->d_sizeq_stats.alloc(kSizeqStatWords));
     if (ctx->alive) {
@@ -2485,6 +2507,47 @@ int kta_header_names_host(const uint8_t *bytes, uint64_t len, int32_t partition,
     });
 }
 
+// ---- value bytes (kta_value_bytes.h holds the rule, kta_value_bytes.hip the kernel, kta_kafka.hip the launch) --------------
+
+int kta_get_value_bytes(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_VALUE_BYTES, out, n_u64); }
+int kta_exchange_value_bytes(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_VALUE_BYTES, out, n_u64); }
+int kta_value_bytes_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_VALUE_BYTES, true, device_ptr, n_u64);
+}
+int kta_value_bytes_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64) { return section_vector(ctx, KTA_RV_VALUE_BYTES, false, device_ptr, n_u64); }
+int kta_merge_value_bytes(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    return merge_section(acc, other, P != 0, value_bytes_shape(P));
+}
+
+int kta_value_bytes_identities(const uint64_t *vec, uint32_t P, const uint64_t *payload_vec, const uint64_t *counter_vec)
+{
+    if (!vec || P == 0 || (payload_vec && P > 4096)) return KTA_ERR_INVALID;   // (a payload vector has 4096 partitions at most)
+    return kta::value_bytes_identities_hold(vec, P, payload_vec, counter_vec, KTA_NCOUNTERS) ? 1 : 0;
+}
+
+int kta_value_bytes_summary(const uint64_t *words, kta_value_bytes_summary_t *out)
+{
+    if (!words || !out) return KTA_ERR_INVALID;
+    const kta::ValueBytesSummary s = kta::value_bytes_summary(words);
+    memset(out, 0, sizeof *out);
+    out->records = s.records, out->values = s.values, out->bytes = s.bytes, out->repeats = s.repeats, out->distinct = s.distinct;
+    out->floor_bytes = s.floor_bytes, out->printable = s.printable, out->zero = s.zero, out->high = s.high, out->top_count = s.top_count;
+    out->entropy_bits = s.entropy_bits, out->top_byte = s.top_byte, out->cls = s.cls;
+    return KTA_OK;
+}
+
+int kta_value_bytes_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t P)
+{
+    if (!bytes || !vec || P == 0) return KTA_ERR_INVALID;
+    if (partition < 0 || (uint32_t)partition >= P) return KTA_OK;             // outside [0, P): adds nothing
+    auto passes = [](long long) { return true; };                               // (no context, no filter)
+    return host_batches(bytes, len, partition, [&](const uint8_t *recs, uint64_t n, uint64_t n_records) {
+        kta::value_bytes_batch_host(vec, (uint32_t)partition, recs, 0, n, n_records, passes);
+    });
+}
+
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
 
 int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
@@ -3038,6 +3101,13 @@ bool kta_internal_header_names(kta_ctx *ctx, kta_internal_hn *out)
     *out = kta_internal_hn{ctx->hn, ctx->d_hn.get(), ctx->d_hn_names.get(), ctx->d_hn_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN,
                            f ? ctx->filter_spec.to_ms : INT64_MAX, f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
     return ctx->hn && !ctx->comp_replay;
+}
+bool kta_internal_value_bytes(kta_ctx *ctx, kta_internal_vb *out)
+{
+    const bool f = ctx->filter;
+    *out = kta_internal_vb{ctx->vb, ctx->d_vb.get(), ctx->d_vb_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
+                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count, ctx->vb_variant};
+    return ctx->vb && !ctx->comp_replay;
 }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {

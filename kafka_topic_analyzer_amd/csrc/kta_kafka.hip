@@ -1173,6 +1173,9 @@ struct KafkaState {
     TimerPool<1> hn_timers{1024};   // the header-name pass (kta_header_names_info)
     uint64_t hn_launches = 0, hn_batches = 0;
     uint32_t hn_workgroups = 0;     // of the last launch
+    TimerPool<1> vb_timers{1024};   // the value-byte pass (kta_value_bytes_info)
+    uint64_t vb_launches = 0, vb_batches = 0;
+    uint32_t vb_workgroups = 0;     // of the last launch
 };
 
 void free_out(kta_batch &o)
@@ -1676,6 +1679,15 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
         if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
         st->hn_launches++, st->hn_batches += n_batches;
     }
+    // The value-byte section (KTA_FLAG_VALUE_BYTES): the same moment and the same bytes, for the bytes of every value.
+    if (kta_internal_vb vb{}; kta_internal_value_bytes(ctx, &vb)) {
+        if (timing) { int rc = st->vb_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        KTA_HIP_AS(ctx, kta::launch_value_bytes(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), vb.from_ms, vb.to_ms, vb.bitmap, vb.vec,
+                                                vb.info, vb.cu_count, vb.variant, &st->vb_workgroups, s),
+                   "kta_value_bytes");
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+        st->vb_launches++, st->vb_batches += n_batches;
+    }
     KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
         KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -1970,6 +1982,25 @@ int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms)
     out[0] = st->hn_launches, out[1] = st->hn_batches, out[2] = st->hn_workgroups, out[3] = timed;
     out[4] = work[0], out[5] = work[1], out[6] = work[2], out[7] = 0;
     if (avg_ms) *avg_ms = ms;
+    return KTA_OK;
+}
+
+int kta_value_bytes_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_vb vb{};
+    (void)kta_internal_value_bytes(ctx, &vb);
+    if (!vb.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_VALUE_BYTES");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KafkaState *st = state_of(ctx);
+    float ms = -1.f;
+    uint64_t timed = 0, work[4] = {0, 0, 0, 0};
+    int rc = st->vb_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipMemcpyAsync(work, vb.info, sizeof work, hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
+    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
+    out[0] = st->vb_launches, out[1] = st->vb_batches, out[2] = st->vb_workgroups, out[3] = work[0];
+    if (avg_ms) *avg_ms = timed ? ms : -1.f;
     return KTA_OK;
 }
 

@@ -139,6 +139,14 @@ def allreduce_header_names_vector(nvec, group=None) -> None:
     _allreduce_sum_max(nvec, nvec.numel(), group)
 
 
+def allreduce_value_bytes_vector(yvec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the value-byte SNAPSHOT (kta_value_bytes_result_vector: device tensor, or a CPU
+    tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_VALUE_BYTES: one all-reduce SUM over
+    all 264 * P words (i64 wrap == u64 wrap)."""
+    assert yvec.numel() == 264 * n_partitions
+    _allreduce_sum_max(yvec, yvec.numel(), group)
+
+
 def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
     """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
     tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM
