@@ -8,6 +8,7 @@
 // Reference semantics (paths under /root/reference):
 //   kta_metrics_scan   src/metric.rs:207-252  MessageMetrics::handle_message
 #include "kta_kernels.h"
+#include "kta_lean_blocks.h"
 
 #include <limits.h>
 #include <type_traits>
@@ -925,8 +926,8 @@ __device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid,
 // ---- the lean loop of the summarised compact / u16 tiles (SUM kernels) ---------------------------------------------
 // The flagship's tiles are all of one kind: compact, u16 lengths, summarised.  Such a tile needs no per-record mask, no
 // bad-partition count and no timestamps: 6 vector registers per lane (a Quad has 20) and two uniform extrema.  The lean
-// loop keeps a ring of such slots, unrolled (no rotation moves), and the tiles' headers and summaries one tile further
-// ahead than the vector loads in scalar registers, so that no vector load waits for a scalar miss of its own tile.
+// loop keeps a ring of such slots, unrolled (no rotation moves); which tiles it takes it knows 64 steps at a time, from
+// two ballots over the tiles' headers, summaries and marks (kta_lean_blocks.h), so a step holds no load but the tile's.
 // Any other tile (cut by rec0 or n, raw, i32 lengths, part_max >= pc, no VALID summary) is left to the loop of before:
 // see the kernel.
 // Plane tiles (kta_tile.h: a marked tile) go through the same loop in their own form (lean_run<NT, true>): the lane's
@@ -935,7 +936,7 @@ __device__ __forceinline__ void accumulate_packed(const Quad &q, uint32_t valid,
 // exact; a workgroup that meets a summarised tile of the other form drains its ring and goes on in the other
 // instantiation (see packed_scan_lean), so a batch that mixes both keeps every summarised tile here.
 #ifndef KTA_LEAN_PREFETCH
-#define KTA_LEAN_PREFETCH 1
+#define KTA_LEAN_PREFETCH 2   // (swept with the plan's workgroups per CU, both forms: profiles/lean_blocks_scan.jsonl)
 #endif
 constexpr int kLeanPrefetch = KTA_LEAN_PREFETCH;   // tiles the lean loop loads ahead of the one it accumulates (1, 2 or 3)
 static_assert(kLeanPrefetch >= 1 && kLeanPrefetch <= 3, "the lean ring has two, three or four slots");
@@ -962,11 +963,13 @@ __device__ __forceinline__ void lean_tile(const kta_tile_hdr &h, const kta_tile_
 }
 
 // the tile's base is uniform, the lane's byte offsets (8 * tid, 16 * tid) constant over the loop
+// B: the first byte the form reads of the tile in its column — T * kTileColBytes of an i32 column, twice that and the
+// plane's offset of ts_ms — which the loop advances by a constant stride
 template <bool NT>
-__device__ __forceinline__ void lean_load(LeanSlot &s, const ScanColumns &c, uint64_t T, uint32_t off8, uint32_t off16)
+__device__ __forceinline__ void lean_load(LeanSlot &s, const ScanColumns &c, uint64_t B, uint32_t off8, uint32_t off16)
 {
-    const char *pb = reinterpret_cast<const char *>(c.partition) + T * kTileColBytes;
-    const char *kb = reinterpret_cast<const char *>(c.key_len) + T * kTileColBytes;
+    const char *pb = reinterpret_cast<const char *>(c.partition) + B;
+    const char *kb = reinterpret_cast<const char *>(c.key_len) + B;
     const v2i *pp = reinterpret_cast<const v2i *>(pb + off8);
     const v4i *kp = reinterpret_cast<const v4i *>(kb + off16);
     s.p = NT ? __builtin_nontemporal_load(pp) : *pp;
@@ -974,9 +977,9 @@ __device__ __forceinline__ void lean_load(LeanSlot &s, const ScanColumns &c, uin
     s.k = make_int4(k.x, k.y, k.z, k.w);
 }
 template <bool NT>
-__device__ __forceinline__ void lean_load(PlaneSlot &s, const ScanColumns &c, uint64_t T, uint32_t, uint32_t off16)
+__device__ __forceinline__ void lean_load(PlaneSlot &s, const ScanColumns &c, uint64_t B, uint32_t, uint32_t off16)
 {
-    const char *tb = reinterpret_cast<const char *>(c.ts_ms) + T * (2u * kTileColBytes) + kTilePlaneOffset;
+    const char *tb = reinterpret_cast<const char *>(c.ts_ms) + B;   // (B: of the tile's plane, kTilePlaneOffset included)
     const v4i *wp = reinterpret_cast<const v4i *>(tb + off16);
     const v4i w = NT ? __builtin_nontemporal_load(wp) : *wp;
     s.w = make_int4(w.x, w.y, w.z, w.w);
@@ -1130,10 +1133,10 @@ struct PackedWg {
 // The lean kernel of a summary-reading scan (kta_metrics_scan_packed<NT, true>); kta_metrics_scan_packed_rest is launched
 // behind it with the same grid.
 // Its loop (lean_run) takes the summarised tiles of one form — plane tiles, or compact / u16 tiles (lean_tile) —
-// through a ring of slots, unrolled, with the next
-// undecided tile's header and summary already requested (scalar loads: a step ahead of the vector loads they decide on),
-// and folds their timestamp extrema into two uniform words.  Every decision is made from uniform values: header,
-// summary, rec0, n, P.  A tile that does not qualify is not accumulated here.  Its step — tile = workgroup + step x grid
+// through a ring of slots, unrolled.  The workgroup's steps are classified a block of 64 at a time: lane l of every
+// wave loads header, summary, mark and size words of step 64 b + l (vector loads, requested a block ahead), applies
+// lean_tile and votes; the two ballots, through lean_block, are the block's masks, and a lane whose bit stays folds its
+// tile's extrema.  Every decision is then made from uniform values.  A tile that does not qualify is not accumulated here.  Its step — tile = workgroup + step x grid
 // — goes on the row's list (kLeanListed steps at most, in three of the row's globals that no fold reads) and the ring
 // goes on behind it; where the list is full the workgroup ends at that tile and hands it and all that follow over.
 // The workgroup of the same index in kta_metrics_scan_packed_rest takes the listed tiles and the handed-over ones
@@ -1148,76 +1151,68 @@ __device__ __forceinline__ uint32_t lean_list_entry(uint64_t list_a, uint64_t li
     return (uint32_t)((i < 2 ? list_a : list_b) >> (32u * (i & 1u)));
 }
 
-// What a workgroup of the lean kernel carries from one run of the loop to the next (uniform).
-// Tiles are counted from the batch's first (t0) in 32 bits: launch_metrics_scan keeps a batch of 2^31 tiles out.
+// A lane's side words of one tile: header, summary (as its two dwords: taking the u16 fields apart belongs to the use,
+// not to the load), mark and the two size words.
+struct LeanSide {
+    kta_tile_hdr h;
+    uint2 s;
+    uint32_t m, z0, z1;
+};
+// Tile T's (vector loads: T differs by lane).  No load is left out where the batch has no marks — it reads a summary's
+// bytes instead, and lean_tile is given a mark of 0: every path then has the same loads in flight.
+__device__ __forceinline__ void lean_side_load(LeanSide &sd, const ScanColumns &c, uint64_t T)
+{
+    const uint32_t *mp = c.mark ? c.mark : reinterpret_cast<const uint32_t *>(c.sum);
+    const uint32_t *zp = c.mark ? c.size : reinterpret_cast<const uint32_t *>(c.sum);
+    sd.h = c.hdr[T];
+    sd.s = reinterpret_cast<const uint2 *>(c.sum)[T];
+    sd.m = mp[T];
+    sd.z0 = zp[2u * T];
+    sd.z1 = zp[2u * T + 1u];
+}
+
+// What a workgroup of the lean kernel carries from one run of the loop to the next: uniform but for `side`.
+// Steps and tiles are counted in 32 bits: launch_metrics_scan keeps a batch of 2^31 tiles out.
 struct LeanRun {
-    uint32_t tile = 0;                  // the next tile to accumulate = workgroup + step x grid
-    uint32_t step = 0;
-    uint32_t end = 0;                   // this kernel's tiles end here: the batch's end, or the handed-over tile
+    LeanBlocks b;                       // the end of this kernel's steps, the list and the handover (kta_lean_blocks.h)
+    uint32_t step = 0;                  // the next step to accumulate: tile = workgroup + step x grid
+    uint32_t open_at = 0;               // the first step of the next block to open; the blocks below it are open
+    uint64_t pm = 0, lm = 0;            // the open block's plane and lean masks, bit l = step open_at - 64 + l
     uint32_t whole_lo = 0, whole_hi = 0;   // tiles [whole_lo, whole_hi) lie wholly inside the batch
-    uint32_t listed = 0;                // entries on the list
-    uint64_t list_a = 0, list_b = 0;    // the list: four steps + 1, 32 bits each
-    uint32_t handover = 0;              // the step the rest kernel takes everything from, + 1
     uint32_t since_flush = 0;
+    LeanSide side;                      // the lane's side words of step open_at + lane, requested a block ahead
 };
 
-// One run of the lean loop over tiles of one form (PLANE: plane tiles, else compact / u16 tiles), from r.tile on, until
-// the workgroup's tiles end or a summarised tile of the OTHER form comes up: r.tile is then that tile, the ring is
-// drained, and the caller goes on in the other instantiation.
+// One run of the lean loop over tiles of one form (PLANE: plane tiles, else compact / u16 tiles), from r.step on, until
+// this kernel's steps end or a summarised tile of the OTHER form comes up: r.step is then that tile's, the ring is
+// dropped, and the caller goes on in the other instantiation.
+// Between two block openings the loop holds no scalar load and no LDS read: a step is a bit of the block's mask and an
+// address that advances by the grid's stride.  The ring's loads go out whatever the bit says (of a tile that is not
+// taken they fetch bytes of the tile's own that nobody uses; past the workgroup's last tile the address stays where it
+// is, so nothing past the batch's last tile is read): a slot is then waited for behind the same number of younger loads
+// on every path, and the wait can let those stay in flight.
 template <bool NT, bool PLANE>
 __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanColumns &c, uint64_t t0, uint32_t last, uint32_t pc,
                                          uint32_t rep_log2)
 {
     using Slot = typename std::conditional<PLANE, PlaneSlot, LeanSlot>::type;
-    const uint32_t tid = wg.tid;
+    constexpr uint64_t kUnit = PLANE ? 2u * kTileColBytes : kTileColBytes;   // a tile's bytes of the column the form reads
+    const uint32_t tid = wg.tid, lane = tid & 63u;
     const uint32_t G = gridDim.x;
-    uint32_t stop = r.end;                    // this run's tiles end here: r.end, or the tile of the other form
-    bool switched = false;
-    uint32_t issued = r.tile;                 // the next tile to decide on and load: kLeanPrefetch steps ahead of r.tile
-    uint32_t istep = r.step;                  // issued = workgroup + istep x grid
-    uint32_t sw_step = 0;
-    kta_tile_hdr ah;                          // header, summary and mark of tile `issued`, requested a step before they
-    uint2 as;                                 // are used (the summary as its two dwords: taking the u16 fields apart
-    uint32_t am = 0;                          // belongs to the use, not to the load); no marks: every mark is 0
-    // (the index is clamped, not the load skipped — a skipped load merges with the old value, and the merge waits —
-    // so nothing past the batch's last tile is read)
-    auto look_ahead = [&]() {
-        const uint64_t T = t0 + (issued < last ? issued : last);
-        ah = c.hdr[T], as = reinterpret_cast<const uint2 *>(c.sum)[T];
-        if (c.mark) am = c.mark[T];
+    const uint64_t stride = (uint64_t)G * kUnit;
+    uint32_t itile = 0;                       // the tile the next load reads, and its first byte in the form's column
+    uint64_t ibyte = 0;
+    auto seek = [&](uint32_t step) {
+        const uint64_t tile = blockIdx.x + (uint64_t)step * G;
+        itile = tile < last ? (uint32_t)tile : last;
+        ibyte = (t0 + itile) * kUnit + (PLANE ? kTilePlaneOffset : 0u);
     };
-    // One step of the ring's front: decide on tile `issued` and load it into slot s; v: the slot holds a tile of this
-    // run's form.
-    // The loads go out whatever the decision (of a tile that is not taken or lies past the end — then the batch's last
-    // tile again — they fetch bytes of the tile's own that nobody uses): a slot is then waited for behind the same
-    // number of younger loads on every path, and the wait can let those stay in flight.
-    auto issue = [&](Slot &s, bool &v) {
-        const uint64_t T = t0 + (issued < last ? issued : last);
-        const bool in = issued < stop;
-        const kta_tile_sum sm{as.x, (uint16_t)(as.y & 0xFFFFu), (uint16_t)(as.y >> 16)};
-        bool lean, plane;
-        lean_tile(ah, sm, am, issued >= r.whole_lo && issued < r.whole_hi, pc, lean, plane);
-        v = (PLANE ? plane : lean) && in;
-        const bool other = (PLANE ? lean : plane) && in;
-        lean_load<NT>(s, c, T, 8u * tid, 16u * tid);
-        if (other) {
-            switched = true;
-            sw_step = istep;
-            stop = issued;
-        } else if (in && !v) {
-            if (r.listed == kLeanListed) {
-                r.handover = istep + 1u;
-                r.end = stop = issued;
-            } else {
-                const uint64_t e = (uint64_t)(istep + 1u) << (32u * (r.listed & 1u));
-                if (r.listed < 2) r.list_a |= e;
-                else r.list_b |= e;
-                r.listed++;
-            }
-        }
-        issued += G;
-        istep++;
-        look_ahead();
+    auto issue = [&](Slot &s) {
+        lean_load<NT>(s, c, ibyte, 8u * tid, 16u * tid);
+        const uint32_t next = itile + G;      // (both below 2^31)
+        const bool adv = next <= last;
+        itile = adv ? next : itile;
+        ibyte += adv ? stride : 0ull;
     };
     auto take = [&](const Slot &s, bool v) {
         if (v) {
@@ -1227,44 +1222,107 @@ __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanCol
                 r.since_flush = 0;
             }
         }
-        r.tile += G;
     };
-    // the ring, unrolled: no rotation moves, one exit
-    Slot s0, s1, s2, s3;
-    bool v0 = false, v1 = false, v2 = false, v3 = false;
-    look_ahead();
-    issue(s0, v0);
-    if (kLeanPrefetch >= 2) issue(s1, v1);
-    if (kLeanPrefetch == 3) issue(s2, v2);
-    while (r.tile < stop) {
+    // the lane's side words of step base + lane (the tile index clamped, not the load skipped)
+    auto side_request = [&](uint32_t base) {
+        const uint64_t tile = blockIdx.x + (uint64_t)(base + lane) * G;
+        lean_side_load(r.side, c, t0 + (tile < last ? tile : last));
+    };
+    // Open the block at r.open_at (= r.step): classify its 64 steps from the side words, one per lane, apply the block
+    // rule (lean_block), fold the extrema of the tiles that stay in a mask — min and max are idempotent, so every wave
+    // folds — and request the side words of the block behind it, whose latency 64 steps hide.
+    auto open_block = [&]() {
+        const uint32_t base = r.open_at;
+        const uint64_t tile = blockIdx.x + (uint64_t)(base + lane) * G;
+        const kta_tile_sum sm{r.side.s.x, (uint16_t)(r.side.s.y & 0xFFFFu), (uint16_t)(r.side.s.y >> 16)};
+        bool lean, plane;
+        lean_tile(r.side.h, sm, c.mark ? r.side.m : 0u, tile >= r.whole_lo && tile < r.whole_hi, pc, lean, plane);
+        r.pm = __ballot(plane);
+        r.lm = __ballot(lean);
+        lean_block(r.b, base, kLeanListed, r.pm, r.lm);
+        const bool tp = (r.pm >> lane) & 1ull, tl = (r.lm >> lane) & 1ull;
+        long long lo, hi;
+        tile_sum_extrema(r.side.h, sm, lo, hi);
+        wg.st.tmin = ((tp || tl) && lo < wg.st.tmin) ? lo : wg.st.tmin;
+        wg.st.tmax = ((tp || tl) && hi > wg.st.tmax) ? hi : wg.st.tmax;
+        wg.st.smin = min(wg.st.smin, tp ? r.side.z0 : 0xFFFFFFFFu);   // (c.size is there wherever c.mark is)
+        wg.st.smax = max(wg.st.smax, tp ? r.side.z1 : 0u);
+        r.open_at = base + kLeanBlockSteps;
+        side_request(r.open_at);
+    };
+    // The steps of this run in the open block from r.step on — up to the first of the other form, the block's end or
+    // r.b.end — and their bits of this form's mask, bit 0 = r.step.
+    auto span = [&](uint64_t &mine) {
+        const uint32_t pos = r.step - (r.open_at - kLeanBlockSteps);
+        const uint64_t a = (PLANE ? r.pm : r.lm) >> pos, o = (PLANE ? r.lm : r.pm) >> pos;
+        uint32_t cnt = o ? (uint32_t)__builtin_ctzll(o) : kLeanBlockSteps - pos;
+        cnt = min(cnt, r.b.end - r.step);
+        mine = cnt < kLeanBlockSteps ? a & ((1ull << cnt) - 1ull) : a;
+        return cnt;
+    };
+    // the ring, unrolled over four steps whatever its depth (no rotation moves; a block is 16 such bodies): the slots
+    // a, b, c hold the kLeanPrefetch tiles in flight
+    Slot a, b, cc, d;
+    auto body = [&](uint64_t &m) {
         if (kLeanPrefetch == 3) {
-            issue(s3, v3);
-            take(s0, v0);
-            issue(s0, v0);
-            take(s1, v1);
-            issue(s1, v1);
-            take(s2, v2);
-            issue(s2, v2);
-            take(s3, v3);
+            issue(d), take(a, (uint32_t)m & 1u);
+            issue(a), take(b, (uint32_t)m & 2u);
+            issue(b), take(cc, (uint32_t)m & 4u);
+            issue(cc), take(d, (uint32_t)m & 8u);
         } else if (kLeanPrefetch == 2) {
-            issue(s2, v2);
-            take(s0, v0);
-            issue(s0, v0);
-            take(s1, v1);
-            issue(s1, v1);
-            take(s2, v2);
+            issue(cc), take(a, (uint32_t)m & 1u);
+            issue(d), take(b, (uint32_t)m & 2u);
+            issue(a), take(cc, (uint32_t)m & 4u);
+            issue(b), take(d, (uint32_t)m & 8u);
         } else {
-            issue(s1, v1);
-            take(s0, v0);
-            issue(s0, v0);
-            take(s1, v1);
+            issue(b), take(a, (uint32_t)m & 1u);
+            issue(a), take(b, (uint32_t)m & 2u);
+            issue(b), take(a, (uint32_t)m & 4u);
+            issue(a), take(b, (uint32_t)m & 8u);
         }
+        m >>= 4;
+    };
+    if (r.step != r.open_at) {
+        // The run begins inside an open block (behind a run of the other form): single steps up to a multiple of four.
+        uint64_t mine;
+        uint32_t cnt = span(mine);
+        const bool ends = cnt < r.open_at - r.step;
+        while ((r.step & 3u) && cnt) {
+            Slot x;
+            seek(r.step);
+            issue(x);
+            take(x, mine & 1u);
+            mine >>= 1;
+            r.step++, cnt--;
+        }
+        if (!cnt && ends) return;
     }
-    // (the unrolled ring may have stepped past `stop`: slots issued at or behind it hold no tile)
-    // (every take follows an issue and kLeanPrefetch issues went ahead: the step is not counted in the loop, whose
-    // scalar registers are all in use)
-    r.step = istep - (uint32_t)kLeanPrefetch;
-    if (switched) r.tile = blockIdx.x + sw_step * G, r.step = sw_step;
+    seek(r.step);
+    issue(a);
+    if (kLeanPrefetch >= 2) issue(b);
+    if (kLeanPrefetch == 3) issue(cc);
+    while (r.step < r.b.end) {
+        uint64_t mine;
+        uint32_t cnt, nb;
+        const bool opens = r.step == r.open_at;
+        if (opens) {
+            // (the first body of a block has the next block's side loads behind the ring's: a copy of its own, whose
+            // waits count them; every later body waits as if there were none)
+            open_block();
+            cnt = span(mine);
+            if (!cnt) break;
+            nb = (cnt + 3u) / 4u - 1u;
+            body(mine);
+        } else {
+            cnt = span(mine);
+            if (!cnt) break;
+            nb = (cnt + 3u) / 4u;
+        }
+        for (; nb; nb--) body(mine);
+        // (the last body may have stepped past the run's steps: their bits are 0, and the slots hold no tile)
+        r.step += cnt;
+        if (r.step != r.open_at) break;
+    }
 }
 
 template <bool NT>
@@ -1279,16 +1337,20 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
     const uint64_t ntiles = (c.rec0 + n + KTA_TILE_RECORDS - 1) / KTA_TILE_RECORDS - t0;
     const uint32_t pc = min(P, (uint32_t)KTA_COMPACT_PART_NONE);
     LeanRun r;
-    r.tile = blockIdx.x;
-    r.end = (uint32_t)ntiles;
+    r.b.end = lean_steps(blockIdx.x, gridDim.x, ntiles);
     r.whole_lo = c.rec0 % KTA_TILE_RECORDS ? 1u : 0u;
     r.whole_hi = (uint32_t)((c.rec0 + n) / KTA_TILE_RECORDS - t0);
-    const uint32_t last = r.end - 1u;
-    // Runs of the two forms in turn (r.tile < ntiles: there is a tile to clamp to).  A run that begins at a tile of the
+    const uint32_t last = (uint32_t)ntiles - 1u;
+    // Runs of the two forms in turn (r.b.end > 0: there is a tile to clamp to).  A run that begins at a tile of the
     // other form ends at once, and the other one takes that tile, so every turn but the first takes a tile.  With marks
     // the plane form goes first: the flagship's tiles are all marked.
     bool plane = c.mark != nullptr;
-    while (r.tile < r.end) {
+    if (r.b.end) {
+        // the first block's side words, before any run
+        const uint64_t tile = blockIdx.x + (uint64_t)(tid & 63u) * gridDim.x;
+        lean_side_load(r.side, c, t0 + (tile < last ? tile : last));
+    }
+    while (r.step < r.b.end) {
         if (plane) lean_run<NT, true>(wg, r, c, t0, last, pc, rep_log2);
         else lean_run<NT, false>(wg, r, c, t0, last, pc, rep_log2);
         // A front interval holds records of one form, so that front_flush has one rule for it: the run's last interval
@@ -1299,32 +1361,14 @@ __device__ __forceinline__ void packed_scan_lean(const ScanColumns &c, uint64_t 
         }
         plane = !plane;
     }
-    // The taken tiles' timestamp extrema, off the loop (where they were some thirty scalar and vector instructions per
-    // tile): every thread folds the summaries of some of the workgroup's tiles below r.end; the same rule decides again
-    // which of them were taken — a listed tile is one it refuses.
-    for (uint64_t i = blockIdx.x + (uint64_t)tid * gridDim.x; i < r.end; i += (uint64_t)kWG * gridDim.x) {
-        const kta_tile_hdr h = c.hdr[t0 + i];
-        const kta_tile_sum sm = c.sum[t0 + i];
-        const uint32_t mark = c.mark ? c.mark[t0 + i] : 0u;
-        bool lean, plane;
-        lean_tile(h, sm, mark, i >= r.whole_lo && i < r.whole_hi, pc, lean, plane);
-        long long lo, hi;
-        tile_sum_extrema(h, sm, lo, hi);
-        wg.st.tmin = ((lean || plane) && lo < wg.st.tmin) ? lo : wg.st.tmin;
-        wg.st.tmax = ((lean || plane) && hi > wg.st.tmax) ? hi : wg.st.tmax;
-        if (plane) {   // (c.size is there wherever c.mark is)
-            wg.st.smin = min(wg.st.smin, c.size[2 * (t0 + i)]);
-            wg.st.smax = max(wg.st.smax, c.size[2 * (t0 + i) + 1]);
-        }
-    }
     // (every run flushed its last interval, and thread p reads from the back level the words it wrote there itself)
     uint64_t *row = partials + (uint64_t)blockIdx.x * row_len;
     wg.write_row(row, s_red);
     if (tid == 0) {   // (behind the zeroes write_scan_globals put there)
         uint64_t *g = row + (uint64_t)P * kScanCols;
-        g[kScanListA] = r.list_a;
-        g[kScanHandover] = r.handover;
-        g[kScanListB] = r.list_b;
+        g[kScanListA] = r.b.list_a;
+        g[kScanHandover] = r.b.handover;
+        g[kScanListB] = r.b.list_b;
     }
 }
 
@@ -1373,6 +1417,25 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed(ScanColumns c, ui
     wg.front_flush();
     wg.write_row(partials + (uint64_t)blockIdx.x * row_len, s_red);
 }
+// The lean kernel, specialised for its register budget alone (the body is the template's SUM branch): left to itself
+// the compiler spends some 100 vector registers on it — the loop needs about 60 — and five workgroups of a CU, the
+// plan's, would not be resident together.  kLeanWavesPerSimd waves per SIMD: 96 registers.
+#ifndef KTA_LEAN_WAVES
+#define KTA_LEAN_WAVES 5
+#endif
+constexpr int kLeanWavesPerSimd = KTA_LEAN_WAVES;
+#define KTA_LEAN_KERNEL(NT)                                                                                                    \
+    template <>                                                                                                                \
+    __global__ __launch_bounds__(kWG, kLeanWavesPerSimd) void kta_metrics_scan_packed<NT, true>(                               \
+        ScanColumns c, uint64_t n, uint32_t P, uint32_t rep_log2, uint64_t *__restrict__ partials, uint32_t row_len)           \
+    {                                                                                                                          \
+        extern __shared__ unsigned long long lds[];                                                                            \
+        __shared__ long long s_red[kWG / 64][6];                                                                               \
+        packed_scan_lean<NT>(c, n, P, rep_log2, partials, row_len, lds, s_red);                                                \
+    }
+KTA_LEAN_KERNEL(true)
+KTA_LEAN_KERNEL(false)
+#undef KTA_LEAN_KERNEL
 
 // The tiles the lean kernel's workgroup of the same index left (see there): the listed ones, then every tile from the
 // handed-over step on, through the loop over Quads with one tile loaded ahead; added to the row.
