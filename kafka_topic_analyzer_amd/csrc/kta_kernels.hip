@@ -9,6 +9,7 @@
 //   kta_metrics_scan   src/metric.rs:207-252  MessageMetrics::handle_message
 #include "kta_kernels.h"
 #include "kta_lean_blocks.h"
+#include "kta_plane_pack.h"
 
 #include <limits.h>
 #include <type_traits>
@@ -761,9 +762,15 @@ constexpr uint64_t kFrontRecords = (uint64_t)kFrontFlushTiles * KTA_TILE_RECORDS
 static_assert(kFrontRecords <= 0xFFFFu, "count, tombstones and null keys of a front interval fit 16 bits");
 static_assert(kFrontRecords + (kFrontRecords << 16) <= 0xFFFFFFFFull, "count | tombstones << 16 stays in W1's low dword");
 static_assert(kFrontRecords * (KTA_COMPACT_LEN_NONE - 1u) < (1ull << 31), "a front interval's u16 sizes sum below 2^31");
-// The plane form adds the lengths as stored, markers included (lean_quad(PlaneSlot)); front_flush(raw) takes them out again:
-static_assert(kFrontRecords * KTA_PLANE_KEY_NONE < (1ull << 23), "a front interval's raw plane key bytes sum below 2^23");
-static_assert(kFrontRecords * KTA_COMPACT_LEN_NONE < (1ull << 31), "a front interval's raw plane value words sum below 2^31");
+// The plane form has words, bounds and an interval of its own (kta_plane_pack.h): one 64-bit add per record of count, raw
+// key sum and raw value sum, whose fields hold the 8192 records that ONE slot takes in min(kFrontFlushTiles, 8 R) tiles
+// — kFrontFlushTiles with four replicas or more, 16 tiles with two, 8 with one.  The 6-byte form, the rest kernel and
+// the kernel without summaries keep kFrontFlushTiles and the two adds above.
+static_assert(kPlaneTileRecords == KTA_TILE_RECORDS && kPlaneKeyNone == KTA_PLANE_KEY_NONE && kPlaneValNone == KTA_COMPACT_LEN_NONE,
+              "kta_plane_pack.h restates the tile's constants");
+static_assert(plane_slot_records(0, kFrontFlushTiles) <= kPlaneSlotRecords && plane_slot_records(1, kFrontFlushTiles) <= kPlaneSlotRecords &&
+              plane_slot_records(2, kFrontFlushTiles) <= kPlaneSlotRecords && plane_slot_records(6, kFrontFlushTiles) <= kPlaneSlotRecords,
+              "a slot of the plane form takes at most kPlaneSlotRecords records between two flushes");
 
 struct PackedLds {
     unsigned long long *W1, *W2;       // front level
@@ -1042,6 +1049,14 @@ __device__ __forceinline__ void lean_quad(const LeanSlot &s, uint32_t rep_log2, 
 // 0xFF for a key of -1 and 0xFFFF for a value of -1 included, and front_flush(raw) subtracts the markers by the
 // interval's counts of null keys and tombstones — no select per record.  No size extrema either: the tile's producer
 // wrote them (kta_tile.h) and packed_scan_lean folds them behind the loop.
+// ONE 64-bit add per record (or uniform quad): count, raw key sum and raw value sum share W1's word, and the two flag
+// counts go with a 32-bit add to the low dword of W2, executed only by the lanes that have a flag (kta_plane_pack.h:
+// the word, its bounds and the shorter interval they ask of a plan with fewer than four replicas).
+__device__ __forceinline__ void plane_add(const PackedLds &L, uint32_t slot, const PlaneAdd &a)
+{
+    atomicAdd(&L.W1[slot], plane_word(a));
+    if (a.flags) atomicAdd(reinterpret_cast<uint32_t *>(&L.W2[slot]), a.flags);   // (little endian: the low dword)
+}
 __device__ __forceinline__ void lean_quad(const PlaneSlot &s, uint32_t rep_log2, uint32_t rep, const PackedLds &L, LaneState &st)
 {
     const uint32_t w[4] = {(uint32_t)s.w.x, (uint32_t)s.w.y, (uint32_t)s.w.z, (uint32_t)s.w.w};
@@ -1062,16 +1077,11 @@ __device__ __forceinline__ void lean_quad(const PlaneSlot &s, uint32_t rep_log2,
         const uint32_t slot = (pt[0] << rep_log2) | rep;
         const uint32_t tombs = tomb[0] + tomb[1] + tomb[2] + tomb[3];
         const uint32_t knulls = knull[0] + knull[1] + knull[2] + knull[3];
-        atomicAdd(&L.W1[slot], pack_dwords(4u | (tombs << 16), ku[0] + ku[1] + ku[2] + ku[3]));
-        atomicAdd(&L.W2[slot], pack_dwords(knulls, vu[0] + vu[1] + vu[2] + vu[3]));
+        plane_add(L, slot, plane_pack(4u, ku[0] + ku[1] + ku[2] + ku[3], vu[0] + vu[1] + vu[2] + vu[3], knulls, tombs));
         return;
     }
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t slot = (pt[j] << rep_log2) | rep;
-        atomicAdd(&L.W1[slot], pack_dwords(1u | (tomb[j] << 16), ku[j]));
-        atomicAdd(&L.W2[slot], pack_dwords(knull[j], vu[j]));
-    }
+    for (int j = 0; j < 4; j++) plane_add(L, (pt[j] << rep_log2) | rep, plane_pack(1u, ku[j], vu[j], knull[j], tomb[j]));
 }
 
 // The workgroup of every packed scan kernel: its LDS words, carved out of the dynamic LDS and zeroed, its lane state,
@@ -1091,13 +1101,32 @@ struct PackedWg {
         rep = tid & ((1u << rep_log2) - 1u);
     }
     // front level into back level: thread p sums and zeroes partition p's replicas, between two barriers
-    // raw: the interval's records were plane records, added with their markers (lean_quad(PlaneSlot)): the null keys'
-    // 0xFF and the tombstones' 0xFFFF leave the two size sums here, by the interval's own counts.  One rule per interval:
-    // a workgroup that changes form flushes first (packed_scan_lean).
+    // raw: the interval's records were plane records, added in the plane's words and with their markers
+    // (lean_quad(PlaneSlot), kta_plane_pack.h): every replica is unpacked on its own — only a single slot's fields are
+    // bounded — and the null keys' 0xFF and the tombstones' 0xFFFF leave the two size sums here, by the interval's own
+    // counts.  One rule per interval: a workgroup that changes form flushes first (packed_scan_lean).
     __device__ __forceinline__ void front_flush(bool raw = false) const
     {
-        const unsigned long long key_none = raw ? KTA_PLANE_KEY_NONE : 0u, val_none = raw ? KTA_COMPACT_LEN_NONE : 0u;
         __syncthreads();
+        if (raw) {
+            for (uint32_t p = tid; p < P; p += kWG) {
+                PlaneSums sums;
+                for (uint32_t r = 0; r < (1u << rep_log2); r++) {
+                    const uint32_t s = (p << rep_log2) | r;
+                    plane_unpack(sums, L.W1[s], L.W2[s]);
+                    L.W1[s] = 0ull;
+                    L.W2[s] = 0ull;
+                }
+                plane_corrected(sums);
+                L.B[p] += sums.cnt;
+                L.B[P + p] += sums.tb;
+                L.B[2u * P + p] += sums.kn;
+                L.B[3u * P + p] += sums.ks;
+                L.B[4u * P + p] += sums.vs;
+            }
+            __syncthreads();
+            return;
+        }
         for (uint32_t p = tid; p < P; p += kWG) {
             unsigned long long w1 = 0, w2 = 0;   // (the replicas' sum obeys the same bound: it is the workgroup's records)
             for (uint32_t r = 0; r < (1u << rep_log2); r++) {
@@ -1110,8 +1139,8 @@ struct PackedWg {
             L.B[p] += w1 & 0xFFFFull;
             L.B[P + p] += (w1 >> 16) & 0xFFFFull;
             L.B[2u * P + p] += w2 & 0xFFFFFFFFull;
-            L.B[3u * P + p] += (w1 >> 32) - key_none * (w2 & 0xFFFFFFFFull);
-            L.B[4u * P + p] += (w2 >> 32) - val_none * ((w1 >> 16) & 0xFFFFull);
+            L.B[3u * P + p] += w1 >> 32;
+            L.B[4u * P + p] += w2 >> 32;
         }
         __syncthreads();
     }
@@ -1200,6 +1229,7 @@ __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanCol
     const uint32_t tid = wg.tid, lane = tid & 63u;
     const uint32_t G = gridDim.x;
     const uint64_t stride = (uint64_t)G * kUnit;
+    const uint32_t interval = PLANE ? plane_interval_tiles(rep_log2, kFrontFlushTiles) : kFrontFlushTiles;   // (uniform)
     uint32_t itile = 0;                       // the tile the next load reads, and its first byte in the form's column
     uint64_t ibyte = 0;
     auto seek = [&](uint32_t step) {
@@ -1217,7 +1247,7 @@ __device__ __forceinline__ void lean_run(PackedWg &wg, LeanRun &r, const ScanCol
     auto take = [&](const Slot &s, bool v) {
         if (v) {
             lean_quad(s, rep_log2, wg.rep, wg.L, wg.st);
-            if (++r.since_flush == kFrontFlushTiles) {
+            if (++r.since_flush == interval) {
                 wg.front_flush(PLANE);
                 r.since_flush = 0;
             }

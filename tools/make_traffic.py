@@ -62,7 +62,7 @@ out = {"round": 14, "source": path,
 # a kernel's entry goes stale with any file its device code comes from: its own and the shared headers (kta_kernels.h
 # includes kta_tile.h; the partition kernels take the keyed stream, the tile layout and the hash from the three headers)
 CSRC = "kafka_topic_analyzer_amd/csrc/"
-SCAN_SRC = "+".join(CSRC + f for f in ("kta_kernels.hip", "kta_tile.h", "kta_lean_blocks.h"))
+SCAN_SRC = "+".join(CSRC + f for f in ("kta_kernels.hip", "kta_tile.h", "kta_lean_blocks.h", "kta_plane_pack.h"))
 n_scan = 1 << 30
 # the flagship's batch is tile-compact and keyless: the packed scan, 4 B per record read where
 # every tile is summarised and has a scan plane (config 4: neither the timestamps nor the u16 forms are loaded); the

@@ -1,7 +1,9 @@
 // Developer microbenchmark (not product code): throughput of 64-bit atomicMax on random slots of a
 // table, by memory scope and working-set size.  Informs the alive-key pass design.
 //   ubench_atomics lds : instead, the rate of non-returning LDS adds (ds_add_u64 / ds_add_u32) in the metrics scan's
-//   geometry: 256 partitions x 4 lane replicas, 5 workgroups of 4 waves per CU.
+//   geometry: 256 partitions x 4 lane replicas, 5 workgroups of 4 waves per CU; and the two forms of
+//   a plane record's adds, per record: two ds_add_u64 (W1 and W2), or one ds_add_u64 and a ds_add_u32 that a random
+//   tenth of the lanes executes (kta_plane_pack.h).
 #include <string.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -69,6 +71,39 @@ __global__ __launch_bounds__(256) void k_lds_add(uint32_t iters, uint64_t seed, 
     if (acc == 0x1234567) *sink = acc;
 }
 
+// A plane record's adds on the scan's slots, two tables as the front level has them.  FORM 0: two ds_add_u64, W1[slot]
+// and W2[slot].  FORM 1: one ds_add_u64 to W1[slot] and one ds_add_u32 to the low dword of W2[slot], executed by the
+// lanes whose draw carries a flag — a random tenth, drawn with the slots before the timed loop.
+template <int FORM>
+__global__ __launch_bounds__(256) void k_lds_pair(uint32_t iters, uint64_t seed, unsigned long long *sink)
+{
+    __shared__ unsigned long long w1[kLdsSlots], w2[kLdsSlots];
+    for (uint32_t i = threadIdx.x; i < kLdsSlots; i += 256) w1[i] = 0, w2[i] = 0;
+    uint32_t slot[kLdsDraws], flagged = 0;
+#pragma unroll
+    for (int j = 0; j < kLdsDraws; j++) {
+        const uint64_t d = mix64(seed + ((uint64_t)blockIdx.x * 256 + threadIdx.x) * kLdsDraws + j);
+        slot[j] = ((uint32_t)d & 255u) << 2 | (threadIdx.x & 3u);
+        flagged |= (uint32_t)((d >> 32) % 10u == 0u) << j;
+    }
+    __syncthreads();
+    for (uint32_t it = 0; it < iters; it++) {
+#pragma unroll
+        for (int j = 0; j < kLdsDraws; j++) {
+            (void)__hip_atomic_fetch_add(&w1[slot[j]], (unsigned long long)(it | 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (FORM == 0)
+                (void)__hip_atomic_fetch_add(&w2[slot[j]], (unsigned long long)(it | 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else if ((flagged >> j) & 1u)
+                (void)__hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(&w2[slot[j]]), it | 1u, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __syncthreads();
+    unsigned long long acc = 0;
+    for (uint32_t i = threadIdx.x; i < kLdsSlots; i += 256) acc += w1[i] + w2[i];
+    if (acc == 0x1234567) *sink = acc;
+}
+
 static int lds_main()
 {
     hipDeviceProp_t prop;
@@ -82,9 +117,10 @@ static int lds_main()
     const uint32_t iters = 4096;
     printf("LDS adds, non-returning: %d CUs x %d workgroups x 4 waves, %u x %d instructions per wave, clock %.0f MHz\n", cus,
            per_cu, iters, kLdsDraws, mhz);
-    const char *names[4] = {"ds_add_u64 scan slots (random part << 2 | lane & 3)", "ds_add_u64 slot = thread",
-                            "ds_add_u32 scan slots (random part << 2 | lane & 3)", "ds_add_u32 slot = thread"};
-    for (int mode = 0; mode < 4; mode++) {
+    const char *names[6] = {"ds_add_u64 scan slots (random part << 2 | lane & 3)", "ds_add_u64 slot = thread",
+                            "ds_add_u32 scan slots (random part << 2 | lane & 3)", "ds_add_u32 slot = thread",
+                            "record: ds_add_u64 + ds_add_u64, scan slots", "record: ds_add_u64 + ds_add_u32 by a tenth of the lanes"};
+    for (int mode = 0; mode < 6; mode++) {
         float best = 1e9;
         for (int rep = 0; rep < 4; rep++) {
             hipEventRecord(a);
@@ -92,7 +128,9 @@ static int lds_main()
             case 0: hipLaunchKernelGGL((k_lds_add<unsigned long long, 0>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
             case 1: hipLaunchKernelGGL((k_lds_add<unsigned long long, 1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
             case 2: hipLaunchKernelGGL((k_lds_add<uint32_t, 0>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
-            default: hipLaunchKernelGGL((k_lds_add<uint32_t, 1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            case 3: hipLaunchKernelGGL((k_lds_add<uint32_t, 1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            case 4: hipLaunchKernelGGL((k_lds_pair<0>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
+            default: hipLaunchKernelGGL((k_lds_pair<1>), dim3(cus * per_cu), dim3(256), 0, 0, iters, 7 + rep, sink); break;
             }
             hipEventRecord(b);
             if (hipEventSynchronize(b) != hipSuccess) { printf("kernel failed\n"); return 1; }
@@ -101,8 +139,8 @@ static int lds_main()
         }
         const double per_cu_insts = (double)per_cu * 4 * iters * kLdsDraws;
         const double ns = best * 1e6 / per_cu_insts;
-        printf("%-56s %8.3f ms  %6.2f ns per wave instruction per CU = %5.1f cycles at %.0f MHz\n", names[mode], best, ns,
-               ns * mhz / 1e3, mhz);
+        printf("%-56s %8.3f ms  %6.2f ns per wave %s per CU = %5.1f cycles at %.0f MHz\n", names[mode], best, ns,
+               mode < 4 ? "instruction" : "record", ns * mhz / 1e3, mhz);
     }
     return 0;
 }
