@@ -8,6 +8,7 @@
 // Reference semantics (paths under /root/reference):
 //   kta_metrics_scan   src/metric.rs:207-252  MessageMetrics::handle_message
 #include "kta_kernels.h"
+#include "kta_fold.h"
 #include "kta_lean_blocks.h"
 #include "kta_plane_pack.h"
 
@@ -1534,88 +1535,18 @@ __global__ __launch_bounds__(kWG) void kta_metrics_scan_packed_rest(ScanColumns 
 // ---------------------------------------------------------------------------------------
 // K5  fold partial rows into the persistent counter vector
 // ---------------------------------------------------------------------------------------
-// Layout of vec: u64[P*7] (reference field order) followed by KTA_NGLOBALS globals
-// (include/kta_hip.h).  grid = (column blocks, row slices); each thread sums one column of
-// the partial workspace over its row slice (consecutive threads read consecutive words), then
-// one device-scope integer atomic per (thread, output).  Integer atomics commute => exact.
+// The body is kta_fold.h's.  grid = (column blocks, row groups of kta_fold_groups.h); each thread folds one column of its
+// group's rows.
 __global__ __launch_bounds__(kWG) void kta_fold_partials(const uint64_t *__restrict__ partials,
                                                          uint32_t rows, uint32_t P,
                                                          uint64_t *__restrict__ vec, uint32_t row_len,
                                                          uint64_t *__restrict__ avec)
 {
-    const uint32_t base_len = P * kScanCols + kScanGlobals;
     const uint32_t col = blockIdx.x * kWG + threadIdx.x;
     if (col >= row_len) return;
-    const uint32_t r0 = (uint32_t)(((uint64_t)rows * blockIdx.y) / gridDim.y);
-    const uint32_t r1 = (uint32_t)(((uint64_t)rows * (blockIdx.y + 1)) / gridDim.y);
-    if (r0 == r1) return;
-    if (col >= base_len) {
-        // analytics tail of the row: [P][4] signed-max extrema, then 2 x 34 histogram sums.
-        // avec layout: [2 x 34 histogram][P][4 extrema]
-        const uint32_t a = col - base_len;
-        if (a < 4u * P) {
-            long long m = LLONG_MIN;
-            for (uint32_t r = r0; r < r1; r++) {
-                const long long x = (long long)partials[(uint64_t)r * row_len + col];
-                m = x > m ? x : m;
-            }
-            atomicMax(reinterpret_cast<long long *>(avec) + 2 * kHistBuckets + a, m);
-        } else {
-            unsigned long long t = 0;
-            for (uint32_t r = r0; r < r1; r++) t += partials[(uint64_t)r * row_len + col];
-            if (t) atomicAdd(reinterpret_cast<unsigned long long *>(avec) + (a - 4u * P), t);
-        }
-        return;
-    }
-    unsigned long long *v = reinterpret_cast<unsigned long long *>(vec);
-    unsigned long long *g = v + (uint64_t)P * 7;
-    if (col < P * kScanCols) {
-        const uint32_t p = col / kScanCols, f = col % kScanCols;
-        unsigned long long s = 0;
-        for (uint32_t r = r0; r < r1; r++) s += partials[(uint64_t)r * row_len + col];
-        if (s == 0) return;
-        unsigned long long *o = v + (uint64_t)p * 7;
-        switch (f) {
-        case 0: // record count: total += s, alive += s, key_non_null += s, records += s
-            atomicAdd(&o[0], s);
-            atomicAdd(&o[2], s);
-            atomicAdd(&o[4], s);
-            atomicAdd(&g[2], s);
-            break;
-        case 1: // tombstones: tombstones += s, alive -= s   (alive = total - tombstones)
-            atomicAdd(&o[1], s);
-            atomicAdd(&o[2], 0ull - s);
-            break;
-        case 2: // key None: key_null += s, key_non_null -= s
-            atomicAdd(&o[3], s);
-            atomicAdd(&o[4], 0ull - s);
-            break;
-        case 3: atomicAdd(&o[5], s); break; // key_size_sum
-        default: atomicAdd(&o[6], s); break; // value_size_sum
-        }
-    } else {
-        const uint32_t gi = col - P * kScanCols;
-        long long *gs = reinterpret_cast<long long *>(g);
-        if (gi == SG_TMIN || gi == SG_SMIN) { // minima are kept bit-complemented: all four are MAX
-            long long m = LLONG_MAX;
-            for (uint32_t r = r0; r < r1; r++) {
-                const long long x = (long long)partials[(uint64_t)r * row_len + col];
-                m = x < m ? x : m;
-            }
-            atomicMax(&gs[gi == SG_TMIN ? 4 : 6], ~m);
-        } else if (gi == SG_TMAX || gi == SG_SMAX) {
-            long long m = LLONG_MIN;
-            for (uint32_t r = r0; r < r1; r++) {
-                const long long x = (long long)partials[(uint64_t)r * row_len + col];
-                m = x > m ? x : m;
-            }
-            atomicMax(&gs[gi == SG_TMAX ? 5 : 7], m);
-        } else if (gi == SG_BAD) {
-            unsigned long long s = 0;
-            for (uint32_t r = r0; r < r1; r++) s += partials[(uint64_t)r * row_len + col];
-            if (s) atomicAdd(&g[0], s);
-        }
-    }
+    uint32_t r0, r1;
+    fold_group_rows(blockIdx.y, rows, r0, r1);   // (launch_fold_partials: gridDim.y = fold_groups(rows))
+    fold_rows(partials, r0, r1, P, vec, row_len, avec, col);
 }
 
 // launch_tiles_to_raw: one workgroup per tile, grid-strided over the allocation tiles that overlap [lo, hi).  what bit 0:
@@ -1806,8 +1737,7 @@ hipError_t launch_metrics_scan(const ScanPlan &pl, const ScanColumns &c, uint64_
 hipError_t launch_fold_partials(const uint64_t *partials, uint32_t rows, uint32_t P, uint64_t *vec,
                                 uint32_t row_len, uint64_t *avec, hipStream_t s)
 {
-    uint32_t slices = rows < 32 ? rows : 32;
-    dim3 grid((row_len + kWG - 1) / kWG, slices), block(kWG);
+    dim3 grid((row_len + kWG - 1) / kWG, fold_groups(rows)), block(kWG);   // (the kernel takes the rows of group blockIdx.y)
     hipLaunchKernelGGL(kta_fold_partials, grid, block, 0, s, partials, rows, P, vec, row_len, avec);
     return hipGetLastError();
 }
