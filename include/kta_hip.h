@@ -503,6 +503,31 @@ typedef struct kta_value_bytes_summary_t {
     uint32_t top_byte, cls;
 } kta_value_bytes_summary_t;
 
+/* Compression what-if (NOT in the reference): the bytes a defined LZ4 compressor, the MODEL, would leave of the records
+ * section of every batch that the raw-log decode delivers (kta_kafka.h: kta_kafka_decode_device, and through it
+ * kta_kafka_blob_submit and kta_kafka_consume), per partition and by the batch's current codec: what would
+ * `compression.type=lz4` save on this topic, at its present batching?  Opt-in at kta_create, independent of every other flag.
+ * Every word is exact and a SUM.  csrc/kta_lz4_model.h is the code of everything below and states the model once.
+ * A batch COUNTS when its descriptor has status 0 and a partition in [0, P); with a filter (kta_set_filter) its partition is
+ * in the set and its [base_ts_ms, max_ts_ms] overlaps the window, the record-batch section's rule: the section is about
+ * whole batches.  During a compaction replay the pass is skipped; failed batches add nothing; compressed batches are read in
+ * their inflated form.
+ * The unit is a batch's inflated records section, cut into independent blocks of at most 65536 bytes.  Its frame is 7 bytes
+ * (magic, FLG 0x60, BD 0x40, HC), per block 4 bytes and min(model(block), block length) bytes — a block that does not shrink is
+ * stored —, and an end mark of 4 bytes; no checksums, no content size.  model(block): the LZ4 block grammar with a match
+ * finder of a 4096-entry table that is looked up 64 positions at a time (kta_lz4_model.h).  The model is a FLOOR of what
+ * compression wins: liblz4 itself finds candidates the model does not, gzip and zstd do better still.
+ * The vector is u64[KTA_COMPRESS_WHATIF_WORDS(P)]: 8 words per partition — batches, blocks, stored_blocks, raw_bytes (the
+ * records sections inflated), now_bytes (sum of batch_bytes - 61: the records sections as they lie on disk), model_bytes (the
+ * frames), sequences (matches), match_bytes (the bytes matches cover) — and behind them 5 codecs x 4 words by the batch's
+ * current codec (0 none, 1 gzip, 2 snappy, 3 lz4, 4 zstd): batches, raw_bytes, now_bytes, model_bytes.  The 61 bytes of a
+ * batch's header are on neither side.  With the flag off no kernel is launched and nothing is allocated. */
+#define KTA_FLAG_COMPRESS_WHATIF 0x2000U /* 8192: bit 13 */
+#define KTA_COMPRESS_WHATIF_PARTITION_WORDS 8
+#define KTA_COMPRESS_WHATIF_CODECS 5
+#define KTA_COMPRESS_WHATIF_CODEC_WORDS 4
+#define KTA_COMPRESS_WHATIF_WORDS(P) (8u * (size_t)(P) + 20u)
+
 /* Record filter (NOT in the reference, which always consumes the whole topic): analyse a time window and a subset of
  * partitions.  kta_set_filter gives a context a window [from_ms, to_ms) and / or a set of partitions.  A record PASSES iff
  * both hold:
@@ -1233,6 +1258,23 @@ int kta_value_bytes_summary(const uint64_t *words, kta_value_bytes_summary_t *ou
  * partition outside [0, P) adds nothing.  No filter. */
 int kta_value_bytes_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t n_partitions);
 
+/* Compression what-if (context created with KTA_FLAG_COMPRESS_WHATIF; definition above KTA_FLAG_COMPRESS_WHATIF).  kta_reset
+ * zeroes the vector; kta_finish_device snapshots it; kta_exchange reduces the snapshot (all SUM).  Every call below that
+ * takes a context fails on one without the flag with KTA_ERR_INVALID and a message naming KTA_FLAG_COMPRESS_WHATIF.
+ * The live accumulator, copied to out[n_u64] (n_u64 = KTA_COMPRESS_WHATIF_WORDS(P); staged messages are flushed first). */
+int kta_get_compress_whatif(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* The SNAPSHOT that kta_finish_device (kta_finish, kta_exchange) takes: after kta_exchange the whole job's vector on every rank. */
+int kta_exchange_compress_whatif(kta_ctx *ctx, uint64_t *out, size_t n_u64);
+/* Device pointer / length (u64) of that snapshot (what collectives reduce in place), and of the live vector. */
+int kta_compress_whatif_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+int kta_compress_whatif_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64);
+/* Host-side merge of two vectors u64[KTA_COMPRESS_WHATIF_WORDS(P)]: acc <- acc + other. */
+int kta_merge_compress_whatif(uint64_t *acc, const uint64_t *other, uint32_t n_partitions);
+/* 1 when the identities between the words of one vector hold, 0 when not (host only): the codec table's sums equal the
+ * partitions' sums; per partition stored_blocks <= blocks, match_bytes <= raw_bytes, model_bytes <= raw_bytes + 11 batches +
+ * 4 blocks, match_bytes >= 4 sequences. */
+int kta_compress_whatif_identities(const uint64_t *vec, uint32_t n_partitions);
+
 /* Compaction what-if (context created with KTA_FLAG_COMPACTION; definition above KTA_FLAG_COMPACTION).  In replay mode a
  * device batch without key columns is refused (KTA_ERR_INVALID, "key columns missing (KTA_FLAG_COMPACTION)") before
  * anything is launched.  The vector is the context's own: kta_finish_device takes no snapshot of it and no exchange reduces
@@ -1542,6 +1584,17 @@ int kta_render_header_names(const uint64_t *vec, const kta_header_name *table, u
  *    zstd win on JSON, is not in it; and a closing `=` rule.
  * A share whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
 int kta_render_value_bytes(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
+/* The opt-in compression what-if section that kta-analyzer prints behind the value-byte section's position with --librdkafka
+ * kta.compress_whatif=lz4, from a what-if vector (host only):
+ *   a title line that names the knob and says that it is not part of the reference report;
+ *   a table (P | Batches | Record bytes/batch | Record bytes | On disk now | Now ratio | LZ4 model | Model ratio | Saving vs
+ *    now % | Stored blocks % | Match %), a row per partition and a `Topic` row of their sum: the ratios are record bytes over
+ *    the bytes with two decimals, the saving is 1 - model / now, the match share is of the record bytes;
+ *   a table by the batches' current codec (Codec | Batches | Record bytes | On disk now | Now ratio | LZ4 model | Model ratio);
+ *   notes: the model in one sentence; it is a floor; the 61 header bytes are on neither side; the ratio is at the topic's
+ *    present batching; and a closing `=` rule.
+ * A figure whose denominator is 0 prints `n/a`.  Output buffer conventions as kta_render_report. */
+int kta_render_compress_whatif(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len);
 int kta_render_filter(int64_t from_ms, int64_t to_ms, const uint32_t *partition_bitmap, uint32_t n_partitions, uint64_t seen,
                       uint64_t passed, char *out, size_t out_cap, size_t *out_len);
 

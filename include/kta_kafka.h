@@ -38,7 +38,9 @@
  * (KTA_FLAG_RECORD_BATCHES, kta_hip.h), from the descriptors and the headers of every decode call; what lies inside the
  * records — value formats, schema-registry ids, record headers — by the opt-in payload section (KTA_FLAG_PAYLOAD); which
  * header names those are by the opt-in header-name section (KTA_FLAG_HEADER_NAMES); what bytes the values are made of — a
- * histogram per partition, behind the payload and header-name passes — by the opt-in value-byte section (KTA_FLAG_VALUE_BYTES).
+ * histogram per partition, behind the payload and header-name passes — by the opt-in value-byte section (KTA_FLAG_VALUE_BYTES);
+ * what `compression.type=lz4` would leave of every batch's records section — a defined LZ4 compressor run over the inflated
+ * bytes while they are resident — by the opt-in compression what-if (KTA_FLAG_COMPRESS_WHATIF).
  */
 #ifndef KTA_KAFKA_H
 #define KTA_KAFKA_H
@@ -113,6 +115,15 @@ int kta_kafka_index_host(const uint8_t *bytes, uint64_t len, int32_t partition, 
 int64_t kta_snappy_inflate_host(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap);
 /* LZ4 frame inflate on the host (the same code the device runs).  Returns the bytes produced or -1. */
 int64_t kta_lz4_inflate_host(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap);
+/* The compression what-if's model compressor (KTA_FLAG_COMPRESS_WHATIF, kta_hip.h; csrc/kta_lz4_model.h states it): the LZ4
+ * frame of src[0, n) with independent blocks of at most 65536 bytes, written to dst[0, cap).  Returns the frame's size — with
+ * dst == NULL only that; with a dst that is too small the size it needs, dst then holds its first cap bytes — or -1 for a
+ * NULL src with n > 0. */
+int64_t kta_lz4_model_host(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap);
+/* The compression what-if's rule on the host, for tests and the CPU suite, as kta_value_bytes_host: the batches of
+ * bytes[0, len), compressed ones inflated, added to vec[KTA_COMPRESS_WHATIF_WORDS(P)].  A partition outside [0, P) adds
+ * nothing.  No filter. */
+int kta_compress_whatif_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t n_partitions);
 /* zstd (one or more frames) inflate on the host (the same code the device runs).  Returns the bytes produced or -1. */
 int64_t kta_zstd_inflate_host(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap);
 /* The same with the table layout of the device's wave-per-batch kernel, where the Huffman table lies over the
@@ -231,6 +242,12 @@ int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms);
  * 32-bit bin could overflow, since creation / kta_reset.  *avg_ms (may be NULL): the pass kernel's mean duration over the
  * timed launches, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute stream. */
 int kta_value_bytes_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
+
+/* The compression what-if's pass (KTA_FLAG_COMPRESS_WHATIF, kta_hip.h): out[0] launches, out[1] batches, out[2] the
+ * workgroups of the last launch, out[3] the timed launches, since the context was created.  *avg_ms (may be NULL): the pass
+ * kernel's mean duration over the timed launches, -1 without one (needs kta_set_timing(ctx, 1)).  Waits for the compute
+ * stream. */
+int kta_compress_whatif_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms);
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,9 @@ __all__ = ["HipMetricHandler", "MessageMetrics", "LogCompactionInMemoryMetrics",
            "payload_identities", "payload_schema_ids", "payload_host", "render_payload", "PAYLOAD_COLUMNS", "PAYLOAD_CLASSES",
            "split_header_names", "merge_header_names", "header_names_identities", "header_names_list", "header_names_host",
            "render_header_names", "HEADER_NAME_DTYPE", "HEADER_NAMES_GLOBALS", "split_value_bytes", "merge_value_bytes",
-           "value_bytes_identities", "value_bytes_summary", "value_bytes_host", "render_value_bytes", "VALUE_BYTES_CLASSES"]
+           "value_bytes_identities", "value_bytes_summary", "value_bytes_host", "render_value_bytes", "VALUE_BYTES_CLASSES",
+           "split_compress_whatif", "merge_compress_whatif", "compress_whatif_identities", "compress_whatif_host", "render_compress_whatif",
+           "lz4_model", "lz4_model_size", "COMPRESS_WHATIF_COLUMNS", "COMPRESS_WHATIF_CODECS", "COMPRESS_WHATIF_CODEC_COLUMNS"]
 
 U64_MAX = 0xFFFFFFFFFFFFFFFF
 
@@ -97,6 +99,8 @@ _SECTIONS = {
     "payload": (lambda P: 24 * P + 16 + 2 * 1024 * 34, "a payload vector of {} partitions"),
     "header_names": (lambda: N.KTA_HEADER_NAMES_WORDS, "a header-name vector"),
     "value_bytes": (lambda P: N.KTA_VALUE_BYTES_PARTITION_WORDS * P, "a value-byte vector of {} partitions"),
+    "compress_whatif": (lambda P: N.KTA_COMPRESS_WHATIF_PARTITION_WORDS * P + N.KTA_COMPRESS_WHATIF_CODECS * N.KTA_COMPRESS_WHATIF_CODEC_WORDS,
+                        "a compression what-if vector of {} partitions"),
     "compaction": (lambda P: N.KTA_COMPACTION_WORDS * P + N.KTA_COMPACTION_GLOBALS, "a compaction vector of {} partitions"),
     "compact_delete": (lambda P, M: segments_words(P, M), "a kept vector of {} partitions and {} rows"),
 }
@@ -148,7 +152,7 @@ class HipMetricHandler:
                  hot_keys: bool = False, ts_order: bool = False, partitioner: bool = False, repartition: Optional[int] = None,
                  compaction: bool = False, size_quantiles: bool = False, segments: Optional[Tuple[int, int, int]] = None,
                  compact_delete: bool = False, record_batches: bool = False, payload: bool = False, header_names: bool = False,
-                 value_bytes: bool = False):
+                 value_bytes: bool = False, compress_whatif: bool = False):
         """alive_table: keep the alive set as the sequence-numbered table (KTA_FLAG_ALIVE_TABLE: batches / shards in
         any order, needed by a rank of a sharded run) instead of the reference's bit set (submission order);
         seq_column: the staging batches carry every record's global sequence number (KTA_FLAG_SEQ_COLUMN);
@@ -173,7 +177,9 @@ class HipMetricHandler:
         header_names: the header-name section (KTA_FLAG_HEADER_NAMES: a census of the names of the record headers of the raw-log
         decode, header_names() and header_name_table());
         value_bytes: the value-byte section (KTA_FLAG_VALUE_BYTES: a byte histogram of the values of the records of the raw-log
-        decode per partition, value_bytes())."""
+        decode per partition, value_bytes());
+        compress_whatif: the compression what-if (KTA_FLAG_COMPRESS_WHATIF: the bytes a defined LZ4 compressor would leave of the
+        records section of every batch of the raw-log decode, compress_whatif())."""
         self._lib = N.load()
         self._ctx = C.c_void_p()
         self.n_partitions = int(n_partitions)
@@ -187,6 +193,7 @@ class HipMetricHandler:
         self.payload_on = bool(payload)
         self.header_names_on = bool(header_names)
         self.value_bytes_on = bool(value_bytes)
+        self.compress_whatif_on = bool(compress_whatif)
         cfg = KtaConfig(device, n_partitions, 1 if count_alive_keys else 0, n_staging, batch_capacity,
                         key_bytes_capacity, (N.KTA_FLAG_ANALYTICS if analytics else 0) |
                         (N.KTA_FLAG_KEY_SKETCH if key_sketch else 0) | (N.KTA_FLAG_HOT_KEYS if hot_keys else 0) |
@@ -194,6 +201,7 @@ class HipMetricHandler:
                         (N.KTA_FLAG_COMPACTION if compaction else 0) | (N.KTA_FLAG_SIZE_QUANTILES if size_quantiles else 0) |
                         (N.KTA_FLAG_RECORD_BATCHES if record_batches else 0) | (N.KTA_FLAG_PAYLOAD if payload else 0) |
                         (N.KTA_FLAG_HEADER_NAMES if header_names else 0) | (N.KTA_FLAG_VALUE_BYTES if value_bytes else 0) |
+                        (N.KTA_FLAG_COMPRESS_WHATIF if compress_whatif else 0) |
                         (N.KTA_FLAG_ALIVE_TABLE if alive_table else 0) | (N.KTA_FLAG_SEQ_COLUMN if seq_column else 0), 0)
         rc = self._lib.kta_create(C.byref(cfg), C.byref(self._ctx))
         if rc != N.KTA_OK:
@@ -830,6 +838,31 @@ class HipMetricHandler:
         out, ms = (C.c_uint64 * 4)(), C.c_float()
         self._check(self._lib.kta_value_bytes_info(self._ctx, C.byref(out), C.byref(ms)))
         return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "mid_flushes": int(out[3]),
+                "kernel_ms": float(ms.value) if ms.value >= 0 else None}
+
+    def compress_whatif(self) -> dict:
+        """The live compression what-if vector as split_compress_whatif gives it (kta_get_compress_whatif; staged messages are
+        flushed first)."""
+        return split_compress_whatif(self._read_section("compress_whatif", self._lib.kta_get_compress_whatif), self.n_partitions)
+
+    def exchange_compress_whatif(self) -> dict:
+        """As compress_whatif(), of the snapshot finish() / exchange() took: after exchange(), the whole job's."""
+        return split_compress_whatif(self._read_section("compress_whatif", self._lib.kta_exchange_compress_whatif), self.n_partitions)
+
+    def compress_whatif_result_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the what-if snapshot (for collectives: allreduce_compress_whatif_vector)."""
+        return self._device_vector(self._lib.kta_compress_whatif_result_vector)
+
+    def compress_whatif_vector(self) -> Tuple[int, int]:
+        """(device pointer, length in u64) of the live what-if vector."""
+        return self._device_vector(self._lib.kta_compress_whatif_vector)
+
+    def compress_whatif_info(self) -> dict:
+        """The what-if pass's work since creation (kta_compress_whatif_info): launches, batches, the workgroups of the last
+        launch, the timed launches; kernel_ms their mean duration (None without one: set_timing(True))."""
+        out, ms = (C.c_uint64 * 4)(), C.c_float()
+        self._check(self._lib.kta_compress_whatif_info(self._ctx, C.byref(out), C.byref(ms)))
+        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
                 "kernel_ms": float(ms.value) if ms.value >= 0 else None}
 
     def size_quantiles_info(self) -> dict:
@@ -1484,6 +1517,71 @@ def value_bytes_host(blob: bytes, partition: int, n_partitions: int, vec=None) -
 def render_value_bytes(vec, n_partitions: int) -> str:
     """kta_render_value_bytes: the section kta-analyzer prints with --librdkafka kta.value_bytes=1."""
     return _render(N.load().kta_render_value_bytes, _np_ptr(_section_vec("value_bytes", vec, n_partitions)), n_partitions)
+
+
+COMPRESS_WHATIF_COLUMNS = ("batches", "blocks", "stored_blocks", "raw_bytes", "now_bytes", "model_bytes", "sequences", "match_bytes")
+COMPRESS_WHATIF_CODECS = ("none", "gzip", "snappy", "lz4", "zstd")
+COMPRESS_WHATIF_CODEC_COLUMNS = ("batches", "raw_bytes", "now_bytes", "model_bytes")
+
+
+def split_compress_whatif(vec, n_partitions: int) -> dict:
+    """A compression what-if vector u64[8 P + 20] as a dict, split by its layout (kta_hip.h, above KTA_FLAG_COMPRESS_WHATIF):
+    "partitions" [P][8] (COMPRESS_WHATIF_COLUMNS), "topic" [8] their sum, "codecs" [5][4] (COMPRESS_WHATIF_CODECS by
+    COMPRESS_WHATIF_CODEC_COLUMNS); the vector under "vector"."""
+    P = n_partitions
+    v = _section_vec("compress_whatif", vec, P)
+    pw = N.KTA_COMPRESS_WHATIF_PARTITION_WORDS
+    parts = v[:pw * P].reshape(P, pw).copy()
+    return {"partitions": parts, "topic": parts.sum(axis=0, dtype=np.uint64),
+            "codecs": v[pw * P:].reshape(N.KTA_COMPRESS_WHATIF_CODECS, N.KTA_COMPRESS_WHATIF_CODEC_WORDS).copy(), "vector": v}
+
+
+def merge_compress_whatif(acc: np.ndarray, other, n_partitions: int) -> np.ndarray:
+    """kta_merge_compress_whatif, in place on `acc` (contiguous uint64 / int64): every word a sum."""
+    return _merge("compress_whatif", acc, other, n_partitions)
+
+
+def compress_whatif_identities(vec, n_partitions: int) -> bool:
+    """kta_compress_whatif_identities: whether the identities between the words of one what-if vector hold."""
+    rc = N.load().kta_compress_whatif_identities(_np_ptr(_section_vec("compress_whatif", vec, n_partitions)), n_partitions)
+    if rc < 0:
+        raise KtaError(rc, "kta_compress_whatif_identities")
+    return rc == 1
+
+
+def compress_whatif_host(blob: bytes, partition: int, n_partitions: int, vec=None) -> np.ndarray:
+    """kta_compress_whatif_host: the section's rule over the batches of `blob` on the host (compressed batches inflated), added
+    to `vec` (a new vector when None)."""
+    v = np.zeros(_section_words("compress_whatif", n_partitions), np.uint64) if vec is None else _section_vec("compress_whatif", vec, n_partitions)
+    rc = N.load().kta_compress_whatif_host(bytes(blob), len(blob), int(partition), _np_ptr(v), n_partitions)
+    if rc != N.KTA_OK:
+        raise KtaError(rc, "kta_compress_whatif_host")
+    return v
+
+
+def render_compress_whatif(vec, n_partitions: int) -> str:
+    """kta_render_compress_whatif: the section kta-analyzer prints with --librdkafka kta.compress_whatif=lz4."""
+    return _render(N.load().kta_render_compress_whatif, _np_ptr(_section_vec("compress_whatif", vec, n_partitions)), n_partitions)
+
+
+def lz4_model_size(data: bytes) -> int:
+    """kta_lz4_model_host without a destination: the size of the model compressor's frame of `data` (one records section)."""
+    data = bytes(data)
+    n = int(N.load().kta_lz4_model_host(data, len(data), None, 0))
+    if n < 0:
+        raise KtaError(N.KTA_ERR_INVALID, "kta_lz4_model_host")
+    return n
+
+
+def lz4_model(data: bytes) -> bytes:
+    """kta_lz4_model_host: the model compressor's frame of `data` (one records section), an LZ4 frame any decoder reads."""
+    data = bytes(data)
+    n = lz4_model_size(data)
+    out = (C.c_uint8 * n)()
+    got = int(N.load().kta_lz4_model_host(data, len(data), out, n))
+    if got != n:
+        raise KtaError(N.KTA_ERR_INVALID, "kta_lz4_model_host")
+    return bytes(out)
 
 
 def size_bin(size: int) -> int:

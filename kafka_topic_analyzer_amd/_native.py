@@ -77,6 +77,10 @@ KTA_HEADER_NAMES_WORDS, KTA_HEADER_NAMES_SLOTS, KTA_HEADER_NAME_BYTES, KTA_HEADE
 KTA_FLAG_VALUE_BYTES = 4096
 KTA_VALUE_BYTES_BINS, KTA_VALUE_BYTES_PARTITION_WORDS = 256, 264
 KTA_VALUE_BYTES_NONE, KTA_VALUE_BYTES_TEXT, KTA_VALUE_BYTES_DENSE, KTA_VALUE_BYTES_BINARY = 0, 1, 2, 3
+# compression what-if vector: u64[8 P + 20] = [P][8: batches, blocks, stored_blocks, raw_bytes, now_bytes, model_bytes, sequences,
+# match_bytes] | [5 codecs][4: batches, raw_bytes, now_bytes, model_bytes]
+KTA_FLAG_COMPRESS_WHATIF = 8192
+KTA_COMPRESS_WHATIF_PARTITION_WORDS, KTA_COMPRESS_WHATIF_CODECS, KTA_COMPRESS_WHATIF_CODEC_WORDS = 8, 5, 4
 KTA_TS_ORDER_HIST = 63            # timestamp-order vector: u64[3 P + 64] = [P][2] | hist[63] | timed | max_late_ms[P]
 KTA_HOT_ROWS, KTA_HOT_CELLS, KTA_HOT_WORDS = 2, 1024, 23
 KTA_HOT_VECTOR_WORDS = KTA_HOT_ROWS * KTA_HOT_CELLS * KTA_HOT_WORDS   # hot-key vector: u64[2][1024][23]
@@ -310,6 +314,16 @@ SIGNATURES = {
     "kta_value_bytes_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint32]),
     "kta_value_bytes_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
     "kta_render_value_bytes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_get_compress_whatif": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_exchange_compress_whatif": (C.c_int, [_P, C.c_void_p, C.c_size_t]),
+    "kta_compress_whatif_result_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_compress_whatif_vector": (C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "kta_merge_compress_whatif": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "kta_compress_whatif_identities": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "kta_compress_whatif_host": (C.c_int, [C.c_char_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint32]),
+    "kta_compress_whatif_info": (C.c_int, [_P, C.POINTER(C.c_uint64 * 4), C.POINTER(C.c_float)]),
+    "kta_render_compress_whatif": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kta_lz4_model_host": (C.c_int64, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64]),
     "kta_render_size_percentiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kta_set_segments": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint32]),
     "kta_segments_words": (C.c_uint32, [C.c_uint32, C.c_uint32]),

@@ -24,7 +24,7 @@ ORACLE_LIB = os.path.join(ORACLE_DIR, "libkta_oracle.so")
 HIP_SOURCES = ["kta_kernels.hip", "kta_alive_table.hip", "kta_alive.hip", "kta_api.hip", "kta_comm.hip", "kta_synth.hip",
                "kta_kafka.hip", "kta_sketch.hip", "kta_hot.hip", "kta_ts_order.hip", "kta_partitioner.hip", "kta_filter.hip",
                "kta_compaction.hip", "kta_size_quantiles.hip", "kta_segments.hip", "kta_record_batches.hip", "kta_payload.hip",
-               "kta_header_names.hip", "kta_value_bytes.hip"]
+               "kta_header_names.hip", "kta_value_bytes.hip", "kta_lz4_model.hip"]
 LIB_HOST_SOURCES = ["host/metric.cpp", "host/report.cpp", "host/kafka_encode.cpp"]  # C++ host mirror, inside libkta_hip.so
 HOST_SOURCES = ["host/main.cpp", "host/rdkafka_source.cpp"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",

@@ -55,6 +55,10 @@
 // kta.value_bytes=1 (0: off; the same sources and refusals as kta.payload=1, with or without it) runs the value-byte pass as well
 // (KTA_FLAG_VALUE_BYTES) and prints its section behind the header-name section's position: per partition and for the topic a
 // byte histogram's read-off — H0, the order-0 floor, the printable, zero, high-bit and repeat shares and a class.
+// kta.compress_whatif=lz4 (the same sources and refusals as kta.payload=1, with or without the sections above; any other value
+// is refused) runs the compression what-if as well (KTA_FLAG_COMPRESS_WHATIF) and prints its section behind the value-byte
+// section's position: per partition, for the topic and by the batches' current codec the bytes a defined LZ4 compressor would
+// leave of the records sections, beside what they take on disk now.
 // kta.ts_order=1 (0: off; every source, kta.per_message=1 and kta.gpus=N included) runs the timestamp-order pass as well
 // (KTA_FLAG_TS_ORDER; no reference counterpart) and prints, after those sections and before the hot keys, the late records
 // per partition — older than one their partition delivered before them — and a histogram of their lateness.
@@ -375,6 +379,7 @@ struct ShardedJob {
     bool payload = false;                              // kta.payload=1: likewise (segment:// only)
     bool headers = false;                              // kta.headers=1: likewise (segment:// only); the name tables stay on their ranks
     bool value_bytes = false;                          // kta.value_bytes=1: likewise (segment:// only)
+    bool compress_whatif = false;                      // kta.compress_whatif=lz4: likewise (segment:// only)
     FilterConfig filter;                              // kta.from / kta.to / kta.partitions: the same on every rank
     SegmentsConfig segments;                           // kta.segments=<size>: every rank's context (a partition's records stay on one rank)
     uint64_t n_records = 0;
@@ -394,7 +399,8 @@ void run_rank(const ShardedJob &job, int rank, const uint8_t *uid, int ndev, kta
                                (job.hot_keys ? KTA_FLAG_HOT_KEYS : 0u) | (job.ts_order ? KTA_FLAG_TS_ORDER : 0u) |
                                (job.partitioner ? KTA_FLAG_PARTITIONER : 0u) | (job.percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) |
                                (job.record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) | (job.payload ? KTA_FLAG_PAYLOAD : 0u) |
-                               (job.headers ? KTA_FLAG_HEADER_NAMES : 0u) | (job.value_bytes ? KTA_FLAG_VALUE_BYTES : 0u);
+                               (job.headers ? KTA_FLAG_HEADER_NAMES : 0u) | (job.value_bytes ? KTA_FLAG_VALUE_BYTES : 0u) |
+                               (job.compress_whatif ? KTA_FLAG_COMPRESS_WHATIF : 0u);
         const bool keys = job.count_alive || job.distinct_keys || job.hot_keys || job.partitioner;   // the staging batches carry key_off / key_bytes
         kta::HipMetricHandler *h = new kta::HipMetricHandler((int32_t)job.P, job.count_alive, (job.device + rank) % ndev,
                                                              job.batch, 0, flags, job.timeline, job.repartition);
@@ -590,6 +596,7 @@ int run_sharded(ShardedJob &job, const std::chrono::steady_clock::time_point sta
             text += kta::render_header_names(h0->header_names()->data(), merged.data(), kHeaderNamesShown);
         }
         if (job.value_bytes) text += kta::render_value_bytes(h0->value_bytes()->data(), job.P);
+        if (job.compress_whatif) text += kta::render_compress_whatif(h0->compress_whatif()->data(), job.P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);
@@ -682,6 +689,21 @@ int main(int argc, char **argv)
         value_bytes = v == "1";
         if (value_bytes && (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1"))) {   // before a broker or a device is asked for anything
             fprintf(stderr, "kta.value_bytes=1: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
+                            "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
+            return 2;
+        }
+    }
+    // kta.compress_whatif: likewise; the value names the codec asked about, and lz4 is the one there is a model of
+    bool compress_whatif = false;
+    if (cfg.count("kta.compress_whatif")) {
+        const std::string &v = cfg["kta.compress_whatif"];
+        if (v != "lz4") {
+            fprintf(stderr, "kta.compress_whatif=%s: expected lz4 (the codec the what-if has a model of)\n", v.c_str());
+            return 2;
+        }
+        compress_whatif = true;
+        if (!segment || (cfg.count("kta.per_message") && cfg["kta.per_message"] == "1")) {   // before a broker or a device is asked for anything
+            fprintf(stderr, "kta.compress_whatif=lz4: needs a segment:// source without kta.per_message=1 (synthetic://, dump://, a broker "
                             "list and kta.per_message=1 deliver records, not the bytes of the log)\n");
             return 2;
         }
@@ -1079,6 +1101,7 @@ int main(int argc, char **argv)
         job.payload = payload;
         job.headers = headers;
         job.value_bytes = value_bytes;
+        job.compress_whatif = compress_whatif;
         std::copy(rb_skipped, rb_skipped + 3, job.rb_skipped);
         job.filter = filter;
         job.segments = segments;
@@ -1103,7 +1126,7 @@ int main(int argc, char **argv)
                                                 (partitioner ? KTA_FLAG_PARTITIONER : 0u) | (compaction ? KTA_FLAG_COMPACTION : 0u) |
                                                 (percentiles ? KTA_FLAG_SIZE_QUANTILES : 0u) | (record_batches ? KTA_FLAG_RECORD_BATCHES : 0u) |
                                                 (payload ? KTA_FLAG_PAYLOAD : 0u) | (headers ? KTA_FLAG_HEADER_NAMES : 0u) |
-                                                (value_bytes ? KTA_FLAG_VALUE_BYTES : 0u),
+                                                (value_bytes ? KTA_FLAG_VALUE_BYTES : 0u) | (compress_whatif ? KTA_FLAG_COMPRESS_WHATIF : 0u),
                                             timeline, repartition);
     } catch (const std::exception &e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1355,6 +1378,7 @@ int main(int argc, char **argv)
         if (payload) text += kta::render_payload(handler->payload()->data(), partitioner_counters(metrics, P).data(), P);
         if (headers) text += kta::render_header_names(handler->header_names()->data(), handler->header_name_table()->data(), kHeaderNamesShown);
         if (value_bytes) text += kta::render_value_bytes(handler->value_bytes()->data(), P);
+        if (compress_whatif) text += kta::render_compress_whatif(handler->compress_whatif()->data(), P);
         fputs(text.c_str(), stdout);
     } catch (const kta::RustPanic &p) {
         rust_panic(p.what(), p.location);

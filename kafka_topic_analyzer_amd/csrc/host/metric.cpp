@@ -76,7 +76,8 @@ HipMetricHandler::HipMetricHandler(int32_t n_partitions, bool count_alive_keys, 
       tso_on_((flags & KTA_FLAG_TS_ORDER) != 0), part_on_((flags & KTA_FLAG_PARTITIONER) != 0),
       part_q_(part_on_ ? (repartition ? repartition : (uint32_t)n_partitions) : 0u), sizeq_on_((flags & KTA_FLAG_SIZE_QUANTILES) != 0),
       rb_on_((flags & KTA_FLAG_RECORD_BATCHES) != 0), pl_on_((flags & KTA_FLAG_PAYLOAD) != 0),
-      hn_on_((flags & KTA_FLAG_HEADER_NAMES) != 0), vb_on_((flags & KTA_FLAG_VALUE_BYTES) != 0)
+      hn_on_((flags & KTA_FLAG_HEADER_NAMES) != 0), vb_on_((flags & KTA_FLAG_VALUE_BYTES) != 0),
+      cw_on_((flags & KTA_FLAG_COMPRESS_WHATIF) != 0)
 {
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);  // Utc::now() (metric.rs:39)
@@ -236,6 +237,10 @@ void HipMetricHandler::read_analytics()
     if (vb_on_) {
         yvec_.assign(KTA_VALUE_BYTES_WORDS(P_), 0);
         check(kta_exchange_value_bytes(ctx_, yvec_.data(), yvec_.size()), "kta_exchange_value_bytes");
+    }
+    if (cw_on_) {
+        wvec_.assign(KTA_COMPRESS_WHATIF_WORDS(P_), 0);
+        check(kta_exchange_compress_whatif(ctx_, wvec_.data(), wvec_.size()), "kta_exchange_compress_whatif");
     }
     if (seg_rows_) {
         gvec_.assign(kta_segments_words((uint32_t)P_, seg_rows_), 0);

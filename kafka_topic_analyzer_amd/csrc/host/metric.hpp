@@ -159,6 +159,8 @@ public:
     const std::vector<kta_header_name> *header_name_table() const { return hn_on_ ? &ntab_ : nullptr; }
     // With KTA_FLAG_VALUE_BYTES: the value-byte vector u64[264 P] of that snapshot; nullptr without the flag.
     const std::vector<uint64_t> *value_bytes() const { return vb_on_ ? &yvec_ : nullptr; }
+    // With KTA_FLAG_COMPRESS_WHATIF: the compression what-if vector u64[8 P + 20] of that snapshot; nullptr without the flag.
+    const std::vector<uint64_t> *compress_whatif() const { return cw_on_ ? &wvec_ : nullptr; }
     // The segment pass of the retention what-if (kta_set_segments): right after construction, before any record; then the
     // segment vector u64[(P M + P) 4 + 8] of the snapshot finish() / exchange() took (after exchange(), the whole job's);
     // nullptr without it.
@@ -212,6 +214,8 @@ private:
     std::vector<kta_header_name> ntab_;
     bool vb_on_ = false;
     std::vector<uint64_t> yvec_;
+    bool cw_on_ = false;
+    std::vector<uint64_t> wvec_;
     uint32_t seg_rows_ = 0;   // M; 0: no segments
     std::vector<uint64_t> gvec_;
 };
@@ -254,6 +258,8 @@ std::string render_payload(const uint64_t *vec, const uint64_t *counters, uint32
 std::string render_header_names(const uint64_t *vec, const kta_header_name *table, uint32_t max_names);
 // (kta_render_value_bytes): vec u64[264 P]
 std::string render_value_bytes(const uint64_t *vec, uint32_t P);
+// (kta_render_compress_whatif): vec u64[8 P + 20]
+std::string render_compress_whatif(const uint64_t *vec, uint32_t P);
 // the opt-in section kta-analyzer prints with kta.segments=<size> after the partitioner and compaction sections and before
 // the filter's (kta_render_retention): vec u64[(P M + P) 4 + 8]; retention -1: the rule is off
 std::string render_retention(const uint64_t *vec, uint32_t P, uint32_t M, int64_t now_ms, int64_t retention_ms, int64_t retention_bytes);

@@ -15,6 +15,7 @@
 #include "kta_record_batches.h"
 #include "kta_segments.h"
 #include "kta_value_bytes.h"
+#include "kta_lz4_model.h"
 #include "kta_size_bins.h"
 #include "metric.hpp"
 
@@ -899,7 +900,72 @@ std::string render_value_bytes(const uint64_t *vec, uint32_t P)
     return o;
 }
 
+// The opt-in compression what-if section (kta.compress_whatif=lz4): no reference counterpart, printed behind the value-byte
+// section's position.  vec: u64[8 P + 20] (kta_hip.h; the layout is kta_lz4_model.h's).
+std::string render_compress_whatif(const uint64_t *vec, uint32_t P)
+{
+    auto ratio = [](uint64_t num, uint64_t den, double scale) -> std::string {
+        if (den == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", (double)num * scale / (double)den);
+        return buf;
+    };
+    auto saving = [](uint64_t model, uint64_t now) -> std::string {            // 1 - model / now, in percent; negative: larger
+        if (now == 0) return "n/a";
+        char buf[48];
+        snprintf(buf, sizeof buf, "%.2f", 100.0 - (double)model * 100.0 / (double)now);
+        return buf;
+    };
+    auto row_of = [&](const std::string &name, const uint64_t *w) {
+        return std::vector<std::string>{name, std::to_string(w[kCwBatches]), ratio(w[kCwRawBytes], w[kCwBatches], 1.0), std::to_string(w[kCwRawBytes]),
+                                        std::to_string(w[kCwNowBytes]), ratio(w[kCwRawBytes], w[kCwNowBytes], 1.0), std::to_string(w[kCwModelBytes]),
+                                        ratio(w[kCwRawBytes], w[kCwModelBytes], 1.0), saving(w[kCwModelBytes], w[kCwNowBytes]),
+                                        ratio(w[kCwStoredBlocks], w[kCwBlocks], 100.0), ratio(w[kCwMatchBytes], w[kCwRawBytes], 100.0)};
+    };
+    std::string o;
+    o += "Compression what-if: what compression.type=lz4 would leave of the record bytes (kta.compress_whatif=lz4; not part of the reference report)\n";
+    std::vector<std::vector<std::string>> rows;
+    rows.push_back({"P", "Batches", "Record bytes/batch", "Record bytes", "On disk now", "Now ratio", "LZ4 model", "Model ratio", "Saving vs now %",
+                    "Stored blocks %", "Match %"});
+    for (uint32_t p = 0; p < P; p++) rows.push_back(row_of(std::to_string(p), vec + (size_t)kCwPartitionWords * p));
+    uint64_t topic[kCwPartitionWords];
+    compress_whatif_topic(vec, P, topic);
+    rows.push_back(row_of("Topic", topic));
+    o += pretty_table(rows);
+    o += "By the batches' current codec:\n";
+    std::vector<std::vector<std::string>> codecs;
+    codecs.push_back({"Codec", "Batches", "Record bytes", "On disk now", "Now ratio", "LZ4 model", "Model ratio"});
+    for (uint32_t c = 0; c < kCwCodecs; c++) {
+        const uint64_t *w = vec + (size_t)kCwPartitionWords * P + (size_t)kCwCodecWords * c;
+        codecs.push_back({compress_whatif_codec_name(c), std::to_string(w[kCwCodecBatches]), std::to_string(w[kCwCodecRawBytes]),
+                          std::to_string(w[kCwCodecNowBytes]), ratio(w[kCwCodecRawBytes], w[kCwCodecNowBytes], 1.0), std::to_string(w[kCwCodecModelBytes]),
+                          ratio(w[kCwCodecRawBytes], w[kCwCodecModelBytes], 1.0)});
+    }
+    o += pretty_table(codecs);
+    o += "The model is an LZ4 frame of every batch's inflated record bytes: independent blocks of 64 KiB, a greedy match finder with a table of 4096 "
+         "positions that is looked up 64 positions at a time, a block that does not shrink stored.\n";
+    o += "It is a floor of what compression would win: liblz4 itself finds matches the model does not see, gzip and zstd do better still.\n";
+    o += "The 61 header bytes of a batch are on neither side: record bytes, on disk now and the model are all without them.\n";
+    o += "The ratios hold at the topic's present batching: small batches compress badly (see Record bytes/batch), and a larger batch.size or "
+         "linger.ms would change them.\n";
+    o += std::string(120, '=') + "\n";
+    return o;
+}
+
 }  // namespace kta
+
+extern "C" int kta_render_compress_whatif(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len)
+{
+    if (!vec || !out_len || n_partitions == 0) return KTA_ERR_INVALID;
+    const std::string text = kta::render_compress_whatif(vec, n_partitions);
+    *out_len = text.size();
+    if (out && out_cap > 0) {
+        const size_t n = std::min(out_cap - 1, text.size());
+        memcpy(out, text.data(), n);
+        out[n] = 0;
+    }
+    return KTA_OK;
+}
 
 extern "C" int kta_render_value_bytes(const uint64_t *vec, uint32_t n_partitions, char *out, size_t out_cap, size_t *out_len)
 {

@@ -15,6 +15,7 @@
 #include "kta_segments.h"
 #include "kta_size_bins.h"
 #include "kta_value_bytes.h"
+#include "kta_lz4_model.h"
 
 #include <limits.h>
 #include <math.h>
@@ -153,6 +154,10 @@ struct kta_ctx {
     bool vb = false;
     int vb_variant = 0;
     DeviceBuf<uint64_t> d_vb, d_vb_out, d_vb_info;
+    // compression what-if (KTA_FLAG_COMPRESS_WHATIF): d_cw u64[8 P + 20] the live vector that the decode call adds to
+    // (kta_internal_compress_whatif), d_cw_out its snapshot
+    bool cw = false;
+    DeviceBuf<uint64_t> d_cw, d_cw_out;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
     // slice's three launches (allocated at the first filtered batch), h_filter_total the slice's total as the host reads
     // it, and the scratch batch the passing records go to (raw layout; grows to the largest slice seen)
@@ -904,6 +909,7 @@ Shape record_batches_shape(uint32_t P) { return Shape{kta::rb_len(P), kta::rb_su
 Shape payload_shape(uint32_t P) { return all_sum(kta::payload_len(P)); }
 Shape header_names_shape() { return all_sum(kta::kHnWords); }
 Shape value_bytes_shape(uint32_t P) { return all_sum(kta::value_bytes_len(P)); }
+Shape compress_whatif_shape(uint32_t P) { return all_sum(kta::compress_whatif_len(P)); }
 Shape compaction_shape(uint32_t P) { return all_sum(kta::compaction_len(P)); }   // (live only: nothing reduces it)
 
 // what include/kta_hip.h says of these shapes in macros, for the callers that size their buffers by them
@@ -940,6 +946,10 @@ static_assert(KTA_VALUE_BYTES_PARTITION_WORDS == kta::kVbPartitionWords && KTA_V
 static_assert(KTA_VALUE_BYTES_NONE == kta::kVbNone && KTA_VALUE_BYTES_TEXT == kta::kVbText && KTA_VALUE_BYTES_DENSE == kta::kVbDense &&
                   KTA_VALUE_BYTES_BINARY == kta::kVbBinary,
               "the classes: kta_value_bytes.h and kta_hip.h");
+static_assert(KTA_COMPRESS_WHATIF_PARTITION_WORDS == kta::kCwPartitionWords && KTA_COMPRESS_WHATIF_CODECS == kta::kCwCodecs &&
+                  KTA_COMPRESS_WHATIF_CODEC_WORDS == kta::kCwCodecWords && KTA_COMPRESS_WHATIF_WORDS(7) == 8 * 7 + 20 &&
+                  kta::kCwBatchHeader == KTA_KAFKA_BATCH_HEADER,
+              "kta_lz4_model.h, kta_hip.h and kta_kafka.h");
 
 // One section of the result as the host layer handles it: a row of sections_of, which states every section once.  live
 // and out point at the context's owners, allocated or not.
@@ -980,6 +990,8 @@ void sections_of(kta_ctx *ctx, Section s[KTA_SEC_KINDS])
                                       "context was created without KTA_FLAG_HEADER_NAMES"};
     s[KTA_RV_VALUE_BYTES] = Section{ctx->vb, &ctx->d_vb, &ctx->d_vb_out, value_bytes_shape(P), true, "value-byte vector",
                                      "context was created without KTA_FLAG_VALUE_BYTES"};
+    s[KTA_RV_COMPRESS_WHATIF] = Section{ctx->cw, &ctx->d_cw, &ctx->d_cw_out, compress_whatif_shape(P), true, "compression what-if vector",
+                                         "context was created without KTA_FLAG_COMPRESS_WHATIF"};
     s[KTA_SEC_COMPACTION] = Section{ctx->comp, &ctx->d_comp, nullptr, compaction_shape(P), true, "compaction vector",
                                     "context was created without KTA_FLAG_COMPACTION"};
     s[KTA_SEC_KEPT] = Section{ctx->cd, &ctx->d_kept, nullptr, segments_shape(P, ctx->seg_M), false, "kept vector",
@@ -1198,9 +1210,9 @@ void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS])
 }
 
 // The batches of bytes[0, len) that count on the host, as kta_kafka_index_host finds them, compressed ones inflated:
-// batch(record bytes, their length, n_records) for each.  A stream that does not inflate is a failed batch: skipped.
+// batch(descriptor, record bytes, their length) for each.  A stream that does not inflate is a failed batch: skipped.
 template <class OnBatch>
-static int host_batches(const uint8_t *bytes, uint64_t len, int32_t partition, OnBatch batch)
+static int host_batches_described(const uint8_t *bytes, uint64_t len, int32_t partition, OnBatch batch)
 {
     kta_kafka_index_stats st;
     int rc = kta_kafka_index_host(bytes, len, partition, 0, 0, (len + 127) & ~63ull, nullptr, 0, &st);
@@ -1214,7 +1226,7 @@ static int host_batches(const uint8_t *bytes, uint64_t len, int32_t partition, O
         const uint8_t *src = bytes + d.byte_off + KTA_KAFKA_BATCH_HEADER;
         const uint64_t n = d.batch_bytes - KTA_KAFKA_BATCH_HEADER;
         if (!(d.flags & (KTA_KB_SNAPPY | KTA_KB_LZ4 | KTA_KB_GZIP | KTA_KB_ZSTD))) {
-            batch(src, n, (uint64_t)d.n_records);
+            batch(d, src, n);
             continue;
         }
         const uint64_t cap = d.payload_end > d.payload_off ? d.payload_end - d.payload_off : 0;   // the index's bound (exact for gzip and Snappy)
@@ -1224,9 +1236,17 @@ static int host_batches(const uint8_t *bytes, uint64_t len, int32_t partition, O
                             : (d.flags & KTA_KB_GZIP) ? kta_gzip_inflate_host(src, n, inflated.data(), cap)
                                                       : kta_zstd_inflate_host(src, n, inflated.data(), cap);
         if (got < 0) continue;
-        batch(inflated.data(), (uint64_t)got, (uint64_t)d.n_records);
+        batch(d, inflated.data(), (uint64_t)got);
     }
     return KTA_OK;
+}
+
+// The same for a caller that needs the records alone: batch(record bytes, their length, n_records).
+template <class OnBatch>
+static int host_batches(const uint8_t *bytes, uint64_t len, int32_t partition, OnBatch batch)
+{
+    return host_batches_described(bytes, len, partition,
+                                  [&](const kta_kafka_batch_desc &d, const uint8_t *recs, uint64_t n) { batch(recs, n, (uint64_t)d.n_records); });
 }
 
 extern "C" {
@@ -1315,6 +1335,7 @@ int kta_create(const kta_config *cfg, kta_ctx **out)
     ctx->pl = (cfg->flags & KTA_FLAG_PAYLOAD) != 0;
     ctx->hn = (cfg->flags & KTA_FLAG_HEADER_NAMES) != 0;
     ctx->vb = (cfg->flags & KTA_FLAG_VALUE_BYTES) != 0;
+    ctx->cw = (cfg->flags & KTA_FLAG_COMPRESS_WHATIF) != 0;
     {
         const char *bv = getenv("KTA_VALUE_BYTES_VARIANT");   // A/B switch of tools/bench_value_bytes.py: 1 every byte its own LDS add, 2 all pairs
         ctx->vb_variant = bv && (bv[0] == '1' || bv[0] == '2') && !bv[1] ? bv[0] - '0' : 0;
@@ -2548,6 +2569,50 @@ int kta_value_bytes_host(const uint8_t *bytes, uint64_t len, int32_t partition, 
     });
 }
 
+// ---- compression what-if (kta_lz4_model.h holds the model and the rule, kta_lz4_model.hip the kernel, kta_kafka.hip the launch)
+
+int kta_get_compress_whatif(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return get_section(ctx, KTA_RV_COMPRESS_WHATIF, out, n_u64); }
+int kta_exchange_compress_whatif(kta_ctx *ctx, uint64_t *out, size_t n_u64) { return exchange_section(ctx, KTA_RV_COMPRESS_WHATIF, out, n_u64); }
+int kta_compress_whatif_result_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_COMPRESS_WHATIF, true, device_ptr, n_u64);
+}
+int kta_compress_whatif_vector(kta_ctx *ctx, void **device_ptr, size_t *n_u64)
+{
+    return section_vector(ctx, KTA_RV_COMPRESS_WHATIF, false, device_ptr, n_u64);
+}
+int kta_merge_compress_whatif(uint64_t *acc, const uint64_t *other, uint32_t P)
+{
+    return merge_section(acc, other, P != 0, compress_whatif_shape(P));
+}
+
+int kta_compress_whatif_identities(const uint64_t *vec, uint32_t P)
+{
+    if (!vec || P == 0) return KTA_ERR_INVALID;
+    return kta::compress_whatif_identities_hold(vec, P) ? 1 : 0;
+}
+
+int64_t kta_lz4_model_host(const uint8_t *src, uint64_t n, uint8_t *dst, uint64_t cap)
+{
+    if (!src && n) return -1;
+    std::vector<uint32_t> table(kta::kLz4mTable);
+    if (!dst) {
+        kta::Lz4mCount out;
+        return (int64_t)kta::lz4m_frame(src, n, table.data(), out).frame_bytes;
+    }
+    kta::Lz4mEmit out{dst, cap};
+    return (int64_t)kta::lz4m_frame(src, n, table.data(), out).frame_bytes;
+}
+
+int kta_compress_whatif_host(const uint8_t *bytes, uint64_t len, int32_t partition, uint64_t *vec, uint32_t P)
+{
+    if (!bytes || !vec || P == 0) return KTA_ERR_INVALID;
+    if (partition < 0 || (uint32_t)partition >= P) return KTA_OK;             // outside [0, P): adds nothing
+    return host_batches_described(bytes, len, partition, [&](const kta_kafka_batch_desc &d, const uint8_t *recs, uint64_t n) {
+        kta::compress_whatif_add(vec, P, (uint32_t)partition, kta::compress_whatif_codec(d.flags), d.batch_bytes, recs, n);
+    });
+}
+
 // ---- compaction what-if (kta_compaction.h holds the rule, kta_compaction.hip the kernel) --------------------------------
 
 int kta_compaction_max_partitions(void) { return (int)kta::kCompactionMaxPartitions; }
@@ -3108,6 +3173,13 @@ bool kta_internal_value_bytes(kta_ctx *ctx, kta_internal_vb *out)
     *out = kta_internal_vb{ctx->vb, ctx->d_vb.get(), ctx->d_vb_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
                            f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count, ctx->vb_variant};
     return ctx->vb && !ctx->comp_replay;
+}
+bool kta_internal_compress_whatif(kta_ctx *ctx, kta_internal_cw *out)
+{
+    const bool f = ctx->filter;
+    *out = kta_internal_cw{ctx->cw, ctx->d_cw.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
+                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
+    return ctx->cw && !ctx->comp_replay;
 }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {

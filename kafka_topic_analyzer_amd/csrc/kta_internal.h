@@ -109,6 +109,21 @@ namespace kta {
 hipError_t launch_value_bytes(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
                               const uint32_t *bitmap, uint64_t *vec, uint64_t *info, int cu_count, int variant, uint32_t *workgroups, hipStream_t s);
 }
+// The compression what-if (KTA_FLAG_COMPRESS_WHATIF) as the decode call sees it: as kta_internal_rb — the section is about
+// whole batches, and the window is the record-batch section's.
+struct kta_internal_cw {
+    bool on;
+    uint64_t *vec;   // the live vector (device)
+    int64_t from_ms, to_ms;
+    const uint32_t *bitmap;
+    int cu_count;
+};
+bool kta_internal_compress_whatif(kta_ctx *ctx, kta_internal_cw *out);
+// The pass (kta_lz4_model.hip), as launch_value_bytes.
+namespace kta {
+hipError_t launch_lz4_model(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
+                            const uint32_t *bitmap, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s);
+}
 // Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
 // allocation that the range overlaps become raw (partition, ts_ms and, in a keyless allocation, the lengths), on the
 // compute stream.
@@ -151,6 +166,7 @@ int kta_internal_resolve(kta_ctx *ctx, const kta_batch *d, kta_internal_columns 
 //   payload     24*P + 69648       all            none
 //   hdr. names  73736              all            none   (the name table beside it stays on its rank)
 //   value bytes 264*P              all            none
+//   compr. w.-if 8*P + 20          all            none
 //   compaction  5*P + 6            (live only: the replay's vector, kta_get_compaction)
 //   kept        (P*M + P)*4 + 8    (live only: the replay's kept vector, kta_get_compact_delete; the segments' shape)
 struct ResultVector {
@@ -160,7 +176,7 @@ struct ResultVector {
 };
 enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH, KTA_RV_HOT_KEYS, KTA_RV_TS_ORDER, KTA_RV_PARTITIONER,
        KTA_RV_SIZE_QUANTILES, KTA_RV_SEGMENTS, KTA_RV_RECORD_BATCHES, KTA_RV_PAYLOAD, KTA_RV_HEADER_NAMES, KTA_RV_VALUE_BYTES,
-       KTA_RV_KINDS,
+       KTA_RV_COMPRESS_WHATIF, KTA_RV_KINDS,
        KTA_SEC_COMPACTION = KTA_RV_KINDS, KTA_SEC_KEPT, KTA_SEC_KINDS };
 // The snapshot kinds of the section table; a section that is off has out == nullptr and words == 0.
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);

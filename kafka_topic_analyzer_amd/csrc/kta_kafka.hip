@@ -1176,6 +1176,9 @@ struct KafkaState {
     TimerPool<1> vb_timers{1024};   // the value-byte pass (kta_value_bytes_info)
     uint64_t vb_launches = 0, vb_batches = 0;
     uint32_t vb_workgroups = 0;     // of the last launch
+    TimerPool<1> cw_timers{1024};   // the compression what-if's pass (kta_compress_whatif_info)
+    uint64_t cw_launches = 0, cw_batches = 0;
+    uint32_t cw_workgroups = 0;     // of the last launch
 };
 
 void free_out(kta_batch &o)
@@ -1688,7 +1691,17 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
         if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
         st->vb_launches++, st->vb_batches += n_batches;
     }
-    KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));          // the descriptors' buffer is free once these kernels are done
+    // The compression what-if (KTA_FLAG_COMPRESS_WHATIF): the same moment and the same bytes, every inflated records section
+    // resident: what the model compressor would leave of each.
+    if (kta_internal_cw cw{}; kta_internal_compress_whatif(ctx, &cw)) {
+        if (timing) { int rc = st->cw_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        KTA_HIP_AS(ctx, kta::launch_lz4_model(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), cw.from_ms, cw.to_ms, cw.bitmap, cw.vec,
+                                              cw.cu_count, &st->cw_workgroups, s),
+                   "kta_lz4_model");
+        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
+        st->cw_launches++, st->cw_batches += n_batches;
+    }
+    KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));         // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
         KTA_HIP(ctx, hipMemcpyAsync(scal, d_scalars, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         KTA_HIP(ctx, hipStreamSynchronize(s));
@@ -2000,6 +2013,24 @@ int kta_value_bytes_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
     KTA_HIP(ctx, hipMemcpyAsync(work, vb.info, sizeof work, hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
     KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
     out[0] = st->vb_launches, out[1] = st->vb_batches, out[2] = st->vb_workgroups, out[3] = work[0];
+    if (avg_ms) *avg_ms = timed ? ms : -1.f;
+    return KTA_OK;
+}
+
+int kta_compress_whatif_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_cw cw{};
+    (void)kta_internal_compress_whatif(ctx, &cw);
+    if (!cw.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_COMPRESS_WHATIF");
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    KafkaState *st = state_of(ctx);
+    float ms = -1.f;
+    uint64_t timed = 0;
+    int rc = st->cw_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
+    out[0] = st->cw_launches, out[1] = st->cw_batches, out[2] = st->cw_workgroups, out[3] = timed;
     if (avg_ms) *avg_ms = timed ? ms : -1.f;
     return KTA_OK;
 }

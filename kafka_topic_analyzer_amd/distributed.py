@@ -147,6 +147,14 @@ def allreduce_value_bytes_vector(yvec, n_partitions: int, group=None) -> None:
     _allreduce_sum_max(yvec, yvec.numel(), group)
 
 
+def allreduce_compress_whatif_vector(wvec, n_partitions: int, group=None) -> None:
+    """In-place exchange of an int64 view of the compression what-if SNAPSHOT (kta_compress_whatif_result_vector: device
+    tensor, or a CPU tensor in the tests) — what kta_exchange does natively when the contexts have KTA_FLAG_COMPRESS_WHATIF:
+    one all-reduce SUM over all 8 * P + 20 words (i64 wrap == u64 wrap)."""
+    assert wvec.numel() == 8 * n_partitions + 20
+    _allreduce_sum_max(wvec, wvec.numel(), group)
+
+
 def allreduce_segments_vector(gvec, n_partitions: int, rows_per_partition: int, group=None) -> None:
     """In-place exchange of an int64 view of the segment SNAPSHOT (kta_segments_result_vector: device tensor, or a CPU
     tensor in the tests) — what kta_exchange does natively for contexts with segments (kta_set_segments): all-reduce SUM

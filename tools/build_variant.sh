@@ -10,7 +10,7 @@ csrc=kafka_topic_analyzer_amd/csrc
 obj=$(mktemp -d)
 trap 'rm -rf "$obj"' EXIT
 common="-O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -I include -I $csrc"
-for s in kta_kernels kta_alive_table kta_alive kta_api kta_comm kta_synth kta_kafka kta_sketch kta_hot kta_ts_order kta_partitioner kta_filter kta_compaction kta_size_quantiles kta_segments kta_record_batches kta_payload kta_header_names kta_value_bytes; do   # (build.py: HIP_SOURCES)
+for s in kta_kernels kta_alive_table kta_alive kta_api kta_comm kta_synth kta_kafka kta_sketch kta_hot kta_ts_order kta_partitioner kta_filter kta_compaction kta_size_quantiles kta_segments kta_record_batches kta_payload kta_header_names kta_value_bytes kta_lz4_model; do   # (build.py: HIP_SOURCES)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 $common "$@" -c $csrc/$s.hip -o $obj/$s.o &
 done
 for s in metric report kafka_encode; do

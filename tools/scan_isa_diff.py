@@ -23,7 +23,7 @@ OLD, NEW = "EEEvNS_11ScanColumnsEmjjPmj", "EJEEEvNS_11ScanColumnsEmjjPmjDpT3_"
 SOURCES = ("kta_kernels.hip", "kta_alive_table.hip", "kta_alive.hip", "kta_sketch.hip", "kta_hot.hip", "kta_kafka.hip",
            "kta_synth.hip", "kta_ts_order.hip", "kta_partitioner.hip", "kta_filter.hip", "kta_compaction.hip",
            "kta_size_quantiles.hip", "kta_segments.hip", "kta_record_batches.hip", "kta_payload.hip", "kta_header_names.hip",
-           "kta_value_bytes.hip")
+           "kta_value_bytes.hip", "kta_lz4_model.hip")
 RESOURCES = ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size")
 # The bound on a changed kernel's instruction lines, as a fraction of the base tree's: the largest change that
 # profiles/r14_scan_isa_diff.txt shows among the kernels that only had the tile codec's functions moved (the TILED scan
