@@ -142,6 +142,10 @@ def _merge(name: str, acc: np.ndarray, other, *shape) -> np.ndarray:
     return acc
 
 
+# the words every kta_*_info of a pass of the decode call begins with (HipMetricHandler._pass_info)
+_PASS_INFO_KEYS = ("launches", "batches", "workgroups", "timed")
+
+
 class HipMetricHandler:
     """Owns one `kta_ctx`.  `handle_message` == MetricHandler::handle_message (kafka.rs:18-20)."""
 
@@ -490,6 +494,15 @@ class HipMetricHandler:
         self._check(self._lib.kta_comm_info(self._ctx, C.byref(nr), C.byref(rk), C.byref(se), C.byref(re)))
         return nr.value, rk.value, se.value, re.value
 
+    def _pass_info(self, fn, keys) -> dict:
+        """What the kta_*_info of a pass of the decode call reports: its words under `keys` (None: a word without a meaning) and
+        kernel_ms, the mean duration of the launches timed since the previous call (None without one)."""
+        out, ms = (C.c_uint64 * len(keys))(), C.c_float()
+        self._check(fn(self._ctx, C.byref(out), C.byref(ms)))
+        info = {k: int(v) for k, v in zip(keys, out) if k}
+        info["kernel_ms"] = float(ms.value) if ms.value >= 0 else None
+        return info
+
     def _device_vector(self, fn) -> Tuple[int, int]:
         """What a `(kta_ctx *, void **device_ptr, size_t *n_u64)` entry point answers."""
         p, n = C.c_void_p(), C.c_size_t()
@@ -752,10 +765,7 @@ class HipMetricHandler:
     def record_batches_info(self) -> dict:
         """The record-batch pass's work since creation (kta_record_batches_info); kernel_ms is the mean duration of the
         launches timed since the previous call, None without one (set_timing(True))."""
-        out, ms = (C.c_uint64 * 4)(), C.c_float()
-        self._check(self._lib.kta_record_batches_info(self._ctx, C.byref(out), C.byref(ms)))
-        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
-                "kernel_ms": float(ms.value) if out[3] else None}
+        return self._pass_info(self._lib.kta_record_batches_info, _PASS_INFO_KEYS)
 
     def get_payload(self) -> dict:
         """The live payload vector as split_payload gives it (kta_get_payload; staged messages are flushed first)."""
@@ -776,10 +786,7 @@ class HipMetricHandler:
     def payload_info(self) -> dict:
         """The payload pass's work since creation (kta_payload_info); kernel_ms is the mean duration of the launches timed
         since the previous call, None without one (set_timing(True))."""
-        out, ms = (C.c_uint64 * 4)(), C.c_float()
-        self._check(self._lib.kta_payload_info(self._ctx, C.byref(out), C.byref(ms)))
-        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
-                "kernel_ms": float(ms.value) if out[3] else None}
+        return self._pass_info(self._lib.kta_payload_info, _PASS_INFO_KEYS)
 
     def header_names(self) -> dict:
         """The live header-name vector as split_header_names gives it, with this context's name table (kta_get_header_names;
@@ -810,10 +817,7 @@ class HipMetricHandler:
         """The header-name pass's work (kta_header_names_info): launches, batches, workgroups and timed launches since creation;
         spills (occurrences that went past the workgroup's cache), claims and early cache flushes since creation / reset();
         kernel_ms as payload_info's."""
-        out, ms = (C.c_uint64 * 8)(), C.c_float()
-        self._check(self._lib.kta_header_names_info(self._ctx, C.byref(out), C.byref(ms)))
-        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]), "spills": int(out[4]),
-                "claims": int(out[5]), "cache_flushes": int(out[6]), "kernel_ms": float(ms.value) if out[3] else None}
+        return self._pass_info(self._lib.kta_header_names_info, _PASS_INFO_KEYS + ("spills", "claims", "cache_flushes", None))
 
     def value_bytes(self) -> dict:
         """The live value-byte vector as split_value_bytes gives it: the vector, the partitions' words and the summaries per
@@ -835,10 +839,7 @@ class HipMetricHandler:
     def value_bytes_info(self) -> dict:
         """The value-byte pass's work (kta_value_bytes_info): launches, batches and workgroups since creation; mid_flushes, the
         flushes of a workgroup's bins in the middle of a pass, since creation / reset(); kernel_ms as payload_info's."""
-        out, ms = (C.c_uint64 * 4)(), C.c_float()
-        self._check(self._lib.kta_value_bytes_info(self._ctx, C.byref(out), C.byref(ms)))
-        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "mid_flushes": int(out[3]),
-                "kernel_ms": float(ms.value) if ms.value >= 0 else None}
+        return self._pass_info(self._lib.kta_value_bytes_info, _PASS_INFO_KEYS[:3] + ("mid_flushes",))
 
     def compress_whatif(self) -> dict:
         """The live compression what-if vector as split_compress_whatif gives it (kta_get_compress_whatif; staged messages are
@@ -860,10 +861,7 @@ class HipMetricHandler:
     def compress_whatif_info(self) -> dict:
         """The what-if pass's work since creation (kta_compress_whatif_info): launches, batches, the workgroups of the last
         launch, the timed launches; kernel_ms their mean duration (None without one: set_timing(True))."""
-        out, ms = (C.c_uint64 * 4)(), C.c_float()
-        self._check(self._lib.kta_compress_whatif_info(self._ctx, C.byref(out), C.byref(ms)))
-        return {"launches": int(out[0]), "batches": int(out[1]), "workgroups": int(out[2]), "timed": int(out[3]),
-                "kernel_ms": float(ms.value) if ms.value >= 0 else None}
+        return self._pass_info(self._lib.kta_compress_whatif_info, _PASS_INFO_KEYS)
 
     def size_quantiles_info(self) -> dict:
         """The plan of the size-percentile pass for this context and its work since creation / reset() (kta_size_quantiles_info)."""

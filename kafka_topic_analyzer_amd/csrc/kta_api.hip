@@ -135,27 +135,27 @@ struct kta_ctx {
     uint32_t sizeq_slice = 0, sizeq_last_workgroups = 0;
     int sizeq_variant = 0;
     // record batches (KTA_FLAG_RECORD_BATCHES): d_rb u64[20 P + 1524] the live vector that kta_kafka.hip's decode call adds to
-    // (kta_internal_record_batches), d_rb_out its snapshot
+    // (kta_internal_blob_pass), d_rb_out its snapshot
     bool rb = false;
     DeviceBuf<uint64_t> d_rb, d_rb_out;
-    // payload (KTA_FLAG_PAYLOAD): d_pl u64[24 P + 69648] the live vector that the decode call adds to (kta_internal_payload),
+    // payload (KTA_FLAG_PAYLOAD): d_pl u64[24 P + 69648] the live vector that the decode call adds to (kta_internal_blob_pass),
     // d_pl_out its snapshot
     bool pl = false;
     DeviceBuf<uint64_t> d_pl, d_pl_out;
     // header names (KTA_FLAG_HEADER_NAMES): d_hn u64[73736] the live vector that the decode call adds to
-    // (kta_internal_header_names), d_hn_out its snapshot, d_hn_names the name table beside it (not snapshotted, not exchanged),
+    // (kta_internal_blob_pass), d_hn_out its snapshot, d_hn_names the name table beside it (not snapshotted, not exchanged),
     // d_hn_info the pass's work counters
     bool hn = false;
     DeviceBuf<uint64_t> d_hn, d_hn_out, d_hn_info;
     DeviceBuf<kta_header_name> d_hn_names;
-    // value bytes (KTA_FLAG_VALUE_BYTES): d_vb u64[264 P] the live vector that the decode call adds to (kta_internal_value_bytes),
+    // value bytes (KTA_FLAG_VALUE_BYTES): d_vb u64[264 P] the live vector that the decode call adds to (kta_internal_blob_pass),
     // d_vb_out its snapshot, d_vb_info the pass's work counters, vb_variant the launch form (KTA_VALUE_BYTES_VARIANT: 0, or 1
     // of tools/bench_value_bytes.py)
     bool vb = false;
     int vb_variant = 0;
     DeviceBuf<uint64_t> d_vb, d_vb_out, d_vb_info;
     // compression what-if (KTA_FLAG_COMPRESS_WHATIF): d_cw u64[8 P + 20] the live vector that the decode call adds to
-    // (kta_internal_compress_whatif), d_cw_out its snapshot
+    // (kta_internal_blob_pass), d_cw_out its snapshot
     bool cw = false;
     DeviceBuf<uint64_t> d_cw, d_cw_out;
     // record filter (kta_set_filter): the window and the set, d_filter_bitmap the set's ceil(P / 32) words, the workspace of a
@@ -3146,41 +3146,25 @@ uint32_t kta_internal_partitions(kta_ctx *ctx) { return ctx->P; }
 uint64_t *kta_internal_table(kta_ctx *ctx) { return ctx->d_table.get(); }
 bool kta_internal_alive_table(kta_ctx *ctx) { return ctx->alive_table; }
 bool kta_internal_compaction(kta_ctx *ctx) { return ctx->comp; }
-bool kta_internal_record_batches(kta_ctx *ctx, kta_internal_rb *out)
+bool kta_internal_blob_pass(kta_ctx *ctx, int kind, kta_internal_pass *out)
+{
+    switch (kind) {
+    case KTA_PASS_RECORD_BATCHES: *out = kta_internal_pass{ctx->rb, ctx->d_rb.get(), nullptr, nullptr, 0}; break;
+    case KTA_PASS_PAYLOAD: *out = kta_internal_pass{ctx->pl, ctx->d_pl.get(), nullptr, nullptr, 0}; break;
+    case KTA_PASS_HEADER_NAMES: *out = kta_internal_pass{ctx->hn, ctx->d_hn.get(), ctx->d_hn_info.get(), ctx->d_hn_names.get(), 0}; break;
+    case KTA_PASS_VALUE_BYTES: *out = kta_internal_pass{ctx->vb, ctx->d_vb.get(), ctx->d_vb_info.get(), nullptr, ctx->vb_variant}; break;
+    case KTA_PASS_COMPRESS_WHATIF: *out = kta_internal_pass{ctx->cw, ctx->d_cw.get(), nullptr, nullptr, 0}; break;
+    default: *out = kta_internal_pass{false, nullptr, nullptr, nullptr, 0}; break;
+    }
+    return out->on && !ctx->comp_replay;
+}
+kta_internal_pass_env kta_internal_blob_pass_env(kta_ctx *ctx)
 {
     const bool f = ctx->filter;
-    *out = kta_internal_rb{ctx->rb, ctx->d_rb.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
-                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
-    return ctx->rb && !ctx->comp_replay;
+    return kta_internal_pass_env{f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
+                                 f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
 }
-bool kta_internal_payload(kta_ctx *ctx, kta_internal_pl *out)
-{
-    const bool f = ctx->filter;
-    *out = kta_internal_pl{ctx->pl, ctx->d_pl.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
-                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
-    return ctx->pl && !ctx->comp_replay;
-}
-bool kta_internal_header_names(kta_ctx *ctx, kta_internal_hn *out)
-{
-    const bool f = ctx->filter;
-    *out = kta_internal_hn{ctx->hn, ctx->d_hn.get(), ctx->d_hn_names.get(), ctx->d_hn_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN,
-                           f ? ctx->filter_spec.to_ms : INT64_MAX, f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
-    return ctx->hn && !ctx->comp_replay;
-}
-bool kta_internal_value_bytes(kta_ctx *ctx, kta_internal_vb *out)
-{
-    const bool f = ctx->filter;
-    *out = kta_internal_vb{ctx->vb, ctx->d_vb.get(), ctx->d_vb_info.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
-                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count, ctx->vb_variant};
-    return ctx->vb && !ctx->comp_replay;
-}
-bool kta_internal_compress_whatif(kta_ctx *ctx, kta_internal_cw *out)
-{
-    const bool f = ctx->filter;
-    *out = kta_internal_cw{ctx->cw, ctx->d_cw.get(), f ? ctx->filter_spec.from_ms : INT64_MIN, f ? ctx->filter_spec.to_ms : INT64_MAX,
-                           f && ctx->filter_spec.parts ? ctx->d_filter_bitmap.get() : nullptr, ctx->cu_count};
-    return ctx->cw && !ctx->comp_replay;
-}
+int kta_internal_section_off(kta_ctx *ctx, int kind) { return section_off(ctx, kind); }
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out)
 {
     *out = kta::WrittenList{ctx->d_written.get(), ctx->d_written_n.get(), ctx->d_written.size()};

@@ -1,7 +1,8 @@
 // kta_internal.h — what the host code of libkta_hip.so shares between its translation units (kta_api.hip,
 // kta_comm.hip, kta_kafka.hip, kta_synth.hip): the context's internal accessors, the HIP-error macro, the owners
-// of device and pinned memory, streams and events, the event-pair timing pool and the description of the result
-// vectors.  Host code only; not installed, not part of the ABI.  The library is linked with -z defs: a
+// of device and pinned memory, streams and events, the event-pair timing pool, the description of the result
+// vectors and the blob passes of the decode call (a new pass: a kind and a launch function there, a row in
+// kta_kafka.hip's table).  Host code only; not installed, not part of the ABI.  The library is linked with -z defs: a
 // declaration here without a definition fails the build.
 #pragma once
 
@@ -18,7 +19,6 @@
 
 namespace kta {
 struct WrittenList;   // kta_kernels.h
-struct RbFilter;      // kta_record_batches.h
 }
 
 // ---- the context, as the other translation units see it (defined in kta_api.hip) ----------------------------------
@@ -40,89 +40,61 @@ uint64_t *kta_internal_table(kta_ctx *ctx);
 int64_t *kta_internal_running(kta_ctx *ctx);
 bool kta_internal_written(kta_ctx *ctx, kta::WrittenList *out);
 uint64_t kta_internal_take_seq(kta_ctx *ctx, uint64_t n);
-// The record-batch section (KTA_FLAG_RECORD_BATCHES) as the decode call sees it.  Returns whether the pass runs now: the flag
-// on and no compaction replay (the replay reads the source a second time; batches are counted once).  on: the flag alone.
-// from_ms / to_ms / bitmap: the context's filter (kta_set_filter: INT64_MIN / INT64_MAX no bound; the partition set on the
-// device, null without one).
-struct kta_internal_rb {
-    bool on;
-    uint64_t *vec;   // the live vector (device)
-    int64_t from_ms, to_ms;
-    const uint32_t *bitmap;
-    int cu_count;
+// ---- the blob passes ------------------------------------------------------------------------------------------------
+// The passes that the decode call (kta_kafka.hip's kta_kafka_decode_device) runs over its descriptors and blob behind the
+// decode kernel, one per opt-in section, in the order they are enqueued on the stream.  A new pass adds a kind here, a case
+// in kta_internal_blob_pass, a launch function of the signature below and a row in kta_kafka.hip's table (blob_passes): the
+// decode call's loop, the timers and the pass's kta_*_info go by that row.
+enum kta_blob_pass_kind {
+    KTA_PASS_RECORD_BATCHES = 0,   // KTA_FLAG_RECORD_BATCHES  (kta_record_batches.hip)
+    KTA_PASS_PAYLOAD,              // KTA_FLAG_PAYLOAD         (kta_payload.hip)
+    KTA_PASS_HEADER_NAMES,         // KTA_FLAG_HEADER_NAMES    (kta_header_names.hip)
+    KTA_PASS_VALUE_BYTES,          // KTA_FLAG_VALUE_BYTES     (kta_value_bytes.hip)
+    KTA_PASS_COMPRESS_WHATIF,      // KTA_FLAG_COMPRESS_WHATIF (kta_lz4_model.hip)
+    KTA_PASS_KINDS
 };
-bool kta_internal_record_batches(kta_ctx *ctx, kta_internal_rb *out);
-// The pass over `n` descriptors (device memory, after the call's inflate and decode kernels) and the blob they index
-// (kta_record_batches.hip); f.bitmap on the device.  *workgroups = the grid.
-namespace kta {
-hipError_t launch_record_batches(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint64_t blob_len, uint32_t P,
-                                 const RbFilter &f, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s);
-}
-// The payload section (KTA_FLAG_PAYLOAD) as the decode call sees it: as kta_internal_record_batches — returns whether the pass
-// runs now (the flag on and no compaction replay), on: the flag alone, the context's filter as that struct states it.
-struct kta_internal_pl {
-    bool on;
+// What the decode call needs of a pass.  info: the pass's work counters u64[4] on the device (header names: spills, claims,
+// cache flushes, 0; value bytes: mid-pass flushes, partition flushes, 0, 0), null where the pass has none.  names: the
+// header-name section's table kta_header_name[2][1024] on the device, null for every other pass.  variant: the form of the
+// value-byte pass's LDS add, the A/B switch of tools/bench_value_bytes.py (KTA_VALUE_BYTES_VARIANT, read when a context is
+// created): 0 a dword of four equal bytes is one add, 1 every byte its own add, 2 whichever bytes of a dword are equal are
+// added once; 0 for every other pass.
+struct kta_internal_pass {
+    bool on;         // the section's flag alone
     uint64_t *vec;   // the live vector (device)
-    int64_t from_ms, to_ms;
-    const uint32_t *bitmap;
-    int cu_count;
-};
-bool kta_internal_payload(kta_ctx *ctx, kta_internal_pl *out);
-// The pass over the records of `n` descriptors (device memory, after the call's inflate and decode kernels) and the blob
-// they index, its inflate area included (kta_payload.hip; blob 16-byte aligned); bitmap on the device.  *workgroups = the grid.
-namespace kta {
-hipError_t launch_payload(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                          const uint32_t *bitmap, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s);
-}
-// The header-name section (KTA_FLAG_HEADER_NAMES) as the decode call sees it: as kta_internal_payload; names the name table
-// kta_header_name[2][1024] and info the pass's work counters u64[4] (spills, claims, cache flushes, 0), both on the device.
-struct kta_internal_hn {
-    bool on;
-    uint64_t *vec;   // the live vector (device)
+    uint64_t *info;
     void *names;
-    uint64_t *info;
+    int variant;
+};
+// Returns whether the pass runs now: the flag on and no compaction replay (the replay reads the source a second time;
+// batches and records are counted once).
+bool kta_internal_blob_pass(kta_ctx *ctx, int kind, kta_internal_pass *out);
+// The context's filter (kta_set_filter: INT64_MIN / INT64_MAX no bound; the partition set on the device, null without one)
+// and its device's compute units, the same for every pass.
+struct kta_internal_pass_env {
     int64_t from_ms, to_ms;
     const uint32_t *bitmap;
     int cu_count;
 };
-bool kta_internal_header_names(kta_ctx *ctx, kta_internal_hn *out);
-// The pass (kta_header_names.hip), as launch_payload.
+kta_internal_pass_env kta_internal_blob_pass_env(kta_ctx *ctx);
+// One pass over `n` descriptors (device memory, after the call's inflate and decode kernels) and the blob they index, its
+// inflate area included.  Each launch function reads the fields it uses, checks them (the record walks want the blob
+// 16-byte aligned) and has its own grid rule.  *workgroups = the grid.
 namespace kta {
-hipError_t launch_header_names(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                               const uint32_t *bitmap, uint64_t *vec, void *names, uint64_t *info, int cu_count, uint32_t *workgroups, hipStream_t s);
-}
-// The value-byte section (KTA_FLAG_VALUE_BYTES) as the decode call sees it: as kta_internal_payload; info the pass's work
-// counters u64[4] (mid-pass flushes, partition flushes, 0, 0) on the device; variant: the form of the LDS add, the A/B switch
-// of tools/bench_value_bytes.py (KTA_VALUE_BYTES_VARIANT, read when a context is created): 0 a dword of four equal bytes is
-// one add, 1 every byte its own add, 2 whichever bytes of a dword are equal are added once.
-struct kta_internal_vb {
-    bool on;
-    uint64_t *vec;   // the live vector (device)
-    uint64_t *info;
-    int64_t from_ms, to_ms;
+struct BlobPassArgs {
+    const kta_kafka_batch_desc *descs;
+    uint64_t n;
+    const uint8_t *blob;
+    uint64_t blob_len;
+    uint32_t P;
+    int64_t from_ms, to_ms;   // kta_internal_pass_env
     const uint32_t *bitmap;
+    uint64_t *vec, *info;     // kta_internal_pass
+    void *names;
     int cu_count, variant;
 };
-bool kta_internal_value_bytes(kta_ctx *ctx, kta_internal_vb *out);
-// The pass (kta_value_bytes.hip), as launch_payload.
-namespace kta {
-hipError_t launch_value_bytes(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                              const uint32_t *bitmap, uint64_t *vec, uint64_t *info, int cu_count, int variant, uint32_t *workgroups, hipStream_t s);
-}
-// The compression what-if (KTA_FLAG_COMPRESS_WHATIF) as the decode call sees it: as kta_internal_rb — the section is about
-// whole batches, and the window is the record-batch section's.
-struct kta_internal_cw {
-    bool on;
-    uint64_t *vec;   // the live vector (device)
-    int64_t from_ms, to_ms;
-    const uint32_t *bitmap;
-    int cu_count;
-};
-bool kta_internal_compress_whatif(kta_ctx *ctx, kta_internal_cw *out);
-// The pass (kta_lz4_model.hip), as launch_value_bytes.
-namespace kta {
-hipError_t launch_lz4_model(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                            const uint32_t *bitmap, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s);
+typedef hipError_t BlobPassLaunch(const BlobPassArgs &a, uint32_t *workgroups, hipStream_t s);
+BlobPassLaunch launch_record_batches, launch_payload, launch_header_names, launch_value_bytes, launch_lz4_model;
 }
 // Before a producer stores the raw layout into records [0, n) of a device batch: the tiles of a tile-compact
 // allocation that the range overlaps become raw (partition, ts_ms and, in a keyless allocation, the lengths), on the
@@ -180,6 +152,8 @@ enum { KTA_RV_COUNTERS = 0, KTA_RV_ANALYTICS, KTA_RV_TIMELINE, KTA_RV_KEY_SKETCH
        KTA_SEC_COMPACTION = KTA_RV_KINDS, KTA_SEC_KEPT, KTA_SEC_KINDS };
 // The snapshot kinds of the section table; a section that is off has out == nullptr and words == 0.
 void kta_internal_result_vectors(kta_ctx *ctx, ResultVector rv[KTA_RV_KINDS]);
+// The refusal of an entry point whose section (a kind above) is off: KTA_ERR_INVALID with the section table's message.
+int kta_internal_section_off(kta_ctx *ctx, int kind);
 
 // ---- errors -------------------------------------------------------------------------------------------------------
 static inline int fail(kta_ctx *ctx, int code, const std::string &msg) { return kta_internal_fail(ctx, code, msg); }

@@ -1143,6 +1143,29 @@ struct BlobStage {
     bool busy = false;
 };
 
+// What the decode call keeps of one blob pass (kta_internal.h) for the pass's kta_*_info.
+struct BlobPassState {
+    TimerPool<1> timers{1024};
+    uint64_t launches = 0, batches = 0;
+    uint32_t workgroups = 0;   // of the last launch
+};
+
+// The passes of a decode call behind its decode kernel, a row per kind, in the order they are enqueued: the descriptors are
+// final there — status, the inflated sizes — and they and the blob, whose inflate area holds the inflated batches, are still
+// alive.  name: what a failed launch is reported under; section: the result section that owns the pass's "off" message.
+struct BlobPassRow {
+    kta::BlobPassLaunch *launch;
+    const char *name;
+    int section;
+};
+const BlobPassRow blob_passes[KTA_PASS_KINDS] = {
+    {kta::launch_record_batches, "kta_record_batches", KTA_RV_RECORD_BATCHES},   // what the batch headers say
+    {kta::launch_payload, "kta_payload", KTA_RV_PAYLOAD},                        // what lies inside the records
+    {kta::launch_header_names, "kta_header_names", KTA_RV_HEADER_NAMES},         // the names of the record headers
+    {kta::launch_value_bytes, "kta_value_bytes", KTA_RV_VALUE_BYTES},            // the bytes of every value
+    {kta::launch_lz4_model, "kta_lz4_model", KTA_RV_COMPRESS_WHATIF},            // what the model compressor would leave of each batch
+};
+
 struct KafkaState {
     // The descriptors of a decode call travel on the COPY stream into one of two device buffers that take turns, so that
     // the upload of call k + 1 (5.9 MB for 66 667 batches; from pageable memory a staged, host-blocking copy) runs beside the
@@ -1164,21 +1187,7 @@ struct KafkaState {
     int cur = 0;
     bool acquired = false;
     TimerPool<2> timers{1024};      // kind 0: the CRC kernel, 1: the decode
-    TimerPool<1> rb_timers{1024};   // the record-batch pass (kta_record_batches_info)
-    uint64_t rb_launches = 0, rb_batches = 0;
-    uint32_t rb_workgroups = 0;     // of the last launch
-    TimerPool<1> pl_timers{1024};   // the payload pass (kta_payload_info)
-    uint64_t pl_launches = 0, pl_batches = 0;
-    uint32_t pl_workgroups = 0;     // of the last launch
-    TimerPool<1> hn_timers{1024};   // the header-name pass (kta_header_names_info)
-    uint64_t hn_launches = 0, hn_batches = 0;
-    uint32_t hn_workgroups = 0;     // of the last launch
-    TimerPool<1> vb_timers{1024};   // the value-byte pass (kta_value_bytes_info)
-    uint64_t vb_launches = 0, vb_batches = 0;
-    uint32_t vb_workgroups = 0;     // of the last launch
-    TimerPool<1> cw_timers{1024};   // the compression what-if's pass (kta_compress_whatif_info)
-    uint64_t cw_launches = 0, cw_batches = 0;
-    uint32_t cw_workgroups = 0;     // of the last launch
+    BlobPassState pass[KTA_PASS_KINDS];   // the passes behind the decode kernel (blob_passes)
 };
 
 void free_out(kta_batch &o)
@@ -1204,6 +1213,30 @@ KafkaState *state_of(kta_ctx *ctx)
     void **slot = kta_internal_ext_slot(ctx, free_state);
     if (!*slot) *slot = new KafkaState();
     return static_cast<KafkaState *>(*slot);
+}
+
+// What every kta_*_info of a blob pass reports: out[0..3] the launches, the batches, the last launch's workgroups and the
+// timed launches since the last call; *avg_ms the pass kernel's average over those (-1: none); work, where asked for, the
+// pass's work counters as they stand on the device.
+int blob_pass_info(kta_ctx *ctx, int kind, uint64_t out[4], uint64_t work[4], float *avg_ms)
+{
+    if (!ctx || !out) return KTA_ERR_INVALID;
+    kta_internal_pass p{};
+    (void)kta_internal_blob_pass(ctx, kind, &p);
+    if (!p.on) return kta_internal_section_off(ctx, blob_passes[kind].section);
+    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
+    BlobPassState &ps = state_of(ctx)->pass[kind];
+    float ms = -1.f;
+    uint64_t timed = 0;
+    int rc = ps.timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
+    if (rc != KTA_OK) return rc;
+    if (work) {
+        KTA_HIP(ctx, hipMemcpyAsync(work, p.info, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
+        KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
+    }
+    out[0] = ps.launches, out[1] = ps.batches, out[2] = ps.workgroups, out[3] = timed;
+    if (avg_ms) *avg_ms = ms;
+    return KTA_OK;
 }
 
 inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -1653,53 +1686,19 @@ int kta_kafka_decode_device(kta_ctx *ctx, const uint8_t *blob_device, uint64_t b
 #undef KTA_DECODE_COOP
     KTA_HIP(ctx, hipGetLastError());
     if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-    // The record-batch section (KTA_FLAG_RECORD_BATCHES): the descriptors are final here — status, the inflated sizes — and
-    // they and the blob are still alive.  Off, or during a compaction replay (the source is read a second time): nothing runs.
-    if (kta_internal_rb rb{}; kta_internal_record_batches(ctx, &rb)) {
-        if (timing) { int rc = st->rb_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
-        KTA_HIP_AS(ctx, kta::launch_record_batches(d_descs, n_batches, blob_device, blob_len, kta_internal_partitions(ctx),
-                                                   kta::RbFilter{rb.from_ms, rb.to_ms, rb.bitmap}, rb.vec, rb.cu_count, &st->rb_workgroups, s),
-                   "kta_record_batches");
+    // The blob passes (blob_passes), each one whose section is on.  During a compaction replay (the source is read a second
+    // time) none runs.
+    const kta_internal_pass_env env = kta_internal_blob_pass_env(ctx);
+    for (int kind = 0; kind < KTA_PASS_KINDS; kind++) {
+        kta_internal_pass p{};
+        if (!kta_internal_blob_pass(ctx, kind, &p)) continue;
+        BlobPassState &ps = st->pass[kind];
+        if (timing) { int rc = ps.timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
+        const kta::BlobPassArgs args{d_descs, n_batches, blob_device, blob_len, kta_internal_partitions(ctx), env.from_ms, env.to_ms,
+                                     env.bitmap, p.vec, p.info, p.names, env.cu_count, p.variant};
+        KTA_HIP_AS(ctx, blob_passes[kind].launch(args, &ps.workgroups, s), blob_passes[kind].name);
         if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-        st->rb_launches++, st->rb_batches += n_batches;
-    }
-    // The payload section (KTA_FLAG_PAYLOAD): the same moment, for what lies inside the records — the blob's inflate area holds
-    // the inflated batches.  Off, or during a compaction replay: nothing runs.
-    if (kta_internal_pl pl{}; kta_internal_payload(ctx, &pl)) {
-        if (timing) { int rc = st->pl_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
-        KTA_HIP_AS(ctx, kta::launch_payload(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), pl.from_ms, pl.to_ms, pl.bitmap, pl.vec,
-                                            pl.cu_count, &st->pl_workgroups, s),
-                   "kta_payload");
-        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-        st->pl_launches++, st->pl_batches += n_batches;
-    }
-    // The header-name section (KTA_FLAG_HEADER_NAMES): the same moment and the same bytes, for the names of the record headers.
-    if (kta_internal_hn hn{}; kta_internal_header_names(ctx, &hn)) {
-        if (timing) { int rc = st->hn_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
-        KTA_HIP_AS(ctx, kta::launch_header_names(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), hn.from_ms, hn.to_ms, hn.bitmap, hn.vec,
-                                                 hn.names, hn.info, hn.cu_count, &st->hn_workgroups, s),
-                   "kta_header_names");
-        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-        st->hn_launches++, st->hn_batches += n_batches;
-    }
-    // The value-byte section (KTA_FLAG_VALUE_BYTES): the same moment and the same bytes, for the bytes of every value.
-    if (kta_internal_vb vb{}; kta_internal_value_bytes(ctx, &vb)) {
-        if (timing) { int rc = st->vb_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
-        KTA_HIP_AS(ctx, kta::launch_value_bytes(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), vb.from_ms, vb.to_ms, vb.bitmap, vb.vec,
-                                                vb.info, vb.cu_count, vb.variant, &st->vb_workgroups, s),
-                   "kta_value_bytes");
-        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-        st->vb_launches++, st->vb_batches += n_batches;
-    }
-    // The compression what-if (KTA_FLAG_COMPRESS_WHATIF): the same moment and the same bytes, every inflated records section
-    // resident: what the model compressor would leave of each.
-    if (kta_internal_cw cw{}; kta_internal_compress_whatif(ctx, &cw)) {
-        if (timing) { int rc = st->cw_timers.pair(ctx, s, 0, &a, &b); if (rc != KTA_OK) return rc; KTA_HIP(ctx, hipEventRecord(a, s)); }
-        KTA_HIP_AS(ctx, kta::launch_lz4_model(d_descs, n_batches, blob_device, kta_internal_partitions(ctx), cw.from_ms, cw.to_ms, cw.bitmap, cw.vec,
-                                              cw.cu_count, &st->cw_workgroups, s),
-                   "kta_lz4_model");
-        if (timing) KTA_HIP(ctx, hipEventRecord(b, s));
-        st->cw_launches++, st->cw_batches += n_batches;
+        ps.launches++, ps.batches += n_batches;
     }
     KTA_HIP(ctx, hipEventRecord(st->ev_desc_free[dk].get(), s));         // the descriptors' buffer is free once these kernels are done
     if (n_bad_batches || n_key_bytes) {
@@ -1944,96 +1943,27 @@ int kta_kafka_set_variant(kta_ctx *ctx, int variant)
     return KTA_OK;
 }
 
-int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    kta_internal_rb rb{};
-    (void)kta_internal_record_batches(ctx, &rb);
-    if (!rb.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_RECORD_BATCHES");
-    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KafkaState *st = state_of(ctx);
-    float ms = -1.f;
-    uint64_t timed = 0;
-    int rc = st->rb_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
-    if (rc != KTA_OK) return rc;
-    out[0] = st->rb_launches, out[1] = st->rb_batches, out[2] = st->rb_workgroups, out[3] = timed;
-    if (avg_ms) *avg_ms = ms;
-    return KTA_OK;
-}
+int kta_record_batches_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms) { return blob_pass_info(ctx, KTA_PASS_RECORD_BATCHES, out, nullptr, avg_ms); }
 
-int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    kta_internal_pl pl{};
-    (void)kta_internal_payload(ctx, &pl);
-    if (!pl.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_PAYLOAD");
-    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KafkaState *st = state_of(ctx);
-    float ms = -1.f;
-    uint64_t timed = 0;
-    int rc = st->pl_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
-    if (rc != KTA_OK) return rc;
-    out[0] = st->pl_launches, out[1] = st->pl_batches, out[2] = st->pl_workgroups, out[3] = timed;
-    if (avg_ms) *avg_ms = ms;
-    return KTA_OK;
-}
+int kta_payload_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms) { return blob_pass_info(ctx, KTA_PASS_PAYLOAD, out, nullptr, avg_ms); }
 
 int kta_header_names_info(kta_ctx *ctx, uint64_t out[8], float *avg_ms)
 {
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    kta_internal_hn hn{};
-    (void)kta_internal_header_names(ctx, &hn);
-    if (!hn.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_HEADER_NAMES");
-    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KafkaState *st = state_of(ctx);
-    float ms = -1.f;
-    uint64_t timed = 0, work[4] = {0, 0, 0, 0};
-    int rc = st->hn_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipMemcpyAsync(work, hn.info, sizeof work, hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
-    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
-    out[0] = st->hn_launches, out[1] = st->hn_batches, out[2] = st->hn_workgroups, out[3] = timed;
-    out[4] = work[0], out[5] = work[1], out[6] = work[2], out[7] = 0;
-    if (avg_ms) *avg_ms = ms;
-    return KTA_OK;
+    uint64_t work[4];
+    const int rc = blob_pass_info(ctx, KTA_PASS_HEADER_NAMES, out, work, avg_ms);
+    if (rc == KTA_OK) out[4] = work[0], out[5] = work[1], out[6] = work[2], out[7] = 0;
+    return rc;
 }
 
 int kta_value_bytes_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
 {
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    kta_internal_vb vb{};
-    (void)kta_internal_value_bytes(ctx, &vb);
-    if (!vb.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_VALUE_BYTES");
-    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KafkaState *st = state_of(ctx);
-    float ms = -1.f;
-    uint64_t timed = 0, work[4] = {0, 0, 0, 0};
-    int rc = st->vb_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipMemcpyAsync(work, vb.info, sizeof work, hipMemcpyDeviceToHost, kta_internal_stream(ctx)));
-    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
-    out[0] = st->vb_launches, out[1] = st->vb_batches, out[2] = st->vb_workgroups, out[3] = work[0];
-    if (avg_ms) *avg_ms = timed ? ms : -1.f;
-    return KTA_OK;
+    uint64_t work[4];
+    const int rc = blob_pass_info(ctx, KTA_PASS_VALUE_BYTES, out, work, avg_ms);
+    if (rc == KTA_OK) out[3] = work[0];   // the mid-pass flushes, not the timed launches
+    return rc;
 }
 
-int kta_compress_whatif_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms)
-{
-    if (!ctx || !out) return KTA_ERR_INVALID;
-    kta_internal_cw cw{};
-    (void)kta_internal_compress_whatif(ctx, &cw);
-    if (!cw.on) return fail(ctx, KTA_ERR_INVALID, "context was created without KTA_FLAG_COMPRESS_WHATIF");
-    KTA_HIP(ctx, hipSetDevice(kta_internal_device(ctx)));
-    KafkaState *st = state_of(ctx);
-    float ms = -1.f;
-    uint64_t timed = 0;
-    int rc = st->cw_timers.stats(ctx, kta_internal_stream(ctx), &ms, &timed);
-    if (rc != KTA_OK) return rc;
-    KTA_HIP(ctx, hipStreamSynchronize(kta_internal_stream(ctx)));
-    out[0] = st->cw_launches, out[1] = st->cw_batches, out[2] = st->cw_workgroups, out[3] = timed;
-    if (avg_ms) *avg_ms = timed ? ms : -1.f;
-    return KTA_OK;
-}
+int kta_compress_whatif_info(kta_ctx *ctx, uint64_t out[4], float *avg_ms) { return blob_pass_info(ctx, KTA_PASS_COMPRESS_WHATIF, out, nullptr, avg_ms); }
 
 int kta_kafka_time_stats(kta_ctx *ctx, float avg_ms[2], uint64_t launches[2])
 {

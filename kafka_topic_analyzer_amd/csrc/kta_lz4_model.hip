@@ -36,18 +36,18 @@ namespace {
 
 } // namespace
 
-hipError_t launch_lz4_model(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                            const uint32_t *bitmap, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s)
+hipError_t launch_lz4_model(const BlobPassArgs &a, uint32_t *workgroups, hipStream_t s)
 {
+    const uint64_t n = a.n;
     *workgroups = 0;
     if (n == 0) return hipSuccess;
-    if (!descs || !blob || !vec || P == 0) return hipErrorInvalidValue;
+    if (!a.descs || !a.blob || !a.vec || a.P == 0) return hipErrorInvalidValue;
     // as many workgroups as are resident at once, each over every grid-th batch: the flushes are bounded by the grid and
     // the partitions' changes, not by the batches
-    const uint64_t cap = kCwWavesPerCu * (uint64_t)(cu_count > 0 ? cu_count : 256);
+    const uint64_t cap = kCwWavesPerCu * (uint64_t)(a.cu_count > 0 ? a.cu_count : 256);
     const uint32_t grid = (uint32_t)(n < cap ? n : cap);
-    hipLaunchKernelGGL(kta_lz4_model<kCwEpochs>, dim3(grid), dim3(64), 0, s, blob, descs, n, P, RbFilter{from_ms, to_ms, bitmap},
-                       reinterpret_cast<unsigned long long *>(vec), grid);
+    hipLaunchKernelGGL(kta_lz4_model<kCwEpochs>, dim3(grid), dim3(64), 0, s, a.blob, a.descs, n, a.P, RbFilter{a.from_ms, a.to_ms, a.bitmap},
+                       reinterpret_cast<unsigned long long *>(a.vec), grid);
     *workgroups = grid;
     return hipGetLastError();
 }

@@ -39,18 +39,19 @@ namespace {
 
 } // namespace
 
-hipError_t launch_payload(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                          const uint32_t *bitmap, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s)
+hipError_t launch_payload(const BlobPassArgs &a, uint32_t *workgroups, hipStream_t s)
 {
+    const uint64_t n = a.n;
+    const uint32_t P = a.P;
     *workgroups = 0;
     if (n == 0) return hipSuccess;
-    if (!descs || !blob || !vec || P == 0 || ((uintptr_t)blob & 15u)) return hipErrorInvalidValue;
+    if (!a.descs || !a.blob || !a.vec || P == 0 || ((uintptr_t)a.blob & 15u)) return hipErrorInvalidValue;
     // as many workgroups as are resident at once (12 waves per CU: 142 registers, 12.9 KiB of LDS), each over every grid-th four
     // batches: the flushes at a workgroup's end are bounded by the grid, not by the batches
-    const uint64_t want = (n + kPlG - 1) / kPlG, cap = kPlWavesPerCu * (uint64_t)(cu_count > 0 ? cu_count : 256);
+    const uint64_t want = (n + kPlG - 1) / kPlG, cap = kPlWavesPerCu * (uint64_t)(a.cu_count > 0 ? a.cu_count : 256);
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kta_payload, dim3(grid), dim3(64), 0, s, reinterpret_cast<const uint4 *>(blob), descs, n, P,
-                       FilterSpec{from_ms, to_ms, P, bitmap ? 1u : 0u}, bitmap, reinterpret_cast<unsigned long long *>(vec), grid);
+    hipLaunchKernelGGL(kta_payload, dim3(grid), dim3(64), 0, s, reinterpret_cast<const uint4 *>(a.blob), a.descs, n, P,
+                       FilterSpec{a.from_ms, a.to_ms, P, a.bitmap ? 1u : 0u}, a.bitmap, reinterpret_cast<unsigned long long *>(a.vec), grid);
     *workgroups = grid;
     return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // kta_payload_kernel.h — the payload section's kernel (kta_payload, KTA_FLAG_PAYLOAD).  kta_payload.hip includes this file
-// INSIDE its unnamed namespace, behind kta_decode_coop.h (pin, load_block, KTA_READLANE); beside kta_wave_src.h it has no includes of its own: the
+// INSIDE its unnamed namespace, behind kta_decode_coop.h (pin, load_block, KTA_READLANE); beside kta_wave_src.h and kta_record_walk.h — the
+// walk over a batch's records: the window, the chain, the parse, the commit rule — it has no includes of its own: the
 // including file has included kta_filter.h, kta_kafka.h, kta_payload.h and kta_records.h (at file scope) and provides the
 // HIP runtime — or, for the CPU suite, tests/native/wave_emu.h, which runs the 64 lanes of a workgroup as fibers that meet at
 // __syncthreads / __any / __shfl_xor / ballots (tests/native/payload_emu.cpp, tests/test_payload_emu.py): the kernel below is
@@ -13,14 +14,13 @@
 #define KTA_UNI(v) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(v)))
 #endif
 
-#include "kta_wave_src.h"       // BlockSrc, WindowSrc, group_sum, wave_sum (shared with kta_header_names_kernel.h)
+#include "kta_wave_src.h"       // BlockSrc, WindowSrc, group_sum, wave_sum
+#include "kta_record_walk.h"    // the batch, the round's window, chain and parse, the commit rule, the advance
 
 constexpr int kPlG = 4;                         // batches per wave
 constexpr uint32_t kPlW = 3072;                 // window bytes
 constexpr uint32_t kPlR = 16;                   // records per round of a group
 constexpr uint32_t kPlL = 64 / kPlG;            // lanes per batch
-constexpr uint32_t kPlNLoad = kPlW / (kPlL * 16);
-constexpr uint32_t kPlPer = kPlW / 1024;
 constexpr uint32_t kPlWavesPerCu = 12;           // resident workgroups per CU (the launch's grid is that many per CU at most)
 constexpr uint32_t kPlIdSlots = 16;             // the workgroup's cache of schema ids: (id, T, B) per slot, in LDS
 static_assert(kPlR == kPlL && kPlL == kWsL && kPlL == kPlHistBins && kta::rec::line_windows(kPlW), "one parse round; a lane per histogram bin; KiB loads");
@@ -123,14 +123,15 @@ __global__ __launch_bounds__(64) KTA_WAVES_PER_EU(3, 8) void kta_payload(const u
 {
     namespace rec = kta::rec;
     constexpr int G = kPlG;
-    constexpr uint32_t W = kPlW, R = kPlR, L = kPlL, NLOAD = kPlNLoad, PER = kPlPer;
-    __shared__ uint4 s_win[G][W / 16 + 1];        // + 1: the register paths read whole dwords up to 16 bytes ahead
+    constexpr uint32_t W = kPlW, R = kPlR, L = kPlL;
+    __shared__ uint4 s_win[G][W / 16 + 1];        // the walk's arrays (kta_record_walk.h: WalkLds)
     __shared__ uint32_t s_start[G][R + 1];
     __shared__ uint64_t s_next[G];
     __shared__ uint32_t s_found[G], s_first_incomplete[G], s_first_bad[G];
     __shared__ uint32_t s_hist[G][kPlHistBins];
     __shared__ uint32_t s_id[kPlIdSlots];
     __shared__ unsigned long long s_id_t[kPlIdSlots], s_id_b[kPlIdSlots];   // T == 0: the slot is empty
+    const WalkLds<G, W, R> lds{s_win, s_start, s_next, s_found, s_first_incomplete, s_first_bad};
     const uint32_t lane = threadIdx.x, g = lane / L, sub = lane % L;
     const uint8_t *win = reinterpret_cast<const uint8_t *>(s_win[g]);
     s_hist[g][sub] = 0u;
@@ -147,25 +148,10 @@ __global__ __launch_bounds__(64) KTA_WAVES_PER_EU(3, 8) void kta_payload(const u
     unsigned long long *table = vec + payload_table_at(P);
     __syncthreads();
   for (uint64_t quad = blockIdx.x; quad * G < n_batches; quad += grid) {      // (uniform)
-    const uint64_t b = quad * G + g;
-    uint64_t end = 0, pos = 0;
-    int64_t ts_base = 0, ts_mask = 0;
-    uint32_t total = 0, j = 0;
-    int32_t partition = 0;
-    bool counted = false;                                 // the batch: status 0, partition in [0, P) and in the filter's set
-    if (b < n_batches) {
-        const kta_kafka_batch_desc &d = descs[b];
-        end = d.payload_end; pos = d.payload_off;
-        const bool append_time = (d.flags & KTA_KB_LOG_APPEND_TIME) != 0;   // every record carries maxTimestamp
-        ts_base = append_time ? d.max_ts_ms : d.base_ts_ms;
-        ts_mask = append_time ? 0 : -1;
-        total = d.n_records > 0 ? (uint32_t)d.n_records : 0u; partition = d.partition;
-        counted = d.status == 0 && (uint32_t)partition < P &&
-                  (!f.parts || ((bitmap[(uint32_t)partition >> 5] >> ((uint32_t)partition & 31u)) & 1u));
-    }
+    WalkBatch bt = walk_batch(descs, quad * G + g, n_batches, P, f, bitmap);
     // the accumulators hold one partition: another one first sends them to the vector (every lane takes part); so does a
     // lane whose 32-bit counts are half full
-    if (__any((counted && acc.part >= 0 && acc.part != partition) || acc.since >= 0x80000000u)) payload_flush_acc(acc, vec, lane);
+    if (__any((bt.counted && acc.part >= 0 && acc.part != bt.partition) || acc.since >= 0x80000000u)) payload_flush_acc(acc, vec, lane);
     if (__any(no_headers >= 0x80000000u)) {                                    // (s_hist's words are 32 bits wide as well)
         if (no_headers) atomicAdd(&s_hist[g][0], no_headers);
         no_headers = 0;
@@ -174,128 +160,60 @@ __global__ __launch_bounds__(64) KTA_WAVES_PER_EU(3, 8) void kta_payload(const u
         s_hist[g][sub] = 0u;
         __syncthreads();
     }
-    if (counted) acc.part = partition;
-    bool run = counted && j < total;                      // uniform inside a group
-    while (__any(run)) {
-        uint64_t wbase = 0;
-        uint32_t limit = 0, end_rel = 0;
-        bool to_the_end = false;
-        uint64_t load_base = 0;                           // a group that does not run reads the blob's first block into its own window
-        uint32_t load_bytes = 16;
-        if (run && pos >= end) run = false;               // (the count promises more records than the batch holds: nothing more)
-        if (run) {
-            wbase = rec::window_base(pos, W);
-            const uint64_t span = ((end + 15) & ~15ull) - wbase, rest = end - wbase;
-            const uint32_t wbytes = span < W ? (uint32_t)span : W;         // a multiple of 16, at least 16
-            to_the_end = rest <= wbytes;
-            limit = to_the_end ? (uint32_t)rest : wbytes;
-            end_rel = rest < 0xF0000000ull ? (uint32_t)rest : 0xF0000000u;
-            load_base = wbase; load_bytes = wbytes;
-            if (sub == 0) { s_first_bad[g] = R + 1; s_first_incomplete[g] = R; }
-        }
-        {
-            uint4 stage[NLOAD];
-#pragma unroll
-            for (uint32_t u = 0; u < NLOAD; u++) {
-                const uint32_t gg = u / PER, c = u % PER;
-                const uint64_t gb = (uint64_t)KTA_READLANE((uint32_t)load_base, gg * L) |
-                                    ((uint64_t)KTA_READLANE((uint32_t)(load_base >> 32), gg * L) << 32);
-                const uint32_t gbytes = KTA_READLANE(load_bytes, gg * L);
-                const uint32_t o = (c * 64 + lane) * 16;
-                stage[u] = load_block(reinterpret_cast<const uint8_t *>(blocks) + gb + (o < gbytes - 16 ? o : gbytes - 16));
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < NLOAD; u++) pin(stage[u]);
-#pragma unroll
-            for (uint32_t u = 0; u < NLOAD; u++) s_win[u / PER][(u % PER) * 64 + lane] = stage[u];
-        }
-        __syncthreads();
-        if (run && sub == 0) {                                                 // chain the length prefixes
-            const uint32_t *w32 = reinterpret_cast<const uint32_t *>(win);
-            const uint32_t want = total - j < R ? total - j : R;
-            uint32_t k = 0, cur = (uint32_t)(pos - wbase);
-            uint64_t next = 0;
-            if (rec::chain(w32, limit, want, s_start[g], k, cur)) {            // a length of three bytes or more: byte by byte
-                uint32_t off = cur;
-                long long len;
-                if (rec::window_varlong(win, off, limit, len)) {
-                    const uint64_t rec_end = wbase + off + (uint64_t)len;
-                    if (len < 0 || rec_end > end) s_first_bad[g] = k;
-                    else { s_start[g][k++] = cur; next = rec_end; }
-                } else if (to_the_end) {
-                    s_first_bad[g] = k;                                        // ran into the end of the batch
-                }                                                              // (else it straddles the window: next round)
-            }
-            if (!next) next = wbase + cur;
-            const uint64_t next_rel = next - wbase;
-            s_start[g][k] = next_rel < 0xFFFFFFFFull ? (uint32_t)next_rel : 0xFFFFFFFFu;
-            s_found[g] = k;
-            s_next[g] = next;
-        }
-        __syncthreads();
+    if (bt.counted) acc.part = bt.partition;
+    while (__any(bt.run)) {
+        const WalkRound rd = walk_open(blocks, bt, lds, lane);
+        const uint64_t wbase = rd.wbase;
+        const uint32_t limit = rd.limit;
         // this lane's record of the round, held until the round knows how far it commits
-        bool have = false, hdr_bad = false;
+        bool hdr_bad = false;
         uint32_t cls = 0, id = 0, hcount_bin = 0;
         uint64_t vb = 0, hcount = 0, hkeyb = 0, hvalb = 0, hnulls = 0, wire = 0;
-        if (run && sub < s_found[g]) {
-            const uint32_t k = sub;
-            const uint32_t start = s_start[g][k], rec_end = s_start[g][k + 1];
-            if (rec_end > end_rel) {                                           // the record overruns the batch
-                atomicMin(&s_first_bad[g], k);
+        BlockSrc src{blocks, ~0ull, make_uint4(0, 0, 0, 0)};
+        const WalkRecord wr = walk_record(bt, rd, lds, f, src, lane);
+        const bool have = wr.counts;
+        if (have) {
+            const rec::Record &r = wr.r;
+            const uint64_t value = wr.value;
+            const uint32_t rec_end = wr.rec_end;
+            const uint64_t rec_end_abs = wbase + rec_end;
+            vb = r.val_len > 0 ? (uint64_t)r.val_len : 0ull;
+            const uint64_t vrel = value - wbase;
+            const uint32_t need = vb >= 5 ? 5u : (vb ? 1u : 0u);
+            uint32_t head[5] = {0xFFu, 0u, 0u, 0u, 0u};
+            if (need == 0u) {
+            } else if (vrel + need <= limit) {                                 // the head lies inside the window: two reads (what
+                const uint32_t *w32 = reinterpret_cast<const uint32_t *>(win);           // lies behind `limit` decides nothing)
+                const uint32_t w0 = rec::window_bytes4(w32, (uint32_t)vrel), w1 = rec::window_bytes4(w32, (uint32_t)vrel + 4u);
+                head[0] = w0 & 0xFFu, head[1] = (w0 >> 8) & 0xFFu, head[2] = (w0 >> 16) & 0xFFu, head[3] = w0 >> 24, head[4] = w1 & 0xFFu;
             } else {
-                BlockSrc src{blocks, ~0ull, make_uint4(0, 0, 0, 0)};
-                const uint64_t rec_end_abs = wbase + rec_end;
-                rec::Record r;
-                uint32_t verdict = rec::parse_record(win, start, rec_end, limit, r);
-                uint64_t value = wbase + r.after;                              // where the value's bytes begin
-                if (verdict == rec::REC_VALUE_LENGTH_OUTSIDE) {                // behind a key of the window's size
-                    verdict = payload_varlong(src, value, rec_end_abs, r.val_len) ? rec::value_fits(r.val_len, value - wbase, rec_end) : rec::REC_BAD;
-                }
-                if (verdict == rec::REC_INCOMPLETE) atomicMin(&s_first_incomplete[g], k);
-                else if (verdict != rec::REC_OK) atomicMin(&s_first_bad[g], k);
-                else if (filter_time_passes(f, ts_base + (r.ts_delta & ts_mask))) {
-                    have = true;
-                    vb = r.val_len > 0 ? (uint64_t)r.val_len : 0ull;
-                    const uint64_t vrel = value - wbase;
-                    const uint32_t need = vb >= 5 ? 5u : (vb ? 1u : 0u);
-                    uint32_t head[5] = {0xFFu, 0u, 0u, 0u, 0u};
-                    if (need == 0u) {
-                    } else if (vrel + need <= limit) {                         // the head lies inside the window: two reads (what
-                        const uint32_t *w32 = reinterpret_cast<const uint32_t *>(win);   // lies behind `limit` decides nothing)
-                        const uint32_t w0 = rec::window_bytes4(w32, (uint32_t)vrel), w1 = rec::window_bytes4(w32, (uint32_t)vrel + 4u);
-                        head[0] = w0 & 0xFFu, head[1] = (w0 >> 8) & 0xFFu, head[2] = (w0 >> 16) & 0xFFu, head[3] = w0 >> 24, head[4] = w1 & 0xFFu;
-                    } else {
 #pragma unroll
-                        for (uint32_t q = 0; q < 5; q++)
-                            if (q < need) head[q] = src.at(value + q);
-                    }
-                    cls = payload_class(r.val_len, head[0]);
-                    id = payload_schema_id(head[1], head[2], head[3], head[4]);
-                    const uint64_t hpos = value + vb;
-                    wire = rec_end_abs - hpos;
-                    if (wire == 1 && hpos - wbase < limit && win[(uint32_t)(hpos - wbase)] == 0u) {
-                        // no headers: the one byte 0, inside the window
-                    } else if (rec_end <= limit) {                             // the record lies inside the window: walked in LDS
-                        WindowSrc ws{win, wbase};
-                        const PayloadHeaders h = payload_walk_headers(ws, hpos, rec_end_abs);
-                        hdr_bad = h.bad, hcount = h.count, hkeyb = h.key_bytes, hvalb = h.value_bytes, hnulls = h.null_values;
-                    } else {
-                        const PayloadHeaders h = payload_walk_headers(src, hpos, rec_end_abs);
-                        hdr_bad = h.bad, hcount = h.count, hkeyb = h.key_bytes, hvalb = h.value_bytes, hnulls = h.null_values;
-                    }
-                    hcount_bin = payload_hist_bin(hcount);
-                }
+                for (uint32_t q = 0; q < 5; q++)
+                    if (q < need) head[q] = src.at(value + q);
             }
+            cls = payload_class(r.val_len, head[0]);
+            id = payload_schema_id(head[1], head[2], head[3], head[4]);
+            const uint64_t hpos = value + vb;
+            wire = rec_end_abs - hpos;
+            if (wire == 1 && hpos - wbase < limit && win[(uint32_t)(hpos - wbase)] == 0u) {
+                // no headers: the one byte 0, inside the window
+            } else if (rec_end <= limit) {                                     // the record lies inside the window: walked in LDS
+                WindowSrc ws{win, wbase};
+                const PayloadHeaders h = payload_walk_headers(ws, hpos, rec_end_abs);
+                hdr_bad = h.bad, hcount = h.count, hkeyb = h.key_bytes, hvalb = h.value_bytes, hnulls = h.null_values;
+            } else {
+                const PayloadHeaders h = payload_walk_headers(src, hpos, rec_end_abs);
+                hdr_bad = h.bad, hcount = h.count, hkeyb = h.key_bytes, hvalb = h.value_bytes, hnulls = h.null_values;
+            }
+            hcount_bin = payload_hist_bin(hcount);
         }
         __syncthreads();
         bool give = false;                                                     // this lane hands its id over: its record carries another
         uint32_t g_id = 0, g_t = 0;
         uint64_t g_b = 0;
-        if (run) {
-            const uint32_t found = s_found[g], first_inc = s_first_incomplete[g], first_bad = s_first_bad[g];
-            const uint32_t done = first_inc < found ? first_inc : found;
-            const uint32_t commit = first_bad < done ? first_bad : done;
-            if (have && sub < commit) {
+        if (bt.run) {
+            const WalkCommit cm = walk_commit(lds, g);
+            if (have && sub < cm.commit) {
                 acc.since++;
 #pragma unroll
                 for (uint32_t c = 0; c < kPlClasses; c++) acc.cls[c] += cls == c ? 1u : 0u;                       // (registers: no indexing)
@@ -313,13 +231,7 @@ __global__ __launch_bounds__(64) KTA_WAVES_PER_EU(3, 8) void kta_payload(const u
                     else atomicAdd(&s_hist[g][hcount_bin], 1u);
                 }
             }
-            if (first_bad <= done || done == 0) {                              // bad framing, or no progress (a truncated batch): the batch ends here
-                run = false;
-            } else {
-                j += done;
-                pos = done < found ? wbase + s_start[g][done] : s_next[g];     // records >= done are redone
-                run = j < total;
-            }
+            walk_advance(bt, rd, lds, g, cm);
         }
         payload_drain_ids(give, g_id, g_t, g_b, s_id, s_id_t, s_id_b, table, lane);
         __syncthreads();

@@ -121,16 +121,17 @@ __global__ __launch_bounds__(kRbThreads) void kta_record_batches(const kta_kafka
 
 } // namespace
 
-hipError_t launch_record_batches(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint64_t blob_len, uint32_t P,
-                                 const RbFilter &f, uint64_t *vec, int cu_count, uint32_t *workgroups, hipStream_t s)
+hipError_t launch_record_batches(const BlobPassArgs &a, uint32_t *workgroups, hipStream_t s)
 {
+    const uint64_t n = a.n;
     *workgroups = 0;
     if (n == 0) return hipSuccess;
-    if (!descs || !blob || !vec || P == 0) return hipErrorInvalidValue;
+    if (!a.descs || !a.blob || !a.vec || a.P == 0) return hipErrorInvalidValue;
     const uint64_t want = (n + kRbThreads - 1) / kRbThreads;
-    const uint64_t cap = 2ull * (uint64_t)(cu_count > 0 ? cu_count : 256);
+    const uint64_t cap = 2ull * (uint64_t)(a.cu_count > 0 ? a.cu_count : 256);
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-    hipLaunchKernelGGL(kta_record_batches, dim3(grid), dim3(kRbThreads), 0, s, descs, n, blob, blob_len, P, f, reinterpret_cast<unsigned long long *>(vec));
+    hipLaunchKernelGGL(kta_record_batches, dim3(grid), dim3(kRbThreads), 0, s, a.descs, n, a.blob, a.blob_len, a.P,
+                       RbFilter{a.from_ms, a.to_ms, a.bitmap}, reinterpret_cast<unsigned long long *>(a.vec));
     *workgroups = grid;
     return hipGetLastError();
 }

@@ -44,19 +44,22 @@ namespace {
 
 } // namespace
 
-hipError_t launch_value_bytes(const kta_kafka_batch_desc *descs, uint64_t n, const uint8_t *blob, uint32_t P, int64_t from_ms, int64_t to_ms,
-                              const uint32_t *bitmap, uint64_t *vec, uint64_t *info, int cu_count, int variant, uint32_t *workgroups, hipStream_t s)
+hipError_t launch_value_bytes(const BlobPassArgs &a, uint32_t *workgroups, hipStream_t s)
 {
+    const kta_kafka_batch_desc *descs = a.descs;
+    const uint64_t n = a.n;
+    const uint32_t P = a.P, *bitmap = a.bitmap;
+    const int variant = a.variant;
     *workgroups = 0;
     if (n == 0) return hipSuccess;
-    if (!descs || !blob || !vec || !info || P == 0 || ((uintptr_t)blob & 15u)) return hipErrorInvalidValue;
+    if (!descs || !a.blob || !a.vec || !a.info || P == 0 || ((uintptr_t)a.blob & 15u)) return hipErrorInvalidValue;
     // as many workgroups as are resident at once, each over every grid-th four batches: the flushes at a workgroup's end are
     // bounded by the grid, not by the batches
-    const uint64_t want = (n + kVbG - 1) / kVbG, cap = kVbWavesPerCu * (uint64_t)(cu_count > 0 ? cu_count : 256);
+    const uint64_t want = (n + kVbG - 1) / kVbG, cap = kVbWavesPerCu * (uint64_t)(a.cu_count > 0 ? a.cu_count : 256);
     const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-    const FilterSpec spec{from_ms, to_ms, P, bitmap ? 1u : 0u};
-    const uint4 *blocks = reinterpret_cast<const uint4 *>(blob);
-    unsigned long long *v = reinterpret_cast<unsigned long long *>(vec), *work = reinterpret_cast<unsigned long long *>(info);
+    const FilterSpec spec{a.from_ms, a.to_ms, P, bitmap ? 1u : 0u};
+    const uint4 *blocks = reinterpret_cast<const uint4 *>(a.blob);
+    unsigned long long *v = reinterpret_cast<unsigned long long *>(a.vec), *work = reinterpret_cast<unsigned long long *>(a.info);
     if (variant == 1)                           // tools/bench_value_bytes.py's A/B switches: every byte its own LDS add
         hipLaunchKernelGGL((kta_value_bytes<kVbFlushBytes, kVbCombineNone>), dim3(grid), dim3(64), 0, s, blocks, descs, n, P, spec, bitmap, v, work, grid);
     else if (variant == 2)                      // ... equal bytes of a dword added once, whichever they are

@@ -1,7 +1,8 @@
 // kta_wave_src.h — what the kernels that walk record bytes behind the decode kernel share (kta_payload_kernel.h,
-// kta_header_names_kernel.h): the two byte sources of the header walks (kta_payload.h's Src) and the sums over a group of
-// sixteen lanes and over the wave.  Included INSIDE the including file's unnamed namespace, as those two are; no includes of
-// its own.  kWsL: the lanes per batch.
+// kta_header_names_kernel.h, kta_value_bytes_kernel.h) beside the walk itself (kta_record_walk.h: the payload kernel's; the
+// other two keep its statements as their own text): the two byte
+// sources of the header walks (kta_payload.h's Src) and the sums over a group of sixteen lanes and over the wave.  Included
+// INSIDE the including file's unnamed namespace, as those three are; no includes of its own.  kWsL: the lanes per batch.
 #pragma once
 
 constexpr uint32_t kWsL = 16;
